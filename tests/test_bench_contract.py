@@ -73,3 +73,38 @@ def test_committed_traffic_matches_the_pmc_summary():
     assert m
     d = json.load(open(_latest_record()))
     assert abs(float(m.group(1)) * 1e-6 / d["roofline"]["avg_launch_ms"] - 1.0) < 0.10
+
+
+def test_plain_run_is_lean_and_full_is_opt_in(monkeypatch):
+    import bench
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 3 and a.full is False and a.dump_outputs is None
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dumped_outputs_are_float_and_bounded(tmp_path):
+    # the cfg4 shape: 1025 rows x 16384 int8 -- 67 MB as float32, so the matrix is a fixed seeded sample of whole rows
+    import numpy as np
+    import bench
+    nrows, B = 1025, 16384
+    off = 16 + 4 * nrows
+    rng = np.random.default_rng(1)
+    pkt = rng.integers(-128, 128, off + nrows * B, dtype=np.int8)
+    out = {"lag": rng.integers(-2048, 2048, nrows).astype(np.int32), "mag": rng.random(nrows, dtype=np.float32),
+           "frac": rng.random(nrows, dtype=np.float32), "phasor": (rng.random(nrows) + 1j * rng.random(nrows)).astype(np.complex64), "packet": pkt}
+    for d in ("a", "b"):
+        bench._dump_outputs(str(tmp_path / d), out, off, nrows, B)
+    total = 0
+    for f in sorted(os.listdir(tmp_path / "a")):
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+        total += os.path.getsize(tmp_path / "a" / f)
+    assert total <= 64e6
+    rows = np.load(tmp_path / "a" / "matrix_rows.npy").astype(np.int64)
+    m = pkt[off:].reshape(nrows, B)
+    assert np.array_equal(np.load(tmp_path / "a" / "matrix.npy"), m[rows].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "lag.npy"), out["lag"])
+    assert np.array_equal(np.load(tmp_path / "a" / "header.npy"), pkt[:off].view(np.uint32).astype(np.float64))

@@ -3,9 +3,9 @@
 set -o pipefail
 O=gpurun_out/r3a; mkdir -p $O
 timeout -k 10 700 python -m pytest tests -m gpu -x -q > $O/tests.log 2>&1; echo "tests rc=$?"; tail -4 $O/tests.log
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 > $O/driver.json 2> $O/driver.err; echo "driver rc=$?"
-timeout -k 10 120 python bench.py --steps 20 --warmup 5 --nsig 128 --no-extras --no-cpu-baseline > $O/nsig128.json 2> $O/nsig128.err; echo "nsig128 rc=$?"
-CRSDR_BENCH_REHEARSAL=1 timeout -k 10 200 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $O/reh2.json 2> $O/reh2.err; echo "reh2 rc=$?"
+timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 > $O/driver.json 2> $O/driver.err; echo "driver rc=$?"
+timeout -k 10 120 python bench.py --full --steps 20 --warmup 5 --nsig 128 --no-extras --no-cpu-baseline > $O/nsig128.json 2> $O/nsig128.err; echo "nsig128 rc=$?"
+CRSDR_BENCH_REHEARSAL=1 timeout -k 10 200 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $O/reh2.json 2> $O/reh2.err; echo "reh2 rc=$?"
 python - <<'PY'
 import json
 for f in ("driver", "nsig128", "reh2"):

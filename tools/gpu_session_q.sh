@@ -3,7 +3,7 @@
 set -o pipefail
 O=gpurun_out/r3q; mkdir -p $O
 for nsig in 128 256; do for v in auto packed; do
-  CRSDR_K1_VARIANT=$v timeout -k 10 120 python bench.py --steps 20 --warmup 5 --nsig $nsig --no-extras --no-cpu-baseline > $O/n${nsig}_$v.json 2> $O/n${nsig}_$v.err
+  CRSDR_K1_VARIANT=$v timeout -k 10 120 python bench.py --full --steps 20 --warmup 5 --nsig $nsig --no-extras --no-cpu-baseline > $O/n${nsig}_$v.json 2> $O/n${nsig}_$v.err
   python - $O/n${nsig}_$v.json $nsig $v <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])
