@@ -15,6 +15,7 @@
 #include <functional>
 #include <mutex>
 #include <new>
+#include <string>
 #include <vector>
 #include <sched.h>
 
@@ -263,6 +264,15 @@ static char k1_pick(int rows_all, bool allow_q)
     if (variant == 'a') variant = rows_all >= 12 * device_cus() ? 'q' : 'p';
     if (variant == 'q' && !allow_q) variant = 'p';   // a plan whose two-row kernel once ran out of a bounded wait stays on the packed kernel
     return variant;
+}
+// polls a folded launch's row workgroups may spend on their block's reference spectrum (CRSDR_K1_REFSPIN, tests only): "-1" makes
+// every row workgroup report the wait as run out without polling, "-1@k" from the process's (k+1)-th folded launch on
+static int fold_refspin()
+{
+    static const int env = [] { const char *e = getenv("CRSDR_K1_REFSPIN"); return e ? atoi(e) : kRefWaitBudget; }();
+    static const long from = [] { const char *e = getenv("CRSDR_K1_REFSPIN"); const char *at = e ? strchr(e, '@') : nullptr; return at ? atol(at + 1) : 0L; }();
+    static long launches = 0;
+    return launches++ >= from ? env : kRefWaitBudget;
 }
 static hipError_t launch_xcorr_lag14(hipStream_t s, const XcorrArgs &a, int row_count, const float2 *twA, const float2 *twB, int *waitflag, bool *used_q,
                                      unsigned int *work, unsigned int *work_base, bool allow_q, const std::function<hipError_t()> &before_bounded)
@@ -753,6 +763,8 @@ extern "C" int crsdr_pmusic2d(float *pm, const float *vec, int m, int k, float d
 // (ii) batched plan
 // ================================================================================================
 constexpr int kStageSlots = 4;
+// launches whose bounded waits report into d_sync[2] (crsdr_plan::k1_waits)
+constexpr unsigned kWaitTwoRow = 1u, kWaitTwoLine = 2u, kWaitFoldRef = 4u;
 constexpr int kMaxBatch = 64;
 
 struct crsdr_plan {
@@ -772,6 +784,9 @@ struct crsdr_plan {
     int obuf = 0;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     bool k1done_valid[2] = {false, false};
+    // the last user of d_refspec[slot] was a folded K1 launch (written and read on the main stream, no ev_k1done record): the next
+    // unfolded batch on that slot records ev_k1done[slot] on the main stream before its K0 on the aux stream may overwrite the slot
+    bool fold_last[2] = {false, false};
     int slot = 0;
     float2 *d_tw = nullptr, *d_twA = nullptr, *d_twB = nullptr, *d_refspec[2] = {nullptr, nullptr}; // [T][B] each
     int8_t *d_rows = nullptr;          // staging for host input [T][nrows][B]
@@ -788,9 +803,10 @@ struct crsdr_plan {
     long long *d_corr = nullptr;       // [T][nrows][2]: integer sums (three-kernel path) or the fused kernel's two hand-over slots
     int chain_slot = 0;                // fused path: slot [chain_slot] of every entry carries this batch's unit phasors,
     int chain_armed[2] = {0, 0};       // the kernel re-arms the other one; leading blocks of each slot known to be all-ones
-    unsigned int *d_sync = nullptr;    // fused K2: [0] ticket counter, [1] status; [2] two-row K1: waits that ran out
+    unsigned int *d_sync = nullptr;    // fused K2: [0] ticket counter, [1] status; [2] bounded waits that ran out (two-row K1, two-line stage B, folded K1)
     unsigned int q_work_base = 0;      // value of the two-row K1's work counter (d_sync[3]) when the next launch starts
-    bool k1_used = false;              // a two-row K1 launch is (or was) in flight: check [2] at the next sync
+    bool k1_used = false;              // a launch with bounded waits is (or was) in flight: check [2] at the next sync
+    unsigned k1_waits = 0;             // ... which kinds since the last status check (kWait*): what the error message names
     // carried state {lag, mag, frac}_state + phase_state[0..1] lives in ONE allocation (d_state) so that the first two-row
     // launch after a clean status check can snapshot it with one stream-ordered copy; a wait that ran out rolls the
     // plan back to that snapshot (check_fused_status) and keeps later launches on the packed kernel
@@ -1387,6 +1403,7 @@ extern "C" int crsdr_plan_submit_batch(crsdr_plan *p, const void *rows, int mem_
                 HIP_TRY(launch_long_rows_q(S, n1, cnt, Yc, p->d_twA, p->d_twB, p->d_refspec[slot], reinterpret_cast<int *>(p->d_sync + 2), p->d_sync + 3, &p->q_work_base,
                                            nullptr, Zc != Yc ? Zc : nullptr));
                 p->k1_used = true;
+                p->k1_waits |= kWaitTwoLine;
             } else
                 HIP_TRY(launch_long_rows<false>(S, n1, cnt, Yc, p->d_twA, p->d_twB, p->d_refspec[slot]));
             HIP_TRY(CRSDR_DISPATCH_N1(l1, (launch_long_inv_cols<LG>(S, cnt, Zc, tw, p->d_part + (size_t)r0 * lb::ntiles(l1)))));
@@ -1418,6 +1435,13 @@ extern "C" int crsdr_plan_submit_batch(crsdr_plan *p, const void *rows, int mem_
                 HIP_TRY(hipEventRecord(p->ev_fork, S)); // input copies, mask copy / the caller's producer work
                 if (!input_ready) HIP_TRY(hipStreamWaitEvent(A, p->ev_fork, 0));
             }
+            if (p->fold_last[slot]) {
+                // a folded launch wrote and read refspec[slot] on the main stream after the last ev_k1done[slot] record (it records
+                // none: see above): the event goes behind it now, once per folded -> unfolded change of the slot
+                HIP_TRY(hipEventRecord(p->ev_k1done[slot], KS));
+                p->k1done_valid[slot] = true;
+                p->fold_last[slot] = false;
+            }
             if (p->k1done_valid[slot]) HIP_TRY(hipStreamWaitEvent(A, p->ev_k1done[slot], 0)); // refspec[slot] free again
             hipEvent_t *pe0 = prof_pair(p, CRSDR_KERNEL_REF_SPECTRUM);
             if (pe0) HIP_TRY(hipEventRecord(pe0[0], A));
@@ -1436,6 +1460,7 @@ extern "C" int crsdr_plan_submit_batch(crsdr_plan *p, const void *rows, int mem_
         if (fold) {
             xa.fold = 1; xa.refspec_w = p->d_refspec[slot]; xa.refflag = p->d_refflag; xa.refgen = ++p->refgen;
             xa.errflag = reinterpret_cast<int *>(p->d_sync + 2);
+            xa.refspin = fold_refspin();
         } else
             HIP_TRY(hipStreamWaitEvent(KS, p->ev_ref[slot], 0));
         hipEvent_t *pe1 = prof_pair(p, CRSDR_KERNEL_XCORR_LAG);
@@ -1448,13 +1473,15 @@ extern "C" int crsdr_plan_submit_batch(crsdr_plan *p, const void *rows, int mem_
             HIP_TRY(launch_xcorr_lag14(KS, xa, p->row_count, p->d_twA, p->d_twB, reinterpret_cast<int *>(p->d_sync + 2), &q, p->d_sync + 3, &p->q_work_base,
                                        !p->q_disabled, snapshot));
             p->k1_used |= q || fold;
+            p->k1_waits |= (q ? kWaitTwoRow : 0u) | (fold ? kWaitFoldRef : 0u);
         }
         else HIP_TRY(CRSDR_DISPATCH_LOG2(p->log2n, (launch_xcorr_lag<LG>(KS, xa, p->row_count, p->d_tw))));
         if (pe1) HIP_TRY(hipEventRecord(pe1[1], KS));
         if (!fold) {                                     // (a folded launch's spectra are written and read on this stream only)
             HIP_TRY(hipEventRecord(p->ev_k1done[slot], KS));
             p->k1done_valid[slot] = true;
-        }
+        } else
+            p->fold_last[slot] = true;                   // ... until an unfolded batch's K0 on the aux stream takes the slot over
     }
     if (fused) {
         // fused phase path: every row is read once (k_align_fused); timed under CRSDR_KERNEL_ALIGN_QUANT
@@ -1553,6 +1580,7 @@ extern "C" int crsdr_plan_submit_batch(crsdr_plan *p, const void *rows, int mem_
                     HIP_TRY(launch_long_rows_q(S, n1, cnt, Yc, p->d_twA, p->d_twB, reinterpret_cast<float2 *>(p->d_rowspec + (size_t)r0 * 8192),
                                                reinterpret_cast<int *>(p->d_sync + 2), p->d_sync + 3, &p->q_work_base, &ra));
                     p->k1_used = true;
+                    p->k1_waits |= kWaitTwoLine;
                 } else
                     HIP_TRY(launch_long_rows_ramp(S, n1, cnt, Yc, p->d_twA, p->d_twB, ra));
                 HIP_TRY(CRSDR_DISPATCH_N1(l1, (launch_long_out_cols<LG>(S, cnt, Yc, tw, obase + (size_t)r0 * (size_t)p->B))));
@@ -1585,8 +1613,9 @@ extern "C" int crsdr_plan_submit(crsdr_plan *p, const void *rows, int mem_kind, 
 // are exact either way)
 static int check_fused_status(crsdr_plan *p)
 {
-    // the two-row K1 (xcorr14q.hpp) bounds its waits for the LDS image and its group barriers; one that runs out means a
-    // scheduling assumption failed and the rows of that launch are not to be trusted: an error, never silent
+    // the two-row K1 (xcorr14q.hpp) bounds its waits for the LDS image and its group barriers, the two-line stage B of long blocks
+    // likewise, and the rows of a folded launch their wait for the block's reference spectrum (xcorr14p.hpp); one that runs out
+    // means a scheduling assumption failed and the rows of that launch are not to be trusted: an error, never silent
     if (p->k1_used) {
         int w = 0;
         HIP_TRY(hipMemcpy(&w, p->d_sync + 2, sizeof(w), hipMemcpyDeviceToHost));
@@ -1610,11 +1639,19 @@ static int check_fused_status(crsdr_plan *p)
             p->chain_armed[0] = p->chain_armed[1] = p->max_batch;
             p->snap_cnt = 0; p->snap_head = 0; p->k1_used = false; p->q_disabled = true; p->submitted = false;
             p->copy_pending = false; p->copy_head = p->copy_tail;       // outstanding asynchronous fetches delivered untrusted data: dropped
-            return fail(CRSDR_EHIP, "xcorr: %d workgroup(s) of the two-row kernel ran out of a bounded wait; the last %lu submitted batch(es) -- everything "
+            // the status word is shared: name every kind of wait that was in flight since the last clean read
+            const unsigned kinds = p->k1_waits;
+            p->k1_waits = 0;
+            const char *names[3] = {(kinds & kWaitTwoRow) ? "the two-row kernel's" : nullptr, (kinds & kWaitTwoLine) ? "the two-line stage B's" : nullptr,
+                                    (kinds & kWaitFoldRef) ? "a folded launch's wait for its reference spectrum" : nullptr};
+            std::string what;
+            for (const char *nm : names)
+                if (nm) what += (what.empty() ? "" : " or ") + std::string(nm);
+            return fail(CRSDR_EHIP, "xcorr: %d workgroup(s) ran out of a bounded wait (%s); the last %lu submitted batch(es) -- everything "
                                     "since the last batch whose status was read clean -- were rolled back (carried lag and phase state restored): resubmit "
-                                    "them; this plan now uses the packed kernel (CRSDR_K1_VARIANT=packed selects it from the start)", w, lost);
+                                    "them; this plan now keeps to the one-row / one-line kernels, unfolded (CRSDR_K1_VARIANT=packed CRSDR_K1_FOLD=0 from the start)", w, what.empty() ? "unknown" : what.c_str(), lost);
         }
-        p->snap_cnt = 0; p->snap_head = 0; p->k1_used = false;      // clean and the streams are drained: the next two-row launch takes a fresh snapshot
+        p->snap_cnt = 0; p->snap_head = 0; p->k1_used = false; p->k1_waits = 0;  // clean and the streams are drained: the next bounded launch takes a fresh snapshot
     }
     return CRSDR_OK;
 }

@@ -5,6 +5,8 @@
 
 namespace crsdr {
 
+constexpr int kRefWaitBudget = 1 << 20;      // polls of >= 0.3 us: a reference item takes ~10 us, this is a third of a second
+
 // K1 (cross-correlation): grid = (owned signal rows, T blocks)
 struct XcorrArgs {
     const int8_t *rows;     // batch base: block t at rows + t*block_stride, layout [nrows][B]
@@ -24,7 +26,8 @@ struct XcorrArgs {
     float2 *refspec_w = nullptr;
     unsigned int *refflag = nullptr;   // [T] device words, monotonic: refgen of the last launch that published block t's spectrum
     unsigned int refgen = 0;
-    int *errflag = nullptr;            // a bounded wait ran out (the two-row kernel's word: the host rolls the plan back)
+    int *errflag = nullptr;            // a bounded wait ran out (the plan's status word, shared with the two-row kernel: the host rolls the plan back)
+    int refspin = kRefWaitBudget;      // polls of a row's wait for its reference spectrum; < 0: report it as run out at once (tests)
 };
 
 // wave-level wait for a published word (every lane leaves with the same verdict); false = the poll budget ran out.
@@ -53,8 +56,6 @@ __device__ __forceinline__ bool wait_word(const unsigned int *word, unsigned int
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     return true;
 }
-constexpr int kRefWaitBudget = 1 << 20;      // polls of >= 0.3 us: a reference item takes ~10 us, this is a third of a second
-
 // A row that did not request a lag keeps its previous lag/mag/frac (src/ccoherent.cc:266: only
 // is_lagrequested() devices are queued): the workgroup just republishes the state and leaves.
 __device__ __forceinline__ bool xcorr_skip(const XcorrArgs &a, int row, int t, int tid)

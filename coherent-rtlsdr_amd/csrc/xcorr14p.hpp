@@ -222,8 +222,9 @@ __device__ __forceinline__ void xcorr_row14(const XcorrArgs &a, unsigned char *s
     CRSDR_STAMP(3);
     // folded launches: the block's reference spectrum comes from a workgroup of this same launch with a LOWER index (dispatched
     // before this one: it is resident or done), published behind refflag[t]
-    if (a.fold && !*refok) {                     // workgroup-uniform; only the first rows of a launch ever come here
-        if (tid < 64 && !wait_word(a.refflag + t, a.refgen, ref_early, kRefWaitBudget) && tid == 0 && a.errflag) atomicAdd(a.errflag, 1);
+    // (refspin < 0, tests only: every row workgroup reports its wait as run out without polling, whether the word was there or not)
+    if (a.fold && (!*refok || a.refspin < 0)) {  // workgroup-uniform; only the first rows of a launch ever come here
+        if (tid < 64 && (a.refspin < 0 || !wait_word(a.refflag + t, a.refgen, ref_early, a.refspin)) && tid == 0 && a.errflag) atomicAdd(a.errflag, 1);
         __syncthreads();
     }
     // junction: DFT16 . conj(ref spectrum) . IDFT16 on the same 16 contiguous points
