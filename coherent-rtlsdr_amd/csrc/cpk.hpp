@@ -209,4 +209,153 @@ __device__ __forceinline__ void dft16_inv_mul(c2 *v, const c2 *r)
     t = v[11]; v[11] = v[14]; v[14] = t;
 }
 
+// ---- FMA-form network (K0 / K1 at B = 16384) -------------------------------------------------------------------------
+// A non-trivial twiddle costs two packed instructions as a product (rot_cs) and the butterfly after it two more.  Factored as
+//     w = c (1 + i t)            (|t| <= 1)      or      w = i s (1 - i t')      (|t'| < 1)
+// the bracket is ONE v_pk_fma_f32 (x + t (i x), the swap and sign by op_sel / neg), and the real factor c (or i s) is not
+// applied: the value carries it as a compile-time scale r i^k (true value = r i^k stored value), and the butterfly that
+// combines two values folds the ratio of their scales into its fused multiply-adds -- a +- (sb / sa) b is one v_pk_fma_f32,
+// the cost of the add it replaces.  A radix-4 butterfly leaves every output with the scale of its input a, so a 16-point
+// transform (4 x 4) ends with the scale of its input 0 -- 1 in every transform below: no scale leaves a transform.
+// Every constant is a compile-time value in an SGPR pair (VOP3P on gfx950 takes no literal; op_sel_hi = 0 reads the low half
+// in both lanes); a ratio of exactly 1 is a plain v_pk_add_f32 and needs none.  Same data flow, same registers, rounding
+// differs from the product form in the last bits (tools/fma_bfly_check.hip checks each primitive against its scalar formula).
+
+// a + i^K r b, one instruction:  K = 0 (a.x + r b.x, a.y + r b.y)   1 (a.x - r b.y, a.y + r b.x)   2 (a.x - r b.x, a.y - r b.y)
+// 3 (a.x + r b.y, a.y - r b.x), each lane one fmaf (r = 1: one v_pk_add_f32, which rounds the same)
+template <int K>
+__device__ __forceinline__ c2 fma_j(c2 a, c2 b, float r)
+{
+    constexpr int k = K & 3;
+    c2 d;
+    if (r == 1.0f) {
+        if constexpr (k == 0) return a + b;
+        else if constexpr (k == 2) return a - b;
+        else if constexpr (k == 1) return sub_mi(a, b);
+        else return add_mi(a, b);
+    }
+    const c2 rr = c2{r, r};
+    if constexpr (k == 0) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(d) : "s"(rr), "v"(b), "v"(a));
+    else if constexpr (k == 2) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]" : "=v"(d) : "s"(rr), "v"(b), "v"(a));
+    else if constexpr (k == 1) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[0,0,1] neg_lo:[1,0,0]" : "=v"(d) : "s"(rr), "v"(b), "v"(a));
+    else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[0,0,1] neg_hi:[1,0,0]" : "=v"(d) : "s"(rr), "v"(b), "v"(a));
+    return d;
+}
+
+namespace fnet {
+
+struct Sc { double r; int k; };                                   // the scale r i^k, r > 0
+constexpr Sc kOne{1.0, 0};
+constexpr Sc sc_mul(Sc a, Sc b) { return Sc{a.r * b.r, (a.k + b.k) & 3}; }
+constexpr Sc sc_div(Sc a, Sc b) { return Sc{a.r / b.r, (a.k - b.k) & 3}; }
+constexpr bool sc_is_one(Sc a) { return a.r == 1.0 && a.k == 0; }
+// cos (pi m / 16) for any integer m
+constexpr double kCosPi16[9] = {1.0, 0.98078528040323044913, 0.92387953251128675613, 0.83146961230254523708, 0.70710678118654752440,
+                                0.55557023301960222474, 0.38268343236508977173, 0.19509032201612826785, 0.0};
+constexpr double cos16(int m)
+{
+    m = ((m % 32) + 32) % 32;
+    return m <= 8 ? kCosPi16[m] : m <= 16 ? -kCosPi16[16 - m] : m <= 24 ? -kCosPi16[m - 16] : kCosPi16[32 - m];
+}
+constexpr double sin16(int m) { return cos16(m - 8); }
+constexpr double dabs(double x) { return x < 0 ? -x : x; }
+// exp(i pi m / 16) = scale * (1 + i^mk * mr):  the factoring with the larger of |cos|, |sin| as the scale (mr = 0: no bracket)
+struct Tw { Sc scale; int mk; double mr; };
+constexpr Tw tw16(int m)
+{
+    const double c = cos16(m), s = sin16(m);
+    if (dabs(c) >= dabs(s)) return Tw{Sc{dabs(c), c < 0 ? 2 : 0}, s / c >= 0 ? 1 : 3, dabs(s / c)};
+    return Tw{Sc{dabs(s), s > 0 ? 1 : 3}, c / s >= 0 ? 3 : 1, dabs(c / s)};
+}
+// W_32^n (forward exp(-2 pi i n / 32), DIR > 0 its conjugate) and W_16^n
+template <int DIR> constexpr Tw w32(int n) { return tw16(DIR < 0 ? -n : n); }
+template <int DIR> constexpr Tw w16(int n) { return tw16(DIR < 0 ? -2 * n : 2 * n); }
+
+// x (1 + i^mk mr): the bracket of the twiddle W_32^N / W_16^N (the scale of w32 / w16), one instruction or none
+template <int MK>
+__device__ __forceinline__ c2 bracket(c2 x, double mr) { return mr == 0.0 ? x : fma_j<MK>(x, x, (float)mr); }
+template <int DIR, int N> __device__ __forceinline__ c2 w32b(c2 x) { return bracket<w32<DIR>(N).mk>(x, w32<DIR>(N).mr); }
+template <int DIR, int N> __device__ __forceinline__ c2 w16b(c2 x) { return bracket<w16<DIR>(N).mk>(x, w16<DIR>(N).mr); }
+
+// the combination a + sign * (sb / sa) b with the fixed factor i^J: a + i^(J + kb - ka) (rb / ra) b
+template <int J, class SA, class SB>
+__device__ __forceinline__ c2 comb(c2 a, c2 b)
+{
+    constexpr Sc q = sc_div(SB::value, SA::value);
+    return fma_j<J + q.k>(a, b, (float)q.r);
+}
+// a compile-time scale as a type (C++17: no floating-point template arguments)
+template <class T, int I> struct At { static constexpr Sc value = T::at(I); };
+
+// radix-4 butterfly on scaled inputs (a, b, c, d) at scale indices (IA, IB, IC, ID) of S; the outputs carry scale IA
+template <int DIR, class S, int IA, int IB, int IC, int ID>
+__device__ __forceinline__ void dft4s(c2 &a, c2 &b, c2 &c, c2 &d)
+{
+    using A = At<S, IA>; using B = At<S, IB>; using C = At<S, IC>; using D = At<S, ID>;
+    const c2 t0 = comb<0, A, C>(a, c), t1 = comb<2, A, C>(a, c);
+    const c2 t2 = comb<0, B, D>(b, d), u = comb<2, B, D>(b, d);       // scale B
+    a = comb<0, A, B>(t0, t2);
+    c = comb<2, A, B>(t0, t2);
+    b = comb<DIR < 0 ? 3 : 1, A, B>(t1, u);                           // t1 + exp(DIR i pi/2) u
+    d = comb<DIR < 0 ? 1 : 3, A, B>(t1, u);
+}
+
+// the scales after the first radix-4 layer and the twiddle brackets of a 16-point transform whose inputs have scales S
+template <int DIR, class S>
+struct Mid16 {
+    // element 4 s + q (before the swap) is output s of group q times W16^(q s)
+    static constexpr Sc at(int i) { return sc_mul(S::at(i & 3), w16<DIR>((i & 3) * (i >> 2)).scale); }
+};
+struct Unit { static constexpr Sc at(int) { return kOne; } };
+
+// second layer of dft16 (mid-twiddle brackets, radix-4 on the scaled values, the output permutation); first-layer scales S
+template <int DIR, class S>
+__device__ __forceinline__ void dft16s_tail(c2 *v)
+{
+    static_assert(sc_is_one(S::at(0)), "a 16-point transform must end unscaled");
+    using M = Mid16<DIR, S>;
+    v[5] = w16b<DIR, 1>(v[5]);
+    v[9] = w16b<DIR, 2>(v[9]);
+    v[13] = w16b<DIR, 3>(v[13]);
+    v[6] = w16b<DIR, 2>(v[6]);
+    v[10] = w16b<DIR, 4>(v[10]);
+    v[14] = w16b<DIR, 6>(v[14]);
+    v[7] = w16b<DIR, 3>(v[7]);
+    v[11] = w16b<DIR, 6>(v[11]);
+    v[15] = w16b<DIR, 9>(v[15]);
+    // v[4 s + q] now holds first-layer output s of group q (scale S::at(q) * W16^(q s)'s scale = M::at(4 s + q))
+    dft4s<DIR, M, 0, 1, 2, 3>(v[0], v[1], v[2], v[3]);
+    dft4s<DIR, M, 4, 5, 6, 7>(v[4], v[5], v[6], v[7]);
+    dft4s<DIR, M, 8, 9, 10, 11>(v[8], v[9], v[10], v[11]);
+    dft4s<DIR, M, 12, 13, 14, 15>(v[12], v[13], v[14], v[15]);
+    c2 t;
+    t = v[1]; v[1] = v[4]; v[4] = t;
+    t = v[2]; v[2] = v[8]; v[8] = t;
+    t = v[3]; v[3] = v[12]; v[12] = t;
+    t = v[6]; v[6] = v[9]; v[9] = t;
+    t = v[7]; v[7] = v[13]; v[13] = t;
+    t = v[11]; v[11] = v[14]; v[14] = t;
+}
+
+// 16-point transform of inputs with scales S (S::at(0) = 1), unscaled outputs in dft16's order
+template <int DIR, class S = Unit>
+__device__ __forceinline__ void dft16s(c2 *v)
+{
+    dft4s<DIR, S, 0, 4, 8, 12>(v[0], v[4], v[8], v[12]);
+    dft4s<DIR, S, 1, 5, 9, 13>(v[1], v[5], v[9], v[13]);
+    dft4s<DIR, S, 2, 6, 10, 14>(v[2], v[6], v[10], v[14]);
+    dft4s<DIR, S, 3, 7, 11, 15>(v[3], v[7], v[11], v[15]);
+    dft16s_tail<DIR, S>(v);
+}
+// dft16_inv_mul with the FMA-form second layer: the products and the first layer as dft4_inv_mul (unscaled outputs)
+__device__ __forceinline__ void dft16s_inv_mul(c2 *v, const c2 *r)
+{
+    dft4_inv_mul(v[0], v[4], v[8], v[12], r[0], r[4], r[8], r[12]);
+    dft4_inv_mul(v[1], v[5], v[9], v[13], r[1], r[5], r[9], r[13]);
+    dft4_inv_mul(v[2], v[6], v[10], v[14], r[2], r[6], r[10], r[14]);
+    dft4_inv_mul(v[3], v[7], v[11], v[15], r[3], r[7], r[11], r[15]);
+    dft16s_tail<+1, Unit>(v);
+}
+
+} // namespace fnet
 } // namespace crsdr

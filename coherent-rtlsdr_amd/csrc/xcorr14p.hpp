@@ -68,6 +68,48 @@ __device__ __forceinline__ void dft32_stage1_pruned(c2 *v)
     }
 }
 
+// ---- the FMA-form 32-point transforms of K0 / K1 (cpk.hpp, fnet): same inputs, same output order as the ones above ------------
+// scales of the upper half after the first radix-2 stage: W_32^i's (v[16 + i] holds (v[i] - v[i + 16]) times its bracket only)
+template <int DIR> struct W32Sc { static constexpr fnet::Sc at(int i) { return fnet::w32<DIR>(i).scale; } };
+// ... after the pruned stage: the same, times -1 for the reference row, whose v[16] is negated outright (a 16-point transform's input 0 has scale 1)
+template <bool IS_REF> struct PrunedSc {
+    static constexpr fnet::Sc at(int i) { return i == 0 ? fnet::kOne : fnet::sc_mul(fnet::w32<-1>(i).scale, fnet::Sc{1.0, IS_REF ? 2 : 0}); }
+};
+template <int DIR, int I>
+__device__ __forceinline__ void dft32s_stage1(c2 *v)
+{
+    if constexpr (I < 16) {
+        const c2 t = csub(v[I], v[I + 16]);
+        v[I] = cadd(v[I], v[I + 16]);
+        v[I + 16] = fnet::w32b<DIR, I>(t);
+        dft32s_stage1<DIR, I + 1>(v);
+    }
+}
+template <int DIR>
+__device__ __forceinline__ void dft32s(c2 *v)
+{
+    dft32s_stage1<DIR, 0>(v);
+    fnet::dft16s<DIR>(v);
+    fnet::dft16s<DIR, W32Sc<DIR>>(v + 16);
+}
+template <int I, bool IS_REF>
+__device__ __forceinline__ void dft32s_stage1_pruned(c2 *v)
+{
+    if constexpr (I < 16) {
+        if constexpr (I == 0) v[16] = IS_REF ? -v[0] : v[0];
+        else v[I + 16] = fnet::w32b<-1, I>(v[I]);
+        dft32s_stage1_pruned<I + 1, IS_REF>(v);
+    }
+}
+// pruned forward 32-point transform of the zero-padded rows (dft32_stage1_pruned + two dft16p, FMA form)
+template <bool IS_REF>
+__device__ __forceinline__ void dft32s_pruned(c2 *v)
+{
+    dft32s_stage1_pruned<0, IS_REF>(v);
+    fnet::dft16s<-1>(v);
+    fnet::dft16s<-1, PrunedSc<IS_REF>>(v + 16);
+}
+
 // twiddles w[k] = w1^k, k in [1,32), from the five table values (product depth <= 4)
 template <int K>
 __device__ __forceinline__ void tw_chain(c2 *w)
@@ -117,9 +159,30 @@ __device__ __forceinline__ void tw_stage1_inv(c2 *v, const c2 *w)
         tw_stage1_inv<I + 1>(v, w);
     }
 }
+// the same head in FMA form: the stage's W_32 twiddle as its bracket, its scale carried into the upper dft16s
+template <int I>
+__device__ __forceinline__ void tw_stage1s_inv(c2 *v, const c2 *w)
+{
+    if constexpr (I < 16) {
+        const c2 p = (I == 0) ? v[0] : cmulc(v[I], w[I]);
+        const c2 s = cmulc_add(p, v[I + 16], w[I + 16]);
+        const c2 t = twice_minus(p, s);
+        v[I] = s;
+        v[I + 16] = fnet::w32b<+1, I>(t);
+        tw_stage1s_inv<I + 1>(v, w);
+    }
+}
 // v[k] = input k (natural order) -> inverse 32-point DFT of (v[k] conj(w[k])), outputs as dft32 leaves them (xpos)
+// FMA: the FMA-form network (K0 / K1); otherwise the product form (long-block stage B, fractional-delay pass)
+template <bool FMA = false>
 __device__ __forceinline__ void tw_dft32_inv(c2 *v, const c2 *w)
 {
+    if constexpr (FMA) {
+        tw_stage1s_inv<0>(v, w);
+        fnet::dft16s<+1>(v);
+        fnet::dft16s<+1, W32Sc<+1>>(v + 16);
+        return;
+    }
 #if CRSDR_K1_FUSED_TW
     tw_stage1_inv<0>(v, w);
     dft16p<+1>(v);
@@ -130,7 +193,21 @@ __device__ __forceinline__ void tw_dft32_inv(c2 *v, const c2 *w)
 #endif
 }
 
-template <bool IS_REF>
+// the junction's 16-point transforms in either form
+template <int DIR, bool FMA>
+__device__ __forceinline__ void dft16x(c2 *v)
+{
+    if constexpr (FMA) fnet::dft16s<DIR>(v);
+    else dft16p<DIR>(v);
+}
+template <bool FMA>
+__device__ __forceinline__ void dft16x_inv_mul(c2 *v, const c2 *r)
+{
+    if constexpr (FMA) fnet::dft16s_inv_mul(v, r);
+    else dft16_inv_mul(v, r);
+}
+
+template <bool IS_REF, bool FMA = false>
 __device__ __forceinline__ void pass0_forward(c2 *A, const int8_t *__restrict__ row, const c2 *__restrict__ twA,
                                               uint32_t xor80, int tid, c2 *w)
 {
@@ -144,9 +221,12 @@ __device__ __forceinline__ void pass0_forward(c2 *A, const int8_t *__restrict__ 
         const uint32_t u = (uint32_t)src[i * 512 + tid] ^ x16;
         v[i] = mk((float)sext8(u, 0), (float)sext8(u, 1));
     }
-    dft32_stage1_pruned<0, IS_REF>(v);
-    dft16p<-1>(v);
-    dft16p<-1>(v + 16);
+    if constexpr (FMA) dft32s_pruned<IS_REF>(v);
+    else {
+        dft32_stage1_pruned<0, IS_REF>(v);
+        dft16p<-1>(v);
+        dft16p<-1>(v + 16);
+    }
     tw_load(w, twA, TWA_STRIDE, tid);           // w: the caller's array -- K1 keeps the column twiddles for its last pass
     tw_apply<-1, true, 1>(v, w);
     const int base = p0_base(tid);
@@ -154,6 +234,7 @@ __device__ __forceinline__ void pass0_forward(c2 *A, const int8_t *__restrict__ 
     for (int k = 0; k < 32; ++k) A[base + k * 528] = v[xpos(k)];
 }
 
+template <bool FMA = false>
 __device__ __forceinline__ void pass1_forward(c2 *A, const c2 *w, int tid)
 {
     const int blk = tid >> 4, n2 = tid & 15;
@@ -162,12 +243,14 @@ __device__ __forceinline__ void pass1_forward(c2 *A, const c2 *w, int tid)
 #pragma unroll
     // volatile: keeps these as 32 ds_read_b64 (2 LDS cycles each); merged into ds_read2_b64 they cost 8 cycles per pair
     for (int i = 0; i < 32; ++i) v[i] = *(const volatile lds_c2 *)(Ab + p1_off(i) + (n2 ^ p1_swz(i)));
-    dft32<-1>(v);
+    if constexpr (FMA) dft32s<-1>(v);
+    else dft32<-1>(v);
     tw_apply<-1, true, 1>(v, w);
 #pragma unroll
     for (int k = 0; k < 32; ++k) Ab[p1_off(k) + (n2 ^ p1_swz(k))] = v[xpos(k)];
 }
 
+template <bool FMA = false>
 __device__ __forceinline__ void pass1_inverse(c2 *A, const c2 *w, int tid)
 {
     const int blk = tid >> 4, n2 = tid & 15;
@@ -175,7 +258,7 @@ __device__ __forceinline__ void pass1_inverse(c2 *A, const c2 *w, int tid)
     c2 v[32];
 #pragma unroll
     for (int k = 0; k < 32; ++k) v[k] = *(const volatile lds_c2 *)(Ab + p1_off(k) + (n2 ^ p1_swz(k)));   // ds_read_b64, not read2 (see pass1_forward)
-    tw_dft32_inv(v, w);
+    tw_dft32_inv<FMA>(v, w);
 #pragma unroll
     for (int i = 0; i < 32; ++i) Ab[p1_off(i) + (n2 ^ p1_swz(i))] = v[xpos(i)];
 }
@@ -195,7 +278,7 @@ __device__ __forceinline__ void xcorr_row14(const XcorrArgs &a, unsigned char *s
     // channel at launch start, K1 + 0.13 ms per launch whatever its size); its verdict travels through LDS at the row's first barrier
     const unsigned int ref_early = (a.fold && tid < 64) ? word_peek(a.refflag + t) : 0u;
     c2 wA[32];                                   // column twiddles: P0 applies them, P0' their conjugates -- one chain, 62 registers
-    pass0_forward<false>(A, src, twA, a.xor80, tid, wA);
+    pass0_forward<false, true>(A, src, twA, a.xor80, tid, wA);
     CRSDR_STAMP(1);
     // P1 / P1' twiddles: one chain per row, computed while the P0 stores drain, alive across J
     c2 wB[32];
@@ -217,7 +300,7 @@ __device__ __forceinline__ void xcorr_row14(const XcorrArgs &a, unsigned char *s
     // +4 % at 8; MI355X_MICROARCH.md "Two waves per SIMD", item 9)
     if (a.stagger > 0 && (tid >> 8))
         for (int i = 0; i < a.stagger; ++i) __builtin_amdgcn_s_sleep(8);
-    pass1_forward(A, wB, tid);
+    pass1_forward<true>(A, wB, tid);
     wave_lds_sync();
     CRSDR_STAMP(3);
     // folded launches: the block's reference spectrum comes from a workgroup of this same launch with a LOWER index (dispatched
@@ -242,29 +325,20 @@ __device__ __forceinline__ void xcorr_row14(const XcorrArgs &a, unsigned char *s
             u[2 * j] = mk(q.x, q.y);
             u[2 * j + 1] = mk(q.z, q.w);
         }
-        dft16p<-1>(u);
-#if CRSDR_K1_FUSED_TW
+        fnet::dft16s<-1>(u);
         {
             c2 rr[16];
 #pragma unroll
             for (int j = 0; j < 8; ++j) { rr[2 * j] = mk(r[j].x, r[j].y); rr[2 * j + 1] = mk(r[j].z, r[j].w); }
-            dft16_inv_mul(u, rr);
+            fnet::dft16s_inv_mul(u, rr);
         }
-#else
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            u[2 * j] = cmul(u[2 * j], mk(r[j].x, r[j].y));
-            u[2 * j + 1] = cmul(u[2 * j + 1], mk(r[j].z, r[j].w));
-        }
-        dft16p<+1>(u);
-#endif
 #pragma unroll
         for (int j = 0; j < 8; ++j)
             A4[base + (j ^ key)] = make_float4(u[2 * j].x, u[2 * j].y, u[2 * j + 1].x, u[2 * j + 1].y);
     }
     wave_lds_sync();
     CRSDR_STAMP(4);
-    pass1_inverse(A, wB, tid);
+    pass1_inverse<true>(A, wB, tid);
     CRSDR_STAMP(5);
     __syncthreads();
     CRSDR_STAMP(6);
@@ -275,7 +349,7 @@ __device__ __forceinline__ void xcorr_row14(const XcorrArgs &a, unsigned char *s
         const int base = p0_base(tid);
 #pragma unroll
         for (int k = 0; k < 32; ++k) v[k] = A[base + k * 528];
-        tw_dft32_inv(v, wA);
+        tw_dft32_inv<true>(v, wA);
 #pragma unroll
         for (int i = 0; i < 32; ++i) {
             const c2 x = v[xpos(i)];
@@ -384,11 +458,11 @@ __device__ __forceinline__ void ref_spectrum_row14(unsigned char *smem, const in
     const float4 *A4 = reinterpret_cast<const float4 *>(smem);
     const int tid = threadIdx.x;
     c2 wA0[32];
-    pass0_forward<true>(A, ref_row, twA, xor80, tid, wA0);
+    pass0_forward<true, true>(A, ref_row, twA, xor80, tid, wA0);
     c2 wB[32];
     tw_load(wB, twB, TWB_STRIDE, tid & 15);
     __syncthreads();
-    pass1_forward(A, wB, tid);
+    pass1_forward<true>(A, wB, tid);
     wave_lds_sync();
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -401,7 +475,7 @@ __device__ __forceinline__ void ref_spectrum_row14(unsigned char *smem, const in
             u[2 * j] = mk(q.x, q.y);
             u[2 * j + 1] = mk(q.z, q.w);
         }
-        dft16p<-1>(u);
+        fnet::dft16s<-1>(u);
 #pragma unroll
         for (int j = 0; j < 8; ++j) { // conj(sfft[0]) for the conjugate multiply of src/ccoherent.cc:177-179
             const float4 c = make_float4(u[2 * j].x, -u[2 * j].y, u[2 * j + 1].x, -u[2 * j + 1].y);

@@ -113,9 +113,7 @@ __device__ __forceinline__ void q_p0_compute(c2 *v, const int8_t *__restrict__ r
         const uint32_t u = (uint32_t)src[i * 512 + vt] ^ x16;
         v[i] = mk((float)sext8(u, 0), (float)sext8(u, 1));
     }
-    dft32_stage1_pruned<0, false>(v);
-    dft16p<-1>(v);
-    dft16p<-1>(v + 16);
+    dft32s_pruned<false>(v);
     c2 w[32];
     tw_load(w, twA, TWA_STRIDE, vt);
     tw_apply<-1, true, 1>(v, w);
@@ -139,7 +137,7 @@ __device__ __forceinline__ void q_p0i_compute(float *m, c2 *v, const c2 *__restr
 {
     c2 w[32];
     tw_load(w, twA, TWA_STRIDE, vt);
-    tw_dft32_inv(v, w);
+    tw_dft32_inv<true>(v, w);
 #pragma unroll
     for (int i = 0; i < 32; ++i) {
         const c2 x = v[xpos(i)];
@@ -153,6 +151,8 @@ __device__ __forceinline__ void q_refspec_load(float4 *r, const float4 *__restri
 #pragma unroll
     for (int j = 0; j < 8; ++j) r[j] = refspec4[j * 1024 + g];
 }
+// FMA: the FMA-form transforms of K1 (k_xcorr_lag14q); otherwise the product form (k_rows14_cf32q)
+template <bool FMA>
 __device__ __forceinline__ void q_junction_half(float4 *A4, const float4 *r, int vt, int h)
 {
     const int g = ((vt >> 6) << 7) + 64 * h + (vt & 63), key = g & 7;
@@ -165,15 +165,16 @@ __device__ __forceinline__ void q_junction_half(float4 *A4, const float4 *r, int
         u[2 * j] = mk(q.x, q.y);
         u[2 * j + 1] = mk(q.z, q.w);
     }
-    dft16p<-1>(u);
+    dft16x<-1, FMA>(u);
 #if CRSDR_K1_FUSED_TW
     {
         c2 rr[16];
 #pragma unroll
         for (int j = 0; j < 8; ++j) { rr[2 * j] = mk(r[j].x, r[j].y); rr[2 * j + 1] = mk(r[j].z, r[j].w); }
-        dft16_inv_mul(u, rr);
+        dft16x_inv_mul<FMA>(u, rr);
     }
 #else
+    static_assert(!FMA, "the FMA-form junction has the fused head only");
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         u[2 * j] = cmul(u[2 * j], mk(r[j].x, r[j].y));
@@ -346,19 +347,19 @@ __global__ __launch_bounds__(2 * QG, 1) void k_xcorr_lag14q(XcorrArgs a, const f
         // second barrier and read by everybody after it (the next write follows the next row's first barrier on either path)
         int drawn = 0;
         if (tid == 0) drawn = 2 * (int)gridDim.x + (int)(atomicAdd(work, 1u) - work_base);
-        pass1_forward(A, wB, vt0);
-        pass1_forward(A, wB, vt1);
+        pass1_forward<true>(A, wB, vt0);
+        pass1_forward<true>(A, wB, vt1);
         wave_lds_sync();
         q_refspec_load(rb, refspec4, vt0, 1);
-        q_junction_half(A4, ra, vt0, 0);
+        q_junction_half<true>(A4, ra, vt0, 0);
         q_refspec_load(ra, refspec4, vt1, 0);
-        q_junction_half(A4, rb, vt0, 1);
+        q_junction_half<true>(A4, rb, vt0, 1);
         q_refspec_load(rb, refspec4, vt1, 1);
-        q_junction_half(A4, ra, vt1, 0);
-        q_junction_half(A4, rb, vt1, 1);
+        q_junction_half<true>(A4, ra, vt1, 0);
+        q_junction_half<true>(A4, rb, vt1, 1);
         wave_lds_sync();
-        pass1_inverse(A, wB, vt0);
-        pass1_inverse(A, wB, vt1);
+        pass1_inverse<true>(A, wB, vt0);
+        pass1_inverse<true>(A, wB, vt1);
         if (tid == 0) sy->next[g] = drawn;
         q_barrier(sy, g, gen, 1);
         float m0[32], m1[32];
@@ -579,12 +580,12 @@ __global__ __launch_bounds__(2 * QG, 1) void k_rows14_cf32q(c2 *__restrict__ Y, 
         pass1_forward(A, wB, vt1);
         wave_lds_sync();
         q_refspec_load(rb, refspec4, vt0, 1);
-        q_junction_half(A4, ra, vt0, 0);
+        q_junction_half<false>(A4, ra, vt0, 0);
         q_refspec_load(ra, refspec4, vt1, 0);
-        q_junction_half(A4, rb, vt0, 1);
+        q_junction_half<false>(A4, rb, vt0, 1);
         q_refspec_load(rb, refspec4, vt1, 1);
-        q_junction_half(A4, ra, vt1, 0);
-        q_junction_half(A4, rb, vt1, 1);
+        q_junction_half<false>(A4, ra, vt1, 0);
+        q_junction_half<false>(A4, rb, vt1, 1);
         wave_lds_sync();
         pass1_inverse(A, wB, vt0);
         pass1_inverse(A, wB, vt1);
