@@ -12,7 +12,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <mutex>
 #include <new>
 #include <string>
@@ -201,49 +200,41 @@ constexpr int kMinLog2 = 4, kMaxLog2 = 14, kMaxLog2Plan = 22; // LDS-resident si
 template <int LOG2N>
 static constexpr size_t fft_lds_bytes() { return sizeof(float2) * ((size_t)1 << LOG2N) + 256; }
 
-// ---- kernel launchers, dispatched on log2(B) ------------------------------------------------------
-template <int LOG2N>
-static hipError_t launch_ref_spectrum(hipStream_t s, int nblocks, const int8_t *rows, size_t block_stride, const float2 *tw,
-                                      float2 *refspec, uint32_t xor80)
+// ---- process-level switches (README, "switches"), read once ---------------------------------------------------------------
+// The spin switches take "n" or "n@k": n polls from the process's (k+1)-th launch of the kernel concerned on (each launch site
+// counts its own launches), the default before it, so that a test can let clean launches come first.
+struct SpinSwitch {
+    int value, dflt;
+    long from;
+    int at(long launch) const { return launch >= from ? value : dflt; }
+};
+static SpinSwitch spin_switch(const char *e, int dflt)
 {
-    auto kern = k_ref_spectrum<LOG2N>;
-    constexpr size_t lds = fft_lds_bytes<LOG2N>();
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(FftGeom<LOG2N>::THREADS), lds, s, rows, block_stride, tw, refspec, xor80);
-    return hipGetLastError();
+    const char *at = e ? strchr(e, '@') : nullptr;
+    return {e ? atoi(e) : dflt, dflt, at ? atol(at + 1) : 0L};
 }
-
-template <int LOG2N>
-static hipError_t launch_xcorr_lag(hipStream_t s, const XcorrArgs &a, int row_count, const float2 *tw)
+struct Switches {
+    // CRSDR_K1_VARIANT: 'a' (auto, default) = the two-row kernel (q, xcorr14q.hpp) for launches with enough rows per CU, the packed
+    // one-row kernel (p, xcorr14p.hpp) otherwise; "packed" / "q" force one of them.  Same arithmetic, identical bits.
+    // (Measured-slower experiments live in tools/: xcorr14h.hpp, half-row LDS images -- dead end (8) of DESIGN.md --, xcorr14w.hpp,
+    // 1024 threads per row -- dead end (11) --, and xcorr14_scalar.hpp, the scalar-fp32 twin of r01.)
+    char k1_variant;
+    SpinSwitch qspin;      // CRSDR_K1_QSPIN: polls per bounded wait of the two-row K1 and the two-line stage B (tests force 0)
+    SpinSwitch refspin;    // CRSDR_K1_REFSPIN (tests only): polls of a folded launch's rows for their block's reference spectrum;
+                           // -1: every row workgroup reports the wait as run out without polling
+    int k2_spin;           // CRSDR_K2_SPIN: look-back polls of the fused phase kernel (one value for every launch)
+    bool long_q;           // CRSDR_LONG_Q: long blocks may run stage B on the two-line kernel
+};
+static const Switches &sw()
 {
-    auto kern = k_xcorr_lag<LOG2N>;
-    constexpr size_t lds = fft_lds_bytes<LOG2N>();
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(row_count, a.nblocks), dim3(FftGeom<LOG2N>::THREADS), lds, s, a, tw);
-    return hipGetLastError();
-}
-
-// CRSDR_K1_VARIANT (README, "switches"): "auto" (default) = the two-row kernel (q, xcorr14q.hpp) for launches with enough rows per
-// CU, the packed one-row kernel (p, xcorr14p.hpp) otherwise; "packed" / "q" force one of them.  Same arithmetic, identical bits.
-// (Measured-slower experiments live in tools/: xcorr14h.hpp, half-row LDS images -- dead end (8) of DESIGN.md --, xcorr14w.hpp,
-// 1024 threads per row -- dead end (11) --, and xcorr14_scalar.hpp, the scalar-fp32 twin of r01.)
-static char k1_variant()
-{
-    static const char v = [] { const char *e = getenv("CRSDR_K1_VARIANT"); const char c = e ? e[0] : 'a'; return (c == 'p' || c == 'q') ? c : 'a'; }();
-    return v;
-}
-
-static hipError_t launch_ref_spectrum14(hipStream_t s, int nblocks, const int8_t *rows, size_t block_stride, const float2 *twA,
-                                        const float2 *twB, float2 *refspec, uint32_t xor80)
-{
-    auto kern = x14p::k_ref_spectrum14p;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, x14::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(x14::THREADS), x14::LDS_BYTES, s, rows, block_stride, reinterpret_cast<const c2 *>(twA),
-                       reinterpret_cast<const c2 *>(twB), (float4 *)refspec, xor80);
-    return hipGetLastError();
+    static const Switches s = [] {
+        const char *v = getenv("CRSDR_K1_VARIANT"), *lq = getenv("CRSDR_LONG_Q");
+        const char c = v ? v[0] : 'a';
+        return Switches{(c == 'p' || c == 'q') ? c : 'a', spin_switch(getenv("CRSDR_K1_QSPIN"), x14p::kQSpinLimit),
+                        spin_switch(getenv("CRSDR_K1_REFSPIN"), kRefWaitBudget), spin_switch(getenv("CRSDR_K2_SPIN"), kFusedSpinLimit).value,
+                        !lq || atoi(lq) != 0};
+    }();
+    return s;
 }
 
 static int device_cus()
@@ -258,64 +249,66 @@ static int device_cus()
 // which B = 16384 cross-correlation kernel a launch of rows_all rows takes: 'q' (two rows per CU) or 'p' (one)
 static char k1_pick(int rows_all, bool allow_q)
 {
-    char variant = k1_variant();
+    char variant = sw().k1_variant;
     // measured (r01, T = 64): q is 3-7 % faster at 1024 / 256 / 128 / 96 / 48 rows per block (256 ... 12 rows per CU and launch),
     // 1.4 % at 64, level with p at 32 and 21 rows (8 and 5 per CU; r03: level at 10 as well)
     if (variant == 'a') variant = rows_all >= 12 * device_cus() ? 'q' : 'p';
     if (variant == 'q' && !allow_q) variant = 'p';   // a plan whose two-row kernel once ran out of a bounded wait stays on the packed kernel
     return variant;
 }
-// polls a folded launch's row workgroups may spend on their block's reference spectrum (CRSDR_K1_REFSPIN, tests only): "-1" makes
-// every row workgroup report the wait as run out without polling, "-1@k" from the process's (k+1)-th folded launch on
-static int fold_refspin()
+
+// ---- kernel launchers, dispatched on log2(B) ------------------------------------------------------
+// every launch: the kernel's dynamic LDS limit (set each time), the launch, the launch's error
+template <typename Kernel, typename... Args>
+static hipError_t launch_lds(Kernel kern, dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args &...args)
 {
-    static const int env = [] { const char *e = getenv("CRSDR_K1_REFSPIN"); return e ? atoi(e) : kRefWaitBudget; }();
-    static const long from = [] { const char *e = getenv("CRSDR_K1_REFSPIN"); const char *at = e ? strchr(e, '@') : nullptr; return at ? atol(at + 1) : 0L; }();
-    static long launches = 0;
-    return launches++ >= from ? env : kRefWaitBudget;
+    const hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, grid, block, lds, s, args...);
+    return hipGetLastError();
 }
-static hipError_t launch_xcorr_lag14(hipStream_t s, const XcorrArgs &a, int row_count, const float2 *twA, const float2 *twB, int *waitflag, bool *used_q,
-                                     unsigned int *work, unsigned int *work_base, bool allow_q, const std::function<hipError_t()> &before_bounded)
+
+template <int LOG2N>
+static hipError_t launch_ref_spectrum(hipStream_t s, int nblocks, const int8_t *rows, size_t block_stride, const float2 *tw,
+                                      float2 *refspec, uint32_t xor80)
 {
-    const int cus = device_cus();
-    const int rows_all = row_count * a.nblocks, items = rows_all + (a.fold ? a.nblocks : 0);
-    const char variant = a.fold ? 'p' : k1_pick(rows_all, allow_q);      // (the caller folds the reference spectra in only where the packed kernel runs)
-    if (used_q) *used_q = variant == 'q';
-    // a launch with bounded waits (the two-row kernel's, a folded launch's wait for its reference spectra) snapshots the carried state first
-    if ((variant == 'q' || a.fold) && before_bounded) { hipError_t eb = before_bounded(); if (eb != hipSuccess) return eb; }
-    if (variant != 'q') {
-        auto kp = x14p::k_xcorr_lag14p;
-        hipError_t ep = hipFuncSetAttribute((const void *)kp, hipFuncAttributeMaxDynamicSharedMemorySize, x14::LDS_BYTES);
-        if (ep != hipSuccess) return ep;
-        hipLaunchKernelGGL(kp, dim3((unsigned)items), dim3(x14::THREADS), x14::LDS_BYTES, s, a, twA, twB, row_count);
-        return hipGetLastError();
-    }
-    {   // two rows per CU in opposite phases (xcorr14q.hpp), one persistent workgroup per CU
-        auto kq = x14p::k_xcorr_lag14q;
-        hipError_t eq = hipFuncSetAttribute((const void *)kq, hipFuncAttributeMaxDynamicSharedMemorySize, x14p::LDSQ_BYTES);
-        if (eq != hipSuccess) return eq;
-        // polls per wait; tests force 0 ("0@3": from the process's fourth two-row launch on, so that clean launches come first)
-        static const int qspin_env = [] { const char *e = getenv("CRSDR_K1_QSPIN"); return e ? atoi(e) : x14p::kQSpinLimit; }();
-        static const long qspin_from = [] { const char *e = getenv("CRSDR_K1_QSPIN"); const char *at = e ? strchr(e, '@') : nullptr; return at ? atol(at + 1) : 0L; }();
-        static long qlaunches = 0;
-        const int qspin = qlaunches++ >= qspin_from ? qspin_env : x14p::kQSpinLimit;
-        hipLaunchKernelGGL(kq, dim3((unsigned)std::max(1, std::min(cus, (items + 1) / 2))), dim3(2 * x14p::QG), x14p::LDSQ_BYTES, s, a, twA, twB, row_count,
-                           waitflag, work, *work_base, qspin);
-        const hipError_t el = hipGetLastError();
-        if (el == hipSuccess) *work_base += (unsigned)items;      // a launch that ran advances the device counter by exactly its item count (xcorr14q.hpp)
-        return el;
-    }
+    return launch_lds(k_ref_spectrum<LOG2N>, dim3(nblocks), dim3(FftGeom<LOG2N>::THREADS), fft_lds_bytes<LOG2N>(), s, rows, block_stride, tw,
+                      refspec, xor80);
+}
+
+template <int LOG2N>
+static hipError_t launch_xcorr_lag(hipStream_t s, const XcorrArgs &a, int row_count, const float2 *tw)
+{
+    return launch_lds(k_xcorr_lag<LOG2N>, dim3(row_count, a.nblocks), dim3(FftGeom<LOG2N>::THREADS), fft_lds_bytes<LOG2N>(), s, a, tw);
+}
+
+static hipError_t launch_ref_spectrum14(hipStream_t s, int nblocks, const int8_t *rows, size_t block_stride, const float2 *twA,
+                                        const float2 *twB, float2 *refspec, uint32_t xor80)
+{
+    return launch_lds(x14p::k_ref_spectrum14p, dim3(nblocks), dim3(x14::THREADS), x14::LDS_BYTES, s, rows, block_stride,
+                      reinterpret_cast<const c2 *>(twA), reinterpret_cast<const c2 *>(twB), (float4 *)refspec, xor80);
+}
+
+// B = 16384 cross-correlation on the kernel the caller picked (k1_pick; 'p' for a folded launch)
+static hipError_t launch_xcorr_lag14(hipStream_t s, char variant, const XcorrArgs &a, int row_count, const float2 *twA, const float2 *twB,
+                                     int *waitflag, unsigned int *work, unsigned int *work_base)
+{
+    const int items = row_count * a.nblocks + (a.fold ? a.nblocks : 0);
+    if (variant != 'q')
+        return launch_lds(x14p::k_xcorr_lag14p, dim3((unsigned)items), dim3(x14::THREADS), x14::LDS_BYTES, s, a, twA, twB, row_count);
+    // two rows per CU in opposite phases (xcorr14q.hpp), one persistent workgroup per CU
+    static long launches = 0;
+    const int qspin = sw().qspin.at(launches++);
+    const hipError_t e = launch_lds(x14p::k_xcorr_lag14q, dim3((unsigned)std::max(1, std::min(device_cus(), (items + 1) / 2))), dim3(2 * x14p::QG),
+                                    x14p::LDSQ_BYTES, s, a, twA, twB, row_count, waitflag, work, *work_base, qspin);
+    if (e == hipSuccess) *work_base += (unsigned)items;      // a launch that ran advances the device counter by exactly its item count (xcorr14q.hpp)
+    return e;
 }
 
 template <int LOG2N, int DIR>
 static hipError_t launch_op_fft(hipStream_t s, int howmany, float2 *out, const float2 *in, const float2 *tw)
 {
-    auto kern = k_op_fft<LOG2N, DIR>;
-    constexpr size_t lds = fft_lds_bytes<LOG2N>();
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(howmany), dim3(FftGeom<LOG2N>::THREADS), lds, s, out, in, tw);
-    return hipGetLastError();
+    return launch_lds(k_op_fft<LOG2N, DIR>, dim3(howmany), dim3(FftGeom<LOG2N>::THREADS), fft_lds_bytes<LOG2N>(), s, out, in, tw);
 }
 
 // ---- long-block path (B = N1 x 16384) ----------------------------------------------------------------
@@ -342,98 +335,60 @@ static int lb_grid(int nwork, bool stage_c = false)
     // workgroup per item: measured r02, cfg5, per launch of 10.5 rows: 55 us against 61 us persistent (its reads alone run at
     // 4.1 TB/s either way: 43 us); stage A (mostly stores) gains: 61 -> 52 us
     const int per_cu = stage_c ? 0 : 2;
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-        return n;
-    }();
 #ifdef CRSDR_LB_EXPERIMENT
     static const int dbg_set = [] { const char *e = getenv("CRSDR_LB_DBG"); int v = e ? atoi(e) : 0; (void)hipMemcpyToSymbol(HIP_SYMBOL(lb::lb_dbg), &v, sizeof(v)); return v; }();
     (void)dbg_set;
 #endif
-    return per_cu > 0 ? std::max(1, std::min(nwork, per_cu * cus)) : nwork;
+    return per_cu > 0 ? std::max(1, std::min(nwork, per_cu * device_cus())) : nwork;
 }
 template <int LOG2N1, bool IS_REF>
 static hipError_t launch_long_fwd_cols(hipStream_t s, int nrows_launch, const int8_t *rows, int row_begin, uint32_t xor80,
                                        const lb::LongTw &tw, float2 *Y)
 {
-    auto kern = lb::k_long_fwd_cols<LOG2N1, IS_REF>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb::LDS_BYTES);
-    if (e != hipSuccess) return e;
     const int nwork = lb::ntiles(LOG2N1) * nrows_launch;
-    hipLaunchKernelGGL(kern, dim3((unsigned)lb_grid(nwork)), dim3(lb::THREADS), lb::LDS_BYTES, s, rows, row_begin, xor80, tw, Y, nwork);
-    return hipGetLastError();
+    return launch_lds(lb::k_long_fwd_cols<LOG2N1, IS_REF>, dim3((unsigned)lb_grid(nwork)), dim3(lb::THREADS), lb::LDS_BYTES, s, rows, row_begin,
+                      xor80, tw, Y, nwork);
 }
 // stage B with two lines per CU in opposite phases (k_rows14_cf32q): a line's HBM phases run beside the other line's transforms
 static hipError_t launch_long_rows_q(hipStream_t s, int n1, int nrows_launch, float2 *Y, const float2 *twA, const float2 *twB, float2 *refspec,
-                                     int *waitflag, unsigned int *work, unsigned int *work_base, const x14p::RampArgs *ramp = nullptr, float2 *Yout = nullptr)
+                                     int *waitflag, const x14p::RampArgs *ramp = nullptr, float2 *Yout = nullptr)
 {
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-        return n;
-    }();
-    auto kq = ramp ? x14p::k_rows14_cf32q<true> : x14p::k_rows14_cf32q<false>;
-    hipError_t e = hipFuncSetAttribute((const void *)kq, hipFuncAttributeMaxDynamicSharedMemorySize, x14p::LDSQ_BYTES);
-    if (e != hipSuccess) return e;
     const int items = n1 * nrows_launch;
-    static const int qspin = [] { const char *ev = getenv("CRSDR_K1_QSPIN"); return ev ? atoi(ev) : x14p::kQSpinLimit; }();
     // (r03: dealing the lines to just as many workgroups as make every round full -- cfg5: 2688 lines = 6 rounds x 448 groups on 224
     // CUs instead of 5 full rounds and a sixth with 128 lines -- measured level: 2 473 / 2 544 against 2 500 / 2 549 blocks/s)
-    const int grid = std::max(1, std::min(cus, (items + 1) / 2));
+    const int grid = std::max(1, std::min(device_cus(), (items + 1) / 2));
     // one queue per XCD (k_rows14_cf32q); static order: the work counter is not used.  (The apply pass's per-row spectra are
     // 2.7 MB for cfg5 and stay in every L2: lines in memory order there.)
     const int nq = (!ramp && n1 % 8 == 0 && grid % 8 == 0) ? 8 : 1;
-    (void)work; (void)work_base;
-    hipLaunchKernelGGL(kq, dim3((unsigned)grid), dim3(2 * x14p::QG), x14p::LDSQ_BYTES, s, reinterpret_cast<c2 *>(Y),
-                       reinterpret_cast<const c2 *>(twA), reinterpret_cast<const c2 *>(twB), (const float4 *)refspec, n1, nrows_launch, nq, waitflag, qspin,
-                       ramp ? *ramp : x14p::RampArgs{}, reinterpret_cast<c2 *>(Yout));
-    return hipGetLastError();
+    static long launches = 0;
+    const int qspin = sw().qspin.at(launches++);
+    return launch_lds(ramp ? x14p::k_rows14_cf32q<true> : x14p::k_rows14_cf32q<false>, dim3((unsigned)grid), dim3(2 * x14p::QG), x14p::LDSQ_BYTES, s,
+                      reinterpret_cast<c2 *>(Y), reinterpret_cast<const c2 *>(twA), reinterpret_cast<const c2 *>(twB), (const float4 *)refspec, n1,
+                      nrows_launch, nq, waitflag, qspin, ramp ? *ramp : x14p::RampArgs{}, reinterpret_cast<c2 *>(Yout));
 }
 // stage B: the 16384-point row transforms run on the 32x32x16 structure of xcorr14.hpp
 template <bool IS_REF>
 static hipError_t launch_long_rows(hipStream_t s, int n1, int nrows_launch, float2 *Y, const float2 *twA, const float2 *twB, float2 *refspec)
 {
-    auto kern = x14p::k_rows14_cf32p<IS_REF, false>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, x14::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(n1, nrows_launch), dim3(x14::THREADS), x14::LDS_BYTES, s, reinterpret_cast<c2 *>(Y), reinterpret_cast<const c2 *>(twA),
-                       reinterpret_cast<const c2 *>(twB), (float4 *)refspec, x14p::RampArgs{});
-    return hipGetLastError();
+    return launch_lds(x14p::k_rows14_cf32p<IS_REF, false>, dim3(n1, nrows_launch), dim3(x14::THREADS), x14::LDS_BYTES, s, reinterpret_cast<c2 *>(Y),
+                      reinterpret_cast<const c2 *>(twA), reinterpret_cast<const c2 *>(twB), (float4 *)refspec, x14p::RampArgs{});
 }
 // apply pass of crsdr_plan_set_frac_apply: row transforms with the row's fractional-delay response, then column transforms to int8
 static hipError_t launch_long_rows_ramp(hipStream_t s, int n1, int nrows_launch, float2 *Y, const float2 *twA, const float2 *twB, const x14p::RampArgs &ra)
 {
-    auto kern = x14p::k_rows14_cf32p<false, true>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, x14::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(n1, nrows_launch), dim3(x14::THREADS), x14::LDS_BYTES, s, reinterpret_cast<c2 *>(Y), reinterpret_cast<const c2 *>(twA),
-                       reinterpret_cast<const c2 *>(twB), (float4 *)nullptr, ra);
-    return hipGetLastError();
+    return launch_lds(x14p::k_rows14_cf32p<false, true>, dim3(n1, nrows_launch), dim3(x14::THREADS), x14::LDS_BYTES, s, reinterpret_cast<c2 *>(Y),
+                      reinterpret_cast<const c2 *>(twA), reinterpret_cast<const c2 *>(twB), (float4 *)nullptr, ra);
 }
 static hipError_t launch_long_rows_ref1(hipStream_t s, float2 *Y, const float2 *twA, const float2 *twB, float2 *refspec)
 {
     return launch_long_rows<true>(s, 1, 1, Y, twA, twB, refspec);
 }
-template <int LOG2N1>
-static hipError_t launch_long_out_cols(hipStream_t s, int nrows_launch, const float2 *Z, const lb::LongTw &tw, int8_t *out)
+// inverse column passes: stage C of the correlation pass (argmax partials into part) or, OUT, the apply pass's int8 rows into out
+template <int LOG2N1, bool OUT = false>
+static hipError_t launch_long_inv_cols(hipStream_t s, int nrows_launch, const float2 *Z, const lb::LongTw &tw, lb::LongPartial *part, int8_t *out)
 {
-    auto kern = lb::k_long_inv_cols<LOG2N1, true>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb::LDS_BYTES);
-    if (e != hipSuccess) return e;
     const int nwork = lb::ntiles(LOG2N1) * nrows_launch;
-    hipLaunchKernelGGL(kern, dim3((unsigned)lb_grid(nwork)), dim3(lb::THREADS), lb::LDS_BYTES, s, Z, tw, (lb::LongPartial *)nullptr, out, nwork);
-    return hipGetLastError();
-}
-template <int LOG2N1>
-static hipError_t launch_long_inv_cols(hipStream_t s, int nrows_launch, const float2 *Z, const lb::LongTw &tw, lb::LongPartial *part)
-{
-    auto kern = lb::k_long_inv_cols<LOG2N1>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    const int nwork = lb::ntiles(LOG2N1) * nrows_launch;
-    hipLaunchKernelGGL(kern, dim3((unsigned)lb_grid(nwork, true)), dim3(lb::THREADS), lb::LDS_BYTES, s, Z, tw, part, (int8_t *)nullptr, nwork);
-    return hipGetLastError();
+    return launch_lds(lb::k_long_inv_cols<LOG2N1, OUT>, dim3((unsigned)lb_grid(nwork, !OUT)), dim3(lb::THREADS), lb::LDS_BYTES, s, Z, tw, part, out, nwork);
 }
 
 template <int LOG2N>
@@ -445,18 +400,10 @@ static hipError_t launch_frac_apply(hipStream_t s, int row_count, int nblocks, c
             x14p::FracRowArgs ra{fa.rows, fa.block_stride, fa.packet, fa.packet_stride, fa.slab, fa.slab_stride, fa.nrows, fa.row_begin, fa.xor80, fa.lag, fa.frac,
                                  fa.frac_override, fa.gain, fa.phasor, k2tab, tw};
             constexpr int lds14 = x14::LDS_BYTES + 2048;          // the image + the row's two response tables
-            hipError_t e = hipFuncSetAttribute((const void *)x14p::k_frac_apply14, hipFuncAttributeMaxDynamicSharedMemorySize, lds14);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(x14p::k_frac_apply14, dim3(row_count, nblocks), dim3(x14::THREADS), lds14, s, ra, twA, twB);
-            return hipGetLastError();
+            return launch_lds(x14p::k_frac_apply14, dim3(row_count, nblocks), dim3(x14::THREADS), lds14, s, ra, twA, twB);
         }
     }
-    auto kern = k_frac_apply<LOG2N>;
-    constexpr size_t lds = sizeof(float2) * ((size_t)1 << LOG2N) + 256;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(row_count, nblocks), dim3(FftGeom<LOG2N>::THREADS), lds, s, fa, tw);
-    return hipGetLastError();
+    return launch_lds(k_frac_apply<LOG2N>, dim3(row_count, nblocks), dim3(FftGeom<LOG2N>::THREADS), fft_lds_bytes<LOG2N>(), s, fa, tw);
 }
 
 #define CRSDR_DISPATCH_LOG2(l2, CALL)                                                   \
@@ -780,7 +727,6 @@ struct crsdr_plan {
     int *h_k1flag = nullptr;                         // page-locked [4]: the two-row K1's error word as copied by each asynchronous fetch
     bool copy_pending = false;                       // the next submit's kernels wait for the newest of them
     hipEvent_t ev_k2done[2] = {nullptr, nullptr};
-    bool k2done_valid[2] = {false, false};
     int obuf = 0;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     bool k1done_valid[2] = {false, false};
@@ -822,7 +768,7 @@ struct crsdr_plan {
     int snap_head = 0, snap_cnt = 0;
     unsigned long submit_idx = 0;          // batches submitted since create / reset / rollback
     unsigned long copy_idx[4] = {0, 0, 0, 0};   // submit index of the batch each outstanding asynchronous fetch belongs to
-    bool fused_k2 = true, fused_used = false;   // CRSDR_K2_FUSED=0: the three-kernel phase path
+    bool fused_k2 = true;                      // CRSDR_K2_FUSED=0: the three-kernel phase path
     // B = 16384: the blocks' reference spectra as the first work items of the cross-correlation launch itself (CRSDR_K1_FOLD=0: from
     // k_ref_spectrum14p on the aux stream, two cross-stream dependencies and an event record per batch more)
     bool fold = true;
@@ -889,7 +835,6 @@ static int plan_init_state(crsdr_plan *p)
     return CRSDR_OK;
 }
 
-static hipError_t launch_long_rows_ref1(hipStream_t s, float2 *Y, const float2 *twA, const float2 *twB, float2 *refspec);
 // Which frequency k2 of the 16384-point row transform sits in which junction register?  Transform a one-hot line
 // x[n] = delta[n - 1] with the reference-row form of the kernel (forward, conj, refspec layout): slot q then holds
 // exp(+2 pi i k2 / 16384) twice over, and k2 is read off the angle.  Done once per long-block plan; the table must be a
@@ -1213,17 +1158,6 @@ extern "C" int crsdr_plan_set_frac_apply(crsdr_plan *p, int enable, float gain, 
     return CRSDR_OK;
 }
 
-// slab mode with tails (crsdr_plan_bind_slab_ex): {lag, mag, frac, phasor} of the owned rows behind the rows of every slot
-static int pack_tails(crsdr_plan *p, hipStream_t S, int nblocks, const int32_t *o_lag, const float *o_mag, const float *o_frac, const uint32_t *d_readcnt,
-                      uint32_t seq)
-{
-    if (!p->d_slab || !p->tail_offset) return CRSDR_OK;
-    hipLaunchKernelGGL(k_pack_tails, dim3((unsigned)((p->row_count + 255) / 256), (unsigned)nblocks), dim3(256), 0, S, p->d_slab, p->slab_stride, p->tail_offset,
-                       p->row_begin, p->row_count, p->nrows, o_lag, o_mag, o_frac, p->d_phasor, d_readcnt, seq);
-    HIP_TRY(hipGetLastError());
-    return CRSDR_OK;
-}
-
 // Snapshot of the carried state before the batch now being submitted (at most one per batch; stream-ordered behind the previous
 // batch's kernels).  The entry only counts once the copy has been accepted by the runtime.
 static hipError_t take_snapshot(crsdr_plan *p, hipStream_t s)
@@ -1246,24 +1180,37 @@ static void retire_snapshots(crsdr_plan *p, unsigned long k)
     if (p->snap_cnt == 1 && p->snaps[p->snap_head].idx <= k && p->submit_idx == k + 1) p->snap_cnt = 0;
 }
 
-extern "C" int crsdr_plan_submit_batch(crsdr_plan *p, const void *rows, int mem_kind, int nblocks, size_t block_stride,
-                                       const uint32_t *readcnt, const uint8_t *lag_mask, uint32_t seq, uint32_t flags)
-{
-    if (!p || !rows) return fail(CRSDR_EINVAL, "plan_submit: NULL plan or rows");
-    if (mem_kind != CRSDR_MEM_HOST && mem_kind != CRSDR_MEM_DEVICE) return fail(CRSDR_EINVAL, "plan_submit: mem_kind = %d", mem_kind);
-    if (nblocks < 1 || nblocks > p->max_batch) return fail(CRSDR_EINVAL, "plan_submit: nblocks = %d (plan max_batch = %d)", nblocks, p->max_batch);
-    const size_t B = (size_t)p->B, n = (size_t)p->nrows, T = (size_t)nblocks;
-    if (block_stride == 0) block_stride = n * B;
-    if (block_stride < n * B) return fail(CRSDR_EINVAL, "plan_submit: block_stride smaller than one block");
-    if (mem_kind == CRSDR_MEM_DEVICE && ((uintptr_t)rows % 4 || block_stride % 4))
-        return fail(CRSDR_EINVAL, "plan_submit: device rows and block_stride must be 4-byte aligned (16-byte for the vector kernels)");
-    HIP_TRY(hipSetDevice(p->device));
-    hipStream_t S = p->stream, A = p->aux;
-    const uint32_t xor80 = (flags & CRSDR_OFFSET_BINARY) ? 0x80808080u : 0u;
+// What one submit carries from stage to stage (crsdr_plan_submit_batch).
+struct Batch {
+    int nblocks;
+    const int8_t *d_in;                // the batch's rows on the device: the caller's, or the plan's staging copy
+    size_t d_stride;
+    bool input_ready;                  // CRSDR_INPUT_READY on device rows: K0 need not wait for the main stream
+    uint32_t xor80;
+    const uint32_t *d_readcnt;
+    const uint8_t *d_mask;
+    bool any_lag;                      // the cross-correlation runs
+    int32_t *o_lag;                    // this batch's {lag, mag, frac}
+    float *o_mag, *o_frac;
+    AlignArgs aa;                      // the phase kernels' arguments
+    bool vec16;                        // 16-byte accesses
+    int chunks;                        // long rows: 16 KiB of the row per workgroup
+    bool fused;                        // the fused phase path
+    bool kept_fwd;                     // long blocks: stage A's output survived the correlation pass (in d_Y; stage B wrote d_Z)
+    bool corr_zeroed;                  // k_long_finalize zeroed the three-kernel path's integer sums
+};
 
-    const int8_t *d_in = (const int8_t *)rows;
-    size_t d_stride = block_stride;
-    bool input_ready = (flags & CRSDR_INPUT_READY) && mem_kind == CRSDR_MEM_DEVICE;
+// Inputs: host rows to the plan's staging area, the small per-batch host arrays through the pinned ring, then the wait for a
+// pipelined fetch and the profiling start.
+static int stage_inputs(crsdr_plan *p, Batch &b, const void *rows, int mem_kind, size_t block_stride, const uint32_t *readcnt,
+                        const uint8_t *lag_mask, uint32_t flags)
+{
+    hipStream_t S = p->stream;
+    const size_t B = (size_t)p->B, n = (size_t)p->nrows, T = (size_t)b.nblocks;
+    b.d_in = (const int8_t *)rows;
+    b.d_stride = block_stride;
+    b.input_ready = (flags & CRSDR_INPUT_READY) && mem_kind == CRSDR_MEM_DEVICE;
+    b.xor80 = (flags & CRSDR_OFFSET_BINARY) ? 0x80808080u : 0u;
     if (mem_kind == CRSDR_MEM_HOST) {
         // reference row + this plan's slab only (cbuffer hand-off, src/crtlsdr.cc:173-203)
         for (size_t t = 0; t < T; ++t) {
@@ -1273,14 +1220,10 @@ extern "C" int crsdr_plan_submit_batch(crsdr_plan *p, const void *rows, int mem_
             HIP_TRY(hipMemcpyAsync(dst + B * (size_t)p->row_begin, src + B * (size_t)p->row_begin, B * (size_t)p->row_count,
                                    hipMemcpyHostToDevice, S));
         }
-        d_in = p->d_rows;
-        d_stride = n * B;
+        b.d_in = p->d_rows;
+        b.d_stride = n * B;
     }
-
-    // small per-batch host arrays through the pinned ring
-    const uint32_t *d_readcnt = nullptr;
-    const uint8_t *d_mask = nullptr;
-    bool any_lag = !(flags & CRSDR_NO_LAG);
+    b.any_lag = !(flags & CRSDR_NO_LAG);
     if (readcnt || lag_mask) {
         const int ss = p->stage_slot;
         p->stage_slot = (ss + 1) % kStageSlots;
@@ -1289,21 +1232,20 @@ extern "C" int crsdr_plan_submit_batch(crsdr_plan *p, const void *rows, int mem_
             uint32_t *h = p->h_readcnt + (size_t)ss * n * (size_t)p->max_batch;
             memcpy(h, readcnt, sizeof(uint32_t) * n * T);
             HIP_TRY(hipMemcpyAsync(p->d_readcnt, h, sizeof(uint32_t) * n * T, hipMemcpyHostToDevice, S));
-            d_readcnt = p->d_readcnt;
+            b.d_readcnt = p->d_readcnt;
         }
         if (lag_mask) {
             uint8_t *h = p->h_mask + (size_t)ss * n;
             memcpy(h, lag_mask, n);
             bool any = false;
             for (int r = p->row_begin; r < p->row_begin + p->row_count; ++r) any |= (h[r] != 0);
-            any_lag = any_lag && any;
+            b.any_lag = b.any_lag && any;
             HIP_TRY(hipMemcpyAsync(p->d_mask, h, n, hipMemcpyHostToDevice, S));
-            d_mask = p->d_mask;
+            b.d_mask = p->d_mask;
         }
         HIP_TRY(hipEventRecord(p->ev_stage[ss], S));
         p->stage_valid[ss] = true;
     }
-
     if (p->copy_pending) {
         // a pipelined fetch of the previous batch is (or was) in flight: this batch's kernels overwrite what it reads.  The
         // input copies above stay ahead of this wait, so they share the link with the device-to-host copies
@@ -1316,230 +1258,261 @@ extern "C" int crsdr_plan_submit_batch(crsdr_plan *p, const void *rows, int mem_
         for (int k = 0; k < kProfKernels; ++k) p->prof_has[(size_t)ps * kProfKernels + k] = 0;
         if (p->prof_mask & (1u << 31)) HIP_TRY(hipEventRecord(p->ev_start, S));
     }
+    return CRSDR_OK;
+}
 
-    const int pin = p->phase_cur, pout = pin ^ 1;
-    const int obuf = (p->obuf ^= 1);                      // this batch's {lag, mag, frac}
-    const size_t ooff = (size_t)obuf * n * (size_t)p->max_batch;
-    int32_t *o_lag = p->d_lag + ooff;
-    float *o_mag = p->d_mag + ooff, *o_frac = p->d_frac + ooff;
-    AlignArgs aa;
-    aa.rows = d_in; aa.block_stride = d_stride; aa.packet = p->d_packet; aa.packet_stride = p->packet_stride;
-    aa.readcnt = d_readcnt; aa.lag_mask = d_mask; aa.lag = o_lag; aa.lag_state = p->d_lag_state; aa.corr = p->d_corr;
-    aa.phase_in = p->d_phase_state[pin]; aa.phase_out = p->d_phase_state[pout]; aa.phasor = p->d_phasor;
-    aa.nrows = p->nrows; aa.B = p->B; aa.row_begin = p->row_begin; aa.nblocks = nblocks;
+// Outputs: this batch's {lag, mag, frac} buffer, the phase kernels' arguments and which phase path runs.
+static void setup_outputs(crsdr_plan *p, Batch &b, uint32_t seq, uint32_t flags)
+{
+    const size_t n = (size_t)p->nrows;
+    const int pin = p->phase_cur;
+    const size_t ooff = (size_t)(p->obuf ^= 1) * n * (size_t)p->max_batch;      // this batch's {lag, mag, frac} buffer
+    b.o_lag = p->d_lag + ooff;
+    b.o_mag = p->d_mag + ooff;
+    b.o_frac = p->d_frac + ooff;
+    AlignArgs &aa = b.aa;
+    aa.rows = b.d_in; aa.block_stride = b.d_stride; aa.packet = p->d_packet; aa.packet_stride = p->packet_stride;
+    aa.readcnt = b.d_readcnt; aa.lag_mask = b.d_mask; aa.lag = b.o_lag; aa.lag_state = p->d_lag_state; aa.corr = p->d_corr;
+    aa.phase_in = p->d_phase_state[pin]; aa.phase_out = p->d_phase_state[pin ^ 1]; aa.phasor = p->d_phasor;
+    aa.nrows = p->nrows; aa.B = p->B; aa.row_begin = p->row_begin; aa.nblocks = b.nblocks;
     aa.digital = (p->mode == CRSDR_MODE_DIGITAL); aa.refnoise = (flags & CRSDR_REFNOISE_ENABLED) ? 1 : 0;
-    aa.xcorr_ran = any_lag ? 1 : 0;
+    aa.xcorr_ran = b.any_lag ? 1 : 0;
     aa.inline_chain = 0;
     // rows in and packet rows out are touched once: non-temporal (measured in the locked cadence, A/B in one call: stores +2.3 %, loads neutral)
     aa.nt = 3;
-    aa.seq = seq; aa.xor80 = xor80;
+    aa.seq = seq; aa.xor80 = b.xor80;
     aa.slab = p->d_slab; aa.slab_stride = p->slab_stride; aa.hdr_first = p->hdr_first; aa.hdr_count = p->hdr_count;
-    aa.lag_out = o_lag; aa.mag_out = o_mag; aa.frac_out = o_frac; aa.mag_state = p->d_mag_state; aa.frac_state = p->d_frac_state;
-
+    aa.lag_out = b.o_lag; aa.mag_out = b.o_mag; aa.frac_out = b.o_frac; aa.mag_state = p->d_mag_state; aa.frac_state = p->d_frac_state;
     // 16-byte accesses need 16-byte aligned rows and matrix rows (always true for the plan's own
     // buffers; a caller-bound packet or device input may only be 4-byte aligned -> word kernels)
-    const bool vec16 = ((uintptr_t)d_in % 16 == 0) && (d_stride % 16 == 0) && (((uintptr_t)p->d_packet + p->matrix_off) % 16 == 0) &&
-                       (p->packet_stride % 16 == 0 || nblocks == 1) &&
-                       (!p->d_slab || ((uintptr_t)p->d_slab % 16 == 0 && p->slab_stride % 16 == 0));
-    const int chunks = p->B > 16384 ? p->B / 16384 : 1; // long rows: 16 KiB of the row per workgroup
-    const bool fused = p->fused_k2 && vec16 && chunks == 1;
-    // (K1 of batch b + 1 on its own stream beside the phase kernel of batch b was built and measured in r01 / r02 -- dead ends 5 and 10
-    // of DESIGN.md: the kernels do overlap, and K1 stretches by exactly what the phase kernel costs alone -- and removed in r03.)
-    bool corr_zeroed = false;
-    bool kept_fwd = false;                        // long blocks: stage A's output survived the correlation pass (in d_Y; stage B wrote d_Z)
-    hipStream_t KS = S;
+    b.vec16 = ((uintptr_t)b.d_in % 16 == 0) && (b.d_stride % 16 == 0) && (((uintptr_t)p->d_packet + p->matrix_off) % 16 == 0) &&
+              (p->packet_stride % 16 == 0 || b.nblocks == 1) &&
+              (!p->d_slab || ((uintptr_t)p->d_slab % 16 == 0 && p->slab_stride % 16 == 0));
+    b.chunks = p->B > 16384 ? p->B / 16384 : 1;
+    b.fused = p->fused_k2 && b.vec16 && b.chunks == 1;
+}
 
-    if (any_lag && p->longblock) {
-        // B = N1 x 16384: column FFTs -> row FFTs (x conj ref, inverse) -> inverse column FFTs + argmax -> finalize
-        lb::LongTw tw{p->d_wc, p->d_wf, p->d_tw1, p->d_tw, (uint32_t)(p->B - 1)};
-        const int n1 = 1 << p->log2n1, l1 = p->log2n1;
-        // The reference row's two stages (one row: 256 tiles, 128 lines -- they cannot fill the device) run on the aux stream
-        // into the other spectrum slot, like K0 of the short blocks: with resident input they sit under the previous block's
-        // stage C and phase kernels instead of in front of this block's stage A (21 us of 521 per cfg5 block).  The work line
-        // d_Yref is only touched on the aux stream; a slot is rewritten after the last stage B that read it (ev_k1done).
-        const int slot = (p->slot ^= 1);
-        const bool forked = !input_ready || d_readcnt || d_mask;
-        if (forked) {
-            HIP_TRY(hipEventRecord(p->ev_fork, S));
-            if (!input_ready) HIP_TRY(hipStreamWaitEvent(A, p->ev_fork, 0));
-        }
-        if (p->k1done_valid[slot]) HIP_TRY(hipStreamWaitEvent(A, p->ev_k1done[slot], 0));
-        hipEvent_t *pe0 = prof_pair(p, CRSDR_KERNEL_REF_SPECTRUM);
-        if (pe0) HIP_TRY(hipEventRecord(pe0[0], A));
-        HIP_TRY(CRSDR_DISPATCH_N1(l1, (launch_long_fwd_cols<LG, true>(A, 1, d_in, 0, xor80, tw, p->d_Yref))));
-        HIP_TRY(launch_long_rows<true>(A, n1, 1, p->d_Yref, p->d_twA, p->d_twB, p->d_refspec[slot]));
-        if (pe0) HIP_TRY(hipEventRecord(pe0[1], A));
-        HIP_TRY(hipEventRecord(p->ev_ref[slot], A));
-        HIP_TRY(hipStreamWaitEvent(S, p->ev_ref[slot], 0));
-        XcorrArgs xa;
-        xa.rows = d_in; xa.block_stride = d_stride; xa.refspec = p->d_refspec[slot]; xa.lag_mask = d_mask;
-        xa.row_begin = p->row_begin; xa.nrows = p->nrows; xa.nblocks = 1; xa.xor80 = xor80; xa.stagger = 0;
-        xa.lag = o_lag; xa.mag = o_mag; xa.frac = o_frac;
-        xa.lag_state = p->d_lag_state; xa.mag_state = p->d_mag_state; xa.frac_state = p->d_frac_state;
-        hipEvent_t *pe1 = prof_pair(p, CRSDR_KERNEL_XCORR_LAG);
-        if (pe1) HIP_TRY(hipEventRecord(pe1[0], S));
-        // with the fractional-delay pass to follow, stage B writes into the second work area: stage A's output stays in d_Y and
-        // the apply pass does not repeat it (73 us of a 770 us cfg5 block) -- for the whole block or not at all (two-line kernel only)
-        {
-            static const int longq0 = [] { const char *e = getenv("CRSDR_LONG_Q"); return e ? atoi(e) : 1; }();
-            const char kv0 = k1_variant();
-            kept_fwd = p->d_Z && p->frac_apply && aa.digital && longq0 && (kv0 == 'a' || kv0 == 'q') && !p->q_disabled;
-            for (int r0 = 0; r0 < p->row_count; r0 += p->long_chunk)
-                kept_fwd = kept_fwd && (long)n1 * std::min(p->long_chunk, p->row_count - r0) >= 1024;
-        }
-        // rows go through the three stages in chunks whose cf32 work area fits the 256 MB memory-side cache
-        for (int r0 = 0; r0 < p->row_count; r0 += p->long_chunk) {
-            const int cnt = std::min(p->long_chunk, p->row_count - r0);
-            float2 *Yc = p->d_Y + (size_t)r0 * (size_t)p->B;
-            HIP_TRY(CRSDR_DISPATCH_N1(l1, (launch_long_fwd_cols<LG, false>(S, cnt, d_in, p->row_begin + r0, xor80, tw, Yc))));
-            // stage B: two lines per CU (k_rows14_cf32q) once a launch has enough lines per CU; the packed one-line kernel otherwise
-            // (and always under CRSDR_K1_VARIANT=packed|scalar, or after a bounded wait of the two-line kernels ran out)
-            static const int longq = [] { const char *e = getenv("CRSDR_LONG_Q"); return e ? atoi(e) : 1; }();
-            const char kv = k1_variant();
-            const bool useq = longq && (kv == 'a' || kv == 'q') && !p->q_disabled && (long)n1 * cnt >= 1024;
-            float2 *Zc = kept_fwd ? p->d_Z + (size_t)r0 * (size_t)p->B : Yc;
-            if (useq) {
-                HIP_TRY(take_snapshot(p, S));              // same rollback protocol as the two-row K1 (check_fused_status)
-                HIP_TRY(launch_long_rows_q(S, n1, cnt, Yc, p->d_twA, p->d_twB, p->d_refspec[slot], reinterpret_cast<int *>(p->d_sync + 2), p->d_sync + 3, &p->q_work_base,
-                                           nullptr, Zc != Yc ? Zc : nullptr));
-                p->k1_used = true;
-                p->k1_waits |= kWaitTwoLine;
-            } else
-                HIP_TRY(launch_long_rows<false>(S, n1, cnt, Yc, p->d_twA, p->d_twB, p->d_refspec[slot]));
-            HIP_TRY(CRSDR_DISPATCH_N1(l1, (launch_long_inv_cols<LG>(S, cnt, Zc, tw, p->d_part + (size_t)r0 * lb::ntiles(l1)))));
-        }
-        HIP_TRY(hipEventRecord(p->ev_k1done[slot], S));       // the last reader of this block's reference spectrum has been enqueued
+// K0 on the aux stream into reference-spectrum slot `slot`, then the main stream's wait for it.  K0 goes behind the main
+// stream's input copies (unless the caller's rows were complete before the submit) and behind the last K1 that read the slot.
+template <typename LaunchK0>
+static int run_k0(crsdr_plan *p, const Batch &b, int slot, LaunchK0 &&launch)
+{
+    hipStream_t S = p->stream, A = p->aux;
+    if (!b.input_ready || b.d_readcnt || b.d_mask) {
+        HIP_TRY(hipEventRecord(p->ev_fork, S)); // input copies, mask copy / the caller's producer work
+        if (!b.input_ready) HIP_TRY(hipStreamWaitEvent(A, p->ev_fork, 0));
+    }
+    if (p->fold_last[slot]) {
+        // a folded launch wrote and read refspec[slot] on the main stream after the last ev_k1done[slot] record (it records
+        // none: see k1_short): the event goes behind it now, once per folded -> unfolded change of the slot
+        HIP_TRY(hipEventRecord(p->ev_k1done[slot], S));
         p->k1done_valid[slot] = true;
-        corr_zeroed = aa.refnoise && !fused && chunks > 1 && nblocks == 1;      // (the three-kernel path's integer sums: see below)
-        hipLaunchKernelGGL(lb::k_long_finalize, dim3(p->row_count), dim3(256), 0, S, kept_fwd ? p->d_Z : p->d_Y, p->d_part, tw, n1, lb::ntiles(l1), xa, corr_zeroed ? p->d_corr : nullptr);
-        HIP_TRY(hipGetLastError());
-        if (pe1) HIP_TRY(hipEventRecord(pe1[1], S));
-    } else if (any_lag) {
-        const int slot = (p->slot ^= 1);
-        // B = 16384: the reference spectra are the first work items of the cross-correlation launch itself (fold) -- one launch, no
-        // second stream, no event between the launches of a batch.  r03, per-rank shape of the 8-GPU run (128 rows x 20 blocks,
-        // 0.16 ms per batch): the kernel on the aux stream could only start when the previous batch's K1 let go of its CUs, and the
-        // cross-stream wait + the event record between K1 and the phase kernel left 11 + 11 us of gaps around 138 us of kernels.
-        // Folded where the launch is small (the packed kernel's launches: a GPU's share of an 8-GPU run, 0.16 ms per batch): K1 itself
-        // grows by the reference items and its first rows' wait for them (0.118 -> 0.129 ms per 2560-row launch), the gaps around it
-        // shrink by more (fenced 110 k -> 117 k blocks/s, back to back 122.9 k -> 124.6 k) and the host issues a batch in 10 us
-        // instead of 26 - 40.  The two-row kernel's large launches keep the aux-stream kernel: there it hides completely, and the
-        // folded form measured 0.910 -> 0.932 ms per 20-block launch of 1024 rows (every group's first row waits for block 0's item).
-        const bool fold = p->fold && p->log2n == 14 && !p->q_disabled && k1_pick(p->row_count * nblocks, !p->q_disabled) == 'p';
-        if (!fold) {
-            // K0 on the aux stream: with resident input it overlaps the previous batch's K1 / K2.  (Putting it on the main stream
-            // when both streams are idle -- a cold batch -- was measured in r02: exposed K0 0.0526 -> 0.0516 ms per cold batch and
-            // no difference beyond the spread in a 20-block timed region; not kept.)
-            const bool forked = !input_ready || d_readcnt || d_mask;
-            if (forked) {
-                HIP_TRY(hipEventRecord(p->ev_fork, S)); // input copies, mask copy / the caller's producer work
-                if (!input_ready) HIP_TRY(hipStreamWaitEvent(A, p->ev_fork, 0));
-            }
-            if (p->fold_last[slot]) {
-                // a folded launch wrote and read refspec[slot] on the main stream after the last ev_k1done[slot] record (it records
-                // none: see above): the event goes behind it now, once per folded -> unfolded change of the slot
-                HIP_TRY(hipEventRecord(p->ev_k1done[slot], KS));
-                p->k1done_valid[slot] = true;
-                p->fold_last[slot] = false;
-            }
-            if (p->k1done_valid[slot]) HIP_TRY(hipStreamWaitEvent(A, p->ev_k1done[slot], 0)); // refspec[slot] free again
-            hipEvent_t *pe0 = prof_pair(p, CRSDR_KERNEL_REF_SPECTRUM);
-            if (pe0) HIP_TRY(hipEventRecord(pe0[0], A));
-            if (p->log2n == 14) HIP_TRY(launch_ref_spectrum14(A, nblocks, d_in, d_stride, p->d_twA, p->d_twB, p->d_refspec[slot], xor80));
-            else HIP_TRY(CRSDR_DISPATCH_LOG2(p->log2n, (launch_ref_spectrum<LG>(A, nblocks, d_in, d_stride, p->d_tw, p->d_refspec[slot], xor80))));
-            if (pe0) HIP_TRY(hipEventRecord(pe0[1], A));
-            HIP_TRY(hipEventRecord(p->ev_ref[slot], A));
-        }
+        p->fold_last[slot] = false;
+    }
+    if (p->k1done_valid[slot]) HIP_TRY(hipStreamWaitEvent(A, p->ev_k1done[slot], 0)); // refspec[slot] free again
+    hipEvent_t *pe0 = prof_pair(p, CRSDR_KERNEL_REF_SPECTRUM);
+    if (pe0) HIP_TRY(hipEventRecord(pe0[0], A));
+    { int rc = launch(A); if (rc) return rc; }
+    if (pe0) HIP_TRY(hipEventRecord(pe0[1], A));
+    HIP_TRY(hipEventRecord(p->ev_ref[slot], A));
+    HIP_TRY(hipStreamWaitEvent(S, p->ev_ref[slot], 0));
+    return CRSDR_OK;
+}
 
-        XcorrArgs xa;
-        xa.rows = d_in; xa.block_stride = d_stride; xa.refspec = p->d_refspec[slot]; xa.lag_mask = d_mask;
-        xa.row_begin = p->row_begin; xa.nrows = p->nrows; xa.nblocks = nblocks; xa.xor80 = xor80;
-        xa.stagger = 0;       // (x 512 cycles of head start for half the waves: measured r01, 0 is best for the packed kernels)
-        xa.lag = o_lag; xa.mag = o_mag; xa.frac = o_frac;
-        xa.lag_state = p->d_lag_state; xa.mag_state = p->d_mag_state; xa.frac_state = p->d_frac_state;
-        if (fold) {
-            xa.fold = 1; xa.refspec_w = p->d_refspec[slot]; xa.refflag = p->d_refflag; xa.refgen = ++p->refgen;
-            xa.errflag = reinterpret_cast<int *>(p->d_sync + 2);
-            xa.refspin = fold_refspin();
-        } else
-            HIP_TRY(hipStreamWaitEvent(KS, p->ev_ref[slot], 0));
-        hipEvent_t *pe1 = prof_pair(p, CRSDR_KERNEL_XCORR_LAG);
-        if (pe1) HIP_TRY(hipEventRecord(pe1[0], KS));
-        if (p->log2n == 14) {
-            bool q = false;
-            // every launch with bounded waits snapshots the carried state first (one 28 B/row copy, ordered after the previous
-            // batch's kernels on this stream) while the ring has room: what a wait that ran out is rolled back to
-            auto snapshot = [p, KS]() -> hipError_t { return take_snapshot(p, KS); };
-            HIP_TRY(launch_xcorr_lag14(KS, xa, p->row_count, p->d_twA, p->d_twB, reinterpret_cast<int *>(p->d_sync + 2), &q, p->d_sync + 3, &p->q_work_base,
-                                       !p->q_disabled, snapshot));
-            p->k1_used |= q || fold;
-            p->k1_waits |= (q ? kWaitTwoRow : 0u) | (fold ? kWaitFoldRef : 0u);
-        }
-        else HIP_TRY(CRSDR_DISPATCH_LOG2(p->log2n, (launch_xcorr_lag<LG>(KS, xa, p->row_count, p->d_tw))));
-        if (pe1) HIP_TRY(hipEventRecord(pe1[1], KS));
-        if (!fold) {                                     // (a folded launch's spectra are written and read on this stream only)
-            HIP_TRY(hipEventRecord(p->ev_k1done[slot], KS));
-            p->k1done_valid[slot] = true;
-        } else
-            p->fold_last[slot] = true;                   // ... until an unfolded batch's K0 on the aux stream takes the slot over
-    }
-    if (fused) {
-        // fused phase path: every row is read once (k_align_fused); timed under CRSDR_KERNEL_ALIGN_QUANT
-        static const int spin_limit = [] { const char *e = getenv("CRSDR_K2_SPIN"); return e ? atoi(e) : kFusedSpinLimit; }();
-        // hand-over words: two slots per (row, block).  A batch publishes into one and its workgroups re-arm the other
-        // (all-ones) for the next batch, so the steady state needs no memset between launches; the host only tracks how
-        // many leading blocks of each slot are armed and falls back to a memset when a batch needs more than that
-        const int cs = p->chain_slot;
-        unsigned long long *chain = reinterpret_cast<unsigned long long *>(p->d_corr);
-        unsigned long long *chainv = chain + 2 * n * (size_t)p->max_batch;      // second half of d_corr: the chain values, same two slots
-        FusedSync fs{p->d_sync, p->d_sync + 1, chain + cs, aa.refnoise ? chain + (cs ^ 1) : nullptr, chainv + cs, aa.refnoise ? chainv + (cs ^ 1) : nullptr,
-                     p->row_count, spin_limit};
-        hipEvent_t *pe = prof_pair(p, CRSDR_KERNEL_ALIGN_QUANT);
-        if (pe) HIP_TRY(hipEventRecord(pe[0], S));
-        if (aa.refnoise) {
-            if (nblocks > 1 && p->chain_armed[cs] < nblocks) {
-                HIP_TRY(hipMemsetAsync(p->d_corr, 0xFF, sizeof(long long) * 4 * n * T, S));
-                p->chain_armed[0] = p->chain_armed[1] = (int)T;
-            }
-            p->chain_armed[cs] = 0;                                             // published into
-            p->chain_armed[cs ^ 1] = std::max(p->chain_armed[cs ^ 1], nblocks); // re-armed by this launch
-            p->chain_slot = cs ^ 1;
-        }
-        {
-            // (two rows per workgroup sharing the reference row's registers: built and measured in r03, 4.05 against 4.85 TB/s -- tools/k2_pair.hpp;
-            //  persistent workgroups with the next item's row loads in flight: 3.1 - 3.6 against 4.76 TB/s -- tools/k2_persist.hpp)
-            const dim3 grid((unsigned)((1 + p->row_count) * nblocks));
-            if (p->B == 16384 && !xor80) hipLaunchKernelGGL((k_align_fused<true, false>), grid, dim3(kAlignThreads), 0, S, aa, fs);
-            else if (p->B == 16384) hipLaunchKernelGGL((k_align_fused<true, true>), grid, dim3(kAlignThreads), 0, S, aa, fs);
-            else hipLaunchKernelGGL((k_align_fused<false, true>), grid, dim3(kAlignThreads), 0, S, aa, fs);
-        }
-        HIP_TRY(hipGetLastError());
-        if (p->frac_apply && !p->longblock && aa.digital) {
-            // fractional-delay correction of LDS-resident blocks: the owned rows once more, through the frequency domain
-            FracArgs fa{d_in, d_stride, p->d_packet, p->packet_stride, p->d_slab, p->slab_stride, p->nrows, p->row_begin, xor80, o_lag, o_frac,
-                        p->frac_override_on ? p->d_frac_override : nullptr, p->frac_gain, p->d_phasor};
-            HIP_TRY(CRSDR_DISPATCH_LOG2(p->log2n, (launch_frac_apply<LG>(S, p->row_count, nblocks, fa, p->d_tw, p->d_twA, p->d_twB, p->frac_generic ? nullptr : p->d_k2tab))));
-        }
-        if (pe) HIP_TRY(hipEventRecord(pe[1], S));
-        { int rc_ = pack_tails(p, S, nblocks, o_lag, o_mag, o_frac, d_readcnt, seq); if (rc_) return rc_; }
-        HIP_TRY(hipEventRecord(p->ev_k2done[obuf], S));
-        p->k2done_valid[obuf] = true;
-        p->fused_used = true;
-        p->phase_cur = pout;
-        p->last_nblocks = nblocks;
-        if (p->prof_slots) { if (p->prof_mask & (1u << 31)) HIP_TRY(hipEventRecord(p->ev_stop, S)); p->prof_count++; }
-        p->submitted = true;
-        p->submit_idx++;
+// K1's arguments: this batch's rows against the reference spectra in refspec[slot], into this batch's {lag, mag, frac}
+static XcorrArgs xcorr_args(const crsdr_plan *p, const Batch &b, int slot)
+{
+    XcorrArgs xa;
+    xa.rows = b.d_in; xa.block_stride = b.d_stride; xa.refspec = p->d_refspec[slot]; xa.lag_mask = b.d_mask;
+    xa.row_begin = p->row_begin; xa.nrows = p->nrows; xa.nblocks = b.nblocks; xa.xor80 = b.xor80;
+    xa.stagger = 0;       // (x 512 cycles of head start for half the waves: measured r01, 0 is best for the packed kernels)
+    xa.lag = b.o_lag; xa.mag = b.o_mag; xa.frac = b.o_frac;
+    xa.lag_state = p->d_lag_state; xa.mag_state = p->d_mag_state; xa.frac_state = p->d_frac_state;
+    return xa;
+}
+
+// Long blocks, stage B of `cnt` rows: two lines per CU (k_rows14_cf32q) once a launch has enough lines per CU; the packed one-line
+// kernel otherwise (and always under CRSDR_LONG_Q=0 or CRSDR_K1_VARIANT=packed, or after a bounded wait of the two-line kernels ran out)
+static bool two_line(const crsdr_plan *p, int cnt)
+{
+    const char kv = sw().k1_variant;
+    return sw().long_q && (kv == 'a' || kv == 'q') && !p->q_disabled && ((long)1 << p->log2n1) * cnt >= 1024;
+}
+
+// K1 of long blocks (B = N1 x 16384): column FFTs -> row FFTs (x conj ref, inverse) -> inverse column FFTs + argmax -> finalize
+static int k1_long(crsdr_plan *p, Batch &b)
+{
+    hipStream_t S = p->stream;
+    const lb::LongTw tw{p->d_wc, p->d_wf, p->d_tw1, p->d_tw, (uint32_t)(p->B - 1)};
+    const int n1 = 1 << p->log2n1, l1 = p->log2n1;
+    // The reference row's two stages (one row: 256 tiles, 128 lines -- they cannot fill the device) run on the aux stream
+    // into the other spectrum slot, like K0 of the short blocks: with resident input they sit under the previous block's
+    // stage C and phase kernels instead of in front of this block's stage A (21 us of 521 per cfg5 block).  The work line
+    // d_Yref is only touched on the aux stream; a slot is rewritten after the last stage B that read it (ev_k1done).
+    const int slot = (p->slot ^= 1);
+    int rc = run_k0(p, b, slot, [&](hipStream_t A) -> int {
+        HIP_TRY(CRSDR_DISPATCH_N1(l1, (launch_long_fwd_cols<LG, true>(A, 1, b.d_in, 0, b.xor80, tw, p->d_Yref))));
+        HIP_TRY(launch_long_rows<true>(A, n1, 1, p->d_Yref, p->d_twA, p->d_twB, p->d_refspec[slot]));
         return CRSDR_OK;
+    });
+    if (rc) return rc;
+    hipEvent_t *pe1 = prof_pair(p, CRSDR_KERNEL_XCORR_LAG);
+    if (pe1) HIP_TRY(hipEventRecord(pe1[0], S));
+    // with the fractional-delay pass to follow, stage B writes into the second work area: stage A's output stays in d_Y and
+    // the apply pass does not repeat it (73 us of a 770 us cfg5 block) -- for the whole block or not at all (two-line kernel only)
+    b.kept_fwd = p->d_Z && p->frac_apply && b.aa.digital;
+    for (int r0 = 0; r0 < p->row_count; r0 += p->long_chunk) b.kept_fwd = b.kept_fwd && two_line(p, std::min(p->long_chunk, p->row_count - r0));
+    // rows go through the three stages in chunks whose cf32 work area fits the 256 MB memory-side cache
+    for (int r0 = 0; r0 < p->row_count; r0 += p->long_chunk) {
+        const int cnt = std::min(p->long_chunk, p->row_count - r0);
+        float2 *Yc = p->d_Y + (size_t)r0 * (size_t)p->B;
+        float2 *Zc = b.kept_fwd ? p->d_Z + (size_t)r0 * (size_t)p->B : Yc;
+        HIP_TRY(CRSDR_DISPATCH_N1(l1, (launch_long_fwd_cols<LG, false>(S, cnt, b.d_in, p->row_begin + r0, b.xor80, tw, Yc))));
+        if (two_line(p, cnt)) {
+            HIP_TRY(take_snapshot(p, S));              // same rollback protocol as the two-row K1 (check_fused_status)
+            HIP_TRY(launch_long_rows_q(S, n1, cnt, Yc, p->d_twA, p->d_twB, p->d_refspec[slot], reinterpret_cast<int *>(p->d_sync + 2), nullptr,
+                                       Zc != Yc ? Zc : nullptr));
+            p->k1_used = true;
+            p->k1_waits |= kWaitTwoLine;
+        } else
+            HIP_TRY(launch_long_rows<false>(S, n1, cnt, Yc, p->d_twA, p->d_twB, p->d_refspec[slot]));
+        HIP_TRY(CRSDR_DISPATCH_N1(l1, (launch_long_inv_cols<LG>(S, cnt, Zc, tw, p->d_part + (size_t)r0 * lb::ntiles(l1), nullptr))));
     }
+    HIP_TRY(hipEventRecord(p->ev_k1done[slot], S));       // the last reader of this block's reference spectrum has been enqueued
+    p->k1done_valid[slot] = true;
+    b.corr_zeroed = b.aa.refnoise && !b.fused && b.chunks > 1 && b.nblocks == 1;      // (the three-kernel path's integer sums: phase_three)
+    hipLaunchKernelGGL(lb::k_long_finalize, dim3(p->row_count), dim3(256), 0, S, b.kept_fwd ? p->d_Z : p->d_Y, p->d_part, tw, n1, lb::ntiles(l1),
+                       xcorr_args(p, b, slot), b.corr_zeroed ? p->d_corr : nullptr);
+    HIP_TRY(hipGetLastError());
+    if (pe1) HIP_TRY(hipEventRecord(pe1[1], S));
+    return CRSDR_OK;
+}
+
+// K1 of LDS-resident blocks (B <= 16384)
+static int k1_short(crsdr_plan *p, Batch &b)
+{
+    hipStream_t S = p->stream;
+    const int slot = (p->slot ^= 1);
+    const char variant = p->log2n == 14 ? k1_pick(p->row_count * b.nblocks, !p->q_disabled) : 0;
+    // B = 16384: the reference spectra are the first work items of the cross-correlation launch itself (fold) -- one launch, no
+    // second stream, no event between the launches of a batch.  r03, per-rank shape of the 8-GPU run (128 rows x 20 blocks,
+    // 0.16 ms per batch): the kernel on the aux stream could only start when the previous batch's K1 let go of its CUs, and the
+    // cross-stream wait + the event record between K1 and the phase kernel left 11 + 11 us of gaps around 138 us of kernels.
+    // Folded where the launch is small (the packed kernel's launches: a GPU's share of an 8-GPU run, 0.16 ms per batch): K1 itself
+    // grows by the reference items and its first rows' wait for them (0.118 -> 0.129 ms per 2560-row launch), the gaps around it
+    // shrink by more (fenced 110 k -> 117 k blocks/s, back to back 122.9 k -> 124.6 k) and the host issues a batch in 10 us
+    // instead of 26 - 40.  The two-row kernel's large launches keep the aux-stream kernel: there it hides completely, and the
+    // folded form measured 0.910 -> 0.932 ms per 20-block launch of 1024 rows (every group's first row waits for block 0's item).
+    const bool fold = p->fold && p->log2n == 14 && !p->q_disabled && variant == 'p';
+    if (!fold) {
+        // K0 on the aux stream: with resident input it overlaps the previous batch's K1 / K2.  (Putting it on the main stream
+        // when both streams are idle -- a cold batch -- was measured in r02: exposed K0 0.0526 -> 0.0516 ms per cold batch and
+        // no difference beyond the spread in a 20-block timed region; not kept.)
+        int rc = run_k0(p, b, slot, [&](hipStream_t A) -> int {
+            if (p->log2n == 14) HIP_TRY(launch_ref_spectrum14(A, b.nblocks, b.d_in, b.d_stride, p->d_twA, p->d_twB, p->d_refspec[slot], b.xor80));
+            else HIP_TRY(CRSDR_DISPATCH_LOG2(p->log2n, (launch_ref_spectrum<LG>(A, b.nblocks, b.d_in, b.d_stride, p->d_tw, p->d_refspec[slot], b.xor80))));
+            return CRSDR_OK;
+        });
+        if (rc) return rc;
+    }
+    XcorrArgs xa = xcorr_args(p, b, slot);
+    if (fold) {
+        static long folded = 0;                          // launches counted for CRSDR_K1_REFSPIN's "@k"
+        xa.fold = 1; xa.refspec_w = p->d_refspec[slot]; xa.refflag = p->d_refflag; xa.refgen = ++p->refgen;
+        xa.errflag = reinterpret_cast<int *>(p->d_sync + 2);
+        xa.refspin = sw().refspin.at(folded++);
+    }
+    hipEvent_t *pe1 = prof_pair(p, CRSDR_KERNEL_XCORR_LAG);
+    if (pe1) HIP_TRY(hipEventRecord(pe1[0], S));
+    if (p->log2n == 14) {
+        const bool q = variant == 'q';
+        // every launch with bounded waits (the two-row kernel's, a folded launch's wait for its reference spectra) snapshots the
+        // carried state first (one 28 B/row copy, ordered after the previous batch's kernels on this stream) while the ring has
+        // room: what a wait that ran out is rolled back to
+        if (q || fold) HIP_TRY(take_snapshot(p, S));
+        HIP_TRY(launch_xcorr_lag14(S, variant, xa, p->row_count, p->d_twA, p->d_twB, reinterpret_cast<int *>(p->d_sync + 2), p->d_sync + 3, &p->q_work_base));
+        p->k1_used |= q || fold;
+        p->k1_waits |= (q ? kWaitTwoRow : 0u) | (fold ? kWaitFoldRef : 0u);
+    } else
+        HIP_TRY(CRSDR_DISPATCH_LOG2(p->log2n, (launch_xcorr_lag<LG>(S, xa, p->row_count, p->d_tw))));
+    if (pe1) HIP_TRY(hipEventRecord(pe1[1], S));
+    if (!fold) {                                     // (a folded launch's spectra are written and read on this stream only)
+        HIP_TRY(hipEventRecord(p->ev_k1done[slot], S));
+        p->k1done_valid[slot] = true;
+    } else
+        p->fold_last[slot] = true;                   // ... until an unfolded batch's K0 on the aux stream takes the slot over
+    return CRSDR_OK;
+}
+
+// Both phase paths end with the fractional-delay pass (frac_pass, below).  The definitions from here on are in the order in which
+// they first name their kernels (fused phase kernel, fractional-delay kernels, three-kernel path, long-block apply pass): that order
+// is the order of the kernels in the code object.
+static int frac_pass(crsdr_plan *p, const Batch &b);
+
+// Fused phase path: every row is read once (k_align_fused); timed under CRSDR_KERNEL_ALIGN_QUANT
+static int phase_fused(crsdr_plan *p, const Batch &b)
+{
+    hipStream_t S = p->stream;
+    const size_t n = (size_t)p->nrows;
+    const int nblocks = b.nblocks;
+    // hand-over words: two slots per (row, block).  A batch publishes into one and its workgroups re-arm the other
+    // (all-ones) for the next batch, so the steady state needs no memset between launches; the host only tracks how
+    // many leading blocks of each slot are armed and falls back to a memset when a batch needs more than that
+    const int cs = p->chain_slot;
+    unsigned long long *chain = reinterpret_cast<unsigned long long *>(p->d_corr);
+    unsigned long long *chainv = chain + 2 * n * (size_t)p->max_batch;      // second half of d_corr: the chain values, same two slots
+    const bool rn = b.aa.refnoise;
+    FusedSync fs{p->d_sync, p->d_sync + 1, chain + cs, rn ? chain + (cs ^ 1) : nullptr, chainv + cs, rn ? chainv + (cs ^ 1) : nullptr,
+                 p->row_count, sw().k2_spin};
+    hipEvent_t *pe = prof_pair(p, CRSDR_KERNEL_ALIGN_QUANT);
+    if (pe) HIP_TRY(hipEventRecord(pe[0], S));
+    if (rn) {
+        if (nblocks > 1 && p->chain_armed[cs] < nblocks) {
+            HIP_TRY(hipMemsetAsync(p->d_corr, 0xFF, sizeof(long long) * 4 * n * (size_t)nblocks, S));
+            p->chain_armed[0] = p->chain_armed[1] = nblocks;
+        }
+        p->chain_armed[cs] = 0;                                             // published into
+        p->chain_armed[cs ^ 1] = std::max(p->chain_armed[cs ^ 1], nblocks); // re-armed by this launch
+        p->chain_slot = cs ^ 1;
+    }
+    // (two rows per workgroup sharing the reference row's registers: built and measured in r03, 4.05 against 4.85 TB/s -- tools/k2_pair.hpp;
+    //  persistent workgroups with the next item's row loads in flight: 3.1 - 3.6 against 4.76 TB/s -- tools/k2_persist.hpp)
+    const dim3 grid((unsigned)((1 + p->row_count) * nblocks));
+    if (p->B == 16384 && !b.xor80) hipLaunchKernelGGL((k_align_fused<true, false>), grid, dim3(kAlignThreads), 0, S, b.aa, fs);
+    else if (p->B == 16384) hipLaunchKernelGGL((k_align_fused<true, true>), grid, dim3(kAlignThreads), 0, S, b.aa, fs);
+    else hipLaunchKernelGGL((k_align_fused<false, true>), grid, dim3(kAlignThreads), 0, S, b.aa, fs);
+    HIP_TRY(hipGetLastError());
+    { int rc = frac_pass(p, b); if (rc) return rc; }
+    if (pe) HIP_TRY(hipEventRecord(pe[1], S));
+    return CRSDR_OK;
+}
+
+// fractional-delay correction of LDS-resident blocks: the owned rows once more, through the frequency domain
+static int frac_short(crsdr_plan *p, const Batch &b)
+{
+    FracArgs fa{b.d_in, b.d_stride, p->d_packet, p->packet_stride, p->d_slab, p->slab_stride, p->nrows, p->row_begin, b.xor80, b.o_lag, b.o_frac,
+                p->frac_override_on ? p->d_frac_override : nullptr, p->frac_gain, p->d_phasor};
+    HIP_TRY(CRSDR_DISPATCH_LOG2(p->log2n, (launch_frac_apply<LG>(p->stream, p->row_count, b.nblocks, fa, p->d_tw, p->d_twA, p->d_twB,
+                                                                 p->frac_generic ? nullptr : p->d_k2tab))));
+    return CRSDR_OK;
+}
+
+// Three-kernel phase path (CRSDR_K2_FUSED=0, word-aligned rows, long rows): exact integer sums (k_phase_dot), the phasor chain
+// (k_phase_chain), rotation and quantisation (k_align_quant)
+static int phase_three(crsdr_plan *p, Batch &b)
+{
+    hipStream_t S = p->stream;
+    const int nblocks = b.nblocks, chunks = b.chunks;
+    AlignArgs &aa = b.aa;
     if (aa.refnoise) {
         hipEvent_t *pe = prof_pair(p, CRSDR_KERNEL_PHASE_DOT);
         if (pe) HIP_TRY(hipEventRecord(pe[0], S));
         p->chain_armed[0] = p->chain_armed[1] = 0;   // this path keeps its integer sums in d_corr
-        if (chunks > 1 && !corr_zeroed) HIP_TRY(hipMemsetAsync(p->d_corr, 0, sizeof(long long) * 2 * n * T, S)); // atomically accumulated (k_long_finalize has zeroed a tracked block's)
+        if (chunks > 1 && !b.corr_zeroed)            // atomically accumulated (k_long_finalize has zeroed a tracked block's)
+            HIP_TRY(hipMemsetAsync(p->d_corr, 0, sizeof(long long) * 2 * (size_t)p->nrows * (size_t)nblocks, S));
         // long rows: 32 KiB per workgroup with all 16 loads of a thread in flight at once (cfg5: 34 -> 30 us per block by the plan's events)
-        if (vec16 && chunks >= 2) hipLaunchKernelGGL((k_phase_dot<true, 8>), dim3(p->row_count, nblocks, chunks / 2), dim3(kAlignThreads), 0, S, aa);
-        else if (vec16) hipLaunchKernelGGL((k_phase_dot<true, 4>), dim3(p->row_count, nblocks, chunks), dim3(kAlignThreads), 0, S, aa);
+        if (b.vec16 && chunks >= 2) hipLaunchKernelGGL((k_phase_dot<true, 8>), dim3(p->row_count, nblocks, chunks / 2), dim3(kAlignThreads), 0, S, aa);
+        else if (b.vec16) hipLaunchKernelGGL((k_phase_dot<true, 4>), dim3(p->row_count, nblocks, chunks), dim3(kAlignThreads), 0, S, aa);
         else hipLaunchKernelGGL((k_phase_dot<false, 4>), dim3(p->row_count, nblocks, chunks), dim3(kAlignThreads), 0, S, aa);
         HIP_TRY(hipGetLastError());
         if (pe) HIP_TRY(hipEventRecord(pe[1], S));
@@ -1551,56 +1524,93 @@ extern "C" int crsdr_plan_submit_batch(crsdr_plan *p, const void *rows, int mem_
         hipLaunchKernelGGL(k_phase_chain, dim3((p->row_count + 63) / 64), dim3(64), 0, S, aa, p->row_count);
         HIP_TRY(hipGetLastError());
     }
-    {
-        hipEvent_t *pe = prof_pair(p, CRSDR_KERNEL_ALIGN_QUANT);
-        if (pe) HIP_TRY(hipEventRecord(pe[0], S));
-        // with the fractional-delay correction on, the rows come from the apply pass below: here only header + readcnt + row 0
-        const unsigned gx = apply ? 1u : 1u + (unsigned)p->row_count;
-        if (vec16) hipLaunchKernelGGL(k_align_quant<true>, dim3(gx, nblocks, chunks), dim3(kAlignThreads), 0, S, aa);
-        else hipLaunchKernelGGL(k_align_quant<false>, dim3(gx, nblocks, chunks), dim3(kAlignThreads), 0, S, aa);
-        HIP_TRY(hipGetLastError());
-        if (apply) {
-            // apply pass (crsdr_plan_set_frac_apply): int8 -> column FFTs -> row FFTs x H_row -> inverse -> inverse column FFTs -> int8
-            lb::LongTw tw{p->d_wc, p->d_wf, p->d_tw1, p->d_tw, (uint32_t)(p->B - 1)};
-            const int n1 = 1 << p->log2n1, l1 = p->log2n1;
-            int8_t *obase = p->d_slab ? p->d_slab : p->d_packet + p->matrix_off + (size_t)p->row_begin * (size_t)p->B;
-            for (int r0 = 0; r0 < p->row_count; r0 += p->long_chunk) {
-                const int cnt = std::min(p->long_chunk, p->row_count - r0);
-                float2 *Yc = p->d_Y + (size_t)r0 * (size_t)p->B;
-                x14p::RampArgs ra{o_lag, o_frac, p->frac_override_on ? p->d_frac_override : nullptr, p->d_phasor, p->d_k2tab, p->d_wc, p->d_wf, lb::FBITS, p->frac_gain, p->row_begin + r0, l1};
-                if (!kept_fwd) HIP_TRY(CRSDR_DISPATCH_N1(l1, (launch_long_fwd_cols<LG, false>(S, cnt, d_in, p->row_begin + r0, xor80, tw, Yc))));
-                // stage B'': two lines per CU with the rows' responses as per-row spectra (k_ramp_rowspec + k_rows14_cf32q<true>) once a
-                // launch has enough lines; the one-line kernel that forms the response per bin otherwise
-                static const int longq2 = [] { const char *e = getenv("CRSDR_LONG_Q"); return e ? atoi(e) : 1; }();
-                const char kv2 = k1_variant();
-                if (longq2 && (kv2 == 'a' || kv2 == 'q') && !p->q_disabled && (long)n1 * cnt >= 1024) {
-                    hipLaunchKernelGGL(x14p::k_ramp_rowspec, dim3(8192 / 256, cnt), dim3(256), 0, S, p->d_rowspec + (size_t)r0 * 8192, ra);
-                    HIP_TRY(hipGetLastError());
-                    HIP_TRY(take_snapshot(p, S));          // (the same rollback protocol as the correlation pass)
-                    HIP_TRY(launch_long_rows_q(S, n1, cnt, Yc, p->d_twA, p->d_twB, reinterpret_cast<float2 *>(p->d_rowspec + (size_t)r0 * 8192),
-                                               reinterpret_cast<int *>(p->d_sync + 2), p->d_sync + 3, &p->q_work_base, &ra));
-                    p->k1_used = true;
-                    p->k1_waits |= kWaitTwoLine;
-                } else
-                    HIP_TRY(launch_long_rows_ramp(S, n1, cnt, Yc, p->d_twA, p->d_twB, ra));
-                HIP_TRY(CRSDR_DISPATCH_N1(l1, (launch_long_out_cols<LG>(S, cnt, Yc, tw, obase + (size_t)r0 * (size_t)p->B))));
-            }
-        } else if (p->frac_apply && !p->longblock && aa.digital) {       // LDS-resident blocks on the three-kernel path: as behind the fused kernel
-            FracArgs fa{d_in, d_stride, p->d_packet, p->packet_stride, p->d_slab, p->slab_stride, p->nrows, p->row_begin, xor80, o_lag, o_frac,
-                        p->frac_override_on ? p->d_frac_override : nullptr, p->frac_gain, p->d_phasor};
-            HIP_TRY(CRSDR_DISPATCH_LOG2(p->log2n, (launch_frac_apply<LG>(S, p->row_count, nblocks, fa, p->d_tw, p->d_twA, p->d_twB, p->frac_generic ? nullptr : p->d_k2tab))));
-        }
-        if (pe) HIP_TRY(hipEventRecord(pe[1], S));
+    hipEvent_t *pe = prof_pair(p, CRSDR_KERNEL_ALIGN_QUANT);
+    if (pe) HIP_TRY(hipEventRecord(pe[0], S));
+    // with the fractional-delay correction on, the rows come from the apply pass (frac_pass): here only header + readcnt + row 0
+    const unsigned gx = apply ? 1u : 1u + (unsigned)p->row_count;
+    if (b.vec16) hipLaunchKernelGGL(k_align_quant<true>, dim3(gx, nblocks, chunks), dim3(kAlignThreads), 0, S, aa);
+    else hipLaunchKernelGGL(k_align_quant<false>, dim3(gx, nblocks, chunks), dim3(kAlignThreads), 0, S, aa);
+    HIP_TRY(hipGetLastError());
+    { int rc = frac_pass(p, b); if (rc) return rc; }
+    if (pe) HIP_TRY(hipEventRecord(pe[1], S));
+    return CRSDR_OK;
+}
+
+// Fractional-delay correction (crsdr_plan_set_frac_apply, digital mode), behind the phase kernels and inside their
+// CRSDR_KERNEL_ALIGN_QUANT event pair: frac_short for LDS-resident blocks; for long blocks the apply pass, int8 -> column FFTs
+// -> row FFTs x H_row -> inverse -> inverse column FFTs -> int8.
+static int frac_pass(crsdr_plan *p, const Batch &b)
+{
+    if (!p->frac_apply || !b.aa.digital) return CRSDR_OK;
+    if (!p->longblock) return frac_short(p, b);
+    hipStream_t S = p->stream;
+    const float *frac_override = p->frac_override_on ? p->d_frac_override : nullptr;
+    const lb::LongTw tw{p->d_wc, p->d_wf, p->d_tw1, p->d_tw, (uint32_t)(p->B - 1)};
+    const int n1 = 1 << p->log2n1, l1 = p->log2n1;
+    int8_t *obase = p->d_slab ? p->d_slab : p->d_packet + p->matrix_off + (size_t)p->row_begin * (size_t)p->B;
+    for (int r0 = 0; r0 < p->row_count; r0 += p->long_chunk) {
+        const int cnt = std::min(p->long_chunk, p->row_count - r0);
+        float2 *Yc = p->d_Y + (size_t)r0 * (size_t)p->B;
+        x14p::RampArgs ra{b.o_lag, b.o_frac, frac_override, p->d_phasor, p->d_k2tab, p->d_wc, p->d_wf, lb::FBITS, p->frac_gain, p->row_begin + r0, l1};
+        if (!b.kept_fwd) HIP_TRY(CRSDR_DISPATCH_N1(l1, (launch_long_fwd_cols<LG, false>(S, cnt, b.d_in, p->row_begin + r0, b.xor80, tw, Yc))));
+        // stage B'': the two-line kernel with the rows' responses as per-row spectra (k_ramp_rowspec + k_rows14_cf32q<true>), or
+        // the one-line kernel that forms the response per bin
+        if (two_line(p, cnt)) {
+            hipLaunchKernelGGL(x14p::k_ramp_rowspec, dim3(8192 / 256, cnt), dim3(256), 0, S, p->d_rowspec + (size_t)r0 * 8192, ra);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(take_snapshot(p, S));          // (the same rollback protocol as the correlation pass)
+            HIP_TRY(launch_long_rows_q(S, n1, cnt, Yc, p->d_twA, p->d_twB, reinterpret_cast<float2 *>(p->d_rowspec + (size_t)r0 * 8192),
+                                       reinterpret_cast<int *>(p->d_sync + 2), &ra));
+            p->k1_used = true;
+            p->k1_waits |= kWaitTwoLine;
+        } else
+            HIP_TRY(launch_long_rows_ramp(S, n1, cnt, Yc, p->d_twA, p->d_twB, ra));
+        HIP_TRY(CRSDR_DISPATCH_N1(l1, (launch_long_inv_cols<LG, true>(S, cnt, Yc, tw, nullptr, obase + (size_t)r0 * (size_t)p->B))));
     }
-    { int rc_ = pack_tails(p, S, nblocks, o_lag, o_mag, o_frac, d_readcnt, seq); if (rc_) return rc_; }
-    HIP_TRY(hipEventRecord(p->ev_k2done[obuf], S));
-    p->k2done_valid[obuf] = true;
-    p->phase_cur = pout;
-    p->last_nblocks = nblocks;
+    return CRSDR_OK;
+}
+
+// End of a batch: the tails, the event a fetch waits for, the plan's bookkeeping
+static int finish_batch(crsdr_plan *p, const Batch &b, uint32_t seq)
+{
+    hipStream_t S = p->stream;
+    if (p->d_slab && p->tail_offset) {
+        // slab mode with tails (crsdr_plan_bind_slab_ex): {lag, mag, frac, phasor} of the owned rows behind the rows of every slot
+        hipLaunchKernelGGL(k_pack_tails, dim3((unsigned)((p->row_count + 255) / 256), (unsigned)b.nblocks), dim3(256), 0, S, p->d_slab, p->slab_stride,
+                           p->tail_offset, p->row_begin, p->row_count, p->nrows, b.o_lag, b.o_mag, b.o_frac, p->d_phasor, b.d_readcnt, seq);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(p->ev_k2done[p->obuf], S));            // (p->obuf: this batch's buffer)
+    p->phase_cur ^= 1;
+    p->last_nblocks = b.nblocks;
     if (p->prof_slots) { if (p->prof_mask & (1u << 31)) HIP_TRY(hipEventRecord(p->ev_stop, S)); p->prof_count++; }
     p->submitted = true;
     p->submit_idx++;
     return CRSDR_OK;
+}
+
+extern "C" int crsdr_plan_submit_batch(crsdr_plan *p, const void *rows, int mem_kind, int nblocks, size_t block_stride,
+                                       const uint32_t *readcnt, const uint8_t *lag_mask, uint32_t seq, uint32_t flags)
+{
+    if (!p || !rows) return fail(CRSDR_EINVAL, "plan_submit: NULL plan or rows");
+    if (mem_kind != CRSDR_MEM_HOST && mem_kind != CRSDR_MEM_DEVICE) return fail(CRSDR_EINVAL, "plan_submit: mem_kind = %d", mem_kind);
+    if (nblocks < 1 || nblocks > p->max_batch) return fail(CRSDR_EINVAL, "plan_submit: nblocks = %d (plan max_batch = %d)", nblocks, p->max_batch);
+    const size_t block_bytes = (size_t)p->nrows * (size_t)p->B;
+    if (block_stride == 0) block_stride = block_bytes;
+    if (block_stride < block_bytes) return fail(CRSDR_EINVAL, "plan_submit: block_stride smaller than one block");
+    if (mem_kind == CRSDR_MEM_DEVICE && ((uintptr_t)rows % 4 || block_stride % 4))
+        return fail(CRSDR_EINVAL, "plan_submit: device rows and block_stride must be 4-byte aligned (16-byte for the vector kernels)");
+    HIP_TRY(hipSetDevice(p->device));
+    Batch b{};
+    b.nblocks = nblocks;
+    int rc = stage_inputs(p, b, rows, mem_kind, block_stride, readcnt, lag_mask, flags);
+    if (rc) return rc;
+    setup_outputs(p, b, seq, flags);
+    // (K1 of batch b + 1 on its own stream beside the phase kernel of batch b was built and measured in r01 / r02 -- dead ends 5 and 10
+    // of DESIGN.md: the kernels do overlap, and K1 stretches by exactly what the phase kernel costs alone -- and removed in r03.)
+    if (b.any_lag && (rc = p->longblock ? k1_long(p, b) : k1_short(p, b))) return rc;
+    if ((rc = b.fused ? phase_fused(p, b) : phase_three(p, b))) return rc;
+    return finish_batch(p, b, seq);
 }
 
 extern "C" int crsdr_plan_submit(crsdr_plan *p, const void *rows, int mem_kind, const uint32_t *readcnt,
