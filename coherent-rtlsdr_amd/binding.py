@@ -34,7 +34,10 @@ ABI_SYMBOLS = [
     "crsdr_plan_bind_slab_ex", "crsdr_exchange_geometry", "crsdr_exchange_rooted_blocks", "crsdr_assemble_slots",
     "crsdr_plan_set_frac_apply", "crsdr_plan_fetch_batch_async", "crsdr_plan_fetch_wait", "crsdr_exchange_unique_id", "crsdr_exchange_create", "crsdr_exchange_destroy", "crsdr_exchange_batch", "crsdr_exchange_schedule",
     "crsdr_exchange_bind_plan", "crsdr_exchange_submit_batch", "crsdr_exchange_fetch_rooted",
+    "crsdr_doa_create", "crsdr_doa_destroy", "crsdr_doa_submit", "crsdr_doa_submit_plan", "crsdr_doa_fetch",
+    "crsdr_doa_device_buffers", "crsdr_doa_last_submit",
 ]
+DOA_KEEP_SPECTRUM, DOA_KEEP_RXX = 1, 2
 XCHG_STAGED, XCHG_INPLACE = 0, 1
 EXCHANGE_ID_BYTES = 128
 KERNEL_REF_SPECTRUM, KERNEL_XCORR_LAG, KERNEL_PHASE_DOT, KERNEL_ALIGN_QUANT = 0, 1, 2, 3
@@ -65,6 +68,12 @@ class XOp(C.Structure):
 class PlanDesc(C.Structure):
     _fields_ = [("nrows", C.c_int32), ("blocksize", C.c_int32), ("mode", C.c_int32), ("device", C.c_int32),
                 ("row_begin", C.c_int32), ("row_count", C.c_int32), ("max_batch", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class DoaDesc(C.Structure):
+    _fields_ = [("nrows", C.c_int32), ("blocksize", C.c_int32), ("device", C.c_int32), ("max_batch", C.c_int32), ("frames", C.c_int32),
+                ("k", C.c_int32), ("mx", C.c_int32), ("my", C.c_int32), ("ncx", C.c_int32), ("ncy", C.c_int32), ("d", C.c_float),
+                ("flags", C.c_uint32)]
 
 
 _lib = None
@@ -143,6 +152,14 @@ def lib():
     L.crsdr_plan_last_elapsed_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.crsdr_plan_enable_profiling.argtypes = [vp, C.c_int, C.c_uint32]
     L.crsdr_plan_kernel_times.argtypes = [vp, C.c_int, f32p, C.c_int, C.POINTER(C.c_int)]
+    if hasattr(L, "crsdr_doa_create"):               # (CRSDR_LIB may name an older build for an A/B of the per-op calls)
+        L.crsdr_doa_create.argtypes = [C.POINTER(vp), C.POINTER(DoaDesc)]
+        L.crsdr_doa_destroy.argtypes = [vp]
+        L.crsdr_doa_submit.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp]
+        L.crsdr_doa_submit_plan.argtypes = [vp, vp]
+        L.crsdr_doa_fetch.argtypes = [vp, i32p, f32p, f32p, i32p, f32p, f32p]
+        L.crsdr_doa_device_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        L.crsdr_doa_last_submit.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -541,6 +558,78 @@ class Plan:
     def close(self):
         if getattr(self, "_h", None):
             lib().crsdr_plan_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Doa:
+    """crsdr_doa: covariance -> noise subspace -> 2-D MUSIC scan + peak for a batch of device-resident packets, one estimate per
+    `frames` consecutive packets.  submit* only enqueue; fetch() waits and returns numpy arrays."""
+
+    def __init__(self, nrows, blocksize, k, d, mx, my, ncx=100, ncy=100, max_batch=1, frames=1, flags=0, device=0):
+        desc = DoaDesc(int(nrows), int(blocksize), int(device), int(max_batch), int(frames), int(k), int(mx), int(my), int(ncx), int(ncy),
+                       float(d), int(flags))
+        h = C.c_void_p()
+        _check(lib().crsdr_doa_create(C.byref(h), C.byref(desc)))
+        self._h = h
+        self.nrows, self.B, self.m, self.k, self.ncx, self.ncy = int(nrows), int(blocksize), int(nrows) - 1, int(k), int(ncx), int(ncy)
+        self.max_batch, self.frames, self.flags = max(1, int(max_batch)), max(1, int(frames)), int(flags)
+
+    def _last(self):
+        nest, launches = C.c_int(0), C.c_int(0)
+        _check(lib().crsdr_doa_last_submit(self._h, C.byref(nest), C.byref(launches)))
+        return nest.value, launches.value
+
+    def submit(self, packets_ptr: int, packet_stride: int, matrix_offset: int, nblocks: int, stream: int | None = None):
+        """nblocks packets on the device: packet t at packets_ptr + t * packet_stride, its matrix at + matrix_offset."""
+        _check(lib().crsdr_doa_submit(self._h, C.c_void_p(int(packets_ptr)), int(packet_stride), int(matrix_offset), int(nblocks),
+                                      C.c_void_p(stream or 0)))
+
+    def submit_plan(self, plan: "Plan"):
+        """The plan's last submitted batch, where its packets are, on the plan's stream."""
+        _check(lib().crsdr_doa_submit_plan(self._h, plan._h))
+
+    def fetch(self, spectrum=None, rxx=None) -> dict:
+        """Waits for the last submit.  peak [nest][2] (cx, cy), peak_value [nest], sv [nest][m], status [nest]; pm [nest][ncx][ncy] and
+        rxx [nest][m][m] complex64 when the object keeps them (spectrum / rxx: override, e.g. False to skip the copy)."""
+        n = self._last()[0]
+        want_pm = bool(self.flags & DOA_KEEP_SPECTRUM) if spectrum is None else bool(spectrum)
+        want_rxx = bool(self.flags & DOA_KEEP_RXX) if rxx is None else bool(rxx)
+        peak, val = np.zeros((n, 2), dtype=np.int32), np.zeros(n, dtype=np.float32)
+        sv, status = np.zeros((n, self.m), dtype=np.float32), np.zeros(n, dtype=np.int32)
+        pm = np.zeros((n, self.ncx, self.ncy), dtype=np.float32) if want_pm else None
+        r = np.zeros((n, self.m, self.m), dtype=np.complex64) if want_rxx else None
+        _check(lib().crsdr_doa_fetch(self._h, _p(peak, C.c_int32), _p(val, C.c_float), _p(sv, C.c_float), _p(status, C.c_int32),
+                                     _p(pm, C.c_float), _p(None if r is None else r.view(np.float32), C.c_float)))
+        out = {"peak": peak, "peak_value": val, "sv": sv, "status": status}
+        if pm is not None:
+            out["pm"] = pm
+        if r is not None:
+            out["rxx"] = r
+        return out
+
+    def fetch_peaks(self) -> np.ndarray:
+        """Only the directions: peak [nest][2]."""
+        peak = np.zeros((self._last()[0], 2), dtype=np.int32)
+        _check(lib().crsdr_doa_fetch(self._h, _p(peak, C.c_int32), None, None, None, None, None))
+        return peak
+
+    def device_buffers(self) -> dict:
+        ptrs = [C.c_void_p() for _ in range(5)]
+        _check(lib().crsdr_doa_device_buffers(self._h, *[C.byref(p) for p in ptrs]))
+        return dict(zip(("peak", "peak_value", "sv", "vec", "pm"), [p.value for p in ptrs]))
+
+    def last_launches(self) -> int:
+        return self._last()[1]
+
+    def close(self):
+        if self._h:
+            lib().crsdr_doa_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -3,6 +3,7 @@
 // No torch types, no CPU fallback: every compute entry point needs a HIP device.
 #include "../../include/crsdr.h"
 #include "kernels.hpp"
+#include "doa.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -1783,6 +1784,198 @@ extern "C" int crsdr_plan_kernel_times(crsdr_plan *p, int which, float *ms, int 
         HIP_TRY(hipEventElapsedTime(&t, pe[0], pe[1]));
         ms[(*count)++] = t;
     }
+    return CRSDR_OK;
+}
+
+// ================================================================================================
+// (iv) batched direction-of-arrival engine (crsdr_doa): covariance -> noise subspace -> 2-D MUSIC scan + peak, one estimate per
+//      `frames` packets, for a whole batch of packets where a plan left them.  Every buffer is allocated at create; a submit is five
+//      launches on one stream whatever the batch size (covariance partials, their reducer, subspace, scan, peak), no lock, no
+//      allocation, no synchronisation.
+// ================================================================================================
+struct crsdr_doa {
+    int nrows = 0, B = 0, m = 0, device = 0, max_batch = 1, frames = 1, k = 1, mx = 0, my = 0, ncx = 0, ncy = 0;
+    float d = 0.f;
+    uint32_t flags = 0;
+    int nt = 1, ntri = 1, spb = 1, nwg = 0;        // operand blocks, tiles, K slices per packet, scan workgroups per estimate
+    size_t lds_sub = 0, lds_scan = 0;
+    hipStream_t own_stream = nullptr, last_stream = nullptr;
+    int *d_partial = nullptr, *d_info = nullptr;
+    int2 *d_psum = nullptr;
+    float2 *d_rxx = nullptr, *d_vec = nullptr;
+    float *d_sv = nullptr, *d_peakv = nullptr, *d_pm = nullptr;
+    int32_t *d_peak = nullptr;
+    unsigned long long *d_wgbest = nullptr;
+    int last_nest = 0, last_launches = 0;
+    bool submitted = false;
+};
+
+static void doa_free(crsdr_doa *q)
+{
+    if (!q) return;
+    (void)hipSetDevice(q->device);
+    if (q->submitted) (void)hipDeviceSynchronize();      // (the last submit's stream may be the caller's, and gone)
+    void *bufs[] = {q->d_partial, q->d_info, q->d_psum, q->d_rxx, q->d_vec, q->d_sv, q->d_peakv, q->d_pm, q->d_peak, q->d_wgbest};
+    for (void *b : bufs) if (b) (void)hipFree(b);
+    if (q->own_stream) (void)hipStreamDestroy(q->own_stream);
+    delete q;
+}
+
+static int doa_alloc(crsdr_doa *q)
+{
+    HIP_TRY(hipSetDevice(q->device));
+    HIP_TRY(hipStreamCreateWithFlags(&q->own_stream, hipStreamNonBlocking));
+    const size_t T = (size_t)q->max_batch, nest = T / (size_t)q->frames, m = (size_t)q->m, grid = (size_t)q->ncx * q->ncy;
+    HIP_TRY(hipMalloc((void **)&q->d_partial, sizeof(int) * T * q->spb * q->ntri * 2 * doa::TILE_ELEMS));
+    HIP_TRY(hipMalloc((void **)&q->d_psum, sizeof(int2) * T * q->spb * doa::MAX_ROWS));
+    HIP_TRY(hipMalloc((void **)&q->d_rxx, sizeof(float2) * nest * m * m));
+    HIP_TRY(hipMalloc((void **)&q->d_vec, sizeof(float2) * nest * m * m));
+    HIP_TRY(hipMalloc((void **)&q->d_sv, sizeof(float) * nest * m));
+    HIP_TRY(hipMalloc((void **)&q->d_info, sizeof(int) * nest * 2));
+    HIP_TRY(hipMalloc((void **)&q->d_wgbest, sizeof(unsigned long long) * nest * q->nwg));
+    HIP_TRY(hipMalloc((void **)&q->d_peak, sizeof(int32_t) * nest * 2));
+    HIP_TRY(hipMalloc((void **)&q->d_peakv, sizeof(float) * nest));
+    if (q->flags & CRSDR_DOA_KEEP_SPECTRUM) HIP_TRY(hipMalloc((void **)&q->d_pm, sizeof(float) * nest * grid));
+    // the kernels' dynamic LDS limits: once, here (the subspace takes 128 KiB at m = 64)
+    HIP_TRY(hipFuncSetAttribute((const void *)doa::k_doa_subspace, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q->lds_sub));
+    HIP_TRY(hipFuncSetAttribute((const void *)doa::k_doa_scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q->lds_scan));
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_create(crsdr_doa **doa, const crsdr_doa_desc *desc)
+{
+    if (!doa || !desc) return fail(CRSDR_EINVAL, "doa_create: NULL argument");
+    *doa = nullptr;
+    const int m = desc->nrows - 1, mb = desc->max_batch ? desc->max_batch : 1, F = desc->frames ? desc->frames : 1;
+    if (m < 2 || m > music::MAX_M || desc->mx < 1 || desc->my < 1 || (long long)desc->mx * desc->my != m)
+        return fail(CRSDR_EINVAL, "doa_create: nrows - 1 = %d signal rows must be mx * my (%d x %d) in [2, %d]", m, desc->mx, desc->my, music::MAX_M);
+    if (desc->blocksize < 32 || desc->blocksize % 32 || desc->blocksize > (1 << kMaxLog2Plan))
+        return fail(CRSDR_EINVAL, "doa_create: blocksize = %d (a multiple of 32 up to %d)", desc->blocksize, 1 << kMaxLog2Plan);
+    if (mb < 1 || mb > kMaxBatch) return fail(CRSDR_EINVAL, "doa_create: max_batch = %d (1..%d)", mb, kMaxBatch);
+    if (F < 1 || F > mb) return fail(CRSDR_EINVAL, "doa_create: frames = %d (1..max_batch = %d)", desc->frames, mb);
+    if (desc->k < 1 || desc->k >= m) return fail(CRSDR_EINVAL, "doa_create: k = %d sources (1 <= k < %d)", desc->k, m);
+    if (desc->ncx < 1 || desc->ncy < 1 || (long long)desc->ncx * desc->ncy > (1 << 24))
+        return fail(CRSDR_EINVAL, "doa_create: scan grid %d x %d (at least 1 x 1, at most 2^24 points)", desc->ncx, desc->ncy);
+    if (desc->flags & ~(uint32_t)(CRSDR_DOA_KEEP_SPECTRUM | CRSDR_DOA_KEEP_RXX)) return fail(CRSDR_EINVAL, "doa_create: flags = 0x%x", desc->flags);
+    { int rc = require_device(); if (rc) return rc; }
+    int ndev = 0;
+    (void)crsdr_device_count(&ndev);
+    if (desc->device < 0 || desc->device >= ndev) return fail(CRSDR_ENODEV, "doa_create: device %d of %d", desc->device, ndev);
+
+    crsdr_doa *q = new (std::nothrow) crsdr_doa();
+    if (!q) return fail(CRSDR_ENOMEM, "doa_create: out of host memory");
+    q->nrows = desc->nrows; q->B = desc->blocksize; q->m = m; q->device = desc->device; q->max_batch = mb; q->frames = F; q->k = desc->k;
+    q->mx = desc->mx; q->my = desc->my; q->ncx = desc->ncx; q->ncy = desc->ncy; q->d = desc->d; q->flags = desc->flags;
+    q->nt = (m + doa::TILE - 1) / doa::TILE; q->ntri = doa::cov_tiles(q->nt);
+    // K slices per packet: about 1024 workgroups for a full batch (four per CU, so that the loads of one cover the MFMAs of another), no
+    // slice beyond 65536 bytes (the int32 partials stay exact), none below 512 (four MFMA steps per wave) unless the bound asks for it
+    const int spb_min = (q->B + 65535) / 65536, spb_max = std::max(spb_min, std::min(64, q->B / 512));
+    q->spb = std::min(std::max((1024 + mb - 1) / mb, spb_min), spb_max);
+    q->nwg = (int)(((size_t)q->ncx * q->ncy + music::PT - 1) / music::PT);
+    q->lds_sub = 2 * sizeof(double2) * (size_t)m * m;
+    q->lds_scan = sizeof(float2) * ((size_t)m * (m - q->k) + (size_t)m * music::PT);
+    int rc = doa_alloc(q);
+    if (rc) { doa_free(q); return rc; }
+    *doa = q;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_destroy(crsdr_doa *doa)
+{
+    if (!doa) return fail(CRSDR_EINVAL, "doa_destroy: NULL doa");
+    doa_free(doa);
+    return CRSDR_OK;
+}
+
+static int doa_launch(crsdr_doa *q, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nblocks, hipStream_t S)
+{
+    const unsigned nest = (unsigned)(nblocks / q->frames), slices = (unsigned)(q->frames * q->spb);
+    int launches = 0;
+    if (q->nt == 1)
+        hipLaunchKernelGGL(doa::k_doa_cov<1>, dim3(slices, nest), dim3(doa::COV_THREADS), 0, S, packets, packet_stride, matrix_offset, q->nrows, q->B, q->frames,
+                           q->spb, q->d_partial, q->d_psum);
+    else
+        hipLaunchKernelGGL(doa::k_doa_cov<2>, dim3(slices, nest), dim3(doa::COV_THREADS), 0, S, packets, packet_stride, matrix_offset, q->nrows, q->B, q->frames,
+                           q->spb, q->d_partial, q->d_psum);
+    HIP_TRY(hipGetLastError()); ++launches;
+    hipLaunchKernelGGL(doa::k_doa_cov_reduce, dim3((unsigned)q->ntri, nest), dim3(256), 0, S, (const int *)q->d_partial, (const int2 *)q->d_psum, (int)slices, q->ntri,
+                       q->nrows, q->B, q->frames, q->d_rxx);
+    HIP_TRY(hipGetLastError()); ++launches;
+    hipLaunchKernelGGL(doa::k_doa_subspace, dim3(nest), dim3(music::JT), q->lds_sub, S, (const float2 *)q->d_rxx, q->m, q->d_sv, q->d_vec, q->d_info);
+    HIP_TRY(hipGetLastError()); ++launches;
+    hipLaunchKernelGGL(doa::k_doa_scan, dim3((unsigned)q->nwg, nest), dim3(music::PT), q->lds_scan, S, (const float2 *)q->d_vec, q->m, q->k, q->d, q->mx, q->my, q->ncx,
+                       q->ncy, q->d_pm, q->d_wgbest);
+    HIP_TRY(hipGetLastError()); ++launches;
+    hipLaunchKernelGGL(doa::k_doa_peak, dim3(nest), dim3(256), 0, S, (const unsigned long long *)q->d_wgbest, q->nwg, q->ncy, q->d_peak, q->d_peakv);
+    HIP_TRY(hipGetLastError()); ++launches;
+    q->last_stream = S; q->last_nest = (int)nest; q->last_launches = launches; q->submitted = true;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_submit(crsdr_doa *q, const void *device_packets, size_t packet_stride, size_t matrix_offset, int nblocks, void *hip_stream)
+{
+    if (!q || !device_packets) return fail(CRSDR_EINVAL, "doa_submit: NULL doa or packets");
+    if (nblocks < 1 || nblocks > q->max_batch || nblocks % q->frames)
+        return fail(CRSDR_EINVAL, "doa_submit: nblocks = %d (1..max_batch = %d, a multiple of frames = %d)", nblocks, q->max_batch, q->frames);
+    if (((uintptr_t)device_packets + matrix_offset) % 4 || packet_stride % 4)
+        return fail(CRSDR_EINVAL, "doa_submit: matrix start and packet stride must be 4-byte aligned");
+    HIP_TRY(hipSetDevice(q->device));
+    return doa_launch(q, (const int8_t *)device_packets, packet_stride, matrix_offset, nblocks, hip_stream ? (hipStream_t)hip_stream : q->own_stream);
+}
+
+extern "C" int crsdr_doa_submit_plan(crsdr_doa *q, crsdr_plan *p)
+{
+    if (!q || !p) return fail(CRSDR_EINVAL, "doa_submit_plan: NULL argument");
+    if (p->nrows != q->nrows || p->B != q->B || p->device != q->device)
+        return fail(CRSDR_EINVAL, "doa_submit_plan: plan is %d x %d on device %d, doa %d x %d on device %d", p->nrows, p->B, p->device, q->nrows, q->B, q->device);
+    if (p->d_slab) return fail(CRSDR_ESTATE, "doa_submit_plan: the plan writes slabs (crsdr_plan_bind_slab): its packets hold no matrix");
+    if (!p->submitted || p->last_nblocks < 1) return fail(CRSDR_ESTATE, "doa_submit_plan: the plan has no submitted batch");
+    if (p->last_nblocks > q->max_batch || p->last_nblocks % q->frames)
+        return fail(CRSDR_EINVAL, "doa_submit_plan: the plan's batch of %d blocks (doa: at most %d, a multiple of frames = %d)", p->last_nblocks, q->max_batch, q->frames);
+    HIP_TRY(hipSetDevice(q->device));
+    // the batch's last kernel is on p->stream: stream order alone puts the covariance behind it
+    return doa_launch(q, p->d_packet, p->packet_stride, p->matrix_off, p->last_nblocks, p->stream);
+}
+
+extern "C" int crsdr_doa_fetch(crsdr_doa *q, int32_t *peak, float *peak_value, float *sv, int32_t *status, float *pm, float *rxx)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_fetch: NULL doa");
+    if (pm && !(q->flags & CRSDR_DOA_KEEP_SPECTRUM)) return fail(CRSDR_EINVAL, "doa_fetch: pm asked of a doa created without CRSDR_DOA_KEEP_SPECTRUM");
+    if (rxx && !(q->flags & CRSDR_DOA_KEEP_RXX)) return fail(CRSDR_EINVAL, "doa_fetch: rxx asked of a doa created without CRSDR_DOA_KEEP_RXX");
+    if (!q->submitted) return fail(CRSDR_ESTATE, "doa_fetch: nothing submitted");
+    HIP_TRY(hipSetDevice(q->device));
+    const size_t nest = (size_t)q->last_nest, m = (size_t)q->m;
+    hipStream_t S = q->last_stream;
+    int info[2 * kMaxBatch];
+    if (peak) HIP_TRY(hipMemcpyAsync(peak, q->d_peak, sizeof(int32_t) * nest * 2, hipMemcpyDeviceToHost, S));
+    if (peak_value) HIP_TRY(hipMemcpyAsync(peak_value, q->d_peakv, sizeof(float) * nest, hipMemcpyDeviceToHost, S));
+    if (sv) HIP_TRY(hipMemcpyAsync(sv, q->d_sv, sizeof(float) * nest * m, hipMemcpyDeviceToHost, S));
+    if (status) HIP_TRY(hipMemcpyAsync(info, q->d_info, sizeof(int) * nest * 2, hipMemcpyDeviceToHost, S));
+    if (pm) HIP_TRY(hipMemcpyAsync(pm, q->d_pm, sizeof(float) * nest * (size_t)q->ncx * q->ncy, hipMemcpyDeviceToHost, S));
+    if (rxx) HIP_TRY(hipMemcpyAsync(rxx, q->d_rxx, sizeof(float2) * nest * m * m, hipMemcpyDeviceToHost, S));
+    HIP_TRY(hipStreamSynchronize(S));
+    if (status)
+        for (size_t e = 0; e < nest; ++e) status[e] = info[2 * e + 1] ? 0 : 1;      // Jacobi sweeps ran out: data, not a failed call
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_device_buffers(crsdr_doa *q, void **peak, void **peak_value, void **sv, void **vec, void **pm)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_device_buffers: NULL doa");
+    if (peak) *peak = q->d_peak;
+    if (peak_value) *peak_value = q->d_peakv;
+    if (sv) *sv = q->d_sv;
+    if (vec) *vec = q->d_vec;
+    if (pm) *pm = q->d_pm;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_last_submit(crsdr_doa *q, int *nest, int *launches)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_last_submit: NULL doa");
+    if (!q->submitted) return fail(CRSDR_ESTATE, "doa_last_submit: nothing submitted");
+    if (nest) *nest = q->last_nest;
+    if (launches) *launches = q->last_launches;
     return CRSDR_OK;
 }
 

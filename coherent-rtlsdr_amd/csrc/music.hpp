@@ -42,8 +42,9 @@ __device__ __forceinline__ double sum16(double v)
 // rxx [M][M] cf32 row-major (Hermitian).  Outputs: sv [M] singular values, descending;
 // vec [M][M] cf32 row-major, column r = the singular vector of sv[r] (so the noise subspace for K sources is
 // columns K .. M-1); info[0] = sweeps used, info[1] = 1 if converged.
-__global__ __launch_bounds__(JT) void k_herm_subspace(const float2 *__restrict__ rxx, int M, float *__restrict__ sv,
-                                                      float2 *__restrict__ vec, int *__restrict__ info)
+// (a device function so that the per-op kernel and the batched one of doa.hpp are the same instruction sequence per matrix)
+__device__ __forceinline__ void herm_subspace(const float2 *__restrict__ rxx, int M, float *__restrict__ sv, float2 *__restrict__ vec,
+                                              int *__restrict__ info)
 {
     extern __shared__ double2 jsm[];
     double2 *G = jsm;                       // [col][row], column-major: a pair's lanes walk consecutive rows
@@ -142,11 +143,18 @@ __global__ __launch_bounds__(JT) void k_herm_subspace(const float2 *__restrict__
     if (tid == 0) { info[0] = sweeps; info[1] = converged; }
 }
 
+__global__ __launch_bounds__(JT) void k_herm_subspace(const float2 *__restrict__ rxx, int M, float *__restrict__ sv,
+                                                      float2 *__restrict__ vec, int *__restrict__ info)
+{
+    herm_subspace(rxx, M, sv, vec, info);
+}
+
 constexpr int PT = 64;               // grid points per workgroup of the scan
 
-// un [M][ldu] cf32 row-major, noise vectors = columns col0 .. col0 + nn - 1;  pm [Cx][Cy] row-major.
-__global__ __launch_bounds__(PT) void k_pmusic2d(const float2 *__restrict__ un, int M, int ldu, int col0, int nn, float d, int Mx,
-                                                 int My, int Cx, int Cy, float *__restrict__ pm)
+// pm of grid point g = blockIdx.x * PT + threadIdx.x (live: g inside the grid), the whole workgroup calling together.
+// un [M][ldu] cf32 row-major, noise vectors = columns col0 .. col0 + nn - 1.  Shared by k_pmusic2d and the batched scan of doa.hpp.
+__device__ __forceinline__ float pmusic2d_point(const float2 *__restrict__ un, int M, int ldu, int col0, int nn, float d, int Mx, int My,
+                                                int Cx, int Cy, int g, bool live)
 {
     extern __shared__ float2 psm[];
     float2 *U = psm;                         // [M][nn]
@@ -156,8 +164,6 @@ __global__ __launch_bounds__(PT) void k_pmusic2d(const float2 *__restrict__ un, 
         const int i = e / nn, j = e - i * nn;
         U[e] = un[(size_t)i * ldu + col0 + j];
     }
-    const int g = blockIdx.x * PT + tid;
-    const bool live = g < Cx * Cy;
     const int cx = live ? g / Cy : 0, cy = live ? g - (g / Cy) * Cy : 0;
     const float pi = 3.14159274101257324f;   // (float) acos(-1), heatmap2d2.cpp:60
     const float alpha = (float)cx * pi / (float)Cx, beta = (float)cy * pi / (float)Cy;
@@ -188,10 +194,18 @@ __global__ __launch_bounds__(PT) void k_pmusic2d(const float2 *__restrict__ un, 
         }
         den += yr * yr + yi * yi;
     }
-    if (live) {
-        const float res = a2 / den;
-        pm[g] = res * res;
-    }
+    const float res = a2 / den;
+    return res * res;
+}
+
+// pm [Cx][Cy] row-major.
+__global__ __launch_bounds__(PT) void k_pmusic2d(const float2 *__restrict__ un, int M, int ldu, int col0, int nn, float d, int Mx,
+                                                 int My, int Cx, int Cy, float *__restrict__ pm)
+{
+    const int g = blockIdx.x * PT + threadIdx.x;
+    const bool live = g < Cx * Cy;
+    const float v = pmusic2d_point(un, M, ldu, col0, nn, d, Mx, My, Cx, Cy, g, live);
+    if (live) pm[g] = v;
 }
 
 } // namespace music

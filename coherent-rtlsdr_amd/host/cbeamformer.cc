@@ -36,4 +36,46 @@ int pmusic2dvec(const cmatrix &U, int M, int K, float d, int Mx, int My, int Cx,
     return rc;
 }
 
+batch::batch(int nrows, int blocksize, int max_batch, int K, int frames, bool keep_spectrum, float d, int Mx, int My, int Cx, int Cy, int device)
+    : m(nrows - 1), cx(Cx), cy(Cy), keep(keep_spectrum)
+{
+    crsdr_doa_desc desc = {};
+    desc.nrows = nrows; desc.blocksize = blocksize; desc.device = device; desc.max_batch = max_batch; desc.frames = frames; desc.k = K;
+    desc.mx = Mx; desc.my = My; desc.ncx = Cx; desc.ncy = Cy; desc.d = d;
+    desc.flags = keep_spectrum ? CRSDR_DOA_KEEP_SPECTRUM : 0u;
+    if (crsdr_doa_create(&doa, &desc)) { std::fprintf(stderr, "cbeamformer::batch: %s\n", crsdr_last_error()); doa = nullptr; }
+}
+
+batch::~batch()
+{
+    if (doa) crsdr_doa_destroy(doa);
+}
+
+int batch::submit(crsdr_plan *plan)
+{
+    int rc = doa ? crsdr_doa_submit_plan(doa, plan) : CRSDR_ESTATE;
+    if (rc && doa) std::fprintf(stderr, "cbeamformer::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::submit(const void *device_packets, size_t packet_stride, size_t matrix_offset, int nblocks, void *hip_stream)
+{
+    int rc = doa ? crsdr_doa_submit(doa, device_packets, packet_stride, matrix_offset, nblocks, hip_stream) : CRSDR_ESTATE;
+    if (rc && doa) std::fprintf(stderr, "cbeamformer::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::fetch()
+{
+    int nest = 0;
+    int rc = doa ? crsdr_doa_last_submit(doa, &nest, nullptr) : CRSDR_ESTATE;
+    if (!rc) {
+        peak.assign(2 * (size_t)nest, 0); peak_value.assign(nest, 0.f); sv.assign((size_t)nest * m, 0.f); status.assign(nest, 0);
+        if (keep) pm.assign((size_t)nest * cx * cy, 0.f);
+        rc = crsdr_doa_fetch(doa, peak.data(), peak_value.data(), sv.data(), status.data(), keep ? pm.data() : nullptr, nullptr);
+    }
+    if (rc && doa) std::fprintf(stderr, "cbeamformer::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
 } // namespace cbeamformer

@@ -24,5 +24,29 @@ int covariance(const int8_t *packet, cmatrix &Rxx, int &M);
 int noisesubspace(const cmatrix &Rxx, int M, cmatrix &U, std::vector<float> *S = nullptr);
 // pm [Cx][Cy] row-major, not normalised
 int pmusic2dvec(const cmatrix &U, int M, int K, float d, int Mx, int My, int Cx, int Cy, std::vector<float> &pm);
+
+// The three steps above for a whole batch of packets where the engine's plan left them on the device (crsdr_doa): one submit, no
+// host work per packet, a direction per `frames` consecutive blocks.  submit() only enqueues (on the plan's stream, behind the batch
+// it reads); fetch() waits and fills the vectors below.  One submit at a time: fetch before the next.
+class batch {
+    crsdr_doa *doa = nullptr;
+    int m = 0, cx = 0, cy = 0;
+    bool keep = false;
+public:
+    // nrows x blocksize: the packets' geometry (1 + Mx * My rows); keep_spectrum: fetch() also fills pm
+    batch(int nrows, int blocksize, int max_batch, int K = 1, int frames = 1, bool keep_spectrum = false, float d = D, int Mx = MX, int My = MY,
+          int Cx = CX, int Cy = CY, int device = 0);
+    ~batch();
+    batch(const batch &) = delete;
+    batch &operator=(const batch &) = delete;
+    bool ok() const { return doa != nullptr; }
+    int submit(crsdr_plan *plan);                    // the plan's last submitted batch
+    int submit(const void *device_packets, size_t packet_stride, size_t matrix_offset, int nblocks, void *hip_stream = nullptr);
+    int fetch();
+    int estimates() const { return (int)status.size(); }
+    std::vector<int32_t> peak;                       // [estimates][2]: (cx, cy) of the largest pm
+    std::vector<float> peak_value, sv, pm;           // [estimates], [estimates][M], [estimates][Cx][Cy] (keep_spectrum)
+    std::vector<int32_t> status;                     // 0 = converged
+};
 }
 #endif

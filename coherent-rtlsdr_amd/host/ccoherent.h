@@ -70,6 +70,7 @@ public:
     std::atomic<bool> do_exit;
     ccoherent(crefsdr *, lvector<csdrdevice *> *, crefnoise *, int nfft, int mode = CRSDR_MODE_FAITHFUL, int batch = 1, const ccoherent_shard *shard = nullptr);
     bool ok() const { return plan != nullptr; }
+    crsdr_plan *engine_plan() const { return plan; }       // for consumers of the device-resident packets (cbeamformer::batch)
     bool sharded() const { return xchg != nullptr; }
     int batch_rooted_first(int slot) const { return brooted_first[slot]; }     // sharded: the blocks of the slot's batch this rank assembled
     int batch_rooted_count(int slot) const { return brooted_count[slot]; }

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <unistd.h>
@@ -274,15 +275,37 @@ int main(int argc, char **argv)
         const int nb = std::max(3, blocks / batch);
         const uint32_t fl = CRSDR_REFNOISE_ENABLED;
         bool ok = true;
+        // --bench --music: a direction per block from the packets where the plan left them (cbeamformer::batch over crsdr_doa), enqueued
+        // behind every batch on the plan's stream; the peaks are the only thing fetched.  The synthetic channels all carry the reference
+        // noise: once aligned, one source at broadside, grid point (50, 50).
+        std::unique_ptr<cbeamformer::batch> doa;
+        if (music && !coherent.sharded()) {
+            doa.reset(new cbeamformer::batch(1 + nsig, B, batch));
+            if (nsig != cbeamformer::MX * cbeamformer::MY || !doa->ok()) { std::printf("doa: unavailable (needs --nsig 21)\nDEMO FAILED\n"); return 1; }
+        }
+        bool report = false;
+        auto directions = [&](int b) {
+            if (!doa || !ok) return;
+            ok = doa->submit(coherent.engine_plan()) == CRSDR_OK && doa->fetch() == CRSDR_OK;
+            if (!ok || !report) return;
+            const int n = doa->estimates();
+            int broadside = 0;
+            for (int e = 0; e < n; ++e) broadside += doa->peak[2 * e] == 50 && doa->peak[2 * e + 1] == 50;
+            std::printf("doa: batch %d: %d directions, first (%d, %d), last (%d, %d), %d at broadside\n", b, n, doa->peak[0], doa->peak[1], doa->peak[2 * n - 2],
+                        doa->peak[2 * n - 1], broadside);
+        };
         auto run = [&](int n) {
             ok = ok && coherent.submit_batch(0, batch, fl);
+            directions(0);
             for (int b = 1; b < n && ok; ++b) {
                 ok = ok && coherent.submit_batch(b & 1, batch, fl);       // upload of batch b overlaps the download of batch b - 1
+                directions(b);
                 ok = ok && coherent.collect_batch((b - 1) & 1);
             }
             ok = ok && coherent.collect_batch((n - 1) & 1);
         };
         run(3);                                                           // warm-up: allocations, code objects, link
+        report = true;
         const auto t0 = std::chrono::steady_clock::now();
         run(nb);
         const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

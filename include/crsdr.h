@@ -420,6 +420,70 @@ int crsdr_noisesubspace(float *vec, float *sv, const float *rxx, int m, int mem_
  *   pm  [ncx][ncy] float row-major, not normalised (the reference divides by the maximum for plotting, :202-203) */
 int crsdr_pmusic2d(float *pm, const float *vec, int m, int k, float d, int mx, int my, int ncx, int ncy, int mem_kind);
 
+/* ------------------------------------------------------------------------------------------
+ * (iv) batched direction-of-arrival engine: the chain above for a whole batch of packets where a plan left them
+ * ---------------------------------------------------------------------------------------- */
+
+/* crsdr_covariance -> crsdr_noisesubspace -> crsdr_pmusic2d -> index of the largest pm, for up to 64 packets per submit, one estimate
+ * per `frames` consecutive packets (their samples stacked, X = [X; Xc] as measurement_script.m does: L = frames * blocksize / 2).
+ * Every buffer is allocated by crsdr_doa_create.  A submit is asynchronous on its stream: five kernel launches whatever the
+ * number of blocks, no allocation, no process-wide lock, nothing that waits for the device.  Per estimate the numbers are those of
+ * the per-op calls on the same matrix, bit for bit (exact integer sums with the same fp64 epilogue; the same instruction sequence
+ * for the subspace and for every grid point). */
+typedef struct crsdr_doa crsdr_doa;
+
+enum {
+    CRSDR_DOA_KEEP_SPECTRUM = 1u << 0, /* keep pm[ncx][ncy] of every estimate (otherwise only the peak leaves the scan) */
+    CRSDR_DOA_KEEP_RXX = 1u << 1       /* allow crsdr_doa_fetch to return the covariances */
+};
+
+typedef struct crsdr_doa_desc {
+    int32_t nrows, blocksize; /* of the packets it reads (as in crsdr_plan_desc); m = nrows - 1 = mx * my signal rows, 2 <= m <= 64;
+                                 blocksize % 32 == 0 */
+    int32_t device;
+    int32_t max_batch;        /* blocks per submit, 1..64 (0 = 1) */
+    int32_t frames;           /* F >= 1 consecutive blocks stacked into one estimate, F <= max_batch (0 = 1) */
+    int32_t k;                /* number of sources, 1 <= k < m */
+    int32_t mx, my, ncx, ncy; /* array and scan grid, as crsdr_pmusic2d */
+    float d;
+    uint32_t flags;           /* CRSDR_DOA_KEEP_* */
+} crsdr_doa_desc;
+
+int crsdr_doa_create(crsdr_doa **doa, const crsdr_doa_desc *desc);
+int crsdr_doa_destroy(crsdr_doa *doa);
+
+/* nblocks packets on the doa's device, packet t at device_packets + t * packet_stride, its matrix [nrows][blocksize] int8 at
+ * + matrix_offset (4-byte aligned, like packet_stride); 1 <= nblocks <= max_batch, nblocks % frames == 0.  Asynchronous on hip_stream
+ * (NULL = the object's own stream); the packets must stay valid until the work has run.  One submit at a time: the next one reuses
+ * the buffers of this one, so fetch (or order the streams) in between. */
+int crsdr_doa_submit(crsdr_doa *doa, const void *device_packets, size_t packet_stride, size_t matrix_offset, int nblocks,
+                     void *hip_stream);
+
+/* The plan's last submitted batch, where its packets are (own buffer or crsdr_plan_bind_packet), on the plan's stream: ordered
+ * behind that batch by the stream alone, no host wait in between.  CRSDR_ESTATE for a plan with nothing submitted or with a slab
+ * bound (the matrix is then not in the packet); CRSDR_EINVAL for another geometry or device, or a batch that is not a multiple of
+ * `frames` or exceeds max_batch. */
+int crsdr_doa_submit_plan(crsdr_doa *doa, crsdr_plan *plan);
+
+/* Waits for the last submit and copies out what is asked for (any pointer may be NULL); nest = nblocks / frames.
+ *   peak       [nest][2] int32 (cx, cy) of the largest pm; the first index in row-major order on ties (as crsdr_indexofmax).  A NaN
+ *              pm counts as the largest value (numpy's argmax convention).
+ *   peak_value [nest]      that pm
+ *   sv         [nest][m]   singular values, descending
+ *   status     [nest]      0 = converged, 1 = the Jacobi sweeps ran out (sv / peak are still written: data, not a failed call)
+ *   pm         [nest][ncx][ncy]   CRSDR_EINVAL without CRSDR_DOA_KEEP_SPECTRUM
+ *   rxx        [nest][m][m][2]    CRSDR_EINVAL without CRSDR_DOA_KEEP_RXX
+ * CRSDR_ESTATE before the first submit. */
+int crsdr_doa_fetch(crsdr_doa *doa, int32_t *peak, float *peak_value, float *sv, int32_t *status, float *pm, float *rxx);
+
+/* Device addresses of the results ([max_batch / frames] estimates each, laid out as above; vec [nest][m][m][2] as
+ * crsdr_noisesubspace writes it; pm is NULL without CRSDR_DOA_KEEP_SPECTRUM), for consumers on the same stream. */
+int crsdr_doa_device_buffers(crsdr_doa *doa, void **peak, void **peak_value, void **sv, void **vec, void **pm);
+
+/* Of the last submit: the number of estimates (what crsdr_doa_fetch will write) and the kernel launches it issued (the same for
+ * every nblocks).  Either pointer may be NULL.  CRSDR_ESTATE before the first submit. */
+int crsdr_doa_last_submit(crsdr_doa *doa, int *nest, int *launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,179 @@
+#!/usr/bin/env python3
+"""Frames per second of the beamformer chain on the 7 x 3 array (22 rows x 16384, T = 64 device-resident packets), per-op against batched:
+
+  (a) the per-op loop: crsdr_covariance -> crsdr_noisesubspace -> crsdr_pmusic2d with CRSDR_MEM_DEVICE pointers, once per packet
+      (pm stays on the device: finding its peak is not even in the figure).  Run in a worker of its own, so that it can load an older
+      build of the library (--perop-lib, e.g. the parent commit's) through CRSDR_LIB.
+  (b) crsdr_doa_submit of the 64 packets + a fetch of the peaks only,
+  (c) the same with the spectra kept and fetched (64 x 40 KB).
+
+--runs runs of each, alternating a, b, c in one session (two worker processes, both alive throughout); medians and ranges.
+Also: what crsdr_doa_submit_plan + the peak fetch add to a 22-row, T = 64 plan batch (plan.submit + sync against
+plan.submit + doa.submit_plan + fetch).  --json FILE keeps the record; --once MODE runs one submit + fetch and exits (for a kernel trace)."""
+import argparse, importlib, json, os, subprocess, sys, time
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NROWS, B, T, M = 22, 16384, 64, 21
+
+
+def _setup():
+    sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import torch
+    import ura
+    b = importlib.import_module("coherent-rtlsdr_amd.binding")
+    rng = np.random.default_rng(1)
+    dev = torch.device("cuda", 0)
+    off = 16 + 4 * NROWS
+    stride = off + NROWS * B
+    host = np.zeros((T, stride), dtype=np.int8)
+    for t in range(T):
+        host[t, off:] = ura.scene(B // 2, [(0.6 + 0.03 * t, 1.2 + 0.02 * t, 1.0)], rng).reshape(-1)
+    pk = torch.from_numpy(host).to(dev)
+    return torch, ura, b, dev, pk, off, stride, host
+
+
+def worker_perop():
+    """(a): one line 'ready', then for every line on stdin one timed loop over the 64 packets and its seconds on stdout."""
+    import ctypes as C
+    torch, ura, b, dev, pk, off, stride, _ = _setup()
+    L = b.lib()
+    f32p, i8p = C.POINTER(C.c_float), C.POINTER(C.c_int8)
+    rxx = torch.zeros(M * M * 2, dtype=torch.float32, device=dev)
+    vec = torch.zeros(M * M * 2, dtype=torch.float32, device=dev)
+    sv = torch.zeros(M, dtype=torch.float32, device=dev)
+    pm = torch.zeros(100 * 100, dtype=torch.float32, device=dev)
+    fp = lambda t: C.cast(C.c_void_p(t.data_ptr()), f32p)
+
+    def loop():
+        for t in range(T):
+            m = C.cast(C.c_void_p(pk.data_ptr() + t * stride + off), i8p)
+            b._check(L.crsdr_covariance(fp(rxx), m, NROWS, B, b.MEM_DEVICE))
+            b._check(L.crsdr_noisesubspace(fp(vec), fp(sv), fp(rxx), M, b.MEM_DEVICE))
+            b._check(L.crsdr_pmusic2d(fp(pm), fp(vec), M, 1, float(ura.D), ura.MX, ura.MY, 100, 100, b.MEM_DEVICE))
+    loop()
+    print("ready", flush=True)
+    for _ in sys.stdin:
+        t0 = time.perf_counter()
+        loop()
+        print(time.perf_counter() - t0, flush=True)
+
+
+def worker_doa():
+    """(b), (c) and the plan figures: 'b' / 'c' / 'plan' / 'plan+doa' on stdin -> seconds of one batch of 64 on stdout."""
+    torch, ura, b, dev, pk, off, stride, host = _setup()
+    peaks = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
+    full = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T, flags=b.DOA_KEEP_SPECTRUM)
+    plan = b.Plan(NROWS, B, b.MODE_DIGITAL, max_batch=T)
+    rows = torch.from_numpy(np.ascontiguousarray(host[:, off:])).to(dev)       # [T][nrows * B], the plan's device input
+    pdoa = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
+
+    def run_b():
+        peaks.submit(pk.data_ptr(), stride, off, T)
+        return peaks.fetch_peaks()
+
+    def run_c():
+        full.submit(pk.data_ptr(), stride, off, T)
+        return full.fetch()
+
+    def run_plan(n=10):
+        for i in range(n):
+            plan.submit(rows.data_ptr(), nblocks=T, seq=i * T)
+        plan.sync()
+
+    def run_plan_doa(n=10):
+        for i in range(n):
+            plan.submit(rows.data_ptr(), nblocks=T, seq=i * T)
+            pdoa.submit_plan(plan)
+            pdoa.fetch_peaks()
+        plan.sync()
+    jobs = {"b": (run_b, 1), "c": (run_c, 1), "plan": (run_plan, 10), "plan+doa": (run_plan_doa, 10)}
+    for f, _ in jobs.values():
+        f()
+    print("ready", flush=True)
+    for line in sys.stdin:
+        f, n = jobs[line.strip()]
+        t0 = time.perf_counter()
+        f()
+        print((time.perf_counter() - t0) / n, flush=True)
+
+
+def once(mode):
+    torch, ura, b, dev, pk, off, stride, _ = _setup()
+    d = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T, flags=b.DOA_KEEP_SPECTRUM if mode == "c" else 0)
+    for _ in range(3):
+        d.submit(pk.data_ptr(), stride, off, T)
+        out = d.fetch()
+    print("peaks", out["peak"][:4].tolist(), "launches", d.last_launches())
+
+
+class Worker:
+    def __init__(self, mode, lib=None):
+        env = dict(os.environ)
+        if lib:
+            env["CRSDR_LIB"] = lib
+        self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", mode], stdin=subprocess.PIPE, stdout=subprocess.PIPE,
+                                  text=True, env=env)
+        line = self.p.stdout.readline().strip()
+        if line != "ready":
+            raise RuntimeError(f"worker {mode} did not start: {line!r} (exit {self.p.poll()})")
+
+    def run(self, what="go"):
+        self.p.stdin.write(what + "\n"); self.p.stdin.flush()
+        line = self.p.stdout.readline().strip()
+        if not line:
+            raise RuntimeError(f"worker died (exit {self.p.wait()})")     # nothing more is started on the device
+        return float(line)
+
+    def close(self):
+        self.p.stdin.close()
+        self.p.wait(timeout=60)
+
+
+def _stat(xs):
+    return {"median": float(np.median(xs)), "min": float(min(xs)), "max": float(max(xs))}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--worker", choices=["perop", "doa"])
+    ap.add_argument("--once", choices=["b", "c"])
+    ap.add_argument("--perop-lib", default=None, help="library for (a), e.g. a build of the parent commit (default: the current one)")
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    if a.worker:
+        return worker_perop() if a.worker == "perop" else worker_doa()
+    if a.once:
+        return once(a.once)
+    wa, wb = Worker("perop", a.perop_lib), Worker("doa")
+    sec = {k: [] for k in ("a", "b", "c", "plan", "plan+doa")}
+    try:
+        for _ in range(a.runs):
+            sec["a"].append(wa.run())
+            sec["b"].append(wb.run("b"))
+            sec["c"].append(wb.run("c"))
+            sec["plan"].append(wb.run("plan"))
+            sec["plan+doa"].append(wb.run("plan+doa"))
+    finally:
+        wa.close(); wb.close()
+    rec = {"shape": {"nrows": NROWS, "blocksize": B, "blocks": T, "grid": [100, 100]}, "runs": a.runs,
+           "perop_lib": a.perop_lib or "current build", "ms_per_batch": {k: _stat([1e3 * x for x in v]) for k, v in sec.items()},
+           "frames_per_s": {k: _stat([T / x for x in sec[k]]) for k in ("a", "b", "c")}}
+    rec["b_faster_than_a_ranges_disjoint"] = rec["ms_per_batch"]["b"]["max"] < rec["ms_per_batch"]["a"]["min"]
+    rec["submit_plan_adds_ms_per_batch"] = rec["ms_per_batch"]["plan+doa"]["median"] - rec["ms_per_batch"]["plan"]["median"]
+    names = {"a": "per-op loop, device pointers", "b": "doa submit + peaks", "c": "doa submit + peaks + spectra",
+             "plan": "plan batch alone", "plan+doa": "plan batch + submit_plan + peaks"}
+    for k, s in rec["ms_per_batch"].items():
+        fps = f"  {T / (1e-3 * s['median']):10.0f} frames/s" if k in rec["frames_per_s"] else ""
+        print(f"({k}) {names[k]:34s} {s['median']:8.3f} ms per 64 blocks  [{s['min']:.3f} .. {s['max']:.3f}]{fps}")
+    print(f"(b) faster than (a), ranges disjoint: {rec['b_faster_than_a_ranges_disjoint']};  "
+          f"a direction per block adds {rec['submit_plan_adds_ms_per_batch']:.3f} ms to a plan batch of 64")
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(rec, f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
