@@ -35,7 +35,8 @@ ABI_SYMBOLS = [
     "crsdr_plan_set_frac_apply", "crsdr_plan_fetch_batch_async", "crsdr_plan_fetch_wait", "crsdr_exchange_unique_id", "crsdr_exchange_create", "crsdr_exchange_destroy", "crsdr_exchange_batch", "crsdr_exchange_schedule",
     "crsdr_exchange_bind_plan", "crsdr_exchange_submit_batch", "crsdr_exchange_fetch_rooted",
     "crsdr_doa_create", "crsdr_doa_destroy", "crsdr_doa_submit", "crsdr_doa_submit_plan", "crsdr_doa_fetch",
-    "crsdr_doa_device_buffers", "crsdr_doa_last_submit",
+    "crsdr_doa_device_buffers", "crsdr_doa_last_submit", "crsdr_doa_set_peaks", "crsdr_doa_fetch_directions",
+    "crsdr_doa_direction_buffers",
 ]
 DOA_KEEP_SPECTRUM, DOA_KEEP_RXX = 1, 2
 XCHG_STAGED, XCHG_INPLACE = 0, 1
@@ -160,6 +161,10 @@ def lib():
         L.crsdr_doa_fetch.argtypes = [vp, i32p, f32p, f32p, i32p, f32p, f32p]
         L.crsdr_doa_device_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.crsdr_doa_last_submit.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(L, "crsdr_doa_set_peaks"):            # (likewise: an older build has the engine without the local-peak pass)
+        L.crsdr_doa_set_peaks.argtypes = [vp, C.c_int, C.c_int]
+        L.crsdr_doa_fetch_directions.argtypes = [vp, i32p, i32p, f32p]
+        L.crsdr_doa_direction_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     _lib = L
     return L
 
@@ -579,6 +584,7 @@ class Doa:
         self._h = h
         self.nrows, self.B, self.m, self.k, self.ncx, self.ncy = int(nrows), int(blocksize), int(nrows) - 1, int(k), int(ncx), int(ncy)
         self.max_batch, self.frames, self.flags = max(1, int(max_batch)), max(1, int(frames)), int(flags)
+        self.npeaks = 0
 
     def _last(self):
         nest, launches = C.c_int(0), C.c_int(0)
@@ -623,6 +629,25 @@ class Doa:
         ptrs = [C.c_void_p() for _ in range(5)]
         _check(lib().crsdr_doa_device_buffers(self._h, *[C.byref(p) for p in ptrs]))
         return dict(zip(("peak", "peak_value", "sv", "vec", "pm"), [p.value for p in ptrs]))
+
+    def set_peaks(self, count: int, radius: int = 1):
+        """crsdr_doa_set_peaks: from the next submit on, the `count` strongest local maxima of each spectrum within a
+        (2 radius + 1)^2 window (count = 0: off).  Waits for the device if a submit was made."""
+        _check(lib().crsdr_doa_set_peaks(self._h, int(count), int(radius)))
+        self.npeaks = int(count)
+
+    def fetch_directions(self) -> dict:
+        """Waits for the last submit.  found [nest], peaks [nest][count][2] (cx, cy), values [nest][count]; slots from found on hold
+        (-1, -1) and -1."""
+        n, c = self._last()[0], self.npeaks
+        found, peaks, values = np.zeros(n, dtype=np.int32), np.zeros((n, c, 2), dtype=np.int32), np.zeros((n, c), dtype=np.float32)
+        _check(lib().crsdr_doa_fetch_directions(self._h, _p(found, C.c_int32), _p(peaks, C.c_int32), _p(values, C.c_float)))
+        return {"found": found, "peaks": peaks, "values": values}
+
+    def direction_buffers(self) -> dict:
+        ptrs = [C.c_void_p() for _ in range(3)]
+        _check(lib().crsdr_doa_direction_buffers(self._h, *[C.byref(p) for p in ptrs]))
+        return dict(zip(("found", "peaks", "values"), [p.value for p in ptrs]))
 
     def last_launches(self) -> int:
         return self._last()[1]

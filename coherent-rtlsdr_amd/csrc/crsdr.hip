@@ -1791,7 +1791,7 @@ extern "C" int crsdr_plan_kernel_times(crsdr_plan *p, int which, float *ms, int 
 // (iv) batched direction-of-arrival engine (crsdr_doa): covariance -> noise subspace -> 2-D MUSIC scan + peak, one estimate per
 //      `frames` packets, for a whole batch of packets where a plan left them.  Every buffer is allocated at create; a submit is five
 //      launches on one stream whatever the batch size (covariance partials, their reducer, subspace, scan, peak), no lock, no
-//      allocation, no synchronisation.
+//      allocation, no synchronisation.  crsdr_doa_set_peaks allocates what the local-peak pass needs and adds its two launches.
 // ================================================================================================
 struct crsdr_doa {
     int nrows = 0, B = 0, m = 0, device = 0, max_batch = 1, frames = 1, k = 1, mx = 0, my = 0, ncx = 0, ncy = 0;
@@ -1808,13 +1808,29 @@ struct crsdr_doa {
     unsigned long long *d_wgbest = nullptr;
     int last_nest = 0, last_launches = 0;
     bool submitted = false;
+    // crsdr_doa_set_peaks: `npeaks` directions per estimate (0 = off), window radius, the spectrum workspace (without
+    // CRSDR_DOA_KEEP_SPECTRUM), the tiles' candidates [nest][tiles][npeaks] and the results; peaks_submitted: a submit since set_peaks
+    int npeaks = 0, radius = 0, lp_tiles = 0;
+    float *d_pmws = nullptr, *d_dirv = nullptr;
+    unsigned long long *d_cand = nullptr;
+    int32_t *d_found = nullptr, *d_dirs = nullptr;
+    bool peaks_submitted = false;
 };
+
+static void doa_free_peaks(crsdr_doa *q)
+{
+    void *bufs[] = {q->d_pmws, q->d_dirv, q->d_cand, q->d_found, q->d_dirs};
+    for (void *b : bufs) if (b) (void)hipFree(b);
+    q->d_pmws = q->d_dirv = nullptr; q->d_cand = nullptr; q->d_found = q->d_dirs = nullptr;
+    q->npeaks = q->radius = 0; q->peaks_submitted = false;
+}
 
 static void doa_free(crsdr_doa *q)
 {
     if (!q) return;
     (void)hipSetDevice(q->device);
     if (q->submitted) (void)hipDeviceSynchronize();      // (the last submit's stream may be the caller's, and gone)
+    doa_free_peaks(q);
     void *bufs[] = {q->d_partial, q->d_info, q->d_psum, q->d_rxx, q->d_vec, q->d_sv, q->d_peakv, q->d_pm, q->d_peak, q->d_wgbest};
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (q->own_stream) (void)hipStreamDestroy(q->own_stream);
@@ -1903,12 +1919,22 @@ static int doa_launch(crsdr_doa *q, const int8_t *packets, size_t packet_stride,
     HIP_TRY(hipGetLastError()); ++launches;
     hipLaunchKernelGGL(doa::k_doa_subspace, dim3(nest), dim3(music::JT), q->lds_sub, S, (const float2 *)q->d_rxx, q->m, q->d_sv, q->d_vec, q->d_info);
     HIP_TRY(hipGetLastError()); ++launches;
+    // with peaks on, the scan always leaves its spectrum: the kept one, or the workspace
+    float *pm = q->npeaks && !q->d_pm ? q->d_pmws : q->d_pm;
     hipLaunchKernelGGL(doa::k_doa_scan, dim3((unsigned)q->nwg, nest), dim3(music::PT), q->lds_scan, S, (const float2 *)q->d_vec, q->m, q->k, q->d, q->mx, q->my, q->ncx,
-                       q->ncy, q->d_pm, q->d_wgbest);
+                       q->ncy, pm, q->d_wgbest);
     HIP_TRY(hipGetLastError()); ++launches;
     hipLaunchKernelGGL(doa::k_doa_peak, dim3(nest), dim3(256), 0, S, (const unsigned long long *)q->d_wgbest, q->nwg, q->ncy, q->d_peak, q->d_peakv);
     HIP_TRY(hipGetLastError()); ++launches;
-    q->last_stream = S; q->last_nest = (int)nest; q->last_launches = launches; q->submitted = true;
+    if (q->npeaks) {
+        hipLaunchKernelGGL(doa::k_doa_local_peaks, dim3((unsigned)q->lp_tiles, nest), dim3(doa::LP_THREADS), doa::lp_lds(q->radius), S, (const float *)pm, q->ncx,
+                           q->ncy, q->radius, q->npeaks, q->d_cand);
+        HIP_TRY(hipGetLastError()); ++launches;
+        hipLaunchKernelGGL(doa::k_doa_peaks_merge, dim3(nest), dim3(doa::LP_THREADS), 0, S, (const unsigned long long *)q->d_cand, q->lp_tiles * q->npeaks, q->ncy,
+                           q->npeaks, q->d_found, q->d_dirs, q->d_dirv);
+        HIP_TRY(hipGetLastError()); ++launches;
+    }
+    q->last_stream = S; q->last_nest = (int)nest; q->last_launches = launches; q->submitted = true; q->peaks_submitted = q->npeaks > 0;
     return CRSDR_OK;
 }
 
@@ -1976,6 +2002,58 @@ extern "C" int crsdr_doa_last_submit(crsdr_doa *q, int *nest, int *launches)
     if (!q->submitted) return fail(CRSDR_ESTATE, "doa_last_submit: nothing submitted");
     if (nest) *nest = q->last_nest;
     if (launches) *launches = q->last_launches;
+    return CRSDR_OK;
+}
+
+static int doa_alloc_peaks(crsdr_doa *q, int count)
+{
+    const size_t nest = (size_t)(q->max_batch / q->frames), grid = (size_t)q->ncx * q->ncy;
+    q->lp_tiles = doa::lp_tiles(q->ncx, q->ncy);
+    if (!q->d_pm) HIP_TRY(hipMalloc((void **)&q->d_pmws, sizeof(float) * nest * grid));
+    HIP_TRY(hipMalloc((void **)&q->d_cand, sizeof(unsigned long long) * nest * q->lp_tiles * count));
+    HIP_TRY(hipMalloc((void **)&q->d_found, sizeof(int32_t) * nest));
+    HIP_TRY(hipMalloc((void **)&q->d_dirs, sizeof(int32_t) * nest * count * 2));
+    HIP_TRY(hipMalloc((void **)&q->d_dirv, sizeof(float) * nest * count));
+    HIP_TRY(hipFuncSetAttribute((const void *)doa::k_doa_local_peaks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)doa::lp_lds(doa::MAX_RADIUS)));
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_set_peaks(crsdr_doa *q, int count, int radius)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_set_peaks: NULL doa");
+    if (count < 0 || count > doa::MAX_PEAKS) return fail(CRSDR_EINVAL, "doa_set_peaks: count = %d (0..%d)", count, doa::MAX_PEAKS);
+    if (count > 0 && (radius < 1 || radius > doa::MAX_RADIUS)) return fail(CRSDR_EINVAL, "doa_set_peaks: radius = %d (1..%d)", radius, doa::MAX_RADIUS);
+    HIP_TRY(hipSetDevice(q->device));
+    if (q->submitted) HIP_TRY(hipDeviceSynchronize());   // the buffers may be in use (the last submit's stream may be the caller's, and gone)
+    doa_free_peaks(q);
+    if (count == 0) return CRSDR_OK;
+    const int rc = doa_alloc_peaks(q, count);
+    if (rc) { doa_free_peaks(q); return rc; }
+    q->npeaks = count; q->radius = radius;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_fetch_directions(crsdr_doa *q, int32_t *found, int32_t *peaks, float *values)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_fetch_directions: NULL doa");
+    if (!q->npeaks) return fail(CRSDR_ESTATE, "doa_fetch_directions: no crsdr_doa_set_peaks");
+    if (!q->peaks_submitted) return fail(CRSDR_ESTATE, "doa_fetch_directions: nothing submitted since crsdr_doa_set_peaks");
+    HIP_TRY(hipSetDevice(q->device));
+    const size_t nest = (size_t)q->last_nest, c = (size_t)q->npeaks;
+    hipStream_t S = q->last_stream;
+    if (found) HIP_TRY(hipMemcpyAsync(found, q->d_found, sizeof(int32_t) * nest, hipMemcpyDeviceToHost, S));
+    if (peaks) HIP_TRY(hipMemcpyAsync(peaks, q->d_dirs, sizeof(int32_t) * nest * c * 2, hipMemcpyDeviceToHost, S));
+    if (values) HIP_TRY(hipMemcpyAsync(values, q->d_dirv, sizeof(float) * nest * c, hipMemcpyDeviceToHost, S));
+    HIP_TRY(hipStreamSynchronize(S));
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_direction_buffers(crsdr_doa *q, void **found, void **peaks, void **values)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_direction_buffers: NULL doa");
+    if (found) *found = q->d_found;
+    if (peaks) *peaks = q->d_dirs;
+    if (values) *values = q->d_dirv;
     return CRSDR_OK;
 }
 

@@ -234,5 +234,134 @@ __global__ __launch_bounds__(256) void k_doa_peak(const unsigned long long *__re
     }
 }
 
+// ---- several directions per estimate (crsdr_doa_set_peaks): the `count` largest local maxima of each spectrum ----
+// Point g is a local peak if its key beats every other key in the (2r+1) x (2r+1) window around it, clipped at the grid's edges.  Keys
+// are unique, so that is "its key is the window's maximum", and the maximum of a rectangle is the maximum over its rows of each row's
+// maximum: 2 (2r + 1) comparisons per point instead of (2r + 1)^2.  Key 0 would need index 0xFFFFFFFF (grids hold at most 2^24 points):
+// it stands for "no point", both outside the grid and in an empty candidate slot.
+constexpr int LP_TX = 16, LP_TY = 64, LP_THREADS = 256, LP_PER_THREAD = LP_TX * LP_TY / LP_THREADS;      // a tile: 16 rows of 64 points
+constexpr int MAX_PEAKS = 16, MAX_RADIUS = 16;
+
+__host__ __device__ constexpr int lp_tiles(int Cx, int Cy) { return ((Cx + LP_TX - 1) / LP_TX) * ((Cy + LP_TY - 1) / LP_TY); }
+__host__ __device__ constexpr size_t lp_lds(int r)
+{
+    return sizeof(unsigned long long) * ((size_t)(LP_TX + 2 * r) * (LP_TY + 2 * r) + (size_t)(LP_TX + 2 * r) * LP_TY);
+}
+
+// the largest `key` of the workgroup (LP_THREADS threads), in every thread; red [LP_THREADS / 64] is free again on return
+__device__ __forceinline__ unsigned long long lp_block_max(unsigned long long key, unsigned long long *red)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned long long o = shfl_xor_u64(key, off);
+        key = o > key ? o : key;
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = key;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < LP_THREADS / 64; ++w) key = red[w] > key ? red[w] : key;
+    __syncthreads();
+    return key;
+}
+
+// Rounds of max-and-remove over the keys a thread holds: round i takes the largest key below the one taken in round i - 1 (keys are
+// unique), thread i keeps it.  Ends early once nothing is left (the round's maximum is the same in every thread).  Returns the number taken.
+template <int N>
+__device__ __forceinline__ int lp_top(const unsigned long long (&keys)[N], int count, unsigned long long *red, unsigned long long &mine)
+{
+    unsigned long long last = ~0ull;
+    int n = 0;
+    mine = 0;
+    for (; n < count; ++n) {
+        unsigned long long best = 0;
+#pragma unroll
+        for (int u = 0; u < N; ++u) best = keys[u] < last && keys[u] > best ? keys[u] : best;
+        best = lp_block_max(best, red);
+        if (best == 0) break;
+        if ((int)threadIdx.x == n) mine = best;
+        last = best;
+    }
+    return n;
+}
+
+// grid (lp_tiles(Cx, Cy), nest), LP_THREADS threads, lp_lds(r) bytes of dynamic LDS.  pm [nest][Cx][Cy];
+// cand [nest][tiles][count]: the tile's local peaks, the `count` largest keys in descending order, then 0.
+__global__ __launch_bounds__(LP_THREADS) void k_doa_local_peaks(const float *__restrict__ pm, int Cx, int Cy, int r, int count,
+                                                                unsigned long long *__restrict__ cand)
+{
+    extern __shared__ unsigned long long lpk[];
+    __shared__ unsigned long long red[LP_THREADS / 64];
+    const int tid = threadIdx.x, tiles_y = (Cy + LP_TY - 1) / LP_TY;
+    const size_t e = blockIdx.y;
+    const int x0 = (int)(blockIdx.x / tiles_y) * LP_TX, y0 = (int)(blockIdx.x % tiles_y) * LP_TY;
+    const int HX = LP_TX + 2 * r, HY = LP_TY + 2 * r;
+    unsigned long long *key = lpk;                  // [HX][HY]: the keys of the tile and its r-wide halo, 0 outside the grid
+    unsigned long long *hmax = lpk + HX * HY;       // [HX][LP_TY]: the largest key of each row's window
+    const float *p = pm + e * Cx * Cy;
+    // row segments of the halo'd tile: consecutive threads read consecutive points of a row
+    for (int i = tid; i < HX * HY; i += LP_THREADS) {
+        const int hx = i / HY, cx = x0 - r + hx, cy = y0 - r + (i - hx * HY);
+        key[i] = cx >= 0 && cx < Cx && cy >= 0 && cy < Cy ? peak_key(p[(size_t)cx * Cy + cy], cx * Cy + cy) : 0ull;
+    }
+    __syncthreads();
+    for (int i = tid; i < HX * LP_TY; i += LP_THREADS) {
+        const int hx = i / LP_TY;
+        const unsigned long long *row = key + hx * HY + (i - hx * LP_TY);
+        unsigned long long m = row[0];
+        for (int j = 1; j <= 2 * r; ++j) m = row[j] > m ? row[j] : m;
+        hmax[i] = m;
+    }
+    __syncthreads();
+    unsigned long long mine[LP_PER_THREAD];
+#pragma unroll
+    for (int u = 0; u < LP_PER_THREAD; ++u) {
+        const int i = tid + u * LP_THREADS, x = i / LP_TY, y = i - x * LP_TY;
+        const unsigned long long k = key[(x + r) * HY + y + r];
+        unsigned long long m = hmax[x * LP_TY + y];
+        for (int j = 1; j <= 2 * r; ++j) m = hmax[(x + j) * LP_TY + y] > m ? hmax[(x + j) * LP_TY + y] : m;
+        mine[u] = m == k ? k : 0ull;                 // (k = 0: a point of the tile outside the grid)
+    }
+    unsigned long long top;
+    lp_top(mine, count, red, top);
+    if (tid < count) cand[(e * gridDim.x + blockIdx.x) * count + tid] = top;
+}
+
+// grid (nest), LP_THREADS threads: the `count` largest of the ncand = tiles * count candidates of an estimate ->
+// found [nest], peaks [nest][count][2] = (cx, cy), values [nest][count]; the slots after found hold (-1, -1) and -1.
+__global__ __launch_bounds__(LP_THREADS) void k_doa_peaks_merge(const unsigned long long *__restrict__ cand, int ncand, int Cy, int count,
+                                                                int32_t *__restrict__ found, int32_t *__restrict__ peaks,
+                                                                float *__restrict__ values)
+{
+    __shared__ unsigned long long red[LP_THREADS / 64];
+    const size_t e = blockIdx.x;
+    const unsigned long long *c = cand + e * ncand;
+    const int tid = threadIdx.x;
+    // most grids leave at most a few candidates per thread (100 x 100: 14 tiles); a larger one is folded down to LP_MERGE keys per thread
+    // first, each thread keeping the largest LP_MERGE of its strided share -- which holds every one of its keys that can be among the
+    // workgroup's `count` largest only if LP_MERGE >= count, so LP_MERGE = MAX_PEAKS
+    constexpr int LP_MERGE = MAX_PEAKS;
+    unsigned long long keys[LP_MERGE];
+#pragma unroll
+    for (int u = 0; u < LP_MERGE; ++u) keys[u] = 0;
+    for (int j = tid; j < ncand; j += LP_THREADS) {
+        unsigned long long o = c[j];
+#pragma unroll
+        for (int u = 0; u < LP_MERGE; ++u) {      // insertion into the descending list keys[]
+            const unsigned long long hi = keys[u] > o ? keys[u] : o, lo = keys[u] > o ? o : keys[u];
+            keys[u] = hi; o = lo;
+        }
+    }
+    unsigned long long mine;
+    const int n = lp_top(keys, count, red, mine);
+    if (tid < count) {
+        const int g = (int)(0xFFFFFFFFu - (uint32_t)mine);
+        const size_t s = e * count + tid;
+        peaks[2 * s] = mine ? g / Cy : -1;
+        peaks[2 * s + 1] = mine ? g - (g / Cy) * Cy : -1;
+        values[s] = mine ? __uint_as_float((uint32_t)(mine >> 32)) : -1.0f;
+    }
+    if (tid == 0) found[e] = n;
+}
+
 } // namespace doa
 } // namespace crsdr

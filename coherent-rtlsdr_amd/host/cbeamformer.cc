@@ -65,6 +65,14 @@ int batch::submit(const void *device_packets, size_t packet_stride, size_t matri
     return rc;
 }
 
+int batch::set_peaks(int count, int radius)
+{
+    int rc = doa ? crsdr_doa_set_peaks(doa, count, radius) : CRSDR_ESTATE;
+    if (!rc) npeaks = count;
+    if (rc && doa) std::fprintf(stderr, "cbeamformer::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
 int batch::fetch()
 {
     int nest = 0;
@@ -73,6 +81,10 @@ int batch::fetch()
         peak.assign(2 * (size_t)nest, 0); peak_value.assign(nest, 0.f); sv.assign((size_t)nest * m, 0.f); status.assign(nest, 0);
         if (keep) pm.assign((size_t)nest * cx * cy, 0.f);
         rc = crsdr_doa_fetch(doa, peak.data(), peak_value.data(), sv.data(), status.data(), keep ? pm.data() : nullptr, nullptr);
+    }
+    if (!rc && npeaks) {
+        found.assign(nest, 0); directions.assign((size_t)nest * npeaks * 2, -1); direction_values.assign((size_t)nest * npeaks, -1.f);
+        rc = crsdr_doa_fetch_directions(doa, found.data(), directions.data(), direction_values.data());
     }
     if (rc && doa) std::fprintf(stderr, "cbeamformer::batch: %s\n", crsdr_last_error());
     return rc;

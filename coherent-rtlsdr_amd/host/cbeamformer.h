@@ -30,7 +30,7 @@ int pmusic2dvec(const cmatrix &U, int M, int K, float d, int Mx, int My, int Cx,
 // it reads); fetch() waits and fills the vectors below.  One submit at a time: fetch before the next.
 class batch {
     crsdr_doa *doa = nullptr;
-    int m = 0, cx = 0, cy = 0;
+    int m = 0, cx = 0, cy = 0, npeaks = 0;
     bool keep = false;
 public:
     // nrows x blocksize: the packets' geometry (1 + Mx * My rows); keep_spectrum: fetch() also fills pm
@@ -42,11 +42,18 @@ public:
     bool ok() const { return doa != nullptr; }
     int submit(crsdr_plan *plan);                    // the plan's last submitted batch
     int submit(const void *device_packets, size_t packet_stride, size_t matrix_offset, int nblocks, void *hip_stream = nullptr);
+    // from the next submit on, the `count` strongest local maxima of each spectrum within a (2 radius + 1)^2 window as well
+    // (crsdr_doa_set_peaks; count = 0: off).  Waits for the device if a submit was made.
+    int set_peaks(int count, int radius = 1);
     int fetch();
     int estimates() const { return (int)status.size(); }
     std::vector<int32_t> peak;                       // [estimates][2]: (cx, cy) of the largest pm
     std::vector<float> peak_value, sv, pm;           // [estimates], [estimates][M], [estimates][Cx][Cy] (keep_spectrum)
     std::vector<int32_t> status;                     // 0 = converged
+    // with set_peaks: local peaks found per estimate (<= count), their (cx, cy) [estimates][count][2] in descending order and their pm
+    // [estimates][count]; slots from found on hold (-1, -1) and -1
+    std::vector<int32_t> found, directions;
+    std::vector<float> direction_values;
 };
 }
 #endif

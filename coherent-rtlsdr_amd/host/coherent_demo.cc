@@ -55,7 +55,7 @@ int main(int argc, char **argv)
     int nsig = 3, L = 8192, blocks = 12, mode = CRSDR_MODE_DIGITAL, dmax = -1;
     std::string dump, zmqaddr;
     bool run_cdsp = false, servo = false, threads = false, music = false, servo_table = false, bench = false, batch_parity = false, batched = false;
-    int batch = 16, engine_delay_ms = 0, pace_us_arg = -1;
+    int batch = 16, engine_delay_ms = 0, pace_us_arg = -1, peaks = 0, peak_radius = 1;
     bool engine_batches = false;
     int ranks = 1, rank = 0, device = 0;
     std::string idfile;
@@ -83,6 +83,8 @@ int main(int argc, char **argv)
         else if (a == "--fs") val(table_fs);
         else if (a == "--bench") bench = true;      // pipelined batched engine over PCIe: blocks/s from C++, no Python in the loop
         else if (a == "--batch") val(batch);
+        else if (a == "--peaks") val(peaks);                   // with --bench --music: that many directions per estimate (crsdr_doa_set_peaks)
+        else if (a == "--peak-radius") val(peak_radius);
         else if (a == "--batch-parity") batch_parity = true;   // the batched engine's packets == step()'s packets, bit for bit (own read counters, a masked row)
         else if (a == "--batched") batched = true;             // with --threads: the engine thread runs a batch at a time (ccoherent::start_batched)
         else if (a == "--engine-delay-ms") val(engine_delay_ms);
@@ -282,6 +284,7 @@ int main(int argc, char **argv)
         if (music && !coherent.sharded()) {
             doa.reset(new cbeamformer::batch(1 + nsig, B, batch));
             if (nsig != cbeamformer::MX * cbeamformer::MY || !doa->ok()) { std::printf("doa: unavailable (needs --nsig 21)\nDEMO FAILED\n"); return 1; }
+            if (peaks && doa->set_peaks(peaks, peak_radius)) { std::printf("doa: --peaks %d --peak-radius %d refused\nDEMO FAILED\n", peaks, peak_radius); return 1; }
         }
         bool report = false;
         auto directions = [&](int b) {
@@ -289,6 +292,17 @@ int main(int argc, char **argv)
             ok = doa->submit(coherent.engine_plan()) == CRSDR_OK && doa->fetch() == CRSDR_OK;
             if (!ok || !report) return;
             const int n = doa->estimates();
+            if (peaks) {
+                // the first estimate's local peaks, strongest first
+                std::string dirs;
+                char buf[32];
+                for (int i = 0; i < doa->found[0]; ++i) {
+                    std::snprintf(buf, sizeof(buf), " (%d, %d)", doa->directions[2 * i], doa->directions[2 * i + 1]);
+                    dirs += buf;
+                }
+                std::printf("doa: batch %d: %d estimates, peaks of the first:%s\n", b, n, dirs.c_str());
+                return;
+            }
             int broadside = 0;
             for (int e = 0; e < n; ++e) broadside += doa->peak[2 * e] == 50 && doa->peak[2 * e + 1] == 50;
             std::printf("doa: batch %d: %d directions, first (%d, %d), last (%d, %d), %d at broadside\n", b, n, doa->peak[0], doa->peak[1], doa->peak[2 * n - 2],

@@ -426,7 +426,7 @@ int crsdr_pmusic2d(float *pm, const float *vec, int m, int k, float d, int mx, i
 
 /* crsdr_covariance -> crsdr_noisesubspace -> crsdr_pmusic2d -> index of the largest pm, for up to 64 packets per submit, one estimate
  * per `frames` consecutive packets (their samples stacked, X = [X; Xc] as measurement_script.m does: L = frames * blocksize / 2).
- * Every buffer is allocated by crsdr_doa_create.  A submit is asynchronous on its stream: five kernel launches whatever the
+ * Every buffer is allocated by crsdr_doa_create (or crsdr_doa_set_peaks).  A submit is asynchronous on its stream: five kernel launches whatever the
  * number of blocks, no allocation, no process-wide lock, nothing that waits for the device.  Per estimate the numbers are those of
  * the per-op calls on the same matrix, bit for bit (exact integer sums with the same fp64 epilogue; the same instruction sequence
  * for the subspace and for every grid point). */
@@ -483,6 +483,27 @@ int crsdr_doa_device_buffers(crsdr_doa *doa, void **peak, void **peak_value, voi
 /* Of the last submit: the number of estimates (what crsdr_doa_fetch will write) and the kernel launches it issued (the same for
  * every nblocks).  Either pointer may be NULL.  CRSDR_ESTATE before the first submit. */
 int crsdr_doa_last_submit(crsdr_doa *doa, int *nest, int *launches);
+
+/* Several directions per estimate: the `count` strongest local maxima of each spectrum, found on the device.  Grid point
+ * g = cx * ncy + cy has the key (bits(pm) << 32) | (0xFFFFFFFF - g) (a NaN pm as 0x7FC00000, as for peak); it is a local peak if its
+ * key is larger than that of every other grid point with |cx' - cx| <= radius and |cy' - cy| <= radius (the window clipped at the
+ * grid's edges, no wrap-around).  The global maximum is always one, so the first direction is crsdr_doa_fetch's peak, bit for bit.
+ * 1 <= count <= 16, 1 <= radius <= 16; count = 0 turns the pass off (radius is then ignored).  Any time: waits for the device if a
+ * submit was made, then allocates what the pass needs (a spectrum workspace [max_batch / frames][ncx][ncy] float unless the object
+ * keeps the spectrum).  A submit with peaks on is seven launches instead of five, the same for every nblocks.  CRSDR_EINVAL for a
+ * bad count or radius. */
+int crsdr_doa_set_peaks(crsdr_doa *doa, int count, int radius);
+
+/* Waits for the last submit and copies out (any pointer may be NULL), nest as for crsdr_doa_fetch:
+ *   found  [nest]            local peaks found, at most count
+ *   peaks  [nest][count][2]  (cx, cy) in descending key order: descending pm, the lower row-major index first on ties
+ *   values [nest][count]     their pm
+ * Slots from found on hold (-1, -1) and -1.0f.  CRSDR_ESTATE without crsdr_doa_set_peaks or before the first submit after it. */
+int crsdr_doa_fetch_directions(crsdr_doa *doa, int32_t *found, int32_t *peaks, float *values);
+
+/* Device addresses of found, peaks and values ([max_batch / frames] estimates, laid out as above; NULL while peaks are off), for
+ * consumers on the same stream.  They change with every crsdr_doa_set_peaks. */
+int crsdr_doa_direction_buffers(crsdr_doa *doa, void **found, void **peaks, void **values);
 
 #ifdef __cplusplus
 }

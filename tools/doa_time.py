@@ -5,9 +5,12 @@
       (pm stays on the device: finding its peak is not even in the figure).  Run in a worker of its own, so that it can load an older
       build of the library (--perop-lib, e.g. the parent commit's) through CRSDR_LIB.
   (b) crsdr_doa_submit of the 64 packets + a fetch of the peaks only,
-  (c) the same with the spectra kept and fetched (64 x 40 KB).
+  (c) the same with the spectra kept and fetched (64 x 40 KB),
+  (p) with --peaks COUNT --radius R: crsdr_doa_set_peaks(COUNT, R), then the submit + crsdr_doa_fetch_directions (the local-peak pass).
 
 --runs runs of each, alternating a, b, c in one session (two worker processes, both alive throughout); medians and ranges.
+--doa-lib LIB starts a second doa worker on another build (e.g. the parent commit's) through CRSDR_LIB and times its (b) and (c) in
+the same alternation, reported as lib:b and lib:c.  --reps N: every (b), (c), (p) figure is the mean of N back-to-back submit + fetch.
 Also: what crsdr_doa_submit_plan + the peak fetch add to a 22-row, T = 64 plan batch (plan.submit + sync against
 plan.submit + doa.submit_plan + fetch).  --json FILE keeps the record; --once MODE runs one submit + fetch and exits (for a kernel trace)."""
 import argparse, importlib, json, os, subprocess, sys, time
@@ -59,22 +62,33 @@ def worker_perop():
         print(time.perf_counter() - t0, flush=True)
 
 
-def worker_doa():
-    """(b), (c) and the plan figures: 'b' / 'c' / 'plan' / 'plan+doa' on stdin -> seconds of one batch of 64 on stdout."""
+def worker_doa(npeaks=0, radius=1, reps=1):
+    """(b), (c), (p) and the plan figures: 'b' / 'c' / 'p' / 'plan' / 'plan+doa' on stdin -> seconds of one batch of 64 on stdout."""
     torch, ura, b, dev, pk, off, stride, host = _setup()
     peaks = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
     full = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T, flags=b.DOA_KEEP_SPECTRUM)
     plan = b.Plan(NROWS, B, b.MODE_DIGITAL, max_batch=T)
     rows = torch.from_numpy(np.ascontiguousarray(host[:, off:])).to(dev)       # [T][nrows * B], the plan's device input
     pdoa = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
+    dirs = None
+    if npeaks:
+        dirs = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
+        dirs.set_peaks(npeaks, radius)
 
     def run_b():
-        peaks.submit(pk.data_ptr(), stride, off, T)
-        return peaks.fetch_peaks()
+        for _ in range(reps):
+            peaks.submit(pk.data_ptr(), stride, off, T)
+            peaks.fetch_peaks()
 
     def run_c():
-        full.submit(pk.data_ptr(), stride, off, T)
-        return full.fetch()
+        for _ in range(reps):
+            full.submit(pk.data_ptr(), stride, off, T)
+            full.fetch()
+
+    def run_p():
+        for _ in range(reps):
+            dirs.submit(pk.data_ptr(), stride, off, T)
+            dirs.fetch_directions()
 
     def run_plan(n=10):
         for i in range(n):
@@ -87,7 +101,9 @@ def worker_doa():
             pdoa.submit_plan(plan)
             pdoa.fetch_peaks()
         plan.sync()
-    jobs = {"b": (run_b, 1), "c": (run_c, 1), "plan": (run_plan, 10), "plan+doa": (run_plan_doa, 10)}
+    jobs = {"b": (run_b, reps), "c": (run_c, reps), "plan": (run_plan, 10), "plan+doa": (run_plan_doa, 10)}
+    if dirs is not None:
+        jobs["p"] = (run_p, reps)
     for f, _ in jobs.values():
         f()
     print("ready", flush=True)
@@ -98,22 +114,26 @@ def worker_doa():
         print((time.perf_counter() - t0) / n, flush=True)
 
 
-def once(mode):
+def once(mode, npeaks=0, radius=1):
     torch, ura, b, dev, pk, off, stride, _ = _setup()
     d = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T, flags=b.DOA_KEEP_SPECTRUM if mode == "c" else 0)
+    if mode == "p":
+        d.set_peaks(npeaks, radius)
     for _ in range(3):
         d.submit(pk.data_ptr(), stride, off, T)
         out = d.fetch()
     print("peaks", out["peak"][:4].tolist(), "launches", d.last_launches())
+    if mode == "p":
+        print("directions of the first", d.fetch_directions()["peaks"][0].tolist())
 
 
 class Worker:
-    def __init__(self, mode, lib=None):
+    def __init__(self, mode, lib=None, extra=()):
         env = dict(os.environ)
         if lib:
             env["CRSDR_LIB"] = lib
-        self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", mode], stdin=subprocess.PIPE, stdout=subprocess.PIPE,
-                                  text=True, env=env)
+        self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", mode, *extra], stdin=subprocess.PIPE,
+                                  stdout=subprocess.PIPE, text=True, env=env)
         line = self.p.stdout.readline().strip()
         if line != "ready":
             raise RuntimeError(f"worker {mode} did not start: {line!r} (exit {self.p.poll()})")
@@ -137,33 +157,50 @@ def _stat(xs):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--worker", choices=["perop", "doa"])
-    ap.add_argument("--once", choices=["b", "c"])
+    ap.add_argument("--once", choices=["b", "c", "p"])
     ap.add_argument("--perop-lib", default=None, help="library for (a), e.g. a build of the parent commit (default: the current one)")
+    ap.add_argument("--doa-lib", default=None, help="a second library whose (b) and (c) are timed in the same alternation (lib:b, lib:c)")
+    ap.add_argument("--peaks", type=int, default=0, help="(p): directions per estimate (crsdr_doa_set_peaks count; 0 = no (p))")
+    ap.add_argument("--radius", type=int, default=1, help="(p): the local-peak window's radius")
+    ap.add_argument("--reps", type=int, default=1, help="submit + fetch pairs per (b), (c), (p) figure")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     if a.worker:
-        return worker_perop() if a.worker == "perop" else worker_doa()
+        return worker_perop() if a.worker == "perop" else worker_doa(a.peaks, a.radius, a.reps)
     if a.once:
-        return once(a.once)
-    wa, wb = Worker("perop", a.perop_lib), Worker("doa")
-    sec = {k: [] for k in ("a", "b", "c", "plan", "plan+doa")}
+        return once(a.once, a.peaks, a.radius)
+    pargs = ["--peaks", str(a.peaks), "--radius", str(a.radius), "--reps", str(a.reps)]
+    wa, wb = Worker("perop", a.perop_lib), Worker("doa", extra=pargs)
+    wl = Worker("doa", a.doa_lib, extra=["--reps", str(a.reps)]) if a.doa_lib else None
+    keys = ["a", "b", "c", "plan", "plan+doa"] + (["lib:b", "lib:c"] if wl else []) + (["p"] if a.peaks else [])
+    sec = {k: [] for k in keys}
     try:
         for _ in range(a.runs):
             sec["a"].append(wa.run())
             sec["b"].append(wb.run("b"))
+            if wl:
+                sec["lib:b"].append(wl.run("b"))
             sec["c"].append(wb.run("c"))
+            if wl:
+                sec["lib:c"].append(wl.run("c"))
+            if a.peaks:
+                sec["p"].append(wb.run("p"))
             sec["plan"].append(wb.run("plan"))
             sec["plan+doa"].append(wb.run("plan+doa"))
     finally:
         wa.close(); wb.close()
-    rec = {"shape": {"nrows": NROWS, "blocksize": B, "blocks": T, "grid": [100, 100]}, "runs": a.runs,
-           "perop_lib": a.perop_lib or "current build", "ms_per_batch": {k: _stat([1e3 * x for x in v]) for k, v in sec.items()},
+        if wl:
+            wl.close()
+    rec = {"shape": {"nrows": NROWS, "blocksize": B, "blocks": T, "grid": [100, 100]}, "runs": a.runs, "reps": a.reps,
+           "perop_lib": a.perop_lib or "current build", "doa_lib": a.doa_lib, "peaks": {"count": a.peaks, "radius": a.radius} if a.peaks else None,
+           "ms_per_batch": {k: _stat([1e3 * x for x in v]) for k, v in sec.items()},
            "frames_per_s": {k: _stat([T / x for x in sec[k]]) for k in ("a", "b", "c")}}
     rec["b_faster_than_a_ranges_disjoint"] = rec["ms_per_batch"]["b"]["max"] < rec["ms_per_batch"]["a"]["min"]
     rec["submit_plan_adds_ms_per_batch"] = rec["ms_per_batch"]["plan+doa"]["median"] - rec["ms_per_batch"]["plan"]["median"]
     names = {"a": "per-op loop, device pointers", "b": "doa submit + peaks", "c": "doa submit + peaks + spectra",
-             "plan": "plan batch alone", "plan+doa": "plan batch + submit_plan + peaks"}
+             "plan": "plan batch alone", "plan+doa": "plan batch + submit_plan + peaks", "lib:b": "--doa-lib: submit + peaks",
+             "lib:c": "--doa-lib: submit + peaks + spectra", "p": f"set_peaks({a.peaks}, {a.radius}): submit + directions"}
     for k, s in rec["ms_per_batch"].items():
         fps = f"  {T / (1e-3 * s['median']):10.0f} frames/s" if k in rec["frames_per_s"] else ""
         print(f"({k}) {names[k]:34s} {s['median']:8.3f} ms per 64 blocks  [{s['min']:.3f} .. {s['max']:.3f}]{fps}")
