@@ -37,8 +37,10 @@ ABI_SYMBOLS = [
     "crsdr_doa_create", "crsdr_doa_destroy", "crsdr_doa_submit", "crsdr_doa_submit_plan", "crsdr_doa_fetch",
     "crsdr_doa_device_buffers", "crsdr_doa_last_submit", "crsdr_doa_set_peaks", "crsdr_doa_fetch_directions",
     "crsdr_doa_direction_buffers",
+    "crsdr_beamform", "crsdr_doa_set_beams", "crsdr_doa_fetch_beams", "crsdr_doa_beam_buffers", "crsdr_doa_fetch_subspace",
 ]
 DOA_KEEP_SPECTRUM, DOA_KEEP_RXX = 1, 2
+BEAM_OFF, BEAM_CONVENTIONAL, BEAM_MVDR = 0, 1, 2
 XCHG_STAGED, XCHG_INPLACE = 0, 1
 EXCHANGE_ID_BYTES = 128
 KERNEL_REF_SPECTRUM, KERNEL_XCORR_LAG, KERNEL_PHASE_DOT, KERNEL_ALIGN_QUANT = 0, 1, 2, 3
@@ -165,6 +167,12 @@ def lib():
         L.crsdr_doa_set_peaks.argtypes = [vp, C.c_int, C.c_int]
         L.crsdr_doa_fetch_directions.argtypes = [vp, i32p, i32p, f32p]
         L.crsdr_doa_direction_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    if hasattr(L, "crsdr_doa_set_beams"):            # (likewise: an older build has no beams)
+        L.crsdr_beamform.argtypes = [f32p, i8p, C.c_int, C.c_int, f32p, C.c_int, C.c_int]
+        L.crsdr_doa_set_beams.argtypes = [vp, C.c_int, C.c_float, C.c_int, f32p]
+        L.crsdr_doa_fetch_beams.argtypes = [vp, f32p, f32p, f32p]
+        L.crsdr_doa_beam_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int)]
+        L.crsdr_doa_fetch_subspace.argtypes = [vp, f32p]
     _lib = L
     return L
 
@@ -325,6 +333,19 @@ def pmusic2d(vec, k, d, mx, my, ncx=100, ncy=100):
     _check(lib().crsdr_pmusic2d(_p(pm, C.c_float), _p(v.view(np.float32), C.c_float), M, int(k), C.c_float(d), int(mx), int(my),
                                 int(ncx), int(ncy), MEM_HOST))
     return pm
+
+
+def beamform(matrix, weights):
+    """crsdr_beamform: out [nbeams][B / 2] complex64 = weights [nbeams][nrows - 1] applied to the signal rows of matrix [nrows][B] int8
+    (sum_c u[c - 1] (I_c + j Q_c) / 127, no conjugate): the batched engine's beam arithmetic on one matrix."""
+    m = np.ascontiguousarray(matrix, dtype=np.int8)
+    w = np.ascontiguousarray(weights, dtype=np.complex64)
+    nrows, B = m.shape
+    if w.ndim != 2 or w.shape[1] != nrows - 1:
+        raise ValueError("weights must be [nbeams][nrows - 1]")
+    out = np.empty((w.shape[0], B // 2), dtype=np.complex64)
+    _check(lib().crsdr_beamform(_p(out.view(np.float32), C.c_float), _p(m, C.c_int8), nrows, B, _p(w.view(np.float32), C.c_float), w.shape[0], MEM_HOST))
+    return out
 
 
 def assemble_slabs(packets_ptr: int, packet_stride: int, nrows: int, B: int, recv_ptr: int, nsrc: int, nblocks: int, stream: int | None = None):
@@ -584,7 +605,7 @@ class Doa:
         self._h = h
         self.nrows, self.B, self.m, self.k, self.ncx, self.ncy = int(nrows), int(blocksize), int(nrows) - 1, int(k), int(ncx), int(ncy)
         self.max_batch, self.frames, self.flags = max(1, int(max_batch)), max(1, int(frames)), int(flags)
-        self.npeaks = 0
+        self.npeaks, self.nbeams = 0, 0
 
     def _last(self):
         nest, launches = C.c_int(0), C.c_int(0)
@@ -648,6 +669,36 @@ class Doa:
         ptrs = [C.c_void_p() for _ in range(3)]
         _check(lib().crsdr_doa_direction_buffers(self._h, *[C.byref(p) for p in ptrs]))
         return dict(zip(("found", "peaks", "values"), [p.value for p in ptrs]))
+
+    def set_beams(self, mode: int, loading: float = 1e-2, fixed_angles=None):
+        """crsdr_doa_set_beams: from the next submit on, weights, power and one IQ stream per direction (BEAM_CONVENTIONAL / BEAM_MVDR;
+        BEAM_OFF frees them).  fixed_angles [n][2] (alpha, beta) in radians: those directions for every estimate; None: the estimate's
+        own (set_peaks' count of them, or the peak).  Waits for the device if a submit was made."""
+        fa = None if fixed_angles is None else np.ascontiguousarray(fixed_angles, dtype=np.float32).reshape(-1, 2)
+        _check(lib().crsdr_doa_set_beams(self._h, int(mode), C.c_float(loading), 0 if fa is None else fa.shape[0], _p(fa, C.c_float)))
+        self.nbeams = self.beam_buffers()["nbeams"]
+
+    def fetch_beams(self, weights=True, power=True, beams=True) -> dict:
+        """Waits for the last submit.  weights [nest][nbeams][m] complex64, power [nest][nbeams], beams [nblocks][nbeams][B / 2]
+        complex64 (each only if asked for)."""
+        n, nb = self._last()[0], self.nbeams
+        w = np.zeros((n, nb, self.m), dtype=np.complex64) if weights else None
+        pw = np.zeros((n, nb), dtype=np.float32) if power else None
+        y = np.zeros((n * self.frames, nb, self.B // 2), dtype=np.complex64) if beams else None
+        _check(lib().crsdr_doa_fetch_beams(self._h, _p(None if w is None else w.view(np.float32), C.c_float), _p(pw, C.c_float),
+                                           _p(None if y is None else y.view(np.float32), C.c_float)))
+        return {k: v for k, v in (("weights", w), ("power", pw), ("beams", y)) if v is not None}
+
+    def beam_buffers(self) -> dict:
+        ptrs, nb = [C.c_void_p() for _ in range(3)], C.c_int(0)
+        _check(lib().crsdr_doa_beam_buffers(self._h, *[C.byref(p) for p in ptrs], C.byref(nb)))
+        return dict(zip(("weights", "power", "beams"), [p.value for p in ptrs]), nbeams=nb.value)
+
+    def fetch_subspace(self) -> np.ndarray:
+        """vec [nest][m][m] complex64 of the last submit (column r of vec[e] = the singular vector of sv[e][r])."""
+        vec = np.zeros((self._last()[0], self.m, self.m), dtype=np.complex64)
+        _check(lib().crsdr_doa_fetch_subspace(self._h, _p(vec.view(np.float32), C.c_float)))
+        return vec
 
     def last_launches(self) -> int:
         return self._last()[1]

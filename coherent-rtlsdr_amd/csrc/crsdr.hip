@@ -4,6 +4,7 @@
 #include "../../include/crsdr.h"
 #include "kernels.hpp"
 #include "doa.hpp"
+#include "beams.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -1791,7 +1792,8 @@ extern "C" int crsdr_plan_kernel_times(crsdr_plan *p, int which, float *ms, int 
 // (iv) batched direction-of-arrival engine (crsdr_doa): covariance -> noise subspace -> 2-D MUSIC scan + peak, one estimate per
 //      `frames` packets, for a whole batch of packets where a plan left them.  Every buffer is allocated at create; a submit is five
 //      launches on one stream whatever the batch size (covariance partials, their reducer, subspace, scan, peak), no lock, no
-//      allocation, no synchronisation.  crsdr_doa_set_peaks allocates what the local-peak pass needs and adds its two launches.
+//      allocation, no synchronisation.  crsdr_doa_set_peaks allocates what the local-peak pass needs and adds its two launches,
+//      crsdr_doa_set_beams what the beams need and theirs (beams.hpp).
 // ================================================================================================
 struct crsdr_doa {
     int nrows = 0, B = 0, m = 0, device = 0, max_batch = 1, frames = 1, k = 1, mx = 0, my = 0, ncx = 0, ncy = 0;
@@ -1815,6 +1817,13 @@ struct crsdr_doa {
     unsigned long long *d_cand = nullptr;
     int32_t *d_found = nullptr, *d_dirs = nullptr;
     bool peaks_submitted = false;
+    // crsdr_doa_set_beams: mode (0 = off), `nbeams` slots per estimate (nfixed of them at the caller's angles, else the estimate's own
+    // directions), weights [nest][nbeams][m], power [nest][nbeams], beams [max_batch][nbeams][B / 2]; beams_submitted: a submit since
+    int beam_mode = 0, nbeams = 0, nfixed = 0, last_nblocks = 0;
+    float loading = 0.f;
+    float2 *d_bw = nullptr, *d_beams = nullptr;
+    float *d_bpow = nullptr, *d_bangles = nullptr;
+    bool beams_submitted = false;
 };
 
 static void doa_free_peaks(crsdr_doa *q)
@@ -1825,12 +1834,21 @@ static void doa_free_peaks(crsdr_doa *q)
     q->npeaks = q->radius = 0; q->peaks_submitted = false;
 }
 
+static void doa_free_beams(crsdr_doa *q)
+{
+    void *bufs[] = {q->d_bw, q->d_beams, q->d_bpow, q->d_bangles};
+    for (void *b : bufs) if (b) (void)hipFree(b);
+    q->d_bw = q->d_beams = nullptr; q->d_bpow = q->d_bangles = nullptr;
+    q->beam_mode = q->nbeams = q->nfixed = 0; q->loading = 0.f; q->beams_submitted = false;
+}
+
 static void doa_free(crsdr_doa *q)
 {
     if (!q) return;
     (void)hipSetDevice(q->device);
     if (q->submitted) (void)hipDeviceSynchronize();      // (the last submit's stream may be the caller's, and gone)
     doa_free_peaks(q);
+    doa_free_beams(q);
     void *bufs[] = {q->d_partial, q->d_info, q->d_psum, q->d_rxx, q->d_vec, q->d_sv, q->d_peakv, q->d_pm, q->d_peak, q->d_wgbest};
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (q->own_stream) (void)hipStreamDestroy(q->own_stream);
@@ -1903,6 +1921,16 @@ extern "C" int crsdr_doa_destroy(crsdr_doa *doa)
     return CRSDR_OK;
 }
 
+// `launch` with NB = the apply kernel's slot count for nbeams (1, 2, 4, 8 or 16)
+#define BEAMS_DISPATCH(nbeams, launch)                                              \
+    switch (beams::slots_for(nbeams)) {                                             \
+    case 1: { constexpr int NB = 1; launch; } break;                                \
+    case 2: { constexpr int NB = 2; launch; } break;                                \
+    case 4: { constexpr int NB = 4; launch; } break;                                \
+    case 8: { constexpr int NB = 8; launch; } break;                                \
+    default: { constexpr int NB = 16; launch; } break;                              \
+    }
+
 static int doa_launch(crsdr_doa *q, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nblocks, hipStream_t S)
 {
     const unsigned nest = (unsigned)(nblocks / q->frames), slices = (unsigned)(q->frames * q->spb);
@@ -1934,7 +1962,18 @@ static int doa_launch(crsdr_doa *q, const int8_t *packets, size_t packet_stride,
                            q->npeaks, q->d_found, q->d_dirs, q->d_dirv);
         HIP_TRY(hipGetLastError()); ++launches;
     }
-    q->last_stream = S; q->last_nest = (int)nest; q->last_launches = launches; q->submitted = true; q->peaks_submitted = q->npeaks > 0;
+    if (q->beam_mode) {
+        hipLaunchKernelGGL(beams::k_doa_beam_weights, dim3(nest, (unsigned)q->nbeams), dim3(beams::BW_THREADS), 0, S, (const float2 *)q->d_vec, (const float *)q->d_sv,
+                           q->m, q->mx, q->d, q->ncx, q->ncy, q->beam_mode, q->loading, (const float *)(q->nfixed ? q->d_bangles : nullptr),
+                           (const int32_t *)(q->npeaks ? q->d_found : nullptr), (const int32_t *)q->d_dirs, (const int32_t *)q->d_peak, q->d_bw, q->d_bpow);
+        HIP_TRY(hipGetLastError()); ++launches;
+        const dim3 grid((unsigned)((q->B / 4 + beams::AP_THREADS - 1) / beams::AP_THREADS), (unsigned)nblocks);
+        BEAMS_DISPATCH(q->nbeams, hipLaunchKernelGGL(beams::k_doa_beam_apply<NB>, grid, dim3(beams::AP_THREADS), 0, S, packets, packet_stride, matrix_offset,
+                                                     q->nrows, q->B, q->frames, (const float2 *)q->d_bw, q->nbeams, q->d_beams));
+        HIP_TRY(hipGetLastError()); ++launches;
+    }
+    q->last_stream = S; q->last_nest = (int)nest; q->last_nblocks = nblocks; q->last_launches = launches; q->submitted = true;
+    q->peaks_submitted = q->npeaks > 0; q->beams_submitted = q->beam_mode != 0;
     return CRSDR_OK;
 }
 
@@ -2023,6 +2062,8 @@ extern "C" int crsdr_doa_set_peaks(crsdr_doa *q, int count, int radius)
     if (!q) return fail(CRSDR_EINVAL, "doa_set_peaks: NULL doa");
     if (count < 0 || count > doa::MAX_PEAKS) return fail(CRSDR_EINVAL, "doa_set_peaks: count = %d (0..%d)", count, doa::MAX_PEAKS);
     if (count > 0 && (radius < 1 || radius > doa::MAX_RADIUS)) return fail(CRSDR_EINVAL, "doa_set_peaks: radius = %d (1..%d)", radius, doa::MAX_RADIUS);
+    if (q->beam_mode && !q->nfixed)
+        return fail(CRSDR_ESTATE, "doa_set_peaks: beams follow the directions (crsdr_doa_set_beams with nfixed = 0) and are sized by them: turn the beams off first");
     HIP_TRY(hipSetDevice(q->device));
     if (q->submitted) HIP_TRY(hipDeviceSynchronize());   // the buffers may be in use (the last submit's stream may be the caller's, and gone)
     doa_free_peaks(q);
@@ -2054,6 +2095,97 @@ extern "C" int crsdr_doa_direction_buffers(crsdr_doa *q, void **found, void **pe
     if (found) *found = q->d_found;
     if (peaks) *peaks = q->d_dirs;
     if (values) *values = q->d_dirv;
+    return CRSDR_OK;
+}
+
+// ---- beams toward the directions (beams.hpp) ----
+extern "C" int crsdr_doa_set_beams(crsdr_doa *q, int mode, float loading, int nfixed, const float *fixed_angles)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_set_beams: NULL doa");
+    if (mode != CRSDR_BEAM_OFF && mode != CRSDR_BEAM_CONVENTIONAL && mode != CRSDR_BEAM_MVDR) return fail(CRSDR_EINVAL, "doa_set_beams: mode = %d", mode);
+    if (mode == CRSDR_BEAM_MVDR && !(loading >= 1e-6f && loading <= 1.0f)) return fail(CRSDR_EINVAL, "doa_set_beams: loading = %g (1e-6..1)", (double)loading);
+    if (mode != CRSDR_BEAM_OFF && (nfixed < 0 || nfixed > beams::MAX_BEAMS)) return fail(CRSDR_EINVAL, "doa_set_beams: nfixed = %d (0..%d)", nfixed, beams::MAX_BEAMS);
+    if (mode != CRSDR_BEAM_OFF && nfixed > 0 && !fixed_angles) return fail(CRSDR_EINVAL, "doa_set_beams: %d fixed directions and no angles", nfixed);
+    HIP_TRY(hipSetDevice(q->device));
+    if (q->submitted) HIP_TRY(hipDeviceSynchronize());   // the buffers may be in use (the last submit's stream may be the caller's, and gone)
+    doa_free_beams(q);
+    if (mode == CRSDR_BEAM_OFF) return CRSDR_OK;
+    const size_t nest = (size_t)(q->max_batch / q->frames), nb = (size_t)(nfixed ? nfixed : q->npeaks ? q->npeaks : 1);
+    int rc = CRSDR_OK;
+    auto alloc = [&](void **p, size_t bytes) { if (!rc && hipMalloc(p, bytes) != hipSuccess) rc = fail(CRSDR_ENOMEM, "doa_set_beams: %zu bytes of device memory", bytes); };
+    alloc((void **)&q->d_bw, sizeof(float2) * nest * nb * (size_t)q->m);
+    alloc((void **)&q->d_bpow, sizeof(float) * nest * nb);
+    alloc((void **)&q->d_beams, sizeof(float2) * (size_t)q->max_batch * nb * (size_t)(q->B / 2));
+    if (nfixed) {
+        alloc((void **)&q->d_bangles, sizeof(float) * 2 * nb);
+        if (!rc && hipMemcpy(q->d_bangles, fixed_angles, sizeof(float) * 2 * nb, hipMemcpyHostToDevice) != hipSuccess) rc = fail(CRSDR_EHIP, "doa_set_beams: copy of the angles");
+    }
+    if (rc) { doa_free_beams(q); return rc; }
+    q->beam_mode = mode; q->nbeams = (int)nb; q->nfixed = nfixed; q->loading = mode == CRSDR_BEAM_MVDR ? loading : 0.f;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_fetch_beams(crsdr_doa *q, float *weights, float *power, float *beams)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_fetch_beams: NULL doa");
+    if (!q->beam_mode) return fail(CRSDR_ESTATE, "doa_fetch_beams: no crsdr_doa_set_beams");
+    if (!q->beams_submitted) return fail(CRSDR_ESTATE, "doa_fetch_beams: nothing submitted since crsdr_doa_set_beams");
+    HIP_TRY(hipSetDevice(q->device));
+    const size_t nest = (size_t)q->last_nest, nb = (size_t)q->nbeams;
+    hipStream_t S = q->last_stream;
+    if (weights) HIP_TRY(hipMemcpyAsync(weights, q->d_bw, sizeof(float2) * nest * nb * (size_t)q->m, hipMemcpyDeviceToHost, S));
+    if (power) HIP_TRY(hipMemcpyAsync(power, q->d_bpow, sizeof(float) * nest * nb, hipMemcpyDeviceToHost, S));
+    if (beams) HIP_TRY(hipMemcpyAsync(beams, q->d_beams, sizeof(float2) * (size_t)q->last_nblocks * nb * (size_t)(q->B / 2), hipMemcpyDeviceToHost, S));
+    HIP_TRY(hipStreamSynchronize(S));
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_beam_buffers(crsdr_doa *q, void **weights, void **power, void **beams, int *nbeams)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_beam_buffers: NULL doa");
+    if (weights) *weights = q->d_bw;
+    if (power) *power = q->d_bpow;
+    if (beams) *beams = q->d_beams;
+    if (nbeams) *nbeams = q->nbeams;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_fetch_subspace(crsdr_doa *q, float *vec)
+{
+    if (!q || !vec) return fail(CRSDR_EINVAL, "doa_fetch_subspace: NULL doa or vec");
+    if (!q->submitted) return fail(CRSDR_ESTATE, "doa_fetch_subspace: nothing submitted");
+    HIP_TRY(hipSetDevice(q->device));
+    HIP_TRY(hipMemcpyAsync(vec, q->d_vec, sizeof(float2) * (size_t)q->last_nest * (size_t)q->m * q->m, hipMemcpyDeviceToHost, q->last_stream));
+    HIP_TRY(hipStreamSynchronize(q->last_stream));
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_beamform(float *out, const int8_t *matrix, int nrows, int blocksize, const float *weights, int nbeams, int mem_kind)
+{
+    if (!out || !matrix || !weights || nrows < 2 || nrows - 1 > beams::MAX_M || blocksize < 32 || (blocksize % 32) || nbeams < 1 || nbeams > beams::MAX_BEAMS)
+        return fail(CRSDR_EINVAL, "beamform: need out, matrix, weights, 2 <= nrows <= %d, blocksize %% 32 == 0, 1 <= nbeams <= %d", beams::MAX_M + 1,
+                    beams::MAX_BEAMS);
+    if (mem_kind != CRSDR_MEM_HOST && mem_kind != CRSDR_MEM_DEVICE) return fail(CRSDR_EINVAL, "beamform: mem_kind = %d", mem_kind);
+    { int rc_ = require_device(); if (rc_) return rc_; }
+    std::lock_guard<std::mutex> lock_(g_op.mu);
+    const size_t mb = (size_t)nrows * (size_t)blocksize, wb = sizeof(float2) * (size_t)nbeams * (size_t)(nrows - 1);
+    const size_t ob = sizeof(float2) * (size_t)nbeams * (size_t)(blocksize / 2);
+    const int8_t *d_m = matrix;
+    const float2 *d_w = (const float2 *)weights;
+    float2 *d_o = (float2 *)out;
+    if (mem_kind == CRSDR_MEM_HOST) {
+        OP_RESERVE(0, mb); OP_RESERVE(1, ob); OP_RESERVE(2, wb);
+        HIP_TRY(hipMemcpy(g_op.buf[0], matrix, mb, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(g_op.buf[2], weights, wb, hipMemcpyHostToDevice));
+        d_m = (const int8_t *)g_op.buf[0]; d_o = (float2 *)g_op.buf[1]; d_w = (const float2 *)g_op.buf[2];
+    } else if ((uintptr_t)d_m % 4 || (uintptr_t)d_o % 16 || (uintptr_t)d_w % 8) {
+        return fail(CRSDR_EINVAL, "beamform: device matrix 4-byte, weights 8-byte, out 16-byte aligned");
+    }
+    const dim3 grid((unsigned)((blocksize / 4 + beams::AP_THREADS - 1) / beams::AP_THREADS));
+    BEAMS_DISPATCH(nbeams, hipLaunchKernelGGL(beams::k_beamform<NB>, grid, dim3(beams::AP_THREADS), 0, 0, d_m, nrows, blocksize, d_w, nbeams, d_o));
+    HIP_TRY(hipGetLastError());
+    if (mem_kind == CRSDR_MEM_HOST) HIP_TRY(hipMemcpy(out, d_o, ob, hipMemcpyDeviceToHost));
+    else HIP_TRY(hipDeviceSynchronize());
     return CRSDR_OK;
 }
 

@@ -37,7 +37,7 @@ int pmusic2dvec(const cmatrix &U, int M, int K, float d, int Mx, int My, int Cx,
 }
 
 batch::batch(int nrows, int blocksize, int max_batch, int K, int frames, bool keep_spectrum, float d, int Mx, int My, int Cx, int Cy, int device)
-    : m(nrows - 1), cx(Cx), cy(Cy), keep(keep_spectrum)
+    : m(nrows - 1), cx(Cx), cy(Cy), half(blocksize / 2), nframes(frames > 0 ? frames : 1), keep(keep_spectrum)
 {
     crsdr_doa_desc desc = {};
     desc.nrows = nrows; desc.blocksize = blocksize; desc.device = device; desc.max_batch = max_batch; desc.frames = frames; desc.k = K;
@@ -73,7 +73,15 @@ int batch::set_peaks(int count, int radius)
     return rc;
 }
 
-int batch::fetch()
+int batch::set_beams(int mode, float loading, int nfixed, const float *fixed_angles)
+{
+    int rc = doa ? crsdr_doa_set_beams(doa, mode, loading, nfixed, fixed_angles) : CRSDR_ESTATE;
+    if (!rc) rc = crsdr_doa_beam_buffers(doa, nullptr, nullptr, nullptr, &nbeams);
+    if (rc && doa) std::fprintf(stderr, "cbeamformer::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::fetch(bool want_beams)
 {
     int nest = 0;
     int rc = doa ? crsdr_doa_last_submit(doa, &nest, nullptr) : CRSDR_ESTATE;
@@ -85,6 +93,12 @@ int batch::fetch()
     if (!rc && npeaks) {
         found.assign(nest, 0); directions.assign((size_t)nest * npeaks * 2, -1); direction_values.assign((size_t)nest * npeaks, -1.f);
         rc = crsdr_doa_fetch_directions(doa, found.data(), directions.data(), direction_values.data());
+    }
+    if (!rc && nbeams) {
+        weights.assign((size_t)nest * nbeams * m, {0.f, 0.f}); beam_power.assign((size_t)nest * nbeams, -1.f);
+        if (want_beams) beams.assign((size_t)nest * nframes * nbeams * half, {0.f, 0.f});
+        rc = crsdr_doa_fetch_beams(doa, reinterpret_cast<float *>(weights.data()), beam_power.data(),
+                                   want_beams ? reinterpret_cast<float *>(beams.data()) : nullptr);
     }
     if (rc && doa) std::fprintf(stderr, "cbeamformer::batch: %s\n", crsdr_last_error());
     return rc;

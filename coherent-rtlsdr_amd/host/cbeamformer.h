@@ -30,7 +30,7 @@ int pmusic2dvec(const cmatrix &U, int M, int K, float d, int Mx, int My, int Cx,
 // it reads); fetch() waits and fills the vectors below.  One submit at a time: fetch before the next.
 class batch {
     crsdr_doa *doa = nullptr;
-    int m = 0, cx = 0, cy = 0, npeaks = 0;
+    int m = 0, cx = 0, cy = 0, npeaks = 0, nbeams = 0, half = 0, nframes = 1;
     bool keep = false;
 public:
     // nrows x blocksize: the packets' geometry (1 + Mx * My rows); keep_spectrum: fetch() also fills pm
@@ -45,7 +45,12 @@ public:
     // from the next submit on, the `count` strongest local maxima of each spectrum within a (2 radius + 1)^2 window as well
     // (crsdr_doa_set_peaks; count = 0: off).  Waits for the device if a submit was made.
     int set_peaks(int count, int radius = 1);
-    int fetch();
+    // from the next submit on, a beam toward every direction of an estimate (crsdr_doa_set_beams: mode CRSDR_BEAM_*, the MVDR diagonal
+    // loading as a fraction of the largest singular value) -- the count of set_peaks, or the one peak -- or toward nfixed (alpha, beta)
+    // pairs in radians.  CRSDR_BEAM_OFF: off.  With following beams on, set_peaks is refused: turn them off first.
+    int set_beams(int mode, float loading = 1e-2f, int nfixed = 0, const float *fixed_angles = nullptr);
+    // want_beams: also copy the beams' samples out (blocks x slots x blocksize / 2 complex floats)
+    int fetch(bool want_beams = false);
     int estimates() const { return (int)status.size(); }
     std::vector<int32_t> peak;                       // [estimates][2]: (cx, cy) of the largest pm
     std::vector<float> peak_value, sv, pm;           // [estimates], [estimates][M], [estimates][Cx][Cy] (keep_spectrum)
@@ -54,6 +59,11 @@ public:
     // [estimates][count]; slots from found on hold (-1, -1) and -1
     std::vector<int32_t> found, directions;
     std::vector<float> direction_values;
+    // with set_beams: weights [estimates][slots][M], beam_power [estimates][slots] (-1 in an empty slot) and, on request, the beams
+    // [blocks][slots][blocksize / 2]
+    int beam_slots() const { return nbeams; }
+    cmatrix weights, beams;
+    std::vector<float> beam_power;
 };
 }
 #endif

@@ -55,7 +55,8 @@ int main(int argc, char **argv)
     int nsig = 3, L = 8192, blocks = 12, mode = CRSDR_MODE_DIGITAL, dmax = -1;
     std::string dump, zmqaddr;
     bool run_cdsp = false, servo = false, threads = false, music = false, servo_table = false, bench = false, batch_parity = false, batched = false;
-    int batch = 16, engine_delay_ms = 0, pace_us_arg = -1, peaks = 0, peak_radius = 1;
+    int batch = 16, engine_delay_ms = 0, pace_us_arg = -1, peaks = 0, peak_radius = 1, beam_mode = CRSDR_BEAM_OFF;
+    float beam_loading = 1e-2f;
     bool engine_batches = false;
     int ranks = 1, rank = 0, device = 0;
     std::string idfile;
@@ -85,6 +86,12 @@ int main(int argc, char **argv)
         else if (a == "--batch") val(batch);
         else if (a == "--peaks") val(peaks);                   // with --bench --music: that many directions per estimate (crsdr_doa_set_peaks)
         else if (a == "--peak-radius") val(peak_radius);
+        // with --bench --music: a beam toward every direction (crsdr_doa_set_beams), its power printed beside the direction
+        else if (a == "--beams" && i + 1 < argc) {
+            const std::string m = argv[++i];
+            beam_mode = m == "conventional" ? CRSDR_BEAM_CONVENTIONAL : m == "mvdr" ? CRSDR_BEAM_MVDR : -1;
+        }
+        else if (a == "--loading" && i + 1 < argc) beam_loading = (float)std::atof(argv[++i]);
         else if (a == "--batch-parity") batch_parity = true;   // the batched engine's packets == step()'s packets, bit for bit (own read counters, a masked row)
         else if (a == "--batched") batched = true;             // with --threads: the engine thread runs a batch at a time (ccoherent::start_batched)
         else if (a == "--engine-delay-ms") val(engine_delay_ms);
@@ -285,6 +292,7 @@ int main(int argc, char **argv)
             doa.reset(new cbeamformer::batch(1 + nsig, B, batch));
             if (nsig != cbeamformer::MX * cbeamformer::MY || !doa->ok()) { std::printf("doa: unavailable (needs --nsig 21)\nDEMO FAILED\n"); return 1; }
             if (peaks && doa->set_peaks(peaks, peak_radius)) { std::printf("doa: --peaks %d --peak-radius %d refused\nDEMO FAILED\n", peaks, peak_radius); return 1; }
+            if (beam_mode && doa->set_beams(beam_mode, beam_loading)) { std::printf("doa: --beams (conventional|mvdr) --loading %g refused\nDEMO FAILED\n", (double)beam_loading); return 1; }
         }
         bool report = false;
         auto directions = [&](int b) {
@@ -295,16 +303,18 @@ int main(int argc, char **argv)
             if (peaks) {
                 // the first estimate's local peaks, strongest first
                 std::string dirs;
-                char buf[32];
+                char buf[64];
                 for (int i = 0; i < doa->found[0]; ++i) {
                     std::snprintf(buf, sizeof(buf), " (%d, %d)", doa->directions[2 * i], doa->directions[2 * i + 1]);
                     dirs += buf;
+                    if (beam_mode) { std::snprintf(buf, sizeof(buf), " power %.4g", (double)doa->beam_power[i]); dirs += buf; }
                 }
                 std::printf("doa: batch %d: %d estimates, peaks of the first:%s\n", b, n, dirs.c_str());
                 return;
             }
             int broadside = 0;
             for (int e = 0; e < n; ++e) broadside += doa->peak[2 * e] == 50 && doa->peak[2 * e + 1] == 50;
+            if (beam_mode) std::printf("doa: batch %d: beam power of the first direction %.4g\n", b, (double)doa->beam_power[0]);
             std::printf("doa: batch %d: %d directions, first (%d, %d), last (%d, %d), %d at broadside\n", b, n, doa->peak[0], doa->peak[1], doa->peak[2 * n - 2],
                         doa->peak[2 * n - 1], broadside);
         };

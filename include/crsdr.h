@@ -420,6 +420,15 @@ int crsdr_noisesubspace(float *vec, float *sv, const float *rxx, int m, int mem_
  *   pm  [ncx][ncy] float row-major, not normalised (the reference divides by the maximum for plotting, :202-203) */
 int crsdr_pmusic2d(float *pm, const float *vec, int m, int k, float d, int mx, int my, int ncx, int ncy, int mem_kind);
 
+/* Beams from one aligned receive matrix: out[b][n] = sum_c weights[b][c-1] * (I_c[n] + j Q_c[n]) / 127 over the signal rows
+ * c = 1 .. nrows-1 (row 0, the reference channel, is dropped as in crsdr_covariance), n < blocksize/2, fp32, no conjugate (see
+ * crsdr_doa_set_beams for why).  The per-op form of the batched engine's beam kernel: the same arithmetic, bit for bit.
+ *   matrix  [nrows][blocksize] int8, 2 <= nrows <= 65, blocksize % 32 == 0
+ *   weights [nbeams][nrows-1][2] float, 1 <= nbeams <= 16
+ *   out     [nbeams][blocksize/2][2] float
+ * mem_kind: CRSDR_MEM_HOST (copied) or CRSDR_MEM_DEVICE (all three on the device: matrix 4-byte, weights 8-byte, out 16-byte aligned). */
+int crsdr_beamform(float *out, const int8_t *matrix, int nrows, int blocksize, const float *weights, int nbeams, int mem_kind);
+
 /* ------------------------------------------------------------------------------------------
  * (iv) batched direction-of-arrival engine: the chain above for a whole batch of packets where a plan left them
  * ---------------------------------------------------------------------------------------- */
@@ -504,6 +513,42 @@ int crsdr_doa_fetch_directions(crsdr_doa *doa, int32_t *found, int32_t *peaks, f
 /* Device addresses of found, peaks and values ([max_batch / frames] estimates, laid out as above; NULL while peaks are off), for
  * consumers on the same stream.  They change with every crsdr_doa_set_peaks. */
 int crsdr_doa_direction_buffers(crsdr_doa *doa, void **found, void **peaks, void **values);
+
+/* Beams toward the directions: per estimate e and beam slot b a weight vector u (m complex entries) from the subspace the engine
+ * holds, and for every block t of the estimate one IQ stream per slot, all on the device, behind the same submit.
+ *   direction  nfixed = 0: slot b of the estimate's own directions -- with crsdr_doa_set_peaks on, peaks[e][b] for b < found[e] (count
+ *              slots); with peaks off one slot, peak[e]; alpha = cx pi / ncx, beta = cy pi / ncy.
+ *              nfixed = 1..16: the (alpha_b, beta_b) of fixed_angles [nfixed][2] (radians, host pointer, copied), for every estimate.
+ *   steering   a[iy*mx + ix] = exp(2 pi j d (ix cos(alpha) sin(beta) + iy cos(beta))), crsdr_pmusic2d's vector, in fp64
+ *   weights    fp64 from the published fp32 vec[e] (column r = v_r) and sv[e], rounded once to fp32:
+ *              CRSDR_BEAM_CONVENTIONAL  u = a / m
+ *              CRSDR_BEAM_MVDR          delta = loading * sv[0],  z = sum_r v_r (v_r^H a) / (sv[r] + delta),  u = z / Re(a^H z);
+ *                                       sv[0] == 0 (an all-zero estimate): u = a / m
+ *   power      conventional: sum_r sv[r] |v_r^H a|^2 / m^2 (= a^H Rxx a / m^2); MVDR: 1 / Re(a^H z), the Capon estimate of the loaded
+ *              covariance (0 in the sv[0] == 0 case).  It tells a source from a side-lobe peak of the MUSIC spectrum.
+ *   beams      y[t][b][n] = sum_c u[c-1] (I_c[n] + j Q_c[n]) / 127 over the signal rows c = 1 .. m, n < blocksize/2, fp32, NO
+ *              conjugate: the covariance is X^H X, the conjugate of E[x x^H], so the steering vector at a MUSIC peak is conj(a_true) and
+ *              w^H x with the textbook w = R^-1 a / (a^H R^-1 a) becomes u^T x; sum_c u_c conj(a_c) = 1 is the distortionless constraint.
+ *              The mean is not removed from the samples.
+ *   Slots b >= found[e]: weights 0, power -1, beam samples 0.
+ * mode CRSDR_BEAM_OFF frees the buffers (the other arguments are then ignored).  loading in [1e-6, 1] (ignored for CONVENTIONAL).
+ * Any time: waits for the device if a submit was made, then allocates weights, power and beams [max_batch][nbeams][blocksize/2][2].
+ * A submit with beams on is two launches more (5 -> 7, 7 -> 9), the same for every nblocks, still without allocation, lock or host wait.
+ * While beams follow the directions (nfixed = 0) crsdr_doa_set_peaks returns CRSDR_ESTATE: their buffers are sized by its count, turn
+ * the beams off first.  CRSDR_EINVAL for a bad mode, loading outside the range in MVDR mode, nfixed outside 0..16 or NULL angles. */
+enum { CRSDR_BEAM_OFF = 0, CRSDR_BEAM_CONVENTIONAL = 1, CRSDR_BEAM_MVDR = 2 };
+int crsdr_doa_set_beams(crsdr_doa *doa, int mode, float loading, int nfixed, const float *fixed_angles);
+
+/* Waits for the last submit and copies out (any pointer may be NULL): weights [nest][nbeams][m][2], power [nest][nbeams],
+ * beams [nblocks][nbeams][blocksize/2][2].  CRSDR_ESTATE with beams off or before the first submit after crsdr_doa_set_beams. */
+int crsdr_doa_fetch_beams(crsdr_doa *doa, float *weights, float *power, float *beams);
+
+/* Device addresses of weights, power and beams (laid out as above for [max_batch / frames] estimates and max_batch blocks; NULL
+ * while beams are off) and the slot count, for consumers on the same stream.  They change with every crsdr_doa_set_beams. */
+int crsdr_doa_beam_buffers(crsdr_doa *doa, void **weights, void **power, void **beams, int *nbeams);
+
+/* vec [nest][m][m][2] of the last submit, as crsdr_noisesubspace writes it.  CRSDR_ESTATE before the first submit. */
+int crsdr_doa_fetch_subspace(crsdr_doa *doa, float *vec);
 
 #ifdef __cplusplus
 }

@@ -7,31 +7,39 @@
   (b) crsdr_doa_submit of the 64 packets + a fetch of the peaks only,
   (c) the same with the spectra kept and fetched (64 x 40 KB),
   (p) with --peaks COUNT --radius R: crsdr_doa_set_peaks(COUNT, R), then the submit + crsdr_doa_fetch_directions (the local-peak pass).
+  (q) with --beams MODE (conventional | mvdr, --loading X) on top of --peaks: crsdr_doa_set_beams, then the submit + a fetch of the beams'
+      power only (weights and beams stay on the device), and
+  (h) what a caller without beams does to form them on the host: the (p) submit + directions, then the 64 packets and vec copied to
+      page-locked host memory (before any host arithmetic).
 
 --runs runs of each, alternating a, b, c in one session (two worker processes, both alive throughout); medians and ranges.
 --doa-lib LIB starts a second doa worker on another build (e.g. the parent commit's) through CRSDR_LIB and times its (b) and (c) in
-the same alternation, reported as lib:b and lib:c.  --reps N: every (b), (c), (p) figure is the mean of N back-to-back submit + fetch.
+the same alternation, reported as lib:b and lib:c.  --reps N: every (b), (c), (p), (q), (h) figure is the mean of N back-to-back submit + fetch.
 Also: what crsdr_doa_submit_plan + the peak fetch add to a 22-row, T = 64 plan batch (plan.submit + sync against
-plan.submit + doa.submit_plan + fetch).  --json FILE keeps the record; --once MODE runs one submit + fetch and exits (for a kernel trace)."""
+plan.submit + doa.submit_plan + fetch).  --json FILE keeps the record; --once MODE runs three submit + fetch and exits (for a kernel trace): b, c, p, q as above, q64 = the
+beams at their largest shape (8 x 8 array, 16 slots: 65 rows x 16384, 64 blocks)."""
 import argparse, importlib, json, os, subprocess, sys, time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NROWS, B, T, M = 22, 16384, 64, 21
+BEAM_MODES = {"conventional": 1, "mvdr": 2}
 
 
-def _setup():
+def _setup(mx=None, my=None):
     sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
     import torch
     import ura
     b = importlib.import_module("coherent-rtlsdr_amd.binding")
     rng = np.random.default_rng(1)
     dev = torch.device("cuda", 0)
-    off = 16 + 4 * NROWS
-    stride = off + NROWS * B
+    mx, my = mx or ura.MX, my or ura.MY
+    nrows = 1 + mx * my
+    off = 16 + 4 * nrows
+    stride = off + nrows * B
     host = np.zeros((T, stride), dtype=np.int8)
     for t in range(T):
-        host[t, off:] = ura.scene(B // 2, [(0.6 + 0.03 * t, 1.2 + 0.02 * t, 1.0)], rng).reshape(-1)
+        host[t, off:] = ura.scene(B // 2, [(0.6 + 0.03 * t, 1.2 + 0.02 * t, 1.0)], rng, mx=mx, my=my).reshape(-1)
     pk = torch.from_numpy(host).to(dev)
     return torch, ura, b, dev, pk, off, stride, host
 
@@ -62,8 +70,9 @@ def worker_perop():
         print(time.perf_counter() - t0, flush=True)
 
 
-def worker_doa(npeaks=0, radius=1, reps=1):
-    """(b), (c), (p) and the plan figures: 'b' / 'c' / 'p' / 'plan' / 'plan+doa' on stdin -> seconds of one batch of 64 on stdout."""
+def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2):
+    """(b), (c), (p), (q), (h) and the plan figures: 'b' / 'c' / 'p' / 'q' / 'h' / 'plan' / 'plan+doa' on stdin -> seconds of one batch of
+    64 on stdout."""
     torch, ura, b, dev, pk, off, stride, host = _setup()
     peaks = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
     full = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T, flags=b.DOA_KEEP_SPECTRUM)
@@ -74,6 +83,27 @@ def worker_doa(npeaks=0, radius=1, reps=1):
     if npeaks:
         dirs = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
         dirs.set_peaks(npeaks, radius)
+    bdoa = None
+    if beams:
+        bdoa = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
+        if npeaks:
+            bdoa.set_peaks(npeaks, radius)
+        bdoa.set_beams(BEAM_MODES[beams], loading)
+        hdoa = dirs or peaks
+        pinned = torch.empty(pk.shape, dtype=torch.int8, pin_memory=True)
+
+    def run_q():
+        for _ in range(reps):
+            bdoa.submit(pk.data_ptr(), stride, off, T)
+            bdoa.fetch_beams(weights=False, beams=False)
+
+    def run_h():
+        for _ in range(reps):
+            hdoa.submit(pk.data_ptr(), stride, off, T)
+            hdoa.fetch_directions() if npeaks else hdoa.fetch_peaks()
+            pinned.copy_(pk, non_blocking=True)
+            hdoa.fetch_subspace()
+            torch.cuda.synchronize()
 
     def run_b():
         for _ in range(reps):
@@ -104,6 +134,8 @@ def worker_doa(npeaks=0, radius=1, reps=1):
     jobs = {"b": (run_b, reps), "c": (run_c, reps), "plan": (run_plan, 10), "plan+doa": (run_plan_doa, 10)}
     if dirs is not None:
         jobs["p"] = (run_p, reps)
+    if bdoa is not None:
+        jobs["q"], jobs["h"] = (run_q, reps), (run_h, reps)
     for f, _ in jobs.values():
         f()
     print("ready", flush=True)
@@ -114,17 +146,25 @@ def worker_doa(npeaks=0, radius=1, reps=1):
         print((time.perf_counter() - t0) / n, flush=True)
 
 
-def once(mode, npeaks=0, radius=1):
-    torch, ura, b, dev, pk, off, stride, _ = _setup()
-    d = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T, flags=b.DOA_KEEP_SPECTRUM if mode == "c" else 0)
-    if mode == "p":
+def once(mode, npeaks=0, radius=1, beams=None, loading=1e-2):
+    mx, my = (8, 8) if mode == "q64" else (None, None)
+    torch, ura, b, dev, pk, off, stride, _ = _setup(mx, my)
+    mx, my = mx or ura.MX, my or ura.MY
+    d = b.Doa(1 + mx * my, B, 1, ura.D, mx, my, max_batch=T, flags=b.DOA_KEEP_SPECTRUM if mode == "c" else 0)
+    if mode == "q64":
+        npeaks, radius = 16, 1
+    if mode in ("p", "q", "q64") and npeaks:
         d.set_peaks(npeaks, radius)
+    if mode in ("q", "q64"):
+        d.set_beams(BEAM_MODES[beams or "mvdr"], loading)
     for _ in range(3):
         d.submit(pk.data_ptr(), stride, off, T)
         out = d.fetch()
     print("peaks", out["peak"][:4].tolist(), "launches", d.last_launches())
-    if mode == "p":
+    if mode in ("p", "q", "q64") and npeaks:
         print("directions of the first", d.fetch_directions()["peaks"][0].tolist())
+    if mode in ("q", "q64"):
+        print("slots", d.nbeams, "beam power of the first", d.fetch_beams(weights=False, beams=False)["power"][0].tolist())
 
 
 class Worker:
@@ -157,23 +197,27 @@ def _stat(xs):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--worker", choices=["perop", "doa"])
-    ap.add_argument("--once", choices=["b", "c", "p"])
+    ap.add_argument("--once", choices=["b", "c", "p", "q", "q64"])
+    ap.add_argument("--beams", choices=sorted(BEAM_MODES), default=None, help="(q), (h): beams toward the directions, this mode")
+    ap.add_argument("--loading", type=float, default=1e-2, help="(q): the MVDR diagonal loading")
     ap.add_argument("--perop-lib", default=None, help="library for (a), e.g. a build of the parent commit (default: the current one)")
     ap.add_argument("--doa-lib", default=None, help="a second library whose (b) and (c) are timed in the same alternation (lib:b, lib:c)")
     ap.add_argument("--peaks", type=int, default=0, help="(p): directions per estimate (crsdr_doa_set_peaks count; 0 = no (p))")
     ap.add_argument("--radius", type=int, default=1, help="(p): the local-peak window's radius")
-    ap.add_argument("--reps", type=int, default=1, help="submit + fetch pairs per (b), (c), (p) figure")
+    ap.add_argument("--reps", type=int, default=1, help="submit + fetch pairs per (b), (c), (p), (q), (h) figure")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     if a.worker:
-        return worker_perop() if a.worker == "perop" else worker_doa(a.peaks, a.radius, a.reps)
+        return worker_perop() if a.worker == "perop" else worker_doa(a.peaks, a.radius, a.reps, a.beams, a.loading)
     if a.once:
-        return once(a.once, a.peaks, a.radius)
-    pargs = ["--peaks", str(a.peaks), "--radius", str(a.radius), "--reps", str(a.reps)]
+        return once(a.once, a.peaks, a.radius, a.beams, a.loading)
+    pargs = ["--peaks", str(a.peaks), "--radius", str(a.radius), "--reps", str(a.reps), "--loading", str(a.loading)]
+    if a.beams:
+        pargs += ["--beams", a.beams]
     wa, wb = Worker("perop", a.perop_lib), Worker("doa", extra=pargs)
     wl = Worker("doa", a.doa_lib, extra=["--reps", str(a.reps)]) if a.doa_lib else None
-    keys = ["a", "b", "c", "plan", "plan+doa"] + (["lib:b", "lib:c"] if wl else []) + (["p"] if a.peaks else [])
+    keys = ["a", "b", "c", "plan", "plan+doa"] + (["lib:b", "lib:c"] if wl else []) + (["p"] if a.peaks else []) + (["q", "h"] if a.beams else [])
     sec = {k: [] for k in keys}
     try:
         for _ in range(a.runs):
@@ -186,6 +230,9 @@ def main():
                 sec["lib:c"].append(wl.run("c"))
             if a.peaks:
                 sec["p"].append(wb.run("p"))
+            if a.beams:
+                sec["q"].append(wb.run("q"))
+                sec["h"].append(wb.run("h"))
             sec["plan"].append(wb.run("plan"))
             sec["plan+doa"].append(wb.run("plan+doa"))
     finally:
@@ -194,13 +241,15 @@ def main():
             wl.close()
     rec = {"shape": {"nrows": NROWS, "blocksize": B, "blocks": T, "grid": [100, 100]}, "runs": a.runs, "reps": a.reps,
            "perop_lib": a.perop_lib or "current build", "doa_lib": a.doa_lib, "peaks": {"count": a.peaks, "radius": a.radius} if a.peaks else None,
+           "beams": {"mode": a.beams, "loading": a.loading} if a.beams else None,
            "ms_per_batch": {k: _stat([1e3 * x for x in v]) for k, v in sec.items()},
            "frames_per_s": {k: _stat([T / x for x in sec[k]]) for k in ("a", "b", "c")}}
     rec["b_faster_than_a_ranges_disjoint"] = rec["ms_per_batch"]["b"]["max"] < rec["ms_per_batch"]["a"]["min"]
     rec["submit_plan_adds_ms_per_batch"] = rec["ms_per_batch"]["plan+doa"]["median"] - rec["ms_per_batch"]["plan"]["median"]
     names = {"a": "per-op loop, device pointers", "b": "doa submit + peaks", "c": "doa submit + peaks + spectra",
              "plan": "plan batch alone", "plan+doa": "plan batch + submit_plan + peaks", "lib:b": "--doa-lib: submit + peaks",
-             "lib:c": "--doa-lib: submit + peaks + spectra", "p": f"set_peaks({a.peaks}, {a.radius}): submit + directions"}
+             "lib:c": "--doa-lib: submit + peaks + spectra", "p": f"set_peaks({a.peaks}, {a.radius}): submit + directions",
+             "q": f"(p) + {a.beams} beams: submit + power", "h": "(p) + packets and vec to the host"}
     for k, s in rec["ms_per_batch"].items():
         fps = f"  {T / (1e-3 * s['median']):10.0f} frames/s" if k in rec["frames_per_s"] else ""
         print(f"({k}) {names[k]:34s} {s['median']:8.3f} ms per 64 blocks  [{s['min']:.3f} .. {s['max']:.3f}]{fps}")
