@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import ura
+from music_model import rxx_reference as _rxx_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -121,21 +122,6 @@ def test_music_chain_matches_the_committed_fixture(b, golden_dir):
     assert np.abs(_projector(vec, k) - g["projector"]).max() < 1e-5
     pm = b.pmusic2d(vec, k, float(g["d"]), int(g["mx"]), int(g["my"]), 40, 40)
     assert np.allclose(pm, g["pm"], rtol=1e-2)
-
-
-def _rxx_reference(rows):
-    """beamformclient/heatmap2d2.cpp:189-199 in exact integer sums (int8 products summed in float64: |sum| <= 2^28) and the fp64 epilogue
-    crsdr_covariance uses: (1/L) sum conj(x_a) x_b - conj(mean_a) mean_b with x = (I + jQ) / 127, rounded once to float."""
-    x = rows[1:].astype(np.float64)
-    I, Q = x[:, 0::2], x[:, 1::2]
-    L = I.shape[1]
-    g1 = I @ I.T + Q @ Q.T
-    g3, g2 = I @ Q.T, Q @ I.T
-    si, sq = I.sum(axis=1), Q.sum(axis=1)
-    scale = 1.0 / (127.0 * 127.0)
-    re = (g1 / L - (np.outer(si, si) + np.outer(sq, sq)) / (L * L)) * scale
-    im = ((g3 - g2) / L - (np.outer(si, sq) - np.outer(sq, si)) / (L * L)) * scale
-    return (re + 1j * im).astype(np.complex64)
 
 
 @pytest.mark.parametrize("nsig,B", [(200, 2048), (64, 128), (1024, 16384), (129, 1024)])
