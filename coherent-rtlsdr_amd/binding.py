@@ -38,9 +38,13 @@ ABI_SYMBOLS = [
     "crsdr_doa_device_buffers", "crsdr_doa_last_submit", "crsdr_doa_set_peaks", "crsdr_doa_fetch_directions",
     "crsdr_doa_direction_buffers",
     "crsdr_beamform", "crsdr_doa_set_beams", "crsdr_doa_fetch_beams", "crsdr_doa_beam_buffers", "crsdr_doa_fetch_subspace",
+    "crsdr_doa_set_smoothing", "crsdr_doa_fetch_smoothed", "crsdr_doa_set_order", "crsdr_doa_fetch_order", "crsdr_doa_order_buffers",
+    "crsdr_smooth_covariance", "crsdr_source_order",
 ]
 DOA_KEEP_SPECTRUM, DOA_KEEP_RXX = 1, 2
 BEAM_OFF, BEAM_CONVENTIONAL, BEAM_MVDR = 0, 1, 2
+SMOOTH_FB = 1
+ORDER_OFF, ORDER_MDL, ORDER_AIC = 0, 1, 2
 XCHG_STAGED, XCHG_INPLACE = 0, 1
 EXCHANGE_ID_BYTES = 128
 KERNEL_REF_SPECTRUM, KERNEL_XCORR_LAG, KERNEL_PHASE_DOT, KERNEL_ALIGN_QUANT = 0, 1, 2, 3
@@ -173,6 +177,14 @@ def lib():
         L.crsdr_doa_fetch_beams.argtypes = [vp, f32p, f32p, f32p]
         L.crsdr_doa_beam_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int)]
         L.crsdr_doa_fetch_subspace.argtypes = [vp, f32p]
+    if hasattr(L, "crsdr_doa_set_smoothing"):        # (likewise: an older build has neither smoothing nor the source count)
+        L.crsdr_doa_set_smoothing.argtypes = [vp, C.c_int, C.c_int, C.c_uint32]
+        L.crsdr_doa_fetch_smoothed.argtypes = [vp, f32p]
+        L.crsdr_doa_set_order.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.crsdr_doa_fetch_order.argtypes = [vp, i32p, f32p]
+        L.crsdr_doa_order_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+        L.crsdr_smooth_covariance.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int]
+        L.crsdr_source_order.argtypes = [vp, vp, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]
     _lib = L
     return L
 
@@ -346,6 +358,37 @@ def beamform(matrix, weights):
     out = np.empty((w.shape[0], B // 2), dtype=np.complex64)
     _check(lib().crsdr_beamform(_p(out.view(np.float32), C.c_float), _p(m, C.c_int8), nrows, B, _p(w.view(np.float32), C.c_float), w.shape[0], MEM_HOST))
     return out
+
+
+def smooth_covariance(rxx, mx, my, sx, sy, flags=0):
+    """crsdr_smooth_covariance: rs [sx sy][sx sy] complex64, the covariance rxx [mx my][mx my] averaged over its sx x sy sub-arrays
+    (and with its backward image: SMOOTH_FB): the batched engine's smoothing on one matrix."""
+    r = np.ascontiguousarray(rxx, dtype=np.complex64)
+    if r.shape != (mx * my, mx * my):
+        raise ValueError("rxx must be [mx * my][mx * my]")
+    rs = np.empty((max(sx * sy, 0), max(sx * sy, 0)), dtype=np.complex64)
+    _check(lib().crsdr_smooth_covariance(rs.ctypes.data, r.ctypes.data, int(mx), int(my), int(sx), int(sy), int(flags), MEM_HOST))
+    return rs
+
+
+def smooth_covariance_device(rs_ptr: int, rxx_ptr: int, mx, my, sx, sy, flags=0):
+    """Same on device memory (both pointers on the current device); returns after the kernel finished."""
+    _check(lib().crsdr_smooth_covariance(int(rs_ptr), int(rxx_ptr), int(mx), int(my), int(sx), int(sy), int(flags), MEM_DEVICE))
+
+
+def source_order(sv, nsnap, criterion=ORDER_MDL, kmin=1, kmax=None):
+    """crsdr_source_order: (k, criterion values [kmax - kmin + 1]) from the singular values sv [m] of nsnap snapshots (ORDER_MDL /
+    ORDER_AIC over k in kmin .. kmax, kmax = m - 1 by default): the batched engine's source count on one estimate."""
+    s = np.ascontiguousarray(sv, dtype=np.float32)
+    kmax = s.size - 1 if kmax is None else int(kmax)
+    k, crit = np.zeros(1, dtype=np.int32), np.zeros(max(kmax - int(kmin) + 1, 1), dtype=np.float32)
+    _check(lib().crsdr_source_order(k.ctypes.data, crit.ctypes.data, s.ctypes.data, s.size, int(nsnap), int(criterion), int(kmin), kmax, MEM_HOST))
+    return int(k[0]), crit
+
+
+def source_order_device(k_ptr: int, crit_ptr: int, sv_ptr: int, m, nsnap, criterion, kmin, kmax):
+    """Same on device memory (crit_ptr may be 0); returns after the kernel finished."""
+    _check(lib().crsdr_source_order(int(k_ptr), int(crit_ptr) or None, int(sv_ptr), int(m), int(nsnap), int(criterion), int(kmin), int(kmax), MEM_DEVICE))
 
 
 def assemble_slabs(packets_ptr: int, packet_stride: int, nrows: int, B: int, recv_ptr: int, nsrc: int, nblocks: int, stream: int | None = None):
@@ -606,6 +649,7 @@ class Doa:
         self.nrows, self.B, self.m, self.k, self.ncx, self.ncy = int(nrows), int(blocksize), int(nrows) - 1, int(k), int(ncx), int(ncy)
         self.max_batch, self.frames, self.flags = max(1, int(max_batch)), max(1, int(frames)), int(flags)
         self.npeaks, self.nbeams = 0, 0
+        self.mx, self.my, self.ms, self.order = int(mx), int(my), self.m, None      # ms: the subspace's size; order: (kmin, kmax)
 
     def _last(self):
         nest, launches = C.c_int(0), C.c_int(0)
@@ -628,7 +672,7 @@ class Doa:
         want_pm = bool(self.flags & DOA_KEEP_SPECTRUM) if spectrum is None else bool(spectrum)
         want_rxx = bool(self.flags & DOA_KEEP_RXX) if rxx is None else bool(rxx)
         peak, val = np.zeros((n, 2), dtype=np.int32), np.zeros(n, dtype=np.float32)
-        sv, status = np.zeros((n, self.m), dtype=np.float32), np.zeros(n, dtype=np.int32)
+        sv, status = np.zeros((n, self.ms), dtype=np.float32), np.zeros(n, dtype=np.int32)
         pm = np.zeros((n, self.ncx, self.ncy), dtype=np.float32) if want_pm else None
         r = np.zeros((n, self.m, self.m), dtype=np.complex64) if want_rxx else None
         _check(lib().crsdr_doa_fetch(self._h, _p(peak, C.c_int32), _p(val, C.c_float), _p(sv, C.c_float), _p(status, C.c_int32),
@@ -696,9 +740,42 @@ class Doa:
 
     def fetch_subspace(self) -> np.ndarray:
         """vec [nest][m][m] complex64 of the last submit (column r of vec[e] = the singular vector of sv[e][r])."""
-        vec = np.zeros((self._last()[0], self.m, self.m), dtype=np.complex64)
+        vec = np.zeros((self._last()[0], self.ms, self.ms), dtype=np.complex64)
         _check(lib().crsdr_doa_fetch_subspace(self._h, _p(vec.view(np.float32), C.c_float)))
         return vec
+
+    def set_smoothing(self, sx: int, sy: int, flags: int = 0):
+        """crsdr_doa_set_smoothing: from the next submit on, the covariance averaged over its sx x sy sub-arrays (SMOOTH_FB: and with its
+        backward image) feeds the subspace; sv and vec then have ms = sx * sy entries.  (mx, my) with flags 0: off.  Waits for the
+        device if a submit was made, and discards that submit's results."""
+        _check(lib().crsdr_doa_set_smoothing(self._h, int(sx), int(sy), int(flags)))
+        self.ms = int(sx) * int(sy)
+
+    def fetch_smoothed(self) -> np.ndarray:
+        """rs [nest][ms][ms] complex64 of the last submit."""
+        rs = np.zeros((self._last()[0], self.ms, self.ms), dtype=np.complex64)
+        _check(lib().crsdr_doa_fetch_smoothed(self._h, _p(rs.view(np.float32), C.c_float)))
+        return rs
+
+    def set_order(self, criterion: int, kmin: int = 1, kmax: int | None = None, limit_directions: bool = False):
+        """crsdr_doa_set_order: from the next submit on, every estimate's source count k_e (ORDER_MDL / ORDER_AIC over kmin .. kmax,
+        kmax = ms - 1 by default) replaces k in its scan; limit_directions: set_peaks reports at most k_e.  ORDER_OFF: off."""
+        kmax = self.ms - 1 if kmax is None else int(kmax)
+        _check(lib().crsdr_doa_set_order(self._h, int(criterion), int(kmin), kmax, int(bool(limit_directions))))
+        self.order = (int(kmin), kmax) if criterion != ORDER_OFF else None
+
+    def fetch_order(self) -> dict:
+        """Waits for the last submit.  k [nest], criterion [nest][kmax - kmin + 1]."""
+        n = self._last()[0]
+        nc = self.order[1] - self.order[0] + 1 if self.order else 0
+        k, crit = np.zeros(n, dtype=np.int32), np.zeros((n, nc), dtype=np.float32)
+        _check(lib().crsdr_doa_fetch_order(self._h, _p(k, C.c_int32), _p(crit, C.c_float)))
+        return {"k": k, "criterion": crit}
+
+    def order_buffers(self) -> dict:
+        ptrs = [C.c_void_p() for _ in range(2)]
+        _check(lib().crsdr_doa_order_buffers(self._h, *[C.byref(p) for p in ptrs]))
+        return dict(zip(("k", "criterion"), [p.value for p in ptrs]))
 
     def last_launches(self) -> int:
         return self._last()[1]

@@ -4,6 +4,7 @@
 #include "../../include/crsdr.h"
 #include "kernels.hpp"
 #include "doa.hpp"
+#include "smooth.hpp"
 #include "beams.hpp"
 
 #include <hip/hip_runtime.h>
@@ -705,6 +706,63 @@ extern "C" int crsdr_pmusic2d(float *pm, const float *vec, int m, int k, float d
     HIP_TRY(hipGetLastError());
     if (mem_kind == CRSDR_MEM_HOST) HIP_TRY(hipMemcpy(pm, d_p, pb, hipMemcpyDeviceToHost));
     else HIP_TRY(hipDeviceSynchronize());
+    return CRSDR_OK;
+}
+
+static bool smooth_shape_ok(int mx, int my, int sx, int sy, uint32_t flags)
+{
+    return mx >= 1 && my >= 1 && (long long)mx * my >= 2 && (long long)mx * my <= music::MAX_M && sx >= 1 && sx <= mx && sy >= 1 && sy <= my &&
+           sx * sy >= 2 && !(flags & ~(uint32_t)CRSDR_SMOOTH_FB);
+}
+
+extern "C" int crsdr_smooth_covariance(float *rs, const float *rxx, int mx, int my, int sx, int sy, uint32_t flags, int mem_kind)
+{
+    if (!rs || !rxx || !smooth_shape_ok(mx, my, sx, sy, flags))
+        return fail(CRSDR_EINVAL, "smooth_covariance: need rs, rxx, m = mx*my in [2, %d], 1 <= sx <= mx, 1 <= sy <= my, sx*sy >= 2, flags = 0 or CRSDR_SMOOTH_FB",
+                    music::MAX_M);
+    if (mem_kind != CRSDR_MEM_HOST && mem_kind != CRSDR_MEM_DEVICE) return fail(CRSDR_EINVAL, "smooth_covariance: mem_kind = %d", mem_kind);
+    { int rc_ = require_device(); if (rc_) return rc_; }
+    std::lock_guard<std::mutex> lock_(g_op.mu);
+    const size_t m = (size_t)mx * my, ms = (size_t)sx * sy, mm = sizeof(float2) * m * m, sb = sizeof(float2) * ms * ms;
+    const float2 *d_r = (const float2 *)rxx;
+    float2 *d_s = (float2 *)rs;
+    if (mem_kind == CRSDR_MEM_HOST) {
+        OP_RESERVE(0, mm); OP_RESERVE(1, sb);
+        HIP_TRY(hipMemcpy(g_op.buf[0], rxx, mm, hipMemcpyHostToDevice));
+        d_r = (const float2 *)g_op.buf[0];
+        d_s = (float2 *)g_op.buf[1];
+    }
+    hipLaunchKernelGGL(smooth::k_smooth_covariance, dim3(1), dim3(smooth::SM_THREADS), 0, 0, d_r, mx, my, sx, sy, flags, d_s);
+    HIP_TRY(hipGetLastError());
+    if (mem_kind == CRSDR_MEM_HOST) HIP_TRY(hipMemcpy(rs, d_s, sb, hipMemcpyDeviceToHost));
+    else HIP_TRY(hipDeviceSynchronize());
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_source_order(int32_t *k, float *criterion_values, const float *sv, int m, int64_t nsnap, int criterion, int kmin, int kmax, int mem_kind)
+{
+    if (!k || !sv || m < 2 || m > music::MAX_M || nsnap < 1 || (criterion != CRSDR_ORDER_MDL && criterion != CRSDR_ORDER_AIC) || kmin < 1 || kmin > kmax ||
+        kmax >= m)
+        return fail(CRSDR_EINVAL, "source_order: need k, sv, 2 <= m <= %d, nsnap >= 1, criterion MDL or AIC, 1 <= kmin <= kmax < m", music::MAX_M);
+    if (mem_kind != CRSDR_MEM_HOST && mem_kind != CRSDR_MEM_DEVICE) return fail(CRSDR_EINVAL, "source_order: mem_kind = %d", mem_kind);
+    { int rc_ = require_device(); if (rc_) return rc_; }
+    std::lock_guard<std::mutex> lock_(g_op.mu);
+    const size_t nc = (size_t)(kmax - kmin + 1);
+    // one staging buffer: sv [MAX_M] float, crit [MAX_M] float, k
+    OP_RESERVE(2, (2 * music::MAX_M) * sizeof(float) + sizeof(int32_t));
+    float *s_sv = (float *)g_op.buf[2], *s_crit = s_sv + music::MAX_M;
+    int32_t *s_k = (int32_t *)(s_crit + music::MAX_M);
+    const bool host = mem_kind == CRSDR_MEM_HOST;
+    if (host) HIP_TRY(hipMemcpy(s_sv, sv, sizeof(float) * (size_t)m, hipMemcpyHostToDevice));
+    float *d_crit = host || !criterion_values ? s_crit : criterion_values;
+    hipLaunchKernelGGL(smooth::k_doa_order, dim3(1), dim3(64), 0, 0, host ? (const float *)s_sv : sv, m, (double)nsnap, criterion, kmin, kmax, host ? s_k : k,
+                       d_crit);
+    HIP_TRY(hipGetLastError());
+    if (host) {
+        HIP_TRY(hipMemcpy(k, s_k, sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (criterion_values) HIP_TRY(hipMemcpy(criterion_values, s_crit, sizeof(float) * nc, hipMemcpyDeviceToHost));
+    } else
+        HIP_TRY(hipDeviceSynchronize());
     return CRSDR_OK;
 }
 
@@ -1793,14 +1851,14 @@ extern "C" int crsdr_plan_kernel_times(crsdr_plan *p, int which, float *ms, int 
 //      `frames` packets, for a whole batch of packets where a plan left them.  Every buffer is allocated at create; a submit is five
 //      launches on one stream whatever the batch size (covariance partials, their reducer, subspace, scan, peak), no lock, no
 //      allocation, no synchronisation.  crsdr_doa_set_peaks allocates what the local-peak pass needs and adds its two launches,
-//      crsdr_doa_set_beams what the beams need and theirs (beams.hpp).
+//      crsdr_doa_set_beams what the beams need and theirs (beams.hpp), crsdr_doa_set_smoothing and crsdr_doa_set_order theirs and one
+//      launch each (smooth.hpp): behind the reducer, and between the subspace and the scan.
 // ================================================================================================
 struct crsdr_doa {
     int nrows = 0, B = 0, m = 0, device = 0, max_batch = 1, frames = 1, k = 1, mx = 0, my = 0, ncx = 0, ncy = 0;
     float d = 0.f;
     uint32_t flags = 0;
     int nt = 1, ntri = 1, spb = 1, nwg = 0;        // operand blocks, tiles, K slices per packet, scan workgroups per estimate
-    size_t lds_sub = 0, lds_scan = 0;
     hipStream_t own_stream = nullptr, last_stream = nullptr;
     int *d_partial = nullptr, *d_info = nullptr;
     int2 *d_psum = nullptr;
@@ -1824,7 +1882,40 @@ struct crsdr_doa {
     float2 *d_bw = nullptr, *d_beams = nullptr;
     float *d_bpow = nullptr, *d_bangles = nullptr;
     bool beams_submitted = false;
+    // crsdr_doa_set_smoothing: sub-arrays of sx x sy elements (ms of them; ms = m while off: ms is the subspace's size either way), the
+    // smoothed covariances [nest][ms][ms]; last_ms: of the last submit
+    bool smooth_on = false, smooth_submitted = false;
+    int sx = 0, sy = 0, ms = 0, last_ms = 0;
+    uint32_t smooth_flags = 0;
+    float2 *d_rs = nullptr;
+    // crsdr_doa_set_order: criterion (0 = off), the candidates kmin .. kmax, whether the directions are capped by the count;
+    // k [nest], criterion values [nest][kmax - kmin + 1]
+    int order_crit = 0, kmin = 0, kmax = 0, limit_dirs = 0;
+    int32_t *d_korder = nullptr;
+    float *d_crit = nullptr;
+    bool order_submitted = false;
 };
+
+// The dynamic LDS limits of the subspace and the scan are function attributes, shared by every live object: each create (and each
+// crsdr_doa_set_order) sets them to the most any object can ask for (m = 64, one signal vector), so that a small object created after
+// a large one cannot lower the limit under it.
+constexpr int kDoaSubLdsMax = (int)(2 * sizeof(double2) * music::MAX_M * music::MAX_M);
+constexpr int kDoaScanLdsMax = (int)(sizeof(float2) * (music::MAX_M * (music::MAX_M - 1) + music::MAX_M * music::PT));
+
+static void doa_free_smooth(crsdr_doa *q)
+{
+    if (q->d_rs) (void)hipFree(q->d_rs);
+    q->d_rs = nullptr;
+    q->smooth_on = q->smooth_submitted = false; q->sx = q->mx; q->sy = q->my; q->ms = q->m; q->smooth_flags = 0;
+}
+
+static void doa_free_order(crsdr_doa *q)
+{
+    if (q->d_korder) (void)hipFree(q->d_korder);
+    if (q->d_crit) (void)hipFree(q->d_crit);
+    q->d_korder = nullptr; q->d_crit = nullptr;
+    q->order_crit = q->kmin = q->kmax = q->limit_dirs = 0; q->order_submitted = false;
+}
 
 static void doa_free_peaks(crsdr_doa *q)
 {
@@ -1849,6 +1940,8 @@ static void doa_free(crsdr_doa *q)
     if (q->submitted) (void)hipDeviceSynchronize();      // (the last submit's stream may be the caller's, and gone)
     doa_free_peaks(q);
     doa_free_beams(q);
+    doa_free_smooth(q);
+    doa_free_order(q);
     void *bufs[] = {q->d_partial, q->d_info, q->d_psum, q->d_rxx, q->d_vec, q->d_sv, q->d_peakv, q->d_pm, q->d_peak, q->d_wgbest};
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (q->own_stream) (void)hipStreamDestroy(q->own_stream);
@@ -1871,8 +1964,8 @@ static int doa_alloc(crsdr_doa *q)
     HIP_TRY(hipMalloc((void **)&q->d_peakv, sizeof(float) * nest));
     if (q->flags & CRSDR_DOA_KEEP_SPECTRUM) HIP_TRY(hipMalloc((void **)&q->d_pm, sizeof(float) * nest * grid));
     // the kernels' dynamic LDS limits: once, here (the subspace takes 128 KiB at m = 64)
-    HIP_TRY(hipFuncSetAttribute((const void *)doa::k_doa_subspace, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q->lds_sub));
-    HIP_TRY(hipFuncSetAttribute((const void *)doa::k_doa_scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q->lds_scan));
+    HIP_TRY(hipFuncSetAttribute((const void *)doa::k_doa_subspace, hipFuncAttributeMaxDynamicSharedMemorySize, kDoaSubLdsMax));
+    HIP_TRY(hipFuncSetAttribute((const void *)doa::k_doa_scan<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kDoaScanLdsMax));
     return CRSDR_OK;
 }
 
@@ -1906,8 +1999,7 @@ extern "C" int crsdr_doa_create(crsdr_doa **doa, const crsdr_doa_desc *desc)
     const int spb_min = (q->B + 65535) / 65536, spb_max = std::max(spb_min, std::min(64, q->B / 512));
     q->spb = std::min(std::max((1024 + mb - 1) / mb, spb_min), spb_max);
     q->nwg = (int)(((size_t)q->ncx * q->ncy + music::PT - 1) / music::PT);
-    q->lds_sub = 2 * sizeof(double2) * (size_t)m * m;
-    q->lds_scan = sizeof(float2) * ((size_t)m * (m - q->k) + (size_t)m * music::PT);
+    q->sx = q->mx; q->sy = q->my; q->ms = m;
     int rc = doa_alloc(q);
     if (rc) { doa_free(q); return rc; }
     *doa = q;
@@ -1945,12 +2037,29 @@ static int doa_launch(crsdr_doa *q, const int8_t *packets, size_t packet_stride,
     hipLaunchKernelGGL(doa::k_doa_cov_reduce, dim3((unsigned)q->ntri, nest), dim3(256), 0, S, (const int *)q->d_partial, (const int2 *)q->d_psum, (int)slices, q->ntri,
                        q->nrows, q->B, q->frames, q->d_rxx);
     HIP_TRY(hipGetLastError()); ++launches;
-    hipLaunchKernelGGL(doa::k_doa_subspace, dim3(nest), dim3(music::JT), q->lds_sub, S, (const float2 *)q->d_rxx, q->m, q->d_sv, q->d_vec, q->d_info);
+    // smoothing on: subspace, order, scan and peaks work on rs, an sx x sy array of M = ms elements (off: sx = mx, sy = my, M = m)
+    const int M = q->ms;
+    const float2 *cov = q->d_rxx;
+    if (q->smooth_on) {
+        hipLaunchKernelGGL(smooth::k_doa_smooth, dim3(nest), dim3(smooth::SM_THREADS), 0, S, (const float2 *)q->d_rxx, q->mx, q->my, q->sx, q->sy, q->smooth_flags,
+                           q->d_rs);
+        HIP_TRY(hipGetLastError()); ++launches;
+        cov = q->d_rs;
+    }
+    hipLaunchKernelGGL(doa::k_doa_subspace, dim3(nest), dim3(music::JT), 2 * sizeof(double2) * (size_t)M * M, S, cov, M, q->d_sv, q->d_vec, q->d_info);
     HIP_TRY(hipGetLastError()); ++launches;
     // with peaks on, the scan always leaves its spectrum: the kept one, or the workspace
     float *pm = q->npeaks && !q->d_pm ? q->d_pmws : q->d_pm;
-    hipLaunchKernelGGL(doa::k_doa_scan, dim3((unsigned)q->nwg, nest), dim3(music::PT), q->lds_scan, S, (const float2 *)q->d_vec, q->m, q->k, q->d, q->mx, q->my, q->ncx,
-                       q->ncy, pm, q->d_wgbest);
+    if (q->order_crit) {
+        hipLaunchKernelGGL(smooth::k_doa_order, dim3(nest), dim3(64), 0, S, (const float *)q->d_sv, M, (double)q->frames * (double)(q->B / 2), q->order_crit, q->kmin,
+                           q->kmax, q->d_korder, q->d_crit);
+        HIP_TRY(hipGetLastError()); ++launches;
+        // the LDS of the most noise vectors an estimate can have, M - kmin
+        hipLaunchKernelGGL(doa::k_doa_scan<true>, dim3((unsigned)q->nwg, nest), dim3(music::PT), sizeof(float2) * ((size_t)M * (M - q->kmin) + (size_t)M * music::PT), S,
+                           (const float2 *)q->d_vec, M, q->k, q->d, q->sx, q->sy, q->ncx, q->ncy, pm, q->d_wgbest, (const int32_t *)q->d_korder);
+    } else
+        hipLaunchKernelGGL(doa::k_doa_scan<false>, dim3((unsigned)q->nwg, nest), dim3(music::PT), sizeof(float2) * ((size_t)M * (M - q->k) + (size_t)M * music::PT), S,
+                           (const float2 *)q->d_vec, M, q->k, q->d, q->sx, q->sy, q->ncx, q->ncy, pm, q->d_wgbest, (const int32_t *)nullptr);
     HIP_TRY(hipGetLastError()); ++launches;
     hipLaunchKernelGGL(doa::k_doa_peak, dim3(nest), dim3(256), 0, S, (const unsigned long long *)q->d_wgbest, q->nwg, q->ncy, q->d_peak, q->d_peakv);
     HIP_TRY(hipGetLastError()); ++launches;
@@ -1959,7 +2068,7 @@ static int doa_launch(crsdr_doa *q, const int8_t *packets, size_t packet_stride,
                            q->ncy, q->radius, q->npeaks, q->d_cand);
         HIP_TRY(hipGetLastError()); ++launches;
         hipLaunchKernelGGL(doa::k_doa_peaks_merge, dim3(nest), dim3(doa::LP_THREADS), 0, S, (const unsigned long long *)q->d_cand, q->lp_tiles * q->npeaks, q->ncy,
-                           q->npeaks, q->d_found, q->d_dirs, q->d_dirv);
+                           q->npeaks, q->d_found, q->d_dirs, q->d_dirv, (const int32_t *)(q->order_crit && q->limit_dirs ? q->d_korder : nullptr));
         HIP_TRY(hipGetLastError()); ++launches;
     }
     if (q->beam_mode) {
@@ -1974,6 +2083,7 @@ static int doa_launch(crsdr_doa *q, const int8_t *packets, size_t packet_stride,
     }
     q->last_stream = S; q->last_nest = (int)nest; q->last_nblocks = nblocks; q->last_launches = launches; q->submitted = true;
     q->peaks_submitted = q->npeaks > 0; q->beams_submitted = q->beam_mode != 0;
+    q->last_ms = M; q->smooth_submitted = q->smooth_on; q->order_submitted = q->order_crit != 0;
     return CRSDR_OK;
 }
 
@@ -2009,12 +2119,12 @@ extern "C" int crsdr_doa_fetch(crsdr_doa *q, int32_t *peak, float *peak_value, f
     if (rxx && !(q->flags & CRSDR_DOA_KEEP_RXX)) return fail(CRSDR_EINVAL, "doa_fetch: rxx asked of a doa created without CRSDR_DOA_KEEP_RXX");
     if (!q->submitted) return fail(CRSDR_ESTATE, "doa_fetch: nothing submitted");
     HIP_TRY(hipSetDevice(q->device));
-    const size_t nest = (size_t)q->last_nest, m = (size_t)q->m;
+    const size_t nest = (size_t)q->last_nest, m = (size_t)q->m, ms = (size_t)q->last_ms;
     hipStream_t S = q->last_stream;
     int info[2 * kMaxBatch];
     if (peak) HIP_TRY(hipMemcpyAsync(peak, q->d_peak, sizeof(int32_t) * nest * 2, hipMemcpyDeviceToHost, S));
     if (peak_value) HIP_TRY(hipMemcpyAsync(peak_value, q->d_peakv, sizeof(float) * nest, hipMemcpyDeviceToHost, S));
-    if (sv) HIP_TRY(hipMemcpyAsync(sv, q->d_sv, sizeof(float) * nest * m, hipMemcpyDeviceToHost, S));
+    if (sv) HIP_TRY(hipMemcpyAsync(sv, q->d_sv, sizeof(float) * nest * ms, hipMemcpyDeviceToHost, S));
     if (status) HIP_TRY(hipMemcpyAsync(info, q->d_info, sizeof(int) * nest * 2, hipMemcpyDeviceToHost, S));
     if (pm) HIP_TRY(hipMemcpyAsync(pm, q->d_pm, sizeof(float) * nest * (size_t)q->ncx * q->ncy, hipMemcpyDeviceToHost, S));
     if (rxx) HIP_TRY(hipMemcpyAsync(rxx, q->d_rxx, sizeof(float2) * nest * m * m, hipMemcpyDeviceToHost, S));
@@ -2106,6 +2216,9 @@ extern "C" int crsdr_doa_set_beams(crsdr_doa *q, int mode, float loading, int nf
     if (mode == CRSDR_BEAM_MVDR && !(loading >= 1e-6f && loading <= 1.0f)) return fail(CRSDR_EINVAL, "doa_set_beams: loading = %g (1e-6..1)", (double)loading);
     if (mode != CRSDR_BEAM_OFF && (nfixed < 0 || nfixed > beams::MAX_BEAMS)) return fail(CRSDR_EINVAL, "doa_set_beams: nfixed = %d (0..%d)", nfixed, beams::MAX_BEAMS);
     if (mode != CRSDR_BEAM_OFF && nfixed > 0 && !fixed_angles) return fail(CRSDR_EINVAL, "doa_set_beams: %d fixed directions and no angles", nfixed);
+    if (mode != CRSDR_BEAM_OFF && q->ms < q->m)
+        return fail(CRSDR_ESTATE, "doa_set_beams: smoothing over %d x %d sub-arrays is on (crsdr_doa_set_smoothing): the weights are %d-vectors and there is no %d x %d subspace",
+                    q->sx, q->sy, q->m, q->m, q->m);
     HIP_TRY(hipSetDevice(q->device));
     if (q->submitted) HIP_TRY(hipDeviceSynchronize());   // the buffers may be in use (the last submit's stream may be the caller's, and gone)
     doa_free_beams(q);
@@ -2155,8 +2268,87 @@ extern "C" int crsdr_doa_fetch_subspace(crsdr_doa *q, float *vec)
     if (!q || !vec) return fail(CRSDR_EINVAL, "doa_fetch_subspace: NULL doa or vec");
     if (!q->submitted) return fail(CRSDR_ESTATE, "doa_fetch_subspace: nothing submitted");
     HIP_TRY(hipSetDevice(q->device));
-    HIP_TRY(hipMemcpyAsync(vec, q->d_vec, sizeof(float2) * (size_t)q->last_nest * (size_t)q->m * q->m, hipMemcpyDeviceToHost, q->last_stream));
+    HIP_TRY(hipMemcpyAsync(vec, q->d_vec, sizeof(float2) * (size_t)q->last_nest * (size_t)q->last_ms * q->last_ms, hipMemcpyDeviceToHost, q->last_stream));
     HIP_TRY(hipStreamSynchronize(q->last_stream));
+    return CRSDR_OK;
+}
+
+// ---- spatial smoothing and the source count (smooth.hpp) ----
+extern "C" int crsdr_doa_set_smoothing(crsdr_doa *q, int sx, int sy, uint32_t flags)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_set_smoothing: NULL doa");
+    if (!smooth_shape_ok(q->mx, q->my, sx, sy, flags))
+        return fail(CRSDR_EINVAL, "doa_set_smoothing: sub-arrays of %d x %d in an array of %d x %d, flags = 0x%x (1 <= sx <= mx, 1 <= sy <= my, sx * sy >= 2, CRSDR_SMOOTH_FB)", sx,
+                    sy, q->mx, q->my, flags);
+    const int ms = sx * sy;
+    if (q->k >= ms) return fail(CRSDR_EINVAL, "doa_set_smoothing: k = %d sources need sub-arrays of more than %d elements (%d x %d)", q->k, q->k, sx, sy);
+    if (q->order_crit && q->kmax >= ms)
+        return fail(CRSDR_EINVAL, "doa_set_smoothing: the order range ends at kmax = %d, sub-arrays of %d x %d have %d elements", q->kmax, sx, sy, ms);
+    if (ms < q->m && q->beam_mode)
+        return fail(CRSDR_ESTATE, "doa_set_smoothing: beams are on (crsdr_doa_set_beams): their weights are %d-vectors from the %d x %d subspace: turn them off first", q->m,
+                    q->m, q->m);
+    HIP_TRY(hipSetDevice(q->device));
+    if (q->submitted) HIP_TRY(hipDeviceSynchronize());   // the buffers may be in use (the last submit's stream may be the caller's, and gone)
+    doa_free_smooth(q);
+    q->submitted = false;                                // sv and vec change their shape: what the last submit left is gone
+    if (ms == q->m && !flags) return CRSDR_OK;
+    const size_t nest = (size_t)(q->max_batch / q->frames);
+    if (hipMalloc((void **)&q->d_rs, sizeof(float2) * nest * ms * ms) != hipSuccess)
+        return fail(CRSDR_ENOMEM, "doa_set_smoothing: %zu bytes of device memory", sizeof(float2) * nest * ms * ms);
+    q->smooth_on = true; q->sx = sx; q->sy = sy; q->ms = ms; q->smooth_flags = flags;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_fetch_smoothed(crsdr_doa *q, float *rs)
+{
+    if (!q || !rs) return fail(CRSDR_EINVAL, "doa_fetch_smoothed: NULL doa or rs");
+    if (!q->smooth_on) return fail(CRSDR_ESTATE, "doa_fetch_smoothed: no crsdr_doa_set_smoothing");
+    if (!q->smooth_submitted) return fail(CRSDR_ESTATE, "doa_fetch_smoothed: nothing submitted since crsdr_doa_set_smoothing");
+    HIP_TRY(hipSetDevice(q->device));
+    HIP_TRY(hipMemcpyAsync(rs, q->d_rs, sizeof(float2) * (size_t)q->last_nest * (size_t)q->ms * q->ms, hipMemcpyDeviceToHost, q->last_stream));
+    HIP_TRY(hipStreamSynchronize(q->last_stream));
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_set_order(crsdr_doa *q, int criterion, int kmin, int kmax, int limit_directions)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_set_order: NULL doa");
+    if (criterion != CRSDR_ORDER_OFF && criterion != CRSDR_ORDER_MDL && criterion != CRSDR_ORDER_AIC) return fail(CRSDR_EINVAL, "doa_set_order: criterion = %d", criterion);
+    if (criterion != CRSDR_ORDER_OFF && (kmin < 1 || kmin > kmax || kmax >= q->ms))
+        return fail(CRSDR_EINVAL, "doa_set_order: k in %d .. %d (1 <= kmin <= kmax < %d, the subspace's size)", kmin, kmax, q->ms);
+    HIP_TRY(hipSetDevice(q->device));
+    if (q->submitted) HIP_TRY(hipDeviceSynchronize());   // the buffers may be in use (the last submit's stream may be the caller's, and gone)
+    doa_free_order(q);
+    if (criterion == CRSDR_ORDER_OFF) return CRSDR_OK;
+    const size_t nest = (size_t)(q->max_batch / q->frames), nc = (size_t)(kmax - kmin + 1);
+    HIP_TRY(hipFuncSetAttribute((const void *)doa::k_doa_scan<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kDoaScanLdsMax));
+    if (hipMalloc((void **)&q->d_korder, sizeof(int32_t) * nest) != hipSuccess || hipMalloc((void **)&q->d_crit, sizeof(float) * nest * nc) != hipSuccess) {
+        doa_free_order(q);
+        return fail(CRSDR_ENOMEM, "doa_set_order: device memory for %zu estimates of %zu candidates", nest, nc);
+    }
+    q->order_crit = criterion; q->kmin = kmin; q->kmax = kmax; q->limit_dirs = limit_directions != 0;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_fetch_order(crsdr_doa *q, int32_t *k, float *criterion_values)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_fetch_order: NULL doa");
+    if (!q->order_crit) return fail(CRSDR_ESTATE, "doa_fetch_order: no crsdr_doa_set_order");
+    if (!q->order_submitted) return fail(CRSDR_ESTATE, "doa_fetch_order: nothing submitted since crsdr_doa_set_order");
+    HIP_TRY(hipSetDevice(q->device));
+    const size_t nest = (size_t)q->last_nest, nc = (size_t)(q->kmax - q->kmin + 1);
+    hipStream_t S = q->last_stream;
+    if (k) HIP_TRY(hipMemcpyAsync(k, q->d_korder, sizeof(int32_t) * nest, hipMemcpyDeviceToHost, S));
+    if (criterion_values) HIP_TRY(hipMemcpyAsync(criterion_values, q->d_crit, sizeof(float) * nest * nc, hipMemcpyDeviceToHost, S));
+    HIP_TRY(hipStreamSynchronize(S));
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_order_buffers(crsdr_doa *q, void **k, void **criterion_values)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_order_buffers: NULL doa");
+    if (k) *k = q->d_korder;
+    if (criterion_values) *criterion_values = q->d_crit;
     return CRSDR_OK;
 }
 

@@ -9,6 +9,8 @@
 //   k_doa_subspace    music::herm_subspace per estimate (one workgroup each, as k_herm_subspace).
 //   k_doa_scan        music::pmusic2d_point per grid point and estimate; the workgroup's largest pm leaves as one 64-bit key.
 //   k_doa_peak        grid (estimate): the largest key -> (cx, cy) and its value.
+// With crsdr_doa_set_smoothing the subspace works on the smoothed covariance (smooth.hpp: k_doa_smooth behind the reducer), with
+// crsdr_doa_set_order the scan takes every estimate's source count from k_doa_order's output (k_doa_scan<true>).
 //
 // Peak order: pm = (a2 / den)^2 is never negative, so the bit pattern of the float orders like the value; the key is
 // (value bits << 32) | (0xFFFFFFFF - row-major index): its maximum is the largest value at the LOWEST index, whatever order the keys are
@@ -192,13 +194,18 @@ __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v,
 }
 
 // grid (ceil(Cx Cy / PT), nest), PT threads = one wave.  vec [nest][M][M]; pm [nest][Cx][Cy] or NULL; wgbest [nest][gridDim.x].
+// PER_EST (crsdr_doa_set_order): estimate e takes its source count from korder [nest] (in [kmin, M - 1]: the dynamic LDS covers
+// M - kmin noise vectors) instead of k; pmusic2d_point is the same either way, so its pm has the bits of a fixed-k = korder[e] scan.
+template <bool PER_EST>
 __global__ __launch_bounds__(music::PT) void k_doa_scan(const float2 *__restrict__ vec, int M, int k, float d, int Mx, int My, int Cx, int Cy,
-                                                        float *__restrict__ pm, unsigned long long *__restrict__ wgbest)
+                                                        float *__restrict__ pm, unsigned long long *__restrict__ wgbest,
+                                                        const int32_t *__restrict__ korder)
 {
     static_assert(music::PT == 64, "the workgroup's peak is reduced with wave shuffles");
     const size_t e = blockIdx.y;
     const int g = blockIdx.x * music::PT + threadIdx.x;
     const bool live = g < Cx * Cy;
+    if constexpr (PER_EST) k = korder[e];
     const float v = music::pmusic2d_point(vec + e * M * M, M, M, k, M - k, d, Mx, My, Cx, Cy, g, live);
     if (pm && live) pm[e * Cx * Cy + g] = v;
     unsigned long long key = live ? peak_key(v, g) : 0ull;
@@ -328,9 +335,10 @@ __global__ __launch_bounds__(LP_THREADS) void k_doa_local_peaks(const float *__r
 
 // grid (nest), LP_THREADS threads: the `count` largest of the ncand = tiles * count candidates of an estimate ->
 // found [nest], peaks [nest][count][2] = (cx, cy), values [nest][count]; the slots after found hold (-1, -1) and -1.
+// cap [nest] or NULL: at most cap[e] of them (crsdr_doa_set_order with limit_directions: the estimate's source count).
 __global__ __launch_bounds__(LP_THREADS) void k_doa_peaks_merge(const unsigned long long *__restrict__ cand, int ncand, int Cy, int count,
                                                                 int32_t *__restrict__ found, int32_t *__restrict__ peaks,
-                                                                float *__restrict__ values)
+                                                                float *__restrict__ values, const int32_t *__restrict__ cap)
 {
     __shared__ unsigned long long red[LP_THREADS / 64];
     const size_t e = blockIdx.x;
@@ -352,7 +360,8 @@ __global__ __launch_bounds__(LP_THREADS) void k_doa_peaks_merge(const unsigned l
         }
     }
     unsigned long long mine;
-    const int n = lp_top(keys, count, red, mine);
+    const int take = cap ? min(count, max(cap[e], 0)) : count;
+    const int n = lp_top(keys, take, red, mine);
     if (tid < count) {
         const int g = (int)(0xFFFFFFFFu - (uint32_t)mine);
         const size_t s = e * count + tid;

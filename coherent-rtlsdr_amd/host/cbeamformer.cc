@@ -37,7 +37,7 @@ int pmusic2dvec(const cmatrix &U, int M, int K, float d, int Mx, int My, int Cx,
 }
 
 batch::batch(int nrows, int blocksize, int max_batch, int K, int frames, bool keep_spectrum, float d, int Mx, int My, int Cx, int Cy, int device)
-    : m(nrows - 1), cx(Cx), cy(Cy), half(blocksize / 2), nframes(frames > 0 ? frames : 1), keep(keep_spectrum)
+    : m(nrows - 1), ms(nrows - 1), cx(Cx), cy(Cy), half(blocksize / 2), nframes(frames > 0 ? frames : 1), keep(keep_spectrum)
 {
     crsdr_doa_desc desc = {};
     desc.nrows = nrows; desc.blocksize = blocksize; desc.device = device; desc.max_batch = max_batch; desc.frames = frames; desc.k = K;
@@ -81,14 +81,34 @@ int batch::set_beams(int mode, float loading, int nfixed, const float *fixed_ang
     return rc;
 }
 
+int batch::set_smoothing(int sx, int sy, bool fb)
+{
+    int rc = doa ? crsdr_doa_set_smoothing(doa, sx, sy, fb ? CRSDR_SMOOTH_FB : 0u) : CRSDR_ESTATE;
+    if (!rc) ms = sx * sy;
+    if (rc && doa) std::fprintf(stderr, "cbeamformer::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::set_order(int criterion, int kmin, int kmax, bool limit_directions)
+{
+    int rc = doa ? crsdr_doa_set_order(doa, criterion, kmin, kmax > 0 ? kmax : ms - 1, limit_directions ? 1 : 0) : CRSDR_ESTATE;
+    if (!rc) counted = criterion != CRSDR_ORDER_OFF;
+    if (rc && doa) std::fprintf(stderr, "cbeamformer::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
 int batch::fetch(bool want_beams)
 {
     int nest = 0;
     int rc = doa ? crsdr_doa_last_submit(doa, &nest, nullptr) : CRSDR_ESTATE;
     if (!rc) {
-        peak.assign(2 * (size_t)nest, 0); peak_value.assign(nest, 0.f); sv.assign((size_t)nest * m, 0.f); status.assign(nest, 0);
+        peak.assign(2 * (size_t)nest, 0); peak_value.assign(nest, 0.f); sv.assign((size_t)nest * ms, 0.f); status.assign(nest, 0);
         if (keep) pm.assign((size_t)nest * cx * cy, 0.f);
         rc = crsdr_doa_fetch(doa, peak.data(), peak_value.data(), sv.data(), status.data(), keep ? pm.data() : nullptr, nullptr);
+    }
+    if (!rc && counted) {
+        order.assign(nest, 0);
+        rc = crsdr_doa_fetch_order(doa, order.data(), nullptr);
     }
     if (!rc && npeaks) {
         found.assign(nest, 0); directions.assign((size_t)nest * npeaks * 2, -1); direction_values.assign((size_t)nest * npeaks, -1.f);

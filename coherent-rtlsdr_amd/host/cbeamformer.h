@@ -30,7 +30,8 @@ int pmusic2dvec(const cmatrix &U, int M, int K, float d, int Mx, int My, int Cx,
 // it reads); fetch() waits and fills the vectors below.  One submit at a time: fetch before the next.
 class batch {
     crsdr_doa *doa = nullptr;
-    int m = 0, cx = 0, cy = 0, npeaks = 0, nbeams = 0, half = 0, nframes = 1;
+    int m = 0, ms = 0, cx = 0, cy = 0, npeaks = 0, nbeams = 0, half = 0, nframes = 1;      // ms: the subspace's size (m, or a sub-array's)
+    bool counted = false;
     bool keep = false;
 public:
     // nrows x blocksize: the packets' geometry (1 + Mx * My rows); keep_spectrum: fetch() also fills pm
@@ -49,12 +50,21 @@ public:
     // loading as a fraction of the largest singular value) -- the count of set_peaks, or the one peak -- or toward nfixed (alpha, beta)
     // pairs in radians.  CRSDR_BEAM_OFF: off.  With following beams on, set_peaks is refused: turn them off first.
     int set_beams(int mode, float loading = 1e-2f, int nfixed = 0, const float *fixed_angles = nullptr);
+    // from the next submit on, the covariance averaged over its sx x sy sub-arrays (fb: and with its backward image) feeds the subspace
+    // (crsdr_doa_set_smoothing: coherent arrivals); sv then has sx * sy entries per estimate.  (Mx, My) without fb: off.  Discards the
+    // last submit's results.  Refused while true sub-arrays and beams would be on together.
+    int set_smoothing(int sx, int sy, bool fb = true);
+    // from the next submit on, every estimate's source count (crsdr_doa_set_order: CRSDR_ORDER_MDL / CRSDR_ORDER_AIC over kmin .. kmax)
+    // replaces K in its scan; limit_directions: set_peaks reports at most that many.  CRSDR_ORDER_OFF: off.
+    int set_order(int criterion, int kmin = 1, int kmax = 0, bool limit_directions = false);      // kmax = 0: the largest, size - 1
     // want_beams: also copy the beams' samples out (blocks x slots x blocksize / 2 complex floats)
     int fetch(bool want_beams = false);
     int estimates() const { return (int)status.size(); }
     std::vector<int32_t> peak;                       // [estimates][2]: (cx, cy) of the largest pm
-    std::vector<float> peak_value, sv, pm;           // [estimates], [estimates][M], [estimates][Cx][Cy] (keep_spectrum)
+    std::vector<float> peak_value, sv, pm;           // [estimates], [estimates][M or sx * sy], [estimates][Cx][Cy] (keep_spectrum)
     std::vector<int32_t> status;                     // 0 = converged
+    int subspace_size() const { return ms; }
+    std::vector<int32_t> order;                      // with set_order: [estimates], the source counts
     // with set_peaks: local peaks found per estimate (<= count), their (cx, cy) [estimates][count][2] in descending order and their pm
     // [estimates][count]; slots from found on hold (-1, -1) and -1
     std::vector<int32_t> found, directions;

@@ -57,6 +57,8 @@ int main(int argc, char **argv)
     bool run_cdsp = false, servo = false, threads = false, music = false, servo_table = false, bench = false, batch_parity = false, batched = false;
     int batch = 16, engine_delay_ms = 0, pace_us_arg = -1, peaks = 0, peak_radius = 1, beam_mode = CRSDR_BEAM_OFF;
     float beam_loading = 1e-2f;
+    int smooth_x = 0, smooth_y = 0, order_crit = CRSDR_ORDER_OFF;
+    bool smooth_fb = false;
     bool engine_batches = false;
     int ranks = 1, rank = 0, device = 0;
     std::string idfile;
@@ -90,6 +92,14 @@ int main(int argc, char **argv)
         else if (a == "--beams" && i + 1 < argc) {
             const std::string m = argv[++i];
             beam_mode = m == "conventional" ? CRSDR_BEAM_CONVENTIONAL : m == "mvdr" ? CRSDR_BEAM_MVDR : -1;
+        }
+        // with --bench --music: sub-arrays of SX x SY elements and / or forward-backward averaging (crsdr_doa_set_smoothing), the source
+        // count per estimate (crsdr_doa_set_order), printed as k
+        else if (a == "--smooth" && i + 1 < argc) { if (std::sscanf(argv[++i], "%dx%d", &smooth_x, &smooth_y) != 2) smooth_x = smooth_y = -1; }
+        else if (a == "--fb") smooth_fb = true;
+        else if (a == "--order" && i + 1 < argc) {
+            const std::string c = argv[++i];
+            order_crit = c == "mdl" ? CRSDR_ORDER_MDL : c == "aic" ? CRSDR_ORDER_AIC : -1;
         }
         else if (a == "--loading" && i + 1 < argc) beam_loading = (float)std::atof(argv[++i]);
         else if (a == "--batch-parity") batch_parity = true;   // the batched engine's packets == step()'s packets, bit for bit (own read counters, a masked row)
@@ -291,6 +301,11 @@ int main(int argc, char **argv)
         if (music && !coherent.sharded()) {
             doa.reset(new cbeamformer::batch(1 + nsig, B, batch));
             if (nsig != cbeamformer::MX * cbeamformer::MY || !doa->ok()) { std::printf("doa: unavailable (needs --nsig 21)\nDEMO FAILED\n"); return 1; }
+            if (smooth_x || smooth_fb) {
+                const int sx = smooth_x ? smooth_x : cbeamformer::MX, sy = smooth_x ? smooth_y : cbeamformer::MY;
+                if (doa->set_smoothing(sx, sy, smooth_fb)) { std::printf("doa: --smooth %dx%d%s refused\nDEMO FAILED\n", sx, sy, smooth_fb ? " --fb" : ""); return 1; }
+            }
+            if (order_crit && doa->set_order(order_crit)) { std::printf("doa: --order (mdl|aic) refused\nDEMO FAILED\n"); return 1; }
             if (peaks && doa->set_peaks(peaks, peak_radius)) { std::printf("doa: --peaks %d --peak-radius %d refused\nDEMO FAILED\n", peaks, peak_radius); return 1; }
             if (beam_mode && doa->set_beams(beam_mode, beam_loading)) { std::printf("doa: --beams (conventional|mvdr) --loading %g refused\nDEMO FAILED\n", (double)beam_loading); return 1; }
         }
@@ -300,6 +315,11 @@ int main(int argc, char **argv)
             ok = doa->submit(coherent.engine_plan()) == CRSDR_OK && doa->fetch() == CRSDR_OK;
             if (!ok || !report) return;
             const int n = doa->estimates();
+            if (order_crit) {
+                std::string ks;
+                for (int e = 0; e < n; ++e) ks += " " + std::to_string(doa->order[e]);
+                std::printf("doa: batch %d: %d estimates of %d elements, k:%s\n", b, n, doa->subspace_size(), ks.c_str());
+            }
             if (peaks) {
                 // the first estimate's local peaks, strongest first
                 std::string dirs;

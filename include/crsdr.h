@@ -547,8 +547,65 @@ int crsdr_doa_fetch_beams(crsdr_doa *doa, float *weights, float *power, float *b
  * while beams are off) and the slot count, for consumers on the same stream.  They change with every crsdr_doa_set_beams. */
 int crsdr_doa_beam_buffers(crsdr_doa *doa, void **weights, void **power, void **beams, int *nbeams);
 
-/* vec [nest][m][m][2] of the last submit, as crsdr_noisesubspace writes it.  CRSDR_ESTATE before the first submit. */
+/* vec [nest][m][m][2] of the last submit, as crsdr_noisesubspace writes it ([nest][ms][ms][2] with crsdr_doa_set_smoothing on).
+ * CRSDR_ESTATE before the first submit. */
 int crsdr_doa_fetch_subspace(crsdr_doa *doa, float *vec);
+
+/* Spatial smoothing and forward-backward averaging of the covariance, between the covariance and the subspace: coherent arrivals (an
+ * emitter and its reflections) leave Rxx with one signal eigenvalue however many paths there are; averaging it over shifted sub-arrays
+ * and with its backward image restores the rank.  Sub-arrays of sx x sy elements, 1 <= sx <= mx, 1 <= sy <= my, ms = sx * sy >= 2,
+ * P = (mx - sx + 1)(my - sy + 1) of them; sub-array (px, py) selects sel_p(iy * sx + ix) = (iy + py) * mx + ix + px.  For a <= b, in
+ * fp64 from the fp32 rxx, p running px fastest, then py:
+ *     acc[a][b] = sum_p rxx[sel_p(a)][sel_p(b)]
+ *     rs[a][b]  = acc[a][b] / P                                          flags = 0
+ *     rs[a][b]  = (acc[a][b] + conj(acc[ms-1-a][ms-1-b])) / (2 P)        flags = CRSDR_SMOOTH_FB
+ * rounded once to fp32, rs[b][a] written as its conjugate.  (Index reversal is the centro-symmetry of a URA in this element order; it
+ * holds for the conjugated steering vectors of the X^H X convention alike.)
+ * (sx, sy) = (mx, my) with flags 0 is "off".  With it on, the subspace, sv, vec, the scan (an sx x sy array of ms elements, the same
+ * d), peak and the directions all work on rs: crsdr_doa_fetch's sv is [nest][ms], crsdr_doa_fetch_subspace's and the device's vec
+ * [nest][ms][ms][2], densely packed; rxx (CRSDR_DOA_KEEP_RXX) stays the raw [m][m] matrix.  A submit is one launch more.
+ * Any time: waits for the device if a submit was made, allocates rs, and discards what the last submit left (the fetch functions return
+ * CRSDR_ESTATE until the next submit).  CRSDR_EINVAL for bad sizes or flags, for desc.k >= ms, or with crsdr_doa_set_order on and its
+ * kmax >= ms.  While true sub-arrays (ms < m) are on, crsdr_doa_set_beams returns CRSDR_ESTATE, and with beams on this call does: the
+ * weights are m-vectors and there is then no m x m subspace.  CRSDR_SMOOTH_FB alone keeps m, and beams work from its subspace. */
+enum { CRSDR_SMOOTH_FB = 1u << 0 };
+int crsdr_doa_set_smoothing(crsdr_doa *doa, int sx, int sy, uint32_t flags);
+
+/* rs [nest][ms][ms][2] of the last submit.  CRSDR_ESTATE with smoothing off or before the first submit after crsdr_doa_set_smoothing. */
+int crsdr_doa_fetch_smoothed(crsdr_doa *doa, float *rs);
+
+/* The number of sources from the singular values, between the subspace and the scan.  M = the subspace's size (m, or ms with smoothing
+ * on), N = frames * blocksize / 2 snapshots (the raw count with smoothing on as well: a definition, not a claim of optimality); in fp64
+ * from the published fp32 sv:
+ *     lambda_i = max(sv[i], sv[0] * 2^-40)
+ *     T_k      = n log((1/n) sum_{i >= k} lambda_i) - sum_{i >= k} log lambda_i,   n = M - k,   for k in [kmin, kmax]
+ *     CRSDR_ORDER_MDL   N T_k + k (2M - k) log(N) / 2
+ *     CRSDR_ORDER_AIC   2 N T_k + 2 k (2M - k)
+ * k_e = the argmin, the smallest k on a tie; sv[0] = 0 (an all-zero estimate): k_e = kmin and every value 0.
+ * 1 <= kmin <= kmax < M: "no source", k = 0, is not representable, the scan needs one signal vector.
+ * With it on, the scan of estimate e projects on columns k_e .. M-1 instead of desc.k .. M-1: its pm has the bits of an engine created
+ * with k = k_e.  limit_directions != 0 with crsdr_doa_set_peaks on: found[e] <= k_e, the slots from there on hold (-1, -1) and -1, and
+ * beams that follow the directions see the capped found.  A submit is one launch more.
+ * CRSDR_ORDER_OFF frees the buffers (the other arguments are then ignored).  Any time: waits for the device if a submit was made.
+ * CRSDR_EINVAL for a bad criterion or range. */
+enum { CRSDR_ORDER_OFF = 0, CRSDR_ORDER_MDL = 1, CRSDR_ORDER_AIC = 2 };
+int crsdr_doa_set_order(crsdr_doa *doa, int criterion, int kmin, int kmax, int limit_directions);
+
+/* Waits for the last submit and copies out (either pointer may be NULL): k [nest] int32, criterion_values [nest][kmax - kmin + 1]
+ * (the fp64 values rounded once to fp32).  CRSDR_ESTATE with order off or before the first submit after crsdr_doa_set_order. */
+int crsdr_doa_fetch_order(crsdr_doa *doa, int32_t *k, float *criterion_values);
+
+/* Device addresses of k and the criterion values ([max_batch / frames] estimates; NULL while order is off), for consumers on the same
+ * stream.  They change with every crsdr_doa_set_order. */
+int crsdr_doa_order_buffers(crsdr_doa *doa, void **k, void **criterion_values);
+
+/* The per-op forms of the two steps: the same device functions, bit for bit.
+ *   rxx [mx*my][mx*my][2] -> rs [sx*sy][sx*sy][2]        (sizes and flags as crsdr_doa_set_smoothing)
+ *   sv [m], nsnap = N >= 1 -> k [1], criterion_values [kmax - kmin + 1] (NULL to skip)
+ * mem_kind: CRSDR_MEM_HOST (copied) or CRSDR_MEM_DEVICE (every pointer on the device). */
+int crsdr_smooth_covariance(float *rs, const float *rxx, int mx, int my, int sx, int sy, uint32_t flags, int mem_kind);
+int crsdr_source_order(int32_t *k, float *criterion_values, const float *sv, int m, int64_t nsnap, int criterion, int kmin, int kmax,
+                       int mem_kind);
 
 #ifdef __cplusplus
 }

@@ -11,19 +11,28 @@
       power only (weights and beams stay on the device), and
   (h) what a caller without beams does to form them on the host: the (p) submit + directions, then the 64 packets and vec copied to
       page-locked host memory (before any host arithmetic).
+  (f) with --fb: crsdr_doa_set_smoothing(7, 3, CRSDR_SMOOTH_FB) (forward-backward averaging alone), then the (b) submit + peaks,
+  (s) with --smooth SXxSY: crsdr_doa_set_smoothing(SX, SY, CRSDR_SMOOTH_FB if --fb), then the (b) submit + peaks, and
+  (o) with --order mdl|aic: crsdr_doa_set_order over k = 1 .. 20, then the (b) submit + peaks (on the unsmoothed covariance).
 
 --runs runs of each, alternating a, b, c in one session (two worker processes, both alive throughout); medians and ranges.
 --doa-lib LIB starts a second doa worker on another build (e.g. the parent commit's) through CRSDR_LIB and times its (b) and (c) in
 the same alternation, reported as lib:b and lib:c.  --reps N: every (b), (c), (p), (q), (h) figure is the mean of N back-to-back submit + fetch.
 Also: what crsdr_doa_submit_plan + the peak fetch add to a 22-row, T = 64 plan batch (plan.submit + sync against
 plan.submit + doa.submit_plan + fetch).  --json FILE keeps the record; --once MODE runs three submit + fetch and exits (for a kernel trace): b, c, p, q as above, q64 = the
-beams at their largest shape (8 x 8 array, 16 slots: 65 rows x 16384, 64 blocks)."""
+beams at their largest shape (8 x 8 array, 16 slots: 65 rows x 16384, 64 blocks), s = --smooth / --fb / --order as given, all on one object."""
 import argparse, importlib, json, os, subprocess, sys, time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NROWS, B, T, M = 22, 16384, 64, 21
 BEAM_MODES = {"conventional": 1, "mvdr": 2}
+ORDER_MODES = {"mdl": 1, "aic": 2}
+
+
+def _sub_array(text):
+    sx, sy = text.lower().split("x")
+    return int(sx), int(sy)
 
 
 def _setup(mx=None, my=None):
@@ -70,9 +79,9 @@ def worker_perop():
         print(time.perf_counter() - t0, flush=True)
 
 
-def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2):
-    """(b), (c), (p), (q), (h) and the plan figures: 'b' / 'c' / 'p' / 'q' / 'h' / 'plan' / 'plan+doa' on stdin -> seconds of one batch of
-    64 on stdout."""
+def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None, fb=False, order=None):
+    """(b), (c), (p), (q), (h), (f), (s), (o) and the plan figures: 'b' / 'c' / 'p' / 'q' / 'h' / 'f' / 's' / 'o' / 'plan' / 'plan+doa' on
+    stdin -> seconds of one batch of 64 on stdout."""
     torch, ura, b, dev, pk, off, stride, host = _setup()
     peaks = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
     full = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T, flags=b.DOA_KEEP_SPECTRUM)
@@ -91,6 +100,24 @@ def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2):
         bdoa.set_beams(BEAM_MODES[beams], loading)
         hdoa = dirs or peaks
         pinned = torch.empty(pk.shape, dtype=torch.int8, pin_memory=True)
+
+    extra = {}
+    if fb:
+        extra["f"] = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
+        extra["f"].set_smoothing(ura.MX, ura.MY, b.SMOOTH_FB)
+    if smooth:
+        extra["s"] = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
+        extra["s"].set_smoothing(*_sub_array(smooth), b.SMOOTH_FB if fb else 0)
+    if order:
+        extra["o"] = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
+        extra["o"].set_order(ORDER_MODES[order], 1, M - 1)
+
+    def run_extra(d):
+        def run():
+            for _ in range(reps):
+                d.submit(pk.data_ptr(), stride, off, T)
+                d.fetch_peaks()
+        return run
 
     def run_q():
         for _ in range(reps):
@@ -136,6 +163,8 @@ def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2):
         jobs["p"] = (run_p, reps)
     if bdoa is not None:
         jobs["q"], jobs["h"] = (run_q, reps), (run_h, reps)
+    for key, d in extra.items():
+        jobs[key] = (run_extra(d), reps)
     for f, _ in jobs.values():
         f()
     print("ready", flush=True)
@@ -146,7 +175,7 @@ def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2):
         print((time.perf_counter() - t0) / n, flush=True)
 
 
-def once(mode, npeaks=0, radius=1, beams=None, loading=1e-2):
+def once(mode, npeaks=0, radius=1, beams=None, loading=1e-2, smooth=None, fb=False, order=None):
     mx, my = (8, 8) if mode == "q64" else (None, None)
     torch, ura, b, dev, pk, off, stride, _ = _setup(mx, my)
     mx, my = mx or ura.MX, my or ura.MY
@@ -157,10 +186,17 @@ def once(mode, npeaks=0, radius=1, beams=None, loading=1e-2):
         d.set_peaks(npeaks, radius)
     if mode in ("q", "q64"):
         d.set_beams(BEAM_MODES[beams or "mvdr"], loading)
+    if mode == "s":
+        if smooth or fb:
+            d.set_smoothing(*(_sub_array(smooth) if smooth else (mx, my)), b.SMOOTH_FB if fb else 0)
+        if order:
+            d.set_order(ORDER_MODES[order], 1, d.ms - 1)
     for _ in range(3):
         d.submit(pk.data_ptr(), stride, off, T)
         out = d.fetch()
     print("peaks", out["peak"][:4].tolist(), "launches", d.last_launches())
+    if mode == "s" and order:
+        print("k", d.fetch_order()["k"].tolist())
     if mode in ("p", "q", "q64") and npeaks:
         print("directions of the first", d.fetch_directions()["peaks"][0].tolist())
     if mode in ("q", "q64"):
@@ -197,7 +233,10 @@ def _stat(xs):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--worker", choices=["perop", "doa"])
-    ap.add_argument("--once", choices=["b", "c", "p", "q", "q64"])
+    ap.add_argument("--once", choices=["b", "c", "p", "q", "q64", "s"])
+    ap.add_argument("--smooth", default=None, metavar="SXxSY", help="(s): sub-arrays of SX x SY elements (crsdr_doa_set_smoothing)")
+    ap.add_argument("--fb", action="store_true", help="(f): forward-backward averaging alone; with --smooth: (s) averages backward as well")
+    ap.add_argument("--order", choices=sorted(ORDER_MODES), default=None, help="(o): the source count per estimate (crsdr_doa_set_order)")
     ap.add_argument("--beams", choices=sorted(BEAM_MODES), default=None, help="(q), (h): beams toward the directions, this mode")
     ap.add_argument("--loading", type=float, default=1e-2, help="(q): the MVDR diagonal loading")
     ap.add_argument("--perop-lib", default=None, help="library for (a), e.g. a build of the parent commit (default: the current one)")
@@ -209,15 +248,22 @@ def main():
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     if a.worker:
-        return worker_perop() if a.worker == "perop" else worker_doa(a.peaks, a.radius, a.reps, a.beams, a.loading)
+        return worker_perop() if a.worker == "perop" else worker_doa(a.peaks, a.radius, a.reps, a.beams, a.loading, a.smooth, a.fb, a.order)
     if a.once:
-        return once(a.once, a.peaks, a.radius, a.beams, a.loading)
+        return once(a.once, a.peaks, a.radius, a.beams, a.loading, a.smooth, a.fb, a.order)
     pargs = ["--peaks", str(a.peaks), "--radius", str(a.radius), "--reps", str(a.reps), "--loading", str(a.loading)]
     if a.beams:
         pargs += ["--beams", a.beams]
+    if a.smooth:
+        pargs += ["--smooth", a.smooth]
+    if a.fb:
+        pargs += ["--fb"]
+    if a.order:
+        pargs += ["--order", a.order]
+    legs = (["f"] if a.fb else []) + (["s"] if a.smooth else []) + (["o"] if a.order else [])
     wa, wb = Worker("perop", a.perop_lib), Worker("doa", extra=pargs)
     wl = Worker("doa", a.doa_lib, extra=["--reps", str(a.reps)]) if a.doa_lib else None
-    keys = ["a", "b", "c", "plan", "plan+doa"] + (["lib:b", "lib:c"] if wl else []) + (["p"] if a.peaks else []) + (["q", "h"] if a.beams else [])
+    keys = ["a", "b", "c", "plan", "plan+doa"] + (["lib:b", "lib:c"] if wl else []) + (["p"] if a.peaks else []) + (["q", "h"] if a.beams else []) + legs
     sec = {k: [] for k in keys}
     try:
         for _ in range(a.runs):
@@ -233,6 +279,8 @@ def main():
             if a.beams:
                 sec["q"].append(wb.run("q"))
                 sec["h"].append(wb.run("h"))
+            for k in legs:
+                sec[k].append(wb.run(k))
             sec["plan"].append(wb.run("plan"))
             sec["plan+doa"].append(wb.run("plan+doa"))
     finally:
@@ -242,6 +290,7 @@ def main():
     rec = {"shape": {"nrows": NROWS, "blocksize": B, "blocks": T, "grid": [100, 100]}, "runs": a.runs, "reps": a.reps,
            "perop_lib": a.perop_lib or "current build", "doa_lib": a.doa_lib, "peaks": {"count": a.peaks, "radius": a.radius} if a.peaks else None,
            "beams": {"mode": a.beams, "loading": a.loading} if a.beams else None,
+           "smoothing": {"sub_array": a.smooth, "fb": a.fb} if (a.smooth or a.fb) else None, "order": a.order,
            "ms_per_batch": {k: _stat([1e3 * x for x in v]) for k, v in sec.items()},
            "frames_per_s": {k: _stat([T / x for x in sec[k]]) for k in ("a", "b", "c")}}
     rec["b_faster_than_a_ranges_disjoint"] = rec["ms_per_batch"]["b"]["max"] < rec["ms_per_batch"]["a"]["min"]
@@ -249,12 +298,18 @@ def main():
     names = {"a": "per-op loop, device pointers", "b": "doa submit + peaks", "c": "doa submit + peaks + spectra",
              "plan": "plan batch alone", "plan+doa": "plan batch + submit_plan + peaks", "lib:b": "--doa-lib: submit + peaks",
              "lib:c": "--doa-lib: submit + peaks + spectra", "p": f"set_peaks({a.peaks}, {a.radius}): submit + directions",
-             "q": f"(p) + {a.beams} beams: submit + power", "h": "(p) + packets and vec to the host"}
+             "q": f"(p) + {a.beams} beams: submit + power", "h": "(p) + packets and vec to the host",
+             "f": "FB alone: submit + peaks", "s": f"{a.smooth}{' + FB' if a.fb else ''}: submit + peaks", "o": f"order {a.order}: submit + peaks"}
     for k, s in rec["ms_per_batch"].items():
         fps = f"  {T / (1e-3 * s['median']):10.0f} frames/s" if k in rec["frames_per_s"] else ""
         print(f"({k}) {names[k]:34s} {s['median']:8.3f} ms per 64 blocks  [{s['min']:.3f} .. {s['max']:.3f}]{fps}")
     print(f"(b) faster than (a), ranges disjoint: {rec['b_faster_than_a_ranges_disjoint']};  "
           f"a direction per block adds {rec['submit_plan_adds_ms_per_batch']:.3f} ms to a plan batch of 64")
+    for k in legs:
+        rec[f"{k}_adds_ms_per_batch"] = rec["ms_per_batch"][k]["median"] - rec["ms_per_batch"]["b"]["median"]
+        print(f"({k}) adds {1e3 * rec[f'{k}_adds_ms_per_batch']:.0f} us to (b)")
+    if wl:
+        rec["b_minus_lib_b_ms"] = rec["ms_per_batch"]["b"]["median"] - rec["ms_per_batch"]["lib:b"]["median"]
     if a.json:
         with open(a.json, "w") as f:
             json.dump(rec, f, indent=1)
