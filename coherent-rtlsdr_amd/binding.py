@@ -40,11 +40,13 @@ ABI_SYMBOLS = [
     "crsdr_beamform", "crsdr_doa_set_beams", "crsdr_doa_fetch_beams", "crsdr_doa_beam_buffers", "crsdr_doa_fetch_subspace",
     "crsdr_doa_set_smoothing", "crsdr_doa_fetch_smoothed", "crsdr_doa_set_order", "crsdr_doa_fetch_order", "crsdr_doa_order_buffers",
     "crsdr_smooth_covariance", "crsdr_source_order",
+    "crsdr_doa_set_subbands", "crsdr_doa_fetch_subbands", "crsdr_doa_subband_buffers", "crsdr_subband_covariance",
 ]
 DOA_KEEP_SPECTRUM, DOA_KEEP_RXX = 1, 2
 BEAM_OFF, BEAM_CONVENTIONAL, BEAM_MVDR = 0, 1, 2
 SMOOTH_FB = 1
 ORDER_OFF, ORDER_MDL, ORDER_AIC = 0, 1, 2
+WINDOW_RECT, WINDOW_HANN = 0, 1
 XCHG_STAGED, XCHG_INPLACE = 0, 1
 EXCHANGE_ID_BYTES = 128
 KERNEL_REF_SPECTRUM, KERNEL_XCORR_LAG, KERNEL_PHASE_DOT, KERNEL_ALIGN_QUANT = 0, 1, 2, 3
@@ -183,6 +185,11 @@ def lib():
         L.crsdr_doa_set_order.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
         L.crsdr_doa_fetch_order.argtypes = [vp, i32p, f32p]
         L.crsdr_doa_order_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    if hasattr(L, "crsdr_doa_set_subbands"):         # (likewise: an older build has no subbands)
+        L.crsdr_doa_set_subbands.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.crsdr_doa_fetch_subbands.argtypes = [vp, f32p]
+        L.crsdr_doa_subband_buffers.argtypes = [vp, C.POINTER(vp)]
+        L.crsdr_subband_covariance.argtypes = [f32p, f32p, i8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         L.crsdr_smooth_covariance.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int]
         L.crsdr_source_order.argtypes = [vp, vp, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]
     _lib = L
@@ -389,6 +396,26 @@ def source_order(sv, nsnap, criterion=ORDER_MDL, kmin=1, kmax=None):
 def source_order_device(k_ptr: int, crit_ptr: int, sv_ptr: int, m, nsnap, criterion, kmin, kmax):
     """Same on device memory (crit_ptr may be 0); returns after the kernel finished."""
     _check(lib().crsdr_source_order(int(k_ptr), int(crit_ptr) or None, int(sv_ptr), int(m), int(nsnap), int(criterion), int(kmin), int(kmax), MEM_DEVICE))
+
+
+def subband_covariance(matrix, nfft, first=0, nbands=1, width=1, window=WINDOW_RECT):
+    """crsdr_subband_covariance: (rbands [nbands][m][m] complex64, power [nbands]) of one packet's int8 matrix [nrows][B]: band i
+    is the sum of the per-bin covariances R_f over the bins (first + i width + u) mod nfft: the batched engine's subband covariance
+    on one estimate of one packet."""
+    m = np.ascontiguousarray(matrix, dtype=np.int8)
+    nrows, B = m.shape
+    rb = np.empty((max(int(nbands), 0), nrows - 1, nrows - 1), dtype=np.complex64)
+    pw = np.empty(max(int(nbands), 0), dtype=np.float32)
+    _check(lib().crsdr_subband_covariance(_p(rb.view(np.float32), C.c_float), _p(pw, C.c_float), _p(m, C.c_int8), nrows, B, int(nfft), int(first),
+                                          int(nbands), int(width), int(window), MEM_HOST))
+    return rb, pw
+
+
+def subband_covariance_device(rbands_ptr: int, power_ptr: int, matrix_ptr: int, nrows, B, nfft, first, nbands, width, window):
+    """Same on device memory (power_ptr may be 0); returns after the kernels finished."""
+    cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
+    _check(lib().crsdr_subband_covariance(cast(rbands_ptr, C.c_float), cast(power_ptr, C.c_float), cast(matrix_ptr, C.c_int8), int(nrows), int(B),
+                                          int(nfft), int(first), int(nbands), int(width), int(window), MEM_DEVICE))
 
 
 def assemble_slabs(packets_ptr: int, packet_stride: int, nrows: int, B: int, recv_ptr: int, nsrc: int, nblocks: int, stream: int | None = None):
@@ -650,6 +677,7 @@ class Doa:
         self.max_batch, self.frames, self.flags = max(1, int(max_batch)), max(1, int(frames)), int(flags)
         self.npeaks, self.nbeams = 0, 0
         self.mx, self.my, self.ms, self.order = int(mx), int(my), self.m, None      # ms: the subspace's size; order: (kmin, kmax)
+        self.nbands = 0                                                             # set_subbands: bands per estimate (0: off)
 
     def _last(self):
         nest, launches = C.c_int(0), C.c_int(0)
@@ -776,6 +804,25 @@ class Doa:
         ptrs = [C.c_void_p() for _ in range(2)]
         _check(lib().crsdr_doa_order_buffers(self._h, *[C.byref(p) for p in ptrs]))
         return dict(zip(("k", "criterion"), [p.value for p in ptrs]))
+
+    def set_subbands(self, nfft: int, first: int = 0, nbands: int = 1, width: int = 1, window: int = WINDOW_RECT):
+        """crsdr_doa_set_subbands: from the next submit on, one covariance per (estimate, band) of `width` bins of an nfft-point
+        transform from bin `first` on (FFT order, wrapping); every fetch then counts nest * nbands entries, estimate e's band i at
+        e * nbands + i.  nfft = 0: off.  Only while peaks, beams, smoothing and order are off (set them afterwards; beams stay off).
+        Waits for the device if a submit was made, and discards that submit's results."""
+        _check(lib().crsdr_doa_set_subbands(self._h, int(nfft), int(first), int(nbands), int(width), int(window)))
+        self.nbands = int(nbands) if nfft else 0
+
+    def fetch_subbands(self) -> np.ndarray:
+        """Waits for the last submit.  power [nest][nbands] = Re trace(R_band) / m."""
+        power = np.zeros((self._last()[0] // self.nbands, self.nbands) if self.nbands else (1, 1), dtype=np.float32)      # (off: the library says so)
+        _check(lib().crsdr_doa_fetch_subbands(self._h, _p(power, C.c_float)))
+        return power
+
+    def subband_buffers(self) -> dict:
+        p = C.c_void_p()
+        _check(lib().crsdr_doa_subband_buffers(self._h, C.byref(p)))
+        return {"power": p.value}
 
     def last_launches(self) -> int:
         return self._last()[1]

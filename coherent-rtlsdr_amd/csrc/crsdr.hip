@@ -6,6 +6,7 @@
 #include "doa.hpp"
 #include "smooth.hpp"
 #include "beams.hpp"
+#include "subband.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -1852,7 +1853,9 @@ extern "C" int crsdr_plan_kernel_times(crsdr_plan *p, int which, float *ms, int 
 //      launches on one stream whatever the batch size (covariance partials, their reducer, subspace, scan, peak), no lock, no
 //      allocation, no synchronisation.  crsdr_doa_set_peaks allocates what the local-peak pass needs and adds its two launches,
 //      crsdr_doa_set_beams what the beams need and theirs (beams.hpp), crsdr_doa_set_smoothing and crsdr_doa_set_order theirs and one
-//      launch each (smooth.hpp): behind the reducer, and between the subspace and the scan.
+//      launch each (smooth.hpp): behind the reducer, and between the subspace and the scan.  crsdr_doa_set_subbands replaces the two
+//      covariance launches by subband.hpp's (one covariance per estimate and frequency band) and reallocates every per-matrix buffer
+//      for (max_batch / frames) * nbands matrices: the launches behind it then run over that many.
 // ================================================================================================
 struct crsdr_doa {
     int nrows = 0, B = 0, m = 0, device = 0, max_batch = 1, frames = 1, k = 1, mx = 0, my = 0, ncx = 0, ncy = 0;
@@ -1894,7 +1897,14 @@ struct crsdr_doa {
     int32_t *d_korder = nullptr;
     float *d_crit = nullptr;
     bool order_submitted = false;
+    // crsdr_doa_set_subbands: nfft (0 = off), the bands (first, nbands, width; nbands = 1 while off: every buffer behind the covariance
+    // holds (max_batch / frames) * nbands matrices either way), the window, K slices per packet, unit groups, the slices' partials
+    // [nest][frames * sb_spb][subband_partial] and the bands' power [nest][nbands]
+    int sb_nfft = 0, sb_log2 = 0, sb_first = 0, nbands = 1, sb_width = 0, sb_window = 0, sb_spb = 1, sb_groups = 1;
+    float2 *d_sbpartial = nullptr;
+    float *d_sbpower = nullptr;
 };
+constexpr int kMaxDoaMatrices = 4096;      // (max_batch / frames) * nbands
 
 // The dynamic LDS limits of the subspace and the scan are function attributes, shared by every live object: each create (and each
 // crsdr_doa_set_order) sets them to the most any object can ask for (m = 64, one signal vector), so that a small object created after
@@ -1933,6 +1943,15 @@ static void doa_free_beams(crsdr_doa *q)
     q->beam_mode = q->nbeams = q->nfixed = 0; q->loading = 0.f; q->beams_submitted = false;
 }
 
+// the buffers with one entry per matrix (estimate, or estimate and band), and the subband workspace
+static void doa_free_matrices(crsdr_doa *q)
+{
+    void *bufs[] = {q->d_info, q->d_rxx, q->d_vec, q->d_sv, q->d_peakv, q->d_pm, q->d_peak, q->d_wgbest, q->d_sbpartial, q->d_sbpower};
+    for (void *b : bufs) if (b) (void)hipFree(b);
+    q->d_info = nullptr; q->d_rxx = q->d_vec = q->d_sbpartial = nullptr; q->d_sv = q->d_peakv = q->d_pm = q->d_sbpower = nullptr;
+    q->d_peak = nullptr; q->d_wgbest = nullptr;
+}
+
 static void doa_free(crsdr_doa *q)
 {
     if (!q) return;
@@ -1942,19 +1961,24 @@ static void doa_free(crsdr_doa *q)
     doa_free_beams(q);
     doa_free_smooth(q);
     doa_free_order(q);
-    void *bufs[] = {q->d_partial, q->d_info, q->d_psum, q->d_rxx, q->d_vec, q->d_sv, q->d_peakv, q->d_pm, q->d_peak, q->d_wgbest};
+    doa_free_matrices(q);
+    void *bufs[] = {q->d_partial, q->d_psum};
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (q->own_stream) (void)hipStreamDestroy(q->own_stream);
     delete q;
 }
 
-static int doa_alloc(crsdr_doa *q)
+// the most matrices a submit leaves: what every setter sizes its buffers by
+static size_t doa_capacity(const crsdr_doa *q) { return (size_t)(q->max_batch / q->frames) * (size_t)q->nbands; }
+
+static int doa_alloc_matrices(crsdr_doa *q)
 {
-    HIP_TRY(hipSetDevice(q->device));
-    HIP_TRY(hipStreamCreateWithFlags(&q->own_stream, hipStreamNonBlocking));
-    const size_t T = (size_t)q->max_batch, nest = T / (size_t)q->frames, m = (size_t)q->m, grid = (size_t)q->ncx * q->ncy;
-    HIP_TRY(hipMalloc((void **)&q->d_partial, sizeof(int) * T * q->spb * q->ntri * 2 * doa::TILE_ELEMS));
-    HIP_TRY(hipMalloc((void **)&q->d_psum, sizeof(int2) * T * q->spb * doa::MAX_ROWS));
+    const size_t nest = doa_capacity(q), m = (size_t)q->m, grid = (size_t)q->ncx * q->ncy;
+    if (q->sb_nfft) {
+        const size_t slices = (size_t)q->max_batch * q->sb_spb;
+        HIP_TRY(hipMalloc((void **)&q->d_sbpartial, sizeof(float2) * slices * subband::subband_partial(q->m, q->sb_nfft)));
+        HIP_TRY(hipMalloc((void **)&q->d_sbpower, sizeof(float) * nest));
+    }
     HIP_TRY(hipMalloc((void **)&q->d_rxx, sizeof(float2) * nest * m * m));
     HIP_TRY(hipMalloc((void **)&q->d_vec, sizeof(float2) * nest * m * m));
     HIP_TRY(hipMalloc((void **)&q->d_sv, sizeof(float) * nest * m));
@@ -1963,6 +1987,17 @@ static int doa_alloc(crsdr_doa *q)
     HIP_TRY(hipMalloc((void **)&q->d_peak, sizeof(int32_t) * nest * 2));
     HIP_TRY(hipMalloc((void **)&q->d_peakv, sizeof(float) * nest));
     if (q->flags & CRSDR_DOA_KEEP_SPECTRUM) HIP_TRY(hipMalloc((void **)&q->d_pm, sizeof(float) * nest * grid));
+    return CRSDR_OK;
+}
+
+static int doa_alloc(crsdr_doa *q)
+{
+    HIP_TRY(hipSetDevice(q->device));
+    HIP_TRY(hipStreamCreateWithFlags(&q->own_stream, hipStreamNonBlocking));
+    const size_t T = (size_t)q->max_batch;
+    HIP_TRY(hipMalloc((void **)&q->d_partial, sizeof(int) * T * q->spb * q->ntri * 2 * doa::TILE_ELEMS));
+    HIP_TRY(hipMalloc((void **)&q->d_psum, sizeof(int2) * T * q->spb * doa::MAX_ROWS));
+    { int rc = doa_alloc_matrices(q); if (rc) return rc; }
     // the kernels' dynamic LDS limits: once, here (the subspace takes 128 KiB at m = 64)
     HIP_TRY(hipFuncSetAttribute((const void *)doa::k_doa_subspace, hipFuncAttributeMaxDynamicSharedMemorySize, kDoaSubLdsMax));
     HIP_TRY(hipFuncSetAttribute((const void *)doa::k_doa_scan<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kDoaScanLdsMax));
@@ -2023,20 +2058,51 @@ extern "C" int crsdr_doa_destroy(crsdr_doa *doa)
     default: { constexpr int NB = 16; launch; } break;                              \
     }
 
+// `launch` with LG = log2 nfft
+#define SUBBAND_DISPATCH(lg, launch)                                                \
+    switch (lg) {                                                                   \
+    case 3: { constexpr int LG = 3; launch; } break;                                \
+    case 4: { constexpr int LG = 4; launch; } break;                                \
+    case 5: { constexpr int LG = 5; launch; } break;                                \
+    case 6: { constexpr int LG = 6; launch; } break;                                \
+    case 7: { constexpr int LG = 7; launch; } break;                                \
+    default: { constexpr int LG = 8; launch; } break;                               \
+    }
+
+// snapshots behind a matrix, for the source count: every sample, or a band's J' * width spectra
+static double doa_snapshots(const crsdr_doa *q)
+{
+    if (q->sb_nfft) return (double)q->frames * (double)(q->B / (2 * q->sb_nfft)) * (double)q->sb_width;
+    return (double)q->frames * (double)(q->B / 2);
+}
+
 static int doa_launch(crsdr_doa *q, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nblocks, hipStream_t S)
 {
-    const unsigned nest = (unsigned)(nblocks / q->frames), slices = (unsigned)(q->frames * q->spb);
+    unsigned nest = (unsigned)(nblocks / q->frames);
+    const unsigned slices = (unsigned)(q->frames * q->spb);
     int launches = 0;
-    if (q->nt == 1)
-        hipLaunchKernelGGL(doa::k_doa_cov<1>, dim3(slices, nest), dim3(doa::COV_THREADS), 0, S, packets, packet_stride, matrix_offset, q->nrows, q->B, q->frames,
-                           q->spb, q->d_partial, q->d_psum);
-    else
-        hipLaunchKernelGGL(doa::k_doa_cov<2>, dim3(slices, nest), dim3(doa::COV_THREADS), 0, S, packets, packet_stride, matrix_offset, q->nrows, q->B, q->frames,
-                           q->spb, q->d_partial, q->d_psum);
-    HIP_TRY(hipGetLastError()); ++launches;
-    hipLaunchKernelGGL(doa::k_doa_cov_reduce, dim3((unsigned)q->ntri, nest), dim3(256), 0, S, (const int *)q->d_partial, (const int2 *)q->d_psum, (int)slices, q->ntri,
-                       q->nrows, q->B, q->frames, q->d_rxx);
-    HIP_TRY(hipGetLastError()); ++launches;
+    if (q->sb_nfft) {
+        // one covariance per (estimate, band); everything behind it runs over nest * nbands matrices, estimate e's band i at e * nbands + i
+        const dim3 grid((unsigned)(q->frames * q->sb_spb), (unsigned)q->sb_groups, nest);
+        SUBBAND_DISPATCH(q->sb_log2, hipLaunchKernelGGL(subband::k_doa_subband_cov<LG>, grid, dim3(subband::SB_THREADS), 0, S, packets, packet_stride, matrix_offset,
+                                                        q->nrows, q->B, q->frames, q->sb_spb, q->sb_window, q->d_sbpartial));
+        HIP_TRY(hipGetLastError()); ++launches;
+        hipLaunchKernelGGL(subband::k_doa_subband_reduce, dim3((unsigned)q->nbands, nest), dim3(256), 0, S, (const float2 *)q->d_sbpartial, (int)grid.x, q->nrows, q->B,
+                           q->frames, q->sb_log2, q->sb_first, q->sb_width, q->sb_window, q->d_rxx, q->d_sbpower);
+        HIP_TRY(hipGetLastError()); ++launches;
+        nest *= (unsigned)q->nbands;
+    } else {
+        if (q->nt == 1)
+            hipLaunchKernelGGL(doa::k_doa_cov<1>, dim3(slices, nest), dim3(doa::COV_THREADS), 0, S, packets, packet_stride, matrix_offset, q->nrows, q->B, q->frames,
+                               q->spb, q->d_partial, q->d_psum);
+        else
+            hipLaunchKernelGGL(doa::k_doa_cov<2>, dim3(slices, nest), dim3(doa::COV_THREADS), 0, S, packets, packet_stride, matrix_offset, q->nrows, q->B, q->frames,
+                               q->spb, q->d_partial, q->d_psum);
+        HIP_TRY(hipGetLastError()); ++launches;
+        hipLaunchKernelGGL(doa::k_doa_cov_reduce, dim3((unsigned)q->ntri, nest), dim3(256), 0, S, (const int *)q->d_partial, (const int2 *)q->d_psum, (int)slices,
+                           q->ntri, q->nrows, q->B, q->frames, q->d_rxx);
+        HIP_TRY(hipGetLastError()); ++launches;
+    }
     // smoothing on: subspace, order, scan and peaks work on rs, an sx x sy array of M = ms elements (off: sx = mx, sy = my, M = m)
     const int M = q->ms;
     const float2 *cov = q->d_rxx;
@@ -2051,7 +2117,7 @@ static int doa_launch(crsdr_doa *q, const int8_t *packets, size_t packet_stride,
     // with peaks on, the scan always leaves its spectrum: the kept one, or the workspace
     float *pm = q->npeaks && !q->d_pm ? q->d_pmws : q->d_pm;
     if (q->order_crit) {
-        hipLaunchKernelGGL(smooth::k_doa_order, dim3(nest), dim3(64), 0, S, (const float *)q->d_sv, M, (double)q->frames * (double)(q->B / 2), q->order_crit, q->kmin,
+        hipLaunchKernelGGL(smooth::k_doa_order, dim3(nest), dim3(64), 0, S, (const float *)q->d_sv, M, doa_snapshots(q), q->order_crit, q->kmin,
                            q->kmax, q->d_korder, q->d_crit);
         HIP_TRY(hipGetLastError()); ++launches;
         // the LDS of the most noise vectors an estimate can have, M - kmin
@@ -2121,7 +2187,8 @@ extern "C" int crsdr_doa_fetch(crsdr_doa *q, int32_t *peak, float *peak_value, f
     HIP_TRY(hipSetDevice(q->device));
     const size_t nest = (size_t)q->last_nest, m = (size_t)q->m, ms = (size_t)q->last_ms;
     hipStream_t S = q->last_stream;
-    int info[2 * kMaxBatch];
+    static_assert(kMaxDoaMatrices >= kMaxBatch, "status of every matrix of a submit");
+    int info[2 * kMaxDoaMatrices];
     if (peak) HIP_TRY(hipMemcpyAsync(peak, q->d_peak, sizeof(int32_t) * nest * 2, hipMemcpyDeviceToHost, S));
     if (peak_value) HIP_TRY(hipMemcpyAsync(peak_value, q->d_peakv, sizeof(float) * nest, hipMemcpyDeviceToHost, S));
     if (sv) HIP_TRY(hipMemcpyAsync(sv, q->d_sv, sizeof(float) * nest * ms, hipMemcpyDeviceToHost, S));
@@ -2156,7 +2223,7 @@ extern "C" int crsdr_doa_last_submit(crsdr_doa *q, int *nest, int *launches)
 
 static int doa_alloc_peaks(crsdr_doa *q, int count)
 {
-    const size_t nest = (size_t)(q->max_batch / q->frames), grid = (size_t)q->ncx * q->ncy;
+    const size_t nest = doa_capacity(q), grid = (size_t)q->ncx * q->ncy;
     q->lp_tiles = doa::lp_tiles(q->ncx, q->ncy);
     if (!q->d_pm) HIP_TRY(hipMalloc((void **)&q->d_pmws, sizeof(float) * nest * grid));
     HIP_TRY(hipMalloc((void **)&q->d_cand, sizeof(unsigned long long) * nest * q->lp_tiles * count));
@@ -2216,6 +2283,8 @@ extern "C" int crsdr_doa_set_beams(crsdr_doa *q, int mode, float loading, int nf
     if (mode == CRSDR_BEAM_MVDR && !(loading >= 1e-6f && loading <= 1.0f)) return fail(CRSDR_EINVAL, "doa_set_beams: loading = %g (1e-6..1)", (double)loading);
     if (mode != CRSDR_BEAM_OFF && (nfixed < 0 || nfixed > beams::MAX_BEAMS)) return fail(CRSDR_EINVAL, "doa_set_beams: nfixed = %d (0..%d)", nfixed, beams::MAX_BEAMS);
     if (mode != CRSDR_BEAM_OFF && nfixed > 0 && !fixed_angles) return fail(CRSDR_EINVAL, "doa_set_beams: %d fixed directions and no angles", nfixed);
+    if (mode != CRSDR_BEAM_OFF && q->sb_nfft)
+        return fail(CRSDR_ESTATE, "doa_set_beams: subbands are on (crsdr_doa_set_subbands): a band's weights applied to the wideband samples mean nothing");
     if (mode != CRSDR_BEAM_OFF && q->ms < q->m)
         return fail(CRSDR_ESTATE, "doa_set_beams: smoothing over %d x %d sub-arrays is on (crsdr_doa_set_smoothing): the weights are %d-vectors and there is no %d x %d subspace",
                     q->sx, q->sy, q->m, q->m, q->m);
@@ -2292,7 +2361,7 @@ extern "C" int crsdr_doa_set_smoothing(crsdr_doa *q, int sx, int sy, uint32_t fl
     doa_free_smooth(q);
     q->submitted = false;                                // sv and vec change their shape: what the last submit left is gone
     if (ms == q->m && !flags) return CRSDR_OK;
-    const size_t nest = (size_t)(q->max_batch / q->frames);
+    const size_t nest = doa_capacity(q);
     if (hipMalloc((void **)&q->d_rs, sizeof(float2) * nest * ms * ms) != hipSuccess)
         return fail(CRSDR_ENOMEM, "doa_set_smoothing: %zu bytes of device memory", sizeof(float2) * nest * ms * ms);
     q->smooth_on = true; q->sx = sx; q->sy = sy; q->ms = ms; q->smooth_flags = flags;
@@ -2320,7 +2389,7 @@ extern "C" int crsdr_doa_set_order(crsdr_doa *q, int criterion, int kmin, int km
     if (q->submitted) HIP_TRY(hipDeviceSynchronize());   // the buffers may be in use (the last submit's stream may be the caller's, and gone)
     doa_free_order(q);
     if (criterion == CRSDR_ORDER_OFF) return CRSDR_OK;
-    const size_t nest = (size_t)(q->max_batch / q->frames), nc = (size_t)(kmax - kmin + 1);
+    const size_t nest = doa_capacity(q), nc = (size_t)(kmax - kmin + 1);
     HIP_TRY(hipFuncSetAttribute((const void *)doa::k_doa_scan<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kDoaScanLdsMax));
     if (hipMalloc((void **)&q->d_korder, sizeof(int32_t) * nest) != hipSuccess || hipMalloc((void **)&q->d_crit, sizeof(float) * nest * nc) != hipSuccess) {
         doa_free_order(q);
@@ -2349,6 +2418,104 @@ extern "C" int crsdr_doa_order_buffers(crsdr_doa *q, void **k, void **criterion_
     if (!q) return fail(CRSDR_EINVAL, "doa_order_buffers: NULL doa");
     if (k) *k = q->d_korder;
     if (criterion_values) *criterion_values = q->d_crit;
+    return CRSDR_OK;
+}
+
+// ---- one covariance per frequency band (subband.hpp) ----
+static int subband_args_ok(const char *who, int blocksize, int nfft, int first, int nbands, int width, int window)
+{
+    if (nfft < (1 << subband::SB_MIN_LOG2) || nfft > (1 << subband::SB_MAX_LOG2) || (nfft & (nfft - 1)))
+        return fail(CRSDR_EINVAL, "%s: nfft = %d (a power of two, %d..%d)", who, nfft, 1 << subband::SB_MIN_LOG2, 1 << subband::SB_MAX_LOG2);
+    if (blocksize % (2 * nfft)) return fail(CRSDR_EINVAL, "%s: blocksize = %d is no multiple of 2 nfft = %d", who, blocksize, 2 * nfft);
+    if (first < 0 || first >= nfft) return fail(CRSDR_EINVAL, "%s: first = %d (0..nfft - 1 = %d)", who, first, nfft - 1);
+    if (nbands < 1 || width < 1 || (long long)nbands * width > nfft)
+        return fail(CRSDR_EINVAL, "%s: %d bands of %d bins (nbands >= 1, width >= 1, nbands * width <= nfft = %d)", who, nbands, width, nfft);
+    if (window != CRSDR_WINDOW_RECT && window != CRSDR_WINDOW_HANN) return fail(CRSDR_EINVAL, "%s: window = %d", who, window);
+    return CRSDR_OK;
+}
+
+static int ilog2(int n) { int lg = 0; while ((1 << lg) < n) ++lg; return lg; }
+
+extern "C" int crsdr_doa_set_subbands(crsdr_doa *q, int nfft, int first, int nbands, int width, int window)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_set_subbands: NULL doa");
+    if (nfft != 0) {
+        const int rc = subband_args_ok("doa_set_subbands", q->B, nfft, first, nbands, width, window);
+        if (rc) return rc;
+        if ((long long)(q->max_batch / q->frames) * nbands > kMaxDoaMatrices)
+            return fail(CRSDR_EINVAL, "doa_set_subbands: %d estimates of %d bands (at most %d matrices per submit)", q->max_batch / q->frames, nbands, kMaxDoaMatrices);
+    }
+    if (q->npeaks || q->beam_mode || q->smooth_on || q->order_crit)
+        return fail(CRSDR_ESTATE, "doa_set_subbands: peaks, beams, smoothing or the source count are on: their buffers are sized by the bands, turn them off first");
+    HIP_TRY(hipSetDevice(q->device));
+    if (q->submitted) HIP_TRY(hipDeviceSynchronize());   // the buffers may be in use (the last submit's stream may be the caller's, and gone)
+    q->submitted = false;                                // the matrices change their number: what the last submit left is gone
+    doa_free_matrices(q);
+    q->sb_nfft = nfft; q->sb_log2 = nfft ? ilog2(nfft) : 0; q->sb_first = nfft ? first : 0; q->nbands = nfft ? nbands : 1; q->sb_width = nfft ? width : 0;
+    q->sb_window = nfft ? window : 0;
+    q->sb_spb = nfft ? subband::subband_spb(q->B, nfft) : 1; q->sb_groups = nfft ? subband::subband_groups(q->m, nfft) : 1;
+    int rc = doa_alloc_matrices(q);
+    if (rc && nfft) {                                    // back to the plain engine, which fitted before
+        doa_free_matrices(q);
+        q->sb_nfft = q->sb_log2 = q->sb_first = q->sb_width = q->sb_window = 0; q->nbands = q->sb_spb = q->sb_groups = 1;
+        (void)doa_alloc_matrices(q);
+    }
+    return rc;
+}
+
+extern "C" int crsdr_doa_fetch_subbands(crsdr_doa *q, float *power)
+{
+    if (!q || !power) return fail(CRSDR_EINVAL, "doa_fetch_subbands: NULL doa or power");
+    if (!q->sb_nfft) return fail(CRSDR_ESTATE, "doa_fetch_subbands: no crsdr_doa_set_subbands");
+    if (!q->submitted) return fail(CRSDR_ESTATE, "doa_fetch_subbands: nothing submitted since crsdr_doa_set_subbands");
+    HIP_TRY(hipSetDevice(q->device));
+    HIP_TRY(hipMemcpyAsync(power, q->d_sbpower, sizeof(float) * (size_t)q->last_nest, hipMemcpyDeviceToHost, q->last_stream));
+    HIP_TRY(hipStreamSynchronize(q->last_stream));
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_subband_buffers(crsdr_doa *q, void **power)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_subband_buffers: NULL doa");
+    if (power) *power = q->d_sbpower;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_subband_covariance(float *rbands, float *power, const int8_t *matrix, int nrows, int blocksize, int nfft, int first, int nbands, int width,
+                                        int window, int mem_kind)
+{
+    if (!rbands || !matrix || nrows < 2 || nrows - 1 > subband::SB_MAX_ROWS || blocksize < 16)
+        return fail(CRSDR_EINVAL, "subband_covariance: need rbands, matrix, 2 <= nrows <= %d, blocksize >= 16", subband::SB_MAX_ROWS + 1);
+    { const int rc_ = subband_args_ok("subband_covariance", blocksize, nfft, first, nbands, width, window); if (rc_) return rc_; }
+    if (mem_kind != CRSDR_MEM_HOST && mem_kind != CRSDR_MEM_DEVICE) return fail(CRSDR_EINVAL, "subband_covariance: mem_kind = %d", mem_kind);
+    { int rc_ = require_device(); if (rc_) return rc_; }
+    std::lock_guard<std::mutex> lock_(g_op.mu);
+    const int m = nrows - 1, spb = subband::subband_spb(blocksize, nfft), lg = ilog2(nfft);
+    const size_t mb = (size_t)nrows * (size_t)blocksize, rb = sizeof(float2) * (size_t)nbands * m * m, pb = sizeof(float) * (size_t)nbands;
+    const int8_t *d_m = matrix;
+    float2 *d_r = (float2 *)rbands;
+    float *d_p = power;
+    if (mem_kind == CRSDR_MEM_HOST || !power) OP_RESERVE(2, pb);
+    if (mem_kind == CRSDR_MEM_HOST) {
+        OP_RESERVE(0, mb); OP_RESERVE(1, rb);
+        HIP_TRY(hipMemcpy(g_op.buf[0], matrix, mb, hipMemcpyHostToDevice));
+        d_m = (const int8_t *)g_op.buf[0]; d_r = (float2 *)g_op.buf[1]; d_p = (float *)g_op.buf[2];
+    } else {
+        if ((uintptr_t)d_m % 4 || (uintptr_t)d_r % 8 || (uintptr_t)power % 4) return fail(CRSDR_EINVAL, "subband_covariance: device matrix and power 4-byte, rbands 8-byte aligned");
+        if (!power) d_p = (float *)g_op.buf[2];
+    }
+    OP_RESERVE(3, sizeof(float2) * (size_t)spb * subband::subband_partial(m, nfft));
+    const dim3 grid((unsigned)spb, (unsigned)subband::subband_groups(m, nfft), 1);
+    SUBBAND_DISPATCH(lg, hipLaunchKernelGGL(subband::k_doa_subband_cov<LG>, grid, dim3(subband::SB_THREADS), 0, 0, d_m, (size_t)0, (size_t)0, nrows, blocksize, 1, spb,
+                                            window, (float2 *)g_op.buf[3]));
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(subband::k_doa_subband_reduce, dim3((unsigned)nbands, 1), dim3(256), 0, 0, (const float2 *)g_op.buf[3], spb, nrows, blocksize, 1, lg, first, width,
+                       window, d_r, d_p);
+    HIP_TRY(hipGetLastError());
+    if (mem_kind == CRSDR_MEM_HOST) {
+        HIP_TRY(hipMemcpy(rbands, d_r, rb, hipMemcpyDeviceToHost));
+        if (power) HIP_TRY(hipMemcpy(power, d_p, pb, hipMemcpyDeviceToHost));
+    } else HIP_TRY(hipDeviceSynchronize());
     return CRSDR_OK;
 }
 

@@ -97,6 +97,14 @@ int batch::set_order(int criterion, int kmin, int kmax, bool limit_directions)
     return rc;
 }
 
+int batch::set_subbands(int nfft, int first, int count, int width, int window)
+{
+    int rc = doa ? crsdr_doa_set_subbands(doa, nfft, first, count, width, window) : CRSDR_ESTATE;
+    if (!rc) nbands = nfft ? count : 0;
+    if (rc && doa) std::fprintf(stderr, "cbeamformer::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
 int batch::fetch(bool want_beams)
 {
     int nest = 0;
@@ -105,6 +113,10 @@ int batch::fetch(bool want_beams)
         peak.assign(2 * (size_t)nest, 0); peak_value.assign(nest, 0.f); sv.assign((size_t)nest * ms, 0.f); status.assign(nest, 0);
         if (keep) pm.assign((size_t)nest * cx * cy, 0.f);
         rc = crsdr_doa_fetch(doa, peak.data(), peak_value.data(), sv.data(), status.data(), keep ? pm.data() : nullptr, nullptr);
+    }
+    if (!rc && nbands) {
+        band_power.assign(nest, 0.f);
+        rc = crsdr_doa_fetch_subbands(doa, band_power.data());
     }
     if (!rc && counted) {
         order.assign(nest, 0);

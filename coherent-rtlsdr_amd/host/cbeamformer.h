@@ -33,6 +33,7 @@ class batch {
     int m = 0, ms = 0, cx = 0, cy = 0, npeaks = 0, nbeams = 0, half = 0, nframes = 1;      // ms: the subspace's size (m, or a sub-array's)
     bool counted = false;
     bool keep = false;
+    int nbands = 0;                                  // set_subbands: bands per estimate (0: off)
 public:
     // nrows x blocksize: the packets' geometry (1 + Mx * My rows); keep_spectrum: fetch() also fills pm
     batch(int nrows, int blocksize, int max_batch, int K = 1, int frames = 1, bool keep_spectrum = false, float d = D, int Mx = MX, int My = MY,
@@ -57,6 +58,13 @@ public:
     // from the next submit on, every estimate's source count (crsdr_doa_set_order: CRSDR_ORDER_MDL / CRSDR_ORDER_AIC over kmin .. kmax)
     // replaces K in its scan; limit_directions: set_peaks reports at most that many.  CRSDR_ORDER_OFF: off.
     int set_order(int criterion, int kmin = 1, int kmax = 0, bool limit_directions = false);      // kmax = 0: the largest, size - 1
+    // from the next submit on, one covariance per (estimate, band) in place of the time-domain one (crsdr_doa_set_subbands): band i is
+    // `width` bins of an nfft-point transform from bin first + i * width on (FFT order, wrapping), window CRSDR_WINDOW_*.  Every vector
+    // below then holds estimates() = blocks / frames * bands() entries, estimate e's band i at e * bands() + i, and band_power is
+    // filled.  nfft = 0: off.  Before set_peaks, set_smoothing and set_order (refused while one of them or beams are on; beams stay off).
+    int set_subbands(int nfft, int first = 0, int count = 1, int width = 1, int window = CRSDR_WINDOW_RECT);
+    int bands() const { return nbands; }
+    std::vector<float> band_power;                   // with set_subbands: [estimates]: Re trace(R_band) / M, the squelch of a band's direction
     // want_beams: also copy the beams' samples out (blocks x slots x blocksize / 2 complex floats)
     int fetch(bool want_beams = false);
     int estimates() const { return (int)status.size(); }

@@ -59,6 +59,7 @@ int main(int argc, char **argv)
     float beam_loading = 1e-2f;
     int smooth_x = 0, smooth_y = 0, order_crit = CRSDR_ORDER_OFF;
     bool smooth_fb = false;
+    int sb_nfft = 0, sb_first = 0, sb_count = 1, sb_width = 1, sb_window = CRSDR_WINDOW_RECT;
     bool engine_batches = false;
     int ranks = 1, rank = 0, device = 0;
     std::string idfile;
@@ -100,6 +101,17 @@ int main(int argc, char **argv)
         else if (a == "--order" && i + 1 < argc) {
             const std::string c = argv[++i];
             order_crit = c == "mdl" ? CRSDR_ORDER_MDL : c == "aic" ? CRSDR_ORDER_AIC : -1;
+        }
+        // with --bench --music: a direction and a power per frequency band (crsdr_doa_set_subbands): COUNT bands of WIDTH bins of an
+        // NFFT-point transform from bin FIRST on
+        else if (a == "--subbands" && i + 1 < argc) {
+            const int n = std::sscanf(argv[++i], "%d:%d:%d:%d", &sb_nfft, &sb_first, &sb_count, &sb_width);
+            if (n < 3) sb_nfft = -1;
+            if (n == 3) sb_width = 1;
+        }
+        else if (a == "--window" && i + 1 < argc) {
+            const std::string w = argv[++i];
+            sb_window = w == "rect" ? CRSDR_WINDOW_RECT : w == "hann" ? CRSDR_WINDOW_HANN : -1;
         }
         else if (a == "--loading" && i + 1 < argc) beam_loading = (float)std::atof(argv[++i]);
         else if (a == "--batch-parity") batch_parity = true;   // the batched engine's packets == step()'s packets, bit for bit (own read counters, a masked row)
@@ -301,6 +313,11 @@ int main(int argc, char **argv)
         if (music && !coherent.sharded()) {
             doa.reset(new cbeamformer::batch(1 + nsig, B, batch));
             if (nsig != cbeamformer::MX * cbeamformer::MY || !doa->ok()) { std::printf("doa: unavailable (needs --nsig 21)\nDEMO FAILED\n"); return 1; }
+            // the bands first: what follows sizes its buffers by them
+            if (sb_nfft && doa->set_subbands(sb_nfft, sb_first, sb_count, sb_width, sb_window)) {
+                std::printf("doa: --subbands %d:%d:%d:%d --window (rect|hann) refused\nDEMO FAILED\n", sb_nfft, sb_first, sb_count, sb_width);
+                return 1;
+            }
             if (smooth_x || smooth_fb) {
                 const int sx = smooth_x ? smooth_x : cbeamformer::MX, sy = smooth_x ? smooth_y : cbeamformer::MY;
                 if (doa->set_smoothing(sx, sy, smooth_fb)) { std::printf("doa: --smooth %dx%d%s refused\nDEMO FAILED\n", sx, sy, smooth_fb ? " --fb" : ""); return 1; }
@@ -315,6 +332,16 @@ int main(int argc, char **argv)
             ok = doa->submit(coherent.engine_plan()) == CRSDR_OK && doa->fetch() == CRSDR_OK;
             if (!ok || !report) return;
             const int n = doa->estimates();
+            if (doa->bands()) {
+                // every estimate's bands: the direction at that frequency and the power that says whether to trust it
+                const int nb_ = doa->bands();
+                for (int e = 0; e < n / nb_; ++e)
+                    for (int i = 0; i < nb_; ++i) {
+                        const int x = e * nb_ + i, f0 = (sb_first + i * sb_width) % sb_nfft;
+                        std::printf("doa: batch %d: estimate %d band %d (bins %d..%d of %d): (%d, %d) power %.4g\n", b, e, i, f0, (f0 + sb_width - 1) % sb_nfft, sb_nfft,
+                                    doa->peak[2 * x], doa->peak[2 * x + 1], (double)doa->band_power[x]);
+                    }
+            }
             if (order_crit) {
                 std::string ks;
                 for (int e = 0; e < n; ++e) ks += " " + std::to_string(doa->order[e]);

@@ -607,6 +607,45 @@ int crsdr_smooth_covariance(float *rs, const float *rxx, int mx, int my, int sx,
 int crsdr_source_order(int32_t *k, float *criterion_values, const float *sv, int m, int64_t nsnap, int criterion, int kmin, int kmax,
                        int mem_kind);
 
+/* One covariance per frequency band, in place of the one time-domain covariance per estimate: "which direction is the signal at THIS
+ * frequency".  Per packet a signal row c holds L = blocksize / 2 samples x_c[n] = (I + jQ) / 127.  Each row is cut into J = L / nfft
+ * segments of N = nfft samples (never across packets; an estimate has J' = frames * J), and with the window w
+ *     X_c[j][f] = sum_n w[n] x_c[jN + n] exp(-2 pi i f n / N)                                    (the forward transform of crsdr_fft)
+ *     R_f[a][b] = 1 / (J' N sum_n w[n]^2) * sum_j conj(X_a[j][f]) X_b[j][f]                      (the X^H X convention of crsdr_covariance)
+ * CRSDR_WINDOW_RECT: w = 1, and sum_f R_f is the raw second moment (1/L') sum conj(x_a) x_b (Parseval).  CRSDR_WINDOW_HANN:
+ * w[n] = 0.5 - 0.5 cos(2 pi n / N), periodic.  No mean is removed: a DC offset lands in bin 0 (Hann: bins 0 and +-1), and the caller
+ * leaves those bands out.  Band i, 0 <= i < nbands, is the sum of R_f over the bins (first + i * width + u) mod N, u < width: FFT
+ * order, negative frequencies in the upper half, and first may wrap.  power[i] = Re trace(R_band_i) / m, the squelch before a band's
+ * direction is trusted.  The sums over j are fp32 per K slice of segments (a split that depends on blocksize and nfft alone: an
+ * estimate has the same bits wherever it sits in a batch), the slices, the band's bins and the scale fp64, rounded once.
+ * Limits: nfft a power of two in 8 .. 256, blocksize % (2 nfft) == 0, 0 <= first < nfft, nbands, width >= 1, nbands * width <= nfft,
+ * (max_batch / frames) * nbands <= 4096.  CRSDR_EINVAL outside them.
+ *
+ * crsdr_doa_set_subbands: from the next submit on the band covariances replace the time-domain one (the same number of launches), and
+ * every later step runs over nest * nbands matrices, estimate e's band i at index e * nbands + i: crsdr_doa_fetch (peak, peak_value, sv,
+ * status, pm, rxx = the band matrices), crsdr_doa_fetch_subspace, the device buffers, and crsdr_doa_last_submit's nest all count
+ * nest * nbands.  Directions, smoothing and the source count work per band (the count with N = J' * width snapshots) and size their
+ * buffers by (max_batch / frames) * nbands, so the order is fixed: this call, on or off (nfft = 0; the other arguments are then ignored),
+ * returns CRSDR_ESTATE while any of crsdr_doa_set_peaks, _set_beams, _set_smoothing or _set_order is on, and crsdr_doa_set_beams returns
+ * CRSDR_ESTATE while subbands are on (a band's weights applied to the wideband samples mean nothing).  Waits for the device if a submit
+ * was made and discards what it left: the fetch functions return CRSDR_ESTATE until the next submit. */
+enum { CRSDR_WINDOW_RECT = 0, CRSDR_WINDOW_HANN = 1 };
+int crsdr_doa_set_subbands(crsdr_doa *doa, int nfft, int first, int nbands, int width, int window);
+
+/* Waits for the last submit and copies out power [nest][nbands].  CRSDR_ESTATE with subbands off or before the first submit after
+ * crsdr_doa_set_subbands. */
+int crsdr_doa_fetch_subbands(crsdr_doa *doa, float *power);
+
+/* Device address of power ([max_batch / frames][nbands]; NULL while subbands are off), for consumers on the same stream.  It changes
+ * with every crsdr_doa_set_subbands, as the addresses of crsdr_doa_device_buffers do. */
+int crsdr_doa_subband_buffers(crsdr_doa *doa, void **power);
+
+/* The per-op form on one packet's matrix [nrows][blocksize] (frames = 1): the same device functions, bit for bit.
+ * rbands [nbands][m][m][2], power [nbands] or NULL, m = nrows - 1 in 2 .. 64.  mem_kind: CRSDR_MEM_HOST (copied) or CRSDR_MEM_DEVICE
+ * (every pointer on the device; matrix and power 4-byte, rbands 8-byte aligned). */
+int crsdr_subband_covariance(float *rbands, float *power, const int8_t *matrix, int nrows, int blocksize, int nfft, int first, int nbands,
+                             int width, int window, int mem_kind);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,13 +14,16 @@
   (f) with --fb: crsdr_doa_set_smoothing(7, 3, CRSDR_SMOOTH_FB) (forward-backward averaging alone), then the (b) submit + peaks,
   (s) with --smooth SXxSY: crsdr_doa_set_smoothing(SX, SY, CRSDR_SMOOTH_FB if --fb), then the (b) submit + peaks, and
   (o) with --order mdl|aic: crsdr_doa_set_order over k = 1 .. 20, then the (b) submit + peaks (on the unsmoothed covariance).
+  (u) with --subbands NFFT:FIRST:COUNT[:WIDTH] [--window rect|hann]: crsdr_doa_set_subbands, then the (b) submit + the peaks of all
+      64 x COUNT band matrices + the bands' power; reported with its frames/s and its ratio to (b).
 
 --runs runs of each, alternating a, b, c in one session (two worker processes, both alive throughout); medians and ranges.
 --doa-lib LIB starts a second doa worker on another build (e.g. the parent commit's) through CRSDR_LIB and times its (b) and (c) in
 the same alternation, reported as lib:b and lib:c.  --reps N: every (b), (c), (p), (q), (h) figure is the mean of N back-to-back submit + fetch.
 Also: what crsdr_doa_submit_plan + the peak fetch add to a 22-row, T = 64 plan batch (plan.submit + sync against
 plan.submit + doa.submit_plan + fetch).  --json FILE keeps the record; --once MODE runs three submit + fetch and exits (for a kernel trace): b, c, p, q as above, q64 = the
-beams at their largest shape (8 x 8 array, 16 slots: 65 rows x 16384, 64 blocks), s = --smooth / --fb / --order as given, all on one object."""
+beams at their largest shape (8 x 8 array, 16 slots: 65 rows x 16384, 64 blocks), s = --smooth / --fb / --order as given, all on one object,
+u = --subbands / --window as given."""
 import argparse, importlib, json, os, subprocess, sys, time
 import numpy as np
 
@@ -28,6 +31,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NROWS, B, T, M = 22, 16384, 64, 21
 BEAM_MODES = {"conventional": 1, "mvdr": 2}
 ORDER_MODES = {"mdl": 1, "aic": 2}
+WINDOWS = {"rect": 0, "hann": 1}
+
+
+def _bands(text):
+    v = [int(x) for x in text.split(":")]
+    if len(v) not in (3, 4):
+        raise ValueError("--subbands NFFT:FIRST:COUNT[:WIDTH]")
+    return v + [1] * (4 - len(v))
 
 
 def _sub_array(text):
@@ -79,7 +90,7 @@ def worker_perop():
         print(time.perf_counter() - t0, flush=True)
 
 
-def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None, fb=False, order=None):
+def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None, fb=False, order=None, subbands=None, window="rect"):
     """(b), (c), (p), (q), (h), (f), (s), (o) and the plan figures: 'b' / 'c' / 'p' / 'q' / 'h' / 'f' / 's' / 'o' / 'plan' / 'plan+doa' on
     stdin -> seconds of one batch of 64 on stdout."""
     torch, ura, b, dev, pk, off, stride, host = _setup()
@@ -111,6 +122,16 @@ def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None
     if order:
         extra["o"] = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
         extra["o"].set_order(ORDER_MODES[order], 1, M - 1)
+    udoa = None
+    if subbands:
+        udoa = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
+        udoa.set_subbands(*_bands(subbands), WINDOWS[window])
+
+    def run_u():
+        for _ in range(reps):
+            udoa.submit(pk.data_ptr(), stride, off, T)
+            udoa.fetch_peaks()
+            udoa.fetch_subbands()
 
     def run_extra(d):
         def run():
@@ -165,6 +186,8 @@ def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None
         jobs["q"], jobs["h"] = (run_q, reps), (run_h, reps)
     for key, d in extra.items():
         jobs[key] = (run_extra(d), reps)
+    if udoa is not None:
+        jobs["u"] = (run_u, reps)
     for f, _ in jobs.values():
         f()
     print("ready", flush=True)
@@ -175,7 +198,7 @@ def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None
         print((time.perf_counter() - t0) / n, flush=True)
 
 
-def once(mode, npeaks=0, radius=1, beams=None, loading=1e-2, smooth=None, fb=False, order=None):
+def once(mode, npeaks=0, radius=1, beams=None, loading=1e-2, smooth=None, fb=False, order=None, subbands=None, window="rect"):
     mx, my = (8, 8) if mode == "q64" else (None, None)
     torch, ura, b, dev, pk, off, stride, _ = _setup(mx, my)
     mx, my = mx or ura.MX, my or ura.MY
@@ -191,9 +214,13 @@ def once(mode, npeaks=0, radius=1, beams=None, loading=1e-2, smooth=None, fb=Fal
             d.set_smoothing(*(_sub_array(smooth) if smooth else (mx, my)), b.SMOOTH_FB if fb else 0)
         if order:
             d.set_order(ORDER_MODES[order], 1, d.ms - 1)
+    if mode == "u":
+        d.set_subbands(*_bands(subbands), WINDOWS[window])
     for _ in range(3):
         d.submit(pk.data_ptr(), stride, off, T)
         out = d.fetch()
+    if mode == "u":
+        print("band power of the first estimate", np.round(d.fetch_subbands()[0], 5).tolist())
     print("peaks", out["peak"][:4].tolist(), "launches", d.last_launches())
     if mode == "s" and order:
         print("k", d.fetch_order()["k"].tolist())
@@ -233,7 +260,9 @@ def _stat(xs):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--worker", choices=["perop", "doa"])
-    ap.add_argument("--once", choices=["b", "c", "p", "q", "q64", "s"])
+    ap.add_argument("--once", choices=["b", "c", "p", "q", "q64", "s", "u"])
+    ap.add_argument("--subbands", default=None, metavar="NFFT:FIRST:COUNT[:WIDTH]", help="(u): a covariance per frequency band (crsdr_doa_set_subbands)")
+    ap.add_argument("--window", choices=sorted(WINDOWS), default="rect", help="(u): the segments' window")
     ap.add_argument("--smooth", default=None, metavar="SXxSY", help="(s): sub-arrays of SX x SY elements (crsdr_doa_set_smoothing)")
     ap.add_argument("--fb", action="store_true", help="(f): forward-backward averaging alone; with --smooth: (s) averages backward as well")
     ap.add_argument("--order", choices=sorted(ORDER_MODES), default=None, help="(o): the source count per estimate (crsdr_doa_set_order)")
@@ -248,9 +277,9 @@ def main():
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     if a.worker:
-        return worker_perop() if a.worker == "perop" else worker_doa(a.peaks, a.radius, a.reps, a.beams, a.loading, a.smooth, a.fb, a.order)
+        return worker_perop() if a.worker == "perop" else worker_doa(a.peaks, a.radius, a.reps, a.beams, a.loading, a.smooth, a.fb, a.order, a.subbands, a.window)
     if a.once:
-        return once(a.once, a.peaks, a.radius, a.beams, a.loading, a.smooth, a.fb, a.order)
+        return once(a.once, a.peaks, a.radius, a.beams, a.loading, a.smooth, a.fb, a.order, a.subbands, a.window)
     pargs = ["--peaks", str(a.peaks), "--radius", str(a.radius), "--reps", str(a.reps), "--loading", str(a.loading)]
     if a.beams:
         pargs += ["--beams", a.beams]
@@ -260,7 +289,9 @@ def main():
         pargs += ["--fb"]
     if a.order:
         pargs += ["--order", a.order]
-    legs = (["f"] if a.fb else []) + (["s"] if a.smooth else []) + (["o"] if a.order else [])
+    if a.subbands:
+        pargs += ["--subbands", a.subbands, "--window", a.window]
+    legs = (["f"] if a.fb else []) + (["s"] if a.smooth else []) + (["o"] if a.order else []) + (["u"] if a.subbands else [])
     wa, wb = Worker("perop", a.perop_lib), Worker("doa", extra=pargs)
     wl = Worker("doa", a.doa_lib, extra=["--reps", str(a.reps)]) if a.doa_lib else None
     keys = ["a", "b", "c", "plan", "plan+doa"] + (["lib:b", "lib:c"] if wl else []) + (["p"] if a.peaks else []) + (["q", "h"] if a.beams else []) + legs
@@ -291,20 +322,26 @@ def main():
            "perop_lib": a.perop_lib or "current build", "doa_lib": a.doa_lib, "peaks": {"count": a.peaks, "radius": a.radius} if a.peaks else None,
            "beams": {"mode": a.beams, "loading": a.loading} if a.beams else None,
            "smoothing": {"sub_array": a.smooth, "fb": a.fb} if (a.smooth or a.fb) else None, "order": a.order,
+           "subbands": dict(zip(("nfft", "first", "nbands", "width"), _bands(a.subbands)), window=a.window) if a.subbands else None,
            "ms_per_batch": {k: _stat([1e3 * x for x in v]) for k, v in sec.items()},
-           "frames_per_s": {k: _stat([T / x for x in sec[k]]) for k in ("a", "b", "c")}}
+           "frames_per_s": {k: _stat([T / x for x in sec[k]]) for k in ("a", "b", "c") + (("u",) if a.subbands else ())}}
+    if a.subbands:
+        rec["u_over_b_ms"] = rec["ms_per_batch"]["u"]["median"] / rec["ms_per_batch"]["b"]["median"]
     rec["b_faster_than_a_ranges_disjoint"] = rec["ms_per_batch"]["b"]["max"] < rec["ms_per_batch"]["a"]["min"]
     rec["submit_plan_adds_ms_per_batch"] = rec["ms_per_batch"]["plan+doa"]["median"] - rec["ms_per_batch"]["plan"]["median"]
     names = {"a": "per-op loop, device pointers", "b": "doa submit + peaks", "c": "doa submit + peaks + spectra",
              "plan": "plan batch alone", "plan+doa": "plan batch + submit_plan + peaks", "lib:b": "--doa-lib: submit + peaks",
              "lib:c": "--doa-lib: submit + peaks + spectra", "p": f"set_peaks({a.peaks}, {a.radius}): submit + directions",
              "q": f"(p) + {a.beams} beams: submit + power", "h": "(p) + packets and vec to the host",
-             "f": "FB alone: submit + peaks", "s": f"{a.smooth}{' + FB' if a.fb else ''}: submit + peaks", "o": f"order {a.order}: submit + peaks"}
+             "f": "FB alone: submit + peaks", "s": f"{a.smooth}{' + FB' if a.fb else ''}: submit + peaks", "o": f"order {a.order}: submit + peaks",
+             "u": f"subbands {a.subbands} {a.window}: submit + peaks + power"}
     for k, s in rec["ms_per_batch"].items():
         fps = f"  {T / (1e-3 * s['median']):10.0f} frames/s" if k in rec["frames_per_s"] else ""
         print(f"({k}) {names[k]:34s} {s['median']:8.3f} ms per 64 blocks  [{s['min']:.3f} .. {s['max']:.3f}]{fps}")
     print(f"(b) faster than (a), ranges disjoint: {rec['b_faster_than_a_ranges_disjoint']};  "
           f"a direction per block adds {rec['submit_plan_adds_ms_per_batch']:.3f} ms to a plan batch of 64")
+    if a.subbands:
+        print(f"(u) takes {rec['u_over_b_ms']:.2f} x the time of (b) for {_bands(a.subbands)[2]} x the matrices")
     for k in legs:
         rec[f"{k}_adds_ms_per_batch"] = rec["ms_per_batch"][k]["median"] - rec["ms_per_batch"]["b"]["median"]
         print(f"({k}) adds {1e3 * rec[f'{k}_adds_ms_per_batch']:.0f} us to (b)")
