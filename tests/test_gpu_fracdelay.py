@@ -12,6 +12,8 @@ import os
 import numpy as np
 import pytest
 
+from peak_cases import _bandlimited_rows      # shared with test_gpu_peak.py
+
 pytestmark = pytest.mark.gpu
 
 
@@ -71,32 +73,6 @@ def test_frac_apply_matches_oracle_and_fp64_model(b, oracle, model, synth, log2B
     exp = plain.block(rows, seq=3)
     assert np.array_equal(got["lag"], exp["lag"])
     plan.close(); plain.close()
-
-
-def _bandlimited_rows(L, total_delays, phis, seed=3, band=0.25, sigma=30.0):
-    """ref = low-pass complex Gaussian noise (|f| < band * fs / 2); row k = ref delayed by total_delays[k] samples
-    (any real number: the delay is a phase ramp on a 4L-point spectrum of a longer realisation, so nothing wraps into
-    the block) and rotated by phis[k]; int8, round half even."""
-    rng = np.random.default_rng(seed)
-    n = 4 * L
-    X = np.fft.fft(rng.standard_normal(n) + 1j * rng.standard_normal(n))
-    f = np.fft.fftfreq(n)
-    X[np.abs(f) > band / 2] = 0
-    base = np.fft.ifft(X)
-    base *= sigma / np.sqrt(np.mean(np.abs(base) ** 2) / 2)
-
-    def q(x):
-        out = np.empty(2 * L, dtype=np.int8)
-        out[0::2] = np.clip(np.rint(x.real), -128, 127)
-        out[1::2] = np.clip(np.rint(x.imag), -128, 127)
-        return out
-
-    rows = np.zeros((1 + len(total_delays), 2 * L), dtype=np.int8)
-    rows[0] = q(base[L:2 * L])
-    for k, (tau, phi) in enumerate(zip(total_delays, phis)):
-        xs = np.fft.ifft(X * np.exp(-2j * np.pi * f * tau)) * (sigma / np.sqrt(np.mean(np.abs(np.fft.ifft(X)) ** 2) / 2))
-        rows[1 + k] = q(xs[L:2 * L] * np.exp(1j * phi))
-    return rows
 
 
 def _residual_delay(y, r, band=0.25):
