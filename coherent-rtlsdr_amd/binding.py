@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "crsdr_doa_set_smoothing", "crsdr_doa_fetch_smoothed", "crsdr_doa_set_order", "crsdr_doa_fetch_order", "crsdr_doa_order_buffers",
     "crsdr_smooth_covariance", "crsdr_source_order",
     "crsdr_doa_set_subbands", "crsdr_doa_fetch_subbands", "crsdr_doa_subband_buffers", "crsdr_subband_covariance",
+    "crsdr_doa_set_subband_beams", "crsdr_doa_fetch_subband_beams", "crsdr_doa_subband_beam_buffers", "crsdr_subband_beamform",
 ]
 DOA_KEEP_SPECTRUM, DOA_KEEP_RXX = 1, 2
 BEAM_OFF, BEAM_CONVENTIONAL, BEAM_MVDR = 0, 1, 2
@@ -192,6 +193,11 @@ def lib():
         L.crsdr_subband_covariance.argtypes = [f32p, f32p, i8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         L.crsdr_smooth_covariance.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int]
         L.crsdr_source_order.argtypes = [vp, vp, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]
+    if hasattr(L, "crsdr_doa_set_subband_beams"):    # (likewise: an older build has no band beams)
+        L.crsdr_doa_set_subband_beams.argtypes = [vp, C.c_int, C.c_float, C.c_int, f32p]
+        L.crsdr_doa_fetch_subband_beams.argtypes = [vp, f32p, f32p, f32p]
+        L.crsdr_doa_subband_beam_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int)]
+        L.crsdr_subband_beamform.argtypes = [f32p, i8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_int]
     _lib = L
     return L
 
@@ -416,6 +422,28 @@ def subband_covariance_device(rbands_ptr: int, power_ptr: int, matrix_ptr: int, 
     cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
     _check(lib().crsdr_subband_covariance(cast(rbands_ptr, C.c_float), cast(power_ptr, C.c_float), cast(matrix_ptr, C.c_int8), int(nrows), int(B),
                                           int(nfft), int(first), int(nbands), int(width), int(window), MEM_DEVICE))
+
+
+def subband_beamform(matrix, weights, nfft, first=0, nbands=1, width=1, window=WINDOW_RECT):
+    """crsdr_subband_beamform: out [nbands][nbeams][J][width] complex64 = weights [nbands][nbeams][nrows - 1] applied to the band
+    spectra of the signal rows of matrix [nrows][B] int8 (J = B / (2 nfft) segments; c_w sum_c u[c - 1] X_c, no conjugate): the batched
+    engine's band beam arithmetic on one matrix."""
+    m = np.ascontiguousarray(matrix, dtype=np.int8)
+    w = np.ascontiguousarray(weights, dtype=np.complex64)
+    nrows, B = m.shape
+    if w.ndim != 3 or w.shape[0] != nbands or w.shape[2] != nrows - 1:
+        raise ValueError("weights must be [nbands][nbeams][nrows - 1]")
+    out = np.empty((w.shape[0], w.shape[1], B // (2 * int(nfft)) if nfft > 0 else 0, max(int(width), 0)), dtype=np.complex64)
+    _check(lib().crsdr_subband_beamform(_p(out.view(np.float32), C.c_float), _p(m, C.c_int8), nrows, B, int(nfft), int(first), int(nbands), int(width),
+                                        int(window), _p(w.view(np.float32), C.c_float), w.shape[1], MEM_HOST))
+    return out
+
+
+def subband_beamform_device(out_ptr: int, matrix_ptr: int, nrows, B, nfft, first, nbands, width, window, weights_ptr: int, nbeams):
+    """Same on device memory; returns after the kernel finished."""
+    cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
+    _check(lib().crsdr_subband_beamform(cast(out_ptr, C.c_float), cast(matrix_ptr, C.c_int8), int(nrows), int(B), int(nfft), int(first), int(nbands),
+                                        int(width), int(window), cast(weights_ptr, C.c_float), int(nbeams), MEM_DEVICE))
 
 
 def assemble_slabs(packets_ptr: int, packet_stride: int, nrows: int, B: int, recv_ptr: int, nsrc: int, nblocks: int, stream: int | None = None):
@@ -678,6 +706,7 @@ class Doa:
         self.npeaks, self.nbeams = 0, 0
         self.mx, self.my, self.ms, self.order = int(mx), int(my), self.m, None      # ms: the subspace's size; order: (kmin, kmax)
         self.nbands = 0                                                             # set_subbands: bands per estimate (0: off)
+        self.band_shape, self.nbandbeams = None, 0                                  # set_subbands: (J, width); set_subband_beams: slots
 
     def _last(self):
         nest, launches = C.c_int(0), C.c_int(0)
@@ -808,10 +837,12 @@ class Doa:
     def set_subbands(self, nfft: int, first: int = 0, nbands: int = 1, width: int = 1, window: int = WINDOW_RECT):
         """crsdr_doa_set_subbands: from the next submit on, one covariance per (estimate, band) of `width` bins of an nfft-point
         transform from bin `first` on (FFT order, wrapping); every fetch then counts nest * nbands entries, estimate e's band i at
-        e * nbands + i.  nfft = 0: off.  Only while peaks, beams, smoothing and order are off (set them afterwards; beams stay off).
+        e * nbands + i.  nfft = 0: off.  Only while peaks, beams, smoothing and order are off (set them afterwards; the beams of the
+        bands are set_subband_beams).
         Waits for the device if a submit was made, and discards that submit's results."""
         _check(lib().crsdr_doa_set_subbands(self._h, int(nfft), int(first), int(nbands), int(width), int(window)))
         self.nbands = int(nbands) if nfft else 0
+        self.band_shape = (self.B // (2 * int(nfft)), int(width)) if nfft else None
 
     def fetch_subbands(self) -> np.ndarray:
         """Waits for the last submit.  power [nest][nbands] = Re trace(R_band) / m."""
@@ -823,6 +854,31 @@ class Doa:
         p = C.c_void_p()
         _check(lib().crsdr_doa_subband_buffers(self._h, C.byref(p)))
         return {"power": p.value}
+
+    def set_subband_beams(self, mode: int, loading: float = 1e-2, fixed_angles=None):
+        """crsdr_doa_set_subband_beams: with subbands on, from the next submit on, weights and power per (estimate, band, slot) and one
+        narrowband IQ stream per (packet, band, slot): the band's weights applied to the rows' band spectra.  Arguments as set_beams.
+        Waits for the device if a submit was made."""
+        fa = None if fixed_angles is None else np.ascontiguousarray(fixed_angles, dtype=np.float32).reshape(-1, 2)
+        _check(lib().crsdr_doa_set_subband_beams(self._h, int(mode), C.c_float(loading), 0 if fa is None else fa.shape[0], _p(fa, C.c_float)))
+        self.nbandbeams = self.subband_beam_buffers()["nbeams"]
+
+    def fetch_subband_beams(self, weights=True, power=True, beams=True) -> dict:
+        """Waits for the last submit.  weights [nest * nbands][nbeams][m] complex64, power [nest * nbands][nbeams], beams
+        [nblocks][nbands][nbeams][J][width] complex64 (each only if asked for)."""
+        n, nb = self._last()[0], self.nbandbeams
+        nbands, (J, width) = max(self.nbands, 1), self.band_shape or (0, 0)
+        w = np.zeros((n, nb, self.m), dtype=np.complex64) if weights else None
+        pw = np.zeros((n, nb), dtype=np.float32) if power else None
+        y = np.zeros((n // nbands * self.frames, nbands, nb, J, width), dtype=np.complex64) if beams else None
+        _check(lib().crsdr_doa_fetch_subband_beams(self._h, _p(None if w is None else w.view(np.float32), C.c_float), _p(pw, C.c_float),
+                                                   _p(None if y is None else y.view(np.float32), C.c_float)))
+        return {k: v for k, v in (("weights", w), ("power", pw), ("beams", y)) if v is not None}
+
+    def subband_beam_buffers(self) -> dict:
+        ptrs, nb = [C.c_void_p() for _ in range(3)], C.c_int(0)
+        _check(lib().crsdr_doa_subband_beam_buffers(self._h, *[C.byref(p) for p in ptrs], C.byref(nb)))
+        return dict(zip(("weights", "power", "beams"), [p.value for p in ptrs]), nbeams=nb.value)
 
     def last_launches(self) -> int:
         return self._last()[1]

@@ -7,6 +7,7 @@
 #include "smooth.hpp"
 #include "beams.hpp"
 #include "subband.hpp"
+#include "subband_beams.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -1855,7 +1856,8 @@ extern "C" int crsdr_plan_kernel_times(crsdr_plan *p, int which, float *ms, int 
 //      crsdr_doa_set_beams what the beams need and theirs (beams.hpp), crsdr_doa_set_smoothing and crsdr_doa_set_order theirs and one
 //      launch each (smooth.hpp): behind the reducer, and between the subspace and the scan.  crsdr_doa_set_subbands replaces the two
 //      covariance launches by subband.hpp's (one covariance per estimate and frequency band) and reallocates every per-matrix buffer
-//      for (max_batch / frames) * nbands matrices: the launches behind it then run over that many.
+//      for (max_batch / frames) * nbands matrices: the launches behind it then run over that many.  crsdr_doa_set_subband_beams on top of
+//      it: the beam weights per (estimate, band) and subband_beams.hpp's apply kernel on the rows' band spectra.
 // ================================================================================================
 struct crsdr_doa {
     int nrows = 0, B = 0, m = 0, device = 0, max_batch = 1, frames = 1, k = 1, mx = 0, my = 0, ncx = 0, ncy = 0;
@@ -1885,6 +1887,11 @@ struct crsdr_doa {
     float2 *d_bw = nullptr, *d_beams = nullptr;
     float *d_bpow = nullptr, *d_bangles = nullptr;
     bool beams_submitted = false;
+    // crsdr_doa_set_subband_beams: the same fields and buffers (the two kinds of beams exclude each other: one needs subbands off, the
+    // other on) with band_beams set: weights [nest * nbands][nbeams][m], power [nest * nbands][nbeams], beams
+    // [max_batch][nbands][nbeams][J][width]; sbb_lds: float2 of dynamic LDS of the apply kernel
+    bool band_beams = false;
+    int sbb_lds = 0;
     // crsdr_doa_set_smoothing: sub-arrays of sx x sy elements (ms of them; ms = m while off: ms is the subspace's size either way), the
     // smoothed covariances [nest][ms][ms]; last_ms: of the last submit
     bool smooth_on = false, smooth_submitted = false;
@@ -1940,7 +1947,7 @@ static void doa_free_beams(crsdr_doa *q)
     void *bufs[] = {q->d_bw, q->d_beams, q->d_bpow, q->d_bangles};
     for (void *b : bufs) if (b) (void)hipFree(b);
     q->d_bw = q->d_beams = nullptr; q->d_bpow = q->d_bangles = nullptr;
-    q->beam_mode = q->nbeams = q->nfixed = 0; q->loading = 0.f; q->beams_submitted = false;
+    q->beam_mode = q->nbeams = q->nfixed = 0; q->loading = 0.f; q->beams_submitted = false; q->band_beams = false; q->sbb_lds = 0;
 }
 
 // the buffers with one entry per matrix (estimate, or estimate and band), and the subband workspace
@@ -2142,9 +2149,17 @@ static int doa_launch(crsdr_doa *q, const int8_t *packets, size_t packet_stride,
                            q->m, q->mx, q->d, q->ncx, q->ncy, q->beam_mode, q->loading, (const float *)(q->nfixed ? q->d_bangles : nullptr),
                            (const int32_t *)(q->npeaks ? q->d_found : nullptr), (const int32_t *)q->d_dirs, (const int32_t *)q->d_peak, q->d_bw, q->d_bpow);
         HIP_TRY(hipGetLastError()); ++launches;
-        const dim3 grid((unsigned)((q->B / 4 + beams::AP_THREADS - 1) / beams::AP_THREADS), (unsigned)nblocks);
-        BEAMS_DISPATCH(q->nbeams, hipLaunchKernelGGL(beams::k_doa_beam_apply<NB>, grid, dim3(beams::AP_THREADS), 0, S, packets, packet_stride, matrix_offset,
-                                                     q->nrows, q->B, q->frames, (const float2 *)q->d_bw, q->nbeams, q->d_beams));
+        if (q->band_beams) {
+            // the weights above are per (estimate, band): applied to the rows' band spectra
+            const dim3 grid((unsigned)sbbeams::sbb_spb(q->B, q->sb_nfft), (unsigned)nblocks);
+            SUBBAND_DISPATCH(q->sb_log2, hipLaunchKernelGGL(sbbeams::k_doa_subband_beam_apply<LG>, grid, dim3(sbbeams::SBB_THREADS), sizeof(float2) * (size_t)q->sbb_lds,
+                                                            S, packets, packet_stride, matrix_offset, q->nrows, q->B, q->frames, q->sb_first, q->nbands, q->sb_width,
+                                                            q->sb_window, (const float2 *)q->d_bw, q->nbeams, q->sbb_lds, q->d_beams));
+        } else {
+            const dim3 grid((unsigned)((q->B / 4 + beams::AP_THREADS - 1) / beams::AP_THREADS), (unsigned)nblocks);
+            BEAMS_DISPATCH(q->nbeams, hipLaunchKernelGGL(beams::k_doa_beam_apply<NB>, grid, dim3(beams::AP_THREADS), 0, S, packets, packet_stride, matrix_offset,
+                                                         q->nrows, q->B, q->frames, (const float2 *)q->d_bw, q->nbeams, q->d_beams));
+        }
         HIP_TRY(hipGetLastError()); ++launches;
     }
     q->last_stream = S; q->last_nest = (int)nest; q->last_nblocks = nblocks; q->last_launches = launches; q->submitted = true;
@@ -2240,7 +2255,7 @@ extern "C" int crsdr_doa_set_peaks(crsdr_doa *q, int count, int radius)
     if (count < 0 || count > doa::MAX_PEAKS) return fail(CRSDR_EINVAL, "doa_set_peaks: count = %d (0..%d)", count, doa::MAX_PEAKS);
     if (count > 0 && (radius < 1 || radius > doa::MAX_RADIUS)) return fail(CRSDR_EINVAL, "doa_set_peaks: radius = %d (1..%d)", radius, doa::MAX_RADIUS);
     if (q->beam_mode && !q->nfixed)
-        return fail(CRSDR_ESTATE, "doa_set_peaks: beams follow the directions (crsdr_doa_set_beams with nfixed = 0) and are sized by them: turn the beams off first");
+        return fail(CRSDR_ESTATE, "doa_set_peaks: beams follow the directions (crsdr_doa_set_beams or _set_subband_beams with nfixed = 0) and are sized by them: turn the beams off first");
     HIP_TRY(hipSetDevice(q->device));
     if (q->submitted) HIP_TRY(hipDeviceSynchronize());   // the buffers may be in use (the last submit's stream may be the caller's, and gone)
     doa_free_peaks(q);
@@ -2288,6 +2303,7 @@ extern "C" int crsdr_doa_set_beams(crsdr_doa *q, int mode, float loading, int nf
     if (mode != CRSDR_BEAM_OFF && q->ms < q->m)
         return fail(CRSDR_ESTATE, "doa_set_beams: smoothing over %d x %d sub-arrays is on (crsdr_doa_set_smoothing): the weights are %d-vectors and there is no %d x %d subspace",
                     q->sx, q->sy, q->m, q->m, q->m);
+    if (q->band_beams) return CRSDR_OK;                  // (off, with subbands on: the band beams are crsdr_doa_set_subband_beams' to turn off)
     HIP_TRY(hipSetDevice(q->device));
     if (q->submitted) HIP_TRY(hipDeviceSynchronize());   // the buffers may be in use (the last submit's stream may be the caller's, and gone)
     doa_free_beams(q);
@@ -2310,7 +2326,7 @@ extern "C" int crsdr_doa_set_beams(crsdr_doa *q, int mode, float loading, int nf
 extern "C" int crsdr_doa_fetch_beams(crsdr_doa *q, float *weights, float *power, float *beams)
 {
     if (!q) return fail(CRSDR_EINVAL, "doa_fetch_beams: NULL doa");
-    if (!q->beam_mode) return fail(CRSDR_ESTATE, "doa_fetch_beams: no crsdr_doa_set_beams");
+    if (!q->beam_mode || q->band_beams) return fail(CRSDR_ESTATE, "doa_fetch_beams: no crsdr_doa_set_beams");
     if (!q->beams_submitted) return fail(CRSDR_ESTATE, "doa_fetch_beams: nothing submitted since crsdr_doa_set_beams");
     HIP_TRY(hipSetDevice(q->device));
     const size_t nest = (size_t)q->last_nest, nb = (size_t)q->nbeams;
@@ -2325,10 +2341,11 @@ extern "C" int crsdr_doa_fetch_beams(crsdr_doa *q, float *weights, float *power,
 extern "C" int crsdr_doa_beam_buffers(crsdr_doa *q, void **weights, void **power, void **beams, int *nbeams)
 {
     if (!q) return fail(CRSDR_EINVAL, "doa_beam_buffers: NULL doa");
-    if (weights) *weights = q->d_bw;
-    if (power) *power = q->d_bpow;
-    if (beams) *beams = q->d_beams;
-    if (nbeams) *nbeams = q->nbeams;
+    const bool on = !q->band_beams;
+    if (weights) *weights = on ? q->d_bw : nullptr;
+    if (power) *power = on ? q->d_bpow : nullptr;
+    if (beams) *beams = on ? q->d_beams : nullptr;
+    if (nbeams) *nbeams = on ? q->nbeams : 0;
     return CRSDR_OK;
 }
 
@@ -2354,7 +2371,7 @@ extern "C" int crsdr_doa_set_smoothing(crsdr_doa *q, int sx, int sy, uint32_t fl
     if (q->order_crit && q->kmax >= ms)
         return fail(CRSDR_EINVAL, "doa_set_smoothing: the order range ends at kmax = %d, sub-arrays of %d x %d have %d elements", q->kmax, sx, sy, ms);
     if (ms < q->m && q->beam_mode)
-        return fail(CRSDR_ESTATE, "doa_set_smoothing: beams are on (crsdr_doa_set_beams): their weights are %d-vectors from the %d x %d subspace: turn them off first", q->m,
+        return fail(CRSDR_ESTATE, "doa_set_smoothing: beams are on (crsdr_doa_set_beams or _set_subband_beams): their weights are %d-vectors from the %d x %d subspace: turn them off first", q->m,
                     q->m, q->m);
     HIP_TRY(hipSetDevice(q->device));
     if (q->submitted) HIP_TRY(hipDeviceSynchronize());   // the buffers may be in use (the last submit's stream may be the caller's, and gone)
@@ -2516,6 +2533,118 @@ extern "C" int crsdr_subband_covariance(float *rbands, float *power, const int8_
         HIP_TRY(hipMemcpy(rbands, d_r, rb, hipMemcpyDeviceToHost));
         if (power) HIP_TRY(hipMemcpy(power, d_p, pb, hipMemcpyDeviceToHost));
     } else HIP_TRY(hipDeviceSynchronize());
+    return CRSDR_OK;
+}
+
+// ---- a beam per frequency band (subband_beams.hpp) ----
+// every instantiation the object or the per-op call can launch may need more than 64 KiB of dynamic LDS
+template <typename K>
+static int sbb_lds_limit(K kern, const char *who)
+{
+    if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)(sizeof(float2) * sbbeams::sbb_seg_stride(sbbeams::SBB_MAX_ROWS, 1 << subband::SB_MAX_LOG2))) != hipSuccess)
+        return fail(CRSDR_EHIP, "%s: dynamic LDS limit of the band beam kernel", who);
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_set_subband_beams(crsdr_doa *q, int mode, float loading, int nfixed, const float *fixed_angles)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_set_subband_beams: NULL doa");
+    if (mode != CRSDR_BEAM_OFF && mode != CRSDR_BEAM_CONVENTIONAL && mode != CRSDR_BEAM_MVDR) return fail(CRSDR_EINVAL, "doa_set_subband_beams: mode = %d", mode);
+    if (mode == CRSDR_BEAM_MVDR && !(loading >= 1e-6f && loading <= 1.0f)) return fail(CRSDR_EINVAL, "doa_set_subband_beams: loading = %g (1e-6..1)", (double)loading);
+    if (mode != CRSDR_BEAM_OFF && (nfixed < 0 || nfixed > beams::MAX_BEAMS))
+        return fail(CRSDR_EINVAL, "doa_set_subband_beams: nfixed = %d (0..%d)", nfixed, beams::MAX_BEAMS);
+    if (mode != CRSDR_BEAM_OFF && nfixed > 0 && !fixed_angles) return fail(CRSDR_EINVAL, "doa_set_subband_beams: %d fixed directions and no angles", nfixed);
+    if (mode != CRSDR_BEAM_OFF && !q->sb_nfft)
+        return fail(CRSDR_ESTATE, "doa_set_subband_beams: subbands are off (crsdr_doa_set_subbands): the wideband beams are crsdr_doa_set_beams");
+    if (mode != CRSDR_BEAM_OFF && q->ms < q->m)
+        return fail(CRSDR_ESTATE, "doa_set_subband_beams: smoothing over %d x %d sub-arrays is on (crsdr_doa_set_smoothing): the weights are %d-vectors and there is no %d x %d subspace",
+                    q->sx, q->sy, q->m, q->m, q->m);
+    if (q->beam_mode && !q->band_beams) return CRSDR_OK; // (off, with subbands off: the wideband beams are crsdr_doa_set_beams' to turn off)
+    HIP_TRY(hipSetDevice(q->device));
+    if (q->submitted) HIP_TRY(hipDeviceSynchronize());   // the buffers may be in use (the last submit's stream may be the caller's, and gone)
+    doa_free_beams(q);
+    if (mode == CRSDR_BEAM_OFF) return CRSDR_OK;
+    const size_t nmat = doa_capacity(q), nb = (size_t)(nfixed ? nfixed : q->npeaks ? q->npeaks : 1);
+    // a packet's beams: nbands * width bins of J segments each, at most blocksize / 2 samples per slot
+    const size_t per_packet = (size_t)q->nbands * nb * (size_t)(q->B / (2 * q->sb_nfft)) * (size_t)q->sb_width;
+    int rc = CRSDR_OK;
+    SUBBAND_DISPATCH(q->sb_log2, rc = sbb_lds_limit(sbbeams::k_doa_subband_beam_apply<LG>, "doa_set_subband_beams"));
+    auto alloc = [&](void **p, size_t bytes) { if (!rc && hipMalloc(p, bytes) != hipSuccess) rc = fail(CRSDR_ENOMEM, "doa_set_subband_beams: %zu bytes of device memory", bytes); };
+    alloc((void **)&q->d_bw, sizeof(float2) * nmat * nb * (size_t)q->m);
+    alloc((void **)&q->d_bpow, sizeof(float) * nmat * nb);
+    alloc((void **)&q->d_beams, sizeof(float2) * (size_t)q->max_batch * per_packet);
+    if (nfixed) {
+        alloc((void **)&q->d_bangles, sizeof(float) * 2 * nb);
+        if (!rc && hipMemcpy(q->d_bangles, fixed_angles, sizeof(float) * 2 * nb, hipMemcpyHostToDevice) != hipSuccess)
+            rc = fail(CRSDR_EHIP, "doa_set_subband_beams: copy of the angles");
+    }
+    if (rc) { doa_free_beams(q); return rc; }
+    q->beam_mode = mode; q->nbeams = (int)nb; q->nfixed = nfixed; q->loading = mode == CRSDR_BEAM_MVDR ? loading : 0.f;
+    q->band_beams = true; q->sbb_lds = sbbeams::sbb_lds_points(q->m, q->B, q->sb_nfft);
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_fetch_subband_beams(crsdr_doa *q, float *weights, float *power, float *beams)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_fetch_subband_beams: NULL doa");
+    if (!q->band_beams) return fail(CRSDR_ESTATE, "doa_fetch_subband_beams: no crsdr_doa_set_subband_beams");
+    if (!q->beams_submitted) return fail(CRSDR_ESTATE, "doa_fetch_subband_beams: nothing submitted since crsdr_doa_set_subband_beams");
+    HIP_TRY(hipSetDevice(q->device));
+    const size_t nmat = (size_t)q->last_nest, nb = (size_t)q->nbeams;
+    const size_t per_packet = (size_t)q->nbands * nb * (size_t)(q->B / (2 * q->sb_nfft)) * (size_t)q->sb_width;
+    hipStream_t S = q->last_stream;
+    if (weights) HIP_TRY(hipMemcpyAsync(weights, q->d_bw, sizeof(float2) * nmat * nb * (size_t)q->m, hipMemcpyDeviceToHost, S));
+    if (power) HIP_TRY(hipMemcpyAsync(power, q->d_bpow, sizeof(float) * nmat * nb, hipMemcpyDeviceToHost, S));
+    if (beams) HIP_TRY(hipMemcpyAsync(beams, q->d_beams, sizeof(float2) * (size_t)q->last_nblocks * per_packet, hipMemcpyDeviceToHost, S));
+    HIP_TRY(hipStreamSynchronize(S));
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_subband_beam_buffers(crsdr_doa *q, void **weights, void **power, void **beams, int *nbeams)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_subband_beam_buffers: NULL doa");
+    const bool on = q->band_beams;
+    if (weights) *weights = on ? q->d_bw : nullptr;
+    if (power) *power = on ? q->d_bpow : nullptr;
+    if (beams) *beams = on ? q->d_beams : nullptr;
+    if (nbeams) *nbeams = on ? q->nbeams : 0;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_subband_beamform(float *out, const int8_t *matrix, int nrows, int blocksize, int nfft, int first, int nbands, int width, int window,
+                                      const float *weights, int nbeams, int mem_kind)
+{
+    if (!out || !matrix || !weights || nrows < 2 || nrows - 1 > sbbeams::SBB_MAX_ROWS || blocksize < 16 || nbeams < 1 || nbeams > sbbeams::SBB_MAX_BEAMS)
+        return fail(CRSDR_EINVAL, "subband_beamform: need out, matrix, weights, 2 <= nrows <= %d, blocksize >= 16, 1 <= nbeams <= %d", sbbeams::SBB_MAX_ROWS + 1,
+                    sbbeams::SBB_MAX_BEAMS);
+    { const int rc_ = subband_args_ok("subband_beamform", blocksize, nfft, first, nbands, width, window); if (rc_) return rc_; }
+    if (mem_kind != CRSDR_MEM_HOST && mem_kind != CRSDR_MEM_DEVICE) return fail(CRSDR_EINVAL, "subband_beamform: mem_kind = %d", mem_kind);
+    { int rc_ = require_device(); if (rc_) return rc_; }
+    std::lock_guard<std::mutex> lock_(g_op.mu);
+    const int m = nrows - 1, lg = ilog2(nfft), J = blocksize / (2 * nfft), points = sbbeams::sbb_lds_points(m, blocksize, nfft);
+    const size_t mb = (size_t)nrows * (size_t)blocksize, wb = sizeof(float2) * (size_t)nbands * nbeams * m;
+    const size_t ob = sizeof(float2) * (size_t)nbands * nbeams * J * width;
+    const int8_t *d_m = matrix;
+    const float2 *d_w = (const float2 *)weights;
+    float2 *d_o = (float2 *)out;
+    if (mem_kind == CRSDR_MEM_HOST) {
+        OP_RESERVE(0, mb); OP_RESERVE(1, ob); OP_RESERVE(2, wb);
+        HIP_TRY(hipMemcpy(g_op.buf[0], matrix, mb, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(g_op.buf[2], weights, wb, hipMemcpyHostToDevice));
+        d_m = (const int8_t *)g_op.buf[0]; d_o = (float2 *)g_op.buf[1]; d_w = (const float2 *)g_op.buf[2];
+    } else if ((uintptr_t)d_m % 4 || (uintptr_t)d_o % 8 || (uintptr_t)d_w % 8) {
+        return fail(CRSDR_EINVAL, "subband_beamform: device matrix 4-byte, weights and out 8-byte aligned");
+    }
+    int rc = CRSDR_OK;
+    SUBBAND_DISPATCH(lg, rc = sbb_lds_limit(sbbeams::k_subband_beamform<LG>, "subband_beamform"));
+    if (rc) return rc;
+    const dim3 grid((unsigned)sbbeams::sbb_spb(blocksize, nfft));
+    SUBBAND_DISPATCH(lg, hipLaunchKernelGGL(sbbeams::k_subband_beamform<LG>, grid, dim3(sbbeams::SBB_THREADS), sizeof(float2) * (size_t)points, 0, d_m, nrows, blocksize,
+                                            first, nbands, width, window, d_w, nbeams, points, d_o));
+    HIP_TRY(hipGetLastError());
+    if (mem_kind == CRSDR_MEM_HOST) HIP_TRY(hipMemcpy(out, d_o, ob, hipMemcpyDeviceToHost));
+    else HIP_TRY(hipDeviceSynchronize());
     return CRSDR_OK;
 }
 

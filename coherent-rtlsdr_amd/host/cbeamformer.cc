@@ -100,7 +100,15 @@ int batch::set_order(int criterion, int kmin, int kmax, bool limit_directions)
 int batch::set_subbands(int nfft, int first, int count, int width, int window)
 {
     int rc = doa ? crsdr_doa_set_subbands(doa, nfft, first, count, width, window) : CRSDR_ESTATE;
-    if (!rc) nbands = nfft ? count : 0;
+    if (!rc) { nbands = nfft ? count : 0; band_j = nfft ? half / nfft : 0; band_width = nfft ? width : 0; }
+    if (rc && doa) std::fprintf(stderr, "cbeamformer::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::set_subband_beams(int mode, float loading, int nfixed, const float *fixed_angles)
+{
+    int rc = doa ? crsdr_doa_set_subband_beams(doa, mode, loading, nfixed, fixed_angles) : CRSDR_ESTATE;
+    if (!rc) rc = crsdr_doa_subband_beam_buffers(doa, nullptr, nullptr, nullptr, &nbandbeams);
     if (rc && doa) std::fprintf(stderr, "cbeamformer::batch: %s\n", crsdr_last_error());
     return rc;
 }
@@ -131,6 +139,13 @@ int batch::fetch(bool want_beams)
         if (want_beams) beams.assign((size_t)nest * nframes * nbeams * half, {0.f, 0.f});
         rc = crsdr_doa_fetch_beams(doa, reinterpret_cast<float *>(weights.data()), beam_power.data(),
                                    want_beams ? reinterpret_cast<float *>(beams.data()) : nullptr);
+    }
+    if (!rc && nbandbeams) {
+        // nest counts (estimate, band) pairs: nest / nbands estimates of nframes blocks each
+        band_weights.assign((size_t)nest * nbandbeams * m, {0.f, 0.f}); band_beam_power.assign((size_t)nest * nbandbeams, -1.f);
+        if (want_beams) band_beams.assign((size_t)nest * nframes * nbandbeams * band_j * band_width, {0.f, 0.f});
+        rc = crsdr_doa_fetch_subband_beams(doa, reinterpret_cast<float *>(band_weights.data()), band_beam_power.data(),
+                                           want_beams ? reinterpret_cast<float *>(band_beams.data()) : nullptr);
     }
     if (rc && doa) std::fprintf(stderr, "cbeamformer::batch: %s\n", crsdr_last_error());
     return rc;

@@ -34,6 +34,7 @@ class batch {
     bool counted = false;
     bool keep = false;
     int nbands = 0;                                  // set_subbands: bands per estimate (0: off)
+    int nbandbeams = 0, band_j = 0, band_width = 0;  // set_subband_beams: slots; set_subbands: segments per block, bins per band
 public:
     // nrows x blocksize: the packets' geometry (1 + Mx * My rows); keep_spectrum: fetch() also fills pm
     batch(int nrows, int blocksize, int max_batch, int K = 1, int frames = 1, bool keep_spectrum = false, float d = D, int Mx = MX, int My = MY,
@@ -61,10 +62,20 @@ public:
     // from the next submit on, one covariance per (estimate, band) in place of the time-domain one (crsdr_doa_set_subbands): band i is
     // `width` bins of an nfft-point transform from bin first + i * width on (FFT order, wrapping), window CRSDR_WINDOW_*.  Every vector
     // below then holds estimates() = blocks / frames * bands() entries, estimate e's band i at e * bands() + i, and band_power is
-    // filled.  nfft = 0: off.  Before set_peaks, set_smoothing and set_order (refused while one of them or beams are on; beams stay off).
+    // filled.  nfft = 0: off.  Before set_peaks, set_smoothing and set_order (refused while one of them or beams are on; the beams of
+    // the bands are set_subband_beams).
     int set_subbands(int nfft, int first = 0, int count = 1, int width = 1, int window = CRSDR_WINDOW_RECT);
     int bands() const { return nbands; }
     std::vector<float> band_power;                   // with set_subbands: [estimates]: Re trace(R_band) / M, the squelch of a band's direction
+    // with set_subbands on: from the next submit on, a beam per band toward every direction of that band (crsdr_doa_set_subband_beams;
+    // the arguments of set_beams): the band's weights applied to the rows' band spectra, one narrowband IQ stream per (block, band, slot).
+    // CRSDR_BEAM_OFF: off.  While on, set_subbands is refused, and set_peaks while the beams follow the directions.
+    int set_subband_beams(int mode, float loading = 1e-2f, int nfixed = 0, const float *fixed_angles = nullptr);
+    // with set_subband_beams: band_weights [estimates][slots][M] and band_beam_power [estimates][slots] (-1 in an empty slot), estimates
+    // counting the bands as above, and, on request (fetch's want_beams), band_beams [blocks][bands][slots][segments][width]
+    int band_beam_slots() const { return nbandbeams; }
+    cmatrix band_weights, band_beams;
+    std::vector<float> band_beam_power;
     // want_beams: also copy the beams' samples out (blocks x slots x blocksize / 2 complex floats)
     int fetch(bool want_beams = false);
     int estimates() const { return (int)status.size(); }

@@ -55,7 +55,7 @@ int main(int argc, char **argv)
     int nsig = 3, L = 8192, blocks = 12, mode = CRSDR_MODE_DIGITAL, dmax = -1;
     std::string dump, zmqaddr;
     bool run_cdsp = false, servo = false, threads = false, music = false, servo_table = false, bench = false, batch_parity = false, batched = false;
-    int batch = 16, engine_delay_ms = 0, pace_us_arg = -1, peaks = 0, peak_radius = 1, beam_mode = CRSDR_BEAM_OFF;
+    int batch = 16, engine_delay_ms = 0, pace_us_arg = -1, peaks = 0, peak_radius = 1, beam_mode = CRSDR_BEAM_OFF, band_beam_mode = CRSDR_BEAM_OFF;
     float beam_loading = 1e-2f;
     int smooth_x = 0, smooth_y = 0, order_crit = CRSDR_ORDER_OFF;
     bool smooth_fb = false;
@@ -112,6 +112,11 @@ int main(int argc, char **argv)
         else if (a == "--window" && i + 1 < argc) {
             const std::string w = argv[++i];
             sb_window = w == "rect" ? CRSDR_WINDOW_RECT : w == "hann" ? CRSDR_WINDOW_HANN : -1;
+        }
+        // with --subbands: a beam per band toward that band's directions (crsdr_doa_set_subband_beams), its power beside the direction
+        else if (a == "--band-beams" && i + 1 < argc) {
+            const std::string m = argv[++i];
+            band_beam_mode = m == "conventional" ? CRSDR_BEAM_CONVENTIONAL : m == "mvdr" ? CRSDR_BEAM_MVDR : -1;
         }
         else if (a == "--loading" && i + 1 < argc) beam_loading = (float)std::atof(argv[++i]);
         else if (a == "--batch-parity") batch_parity = true;   // the batched engine's packets == step()'s packets, bit for bit (own read counters, a masked row)
@@ -325,6 +330,10 @@ int main(int argc, char **argv)
             if (order_crit && doa->set_order(order_crit)) { std::printf("doa: --order (mdl|aic) refused\nDEMO FAILED\n"); return 1; }
             if (peaks && doa->set_peaks(peaks, peak_radius)) { std::printf("doa: --peaks %d --peak-radius %d refused\nDEMO FAILED\n", peaks, peak_radius); return 1; }
             if (beam_mode && doa->set_beams(beam_mode, beam_loading)) { std::printf("doa: --beams (conventional|mvdr) --loading %g refused\nDEMO FAILED\n", (double)beam_loading); return 1; }
+            if (band_beam_mode && (!sb_nfft || doa->set_subband_beams(band_beam_mode, beam_loading))) {
+                std::printf("doa: --band-beams (conventional|mvdr) --loading %g refused (it needs --subbands)\nDEMO FAILED\n", (double)beam_loading);
+                return 1;
+            }
         }
         bool report = false;
         auto directions = [&](int b) {
@@ -338,8 +347,11 @@ int main(int argc, char **argv)
                 for (int e = 0; e < n / nb_; ++e)
                     for (int i = 0; i < nb_; ++i) {
                         const int x = e * nb_ + i, f0 = (sb_first + i * sb_width) % sb_nfft;
-                        std::printf("doa: batch %d: estimate %d band %d (bins %d..%d of %d): (%d, %d) power %.4g\n", b, e, i, f0, (f0 + sb_width - 1) % sb_nfft, sb_nfft,
+                        std::printf("doa: batch %d: estimate %d band %d (bins %d..%d of %d): (%d, %d) power %.4g", b, e, i, f0, (f0 + sb_width - 1) % sb_nfft, sb_nfft,
                                     doa->peak[2 * x], doa->peak[2 * x + 1], (double)doa->band_power[x]);
+                        // the band's beam toward its strongest direction (slot 0 is the peak, with or without --peaks)
+                        if (band_beam_mode) std::printf(" beam power %.4g", (double)doa->band_beam_power[(size_t)x * doa->band_beam_slots()]);
+                        std::printf("\n");
                     }
             }
             if (order_crit) {

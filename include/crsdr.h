@@ -626,9 +626,10 @@ int crsdr_source_order(int32_t *k, float *criterion_values, const float *sv, int
  * status, pm, rxx = the band matrices), crsdr_doa_fetch_subspace, the device buffers, and crsdr_doa_last_submit's nest all count
  * nest * nbands.  Directions, smoothing and the source count work per band (the count with N = J' * width snapshots) and size their
  * buffers by (max_batch / frames) * nbands, so the order is fixed: this call, on or off (nfft = 0; the other arguments are then ignored),
- * returns CRSDR_ESTATE while any of crsdr_doa_set_peaks, _set_beams, _set_smoothing or _set_order is on, and crsdr_doa_set_beams returns
- * CRSDR_ESTATE while subbands are on (a band's weights applied to the wideband samples mean nothing).  Waits for the device if a submit
- * was made and discards what it left: the fetch functions return CRSDR_ESTATE until the next submit. */
+ * returns CRSDR_ESTATE while any of crsdr_doa_set_peaks, _set_beams, _set_subband_beams, _set_smoothing or _set_order is on, and
+ * crsdr_doa_set_beams returns CRSDR_ESTATE while subbands are on (a band's weights applied to the wideband samples mean nothing: the
+ * beams of the bands are crsdr_doa_set_subband_beams).  Waits for the device if a submit was made and discards what it left: the fetch
+ * functions return CRSDR_ESTATE until the next submit. */
 enum { CRSDR_WINDOW_RECT = 0, CRSDR_WINDOW_HANN = 1 };
 int crsdr_doa_set_subbands(crsdr_doa *doa, int nfft, int first, int nbands, int width, int window);
 
@@ -645,6 +646,43 @@ int crsdr_doa_subband_buffers(crsdr_doa *doa, void **power);
  * (every pointer on the device; matrix and power 4-byte, rbands 8-byte aligned). */
 int crsdr_subband_covariance(float *rbands, float *power, const int8_t *matrix, int nrows, int blocksize, int nfft, int first, int nbands,
                              int width, int window, int mem_kind);
+
+/* A beam per frequency band toward each band's directions: with subbands on every (estimate e, band i) has its own subspace, peak and
+ * directions, at matrix index e * nbands + i.  Per matrix and beam slot b: direction, steering vector, weights u (m complex, fp32) and
+ * power exactly as crsdr_doa_set_beams defines them, from that matrix's vec, sv and peak / peaks / found (or the fixed angles); slots
+ * b >= found: weights 0, power -1.  The weighted sum is taken of the rows' band spectra instead of their samples: with X_c[t][j][f]
+ * the segment spectrum of signal row c of packet t as crsdr_doa_set_subbands defines it (samples (I + jQ) / 127, window w, forward
+ * transform, N = nfft) and c_w = 1 / sqrt(N sum_n w[n]^2), for every packet t of estimate e, segment j < J = blocksize / (2 N) and u < width
+ *     Y[t][i][b][j][u] = c_w sum_c u_{e,i,b}[c-1] X_c[t][j][(first + i width + u) mod N]
+ * fp32 throughout, NO conjugate (the X^H X convention, argued at crsdr_doa_set_beams); empty slots: zeros, written.  c_w is the
+ * normalisation behind R_f: the sum over all N bins of the mean |Y|^2 is the beam's mean sample power, and for one bin
+ * mean_j |Y|^2 = u^H R_f u.  One narrowband IQ stream per (packet, band, slot): the band's channeliser output, `width` bins at J
+ * samples per packet.
+ *   beams [nblocks][nbands][nbeams][J][width][2] float: for width = 1 a (band, slot) stream is J contiguous complex samples per packet.
+ * mode, loading, nfixed, fixed_angles and their ranges as crsdr_doa_set_beams (CRSDR_BEAM_OFF frees the buffers).  Any time: waits for
+ * the device if a submit was made, then allocates weights [(max_batch / frames) * nbands][nbeams][m][2], power and the beams.  A submit
+ * with them on is two launches more, the same for every nblocks, without allocation, lock or host wait.  With crsdr_doa_set_order's
+ * limit_directions the beams see the capped found.
+ * CRSDR_ESTATE while subbands are off, and while true sub-arrays (ms < m) are on (crsdr_doa_set_smoothing with true sub-arrays returns
+ * CRSDR_ESTATE while these beams are on; CRSDR_SMOOTH_FB alone is fine).  While they are on crsdr_doa_set_subbands, on or off, returns
+ * CRSDR_ESTATE, and while they follow the directions (nfixed = 0) crsdr_doa_set_peaks does.  crsdr_doa_set_beams, crsdr_doa_fetch_beams
+ * and crsdr_doa_beam_buffers keep to the wideband beams: these beams are not theirs.  CRSDR_EINVAL as crsdr_doa_set_beams. */
+int crsdr_doa_set_subband_beams(crsdr_doa *doa, int mode, float loading, int nfixed, const float *fixed_angles);
+
+/* Waits for the last submit and copies out (any pointer may be NULL): weights [nest * nbands][nbeams][m][2], power [nest * nbands][nbeams],
+ * beams as above.  CRSDR_ESTATE with these beams off or before the first submit after crsdr_doa_set_subband_beams. */
+int crsdr_doa_fetch_subband_beams(crsdr_doa *doa, float *weights, float *power, float *beams);
+
+/* Device addresses of weights, power and beams (laid out as above for (max_batch / frames) * nbands matrices and max_batch blocks; NULL
+ * while these beams are off) and the slot count, for consumers on the same stream.  They change with every crsdr_doa_set_subband_beams. */
+int crsdr_doa_subband_beam_buffers(crsdr_doa *doa, void **weights, void **power, void **beams, int *nbeams);
+
+/* The per-op form on one packet's matrix [nrows][blocksize]: the same device function as the batched kernel, bit for bit.
+ *   weights [nbands][nbeams][nrows-1][2] float, 1 <= nbeams <= 16;  out [nbands][nbeams][J][width][2] float
+ * nrows, blocksize, nfft, first, nbands, width, window as crsdr_subband_covariance; every argument is checked before a device is
+ * touched.  mem_kind: CRSDR_MEM_HOST (copied) or CRSDR_MEM_DEVICE (all three on the device: matrix 4-byte, weights and out 8-byte aligned). */
+int crsdr_subband_beamform(float *out, const int8_t *matrix, int nrows, int blocksize, int nfft, int first, int nbands, int width, int window,
+                           const float *weights, int nbeams, int mem_kind);
 
 #ifdef __cplusplus
 }

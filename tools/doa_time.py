@@ -16,6 +16,10 @@
   (o) with --order mdl|aic: crsdr_doa_set_order over k = 1 .. 20, then the (b) submit + peaks (on the unsmoothed covariance).
   (u) with --subbands NFFT:FIRST:COUNT[:WIDTH] [--window rect|hann]: crsdr_doa_set_subbands, then the (b) submit + the peaks of all
       64 x COUNT band matrices + the bands' power; reported with its frames/s and its ratio to (b).
+  (v) with --band-beams MODE (conventional | mvdr, --loading X) on top of --subbands [--peaks]: crsdr_doa_set_subband_beams, then the
+      submit + a fetch of the band beams' power only (weights and beams stay on the device), and
+  (w) what a caller without them does to form the bands' beams on the host: the same object without the beams, submit + directions,
+      then the 64 packets and vec of every band matrix copied to page-locked host memory (before any host arithmetic).
 
 --runs runs of each, alternating a, b, c in one session (two worker processes, both alive throughout); medians and ranges.
 --doa-lib LIB starts a second doa worker on another build (e.g. the parent commit's) through CRSDR_LIB and times its (b) and (c) in
@@ -23,7 +27,7 @@ the same alternation, reported as lib:b and lib:c.  --reps N: every (b), (c), (p
 Also: what crsdr_doa_submit_plan + the peak fetch add to a 22-row, T = 64 plan batch (plan.submit + sync against
 plan.submit + doa.submit_plan + fetch).  --json FILE keeps the record; --once MODE runs three submit + fetch and exits (for a kernel trace): b, c, p, q as above, q64 = the
 beams at their largest shape (8 x 8 array, 16 slots: 65 rows x 16384, 64 blocks), s = --smooth / --fb / --order as given, all on one object,
-u = --subbands / --window as given."""
+u = --subbands / --window as given, v = u with --peaks and --band-beams as given."""
 import argparse, importlib, json, os, subprocess, sys, time
 import numpy as np
 
@@ -90,7 +94,7 @@ def worker_perop():
         print(time.perf_counter() - t0, flush=True)
 
 
-def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None, fb=False, order=None, subbands=None, window="rect"):
+def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None, fb=False, order=None, subbands=None, window="rect", band_beams=None):
     """(b), (c), (p), (q), (h), (f), (s), (o) and the plan figures: 'b' / 'c' / 'p' / 'q' / 'h' / 'f' / 's' / 'o' / 'plan' / 'plan+doa' on
     stdin -> seconds of one batch of 64 on stdout."""
     torch, ura, b, dev, pk, off, stride, host = _setup()
@@ -126,6 +130,29 @@ def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None
     if subbands:
         udoa = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
         udoa.set_subbands(*_bands(subbands), WINDOWS[window])
+
+    vdoa = wdoa = None
+    if subbands and band_beams:
+        vdoa, wdoa = (b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T) for _ in range(2))
+        for d in (vdoa, wdoa):
+            d.set_subbands(*_bands(subbands), WINDOWS[window])
+            if npeaks:
+                d.set_peaks(npeaks, radius)
+        vdoa.set_subband_beams(BEAM_MODES[band_beams], loading)
+        wpinned = torch.empty(pk.shape, dtype=torch.int8, pin_memory=True)
+
+    def run_v():
+        for _ in range(reps):
+            vdoa.submit(pk.data_ptr(), stride, off, T)
+            vdoa.fetch_subband_beams(weights=False, beams=False)
+
+    def run_w():
+        for _ in range(reps):
+            wdoa.submit(pk.data_ptr(), stride, off, T)
+            wdoa.fetch_directions() if npeaks else wdoa.fetch_peaks()
+            wpinned.copy_(pk, non_blocking=True)
+            wdoa.fetch_subspace()
+            torch.cuda.synchronize()
 
     def run_u():
         for _ in range(reps):
@@ -188,6 +215,8 @@ def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None
         jobs[key] = (run_extra(d), reps)
     if udoa is not None:
         jobs["u"] = (run_u, reps)
+    if vdoa is not None:
+        jobs["v"], jobs["w"] = (run_v, reps), (run_w, reps)
     for f, _ in jobs.values():
         f()
     print("ready", flush=True)
@@ -198,7 +227,7 @@ def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None
         print((time.perf_counter() - t0) / n, flush=True)
 
 
-def once(mode, npeaks=0, radius=1, beams=None, loading=1e-2, smooth=None, fb=False, order=None, subbands=None, window="rect"):
+def once(mode, npeaks=0, radius=1, beams=None, loading=1e-2, smooth=None, fb=False, order=None, subbands=None, window="rect", band_beams=None):
     mx, my = (8, 8) if mode == "q64" else (None, None)
     torch, ura, b, dev, pk, off, stride, _ = _setup(mx, my)
     mx, my = mx or ura.MX, my or ura.MY
@@ -214,18 +243,24 @@ def once(mode, npeaks=0, radius=1, beams=None, loading=1e-2, smooth=None, fb=Fal
             d.set_smoothing(*(_sub_array(smooth) if smooth else (mx, my)), b.SMOOTH_FB if fb else 0)
         if order:
             d.set_order(ORDER_MODES[order], 1, d.ms - 1)
-    if mode == "u":
+    if mode in ("u", "v"):
         d.set_subbands(*_bands(subbands), WINDOWS[window])
+    if mode == "v":
+        if npeaks:
+            d.set_peaks(npeaks, radius)
+        d.set_subband_beams(BEAM_MODES[band_beams or "mvdr"], loading)
     for _ in range(3):
         d.submit(pk.data_ptr(), stride, off, T)
         out = d.fetch()
-    if mode == "u":
+    if mode in ("u", "v"):
         print("band power of the first estimate", np.round(d.fetch_subbands()[0], 5).tolist())
     print("peaks", out["peak"][:4].tolist(), "launches", d.last_launches())
     if mode == "s" and order:
         print("k", d.fetch_order()["k"].tolist())
     if mode in ("p", "q", "q64") and npeaks:
         print("directions of the first", d.fetch_directions()["peaks"][0].tolist())
+    if mode == "v":
+        print("slots", d.nbandbeams, "band beam power of the first estimate", d.fetch_subband_beams(weights=False, beams=False)["power"][:d.nbands].tolist())
     if mode in ("q", "q64"):
         print("slots", d.nbeams, "beam power of the first", d.fetch_beams(weights=False, beams=False)["power"][0].tolist())
 
@@ -260,14 +295,15 @@ def _stat(xs):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--worker", choices=["perop", "doa"])
-    ap.add_argument("--once", choices=["b", "c", "p", "q", "q64", "s", "u"])
+    ap.add_argument("--once", choices=["b", "c", "p", "q", "q64", "s", "u", "v"])
     ap.add_argument("--subbands", default=None, metavar="NFFT:FIRST:COUNT[:WIDTH]", help="(u): a covariance per frequency band (crsdr_doa_set_subbands)")
     ap.add_argument("--window", choices=sorted(WINDOWS), default="rect", help="(u): the segments' window")
     ap.add_argument("--smooth", default=None, metavar="SXxSY", help="(s): sub-arrays of SX x SY elements (crsdr_doa_set_smoothing)")
     ap.add_argument("--fb", action="store_true", help="(f): forward-backward averaging alone; with --smooth: (s) averages backward as well")
     ap.add_argument("--order", choices=sorted(ORDER_MODES), default=None, help="(o): the source count per estimate (crsdr_doa_set_order)")
     ap.add_argument("--beams", choices=sorted(BEAM_MODES), default=None, help="(q), (h): beams toward the directions, this mode")
-    ap.add_argument("--loading", type=float, default=1e-2, help="(q): the MVDR diagonal loading")
+    ap.add_argument("--band-beams", choices=sorted(BEAM_MODES), default=None, help="(v), (w): with --subbands, a beam per band toward its directions, this mode")
+    ap.add_argument("--loading", type=float, default=1e-2, help="(q), (v): the MVDR diagonal loading")
     ap.add_argument("--perop-lib", default=None, help="library for (a), e.g. a build of the parent commit (default: the current one)")
     ap.add_argument("--doa-lib", default=None, help="a second library whose (b) and (c) are timed in the same alternation (lib:b, lib:c)")
     ap.add_argument("--peaks", type=int, default=0, help="(p): directions per estimate (crsdr_doa_set_peaks count; 0 = no (p))")
@@ -277,9 +313,12 @@ def main():
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     if a.worker:
-        return worker_perop() if a.worker == "perop" else worker_doa(a.peaks, a.radius, a.reps, a.beams, a.loading, a.smooth, a.fb, a.order, a.subbands, a.window)
+        return worker_perop() if a.worker == "perop" else worker_doa(a.peaks, a.radius, a.reps, a.beams, a.loading, a.smooth, a.fb, a.order, a.subbands, a.window,
+                                                                           a.band_beams)
+    if a.band_beams and not a.subbands:
+        ap.error("--band-beams needs --subbands")
     if a.once:
-        return once(a.once, a.peaks, a.radius, a.beams, a.loading, a.smooth, a.fb, a.order, a.subbands, a.window)
+        return once(a.once, a.peaks, a.radius, a.beams, a.loading, a.smooth, a.fb, a.order, a.subbands, a.window, a.band_beams)
     pargs = ["--peaks", str(a.peaks), "--radius", str(a.radius), "--reps", str(a.reps), "--loading", str(a.loading)]
     if a.beams:
         pargs += ["--beams", a.beams]
@@ -291,7 +330,9 @@ def main():
         pargs += ["--order", a.order]
     if a.subbands:
         pargs += ["--subbands", a.subbands, "--window", a.window]
-    legs = (["f"] if a.fb else []) + (["s"] if a.smooth else []) + (["o"] if a.order else []) + (["u"] if a.subbands else [])
+    if a.band_beams:
+        pargs += ["--band-beams", a.band_beams]
+    legs = (["f"] if a.fb else []) + (["s"] if a.smooth else []) + (["o"] if a.order else []) + (["u"] if a.subbands else []) + (["v", "w"] if a.band_beams else [])
     wa, wb = Worker("perop", a.perop_lib), Worker("doa", extra=pargs)
     wl = Worker("doa", a.doa_lib, extra=["--reps", str(a.reps)]) if a.doa_lib else None
     keys = ["a", "b", "c", "plan", "plan+doa"] + (["lib:b", "lib:c"] if wl else []) + (["p"] if a.peaks else []) + (["q", "h"] if a.beams else []) + legs
@@ -323,6 +364,7 @@ def main():
            "beams": {"mode": a.beams, "loading": a.loading} if a.beams else None,
            "smoothing": {"sub_array": a.smooth, "fb": a.fb} if (a.smooth or a.fb) else None, "order": a.order,
            "subbands": dict(zip(("nfft", "first", "nbands", "width"), _bands(a.subbands)), window=a.window) if a.subbands else None,
+           "band_beams": {"mode": a.band_beams, "loading": a.loading} if a.band_beams else None,
            "ms_per_batch": {k: _stat([1e3 * x for x in v]) for k, v in sec.items()},
            "frames_per_s": {k: _stat([T / x for x in sec[k]]) for k in ("a", "b", "c") + (("u",) if a.subbands else ())}}
     if a.subbands:
@@ -334,7 +376,8 @@ def main():
              "lib:c": "--doa-lib: submit + peaks + spectra", "p": f"set_peaks({a.peaks}, {a.radius}): submit + directions",
              "q": f"(p) + {a.beams} beams: submit + power", "h": "(p) + packets and vec to the host",
              "f": "FB alone: submit + peaks", "s": f"{a.smooth}{' + FB' if a.fb else ''}: submit + peaks", "o": f"order {a.order}: submit + peaks",
-             "u": f"subbands {a.subbands} {a.window}: submit + peaks + power"}
+             "u": f"subbands {a.subbands} {a.window}: submit + peaks + power",
+             "v": f"subbands + {a.band_beams} band beams: submit + power", "w": "subbands: packets and vec to the host"}
     for k, s in rec["ms_per_batch"].items():
         fps = f"  {T / (1e-3 * s['median']):10.0f} frames/s" if k in rec["frames_per_s"] else ""
         print(f"({k}) {names[k]:34s} {s['median']:8.3f} ms per 64 blocks  [{s['min']:.3f} .. {s['max']:.3f}]{fps}")
@@ -345,6 +388,9 @@ def main():
     for k in legs:
         rec[f"{k}_adds_ms_per_batch"] = rec["ms_per_batch"][k]["median"] - rec["ms_per_batch"]["b"]["median"]
         print(f"({k}) adds {1e3 * rec[f'{k}_adds_ms_per_batch']:.0f} us to (b)")
+    if a.band_beams:
+        rec["v_over_w_ms"] = rec["ms_per_batch"]["v"]["median"] / rec["ms_per_batch"]["w"]["median"]
+        print(f"(v) takes {rec['v_over_w_ms']:.2f} x the time of (w)")
     if wl:
         rec["b_minus_lib_b_ms"] = rec["ms_per_batch"]["b"]["median"] - rec["ms_per_batch"]["lib:b"]["median"]
     if a.json:
