@@ -47,6 +47,9 @@ static int fail(int code, const char *fmt, ...)
                         "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
+// HIP_TRY as a value: the CRSDR_* code of `expr`, for code that goes on after a failure
+#define HIP_RC(expr) [&]() -> int { HIP_TRY(expr); return CRSDR_OK; }()
+
 extern "C" int crsdr_abi_version(void) { return CRSDR_ABI_VERSION; }
 extern "C" const char *crsdr_last_error(void) { return g_err; }
 
@@ -151,6 +154,25 @@ static int ilog2_exact(int n)
     int l = 0;
     while ((1 << l) < n) ++l;
     return l;
+}
+
+// argument checks shared by the per-op calls and the engine (doa_engine.hpp)
+static bool smooth_shape_ok(int mx, int my, int sx, int sy, uint32_t flags)
+{
+    return mx >= 1 && my >= 1 && (long long)mx * my >= 2 && (long long)mx * my <= music::MAX_M && sx >= 1 && sx <= mx && sy >= 1 && sy <= my &&
+           sx * sy >= 2 && !(flags & ~(uint32_t)CRSDR_SMOOTH_FB);
+}
+
+static int subband_args_ok(const char *who, int blocksize, int nfft, int first, int nbands, int width, int window)
+{
+    if (nfft < (1 << subband::SB_MIN_LOG2) || nfft > (1 << subband::SB_MAX_LOG2) || (nfft & (nfft - 1)))
+        return fail(CRSDR_EINVAL, "%s: nfft = %d (a power of two, %d..%d)", who, nfft, 1 << subband::SB_MIN_LOG2, 1 << subband::SB_MAX_LOG2);
+    if (blocksize % (2 * nfft)) return fail(CRSDR_EINVAL, "%s: blocksize = %d is no multiple of 2 nfft = %d", who, blocksize, 2 * nfft);
+    if (first < 0 || first >= nfft) return fail(CRSDR_EINVAL, "%s: first = %d (0..nfft - 1 = %d)", who, first, nfft - 1);
+    if (nbands < 1 || width < 1 || (long long)nbands * width > nfft)
+        return fail(CRSDR_EINVAL, "%s: %d bands of %d bins (nbands >= 1, width >= 1, nbands * width <= nfft = %d)", who, nbands, width, nfft);
+    if (window != CRSDR_WINDOW_RECT && window != CRSDR_WINDOW_HANN) return fail(CRSDR_EINVAL, "%s: window = %d", who, window);
+    return CRSDR_OK;
 }
 
 // forward twiddle table W_n^k = (cos, -sin)(2 pi k / n), generated in double, rounded once
@@ -469,7 +491,37 @@ inline dim3 grid1d(size_t n, int bs = 256) { return dim3((unsigned)((n + bs - 1)
     { int rc_ = require_device(); if (rc_) return rc_; }      \
     std::lock_guard<std::mutex> lock_(g_op.mu)
 
+// the same for the downstream calls, which take host or device pointers: behind their own argument checks
+#define OP_PROLOGUE_MEM(who, mem_kind)                                                                                              \
+    if (mem_kind != CRSDR_MEM_HOST && mem_kind != CRSDR_MEM_DEVICE) return fail(CRSDR_EINVAL, who ": mem_kind = %d", mem_kind);   \
+    { int rc_ = require_device(); if (rc_) return rc_; }                                                                            \
+    std::lock_guard<std::mutex> lock_(g_op.mu)
+
 #define OP_RESERVE(slot, bytes) { int rc_ = op_reserve(slot, bytes); if (rc_) return rc_; }
+
+// The mem_kind pattern of the downstream per-op calls (under g_op.mu).  CRSDR_MEM_HOST: inputs are copied into staging slots, the
+// kernels write into slots, back() copies out.  CRSDR_MEM_DEVICE: the caller's pointers as they are (misaligned: one of them missed
+// the alignment its call asks for), finish() waits for the device.  rc: the first failure; the calls behind it do nothing.
+struct OpStage {
+    const bool host;
+    bool misaligned = false;
+    int rc = CRSDR_OK;
+    explicit OpStage(int mem_kind) : host(mem_kind == CRSDR_MEM_HOST) {}
+    const void *in(int slot, const void *p, size_t bytes, size_t align = 1)
+    {
+        void *d = out(slot, const_cast<void *>(p), bytes, align);
+        if (host && !rc) rc = HIP_RC(hipMemcpy(d, p, bytes, hipMemcpyHostToDevice));
+        return d;
+    }
+    void *out(int slot, void *p, size_t bytes, size_t align = 1)
+    {
+        if (!host) { misaligned |= (uintptr_t)p % align != 0; return p; }
+        if (!rc) rc = op_reserve(slot, bytes);
+        return g_op.buf[slot];
+    }
+    void back(void *p, const void *d, size_t bytes) { if (host && p && !rc) rc = HIP_RC(hipMemcpy(p, d, bytes, hipMemcpyDeviceToHost)); }
+    int finish() { return rc || host ? rc : HIP_RC(hipDeviceSynchronize()); }
+};
 
 extern "C" int crsdr_convtosigned(const uint8_t *in, uint8_t *out, int n)
 {
@@ -606,18 +658,12 @@ static int cov_pick_split(int ntri, int npairs, int blocksize, int cus)
 extern "C" int crsdr_covariance(float *rxx, const int8_t *matrix, int nrows, int blocksize, int mem_kind)
 {
     if (!rxx || !matrix || nrows < 2 || blocksize < 32 || (blocksize % 32)) return fail(CRSDR_EINVAL, "covariance: need rxx, matrix, nrows >= 2, blocksize % 32 == 0");
-    if (mem_kind != CRSDR_MEM_HOST && mem_kind != CRSDR_MEM_DEVICE) return fail(CRSDR_EINVAL, "covariance: mem_kind = %d", mem_kind);
-    { int rc_ = require_device(); if (rc_) return rc_; }
-    std::lock_guard<std::mutex> lock_(g_op.mu);
+    OP_PROLOGUE_MEM("covariance", mem_kind);
     const size_t mb = (size_t)nrows * (size_t)blocksize, nsig = (size_t)nrows - 1, rb = sizeof(float2) * nsig * nsig;
-    const int8_t *d_m = matrix;
-    float2 *d_r = (float2 *)rxx;
-    if (mem_kind == CRSDR_MEM_HOST) {
-        OP_RESERVE(0, mb); OP_RESERVE(1, rb);
-        HIP_TRY(hipMemcpy(g_op.buf[0], matrix, mb, hipMemcpyHostToDevice));
-        d_m = (const int8_t *)g_op.buf[0];
-        d_r = (float2 *)g_op.buf[1];
-    }
+    OpStage st(mem_kind);
+    const int8_t *d_m = (const int8_t *)st.in(0, matrix, mb);
+    float2 *d_r = (float2 *)st.out(1, rxx, rb);
+    if (st.rc) return st.rc;
     // (the one-tile-per-wave kernel keeps a whole row's sums in int32: exact up to 65536 bytes per row; longer rows take the tiled path,
     // whose K split keeps every partial inside that bound, whatever the channel count)
     if (blocksize > 65536 && (blocksize % (2 * cov::KC) || (uintptr_t)d_m % 4))
@@ -644,17 +690,14 @@ extern "C" int crsdr_covariance(float *rxx, const int8_t *matrix, int nrows, int
         hipLaunchKernelGGL(cov::k_covariance, dim3(tiles, tiles), dim3(256), 0, 0, d_m, nrows, blocksize, (const int2 *)g_op.buf[2], d_r);
         HIP_TRY(hipGetLastError());
     }
-    if (mem_kind == CRSDR_MEM_HOST) HIP_TRY(hipMemcpy(rxx, d_r, rb, hipMemcpyDeviceToHost));
-    else HIP_TRY(hipDeviceSynchronize());
-    return CRSDR_OK;
+    st.back(rxx, d_r, rb);
+    return st.finish();
 }
 
 extern "C" int crsdr_noisesubspace(float *vec, float *sv, const float *rxx, int m, int mem_kind)
 {
     if (!vec || !rxx || m < 2 || m > music::MAX_M) return fail(CRSDR_EINVAL, "noisesubspace: need vec, rxx, 2 <= m <= %d", music::MAX_M);
-    if (mem_kind != CRSDR_MEM_HOST && mem_kind != CRSDR_MEM_DEVICE) return fail(CRSDR_EINVAL, "noisesubspace: mem_kind = %d", mem_kind);
-    { int rc_ = require_device(); if (rc_) return rc_; }
-    std::lock_guard<std::mutex> lock_(g_op.mu);
+    OP_PROLOGUE_MEM("noisesubspace", mem_kind);
     const size_t mm = sizeof(float2) * (size_t)m * m;
     OP_RESERVE(2, music::MAX_M * sizeof(float) + 2 * sizeof(int));
     float *d_sv = (float *)g_op.buf[2];
@@ -688,33 +731,20 @@ extern "C" int crsdr_pmusic2d(float *pm, const float *vec, int m, int k, float d
     if (!pm || !vec || m < 2 || m > music::MAX_M || mx < 1 || my < 1 || mx * my != m || k < 1 || k >= m || ncx < 1 || ncy < 1 ||
         (long long)ncx * ncy > (1 << 24))
         return fail(CRSDR_EINVAL, "pmusic2d: need pm, vec, m = mx*my in [2, %d], 1 <= k < m, grid <= 2^24 points", music::MAX_M);
-    if (mem_kind != CRSDR_MEM_HOST && mem_kind != CRSDR_MEM_DEVICE) return fail(CRSDR_EINVAL, "pmusic2d: mem_kind = %d", mem_kind);
-    { int rc_ = require_device(); if (rc_) return rc_; }
-    std::lock_guard<std::mutex> lock_(g_op.mu);
+    OP_PROLOGUE_MEM("pmusic2d", mem_kind);
     const size_t mm = sizeof(float2) * (size_t)m * m, pb = sizeof(float) * (size_t)ncx * ncy;
-    const float2 *d_v = (const float2 *)vec;
-    float *d_p = pm;
-    if (mem_kind == CRSDR_MEM_HOST) {
-        OP_RESERVE(0, mm); OP_RESERVE(1, pb);
-        HIP_TRY(hipMemcpy(g_op.buf[0], vec, mm, hipMemcpyHostToDevice));
-        d_v = (const float2 *)g_op.buf[0];
-        d_p = (float *)g_op.buf[1];
-    }
+    OpStage st(mem_kind);
+    const float2 *d_v = (const float2 *)st.in(0, vec, mm);
+    float *d_p = (float *)st.out(1, pm, pb);
+    if (st.rc) return st.rc;
     const int nn = m - k;
     const size_t lds = sizeof(float2) * ((size_t)m * nn + (size_t)m * music::PT);
     HIP_TRY(hipFuncSetAttribute((const void *)music::k_pmusic2d, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const unsigned blocks = (unsigned)(((size_t)ncx * ncy + music::PT - 1) / music::PT);
     hipLaunchKernelGGL(music::k_pmusic2d, dim3(blocks), dim3(music::PT), lds, 0, d_v, m, m, k, nn, d, mx, my, ncx, ncy, d_p);
     HIP_TRY(hipGetLastError());
-    if (mem_kind == CRSDR_MEM_HOST) HIP_TRY(hipMemcpy(pm, d_p, pb, hipMemcpyDeviceToHost));
-    else HIP_TRY(hipDeviceSynchronize());
-    return CRSDR_OK;
-}
-
-static bool smooth_shape_ok(int mx, int my, int sx, int sy, uint32_t flags)
-{
-    return mx >= 1 && my >= 1 && (long long)mx * my >= 2 && (long long)mx * my <= music::MAX_M && sx >= 1 && sx <= mx && sy >= 1 && sy <= my &&
-           sx * sy >= 2 && !(flags & ~(uint32_t)CRSDR_SMOOTH_FB);
+    st.back(pm, d_p, pb);
+    return st.finish();
 }
 
 extern "C" int crsdr_smooth_covariance(float *rs, const float *rxx, int mx, int my, int sx, int sy, uint32_t flags, int mem_kind)
@@ -722,23 +752,16 @@ extern "C" int crsdr_smooth_covariance(float *rs, const float *rxx, int mx, int 
     if (!rs || !rxx || !smooth_shape_ok(mx, my, sx, sy, flags))
         return fail(CRSDR_EINVAL, "smooth_covariance: need rs, rxx, m = mx*my in [2, %d], 1 <= sx <= mx, 1 <= sy <= my, sx*sy >= 2, flags = 0 or CRSDR_SMOOTH_FB",
                     music::MAX_M);
-    if (mem_kind != CRSDR_MEM_HOST && mem_kind != CRSDR_MEM_DEVICE) return fail(CRSDR_EINVAL, "smooth_covariance: mem_kind = %d", mem_kind);
-    { int rc_ = require_device(); if (rc_) return rc_; }
-    std::lock_guard<std::mutex> lock_(g_op.mu);
+    OP_PROLOGUE_MEM("smooth_covariance", mem_kind);
     const size_t m = (size_t)mx * my, ms = (size_t)sx * sy, mm = sizeof(float2) * m * m, sb = sizeof(float2) * ms * ms;
-    const float2 *d_r = (const float2 *)rxx;
-    float2 *d_s = (float2 *)rs;
-    if (mem_kind == CRSDR_MEM_HOST) {
-        OP_RESERVE(0, mm); OP_RESERVE(1, sb);
-        HIP_TRY(hipMemcpy(g_op.buf[0], rxx, mm, hipMemcpyHostToDevice));
-        d_r = (const float2 *)g_op.buf[0];
-        d_s = (float2 *)g_op.buf[1];
-    }
+    OpStage st(mem_kind);
+    const float2 *d_r = (const float2 *)st.in(0, rxx, mm);
+    float2 *d_s = (float2 *)st.out(1, rs, sb);
+    if (st.rc) return st.rc;
     hipLaunchKernelGGL(smooth::k_smooth_covariance, dim3(1), dim3(smooth::SM_THREADS), 0, 0, d_r, mx, my, sx, sy, flags, d_s);
     HIP_TRY(hipGetLastError());
-    if (mem_kind == CRSDR_MEM_HOST) HIP_TRY(hipMemcpy(rs, d_s, sb, hipMemcpyDeviceToHost));
-    else HIP_TRY(hipDeviceSynchronize());
-    return CRSDR_OK;
+    st.back(rs, d_s, sb);
+    return st.finish();
 }
 
 extern "C" int crsdr_source_order(int32_t *k, float *criterion_values, const float *sv, int m, int64_t nsnap, int criterion, int kmin, int kmax, int mem_kind)
@@ -746,9 +769,7 @@ extern "C" int crsdr_source_order(int32_t *k, float *criterion_values, const flo
     if (!k || !sv || m < 2 || m > music::MAX_M || nsnap < 1 || (criterion != CRSDR_ORDER_MDL && criterion != CRSDR_ORDER_AIC) || kmin < 1 || kmin > kmax ||
         kmax >= m)
         return fail(CRSDR_EINVAL, "source_order: need k, sv, 2 <= m <= %d, nsnap >= 1, criterion MDL or AIC, 1 <= kmin <= kmax < m", music::MAX_M);
-    if (mem_kind != CRSDR_MEM_HOST && mem_kind != CRSDR_MEM_DEVICE) return fail(CRSDR_EINVAL, "source_order: mem_kind = %d", mem_kind);
-    { int rc_ = require_device(); if (rc_) return rc_; }
-    std::lock_guard<std::mutex> lock_(g_op.mu);
+    OP_PROLOGUE_MEM("source_order", mem_kind);
     const size_t nc = (size_t)(kmax - kmin + 1);
     // one staging buffer: sv [MAX_M] float, crit [MAX_M] float, k
     OP_RESERVE(2, (2 * music::MAX_M) * sizeof(float) + sizeof(int32_t));
@@ -1849,678 +1870,27 @@ extern "C" int crsdr_plan_kernel_times(crsdr_plan *p, int which, float *ms, int 
 }
 
 // ================================================================================================
-// (iv) batched direction-of-arrival engine (crsdr_doa): covariance -> noise subspace -> 2-D MUSIC scan + peak, one estimate per
-//      `frames` packets, for a whole batch of packets where a plan left them.  Every buffer is allocated at create; a submit is five
-//      launches on one stream whatever the batch size (covariance partials, their reducer, subspace, scan, peak), no lock, no
-//      allocation, no synchronisation.  crsdr_doa_set_peaks allocates what the local-peak pass needs and adds its two launches,
-//      crsdr_doa_set_beams what the beams need and theirs (beams.hpp), crsdr_doa_set_smoothing and crsdr_doa_set_order theirs and one
-//      launch each (smooth.hpp): behind the reducer, and between the subspace and the scan.  crsdr_doa_set_subbands replaces the two
-//      covariance launches by subband.hpp's (one covariance per estimate and frequency band) and reallocates every per-matrix buffer
-//      for (max_batch / frames) * nbands matrices: the launches behind it then run over that many.  crsdr_doa_set_subband_beams on top of
-//      it: the beam weights per (estimate, band) and subband_beams.hpp's apply kernel on the rows' band spectra.
+// (iv) batched direction-of-arrival engine (crsdr_doa)
 // ================================================================================================
-struct crsdr_doa {
-    int nrows = 0, B = 0, m = 0, device = 0, max_batch = 1, frames = 1, k = 1, mx = 0, my = 0, ncx = 0, ncy = 0;
-    float d = 0.f;
-    uint32_t flags = 0;
-    int nt = 1, ntri = 1, spb = 1, nwg = 0;        // operand blocks, tiles, K slices per packet, scan workgroups per estimate
-    hipStream_t own_stream = nullptr, last_stream = nullptr;
-    int *d_partial = nullptr, *d_info = nullptr;
-    int2 *d_psum = nullptr;
-    float2 *d_rxx = nullptr, *d_vec = nullptr;
-    float *d_sv = nullptr, *d_peakv = nullptr, *d_pm = nullptr;
-    int32_t *d_peak = nullptr;
-    unsigned long long *d_wgbest = nullptr;
-    int last_nest = 0, last_launches = 0;
-    bool submitted = false;
-    // crsdr_doa_set_peaks: `npeaks` directions per estimate (0 = off), window radius, the spectrum workspace (without
-    // CRSDR_DOA_KEEP_SPECTRUM), the tiles' candidates [nest][tiles][npeaks] and the results; peaks_submitted: a submit since set_peaks
-    int npeaks = 0, radius = 0, lp_tiles = 0;
-    float *d_pmws = nullptr, *d_dirv = nullptr;
-    unsigned long long *d_cand = nullptr;
-    int32_t *d_found = nullptr, *d_dirs = nullptr;
-    bool peaks_submitted = false;
-    // crsdr_doa_set_beams: mode (0 = off), `nbeams` slots per estimate (nfixed of them at the caller's angles, else the estimate's own
-    // directions), weights [nest][nbeams][m], power [nest][nbeams], beams [max_batch][nbeams][B / 2]; beams_submitted: a submit since
-    int beam_mode = 0, nbeams = 0, nfixed = 0, last_nblocks = 0;
-    float loading = 0.f;
-    float2 *d_bw = nullptr, *d_beams = nullptr;
-    float *d_bpow = nullptr, *d_bangles = nullptr;
-    bool beams_submitted = false;
-    // crsdr_doa_set_subband_beams: the same fields and buffers (the two kinds of beams exclude each other: one needs subbands off, the
-    // other on) with band_beams set: weights [nest * nbands][nbeams][m], power [nest * nbands][nbeams], beams
-    // [max_batch][nbands][nbeams][J][width]; sbb_lds: float2 of dynamic LDS of the apply kernel
-    bool band_beams = false;
-    int sbb_lds = 0;
-    // crsdr_doa_set_smoothing: sub-arrays of sx x sy elements (ms of them; ms = m while off: ms is the subspace's size either way), the
-    // smoothed covariances [nest][ms][ms]; last_ms: of the last submit
-    bool smooth_on = false, smooth_submitted = false;
-    int sx = 0, sy = 0, ms = 0, last_ms = 0;
-    uint32_t smooth_flags = 0;
-    float2 *d_rs = nullptr;
-    // crsdr_doa_set_order: criterion (0 = off), the candidates kmin .. kmax, whether the directions are capped by the count;
-    // k [nest], criterion values [nest][kmax - kmin + 1]
-    int order_crit = 0, kmin = 0, kmax = 0, limit_dirs = 0;
-    int32_t *d_korder = nullptr;
-    float *d_crit = nullptr;
-    bool order_submitted = false;
-    // crsdr_doa_set_subbands: nfft (0 = off), the bands (first, nbands, width; nbands = 1 while off: every buffer behind the covariance
-    // holds (max_batch / frames) * nbands matrices either way), the window, K slices per packet, unit groups, the slices' partials
-    // [nest][frames * sb_spb][subband_partial] and the bands' power [nest][nbands]
-    int sb_nfft = 0, sb_log2 = 0, sb_first = 0, nbands = 1, sb_width = 0, sb_window = 0, sb_spb = 1, sb_groups = 1;
-    float2 *d_sbpartial = nullptr;
-    float *d_sbpower = nullptr;
-};
-constexpr int kMaxDoaMatrices = 4096;      // (max_batch / frames) * nbands
+#include "doa_engine.hpp"
 
-// The dynamic LDS limits of the subspace and the scan are function attributes, shared by every live object: each create (and each
-// crsdr_doa_set_order) sets them to the most any object can ask for (m = 64, one signal vector), so that a small object created after
-// a large one cannot lower the limit under it.
-constexpr int kDoaSubLdsMax = (int)(2 * sizeof(double2) * music::MAX_M * music::MAX_M);
-constexpr int kDoaScanLdsMax = (int)(sizeof(float2) * (music::MAX_M * (music::MAX_M - 1) + music::MAX_M * music::PT));
-
-static void doa_free_smooth(crsdr_doa *q)
-{
-    if (q->d_rs) (void)hipFree(q->d_rs);
-    q->d_rs = nullptr;
-    q->smooth_on = q->smooth_submitted = false; q->sx = q->mx; q->sy = q->my; q->ms = q->m; q->smooth_flags = 0;
-}
-
-static void doa_free_order(crsdr_doa *q)
-{
-    if (q->d_korder) (void)hipFree(q->d_korder);
-    if (q->d_crit) (void)hipFree(q->d_crit);
-    q->d_korder = nullptr; q->d_crit = nullptr;
-    q->order_crit = q->kmin = q->kmax = q->limit_dirs = 0; q->order_submitted = false;
-}
-
-static void doa_free_peaks(crsdr_doa *q)
-{
-    void *bufs[] = {q->d_pmws, q->d_dirv, q->d_cand, q->d_found, q->d_dirs};
-    for (void *b : bufs) if (b) (void)hipFree(b);
-    q->d_pmws = q->d_dirv = nullptr; q->d_cand = nullptr; q->d_found = q->d_dirs = nullptr;
-    q->npeaks = q->radius = 0; q->peaks_submitted = false;
-}
-
-static void doa_free_beams(crsdr_doa *q)
-{
-    void *bufs[] = {q->d_bw, q->d_beams, q->d_bpow, q->d_bangles};
-    for (void *b : bufs) if (b) (void)hipFree(b);
-    q->d_bw = q->d_beams = nullptr; q->d_bpow = q->d_bangles = nullptr;
-    q->beam_mode = q->nbeams = q->nfixed = 0; q->loading = 0.f; q->beams_submitted = false; q->band_beams = false; q->sbb_lds = 0;
-}
-
-// the buffers with one entry per matrix (estimate, or estimate and band), and the subband workspace
-static void doa_free_matrices(crsdr_doa *q)
-{
-    void *bufs[] = {q->d_info, q->d_rxx, q->d_vec, q->d_sv, q->d_peakv, q->d_pm, q->d_peak, q->d_wgbest, q->d_sbpartial, q->d_sbpower};
-    for (void *b : bufs) if (b) (void)hipFree(b);
-    q->d_info = nullptr; q->d_rxx = q->d_vec = q->d_sbpartial = nullptr; q->d_sv = q->d_peakv = q->d_pm = q->d_sbpower = nullptr;
-    q->d_peak = nullptr; q->d_wgbest = nullptr;
-}
-
-static void doa_free(crsdr_doa *q)
-{
-    if (!q) return;
-    (void)hipSetDevice(q->device);
-    if (q->submitted) (void)hipDeviceSynchronize();      // (the last submit's stream may be the caller's, and gone)
-    doa_free_peaks(q);
-    doa_free_beams(q);
-    doa_free_smooth(q);
-    doa_free_order(q);
-    doa_free_matrices(q);
-    void *bufs[] = {q->d_partial, q->d_psum};
-    for (void *b : bufs) if (b) (void)hipFree(b);
-    if (q->own_stream) (void)hipStreamDestroy(q->own_stream);
-    delete q;
-}
-
-// the most matrices a submit leaves: what every setter sizes its buffers by
-static size_t doa_capacity(const crsdr_doa *q) { return (size_t)(q->max_batch / q->frames) * (size_t)q->nbands; }
-
-static int doa_alloc_matrices(crsdr_doa *q)
-{
-    const size_t nest = doa_capacity(q), m = (size_t)q->m, grid = (size_t)q->ncx * q->ncy;
-    if (q->sb_nfft) {
-        const size_t slices = (size_t)q->max_batch * q->sb_spb;
-        HIP_TRY(hipMalloc((void **)&q->d_sbpartial, sizeof(float2) * slices * subband::subband_partial(q->m, q->sb_nfft)));
-        HIP_TRY(hipMalloc((void **)&q->d_sbpower, sizeof(float) * nest));
-    }
-    HIP_TRY(hipMalloc((void **)&q->d_rxx, sizeof(float2) * nest * m * m));
-    HIP_TRY(hipMalloc((void **)&q->d_vec, sizeof(float2) * nest * m * m));
-    HIP_TRY(hipMalloc((void **)&q->d_sv, sizeof(float) * nest * m));
-    HIP_TRY(hipMalloc((void **)&q->d_info, sizeof(int) * nest * 2));
-    HIP_TRY(hipMalloc((void **)&q->d_wgbest, sizeof(unsigned long long) * nest * q->nwg));
-    HIP_TRY(hipMalloc((void **)&q->d_peak, sizeof(int32_t) * nest * 2));
-    HIP_TRY(hipMalloc((void **)&q->d_peakv, sizeof(float) * nest));
-    if (q->flags & CRSDR_DOA_KEEP_SPECTRUM) HIP_TRY(hipMalloc((void **)&q->d_pm, sizeof(float) * nest * grid));
-    return CRSDR_OK;
-}
-
-static int doa_alloc(crsdr_doa *q)
-{
-    HIP_TRY(hipSetDevice(q->device));
-    HIP_TRY(hipStreamCreateWithFlags(&q->own_stream, hipStreamNonBlocking));
-    const size_t T = (size_t)q->max_batch;
-    HIP_TRY(hipMalloc((void **)&q->d_partial, sizeof(int) * T * q->spb * q->ntri * 2 * doa::TILE_ELEMS));
-    HIP_TRY(hipMalloc((void **)&q->d_psum, sizeof(int2) * T * q->spb * doa::MAX_ROWS));
-    { int rc = doa_alloc_matrices(q); if (rc) return rc; }
-    // the kernels' dynamic LDS limits: once, here (the subspace takes 128 KiB at m = 64)
-    HIP_TRY(hipFuncSetAttribute((const void *)doa::k_doa_subspace, hipFuncAttributeMaxDynamicSharedMemorySize, kDoaSubLdsMax));
-    HIP_TRY(hipFuncSetAttribute((const void *)doa::k_doa_scan<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kDoaScanLdsMax));
-    return CRSDR_OK;
-}
-
-extern "C" int crsdr_doa_create(crsdr_doa **doa, const crsdr_doa_desc *desc)
-{
-    if (!doa || !desc) return fail(CRSDR_EINVAL, "doa_create: NULL argument");
-    *doa = nullptr;
-    const int m = desc->nrows - 1, mb = desc->max_batch ? desc->max_batch : 1, F = desc->frames ? desc->frames : 1;
-    if (m < 2 || m > music::MAX_M || desc->mx < 1 || desc->my < 1 || (long long)desc->mx * desc->my != m)
-        return fail(CRSDR_EINVAL, "doa_create: nrows - 1 = %d signal rows must be mx * my (%d x %d) in [2, %d]", m, desc->mx, desc->my, music::MAX_M);
-    if (desc->blocksize < 32 || desc->blocksize % 32 || desc->blocksize > (1 << kMaxLog2Plan))
-        return fail(CRSDR_EINVAL, "doa_create: blocksize = %d (a multiple of 32 up to %d)", desc->blocksize, 1 << kMaxLog2Plan);
-    if (mb < 1 || mb > kMaxBatch) return fail(CRSDR_EINVAL, "doa_create: max_batch = %d (1..%d)", mb, kMaxBatch);
-    if (F < 1 || F > mb) return fail(CRSDR_EINVAL, "doa_create: frames = %d (1..max_batch = %d)", desc->frames, mb);
-    if (desc->k < 1 || desc->k >= m) return fail(CRSDR_EINVAL, "doa_create: k = %d sources (1 <= k < %d)", desc->k, m);
-    if (desc->ncx < 1 || desc->ncy < 1 || (long long)desc->ncx * desc->ncy > (1 << 24))
-        return fail(CRSDR_EINVAL, "doa_create: scan grid %d x %d (at least 1 x 1, at most 2^24 points)", desc->ncx, desc->ncy);
-    if (desc->flags & ~(uint32_t)(CRSDR_DOA_KEEP_SPECTRUM | CRSDR_DOA_KEEP_RXX)) return fail(CRSDR_EINVAL, "doa_create: flags = 0x%x", desc->flags);
-    { int rc = require_device(); if (rc) return rc; }
-    int ndev = 0;
-    (void)crsdr_device_count(&ndev);
-    if (desc->device < 0 || desc->device >= ndev) return fail(CRSDR_ENODEV, "doa_create: device %d of %d", desc->device, ndev);
-
-    crsdr_doa *q = new (std::nothrow) crsdr_doa();
-    if (!q) return fail(CRSDR_ENOMEM, "doa_create: out of host memory");
-    q->nrows = desc->nrows; q->B = desc->blocksize; q->m = m; q->device = desc->device; q->max_batch = mb; q->frames = F; q->k = desc->k;
-    q->mx = desc->mx; q->my = desc->my; q->ncx = desc->ncx; q->ncy = desc->ncy; q->d = desc->d; q->flags = desc->flags;
-    q->nt = (m + doa::TILE - 1) / doa::TILE; q->ntri = doa::cov_tiles(q->nt);
-    // K slices per packet: about 1024 workgroups for a full batch (four per CU, so that the loads of one cover the MFMAs of another), no
-    // slice beyond 65536 bytes (the int32 partials stay exact), none below 512 (four MFMA steps per wave) unless the bound asks for it
-    const int spb_min = (q->B + 65535) / 65536, spb_max = std::max(spb_min, std::min(64, q->B / 512));
-    q->spb = std::min(std::max((1024 + mb - 1) / mb, spb_min), spb_max);
-    q->nwg = (int)(((size_t)q->ncx * q->ncy + music::PT - 1) / music::PT);
-    q->sx = q->mx; q->sy = q->my; q->ms = m;
-    int rc = doa_alloc(q);
-    if (rc) { doa_free(q); return rc; }
-    *doa = q;
-    return CRSDR_OK;
-}
-
-extern "C" int crsdr_doa_destroy(crsdr_doa *doa)
-{
-    if (!doa) return fail(CRSDR_EINVAL, "doa_destroy: NULL doa");
-    doa_free(doa);
-    return CRSDR_OK;
-}
-
-// `launch` with NB = the apply kernel's slot count for nbeams (1, 2, 4, 8 or 16)
-#define BEAMS_DISPATCH(nbeams, launch)                                              \
-    switch (beams::slots_for(nbeams)) {                                             \
-    case 1: { constexpr int NB = 1; launch; } break;                                \
-    case 2: { constexpr int NB = 2; launch; } break;                                \
-    case 4: { constexpr int NB = 4; launch; } break;                                \
-    case 8: { constexpr int NB = 8; launch; } break;                                \
-    default: { constexpr int NB = 16; launch; } break;                              \
-    }
-
-// `launch` with LG = log2 nfft
-#define SUBBAND_DISPATCH(lg, launch)                                                \
-    switch (lg) {                                                                   \
-    case 3: { constexpr int LG = 3; launch; } break;                                \
-    case 4: { constexpr int LG = 4; launch; } break;                                \
-    case 5: { constexpr int LG = 5; launch; } break;                                \
-    case 6: { constexpr int LG = 6; launch; } break;                                \
-    case 7: { constexpr int LG = 7; launch; } break;                                \
-    default: { constexpr int LG = 8; launch; } break;                               \
-    }
-
-// snapshots behind a matrix, for the source count: every sample, or a band's J' * width spectra
-static double doa_snapshots(const crsdr_doa *q)
-{
-    if (q->sb_nfft) return (double)q->frames * (double)(q->B / (2 * q->sb_nfft)) * (double)q->sb_width;
-    return (double)q->frames * (double)(q->B / 2);
-}
-
-static int doa_launch(crsdr_doa *q, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nblocks, hipStream_t S)
-{
-    unsigned nest = (unsigned)(nblocks / q->frames);
-    const unsigned slices = (unsigned)(q->frames * q->spb);
-    int launches = 0;
-    if (q->sb_nfft) {
-        // one covariance per (estimate, band); everything behind it runs over nest * nbands matrices, estimate e's band i at e * nbands + i
-        const dim3 grid((unsigned)(q->frames * q->sb_spb), (unsigned)q->sb_groups, nest);
-        SUBBAND_DISPATCH(q->sb_log2, hipLaunchKernelGGL(subband::k_doa_subband_cov<LG>, grid, dim3(subband::SB_THREADS), 0, S, packets, packet_stride, matrix_offset,
-                                                        q->nrows, q->B, q->frames, q->sb_spb, q->sb_window, q->d_sbpartial));
-        HIP_TRY(hipGetLastError()); ++launches;
-        hipLaunchKernelGGL(subband::k_doa_subband_reduce, dim3((unsigned)q->nbands, nest), dim3(256), 0, S, (const float2 *)q->d_sbpartial, (int)grid.x, q->nrows, q->B,
-                           q->frames, q->sb_log2, q->sb_first, q->sb_width, q->sb_window, q->d_rxx, q->d_sbpower);
-        HIP_TRY(hipGetLastError()); ++launches;
-        nest *= (unsigned)q->nbands;
-    } else {
-        if (q->nt == 1)
-            hipLaunchKernelGGL(doa::k_doa_cov<1>, dim3(slices, nest), dim3(doa::COV_THREADS), 0, S, packets, packet_stride, matrix_offset, q->nrows, q->B, q->frames,
-                               q->spb, q->d_partial, q->d_psum);
-        else
-            hipLaunchKernelGGL(doa::k_doa_cov<2>, dim3(slices, nest), dim3(doa::COV_THREADS), 0, S, packets, packet_stride, matrix_offset, q->nrows, q->B, q->frames,
-                               q->spb, q->d_partial, q->d_psum);
-        HIP_TRY(hipGetLastError()); ++launches;
-        hipLaunchKernelGGL(doa::k_doa_cov_reduce, dim3((unsigned)q->ntri, nest), dim3(256), 0, S, (const int *)q->d_partial, (const int2 *)q->d_psum, (int)slices,
-                           q->ntri, q->nrows, q->B, q->frames, q->d_rxx);
-        HIP_TRY(hipGetLastError()); ++launches;
-    }
-    // smoothing on: subspace, order, scan and peaks work on rs, an sx x sy array of M = ms elements (off: sx = mx, sy = my, M = m)
-    const int M = q->ms;
-    const float2 *cov = q->d_rxx;
-    if (q->smooth_on) {
-        hipLaunchKernelGGL(smooth::k_doa_smooth, dim3(nest), dim3(smooth::SM_THREADS), 0, S, (const float2 *)q->d_rxx, q->mx, q->my, q->sx, q->sy, q->smooth_flags,
-                           q->d_rs);
-        HIP_TRY(hipGetLastError()); ++launches;
-        cov = q->d_rs;
-    }
-    hipLaunchKernelGGL(doa::k_doa_subspace, dim3(nest), dim3(music::JT), 2 * sizeof(double2) * (size_t)M * M, S, cov, M, q->d_sv, q->d_vec, q->d_info);
-    HIP_TRY(hipGetLastError()); ++launches;
-    // with peaks on, the scan always leaves its spectrum: the kept one, or the workspace
-    float *pm = q->npeaks && !q->d_pm ? q->d_pmws : q->d_pm;
-    if (q->order_crit) {
-        hipLaunchKernelGGL(smooth::k_doa_order, dim3(nest), dim3(64), 0, S, (const float *)q->d_sv, M, doa_snapshots(q), q->order_crit, q->kmin,
-                           q->kmax, q->d_korder, q->d_crit);
-        HIP_TRY(hipGetLastError()); ++launches;
-        // the LDS of the most noise vectors an estimate can have, M - kmin
-        hipLaunchKernelGGL(doa::k_doa_scan<true>, dim3((unsigned)q->nwg, nest), dim3(music::PT), sizeof(float2) * ((size_t)M * (M - q->kmin) + (size_t)M * music::PT), S,
-                           (const float2 *)q->d_vec, M, q->k, q->d, q->sx, q->sy, q->ncx, q->ncy, pm, q->d_wgbest, (const int32_t *)q->d_korder);
-    } else
-        hipLaunchKernelGGL(doa::k_doa_scan<false>, dim3((unsigned)q->nwg, nest), dim3(music::PT), sizeof(float2) * ((size_t)M * (M - q->k) + (size_t)M * music::PT), S,
-                           (const float2 *)q->d_vec, M, q->k, q->d, q->sx, q->sy, q->ncx, q->ncy, pm, q->d_wgbest, (const int32_t *)nullptr);
-    HIP_TRY(hipGetLastError()); ++launches;
-    hipLaunchKernelGGL(doa::k_doa_peak, dim3(nest), dim3(256), 0, S, (const unsigned long long *)q->d_wgbest, q->nwg, q->ncy, q->d_peak, q->d_peakv);
-    HIP_TRY(hipGetLastError()); ++launches;
-    if (q->npeaks) {
-        hipLaunchKernelGGL(doa::k_doa_local_peaks, dim3((unsigned)q->lp_tiles, nest), dim3(doa::LP_THREADS), doa::lp_lds(q->radius), S, (const float *)pm, q->ncx,
-                           q->ncy, q->radius, q->npeaks, q->d_cand);
-        HIP_TRY(hipGetLastError()); ++launches;
-        hipLaunchKernelGGL(doa::k_doa_peaks_merge, dim3(nest), dim3(doa::LP_THREADS), 0, S, (const unsigned long long *)q->d_cand, q->lp_tiles * q->npeaks, q->ncy,
-                           q->npeaks, q->d_found, q->d_dirs, q->d_dirv, (const int32_t *)(q->order_crit && q->limit_dirs ? q->d_korder : nullptr));
-        HIP_TRY(hipGetLastError()); ++launches;
-    }
-    if (q->beam_mode) {
-        hipLaunchKernelGGL(beams::k_doa_beam_weights, dim3(nest, (unsigned)q->nbeams), dim3(beams::BW_THREADS), 0, S, (const float2 *)q->d_vec, (const float *)q->d_sv,
-                           q->m, q->mx, q->d, q->ncx, q->ncy, q->beam_mode, q->loading, (const float *)(q->nfixed ? q->d_bangles : nullptr),
-                           (const int32_t *)(q->npeaks ? q->d_found : nullptr), (const int32_t *)q->d_dirs, (const int32_t *)q->d_peak, q->d_bw, q->d_bpow);
-        HIP_TRY(hipGetLastError()); ++launches;
-        if (q->band_beams) {
-            // the weights above are per (estimate, band): applied to the rows' band spectra
-            const dim3 grid((unsigned)sbbeams::sbb_spb(q->B, q->sb_nfft), (unsigned)nblocks);
-            SUBBAND_DISPATCH(q->sb_log2, hipLaunchKernelGGL(sbbeams::k_doa_subband_beam_apply<LG>, grid, dim3(sbbeams::SBB_THREADS), sizeof(float2) * (size_t)q->sbb_lds,
-                                                            S, packets, packet_stride, matrix_offset, q->nrows, q->B, q->frames, q->sb_first, q->nbands, q->sb_width,
-                                                            q->sb_window, (const float2 *)q->d_bw, q->nbeams, q->sbb_lds, q->d_beams));
-        } else {
-            const dim3 grid((unsigned)((q->B / 4 + beams::AP_THREADS - 1) / beams::AP_THREADS), (unsigned)nblocks);
-            BEAMS_DISPATCH(q->nbeams, hipLaunchKernelGGL(beams::k_doa_beam_apply<NB>, grid, dim3(beams::AP_THREADS), 0, S, packets, packet_stride, matrix_offset,
-                                                         q->nrows, q->B, q->frames, (const float2 *)q->d_bw, q->nbeams, q->d_beams));
-        }
-        HIP_TRY(hipGetLastError()); ++launches;
-    }
-    q->last_stream = S; q->last_nest = (int)nest; q->last_nblocks = nblocks; q->last_launches = launches; q->submitted = true;
-    q->peaks_submitted = q->npeaks > 0; q->beams_submitted = q->beam_mode != 0;
-    q->last_ms = M; q->smooth_submitted = q->smooth_on; q->order_submitted = q->order_crit != 0;
-    return CRSDR_OK;
-}
-
-extern "C" int crsdr_doa_submit(crsdr_doa *q, const void *device_packets, size_t packet_stride, size_t matrix_offset, int nblocks, void *hip_stream)
-{
-    if (!q || !device_packets) return fail(CRSDR_EINVAL, "doa_submit: NULL doa or packets");
-    if (nblocks < 1 || nblocks > q->max_batch || nblocks % q->frames)
-        return fail(CRSDR_EINVAL, "doa_submit: nblocks = %d (1..max_batch = %d, a multiple of frames = %d)", nblocks, q->max_batch, q->frames);
-    if (((uintptr_t)device_packets + matrix_offset) % 4 || packet_stride % 4)
-        return fail(CRSDR_EINVAL, "doa_submit: matrix start and packet stride must be 4-byte aligned");
-    HIP_TRY(hipSetDevice(q->device));
-    return doa_launch(q, (const int8_t *)device_packets, packet_stride, matrix_offset, nblocks, hip_stream ? (hipStream_t)hip_stream : q->own_stream);
-}
-
-extern "C" int crsdr_doa_submit_plan(crsdr_doa *q, crsdr_plan *p)
-{
-    if (!q || !p) return fail(CRSDR_EINVAL, "doa_submit_plan: NULL argument");
-    if (p->nrows != q->nrows || p->B != q->B || p->device != q->device)
-        return fail(CRSDR_EINVAL, "doa_submit_plan: plan is %d x %d on device %d, doa %d x %d on device %d", p->nrows, p->B, p->device, q->nrows, q->B, q->device);
-    if (p->d_slab) return fail(CRSDR_ESTATE, "doa_submit_plan: the plan writes slabs (crsdr_plan_bind_slab): its packets hold no matrix");
-    if (!p->submitted || p->last_nblocks < 1) return fail(CRSDR_ESTATE, "doa_submit_plan: the plan has no submitted batch");
-    if (p->last_nblocks > q->max_batch || p->last_nblocks % q->frames)
-        return fail(CRSDR_EINVAL, "doa_submit_plan: the plan's batch of %d blocks (doa: at most %d, a multiple of frames = %d)", p->last_nblocks, q->max_batch, q->frames);
-    HIP_TRY(hipSetDevice(q->device));
-    // the batch's last kernel is on p->stream: stream order alone puts the covariance behind it
-    return doa_launch(q, p->d_packet, p->packet_stride, p->matrix_off, p->last_nblocks, p->stream);
-}
-
-extern "C" int crsdr_doa_fetch(crsdr_doa *q, int32_t *peak, float *peak_value, float *sv, int32_t *status, float *pm, float *rxx)
-{
-    if (!q) return fail(CRSDR_EINVAL, "doa_fetch: NULL doa");
-    if (pm && !(q->flags & CRSDR_DOA_KEEP_SPECTRUM)) return fail(CRSDR_EINVAL, "doa_fetch: pm asked of a doa created without CRSDR_DOA_KEEP_SPECTRUM");
-    if (rxx && !(q->flags & CRSDR_DOA_KEEP_RXX)) return fail(CRSDR_EINVAL, "doa_fetch: rxx asked of a doa created without CRSDR_DOA_KEEP_RXX");
-    if (!q->submitted) return fail(CRSDR_ESTATE, "doa_fetch: nothing submitted");
-    HIP_TRY(hipSetDevice(q->device));
-    const size_t nest = (size_t)q->last_nest, m = (size_t)q->m, ms = (size_t)q->last_ms;
-    hipStream_t S = q->last_stream;
-    static_assert(kMaxDoaMatrices >= kMaxBatch, "status of every matrix of a submit");
-    int info[2 * kMaxDoaMatrices];
-    if (peak) HIP_TRY(hipMemcpyAsync(peak, q->d_peak, sizeof(int32_t) * nest * 2, hipMemcpyDeviceToHost, S));
-    if (peak_value) HIP_TRY(hipMemcpyAsync(peak_value, q->d_peakv, sizeof(float) * nest, hipMemcpyDeviceToHost, S));
-    if (sv) HIP_TRY(hipMemcpyAsync(sv, q->d_sv, sizeof(float) * nest * ms, hipMemcpyDeviceToHost, S));
-    if (status) HIP_TRY(hipMemcpyAsync(info, q->d_info, sizeof(int) * nest * 2, hipMemcpyDeviceToHost, S));
-    if (pm) HIP_TRY(hipMemcpyAsync(pm, q->d_pm, sizeof(float) * nest * (size_t)q->ncx * q->ncy, hipMemcpyDeviceToHost, S));
-    if (rxx) HIP_TRY(hipMemcpyAsync(rxx, q->d_rxx, sizeof(float2) * nest * m * m, hipMemcpyDeviceToHost, S));
-    HIP_TRY(hipStreamSynchronize(S));
-    if (status)
-        for (size_t e = 0; e < nest; ++e) status[e] = info[2 * e + 1] ? 0 : 1;      // Jacobi sweeps ran out: data, not a failed call
-    return CRSDR_OK;
-}
-
-extern "C" int crsdr_doa_device_buffers(crsdr_doa *q, void **peak, void **peak_value, void **sv, void **vec, void **pm)
-{
-    if (!q) return fail(CRSDR_EINVAL, "doa_device_buffers: NULL doa");
-    if (peak) *peak = q->d_peak;
-    if (peak_value) *peak_value = q->d_peakv;
-    if (sv) *sv = q->d_sv;
-    if (vec) *vec = q->d_vec;
-    if (pm) *pm = q->d_pm;
-    return CRSDR_OK;
-}
-
-extern "C" int crsdr_doa_last_submit(crsdr_doa *q, int *nest, int *launches)
-{
-    if (!q) return fail(CRSDR_EINVAL, "doa_last_submit: NULL doa");
-    if (!q->submitted) return fail(CRSDR_ESTATE, "doa_last_submit: nothing submitted");
-    if (nest) *nest = q->last_nest;
-    if (launches) *launches = q->last_launches;
-    return CRSDR_OK;
-}
-
-static int doa_alloc_peaks(crsdr_doa *q, int count)
-{
-    const size_t nest = doa_capacity(q), grid = (size_t)q->ncx * q->ncy;
-    q->lp_tiles = doa::lp_tiles(q->ncx, q->ncy);
-    if (!q->d_pm) HIP_TRY(hipMalloc((void **)&q->d_pmws, sizeof(float) * nest * grid));
-    HIP_TRY(hipMalloc((void **)&q->d_cand, sizeof(unsigned long long) * nest * q->lp_tiles * count));
-    HIP_TRY(hipMalloc((void **)&q->d_found, sizeof(int32_t) * nest));
-    HIP_TRY(hipMalloc((void **)&q->d_dirs, sizeof(int32_t) * nest * count * 2));
-    HIP_TRY(hipMalloc((void **)&q->d_dirv, sizeof(float) * nest * count));
-    HIP_TRY(hipFuncSetAttribute((const void *)doa::k_doa_local_peaks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)doa::lp_lds(doa::MAX_RADIUS)));
-    return CRSDR_OK;
-}
-
-extern "C" int crsdr_doa_set_peaks(crsdr_doa *q, int count, int radius)
-{
-    if (!q) return fail(CRSDR_EINVAL, "doa_set_peaks: NULL doa");
-    if (count < 0 || count > doa::MAX_PEAKS) return fail(CRSDR_EINVAL, "doa_set_peaks: count = %d (0..%d)", count, doa::MAX_PEAKS);
-    if (count > 0 && (radius < 1 || radius > doa::MAX_RADIUS)) return fail(CRSDR_EINVAL, "doa_set_peaks: radius = %d (1..%d)", radius, doa::MAX_RADIUS);
-    if (q->beam_mode && !q->nfixed)
-        return fail(CRSDR_ESTATE, "doa_set_peaks: beams follow the directions (crsdr_doa_set_beams or _set_subband_beams with nfixed = 0) and are sized by them: turn the beams off first");
-    HIP_TRY(hipSetDevice(q->device));
-    if (q->submitted) HIP_TRY(hipDeviceSynchronize());   // the buffers may be in use (the last submit's stream may be the caller's, and gone)
-    doa_free_peaks(q);
-    if (count == 0) return CRSDR_OK;
-    const int rc = doa_alloc_peaks(q, count);
-    if (rc) { doa_free_peaks(q); return rc; }
-    q->npeaks = count; q->radius = radius;
-    return CRSDR_OK;
-}
-
-extern "C" int crsdr_doa_fetch_directions(crsdr_doa *q, int32_t *found, int32_t *peaks, float *values)
-{
-    if (!q) return fail(CRSDR_EINVAL, "doa_fetch_directions: NULL doa");
-    if (!q->npeaks) return fail(CRSDR_ESTATE, "doa_fetch_directions: no crsdr_doa_set_peaks");
-    if (!q->peaks_submitted) return fail(CRSDR_ESTATE, "doa_fetch_directions: nothing submitted since crsdr_doa_set_peaks");
-    HIP_TRY(hipSetDevice(q->device));
-    const size_t nest = (size_t)q->last_nest, c = (size_t)q->npeaks;
-    hipStream_t S = q->last_stream;
-    if (found) HIP_TRY(hipMemcpyAsync(found, q->d_found, sizeof(int32_t) * nest, hipMemcpyDeviceToHost, S));
-    if (peaks) HIP_TRY(hipMemcpyAsync(peaks, q->d_dirs, sizeof(int32_t) * nest * c * 2, hipMemcpyDeviceToHost, S));
-    if (values) HIP_TRY(hipMemcpyAsync(values, q->d_dirv, sizeof(float) * nest * c, hipMemcpyDeviceToHost, S));
-    HIP_TRY(hipStreamSynchronize(S));
-    return CRSDR_OK;
-}
-
-extern "C" int crsdr_doa_direction_buffers(crsdr_doa *q, void **found, void **peaks, void **values)
-{
-    if (!q) return fail(CRSDR_EINVAL, "doa_direction_buffers: NULL doa");
-    if (found) *found = q->d_found;
-    if (peaks) *peaks = q->d_dirs;
-    if (values) *values = q->d_dirv;
-    return CRSDR_OK;
-}
-
-// ---- beams toward the directions (beams.hpp) ----
-extern "C" int crsdr_doa_set_beams(crsdr_doa *q, int mode, float loading, int nfixed, const float *fixed_angles)
-{
-    if (!q) return fail(CRSDR_EINVAL, "doa_set_beams: NULL doa");
-    if (mode != CRSDR_BEAM_OFF && mode != CRSDR_BEAM_CONVENTIONAL && mode != CRSDR_BEAM_MVDR) return fail(CRSDR_EINVAL, "doa_set_beams: mode = %d", mode);
-    if (mode == CRSDR_BEAM_MVDR && !(loading >= 1e-6f && loading <= 1.0f)) return fail(CRSDR_EINVAL, "doa_set_beams: loading = %g (1e-6..1)", (double)loading);
-    if (mode != CRSDR_BEAM_OFF && (nfixed < 0 || nfixed > beams::MAX_BEAMS)) return fail(CRSDR_EINVAL, "doa_set_beams: nfixed = %d (0..%d)", nfixed, beams::MAX_BEAMS);
-    if (mode != CRSDR_BEAM_OFF && nfixed > 0 && !fixed_angles) return fail(CRSDR_EINVAL, "doa_set_beams: %d fixed directions and no angles", nfixed);
-    if (mode != CRSDR_BEAM_OFF && q->sb_nfft)
-        return fail(CRSDR_ESTATE, "doa_set_beams: subbands are on (crsdr_doa_set_subbands): a band's weights applied to the wideband samples mean nothing");
-    if (mode != CRSDR_BEAM_OFF && q->ms < q->m)
-        return fail(CRSDR_ESTATE, "doa_set_beams: smoothing over %d x %d sub-arrays is on (crsdr_doa_set_smoothing): the weights are %d-vectors and there is no %d x %d subspace",
-                    q->sx, q->sy, q->m, q->m, q->m);
-    if (q->band_beams) return CRSDR_OK;                  // (off, with subbands on: the band beams are crsdr_doa_set_subband_beams' to turn off)
-    HIP_TRY(hipSetDevice(q->device));
-    if (q->submitted) HIP_TRY(hipDeviceSynchronize());   // the buffers may be in use (the last submit's stream may be the caller's, and gone)
-    doa_free_beams(q);
-    if (mode == CRSDR_BEAM_OFF) return CRSDR_OK;
-    const size_t nest = (size_t)(q->max_batch / q->frames), nb = (size_t)(nfixed ? nfixed : q->npeaks ? q->npeaks : 1);
-    int rc = CRSDR_OK;
-    auto alloc = [&](void **p, size_t bytes) { if (!rc && hipMalloc(p, bytes) != hipSuccess) rc = fail(CRSDR_ENOMEM, "doa_set_beams: %zu bytes of device memory", bytes); };
-    alloc((void **)&q->d_bw, sizeof(float2) * nest * nb * (size_t)q->m);
-    alloc((void **)&q->d_bpow, sizeof(float) * nest * nb);
-    alloc((void **)&q->d_beams, sizeof(float2) * (size_t)q->max_batch * nb * (size_t)(q->B / 2));
-    if (nfixed) {
-        alloc((void **)&q->d_bangles, sizeof(float) * 2 * nb);
-        if (!rc && hipMemcpy(q->d_bangles, fixed_angles, sizeof(float) * 2 * nb, hipMemcpyHostToDevice) != hipSuccess) rc = fail(CRSDR_EHIP, "doa_set_beams: copy of the angles");
-    }
-    if (rc) { doa_free_beams(q); return rc; }
-    q->beam_mode = mode; q->nbeams = (int)nb; q->nfixed = nfixed; q->loading = mode == CRSDR_BEAM_MVDR ? loading : 0.f;
-    return CRSDR_OK;
-}
-
-extern "C" int crsdr_doa_fetch_beams(crsdr_doa *q, float *weights, float *power, float *beams)
-{
-    if (!q) return fail(CRSDR_EINVAL, "doa_fetch_beams: NULL doa");
-    if (!q->beam_mode || q->band_beams) return fail(CRSDR_ESTATE, "doa_fetch_beams: no crsdr_doa_set_beams");
-    if (!q->beams_submitted) return fail(CRSDR_ESTATE, "doa_fetch_beams: nothing submitted since crsdr_doa_set_beams");
-    HIP_TRY(hipSetDevice(q->device));
-    const size_t nest = (size_t)q->last_nest, nb = (size_t)q->nbeams;
-    hipStream_t S = q->last_stream;
-    if (weights) HIP_TRY(hipMemcpyAsync(weights, q->d_bw, sizeof(float2) * nest * nb * (size_t)q->m, hipMemcpyDeviceToHost, S));
-    if (power) HIP_TRY(hipMemcpyAsync(power, q->d_bpow, sizeof(float) * nest * nb, hipMemcpyDeviceToHost, S));
-    if (beams) HIP_TRY(hipMemcpyAsync(beams, q->d_beams, sizeof(float2) * (size_t)q->last_nblocks * nb * (size_t)(q->B / 2), hipMemcpyDeviceToHost, S));
-    HIP_TRY(hipStreamSynchronize(S));
-    return CRSDR_OK;
-}
-
-extern "C" int crsdr_doa_beam_buffers(crsdr_doa *q, void **weights, void **power, void **beams, int *nbeams)
-{
-    if (!q) return fail(CRSDR_EINVAL, "doa_beam_buffers: NULL doa");
-    const bool on = !q->band_beams;
-    if (weights) *weights = on ? q->d_bw : nullptr;
-    if (power) *power = on ? q->d_bpow : nullptr;
-    if (beams) *beams = on ? q->d_beams : nullptr;
-    if (nbeams) *nbeams = on ? q->nbeams : 0;
-    return CRSDR_OK;
-}
-
-extern "C" int crsdr_doa_fetch_subspace(crsdr_doa *q, float *vec)
-{
-    if (!q || !vec) return fail(CRSDR_EINVAL, "doa_fetch_subspace: NULL doa or vec");
-    if (!q->submitted) return fail(CRSDR_ESTATE, "doa_fetch_subspace: nothing submitted");
-    HIP_TRY(hipSetDevice(q->device));
-    HIP_TRY(hipMemcpyAsync(vec, q->d_vec, sizeof(float2) * (size_t)q->last_nest * (size_t)q->last_ms * q->last_ms, hipMemcpyDeviceToHost, q->last_stream));
-    HIP_TRY(hipStreamSynchronize(q->last_stream));
-    return CRSDR_OK;
-}
-
-// ---- spatial smoothing and the source count (smooth.hpp) ----
-extern "C" int crsdr_doa_set_smoothing(crsdr_doa *q, int sx, int sy, uint32_t flags)
-{
-    if (!q) return fail(CRSDR_EINVAL, "doa_set_smoothing: NULL doa");
-    if (!smooth_shape_ok(q->mx, q->my, sx, sy, flags))
-        return fail(CRSDR_EINVAL, "doa_set_smoothing: sub-arrays of %d x %d in an array of %d x %d, flags = 0x%x (1 <= sx <= mx, 1 <= sy <= my, sx * sy >= 2, CRSDR_SMOOTH_FB)", sx,
-                    sy, q->mx, q->my, flags);
-    const int ms = sx * sy;
-    if (q->k >= ms) return fail(CRSDR_EINVAL, "doa_set_smoothing: k = %d sources need sub-arrays of more than %d elements (%d x %d)", q->k, q->k, sx, sy);
-    if (q->order_crit && q->kmax >= ms)
-        return fail(CRSDR_EINVAL, "doa_set_smoothing: the order range ends at kmax = %d, sub-arrays of %d x %d have %d elements", q->kmax, sx, sy, ms);
-    if (ms < q->m && q->beam_mode)
-        return fail(CRSDR_ESTATE, "doa_set_smoothing: beams are on (crsdr_doa_set_beams or _set_subband_beams): their weights are %d-vectors from the %d x %d subspace: turn them off first", q->m,
-                    q->m, q->m);
-    HIP_TRY(hipSetDevice(q->device));
-    if (q->submitted) HIP_TRY(hipDeviceSynchronize());   // the buffers may be in use (the last submit's stream may be the caller's, and gone)
-    doa_free_smooth(q);
-    q->submitted = false;                                // sv and vec change their shape: what the last submit left is gone
-    if (ms == q->m && !flags) return CRSDR_OK;
-    const size_t nest = doa_capacity(q);
-    if (hipMalloc((void **)&q->d_rs, sizeof(float2) * nest * ms * ms) != hipSuccess)
-        return fail(CRSDR_ENOMEM, "doa_set_smoothing: %zu bytes of device memory", sizeof(float2) * nest * ms * ms);
-    q->smooth_on = true; q->sx = sx; q->sy = sy; q->ms = ms; q->smooth_flags = flags;
-    return CRSDR_OK;
-}
-
-extern "C" int crsdr_doa_fetch_smoothed(crsdr_doa *q, float *rs)
-{
-    if (!q || !rs) return fail(CRSDR_EINVAL, "doa_fetch_smoothed: NULL doa or rs");
-    if (!q->smooth_on) return fail(CRSDR_ESTATE, "doa_fetch_smoothed: no crsdr_doa_set_smoothing");
-    if (!q->smooth_submitted) return fail(CRSDR_ESTATE, "doa_fetch_smoothed: nothing submitted since crsdr_doa_set_smoothing");
-    HIP_TRY(hipSetDevice(q->device));
-    HIP_TRY(hipMemcpyAsync(rs, q->d_rs, sizeof(float2) * (size_t)q->last_nest * (size_t)q->ms * q->ms, hipMemcpyDeviceToHost, q->last_stream));
-    HIP_TRY(hipStreamSynchronize(q->last_stream));
-    return CRSDR_OK;
-}
-
-extern "C" int crsdr_doa_set_order(crsdr_doa *q, int criterion, int kmin, int kmax, int limit_directions)
-{
-    if (!q) return fail(CRSDR_EINVAL, "doa_set_order: NULL doa");
-    if (criterion != CRSDR_ORDER_OFF && criterion != CRSDR_ORDER_MDL && criterion != CRSDR_ORDER_AIC) return fail(CRSDR_EINVAL, "doa_set_order: criterion = %d", criterion);
-    if (criterion != CRSDR_ORDER_OFF && (kmin < 1 || kmin > kmax || kmax >= q->ms))
-        return fail(CRSDR_EINVAL, "doa_set_order: k in %d .. %d (1 <= kmin <= kmax < %d, the subspace's size)", kmin, kmax, q->ms);
-    HIP_TRY(hipSetDevice(q->device));
-    if (q->submitted) HIP_TRY(hipDeviceSynchronize());   // the buffers may be in use (the last submit's stream may be the caller's, and gone)
-    doa_free_order(q);
-    if (criterion == CRSDR_ORDER_OFF) return CRSDR_OK;
-    const size_t nest = doa_capacity(q), nc = (size_t)(kmax - kmin + 1);
-    HIP_TRY(hipFuncSetAttribute((const void *)doa::k_doa_scan<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kDoaScanLdsMax));
-    if (hipMalloc((void **)&q->d_korder, sizeof(int32_t) * nest) != hipSuccess || hipMalloc((void **)&q->d_crit, sizeof(float) * nest * nc) != hipSuccess) {
-        doa_free_order(q);
-        return fail(CRSDR_ENOMEM, "doa_set_order: device memory for %zu estimates of %zu candidates", nest, nc);
-    }
-    q->order_crit = criterion; q->kmin = kmin; q->kmax = kmax; q->limit_dirs = limit_directions != 0;
-    return CRSDR_OK;
-}
-
-extern "C" int crsdr_doa_fetch_order(crsdr_doa *q, int32_t *k, float *criterion_values)
-{
-    if (!q) return fail(CRSDR_EINVAL, "doa_fetch_order: NULL doa");
-    if (!q->order_crit) return fail(CRSDR_ESTATE, "doa_fetch_order: no crsdr_doa_set_order");
-    if (!q->order_submitted) return fail(CRSDR_ESTATE, "doa_fetch_order: nothing submitted since crsdr_doa_set_order");
-    HIP_TRY(hipSetDevice(q->device));
-    const size_t nest = (size_t)q->last_nest, nc = (size_t)(q->kmax - q->kmin + 1);
-    hipStream_t S = q->last_stream;
-    if (k) HIP_TRY(hipMemcpyAsync(k, q->d_korder, sizeof(int32_t) * nest, hipMemcpyDeviceToHost, S));
-    if (criterion_values) HIP_TRY(hipMemcpyAsync(criterion_values, q->d_crit, sizeof(float) * nest * nc, hipMemcpyDeviceToHost, S));
-    HIP_TRY(hipStreamSynchronize(S));
-    return CRSDR_OK;
-}
-
-extern "C" int crsdr_doa_order_buffers(crsdr_doa *q, void **k, void **criterion_values)
-{
-    if (!q) return fail(CRSDR_EINVAL, "doa_order_buffers: NULL doa");
-    if (k) *k = q->d_korder;
-    if (criterion_values) *criterion_values = q->d_crit;
-    return CRSDR_OK;
-}
-
-// ---- one covariance per frequency band (subband.hpp) ----
-static int subband_args_ok(const char *who, int blocksize, int nfft, int first, int nbands, int width, int window)
-{
-    if (nfft < (1 << subband::SB_MIN_LOG2) || nfft > (1 << subband::SB_MAX_LOG2) || (nfft & (nfft - 1)))
-        return fail(CRSDR_EINVAL, "%s: nfft = %d (a power of two, %d..%d)", who, nfft, 1 << subband::SB_MIN_LOG2, 1 << subband::SB_MAX_LOG2);
-    if (blocksize % (2 * nfft)) return fail(CRSDR_EINVAL, "%s: blocksize = %d is no multiple of 2 nfft = %d", who, blocksize, 2 * nfft);
-    if (first < 0 || first >= nfft) return fail(CRSDR_EINVAL, "%s: first = %d (0..nfft - 1 = %d)", who, first, nfft - 1);
-    if (nbands < 1 || width < 1 || (long long)nbands * width > nfft)
-        return fail(CRSDR_EINVAL, "%s: %d bands of %d bins (nbands >= 1, width >= 1, nbands * width <= nfft = %d)", who, nbands, width, nfft);
-    if (window != CRSDR_WINDOW_RECT && window != CRSDR_WINDOW_HANN) return fail(CRSDR_EINVAL, "%s: window = %d", who, window);
-    return CRSDR_OK;
-}
-
-static int ilog2(int n) { int lg = 0; while ((1 << lg) < n) ++lg; return lg; }
-
-extern "C" int crsdr_doa_set_subbands(crsdr_doa *q, int nfft, int first, int nbands, int width, int window)
-{
-    if (!q) return fail(CRSDR_EINVAL, "doa_set_subbands: NULL doa");
-    if (nfft != 0) {
-        const int rc = subband_args_ok("doa_set_subbands", q->B, nfft, first, nbands, width, window);
-        if (rc) return rc;
-        if ((long long)(q->max_batch / q->frames) * nbands > kMaxDoaMatrices)
-            return fail(CRSDR_EINVAL, "doa_set_subbands: %d estimates of %d bands (at most %d matrices per submit)", q->max_batch / q->frames, nbands, kMaxDoaMatrices);
-    }
-    if (q->npeaks || q->beam_mode || q->smooth_on || q->order_crit)
-        return fail(CRSDR_ESTATE, "doa_set_subbands: peaks, beams, smoothing or the source count are on: their buffers are sized by the bands, turn them off first");
-    HIP_TRY(hipSetDevice(q->device));
-    if (q->submitted) HIP_TRY(hipDeviceSynchronize());   // the buffers may be in use (the last submit's stream may be the caller's, and gone)
-    q->submitted = false;                                // the matrices change their number: what the last submit left is gone
-    doa_free_matrices(q);
-    q->sb_nfft = nfft; q->sb_log2 = nfft ? ilog2(nfft) : 0; q->sb_first = nfft ? first : 0; q->nbands = nfft ? nbands : 1; q->sb_width = nfft ? width : 0;
-    q->sb_window = nfft ? window : 0;
-    q->sb_spb = nfft ? subband::subband_spb(q->B, nfft) : 1; q->sb_groups = nfft ? subband::subband_groups(q->m, nfft) : 1;
-    int rc = doa_alloc_matrices(q);
-    if (rc && nfft) {                                    // back to the plain engine, which fitted before
-        doa_free_matrices(q);
-        q->sb_nfft = q->sb_log2 = q->sb_first = q->sb_width = q->sb_window = 0; q->nbands = q->sb_spb = q->sb_groups = 1;
-        (void)doa_alloc_matrices(q);
-    }
-    return rc;
-}
-
-extern "C" int crsdr_doa_fetch_subbands(crsdr_doa *q, float *power)
-{
-    if (!q || !power) return fail(CRSDR_EINVAL, "doa_fetch_subbands: NULL doa or power");
-    if (!q->sb_nfft) return fail(CRSDR_ESTATE, "doa_fetch_subbands: no crsdr_doa_set_subbands");
-    if (!q->submitted) return fail(CRSDR_ESTATE, "doa_fetch_subbands: nothing submitted since crsdr_doa_set_subbands");
-    HIP_TRY(hipSetDevice(q->device));
-    HIP_TRY(hipMemcpyAsync(power, q->d_sbpower, sizeof(float) * (size_t)q->last_nest, hipMemcpyDeviceToHost, q->last_stream));
-    HIP_TRY(hipStreamSynchronize(q->last_stream));
-    return CRSDR_OK;
-}
-
-extern "C" int crsdr_doa_subband_buffers(crsdr_doa *q, void **power)
-{
-    if (!q) return fail(CRSDR_EINVAL, "doa_subband_buffers: NULL doa");
-    if (power) *power = q->d_sbpower;
-    return CRSDR_OK;
-}
-
+// ---- (iii) continued: the per-op calls on the engine's kernels (BEAMS_DISPATCH, SUBBAND_DISPATCH: doa_engine.hpp) ----
 extern "C" int crsdr_subband_covariance(float *rbands, float *power, const int8_t *matrix, int nrows, int blocksize, int nfft, int first, int nbands, int width,
                                         int window, int mem_kind)
 {
     if (!rbands || !matrix || nrows < 2 || nrows - 1 > subband::SB_MAX_ROWS || blocksize < 16)
         return fail(CRSDR_EINVAL, "subband_covariance: need rbands, matrix, 2 <= nrows <= %d, blocksize >= 16", subband::SB_MAX_ROWS + 1);
     { const int rc_ = subband_args_ok("subband_covariance", blocksize, nfft, first, nbands, width, window); if (rc_) return rc_; }
-    if (mem_kind != CRSDR_MEM_HOST && mem_kind != CRSDR_MEM_DEVICE) return fail(CRSDR_EINVAL, "subband_covariance: mem_kind = %d", mem_kind);
-    { int rc_ = require_device(); if (rc_) return rc_; }
-    std::lock_guard<std::mutex> lock_(g_op.mu);
-    const int m = nrows - 1, spb = subband::subband_spb(blocksize, nfft), lg = ilog2(nfft);
+    OP_PROLOGUE_MEM("subband_covariance", mem_kind);
+    const int m = nrows - 1, spb = subband::subband_spb(blocksize, nfft), lg = ilog2_exact(nfft);
     const size_t mb = (size_t)nrows * (size_t)blocksize, rb = sizeof(float2) * (size_t)nbands * m * m, pb = sizeof(float) * (size_t)nbands;
-    const int8_t *d_m = matrix;
-    float2 *d_r = (float2 *)rbands;
-    float *d_p = power;
-    if (mem_kind == CRSDR_MEM_HOST || !power) OP_RESERVE(2, pb);
-    if (mem_kind == CRSDR_MEM_HOST) {
-        OP_RESERVE(0, mb); OP_RESERVE(1, rb);
-        HIP_TRY(hipMemcpy(g_op.buf[0], matrix, mb, hipMemcpyHostToDevice));
-        d_m = (const int8_t *)g_op.buf[0]; d_r = (float2 *)g_op.buf[1]; d_p = (float *)g_op.buf[2];
-    } else {
-        if ((uintptr_t)d_m % 4 || (uintptr_t)d_r % 8 || (uintptr_t)power % 4) return fail(CRSDR_EINVAL, "subband_covariance: device matrix and power 4-byte, rbands 8-byte aligned");
-        if (!power) d_p = (float *)g_op.buf[2];
-    }
+    OpStage st(mem_kind);
+    const int8_t *d_m = (const int8_t *)st.in(0, matrix, mb, 4);
+    float2 *d_r = (float2 *)st.out(1, rbands, rb, 8);
+    float *d_p = (float *)st.out(2, power, pb, 4);
+    if (st.rc) return st.rc;
+    if (st.misaligned) return fail(CRSDR_EINVAL, "subband_covariance: device matrix and power 4-byte, rbands 8-byte aligned");
+    if (!d_p) { OP_RESERVE(2, pb); d_p = (float *)g_op.buf[2]; }      // (device memory and no power asked for: the reducer writes it all the same)
     OP_RESERVE(3, sizeof(float2) * (size_t)spb * subband::subband_partial(m, nfft));
     const dim3 grid((unsigned)spb, (unsigned)subband::subband_groups(m, nfft), 1);
     SUBBAND_DISPATCH(lg, hipLaunchKernelGGL(subband::k_doa_subband_cov<LG>, grid, dim3(subband::SB_THREADS), 0, 0, d_m, (size_t)0, (size_t)0, nrows, blocksize, 1, spb,
@@ -2529,86 +1899,18 @@ extern "C" int crsdr_subband_covariance(float *rbands, float *power, const int8_
     hipLaunchKernelGGL(subband::k_doa_subband_reduce, dim3((unsigned)nbands, 1), dim3(256), 0, 0, (const float2 *)g_op.buf[3], spb, nrows, blocksize, 1, lg, first, width,
                        window, d_r, d_p);
     HIP_TRY(hipGetLastError());
-    if (mem_kind == CRSDR_MEM_HOST) {
-        HIP_TRY(hipMemcpy(rbands, d_r, rb, hipMemcpyDeviceToHost));
-        if (power) HIP_TRY(hipMemcpy(power, d_p, pb, hipMemcpyDeviceToHost));
-    } else HIP_TRY(hipDeviceSynchronize());
-    return CRSDR_OK;
+    st.back(rbands, d_r, rb);
+    st.back(power, d_p, pb);
+    return st.finish();
 }
 
-// ---- a beam per frequency band (subband_beams.hpp) ----
-// every instantiation the object or the per-op call can launch may need more than 64 KiB of dynamic LDS
+// every instantiation the per-op call can launch may need more than 64 KiB of dynamic LDS
 template <typename K>
 static int sbb_lds_limit(K kern, const char *who)
 {
     if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)(sizeof(float2) * sbbeams::sbb_seg_stride(sbbeams::SBB_MAX_ROWS, 1 << subband::SB_MAX_LOG2))) != hipSuccess)
         return fail(CRSDR_EHIP, "%s: dynamic LDS limit of the band beam kernel", who);
-    return CRSDR_OK;
-}
-
-extern "C" int crsdr_doa_set_subband_beams(crsdr_doa *q, int mode, float loading, int nfixed, const float *fixed_angles)
-{
-    if (!q) return fail(CRSDR_EINVAL, "doa_set_subband_beams: NULL doa");
-    if (mode != CRSDR_BEAM_OFF && mode != CRSDR_BEAM_CONVENTIONAL && mode != CRSDR_BEAM_MVDR) return fail(CRSDR_EINVAL, "doa_set_subband_beams: mode = %d", mode);
-    if (mode == CRSDR_BEAM_MVDR && !(loading >= 1e-6f && loading <= 1.0f)) return fail(CRSDR_EINVAL, "doa_set_subband_beams: loading = %g (1e-6..1)", (double)loading);
-    if (mode != CRSDR_BEAM_OFF && (nfixed < 0 || nfixed > beams::MAX_BEAMS))
-        return fail(CRSDR_EINVAL, "doa_set_subband_beams: nfixed = %d (0..%d)", nfixed, beams::MAX_BEAMS);
-    if (mode != CRSDR_BEAM_OFF && nfixed > 0 && !fixed_angles) return fail(CRSDR_EINVAL, "doa_set_subband_beams: %d fixed directions and no angles", nfixed);
-    if (mode != CRSDR_BEAM_OFF && !q->sb_nfft)
-        return fail(CRSDR_ESTATE, "doa_set_subband_beams: subbands are off (crsdr_doa_set_subbands): the wideband beams are crsdr_doa_set_beams");
-    if (mode != CRSDR_BEAM_OFF && q->ms < q->m)
-        return fail(CRSDR_ESTATE, "doa_set_subband_beams: smoothing over %d x %d sub-arrays is on (crsdr_doa_set_smoothing): the weights are %d-vectors and there is no %d x %d subspace",
-                    q->sx, q->sy, q->m, q->m, q->m);
-    if (q->beam_mode && !q->band_beams) return CRSDR_OK; // (off, with subbands off: the wideband beams are crsdr_doa_set_beams' to turn off)
-    HIP_TRY(hipSetDevice(q->device));
-    if (q->submitted) HIP_TRY(hipDeviceSynchronize());   // the buffers may be in use (the last submit's stream may be the caller's, and gone)
-    doa_free_beams(q);
-    if (mode == CRSDR_BEAM_OFF) return CRSDR_OK;
-    const size_t nmat = doa_capacity(q), nb = (size_t)(nfixed ? nfixed : q->npeaks ? q->npeaks : 1);
-    // a packet's beams: nbands * width bins of J segments each, at most blocksize / 2 samples per slot
-    const size_t per_packet = (size_t)q->nbands * nb * (size_t)(q->B / (2 * q->sb_nfft)) * (size_t)q->sb_width;
-    int rc = CRSDR_OK;
-    SUBBAND_DISPATCH(q->sb_log2, rc = sbb_lds_limit(sbbeams::k_doa_subband_beam_apply<LG>, "doa_set_subband_beams"));
-    auto alloc = [&](void **p, size_t bytes) { if (!rc && hipMalloc(p, bytes) != hipSuccess) rc = fail(CRSDR_ENOMEM, "doa_set_subband_beams: %zu bytes of device memory", bytes); };
-    alloc((void **)&q->d_bw, sizeof(float2) * nmat * nb * (size_t)q->m);
-    alloc((void **)&q->d_bpow, sizeof(float) * nmat * nb);
-    alloc((void **)&q->d_beams, sizeof(float2) * (size_t)q->max_batch * per_packet);
-    if (nfixed) {
-        alloc((void **)&q->d_bangles, sizeof(float) * 2 * nb);
-        if (!rc && hipMemcpy(q->d_bangles, fixed_angles, sizeof(float) * 2 * nb, hipMemcpyHostToDevice) != hipSuccess)
-            rc = fail(CRSDR_EHIP, "doa_set_subband_beams: copy of the angles");
-    }
-    if (rc) { doa_free_beams(q); return rc; }
-    q->beam_mode = mode; q->nbeams = (int)nb; q->nfixed = nfixed; q->loading = mode == CRSDR_BEAM_MVDR ? loading : 0.f;
-    q->band_beams = true; q->sbb_lds = sbbeams::sbb_lds_points(q->m, q->B, q->sb_nfft);
-    return CRSDR_OK;
-}
-
-extern "C" int crsdr_doa_fetch_subband_beams(crsdr_doa *q, float *weights, float *power, float *beams)
-{
-    if (!q) return fail(CRSDR_EINVAL, "doa_fetch_subband_beams: NULL doa");
-    if (!q->band_beams) return fail(CRSDR_ESTATE, "doa_fetch_subband_beams: no crsdr_doa_set_subband_beams");
-    if (!q->beams_submitted) return fail(CRSDR_ESTATE, "doa_fetch_subband_beams: nothing submitted since crsdr_doa_set_subband_beams");
-    HIP_TRY(hipSetDevice(q->device));
-    const size_t nmat = (size_t)q->last_nest, nb = (size_t)q->nbeams;
-    const size_t per_packet = (size_t)q->nbands * nb * (size_t)(q->B / (2 * q->sb_nfft)) * (size_t)q->sb_width;
-    hipStream_t S = q->last_stream;
-    if (weights) HIP_TRY(hipMemcpyAsync(weights, q->d_bw, sizeof(float2) * nmat * nb * (size_t)q->m, hipMemcpyDeviceToHost, S));
-    if (power) HIP_TRY(hipMemcpyAsync(power, q->d_bpow, sizeof(float) * nmat * nb, hipMemcpyDeviceToHost, S));
-    if (beams) HIP_TRY(hipMemcpyAsync(beams, q->d_beams, sizeof(float2) * (size_t)q->last_nblocks * per_packet, hipMemcpyDeviceToHost, S));
-    HIP_TRY(hipStreamSynchronize(S));
-    return CRSDR_OK;
-}
-
-extern "C" int crsdr_doa_subband_beam_buffers(crsdr_doa *q, void **weights, void **power, void **beams, int *nbeams)
-{
-    if (!q) return fail(CRSDR_EINVAL, "doa_subband_beam_buffers: NULL doa");
-    const bool on = q->band_beams;
-    if (weights) *weights = on ? q->d_bw : nullptr;
-    if (power) *power = on ? q->d_bpow : nullptr;
-    if (beams) *beams = on ? q->d_beams : nullptr;
-    if (nbeams) *nbeams = on ? q->nbeams : 0;
     return CRSDR_OK;
 }
 
@@ -2619,23 +1921,16 @@ extern "C" int crsdr_subband_beamform(float *out, const int8_t *matrix, int nrow
         return fail(CRSDR_EINVAL, "subband_beamform: need out, matrix, weights, 2 <= nrows <= %d, blocksize >= 16, 1 <= nbeams <= %d", sbbeams::SBB_MAX_ROWS + 1,
                     sbbeams::SBB_MAX_BEAMS);
     { const int rc_ = subband_args_ok("subband_beamform", blocksize, nfft, first, nbands, width, window); if (rc_) return rc_; }
-    if (mem_kind != CRSDR_MEM_HOST && mem_kind != CRSDR_MEM_DEVICE) return fail(CRSDR_EINVAL, "subband_beamform: mem_kind = %d", mem_kind);
-    { int rc_ = require_device(); if (rc_) return rc_; }
-    std::lock_guard<std::mutex> lock_(g_op.mu);
-    const int m = nrows - 1, lg = ilog2(nfft), J = blocksize / (2 * nfft), points = sbbeams::sbb_lds_points(m, blocksize, nfft);
+    OP_PROLOGUE_MEM("subband_beamform", mem_kind);
+    const int m = nrows - 1, lg = ilog2_exact(nfft), J = blocksize / (2 * nfft), points = sbbeams::sbb_lds_points(m, blocksize, nfft);
     const size_t mb = (size_t)nrows * (size_t)blocksize, wb = sizeof(float2) * (size_t)nbands * nbeams * m;
     const size_t ob = sizeof(float2) * (size_t)nbands * nbeams * J * width;
-    const int8_t *d_m = matrix;
-    const float2 *d_w = (const float2 *)weights;
-    float2 *d_o = (float2 *)out;
-    if (mem_kind == CRSDR_MEM_HOST) {
-        OP_RESERVE(0, mb); OP_RESERVE(1, ob); OP_RESERVE(2, wb);
-        HIP_TRY(hipMemcpy(g_op.buf[0], matrix, mb, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(g_op.buf[2], weights, wb, hipMemcpyHostToDevice));
-        d_m = (const int8_t *)g_op.buf[0]; d_o = (float2 *)g_op.buf[1]; d_w = (const float2 *)g_op.buf[2];
-    } else if ((uintptr_t)d_m % 4 || (uintptr_t)d_o % 8 || (uintptr_t)d_w % 8) {
-        return fail(CRSDR_EINVAL, "subband_beamform: device matrix 4-byte, weights and out 8-byte aligned");
-    }
+    OpStage st(mem_kind);
+    const int8_t *d_m = (const int8_t *)st.in(0, matrix, mb, 4);
+    float2 *d_o = (float2 *)st.out(1, out, ob, 8);
+    const float2 *d_w = (const float2 *)st.in(2, weights, wb, 8);
+    if (st.rc) return st.rc;
+    if (st.misaligned) return fail(CRSDR_EINVAL, "subband_beamform: device matrix 4-byte, weights and out 8-byte aligned");
     int rc = CRSDR_OK;
     SUBBAND_DISPATCH(lg, rc = sbb_lds_limit(sbbeams::k_subband_beamform<LG>, "subband_beamform"));
     if (rc) return rc;
@@ -2643,9 +1938,8 @@ extern "C" int crsdr_subband_beamform(float *out, const int8_t *matrix, int nrow
     SUBBAND_DISPATCH(lg, hipLaunchKernelGGL(sbbeams::k_subband_beamform<LG>, grid, dim3(sbbeams::SBB_THREADS), sizeof(float2) * (size_t)points, 0, d_m, nrows, blocksize,
                                             first, nbands, width, window, d_w, nbeams, points, d_o));
     HIP_TRY(hipGetLastError());
-    if (mem_kind == CRSDR_MEM_HOST) HIP_TRY(hipMemcpy(out, d_o, ob, hipMemcpyDeviceToHost));
-    else HIP_TRY(hipDeviceSynchronize());
-    return CRSDR_OK;
+    st.back(out, d_o, ob);
+    return st.finish();
 }
 
 extern "C" int crsdr_beamform(float *out, const int8_t *matrix, int nrows, int blocksize, const float *weights, int nbeams, int mem_kind)
@@ -2653,28 +1947,20 @@ extern "C" int crsdr_beamform(float *out, const int8_t *matrix, int nrows, int b
     if (!out || !matrix || !weights || nrows < 2 || nrows - 1 > beams::MAX_M || blocksize < 32 || (blocksize % 32) || nbeams < 1 || nbeams > beams::MAX_BEAMS)
         return fail(CRSDR_EINVAL, "beamform: need out, matrix, weights, 2 <= nrows <= %d, blocksize %% 32 == 0, 1 <= nbeams <= %d", beams::MAX_M + 1,
                     beams::MAX_BEAMS);
-    if (mem_kind != CRSDR_MEM_HOST && mem_kind != CRSDR_MEM_DEVICE) return fail(CRSDR_EINVAL, "beamform: mem_kind = %d", mem_kind);
-    { int rc_ = require_device(); if (rc_) return rc_; }
-    std::lock_guard<std::mutex> lock_(g_op.mu);
+    OP_PROLOGUE_MEM("beamform", mem_kind);
     const size_t mb = (size_t)nrows * (size_t)blocksize, wb = sizeof(float2) * (size_t)nbeams * (size_t)(nrows - 1);
     const size_t ob = sizeof(float2) * (size_t)nbeams * (size_t)(blocksize / 2);
-    const int8_t *d_m = matrix;
-    const float2 *d_w = (const float2 *)weights;
-    float2 *d_o = (float2 *)out;
-    if (mem_kind == CRSDR_MEM_HOST) {
-        OP_RESERVE(0, mb); OP_RESERVE(1, ob); OP_RESERVE(2, wb);
-        HIP_TRY(hipMemcpy(g_op.buf[0], matrix, mb, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(g_op.buf[2], weights, wb, hipMemcpyHostToDevice));
-        d_m = (const int8_t *)g_op.buf[0]; d_o = (float2 *)g_op.buf[1]; d_w = (const float2 *)g_op.buf[2];
-    } else if ((uintptr_t)d_m % 4 || (uintptr_t)d_o % 16 || (uintptr_t)d_w % 8) {
-        return fail(CRSDR_EINVAL, "beamform: device matrix 4-byte, weights 8-byte, out 16-byte aligned");
-    }
+    OpStage st(mem_kind);
+    const int8_t *d_m = (const int8_t *)st.in(0, matrix, mb, 4);
+    float2 *d_o = (float2 *)st.out(1, out, ob, 16);
+    const float2 *d_w = (const float2 *)st.in(2, weights, wb, 8);
+    if (st.rc) return st.rc;
+    if (st.misaligned) return fail(CRSDR_EINVAL, "beamform: device matrix 4-byte, weights 8-byte, out 16-byte aligned");
     const dim3 grid((unsigned)((blocksize / 4 + beams::AP_THREADS - 1) / beams::AP_THREADS));
     BEAMS_DISPATCH(nbeams, hipLaunchKernelGGL(beams::k_beamform<NB>, grid, dim3(beams::AP_THREADS), 0, 0, d_m, nrows, blocksize, d_w, nbeams, d_o));
     HIP_TRY(hipGetLastError());
-    if (mem_kind == CRSDR_MEM_HOST) HIP_TRY(hipMemcpy(out, d_o, ob, hipMemcpyDeviceToHost));
-    else HIP_TRY(hipDeviceSynchronize());
-    return CRSDR_OK;
+    st.back(out, d_o, ob);
+    return st.finish();
 }
 
 #include "exchange_impl.hpp"

@@ -52,6 +52,59 @@ __host__ __device__ constexpr int subband_groups(int m, int N) { return (sb_bloc
 // float2 of partials per (estimate, slice)
 __host__ __device__ constexpr size_t subband_partial(int m, int N) { return (size_t)sb_blocks(m) * N * SB_UNIT; }
 
+// ---- the front end of a chunk, shared with subband_beams.hpp: both kernels stage the same spectra because they run these four ----
+// the workgroup's tables: tw[t] = W_N^t, win[t] = the window
+template <int LOG2N>
+__device__ __forceinline__ void sb_fill_tables(float2 *tw, float *win, int window)
+{
+    constexpr int N = 1 << LOG2N;
+    for (int t = threadIdx.x; t < N; t += SB_THREADS) {
+        double s, c;
+        sincospi(2.0 * (double)t / (double)N, &s, &c);
+        tw[t] = make_float2((float)c, (float)-s);
+        win[t] = window == WINDOW_HANN ? (float)(0.5 - 0.5 * c) : 1.0f;
+    }
+}
+// one 16-byte piece = 8 samples (I, Q int8) from sample n0 of the segment on -> dst[0 .. 7] = win[n0 + n] (I + jQ)
+__device__ __forceinline__ void sb_unpack_window(const uint4 wd, const float *win, int n0, float2 *dst)
+{
+    const uint32_t w4[4] = {wd.x, wd.y, wd.z, wd.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float w0 = win[n0 + 2 * k], w1 = win[n0 + 2 * k + 1];
+        dst[2 * k] = make_float2(w0 * (float)(int8_t)(w4[k] & 0xFF), w0 * (float)(int8_t)((w4[k] >> 8) & 0xFF));
+        dst[2 * k + 1] = make_float2(w1 * (float)(int8_t)((w4[k] >> 16) & 0xFF), w1 * (float)(int8_t)(w4[k] >> 24));
+    }
+}
+// a pass-1 item: the FA-point DFT of the points at p + k FB, then W_N^(n2 k1); p = the segment's row + n2
+template <int LOG2N>
+__device__ __forceinline__ void sb_pass1(float2 *p, const float2 *tw, int n2)
+{
+    constexpr int LA = sb_fa_log2(LOG2N), FA = 1 << LA, LB = LOG2N - LA, FB = 1 << LB;
+    float2 v[FA];
+#pragma unroll
+    for (int k = 0; k < FA; ++k) v[k] = p[k << LB];
+    dft<FA, -1>(v);
+    if constexpr (FB > 1) {
+#pragma unroll
+        for (int k = 1; k < FA; ++k) v[k] = cmul(v[k], tw[n2 * k]);
+    }
+#pragma unroll
+    for (int k = 0; k < FA; ++k) p[k << LB] = v[k];
+}
+// a pass-2 item: the FB-point DFT of the consecutive points at p = the segment's row + k1 FB
+template <int LOG2N>
+__device__ __forceinline__ void sb_pass2(float2 *p)
+{
+    constexpr int FB = 1 << (LOG2N - sb_fa_log2(LOG2N));
+    float2 v[FB];
+#pragma unroll
+    for (int k = 0; k < FB; ++k) v[k] = p[k];
+    dft<FB, -1>(v);
+#pragma unroll
+    for (int k = 0; k < FB; ++k) p[k] = v[k];
+}
+
 // Packet t of the batch at packets + t * packet_stride, its matrix [nrows][B] int8 at + matrix_off (4-byte aligned).  Estimate e stacks
 // packets e * frames .. + frames - 1.  grid (frames * spb, groups, nest): slice z = (frame z / spb, part z % spb of its J segments).
 //   partial [nest][S][blocks][N slots][8][8] float2 = sum_j conj(X'_a) X'_b over the slice, X' the transform of w (I + jQ)
@@ -78,12 +131,7 @@ __global__ __launch_bounds__(SB_THREADS) void k_doa_subband_cov(const int8_t *__
         while (left >= nb - bi) { left -= nb - bi; ++bi; }
         bj = bi + left;
     }
-    for (int t = tid; t < N; t += SB_THREADS) {
-        double s, c;
-        sincospi(2.0 * (double)t / (double)N, &s, &c);
-        tw[t] = make_float2((float)c, (float)-s);
-        win[t] = window == WINDOW_HANN ? (float)(0.5 - 0.5 * c) : 1.0f;
-    }
+    sb_fill_tables<LOG2N>(tw, win, window);
     if (tid == 0) {
         const int b_lo = (blockIdx.y * SB_THREADS) >> LOG2N, b_hi = min((blockIdx.y * SB_THREADS + SB_THREADS - 1) >> LOG2N, nblk - 1);
         unsigned long long mask = 0;
@@ -121,43 +169,18 @@ __global__ __launch_bounds__(SB_THREADS) void k_doa_subband_cov(const int8_t *__
             const int r = it / ppr, piece = it - r * ppr;
             const uint4 wd = cov::cov_load16(matrix + (size_t)(1 + rows[r]) * B + (size_t)s0 * 2 * N + (size_t)piece * 16);
             const int jj = (piece * 8) >> LOG2N, n0 = (piece * 8) & (N - 1);
-            float2 *dst = A + (jj * R + r) * N + n0;
-            const uint32_t w4[4] = {wd.x, wd.y, wd.z, wd.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float w0 = win[n0 + 2 * k], w1 = win[n0 + 2 * k + 1];
-                dst[2 * k] = make_float2(w0 * (float)(int8_t)(w4[k] & 0xFF), w0 * (float)(int8_t)((w4[k] >> 8) & 0xFF));
-                dst[2 * k + 1] = make_float2(w1 * (float)(int8_t)((w4[k] >> 16) & 0xFF), w1 * (float)(int8_t)(w4[k] >> 24));
-            }
+            sb_unpack_window(wd, win, n0, A + (jj * R + r) * N + n0);
         }
         __syncthreads();
         // pass 1: FA-point DFTs at stride FB, then W_N^(n2 k1)
         for (int it = tid; it < sc * R * FB; it += SB_THREADS) {
             const int n2 = it & (FB - 1);
-            float2 *p = A + (it >> LB) * N + n2;
-            float2 v[FA];
-#pragma unroll
-            for (int k = 0; k < FA; ++k) v[k] = p[k << LB];
-            dft<FA, -1>(v);
-            if constexpr (FB > 1) {
-#pragma unroll
-                for (int k = 1; k < FA; ++k) v[k] = cmul(v[k], tw[n2 * k]);
-            }
-#pragma unroll
-            for (int k = 0; k < FA; ++k) p[k << LB] = v[k];
+            sb_pass1<LOG2N>(A + (it >> LB) * N + n2, tw, n2);
         }
         __syncthreads();
         if constexpr (FB > 1) {
             // pass 2: FB-point DFTs of consecutive points
-            for (int it = tid; it < sc * R * FA; it += SB_THREADS) {
-                float2 *p = A + it * FB;
-                float2 v[FB];
-#pragma unroll
-                for (int k = 0; k < FB; ++k) v[k] = p[k];
-                dft<FB, -1>(v);
-#pragma unroll
-                for (int k = 0; k < FB; ++k) p[k] = v[k];
-            }
+            for (int it = tid; it < sc * R * FA; it += SB_THREADS) sb_pass2<LOG2N>(A + it * FB);
             __syncthreads();
         }
         if (active) {

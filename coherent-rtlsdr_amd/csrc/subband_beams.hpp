@@ -10,8 +10,8 @@
 //
 //   k_doa_subband_beam_apply  grid (K slice of segments, packet), 256 threads, dynamic LDS.  Per chunk of segments the workgroup loads
 //                             ALL m rows (16-byte loads of the int8 packets), applies the window and runs the N-point transform in
-//                             LDS exactly as k_doa_subband_cov stages it (the same passes, so the same spectra: restated here, the
-//                             covariance kernel is left alone) -- every row once per segment, where the covariance transforms a row
+//                             LDS with k_doa_subband_cov's own front end (subband.hpp's sb_fill_tables, sb_unpack_window, sb_pass1 and
+//                             sb_pass2: one statement of the passes, so the same spectra) -- every row once per segment, where the covariance transforms a row
 //                             once per unit group that touches it.  Then a thread owns one (band, segment, bin of the band) and
 //                             runs over the m channels once per group of up to four slots, the spectra and the band's weights
 //                             both from LDS, 4 fmaf per (channel, slot).
@@ -37,7 +37,7 @@
 namespace crsdr {
 namespace sbbeams {
 
-constexpr int SBB_THREADS = 256, SBB_MAX_ROWS = 64, SBB_MAX_BEAMS = 16;
+constexpr int SBB_THREADS = subband::SB_THREADS, SBB_MAX_ROWS = 64, SBB_MAX_BEAMS = 16;      // (the shared front end strides by SB_THREADS)
 constexpr int SBB_LDS_POINTS = 5120;       // float2 of spectra per chunk (40 KiB) wherever a segment of all rows is smaller
 constexpr int SBB_WEIGHT_POINTS = 2048;    // float2 of staged weights (16 KiB): at least one band (64 rows x 16 slots = 1024)
 
@@ -114,12 +114,7 @@ __device__ __forceinline__ void subband_beam_slice(const int8_t *__restrict__ ma
     const int tid = threadIdx.x, J = B / (2 * N), stride = sbb_seg_stride(m, N);
     const int SC = min(lds_points / stride, seg_hi - seg_lo);
     const int nbp = sbb_padded(nbeams), bg_max = min(nbands, SBB_WEIGHT_POINTS / (m * nbp));
-    for (int t = tid; t < N; t += SBB_THREADS) {
-        double s, c;
-        sincospi(2.0 * (double)t / (double)N, &s, &c);
-        tw[t] = make_float2((float)c, (float)-s);
-        win[t] = window == subband::WINDOW_HANN ? (float)(0.5 - 0.5 * c) : 1.0f;
-    }
+    subband::sb_fill_tables<LOG2N>(tw, win, window);
     // c_w / 127: 1 / (127 sqrt(N sum w^2)), sum w^2 = N (rect), 3 N / 8 (periodic Hann)
     const float scale = (float)(1.0 / (127.0 * sqrt((double)N * (window == subband::WINDOW_HANN ? 0.375 * (double)N : (double)N))));
     // bands g0 .. g0 + bg - 1 -> wl, slots past nbeams zero
@@ -140,43 +135,20 @@ __device__ __forceinline__ void subband_beam_slice(const int8_t *__restrict__ ma
             const int r = it / ppr, piece = it - r * ppr;
             const uint4 wd = cov::cov_load16(matrix + (size_t)(1 + r) * B + (size_t)s0 * 2 * N + (size_t)piece * 16);
             const int jj = (piece * 8) >> LOG2N, n0 = (piece * 8) & (N - 1);
-            float2 *dst = A + jj * stride + r * N + n0;
-            const uint32_t w4[4] = {wd.x, wd.y, wd.z, wd.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float w0 = win[n0 + 2 * k], w1 = win[n0 + 2 * k + 1];
-                dst[2 * k] = make_float2(w0 * (float)(int8_t)(w4[k] & 0xFF), w0 * (float)(int8_t)((w4[k] >> 8) & 0xFF));
-                dst[2 * k + 1] = make_float2(w1 * (float)(int8_t)((w4[k] >> 16) & 0xFF), w1 * (float)(int8_t)(w4[k] >> 24));
-            }
+            subband::sb_unpack_window(wd, win, n0, A + jj * stride + r * N + n0);
         }
         __syncthreads();
         // pass 1: FA-point DFTs at stride FB, then W_N^(n2 k1)
         for (int it = tid; it < sc * m * FB; it += SBB_THREADS) {
             const int n2 = it & (FB - 1), sr = it >> LB, jj = sr / m;
-            float2 *p = A + jj * stride + (sr - jj * m) * N + n2;
-            float2 v[FA];
-#pragma unroll
-            for (int k = 0; k < FA; ++k) v[k] = p[k << LB];
-            dft<FA, -1>(v);
-            if constexpr (FB > 1) {
-#pragma unroll
-                for (int k = 1; k < FA; ++k) v[k] = cmul(v[k], tw[n2 * k]);
-            }
-#pragma unroll
-            for (int k = 0; k < FA; ++k) p[k << LB] = v[k];
+            subband::sb_pass1<LOG2N>(A + jj * stride + (sr - jj * m) * N + n2, tw, n2);
         }
         __syncthreads();
         if constexpr (FB > 1) {
             // pass 2: FB-point DFTs of consecutive points
             for (int it = tid; it < sc * m * FA; it += SBB_THREADS) {
                 const int k1 = it & (FA - 1), sr = it >> LA, jj = sr / m;
-                float2 *p = A + jj * stride + (sr - jj * m) * N + k1 * FB;
-                float2 v[FB];
-#pragma unroll
-                for (int k = 0; k < FB; ++k) v[k] = p[k];
-                dft<FB, -1>(v);
-#pragma unroll
-                for (int k = 0; k < FB; ++k) p[k] = v[k];
+                subband::sb_pass2<LOG2N>(A + jj * stride + (sr - jj * m) * N + k1 * FB);
             }
             __syncthreads();
         }
