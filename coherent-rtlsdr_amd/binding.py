@@ -42,11 +42,13 @@ ABI_SYMBOLS = [
     "crsdr_smooth_covariance", "crsdr_source_order",
     "crsdr_doa_set_subbands", "crsdr_doa_fetch_subbands", "crsdr_doa_subband_buffers", "crsdr_subband_covariance",
     "crsdr_doa_set_subband_beams", "crsdr_doa_fetch_subband_beams", "crsdr_doa_subband_beam_buffers", "crsdr_subband_beamform",
+    "crsdr_doa_set_spectrum", "crsdr_spectrum2d",
 ]
 DOA_KEEP_SPECTRUM, DOA_KEEP_RXX = 1, 2
 BEAM_OFF, BEAM_CONVENTIONAL, BEAM_MVDR = 0, 1, 2
 SMOOTH_FB = 1
 ORDER_OFF, ORDER_MDL, ORDER_AIC = 0, 1, 2
+SPECTRUM_MUSIC, SPECTRUM_BARTLETT, SPECTRUM_CAPON = 0, 1, 2
 WINDOW_RECT, WINDOW_HANN = 0, 1
 XCHG_STAGED, XCHG_INPLACE = 0, 1
 EXCHANGE_ID_BYTES = 128
@@ -198,6 +200,9 @@ def lib():
         L.crsdr_doa_fetch_subband_beams.argtypes = [vp, f32p, f32p, f32p]
         L.crsdr_doa_subband_beam_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int)]
         L.crsdr_subband_beamform.argtypes = [f32p, i8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_int]
+    if hasattr(L, "crsdr_doa_set_spectrum"):         # (likewise: an older build has the MUSIC map alone)
+        L.crsdr_doa_set_spectrum.argtypes = [vp, C.c_int, C.c_float]
+        L.crsdr_spectrum2d.argtypes = [f32p, f32p, f32p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     _lib = L
     return L
 
@@ -358,6 +363,27 @@ def pmusic2d(vec, k, d, mx, my, ncx=100, ncy=100):
     _check(lib().crsdr_pmusic2d(_p(pm, C.c_float), _p(v.view(np.float32), C.c_float), M, int(k), C.c_float(d), int(mx), int(my),
                                 int(ncx), int(ncy), MEM_HOST))
     return pm
+
+
+def spectrum2d(vec, sv, kind, d, mx, my, ncx=100, ncy=100, loading=1e-2):
+    """crsdr_spectrum2d: the Bartlett (SPECTRUM_BARTLETT) or Capon (SPECTRUM_CAPON, with its diagonal loading) power map
+    pm [ncx][ncy] of the subspace (vec, sv) as noisesubspace returns it, over the grid and with the steering vector of pmusic2d."""
+    v = np.ascontiguousarray(vec, dtype=np.complex64)
+    s = np.ascontiguousarray(sv, dtype=np.float32)
+    M = v.shape[0]
+    if v.shape != (M, M) or s.shape != (M,):
+        raise ValueError("vec must be [m][m] and sv [m]")
+    pm = np.empty((max(ncx, 0), max(ncy, 0)), dtype=np.float32)
+    _check(lib().crsdr_spectrum2d(_p(pm, C.c_float), _p(v.view(np.float32), C.c_float), _p(s, C.c_float), M, int(kind), C.c_float(loading),
+                                  C.c_float(d), int(mx), int(my), int(ncx), int(ncy), MEM_HOST))
+    return pm
+
+
+def spectrum2d_device(pm_ptr: int, vec_ptr: int, sv_ptr: int, m, kind, d, mx, my, ncx=100, ncy=100, loading=1e-2):
+    """Same on device memory (all three pointers on the current device); returns after the kernel finished."""
+    f32p = C.POINTER(C.c_float)
+    _check(lib().crsdr_spectrum2d(C.cast(C.c_void_p(int(pm_ptr)), f32p), C.cast(C.c_void_p(int(vec_ptr)), f32p), C.cast(C.c_void_p(int(sv_ptr)), f32p),
+                                  int(m), int(kind), C.c_float(loading), C.c_float(d), int(mx), int(my), int(ncx), int(ncy), MEM_DEVICE))
 
 
 def beamform(matrix, weights):
@@ -879,6 +905,12 @@ class Doa:
         ptrs, nb = [C.c_void_p() for _ in range(3)], C.c_int(0)
         _check(lib().crsdr_doa_subband_beam_buffers(self._h, *[C.byref(p) for p in ptrs], C.byref(nb)))
         return dict(zip(("weights", "power", "beams"), [p.value for p in ptrs]), nbeams=nb.value)
+
+    def set_spectrum(self, kind: int, loading: float = 1e-2):
+        """crsdr_doa_set_spectrum: from the next submit on the scan computes the Bartlett or the Capon power map (SPECTRUM_BARTLETT,
+        SPECTRUM_CAPON with its diagonal loading) in place of the MUSIC pseudo-spectrum (SPECTRUM_MUSIC: back to it), and pm, peak, the
+        directions and the beams that follow them work on that map.  Waits for the device if a submit was made; what it left is gone."""
+        _check(lib().crsdr_doa_set_spectrum(self._h, int(kind), C.c_float(loading)))
 
     def last_launches(self) -> int:
         return self._last()[1]

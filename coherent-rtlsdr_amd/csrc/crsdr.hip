@@ -8,6 +8,7 @@
 #include "beams.hpp"
 #include "subband.hpp"
 #include "subband_beams.hpp"
+#include "spectrum.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -172,6 +173,15 @@ static int subband_args_ok(const char *who, int blocksize, int nfft, int first, 
     if (nbands < 1 || width < 1 || (long long)nbands * width > nfft)
         return fail(CRSDR_EINVAL, "%s: %d bands of %d bins (nbands >= 1, width >= 1, nbands * width <= nfft = %d)", who, nbands, width, nfft);
     if (window != CRSDR_WINDOW_RECT && window != CRSDR_WINDOW_HANN) return fail(CRSDR_EINVAL, "%s: window = %d", who, window);
+    return CRSDR_OK;
+}
+
+// kind of crsdr_doa_set_spectrum (music_ok) / crsdr_spectrum2d, and CAPON's loading
+static int spectrum_args_ok(const char *who, int kind, float loading, bool music_ok)
+{
+    if (kind != CRSDR_SPECTRUM_BARTLETT && kind != CRSDR_SPECTRUM_CAPON && !(music_ok && kind == CRSDR_SPECTRUM_MUSIC))
+        return fail(CRSDR_EINVAL, "%s: kind = %d", who, kind);
+    if (kind == CRSDR_SPECTRUM_CAPON && !(loading >= 1e-6f && loading <= 1.0f)) return fail(CRSDR_EINVAL, "%s: loading = %g (1e-6..1)", who, (double)loading);
     return CRSDR_OK;
 }
 
@@ -1939,6 +1949,29 @@ extern "C" int crsdr_subband_beamform(float *out, const int8_t *matrix, int nrow
                                             first, nbands, width, window, d_w, nbeams, points, d_o));
     HIP_TRY(hipGetLastError());
     st.back(out, d_o, ob);
+    return st.finish();
+}
+
+extern "C" int crsdr_spectrum2d(float *pm, const float *vec, const float *sv, int m, int kind, float loading, float d, int mx, int my, int ncx, int ncy,
+                                int mem_kind)
+{
+    if (!pm || !vec || !sv || m < 2 || m > music::MAX_M || mx < 1 || my < 1 || (long long)mx * my != m || ncx < 1 || ncy < 1 || (long long)ncx * ncy > (1 << 24))
+        return fail(CRSDR_EINVAL, "spectrum2d: need pm, vec, sv, m = mx*my in [2, %d], grid <= 2^24 points", music::MAX_M);
+    { const int rc_ = spectrum_args_ok("spectrum2d", kind, loading, false); if (rc_) return rc_; }
+    OP_PROLOGUE_MEM("spectrum2d", mem_kind);
+    const size_t mm = sizeof(float2) * (size_t)m * m, pb = sizeof(float) * (size_t)ncx * ncy;
+    OpStage st(mem_kind);
+    const float2 *d_v = (const float2 *)st.in(0, vec, mm, 8);
+    float *d_p = (float *)st.out(1, pm, pb, 4);
+    const float *d_s = (const float *)st.in(2, sv, sizeof(float) * (size_t)m, 4);
+    if (st.rc) return st.rc;
+    if (st.misaligned) return fail(CRSDR_EINVAL, "spectrum2d: device vec 8-byte, sv and pm 4-byte aligned");
+    const size_t lds = spectrum::lds_bytes(m);           // 65 792 bytes at m = 64: above the default limit
+    HIP_TRY(hipFuncSetAttribute((const void *)spectrum::k_spectrum2d, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const unsigned blocks = (unsigned)(((size_t)ncx * ncy + spectrum::PT - 1) / spectrum::PT);
+    hipLaunchKernelGGL(spectrum::k_spectrum2d, dim3(blocks), dim3(spectrum::PT), lds, 0, d_v, d_s, m, kind, loading, d, mx, my, ncx, ncy, d_p);
+    HIP_TRY(hipGetLastError());
+    st.back(pm, d_p, pb);
     return st.finish();
 }
 

@@ -8,7 +8,8 @@
 //      launch each (smooth.hpp): behind the reducer, and between the subspace and the scan.  crsdr_doa_set_subbands replaces the two
 //      covariance launches by subband.hpp's (one covariance per estimate and frequency band) and reallocates every per-matrix buffer
 //      for (max_batch / frames) * nbands matrices: the launches behind it then run over that many.  crsdr_doa_set_subband_beams on top of
-//      it: the beam weights per (estimate, band) and subband_beams.hpp's apply kernel on the rows' band spectra.
+//      it: the beam weights per (estimate, band) and subband_beams.hpp's apply kernel on the rows' band spectra.  crsdr_doa_set_spectrum
+//      replaces the scan's kernel by spectrum.hpp's (the Bartlett or the Capon map): the same launches, nothing allocated.
 //
 // Shape of the host code.  A feature is a sub-struct of crsdr_doa: its parameters and its device buffers, each buffer owned by a
 // DevBuf, so that "off" is an assignment of {} and nothing is freed by a list kept by hand.  What the last submit left (DoaLast) is
@@ -127,6 +128,8 @@ struct crsdr_doa {
     DoaBeams beams;
     DoaSmooth smooth;
     DoaOrder order;
+    int spectrum = CRSDR_SPECTRUM_MUSIC;           // crsdr_doa_set_spectrum: the map the scan computes, and CAPON's loading
+    float spectrum_loading = 0.f;
     DoaLast last;
     // what the subspace, the order, the scan and the peaks work on: the sub-arrays while smoothing is on, the array otherwise
     int sx() const { return smooth.on ? smooth.sx : mx; }
@@ -306,10 +309,17 @@ static int doa_stage_scan(crsdr_doa *q, DoaRun &r)
                                q->order.kmax, q->order.k.p, q->order.values.p);
         if (rc) return rc;
     }
-    // the counts in place of k: the LDS of the most noise vectors an estimate can have, M - kmin
-    const auto scan = q->order.crit ? doa::k_doa_scan<true> : doa::k_doa_scan<false>;
-    const int rc = doa_run(r, scan, grid, dim3(music::PT), sizeof(float2) * ((size_t)M * (M - (q->order.crit ? q->order.kmin : q->k)) + (size_t)M * music::PT),
-                           (const float2 *)q->mat.vec, M, q->k, q->d, q->sx(), q->sy(), q->ncx, q->ncy, r.pm, q->mat.wgbest.p, (const int32_t *)q->order.k);
+    int rc;
+    if (q->spectrum != CRSDR_SPECTRUM_MUSIC) {
+        // a power map in the scan's place: every column of vec weighted by sv, whatever k or the counts say
+        rc = doa_run(r, spectrum::k_doa_spectrum, grid, dim3(spectrum::PT), spectrum::lds_bytes(M), (const float2 *)q->mat.vec, (const float *)q->mat.sv, M, q->spectrum,
+                     q->spectrum_loading, q->d, q->sx(), q->sy(), q->ncx, q->ncy, r.pm, q->mat.wgbest.p);
+    } else {
+        // the counts in place of k: the LDS of the most noise vectors an estimate can have, M - kmin
+        const auto scan = q->order.crit ? doa::k_doa_scan<true> : doa::k_doa_scan<false>;
+        rc = doa_run(r, scan, grid, dim3(music::PT), sizeof(float2) * ((size_t)M * (M - (q->order.crit ? q->order.kmin : q->k)) + (size_t)M * music::PT),
+                     (const float2 *)q->mat.vec, M, q->k, q->d, q->sx(), q->sy(), q->ncx, q->ncy, r.pm, q->mat.wgbest.p, (const int32_t *)q->order.k);
+    }
     if (rc) return rc;
     return doa_run(r, doa::k_doa_peak, dim3(r.nest), dim3(256), 0, (const unsigned long long *)q->mat.wgbest, q->nwg, q->ncy, q->mat.peak.p, q->mat.peakv.p);
 }
@@ -362,7 +372,7 @@ static int doa_launch(crsdr_doa *q, const int8_t *packets, size_t packet_stride,
 }
 
 // The kernels' dynamic LDS limits are function attributes, shared by every live object: each create sets every limit the engine's
-// kernels can need to the most any object can ask for (subspace and scan: m = 64, one signal vector; local peaks: the largest radius;
+// kernels can need to the most any object can ask for (subspace and scan: m = 64, one signal vector; power maps: m = 64; local peaks: the largest radius;
 // band beams: 64 rows of 256 points), so that a small object created after a large one cannot lower a limit under it, and no setter
 // has to think of them.  (The per-op calls set their own kernels' limits.)
 static int doa_lds_limits()
@@ -374,6 +384,7 @@ static int doa_lds_limits()
     HIP_TRY(limit((const void *)doa::k_doa_subspace, sub));
     HIP_TRY(limit(kDoaPlainScan, scan));
     HIP_TRY(limit((const void *)doa::k_doa_scan<true>, scan));
+    HIP_TRY(limit((const void *)spectrum::k_doa_spectrum, spectrum::lds_bytes(music::MAX_M)));
     HIP_TRY(limit((const void *)doa::k_doa_local_peaks, doa::lp_lds(doa::MAX_RADIUS)));
     for (int lg = subband::SB_MIN_LOG2; lg <= subband::SB_MAX_LOG2; ++lg) SUBBAND_DISPATCH(lg, HIP_TRY(limit((const void *)sbbeams::k_doa_subband_beam_apply<LG>, sbb)));
     return CRSDR_OK;
@@ -591,6 +602,18 @@ extern "C" int crsdr_doa_fetch_subband_beams(crsdr_doa *q, float *weights, float
 { return doa_fetch_beams(q, "doa_fetch_subband_beams", true, weights, power, beams); }
 extern "C" int crsdr_doa_subband_beam_buffers(crsdr_doa *q, void **weights, void **power, void **beams, int *nbeams)
 { return doa_beam_buffers(q, "doa_subband_beam_buffers", true, weights, power, beams, nbeams); }
+
+// ---- the map the scan computes (spectrum.hpp) ----
+extern "C" int crsdr_doa_set_spectrum(crsdr_doa *q, int kind, float loading)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_set_spectrum: NULL doa");
+    { const int rc = spectrum_args_ok("doa_set_spectrum", kind, loading, true); if (rc) return rc; }
+    { const int rc = doa_quiesce(q); if (rc) return rc; }
+    // pm, the peak, the directions and the beams toward them all change their meaning: nothing the last submit left stays
+    q->last.ran = 0;
+    q->spectrum = kind; q->spectrum_loading = kind == CRSDR_SPECTRUM_CAPON ? loading : 0.f;
+    return CRSDR_OK;
+}
 
 // ---- spatial smoothing and the source count (smooth.hpp) ----
 extern "C" int crsdr_doa_set_smoothing(crsdr_doa *q, int sx, int sy, uint32_t flags)

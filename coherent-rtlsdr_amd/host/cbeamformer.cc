@@ -36,6 +36,17 @@ int pmusic2dvec(const cmatrix &U, int M, int K, float d, int Mx, int My, int Cx,
     return rc;
 }
 
+int pspectrum2dvec(const cmatrix &U, const std::vector<float> &S, int M, int kind, float loading, float d, int Mx, int My, int Cx, int Cy,
+                   std::vector<float> &pm)
+{
+    // (the sizes that decide the allocation below are checked here, ahead of it; the rest by crsdr_spectrum2d)
+    if (M < 0 || U.size() != (size_t)M * M || S.size() != (size_t)M || Cx < 1 || Cy < 1 || (long long)Cx * Cy > (1 << 24)) return CRSDR_EINVAL;
+    pm.assign((size_t)Cx * Cy, 0.f);
+    int rc = crsdr_spectrum2d(pm.data(), reinterpret_cast<const float *>(U.data()), S.data(), M, kind, loading, d, Mx, My, Cx, Cy, CRSDR_MEM_HOST);
+    if (rc) std::fprintf(stderr, "pspectrum2dvec: %s\n", crsdr_last_error());
+    return rc;
+}
+
 batch::batch(int nrows, int blocksize, int max_batch, int K, int frames, bool keep_spectrum, float d, int Mx, int My, int Cx, int Cy, int device)
     : m(nrows - 1), ms(nrows - 1), cx(Cx), cy(Cy), half(blocksize / 2), nframes(frames > 0 ? frames : 1), keep(keep_spectrum)
 {
@@ -101,6 +112,13 @@ int batch::set_subbands(int nfft, int first, int count, int width, int window)
 {
     int rc = doa ? crsdr_doa_set_subbands(doa, nfft, first, count, width, window) : CRSDR_ESTATE;
     if (!rc) { nbands = nfft ? count : 0; band_j = nfft ? half / nfft : 0; band_width = nfft ? width : 0; }
+    if (rc && doa) std::fprintf(stderr, "cbeamformer::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::set_spectrum(int kind, float loading)
+{
+    int rc = doa ? crsdr_doa_set_spectrum(doa, kind, loading) : CRSDR_ESTATE;
     if (rc && doa) std::fprintf(stderr, "cbeamformer::batch: %s\n", crsdr_last_error());
     return rc;
 }

@@ -24,6 +24,10 @@ int covariance(const int8_t *packet, cmatrix &Rxx, int &M);
 int noisesubspace(const cmatrix &Rxx, int M, cmatrix &U, std::vector<float> *S = nullptr);
 // pm [Cx][Cy] row-major, not normalised
 int pmusic2dvec(const cmatrix &U, int M, int K, float d, int Mx, int My, int Cx, int Cy, std::vector<float> &pm);
+// the same grid as a power map in units of ((I + jQ) / 127)^2 (crsdr_spectrum2d): kind CRSDR_SPECTRUM_BARTLETT, a^H R a / M^2, or
+// CRSDR_SPECTRUM_CAPON, 1 / a^H (R + loading S[0] I)^-1 a, from all of U and S as noisesubspace returns them.  No source count.
+int pspectrum2dvec(const cmatrix &U, const std::vector<float> &S, int M, int kind, float loading, float d, int Mx, int My, int Cx, int Cy,
+                   std::vector<float> &pm);
 
 // The three steps above for a whole batch of packets where the engine's plan left them on the device (crsdr_doa): one submit, no
 // host work per packet, a direction per `frames` consecutive blocks.  submit() only enqueues (on the plan's stream, behind the batch
@@ -65,6 +69,11 @@ public:
     // filled.  nfft = 0: off.  Before set_peaks, set_smoothing and set_order (refused while one of them or beams are on; the beams of
     // the bands are set_subband_beams).
     int set_subbands(int nfft, int first = 0, int count = 1, int width = 1, int window = CRSDR_WINDOW_RECT);
+    // from the next submit on, the scan computes the Bartlett or the Capon power map (crsdr_doa_set_spectrum: kind CRSDR_SPECTRUM_*,
+    // loading: Capon's diagonal loading as a fraction of the largest singular value) in place of the MUSIC pseudo-spectrum: pm, peak,
+    // peak_value, the directions and the beams that follow them are then that map's, K and the source counts are not used.
+    // CRSDR_SPECTRUM_MUSIC: back.  Any time; discards the last submit's results.
+    int set_spectrum(int kind, float loading = 1e-2f);
     int bands() const { return nbands; }
     std::vector<float> band_power;                   // with set_subbands: [estimates]: Re trace(R_band) / M, the squelch of a band's direction
     // with set_subbands on: from the next submit on, a beam per band toward every direction of that band (crsdr_doa_set_subband_beams;

@@ -57,7 +57,7 @@ int main(int argc, char **argv)
     bool run_cdsp = false, servo = false, threads = false, music = false, servo_table = false, bench = false, batch_parity = false, batched = false;
     int batch = 16, engine_delay_ms = 0, pace_us_arg = -1, peaks = 0, peak_radius = 1, beam_mode = CRSDR_BEAM_OFF, band_beam_mode = CRSDR_BEAM_OFF;
     float beam_loading = 1e-2f;
-    int smooth_x = 0, smooth_y = 0, order_crit = CRSDR_ORDER_OFF;
+    int smooth_x = 0, smooth_y = 0, order_crit = CRSDR_ORDER_OFF, spectrum_kind = CRSDR_SPECTRUM_MUSIC;
     bool smooth_fb = false;
     int sb_nfft = 0, sb_first = 0, sb_count = 1, sb_width = 1, sb_window = CRSDR_WINDOW_RECT;
     bool engine_batches = false;
@@ -117,6 +117,12 @@ int main(int argc, char **argv)
         else if (a == "--band-beams" && i + 1 < argc) {
             const std::string m = argv[++i];
             band_beam_mode = m == "conventional" ? CRSDR_BEAM_CONVENTIONAL : m == "mvdr" ? CRSDR_BEAM_MVDR : -1;
+        }
+        // with --bench --music: the map the scan computes (crsdr_doa_set_spectrum); the two power maps print their peak values in dB
+        // (of full scale, ((I + jQ) / 127)^2 = 1) and take --loading as Capon's diagonal loading
+        else if (a == "--spectrum" && i + 1 < argc) {
+            const std::string m = argv[++i];
+            spectrum_kind = m == "music" ? CRSDR_SPECTRUM_MUSIC : m == "bartlett" ? CRSDR_SPECTRUM_BARTLETT : m == "capon" ? CRSDR_SPECTRUM_CAPON : -1;
         }
         else if (a == "--loading" && i + 1 < argc) beam_loading = (float)std::atof(argv[++i]);
         else if (a == "--batch-parity") batch_parity = true;   // the batched engine's packets == step()'s packets, bit for bit (own read counters, a masked row)
@@ -328,6 +334,10 @@ int main(int argc, char **argv)
                 if (doa->set_smoothing(sx, sy, smooth_fb)) { std::printf("doa: --smooth %dx%d%s refused\nDEMO FAILED\n", sx, sy, smooth_fb ? " --fb" : ""); return 1; }
             }
             if (order_crit && doa->set_order(order_crit)) { std::printf("doa: --order (mdl|aic) refused\nDEMO FAILED\n"); return 1; }
+            if (spectrum_kind && doa->set_spectrum(spectrum_kind, beam_loading)) {
+                std::printf("doa: --spectrum (music|bartlett|capon) --loading %g refused\nDEMO FAILED\n", (double)beam_loading);
+                return 1;
+            }
             if (peaks && doa->set_peaks(peaks, peak_radius)) { std::printf("doa: --peaks %d --peak-radius %d refused\nDEMO FAILED\n", peaks, peak_radius); return 1; }
             if (beam_mode && doa->set_beams(beam_mode, beam_loading)) { std::printf("doa: --beams (conventional|mvdr) --loading %g refused\nDEMO FAILED\n", (double)beam_loading); return 1; }
             if (band_beam_mode && (!sb_nfft || doa->set_subband_beams(band_beam_mode, beam_loading))) {
@@ -366,6 +376,7 @@ int main(int argc, char **argv)
                 for (int i = 0; i < doa->found[0]; ++i) {
                     std::snprintf(buf, sizeof(buf), " (%d, %d)", doa->directions[2 * i], doa->directions[2 * i + 1]);
                     dirs += buf;
+                    if (spectrum_kind) { std::snprintf(buf, sizeof(buf), " value %.2f dB", 10.0 * std::log10((double)doa->direction_values[i])); dirs += buf; }
                     if (beam_mode) { std::snprintf(buf, sizeof(buf), " power %.4g", (double)doa->beam_power[i]); dirs += buf; }
                 }
                 std::printf("doa: batch %d: %d estimates, peaks of the first:%s\n", b, n, dirs.c_str());
@@ -373,6 +384,7 @@ int main(int argc, char **argv)
             }
             int broadside = 0;
             for (int e = 0; e < n; ++e) broadside += doa->peak[2 * e] == 50 && doa->peak[2 * e + 1] == 50;
+            if (spectrum_kind) std::printf("doa: batch %d: peak value of the first direction %.2f dB\n", b, 10.0 * std::log10((double)doa->peak_value[0]));
             if (beam_mode) std::printf("doa: batch %d: beam power of the first direction %.4g\n", b, (double)doa->beam_power[0]);
             std::printf("doa: batch %d: %d directions, first (%d, %d), last (%d, %d), %d at broadside\n", b, n, doa->peak[0], doa->peak[1], doa->peak[2 * n - 2],
                         doa->peak[2 * n - 1], broadside);

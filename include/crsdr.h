@@ -684,6 +684,43 @@ int crsdr_doa_subband_beam_buffers(crsdr_doa *doa, void **weights, void **power,
 int crsdr_subband_beamform(float *out, const int8_t *matrix, int nrows, int blocksize, int nfft, int first, int nbands, int width, int window,
                            const float *weights, int nbeams, int mem_kind);
 
+/* Two power maps beside the MUSIC pseudo-spectrum, over the same grid: MUSIC needs the number of sources beforehand, has no unit and
+ * cannot say how strong an arrival is; these are in power units ((I + jQ) / 127)^2 and use no source count.
+ *   M       the size of the subspace: m, or ms while crsdr_doa_set_smoothing runs true sub-arrays (the array is then sx x sy)
+ *   v_r     column r of the published fp32 vec, sv the published fp32 values
+ *   a       the steering vector of crsdr_pmusic2d at alpha = cx pi / ncx, beta = cy pi / ncy, evaluated in fp32 with that call's
+ *           expressions in their order: a grid point is the same direction in all three maps
+ *   y_r     = v_r^H a = sum_i conj(vec[i][r]) a[i], for ALL r = 0 .. M-1, fp32
+ *   w_r     fp64 from the fp32 sv, rounded once to fp32 (as the beams' power is formed):
+ *           CRSDR_SPECTRUM_BARTLETT  w_r = sv[r] / M^2
+ *           CRSDR_SPECTRUM_CAPON     delta = (double)loading * sv[0],  w_r = 1 / (sv[r] + delta)
+ *   S       = sum_r w_r |y_r|^2 in fp32, r ascending
+ *   pm      BARTLETT: S = a^H R a / M^2, the power a delay-and-sum beam toward the grid point receives (crsdr_doa_set_beams'
+ *           conventional power); CAPON: 1 / S = 1 / a^H (R + delta I)^-1 a, the MVDR beam's power: adaptive side-lobe suppression,
+ *           close sources resolved.
+ * sv[0] == 0 (an all-zero estimate): pm = 0 at every grid point, for both kinds.  Otherwise w_r >= 0 with w_0 > 0: CAPON has every w_r > 0 and
+ * sum_r |y_r|^2 = M, so S > 0 and 1 / S is finite; BARTLETT on a rank-deficient estimate has w_r = 0 behind the rank, and S = 0 where a is
+ * orthogonal to the signal columns.  Neither kind gives a negative or NaN pm from finite input, and the keys of peak and crsdr_doa_set_peaks order it like the value.
+ * loading in [1e-6, 1] for CAPON (the range of crsdr_doa_set_beams), ignored otherwise.
+ *
+ * crsdr_doa_set_spectrum: from the next submit on the scan computes the chosen map in place of MUSIC's, and everything behind it works
+ * on that map: pm (CRSDR_DOA_KEEP_SPECTRUM), peak / peak_value, the local maxima of crsdr_doa_set_peaks and their values, the beams and
+ * band beams that follow the directions, limit_directions.  Smoothing and subbands feed it as they feed MUSIC: per (estimate, band),
+ * with the sub-arrays' M.  desc.k and crsdr_doa_set_order's k_e are ignored by BARTLETT and CAPON (the order is still computed, fetched
+ * and applied to found under limit_directions).  The scan's kernel is replaced, not added: a submit issues the launches it issued before.
+ * CRSDR_SPECTRUM_MUSIC restores the MUSIC scan, bit for bit.  Any time: waits for the device if a submit was made and discards what it
+ * left (every fetch function returns CRSDR_ESTATE until the next submit); allocates nothing, and no other setter refuses or is refused
+ * because of it.  CRSDR_EINVAL for a bad kind, or for loading outside the range with CAPON. */
+enum { CRSDR_SPECTRUM_MUSIC = 0, CRSDR_SPECTRUM_BARTLETT = 1, CRSDR_SPECTRUM_CAPON = 2 };
+int crsdr_doa_set_spectrum(crsdr_doa *doa, int kind, float loading);
+
+/* The per-op form: the same device function as the batched scan, bit for bit.  BARTLETT and CAPON only (MUSIC is crsdr_pmusic2d).
+ *   vec [m][m][2] and sv [m] as crsdr_noisesubspace writes them, 2 <= m = mx * my <= 64;  pm [ncx][ncy] float row-major
+ * Every argument is checked before a device is touched.  mem_kind: CRSDR_MEM_HOST (copied) or CRSDR_MEM_DEVICE (all three on the
+ * device: vec 8-byte, sv and pm 4-byte aligned). */
+int crsdr_spectrum2d(float *pm, const float *vec, const float *sv, int m, int kind, float loading, float d, int mx, int my, int ncx, int ncy,
+                     int mem_kind);
+
 #ifdef __cplusplus
 }
 #endif

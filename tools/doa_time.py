@@ -20,6 +20,9 @@
       submit + a fetch of the band beams' power only (weights and beams stay on the device), and
   (w) what a caller without them does to form the bands' beams on the host: the same object without the beams, submit + directions,
       then the 64 packets and vec of every band matrix copied to page-locked host memory (before any host arithmetic).
+  (m) with --spectrum bartlett|capon (--loading X): crsdr_doa_set_spectrum, then the (b) submit + peaks: the power map in the scan's place,
+      against the MUSIC submit (b) of the same build and, with --doa-lib, of another (lib:b) in the same alternation.
+--array MXxMY runs everything on another array than the 7 x 3 one (8x8: M = 64, the largest).
 
 --runs runs of each, alternating a, b, c in one session (two worker processes, both alive throughout); medians and ranges.
 --doa-lib LIB starts a second doa worker on another build (e.g. the parent commit's) through CRSDR_LIB and times its (b) and (c) in
@@ -27,12 +30,14 @@ the same alternation, reported as lib:b and lib:c.  --reps N: every (b), (c), (p
 Also: what crsdr_doa_submit_plan + the peak fetch add to a 22-row, T = 64 plan batch (plan.submit + sync against
 plan.submit + doa.submit_plan + fetch).  --json FILE keeps the record; --once MODE runs three submit + fetch and exits (for a kernel trace): b, c, p, q as above, q64 = the
 beams at their largest shape (8 x 8 array, 16 slots: 65 rows x 16384, 64 blocks), s = --smooth / --fb / --order as given, all on one object,
-u = --subbands / --window as given, v = u with --peaks and --band-beams as given."""
+u = --subbands / --window as given, v = u with --peaks and --band-beams as given, m = --spectrum as given."""
 import argparse, importlib, json, os, subprocess, sys, time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NROWS, B, T, M = 22, 16384, 64, 21
+ARRAY = (7, 3)                             # --array: (mx, my), NROWS = 1 + mx my, M = mx my
+SPECTRA = {"bartlett": 1, "capon": 2}
 BEAM_MODES = {"conventional": 1, "mvdr": 2}
 ORDER_MODES = {"mdl": 1, "aic": 2}
 WINDOWS = {"rect": 0, "hann": 1}
@@ -50,6 +55,15 @@ def _sub_array(text):
     return int(sx), int(sy)
 
 
+def _set_array(text):
+    """--array MXxMY: the one place the shape constants change, straight after parsing (the workers get the option passed on)."""
+    global ARRAY, NROWS, M
+    if text:
+        ARRAY = _sub_array(text)
+        M = ARRAY[0] * ARRAY[1]
+        NROWS = M + 1
+
+
 def _setup(mx=None, my=None):
     sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
     import torch
@@ -57,7 +71,7 @@ def _setup(mx=None, my=None):
     b = importlib.import_module("coherent-rtlsdr_amd.binding")
     rng = np.random.default_rng(1)
     dev = torch.device("cuda", 0)
-    mx, my = mx or ura.MX, my or ura.MY
+    mx, my = mx or ARRAY[0], my or ARRAY[1]
     nrows = 1 + mx * my
     off = 16 + 4 * nrows
     stride = off + nrows * B
@@ -85,7 +99,7 @@ def worker_perop():
             m = C.cast(C.c_void_p(pk.data_ptr() + t * stride + off), i8p)
             b._check(L.crsdr_covariance(fp(rxx), m, NROWS, B, b.MEM_DEVICE))
             b._check(L.crsdr_noisesubspace(fp(vec), fp(sv), fp(rxx), M, b.MEM_DEVICE))
-            b._check(L.crsdr_pmusic2d(fp(pm), fp(vec), M, 1, float(ura.D), ura.MX, ura.MY, 100, 100, b.MEM_DEVICE))
+            b._check(L.crsdr_pmusic2d(fp(pm), fp(vec), M, 1, float(ura.D), *ARRAY, 100, 100, b.MEM_DEVICE))
     loop()
     print("ready", flush=True)
     for _ in sys.stdin:
@@ -94,22 +108,23 @@ def worker_perop():
         print(time.perf_counter() - t0, flush=True)
 
 
-def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None, fb=False, order=None, subbands=None, window="rect", band_beams=None):
+def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None, fb=False, order=None, subbands=None, window="rect", band_beams=None,
+               spectrum=None):
     """(b), (c), (p), (q), (h), (f), (s), (o) and the plan figures: 'b' / 'c' / 'p' / 'q' / 'h' / 'f' / 's' / 'o' / 'plan' / 'plan+doa' on
     stdin -> seconds of one batch of 64 on stdout."""
     torch, ura, b, dev, pk, off, stride, host = _setup()
-    peaks = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
-    full = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T, flags=b.DOA_KEEP_SPECTRUM)
+    peaks = b.Doa(NROWS, B, 1, ura.D, *ARRAY, max_batch=T)
+    full = b.Doa(NROWS, B, 1, ura.D, *ARRAY, max_batch=T, flags=b.DOA_KEEP_SPECTRUM)
     plan = b.Plan(NROWS, B, b.MODE_DIGITAL, max_batch=T)
     rows = torch.from_numpy(np.ascontiguousarray(host[:, off:])).to(dev)       # [T][nrows * B], the plan's device input
-    pdoa = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
+    pdoa = b.Doa(NROWS, B, 1, ura.D, *ARRAY, max_batch=T)
     dirs = None
     if npeaks:
-        dirs = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
+        dirs = b.Doa(NROWS, B, 1, ura.D, *ARRAY, max_batch=T)
         dirs.set_peaks(npeaks, radius)
     bdoa = None
     if beams:
-        bdoa = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
+        bdoa = b.Doa(NROWS, B, 1, ura.D, *ARRAY, max_batch=T)
         if npeaks:
             bdoa.set_peaks(npeaks, radius)
         bdoa.set_beams(BEAM_MODES[beams], loading)
@@ -118,22 +133,25 @@ def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None
 
     extra = {}
     if fb:
-        extra["f"] = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
-        extra["f"].set_smoothing(ura.MX, ura.MY, b.SMOOTH_FB)
+        extra["f"] = b.Doa(NROWS, B, 1, ura.D, *ARRAY, max_batch=T)
+        extra["f"].set_smoothing(*ARRAY, b.SMOOTH_FB)
     if smooth:
-        extra["s"] = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
+        extra["s"] = b.Doa(NROWS, B, 1, ura.D, *ARRAY, max_batch=T)
         extra["s"].set_smoothing(*_sub_array(smooth), b.SMOOTH_FB if fb else 0)
     if order:
-        extra["o"] = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
+        extra["o"] = b.Doa(NROWS, B, 1, ura.D, *ARRAY, max_batch=T)
         extra["o"].set_order(ORDER_MODES[order], 1, M - 1)
+    if spectrum:
+        extra["m"] = b.Doa(NROWS, B, 1, ura.D, *ARRAY, max_batch=T)
+        extra["m"].set_spectrum(SPECTRA[spectrum], loading)
     udoa = None
     if subbands:
-        udoa = b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T)
+        udoa = b.Doa(NROWS, B, 1, ura.D, *ARRAY, max_batch=T)
         udoa.set_subbands(*_bands(subbands), WINDOWS[window])
 
     vdoa = wdoa = None
     if subbands and band_beams:
-        vdoa, wdoa = (b.Doa(NROWS, B, 1, ura.D, ura.MX, ura.MY, max_batch=T) for _ in range(2))
+        vdoa, wdoa = (b.Doa(NROWS, B, 1, ura.D, *ARRAY, max_batch=T) for _ in range(2))
         for d in (vdoa, wdoa):
             d.set_subbands(*_bands(subbands), WINDOWS[window])
             if npeaks:
@@ -227,10 +245,10 @@ def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None
         print((time.perf_counter() - t0) / n, flush=True)
 
 
-def once(mode, npeaks=0, radius=1, beams=None, loading=1e-2, smooth=None, fb=False, order=None, subbands=None, window="rect", band_beams=None):
+def once(mode, npeaks=0, radius=1, beams=None, loading=1e-2, smooth=None, fb=False, order=None, subbands=None, window="rect", band_beams=None, spectrum=None):
     mx, my = (8, 8) if mode == "q64" else (None, None)
     torch, ura, b, dev, pk, off, stride, _ = _setup(mx, my)
-    mx, my = mx or ura.MX, my or ura.MY
+    mx, my = mx or ARRAY[0], my or ARRAY[1]
     d = b.Doa(1 + mx * my, B, 1, ura.D, mx, my, max_batch=T, flags=b.DOA_KEEP_SPECTRUM if mode == "c" else 0)
     if mode == "q64":
         npeaks, radius = 16, 1
@@ -243,6 +261,8 @@ def once(mode, npeaks=0, radius=1, beams=None, loading=1e-2, smooth=None, fb=Fal
             d.set_smoothing(*(_sub_array(smooth) if smooth else (mx, my)), b.SMOOTH_FB if fb else 0)
         if order:
             d.set_order(ORDER_MODES[order], 1, d.ms - 1)
+    if mode == "m":
+        d.set_spectrum(SPECTRA[spectrum or "capon"], loading)
     if mode in ("u", "v"):
         d.set_subbands(*_bands(subbands), WINDOWS[window])
     if mode == "v":
@@ -255,6 +275,8 @@ def once(mode, npeaks=0, radius=1, beams=None, loading=1e-2, smooth=None, fb=Fal
     if mode in ("u", "v"):
         print("band power of the first estimate", np.round(d.fetch_subbands()[0], 5).tolist())
     print("peaks", out["peak"][:4].tolist(), "launches", d.last_launches())
+    if mode == "m":
+        print("peak values of the first four, dB", np.round(10 * np.log10(out["peak_value"][:4]), 2).tolist())
     if mode == "s" and order:
         print("k", d.fetch_order()["k"].tolist())
     if mode in ("p", "q", "q64") and npeaks:
@@ -295,7 +317,9 @@ def _stat(xs):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--worker", choices=["perop", "doa"])
-    ap.add_argument("--once", choices=["b", "c", "p", "q", "q64", "s", "u", "v"])
+    ap.add_argument("--once", choices=["b", "c", "p", "q", "q64", "s", "u", "v", "m"])
+    ap.add_argument("--spectrum", choices=sorted(SPECTRA), default=None, help="(m): this power map in the scan's place (crsdr_doa_set_spectrum, --loading for capon)")
+    ap.add_argument("--array", default=None, metavar="MXxMY", help="the array, 2 <= MX MY <= 64 (default 7x3)")
     ap.add_argument("--subbands", default=None, metavar="NFFT:FIRST:COUNT[:WIDTH]", help="(u): a covariance per frequency band (crsdr_doa_set_subbands)")
     ap.add_argument("--window", choices=sorted(WINDOWS), default="rect", help="(u): the segments' window")
     ap.add_argument("--smooth", default=None, metavar="SXxSY", help="(s): sub-arrays of SX x SY elements (crsdr_doa_set_smoothing)")
@@ -312,14 +336,18 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
+    _set_array(a.array)                      # first thing: every worker, --once and the record read the shape from the globals
+    shape = ["--array", a.array] if a.array else []
     if a.worker:
         return worker_perop() if a.worker == "perop" else worker_doa(a.peaks, a.radius, a.reps, a.beams, a.loading, a.smooth, a.fb, a.order, a.subbands, a.window,
-                                                                           a.band_beams)
+                                                                           a.band_beams, a.spectrum)
     if a.band_beams and not a.subbands:
         ap.error("--band-beams needs --subbands")
     if a.once:
-        return once(a.once, a.peaks, a.radius, a.beams, a.loading, a.smooth, a.fb, a.order, a.subbands, a.window, a.band_beams)
-    pargs = ["--peaks", str(a.peaks), "--radius", str(a.radius), "--reps", str(a.reps), "--loading", str(a.loading)]
+        return once(a.once, a.peaks, a.radius, a.beams, a.loading, a.smooth, a.fb, a.order, a.subbands, a.window, a.band_beams, a.spectrum)
+    pargs = shape + ["--peaks", str(a.peaks), "--radius", str(a.radius), "--reps", str(a.reps), "--loading", str(a.loading)]
+    if a.spectrum:
+        pargs += ["--spectrum", a.spectrum]
     if a.beams:
         pargs += ["--beams", a.beams]
     if a.smooth:
@@ -332,9 +360,9 @@ def main():
         pargs += ["--subbands", a.subbands, "--window", a.window]
     if a.band_beams:
         pargs += ["--band-beams", a.band_beams]
-    legs = (["f"] if a.fb else []) + (["s"] if a.smooth else []) + (["o"] if a.order else []) + (["u"] if a.subbands else []) + (["v", "w"] if a.band_beams else [])
-    wa, wb = Worker("perop", a.perop_lib), Worker("doa", extra=pargs)
-    wl = Worker("doa", a.doa_lib, extra=["--reps", str(a.reps)]) if a.doa_lib else None
+    legs = (["f"] if a.fb else []) + (["s"] if a.smooth else []) + (["o"] if a.order else []) + (["u"] if a.subbands else []) + (["v", "w"] if a.band_beams else []) + (["m"] if a.spectrum else [])
+    wa, wb = Worker("perop", a.perop_lib, extra=shape), Worker("doa", extra=pargs)
+    wl = Worker("doa", a.doa_lib, extra=shape + ["--reps", str(a.reps)]) if a.doa_lib else None
     keys = ["a", "b", "c", "plan", "plan+doa"] + (["lib:b", "lib:c"] if wl else []) + (["p"] if a.peaks else []) + (["q", "h"] if a.beams else []) + legs
     sec = {k: [] for k in keys}
     try:
@@ -365,6 +393,7 @@ def main():
            "smoothing": {"sub_array": a.smooth, "fb": a.fb} if (a.smooth or a.fb) else None, "order": a.order,
            "subbands": dict(zip(("nfft", "first", "nbands", "width"), _bands(a.subbands)), window=a.window) if a.subbands else None,
            "band_beams": {"mode": a.band_beams, "loading": a.loading} if a.band_beams else None,
+           "spectrum": {"kind": a.spectrum, "loading": a.loading} if a.spectrum else None,
            "ms_per_batch": {k: _stat([1e3 * x for x in v]) for k, v in sec.items()},
            "frames_per_s": {k: _stat([T / x for x in sec[k]]) for k in ("a", "b", "c") + (("u",) if a.subbands else ())}}
     if a.subbands:
@@ -377,7 +406,8 @@ def main():
              "q": f"(p) + {a.beams} beams: submit + power", "h": "(p) + packets and vec to the host",
              "f": "FB alone: submit + peaks", "s": f"{a.smooth}{' + FB' if a.fb else ''}: submit + peaks", "o": f"order {a.order}: submit + peaks",
              "u": f"subbands {a.subbands} {a.window}: submit + peaks + power",
-             "v": f"subbands + {a.band_beams} band beams: submit + power", "w": "subbands: packets and vec to the host"}
+             "v": f"subbands + {a.band_beams} band beams: submit + power", "w": "subbands: packets and vec to the host",
+             "m": f"{a.spectrum} map: submit + peaks"}
     for k, s in rec["ms_per_batch"].items():
         fps = f"  {T / (1e-3 * s['median']):10.0f} frames/s" if k in rec["frames_per_s"] else ""
         print(f"({k}) {names[k]:34s} {s['median']:8.3f} ms per 64 blocks  [{s['min']:.3f} .. {s['max']:.3f}]{fps}")
@@ -391,6 +421,12 @@ def main():
     if a.band_beams:
         rec["v_over_w_ms"] = rec["ms_per_batch"]["v"]["median"] / rec["ms_per_batch"]["w"]["median"]
         print(f"(v) takes {rec['v_over_w_ms']:.2f} x the time of (w)")
+    if a.spectrum:
+        rec["m_over_b_ms"] = rec["ms_per_batch"]["m"]["median"] / rec["ms_per_batch"]["b"]["median"]
+        print(f"(m) takes {rec['m_over_b_ms']:.3f} x the time of (b), the MUSIC submit at k = 1; the scan's operation count is M / (M - 1) = {M / (M - 1):.3f} x")
+        if wl:
+            rec["m_over_lib_b_ms"] = rec["ms_per_batch"]["m"]["median"] / rec["ms_per_batch"]["lib:b"]["median"]
+            print(f"(m) takes {rec['m_over_lib_b_ms']:.3f} x the time of lib:b")
     if wl:
         rec["b_minus_lib_b_ms"] = rec["ms_per_batch"]["b"]["median"] - rec["ms_per_batch"]["lib:b"]["median"]
     if a.json:
