@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "crsdr_doa_set_subbands", "crsdr_doa_fetch_subbands", "crsdr_doa_subband_buffers", "crsdr_subband_covariance",
     "crsdr_doa_set_subband_beams", "crsdr_doa_fetch_subband_beams", "crsdr_doa_subband_beam_buffers", "crsdr_subband_beamform",
     "crsdr_doa_set_spectrum", "crsdr_spectrum2d",
+    "crsdr_doa_set_refine", "crsdr_doa_fetch_refined", "crsdr_doa_refined_buffers", "crsdr_refine2d",
 ]
 DOA_KEEP_SPECTRUM, DOA_KEEP_RXX = 1, 2
 BEAM_OFF, BEAM_CONVENTIONAL, BEAM_MVDR = 0, 1, 2
@@ -203,6 +204,12 @@ def lib():
     if hasattr(L, "crsdr_doa_set_spectrum"):         # (likewise: an older build has the MUSIC map alone)
         L.crsdr_doa_set_spectrum.argtypes = [vp, C.c_int, C.c_float]
         L.crsdr_spectrum2d.argtypes = [f32p, f32p, f32p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    if hasattr(L, "crsdr_doa_set_refine"):           # (likewise: an older build reports grid points alone)
+        L.crsdr_doa_set_refine.argtypes = [vp, C.c_int]
+        L.crsdr_doa_fetch_refined.argtypes = [vp, f32p, f32p, f32p]
+        L.crsdr_doa_refined_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int)]
+        L.crsdr_refine2d.argtypes = [f32p, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, i32p,
+                                     C.c_int, C.c_int, C.c_int]
     _lib = L
     return L
 
@@ -384,6 +391,22 @@ def spectrum2d_device(pm_ptr: int, vec_ptr: int, sv_ptr: int, m, kind, d, mx, my
     f32p = C.POINTER(C.c_float)
     _check(lib().crsdr_spectrum2d(C.cast(C.c_void_p(int(pm_ptr)), f32p), C.cast(C.c_void_p(int(vec_ptr)), f32p), C.cast(C.c_void_p(int(sv_ptr)), f32p),
                                   int(m), int(kind), C.c_float(loading), C.c_float(d), int(mx), int(my), int(ncx), int(ncy), MEM_DEVICE))
+
+
+def refine2d(vec, sv, kind, peaks, d, mx, my, ncx=100, ncy=100, k=1, loading=1e-2, levels=5):
+    """crsdr_refine2d: the directions peaks [n][2] (cx, cy) of the map `kind` (SPECTRUM_*; k: MUSIC's sources, loading: Capon's) of the
+    subspace (vec, sv), refined off the grid by `levels` levels of the zoom search.  offsets [n][2] in grid cells, angles [n][2]
+    (alpha, beta) in radians, values [n]."""
+    v = np.ascontiguousarray(vec, dtype=np.complex64)
+    s = np.ascontiguousarray(sv, dtype=np.float32)
+    pk = np.ascontiguousarray(peaks, dtype=np.int32).reshape(-1, 2)
+    M, n = v.shape[0], pk.shape[0]
+    if v.shape != (M, M) or s.shape != (M,):
+        raise ValueError("vec must be [m][m] and sv [m]")
+    off, ang, val = np.zeros((n, 2), dtype=np.float32), np.zeros((n, 2), dtype=np.float32), np.zeros(n, dtype=np.float32)
+    _check(lib().crsdr_refine2d(_p(off, C.c_float), _p(ang, C.c_float), _p(val, C.c_float), _p(v.view(np.float32), C.c_float), _p(s, C.c_float), M, int(kind),
+                                int(k), C.c_float(loading), C.c_float(d), int(mx), int(my), int(ncx), int(ncy), _p(pk, C.c_int32), n, int(levels), MEM_HOST))
+    return {"offsets": off, "angles": ang, "values": val}
 
 
 def beamform(matrix, weights):
@@ -729,6 +752,7 @@ class Doa:
         self._h = h
         self.nrows, self.B, self.m, self.k, self.ncx, self.ncy = int(nrows), int(blocksize), int(nrows) - 1, int(k), int(ncx), int(ncy)
         self.max_batch, self.frames, self.flags = max(1, int(max_batch)), max(1, int(frames)), int(flags)
+        self.d, self._sub = float(d), (int(mx), int(my))                            # _sub: set_smoothing's sub-array
         self.npeaks, self.nbeams = 0, 0
         self.mx, self.my, self.ms, self.order = int(mx), int(my), self.m, None      # ms: the subspace's size; order: (kmin, kmax)
         self.nbands = 0                                                             # set_subbands: bands per estimate (0: off)
@@ -832,7 +856,7 @@ class Doa:
         backward image) feeds the subspace; sv and vec then have ms = sx * sy entries.  (mx, my) with flags 0: off.  Waits for the
         device if a submit was made, and discards that submit's results."""
         _check(lib().crsdr_doa_set_smoothing(self._h, int(sx), int(sy), int(flags)))
-        self.ms = int(sx) * int(sy)
+        self.ms, self._sub = int(sx) * int(sy), (int(sx), int(sy))
 
     def fetch_smoothed(self) -> np.ndarray:
         """rs [nest][ms][ms] complex64 of the last submit."""
@@ -911,6 +935,31 @@ class Doa:
         SPECTRUM_CAPON with its diagonal loading) in place of the MUSIC pseudo-spectrum (SPECTRUM_MUSIC: back to it), and pm, peak, the
         directions and the beams that follow them work on that map.  Waits for the device if a submit was made; what it left is gone."""
         _check(lib().crsdr_doa_set_spectrum(self._h, int(kind), C.c_float(loading)))
+
+    def set_refine(self, levels: int = 5):
+        """crsdr_doa_set_refine: from the next submit on every direction (set_peaks' slots, or the peak) is refined off the grid by
+        `levels` levels (1 .. 8) of the fp64 zoom search, and following beams steer there.  0: off.  Waits for the device if a submit
+        was made."""
+        _check(lib().crsdr_doa_set_refine(self._h, int(levels)))
+
+    def fetch_refined(self) -> dict:
+        """Waits for the last submit.  offsets [nest][slots][2] (grid cells, exact), angles [nest][slots][2] (alpha, beta in radians),
+        values [nest][slots]; empty slots hold (0, 0), (-1, -1) and -1."""
+        n, c = self._last()[0], self.refined_buffers()["slots"]
+        off, ang, val = np.zeros((n, c, 2), dtype=np.float32), np.zeros((n, c, 2), dtype=np.float32), np.zeros((n, c), dtype=np.float32)
+        _check(lib().crsdr_doa_fetch_refined(self._h, _p(off, C.c_float), _p(ang, C.c_float), _p(val, C.c_float)))
+        return {"offsets": off, "angles": ang, "values": val}
+
+    def refined_buffers(self) -> dict:
+        ptrs, slots = [C.c_void_p() for _ in range(3)], C.c_int(0)
+        _check(lib().crsdr_doa_refined_buffers(self._h, *[C.byref(p) for p in ptrs], C.byref(slots)))
+        return dict(zip(("offsets", "angles", "values"), [p.value for p in ptrs]), slots=slots.value)
+
+    def refine2d(self, vec, sv, peaks, kind=SPECTRUM_MUSIC, k=None, loading=1e-2, levels=5) -> dict:
+        """crsdr_refine2d with this object's geometry (the sub-arrays' while smoothing is on) on one matrix's vec, sv and directions."""
+        M = np.asarray(vec).shape[0]
+        sx, sy = (self.mx, self.my) if M == self.m else self._sub
+        return refine2d(vec, sv, kind, peaks, self.d, sx, sy, self.ncx, self.ncy, k=self.k if k is None else k, loading=loading, levels=levels)
 
     def last_launches(self) -> int:
         return self._last()[1]

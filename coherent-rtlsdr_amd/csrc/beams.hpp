@@ -32,12 +32,14 @@ enum { MODE_OFF = 0, MODE_CONVENTIONAL = 1, MODE_MVDR = 2 };
 
 // grid (nest, nbeams), BW_THREADS = 64 threads (m <= 64: thread i owns element i and column i).
 //   vec [nest][m][m] (column r = v_r), sv [nest][m];  the slot's direction: fixed ? angles [nbeams][2] (alpha, beta)
-//   : found ? peaks [nest][nbeams][2] with found [nest] : peak [nest][2] (one slot)
+//   : found ? peaks [nest][nbeams][2] with found [nest] : peak [nest][2] (one slot); refined: NULL, or offsets [nest][nbeams][2] in
+//   grid cells added to the slot's grid point in fp64 (crsdr_doa_set_refine).  With NULL the arithmetic is what it was without it.
 //   weights [nest][nbeams][m], power [nest][nbeams]
 __global__ __launch_bounds__(BW_THREADS) void k_doa_beam_weights(const float2 *__restrict__ vec, const float *__restrict__ sv, int m, int mx, float d, int ncx,
                                                                   int ncy, int mode, float loading, const float *__restrict__ angles,
                                                                   const int32_t *__restrict__ found, const int32_t *__restrict__ peaks,
-                                                                  const int32_t *__restrict__ peak, float2 *__restrict__ weights, float *__restrict__ power)
+                                                                  const int32_t *__restrict__ peak, const float *__restrict__ refined, float2 *__restrict__ weights,
+                                                                  float *__restrict__ power)
 {
     __shared__ double2 sa[MAX_M], sg[MAX_M];
     __shared__ double sred[MAX_M];
@@ -55,7 +57,11 @@ __global__ __launch_bounds__(BW_THREADS) void k_doa_beam_weights(const float2 *_
             return;
         }
         const double pi = 3.14159265358979323846;
-        alpha = (double)p[0] * pi / (double)ncx; beta = (double)p[1] * pi / (double)ncy;
+        if (refined) {
+            alpha = ((double)p[0] + (double)refined[2 * slot]) * pi / (double)ncx; beta = ((double)p[1] + (double)refined[2 * slot + 1]) * pi / (double)ncy;
+        } else {
+            alpha = (double)p[0] * pi / (double)ncx; beta = (double)p[1] * pi / (double)ncy;
+        }
     }
     const float2 *V = vec + (size_t)e * m * m;
     const float *s = sv + (size_t)e * m;

@@ -9,6 +9,7 @@
 #include "subband.hpp"
 #include "subband_beams.hpp"
 #include "spectrum.hpp"
+#include "refine.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -467,8 +468,8 @@ static hipError_t launch_frac_apply(hipStream_t s, int row_count, int nblocks, c
 namespace {
 struct OpCtx {
     std::mutex mu;
-    void *buf[4] = {nullptr, nullptr, nullptr, nullptr};      // [3]: the tiled covariance's partial sums
-    size_t cap[4] = {0, 0, 0, 0};
+    void *buf[6] = {};                                        // [3]: the tiled covariance's partial sums; [4], [5]: crsdr_refine2d's further arguments
+    size_t cap[6] = {};
     float2 *tw[kMaxLog2 + 1] = {};
     int tw_dev[kMaxLog2 + 1] = {};
     int dev = -1;
@@ -480,7 +481,7 @@ int op_reserve(int slot, size_t bytes)
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     if (g_op.dev != dev) {
-        for (int i = 0; i < 4; ++i) { if (g_op.buf[i]) (void)hipFree(g_op.buf[i]); g_op.buf[i] = nullptr; g_op.cap[i] = 0; }
+        for (int i = 0; i < 6; ++i) { if (g_op.buf[i]) (void)hipFree(g_op.buf[i]); g_op.buf[i] = nullptr; g_op.cap[i] = 0; }
         for (int i = 0; i <= kMaxLog2; ++i) { if (g_op.tw[i]) (void)hipFree(g_op.tw[i]); g_op.tw[i] = nullptr; }
         g_op.dev = dev;
     }
@@ -1997,3 +1998,48 @@ extern "C" int crsdr_beamform(float *out, const int8_t *matrix, int nrows, int b
 }
 
 #include "exchange_impl.hpp"
+
+// ================================================================================================
+// (iv) continued: the directions off the scan grid (refine.hpp).  The kernel's first use is here, behind every other kernel's: the
+// code object's other kernels stay in the order they had (doa_engine.hpp)
+// ================================================================================================
+static const void *doa_refine_kernel() { return (const void *)refine::k_doa_refine<refine::RF_WAVES>; }
+
+static void doa_refine_enqueue(dim3 grid, hipStream_t S, const float2 *vec, const float *sv, int M, int kind, int k, const int32_t *korder, float loading, float d, int Mx,
+                               int Cx, int Cy, const int32_t *dirs, const int32_t *found, int levels, float *offsets, float *angles, float *values)
+{
+    hipLaunchKernelGGL(refine::k_doa_refine<refine::RF_WAVES>, grid, dim3(refine::RF_THREADS), refine::lds_bytes(M), S, vec, sv, M, kind, k, korder, loading, d, Mx, Cx, Cy,
+                       dirs, found, levels, offsets, angles, values);
+}
+
+extern "C" int crsdr_refine2d(float *offsets, float *angles, float *values, const float *vec, const float *sv, int m, int kind, int k, float loading, float d, int mx,
+                              int my, int ncx, int ncy, const int32_t *peaks, int npeaks, int levels, int mem_kind)
+{
+    if (!offsets || !angles || !values || !vec || !sv || !peaks || m < 2 || m > refine::MAX_M || mx < 1 || my < 1 || (long long)mx * my != m || ncx < 1 || ncy < 1 ||
+        (long long)ncx * ncy > (1 << 24))
+        return fail(CRSDR_EINVAL, "refine2d: need offsets, angles, values, vec, sv, peaks, m = mx*my in [2, %d], grid <= 2^24 points", refine::MAX_M);
+    { const int rc_ = spectrum_args_ok("refine2d", kind, loading, true); if (rc_) return rc_; }
+    if (kind == CRSDR_SPECTRUM_MUSIC && (k < 1 || k >= m)) return fail(CRSDR_EINVAL, "refine2d: k = %d sources (1 <= k < %d)", k, m);
+    if (npeaks < 1 || npeaks > doa::MAX_PEAKS) return fail(CRSDR_EINVAL, "refine2d: npeaks = %d (1..%d)", npeaks, doa::MAX_PEAKS);
+    if (levels < 1 || levels > refine::MAX_LEVELS) return fail(CRSDR_EINVAL, "refine2d: levels = %d (1..%d)", levels, refine::MAX_LEVELS);
+    OP_PROLOGUE_MEM("refine2d", mem_kind);
+    const size_t mm = sizeof(float2) * (size_t)m * m, n2 = sizeof(float) * 2 * (size_t)npeaks;
+    OpStage st(mem_kind);
+    const float2 *d_v = (const float2 *)st.in(0, vec, mm, 8);
+    float *d_o = (float *)st.out(1, offsets, n2, 4);
+    const float *d_s = (const float *)st.in(2, sv, sizeof(float) * (size_t)m, 4);
+    float *d_a = (float *)st.out(3, angles, n2, 4);
+    float *d_f = (float *)st.out(4, values, n2 / 2, 4);
+    const int32_t *d_p = (const int32_t *)st.in(5, peaks, sizeof(int32_t) * 2 * (size_t)npeaks, 4);
+    if (st.rc) return st.rc;
+    if (st.misaligned) return fail(CRSDR_EINVAL, "refine2d: device vec 8-byte, every other pointer 4-byte aligned");
+    // the engine's kernel: the limit doa_lds_limits() gives it, so that this call cannot lower it under a live object
+    HIP_TRY(hipFuncSetAttribute(doa_refine_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)refine::lds_bytes(refine::MAX_M)));
+    doa_refine_enqueue(dim3((unsigned)npeaks, 1), 0, d_v, d_s, m, kind, k, nullptr, kind == CRSDR_SPECTRUM_CAPON ? loading : 0.f, d, mx, ncx, ncy, d_p, nullptr, levels, d_o,
+                       d_a, d_f);
+    HIP_TRY(hipGetLastError());
+    st.back(offsets, d_o, n2);
+    st.back(angles, d_a, n2);
+    st.back(values, d_f, n2 / 2);
+    return st.finish();
+}

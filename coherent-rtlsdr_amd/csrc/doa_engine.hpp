@@ -10,6 +10,7 @@
 //      for (max_batch / frames) * nbands matrices: the launches behind it then run over that many.  crsdr_doa_set_subband_beams on top of
 //      it: the beam weights per (estimate, band) and subband_beams.hpp's apply kernel on the rows' band spectra.  crsdr_doa_set_spectrum
 //      replaces the scan's kernel by spectrum.hpp's (the Bartlett or the Capon map): the same launches, nothing allocated.
+//      crsdr_doa_set_refine adds refine.hpp's launch behind the directions and ahead of the beams, which then steer off the grid.
 //
 // Shape of the host code.  A feature is a sub-struct of crsdr_doa: its parameters and its device buffers, each buffer owned by a
 // DevBuf, so that "off" is an assignment of {} and nothing is freed by a list kept by hand.  What the last submit left (DoaLast) is
@@ -105,13 +106,20 @@ struct DoaOrder {
     DevBuf<int32_t> k;
     DevBuf<float> values;
 };
+// crsdr_doa_set_refine: levels of the zoom search (0 = off); offsets and angles [nmat][slots][2], values [nmat][slots], slots = the
+// directions of set_peaks or the one peak.  Allocated for the most matrices and slots there can be: no other setter resizes them
+struct DoaRefine {
+    int levels = 0;
+    DevBuf<float> offsets, angles, values;
+};
 // what the last submit left: where, how much, and which features ran (kRan*).  A setter clears its feature's bit: "nothing submitted
 // since"; without kRanBase nothing is left at all
-constexpr unsigned kRanBase = 1u, kRanPeaks = 2u, kRanBeams = 4u, kRanSmooth = 8u, kRanOrder = 16u;
+constexpr unsigned kRanBase = 1u, kRanPeaks = 2u, kRanBeams = 4u, kRanSmooth = 8u, kRanOrder = 16u, kRanRefine = 32u;
 struct DoaLast {
     hipStream_t stream = nullptr;
     int nest = 0, nblocks = 0, ms = 0, launches = 0;
     unsigned ran = 0;
+    int slots = 0;               // refined directions per matrix (the layout of that submit, whatever set_peaks says since)
 };
 
 struct crsdr_doa {
@@ -128,6 +136,7 @@ struct crsdr_doa {
     DoaBeams beams;
     DoaSmooth smooth;
     DoaOrder order;
+    DoaRefine refine;
     int spectrum = CRSDR_SPECTRUM_MUSIC;           // crsdr_doa_set_spectrum: the map the scan computes, and CAPON's loading
     float spectrum_loading = 0.f;
     DoaLast last;
@@ -139,6 +148,11 @@ struct crsdr_doa {
 constexpr int kMaxDoaMatrices = 4096;      // (max_batch / frames) * nbands
 
 static int doa_lds_limits();               // (behind the stages, which name the kernels it covers)
+// refine.hpp's kernel is reached through these two, defined at the end of the translation unit: its first use lies behind every other
+// kernel's, so the kernels ahead of it keep their order in the code object (see below)
+static const void *doa_refine_kernel();
+static void doa_refine_enqueue(dim3 grid, hipStream_t S, const float2 *vec, const float *sv, int M, int kind, int k, const int32_t *korder, float loading, float d, int Mx,
+                               int Cx, int Cy, const int32_t *dirs, const int32_t *found, int levels, float *offsets, float *angles, float *values);
 // k_doa_scan<false> is named here, ahead of the stages, to keep the code object's kernels in the order they have always had: a
 // device-only assembly of the translation unit then compares line by line with an earlier build's
 static const void *const kDoaPlainScan = (const void *)doa::k_doa_scan<false>;
@@ -335,6 +349,20 @@ static int doa_stage_local_peaks(crsdr_doa *q, DoaRun &r)
                    pk.found.p, pk.dirs.p, pk.values.p, (const int32_t *)(q->order.crit && q->order.limit_dirs ? q->order.k.p : nullptr));
 }
 
+// the directions off the grid: one workgroup per (slot, matrix) on the subspace the scan used
+static int doa_stage_refine(crsdr_doa *q, DoaRun &r)
+{
+    const DoaRefine &rf = q->refine;
+    if (!rf.levels) return CRSDR_OK;
+    const bool pk = q->peaks.count != 0;
+    doa_refine_enqueue(dim3((unsigned)(pk ? q->peaks.count : 1), r.nest), r.S, (const float2 *)q->mat.vec, (const float *)q->mat.sv, r.M, q->spectrum, q->k,
+                       (const int32_t *)q->order.k, q->spectrum_loading, q->d, q->sx(), q->ncx, q->ncy, (const int32_t *)(pk ? q->peaks.dirs.p : q->mat.peak.p),
+                       (const int32_t *)(pk ? q->peaks.found.p : nullptr), rf.levels, rf.offsets.p, rf.angles.p, rf.values.p);
+    HIP_TRY(hipGetLastError());
+    ++r.launches;
+    return CRSDR_OK;
+}
+
 // the weights per matrix, then the apply kernel over the packets: on their samples, or on their band spectra
 static int doa_stage_beams(crsdr_doa *q, DoaRun &r)
 {
@@ -342,8 +370,8 @@ static int doa_stage_beams(crsdr_doa *q, DoaRun &r)
     if (!bm.mode) return CRSDR_OK;
     int rc = doa_run(r, beams::k_doa_beam_weights, dim3(r.nest, (unsigned)bm.nbeams), dim3(beams::BW_THREADS), 0, (const float2 *)q->mat.vec, (const float *)q->mat.sv,
                      q->m, q->mx, q->d, q->ncx, q->ncy, bm.mode, bm.loading, (const float *)(bm.nfixed ? bm.angles.p : nullptr),
-                     (const int32_t *)(q->peaks.count ? q->peaks.found.p : nullptr), (const int32_t *)q->peaks.dirs, (const int32_t *)q->mat.peak, bm.weights.p,
-                     bm.power.p);
+                     (const int32_t *)(q->peaks.count ? q->peaks.found.p : nullptr), (const int32_t *)q->peaks.dirs, (const int32_t *)q->mat.peak,
+                     (const float *)(q->refine.levels && !bm.nfixed ? q->refine.offsets.p : nullptr), bm.weights.p, bm.power.p);
     if (rc) return rc;
     if (bm.band) {
         // the weights above are per (estimate, band): applied to the rows' band spectra
@@ -364,16 +392,18 @@ static int doa_launch(crsdr_doa *q, const int8_t *packets, size_t packet_stride,
     DoaRun r{packets, packet_stride, matrix_offset, nblocks, S, (unsigned)(nblocks / q->frames), q->ms()};
     int rc = CRSDR_OK;
     if ((rc = doa_stage_covariance(q, r)) || (rc = doa_stage_subspace(q, r)) || (rc = doa_stage_scan(q, r)) || (rc = doa_stage_local_peaks(q, r)) ||
-        (rc = doa_stage_beams(q, r)))
+        (rc = doa_stage_refine(q, r)) || (rc = doa_stage_beams(q, r)))
         return rc;
     q->last = DoaLast{S, (int)r.nest, nblocks, r.M, r.launches,
-                      kRanBase | (q->peaks.count ? kRanPeaks : 0u) | (q->beams.mode ? kRanBeams : 0u) | (q->smooth.on ? kRanSmooth : 0u) | (q->order.crit ? kRanOrder : 0u)};
+                      kRanBase | (q->peaks.count ? kRanPeaks : 0u) | (q->beams.mode ? kRanBeams : 0u) | (q->smooth.on ? kRanSmooth : 0u) | (q->order.crit ? kRanOrder : 0u) |
+                          (q->refine.levels ? kRanRefine : 0u),
+                      q->refine.levels ? (q->peaks.count ? q->peaks.count : 1) : 0};
     return CRSDR_OK;
 }
 
 // The kernels' dynamic LDS limits are function attributes, shared by every live object: each create sets every limit the engine's
 // kernels can need to the most any object can ask for (subspace and scan: m = 64, one signal vector; power maps: m = 64; local peaks: the largest radius;
-// band beams: 64 rows of 256 points), so that a small object created after a large one cannot lower a limit under it, and no setter
+// band beams: 64 rows of 256 points; the refinement: m = 64), so that a small object created after a large one cannot lower a limit under it, and no setter
 // has to think of them.  (The per-op calls set their own kernels' limits.)
 static int doa_lds_limits()
 {
@@ -386,6 +416,7 @@ static int doa_lds_limits()
     HIP_TRY(limit((const void *)doa::k_doa_scan<true>, scan));
     HIP_TRY(limit((const void *)spectrum::k_doa_spectrum, spectrum::lds_bytes(music::MAX_M)));
     HIP_TRY(limit((const void *)doa::k_doa_local_peaks, doa::lp_lds(doa::MAX_RADIUS)));
+    HIP_TRY(limit(doa_refine_kernel(), refine::lds_bytes(refine::MAX_M)));
     for (int lg = subband::SB_MIN_LOG2; lg <= subband::SB_MAX_LOG2; ++lg) SUBBAND_DISPATCH(lg, HIP_TRY(limit((const void *)sbbeams::k_doa_subband_beam_apply<LG>, sbb)));
     return CRSDR_OK;
 }
@@ -612,6 +643,44 @@ extern "C" int crsdr_doa_set_spectrum(crsdr_doa *q, int kind, float loading)
     // pm, the peak, the directions and the beams toward them all change their meaning: nothing the last submit left stays
     q->last.ran = 0;
     q->spectrum = kind; q->spectrum_loading = kind == CRSDR_SPECTRUM_CAPON ? loading : 0.f;
+    return CRSDR_OK;
+}
+
+// ---- the directions off the scan grid (refine.hpp) ----
+extern "C" int crsdr_doa_set_refine(crsdr_doa *q, int levels)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_set_refine: NULL doa");
+    if (levels < 0 || levels > refine::MAX_LEVELS) return fail(CRSDR_EINVAL, "doa_set_refine: levels = %d (0..%d)", levels, refine::MAX_LEVELS);
+    { const int rc = doa_quiesce(q); if (rc) return rc; }
+    q->refine = {}; q->last.ran &= ~kRanRefine;
+    if (levels == 0) return CRSDR_OK;
+    // the most matrices and slots any later setter can ask for
+    const size_t slots = (size_t)kMaxDoaMatrices * doa::MAX_PEAKS;
+    DoaRefine &rf = q->refine;
+    if (rf.offsets.alloc(2 * slots) || rf.angles.alloc(2 * slots) || rf.values.alloc(slots)) {
+        q->refine = {};
+        return fail(CRSDR_ENOMEM, "doa_set_refine: %zu bytes of device memory", sizeof(float) * 5 * slots);
+    }
+    rf.levels = levels;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_fetch_refined(crsdr_doa *q, float *offsets, float *angles, float *values)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_fetch_refined: NULL doa");
+    if (!q->refine.levels) return fail(CRSDR_ESTATE, "doa_fetch_refined: no crsdr_doa_set_refine");
+    if (!(q->last.ran & kRanRefine)) return fail(CRSDR_ESTATE, "doa_fetch_refined: nothing submitted since crsdr_doa_set_refine");
+    const size_t n = (size_t)q->last.nest * (size_t)q->last.slots;
+    return DoaFetch(q).copy(offsets, q->refine.offsets.p, 2 * n).copy(angles, q->refine.angles.p, 2 * n).copy(values, q->refine.values.p, n).wait();
+}
+
+extern "C" int crsdr_doa_refined_buffers(crsdr_doa *q, void **offsets, void **angles, void **values, int *slots)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_refined_buffers: NULL doa");
+    if (offsets) *offsets = q->refine.offsets;
+    if (angles) *angles = q->refine.angles;
+    if (values) *values = q->refine.values;
+    if (slots) *slots = q->refine.levels ? (q->last.ran & kRanRefine ? q->last.slots : q->peaks.count ? q->peaks.count : 1) : 0;
     return CRSDR_OK;
 }
 

@@ -123,6 +123,14 @@ int batch::set_spectrum(int kind, float loading)
     return rc;
 }
 
+int batch::set_refine(int levels)
+{
+    int rc = doa ? crsdr_doa_set_refine(doa, levels) : CRSDR_ESTATE;
+    if (!rc) refining = levels;
+    if (rc && doa) std::fprintf(stderr, "cbeamformer::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
 int batch::set_subband_beams(int mode, float loading, int nfixed, const float *fixed_angles)
 {
     int rc = doa ? crsdr_doa_set_subband_beams(doa, mode, loading, nfixed, fixed_angles) : CRSDR_ESTATE;
@@ -151,6 +159,12 @@ int batch::fetch(bool want_beams)
     if (!rc && npeaks) {
         found.assign(nest, 0); directions.assign((size_t)nest * npeaks * 2, -1); direction_values.assign((size_t)nest * npeaks, -1.f);
         rc = crsdr_doa_fetch_directions(doa, found.data(), directions.data(), direction_values.data());
+    }
+    if (!rc && refining) {
+        rc = crsdr_doa_refined_buffers(doa, nullptr, nullptr, nullptr, &nrefined);
+        const size_t n = (size_t)nest * nrefined;
+        refined_offsets.assign(2 * n, 0.f); refined_angles.assign(2 * n, -1.f); refined_values.assign(n, -1.f);
+        if (!rc) rc = crsdr_doa_fetch_refined(doa, refined_offsets.data(), refined_angles.data(), refined_values.data());
     }
     if (!rc && nbeams) {
         weights.assign((size_t)nest * nbeams * m, {0.f, 0.f}); beam_power.assign((size_t)nest * nbeams, -1.f);

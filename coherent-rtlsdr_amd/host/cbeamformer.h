@@ -36,6 +36,7 @@ class batch {
     crsdr_doa *doa = nullptr;
     int m = 0, ms = 0, cx = 0, cy = 0, npeaks = 0, nbeams = 0, half = 0, nframes = 1;      // ms: the subspace's size (m, or a sub-array's)
     bool counted = false;
+    int refining = 0, nrefined = 0;                  // set_refine: levels; slots per estimate of the last fetch
     bool keep = false;
     int nbands = 0;                                  // set_subbands: bands per estimate (0: off)
     int nbandbeams = 0, band_j = 0, band_width = 0;  // set_subband_beams: slots; set_subbands: segments per block, bins per band
@@ -74,6 +75,13 @@ public:
     // peak_value, the directions and the beams that follow them are then that map's, K and the source counts are not used.
     // CRSDR_SPECTRUM_MUSIC: back.  Any time; discards the last submit's results.
     int set_spectrum(int kind, float loading = 1e-2f);
+    // from the next submit on, every direction (the slots of set_peaks, or the one peak) refined off the scan grid by `levels` levels
+    // (1 .. 8) of the fp64 zoom search (crsdr_doa_set_refine); following beams then steer at the refined direction.  0: off.  Any time.
+    int set_refine(int levels = 5);
+    // with set_refine: per estimate and slot the offset from the grid point in cells [estimates][slots][2], (alpha, beta) in radians
+    // [estimates][slots][2] and the map's value there [estimates][slots]; empty slots hold (0, 0), (-1, -1) and -1
+    int refined_slots() const { return nrefined; }
+    std::vector<float> refined_offsets, refined_angles, refined_values;
     int bands() const { return nbands; }
     std::vector<float> band_power;                   // with set_subbands: [estimates]: Re trace(R_band) / M, the squelch of a band's direction
     // with set_subbands on: from the next submit on, a beam per band toward every direction of that band (crsdr_doa_set_subband_beams;

@@ -57,7 +57,7 @@ int main(int argc, char **argv)
     bool run_cdsp = false, servo = false, threads = false, music = false, servo_table = false, bench = false, batch_parity = false, batched = false;
     int batch = 16, engine_delay_ms = 0, pace_us_arg = -1, peaks = 0, peak_radius = 1, beam_mode = CRSDR_BEAM_OFF, band_beam_mode = CRSDR_BEAM_OFF;
     float beam_loading = 1e-2f;
-    int smooth_x = 0, smooth_y = 0, order_crit = CRSDR_ORDER_OFF, spectrum_kind = CRSDR_SPECTRUM_MUSIC;
+    int smooth_x = 0, smooth_y = 0, order_crit = CRSDR_ORDER_OFF, spectrum_kind = CRSDR_SPECTRUM_MUSIC, refine_levels = 0;
     bool smooth_fb = false;
     int sb_nfft = 0, sb_first = 0, sb_count = 1, sb_width = 1, sb_window = CRSDR_WINDOW_RECT;
     bool engine_batches = false;
@@ -123,6 +123,12 @@ int main(int argc, char **argv)
         else if (a == "--spectrum" && i + 1 < argc) {
             const std::string m = argv[++i];
             spectrum_kind = m == "music" ? CRSDR_SPECTRUM_MUSIC : m == "bartlett" ? CRSDR_SPECTRUM_BARTLETT : m == "capon" ? CRSDR_SPECTRUM_CAPON : -1;
+        }
+        // with --bench --music: every direction refined off the scan grid (crsdr_doa_set_refine; 5 levels unless a number follows), its
+        // angles in degrees printed beside the grid point
+        else if (a == "--refine") {
+            refine_levels = 5;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') refine_levels = std::atoi(argv[++i]);
         }
         else if (a == "--loading" && i + 1 < argc) beam_loading = (float)std::atof(argv[++i]);
         else if (a == "--batch-parity") batch_parity = true;   // the batched engine's packets == step()'s packets, bit for bit (own read counters, a masked row)
@@ -339,6 +345,7 @@ int main(int argc, char **argv)
                 return 1;
             }
             if (peaks && doa->set_peaks(peaks, peak_radius)) { std::printf("doa: --peaks %d --peak-radius %d refused\nDEMO FAILED\n", peaks, peak_radius); return 1; }
+            if (refine_levels && doa->set_refine(refine_levels)) { std::printf("doa: --refine %d refused (1..8 levels)\nDEMO FAILED\n", refine_levels); return 1; }
             if (beam_mode && doa->set_beams(beam_mode, beam_loading)) { std::printf("doa: --beams (conventional|mvdr) --loading %g refused\nDEMO FAILED\n", (double)beam_loading); return 1; }
             if (band_beam_mode && (!sb_nfft || doa->set_subband_beams(band_beam_mode, beam_loading))) {
                 std::printf("doa: --band-beams (conventional|mvdr) --loading %g refused (it needs --subbands)\nDEMO FAILED\n", (double)beam_loading);
@@ -351,14 +358,20 @@ int main(int argc, char **argv)
             ok = doa->submit(coherent.engine_plan()) == CRSDR_OK && doa->fetch() == CRSDR_OK;
             if (!ok || !report) return;
             const int n = doa->estimates();
+            const double deg = 180.0 / 3.14159265358979323846;
             if (doa->bands()) {
                 // every estimate's bands: the direction at that frequency and the power that says whether to trust it
                 const int nb_ = doa->bands();
                 for (int e = 0; e < n / nb_; ++e)
                     for (int i = 0; i < nb_; ++i) {
                         const int x = e * nb_ + i, f0 = (sb_first + i * sb_width) % sb_nfft;
-                        std::printf("doa: batch %d: estimate %d band %d (bins %d..%d of %d): (%d, %d) power %.4g", b, e, i, f0, (f0 + sb_width - 1) % sb_nfft, sb_nfft,
-                                    doa->peak[2 * x], doa->peak[2 * x + 1], (double)doa->band_power[x]);
+                        std::printf("doa: batch %d: estimate %d band %d (bins %d..%d of %d): (%d, %d)", b, e, i, f0, (f0 + sb_width - 1) % sb_nfft, sb_nfft,
+                                    doa->peak[2 * x], doa->peak[2 * x + 1]);
+                        if (refine_levels) {
+                            const size_t r = 2 * (size_t)x * doa->refined_slots();
+                            std::printf(" = (%.3f, %.3f) deg", deg * doa->refined_angles[r], deg * doa->refined_angles[r + 1]);
+                        }
+                        std::printf(" power %.4g", (double)doa->band_power[x]);
                         // the band's beam toward its strongest direction (slot 0 is the peak, with or without --peaks)
                         if (band_beam_mode) std::printf(" beam power %.4g", (double)doa->band_beam_power[(size_t)x * doa->band_beam_slots()]);
                         std::printf("\n");
@@ -376,6 +389,10 @@ int main(int argc, char **argv)
                 for (int i = 0; i < doa->found[0]; ++i) {
                     std::snprintf(buf, sizeof(buf), " (%d, %d)", doa->directions[2 * i], doa->directions[2 * i + 1]);
                     dirs += buf;
+                    if (refine_levels) {
+                        std::snprintf(buf, sizeof(buf), " = (%.3f, %.3f) deg", deg * doa->refined_angles[2 * i], deg * doa->refined_angles[2 * i + 1]);
+                        dirs += buf;
+                    }
                     if (spectrum_kind) { std::snprintf(buf, sizeof(buf), " value %.2f dB", 10.0 * std::log10((double)doa->direction_values[i])); dirs += buf; }
                     if (beam_mode) { std::snprintf(buf, sizeof(buf), " power %.4g", (double)doa->beam_power[i]); dirs += buf; }
                 }
@@ -386,6 +403,9 @@ int main(int argc, char **argv)
             for (int e = 0; e < n; ++e) broadside += doa->peak[2 * e] == 50 && doa->peak[2 * e + 1] == 50;
             if (spectrum_kind) std::printf("doa: batch %d: peak value of the first direction %.2f dB\n", b, 10.0 * std::log10((double)doa->peak_value[0]));
             if (beam_mode) std::printf("doa: batch %d: beam power of the first direction %.4g\n", b, (double)doa->beam_power[0]);
+            if (refine_levels)
+                std::printf("doa: batch %d: first direction (%d, %d) refined to (%.3f, %.3f) deg\n", b, doa->peak[0], doa->peak[1], deg * doa->refined_angles[0],
+                            deg * doa->refined_angles[1]);
             std::printf("doa: batch %d: %d directions, first (%d, %d), last (%d, %d), %d at broadside\n", b, n, doa->peak[0], doa->peak[1], doa->peak[2 * n - 2],
                         doa->peak[2 * n - 1], broadside);
         };

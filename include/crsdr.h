@@ -721,6 +721,55 @@ int crsdr_doa_set_spectrum(crsdr_doa *doa, int kind, float loading);
 int crsdr_spectrum2d(float *pm, const float *vec, const float *sv, int m, int kind, float loading, float d, int mx, int my, int ncx, int ncy,
                      int mem_kind);
 
+/* Directions off the scan grid.  Every direction above is a grid index (cx, cy): on a 100 x 100 grid 1.8 degrees per step, where the
+ * array and the data carry far more.  The refinement is an fp64 zoom search for the maximum of the same map between the grid points:
+ * no derivatives, no iteration to convergence, the same 49 points per level whatever the data.
+ *   input   one matrix (vec, sv as published, of size M = sx * sy while smoothing runs sub-arrays), one of its directions (cx, cy),
+ *           levels L in 1 .. 8
+ *   x, y    cell coordinates (doubles), alpha = x pi / ncx, beta = y pi / ncy; the steering vector is the beam weights' fp64 expression
+ *           ph_i = 2 pi (double)d (ix cos(alpha) sin(beta) + iy cos(beta)), a_i = (cos ph_i, sin ph_i)
+ *   f(x, y) the map the object's scan computes, in fp64 from the fp32 vec / sv, y_r = v_r^H a:
+ *           MUSIC     (M / sum_{r >= k_e} |y_r|^2)^2, k_e the object's k or, with crsdr_doa_set_order, the estimate's count
+ *           BARTLETT  S,  CAPON 1 / S,  S = sum_r w_r |y_r|^2 with the w_r of crsdr_doa_set_spectrum in fp64, not rounded to fp32
+ *           sv[0] == 0: f = 0
+ *   x = cx, y = cy, s = 1/2
+ *   repeat L times:
+ *       c = f(x, y); best = c; (bx, by) = (x, y)
+ *       for i in -3..3, for j in -3..3 (row-major, i major), (i, j) != (0, 0):
+ *           px = min(max(x + i s, 0), ncx); py = min(max(y + j s, 0), ncy);  v = f(px, py)
+ *           if v > c and v > best: best = v; (bx, by) = (px, py)
+ *       (x, y) = (bx, by); s = s / 4
+ * The comparison is strict: the centre keeps ties, a NaN never wins, the lowest index wins equal values.  Level l spans +-3 s_l, the
+ * next +-(3/4) s_l around a point at most s_l / 2 from the maximum of a locally unimodal map: a near-tie between neighbouring lattice
+ * points does not lose the maximum.  |x - cx| < 2, and every coordinate is a multiple of 2^-(2L - 1): the offsets are exact in float.
+ * The definition does not pin the order of the fp64 operations inside f.
+ *
+ * crsdr_doa_set_refine: levels = 0 off, 1 .. 8 on.  From the next submit on, one more launch behind the directions and ahead of the beams
+ * refines every direction of every matrix (estimate, or estimate and band): the `count` slots of crsdr_doa_set_peaks, or the one peak
+ * while they are off.  Beams that follow the directions (nfixed = 0, wideband and band beams) then steer at the refined direction;
+ * beams at fixed angles are untouched.  Works with smoothing, the source count, subbands and all three maps.  Any time: waits for the
+ * device if a submit was made; allocates for the most matrices and slots there can be, so no other setter refuses or is refused because
+ * of it.  With levels = 0 a submit issues the launches and computes the bits it did before the call.
+ * crsdr_doa_fetch_refined (any pointer NULL = skip), per matrix and slot of the last submit (its own slot count, whatever
+ * crsdr_doa_set_peaks was called with since):
+ *   offsets [nest][slots][2] float  (x - cx, y - cy) in grid cells, exact
+ *   angles  [nest][slots][2] float  (alpha, beta) in radians, rounded once from fp64: the convention of fixed_angles
+ *   values  [nest][slots]    float  f at the refined point
+ * Empty slots (from found on) hold (0, 0), (-1, -1) and -1.  CRSDR_ESTATE without crsdr_doa_set_refine, or before the first submit after it.
+ * crsdr_doa_refined_buffers: the device addresses (NULL while off), and the slots per matrix a fetch would read. */
+int crsdr_doa_set_refine(crsdr_doa *doa, int levels);
+int crsdr_doa_fetch_refined(crsdr_doa *doa, float *offsets, float *angles, float *values);
+int crsdr_doa_refined_buffers(crsdr_doa *doa, void **offsets, void **angles, void **values, int *slots);
+
+/* The per-op form: the same kernel on one matrix, bit for bit.
+ *   vec [m][m][2] and sv [m] as crsdr_noisesubspace writes them, 2 <= m = mx * my <= 64;  kind CRSDR_SPECTRUM_*; k: the sources (MUSIC:
+ *   1 <= k < m, ignored otherwise); loading: CAPON's, in [1e-6, 1];  peaks [npeaks][2] int32 (cx, cy), 1 <= npeaks <= 16 (a direction
+ *   outside [0, ncx] x [0, ncy] is an empty slot);  levels 1 .. 8;  offsets, angles [npeaks][2], values [npeaks]
+ * Every argument is checked before a device is touched.  mem_kind: CRSDR_MEM_HOST (copied) or CRSDR_MEM_DEVICE (all on the device: vec
+ * 8-byte, the others 4-byte aligned). */
+int crsdr_refine2d(float *offsets, float *angles, float *values, const float *vec, const float *sv, int m, int kind, int k, float loading, float d, int mx,
+                   int my, int ncx, int ncy, const int32_t *peaks, int npeaks, int levels, int mem_kind);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,8 @@
       then the 64 packets and vec of every band matrix copied to page-locked host memory (before any host arithmetic).
   (m) with --spectrum bartlett|capon (--loading X): crsdr_doa_set_spectrum, then the (b) submit + peaks: the power map in the scan's place,
       against the MUSIC submit (b) of the same build and, with --doa-lib, of another (lib:b) in the same alternation.
+  (r) with --refine L [--peaks COUNT --radius R]: crsdr_doa_set_refine(L) on an object like (p)'s (or (b)'s without --peaks), then the
+      submit + directions (or peaks) + crsdr_doa_fetch_refined: against (p) (or (b)) of the same build in the same alternation.
 --array MXxMY runs everything on another array than the 7 x 3 one (8x8: M = 64, the largest).
 
 --runs runs of each, alternating a, b, c in one session (two worker processes, both alive throughout); medians and ranges.
@@ -30,7 +32,7 @@ the same alternation, reported as lib:b and lib:c.  --reps N: every (b), (c), (p
 Also: what crsdr_doa_submit_plan + the peak fetch add to a 22-row, T = 64 plan batch (plan.submit + sync against
 plan.submit + doa.submit_plan + fetch).  --json FILE keeps the record; --once MODE runs three submit + fetch and exits (for a kernel trace): b, c, p, q as above, q64 = the
 beams at their largest shape (8 x 8 array, 16 slots: 65 rows x 16384, 64 blocks), s = --smooth / --fb / --order as given, all on one object,
-u = --subbands / --window as given, v = u with --peaks and --band-beams as given, m = --spectrum as given."""
+u = --subbands / --window as given, v = u with --peaks and --band-beams as given, m = --spectrum as given, r = --refine with --peaks as given."""
 import argparse, importlib, json, os, subprocess, sys, time
 import numpy as np
 
@@ -109,7 +111,7 @@ def worker_perop():
 
 
 def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None, fb=False, order=None, subbands=None, window="rect", band_beams=None,
-               spectrum=None):
+               spectrum=None, refine=0):
     """(b), (c), (p), (q), (h), (f), (s), (o) and the plan figures: 'b' / 'c' / 'p' / 'q' / 'h' / 'f' / 's' / 'o' / 'plan' / 'plan+doa' on
     stdin -> seconds of one batch of 64 on stdout."""
     torch, ura, b, dev, pk, off, stride, host = _setup()
@@ -144,6 +146,12 @@ def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None
     if spectrum:
         extra["m"] = b.Doa(NROWS, B, 1, ura.D, *ARRAY, max_batch=T)
         extra["m"].set_spectrum(SPECTRA[spectrum], loading)
+    rdoa = None
+    if refine:
+        rdoa = b.Doa(NROWS, B, 1, ura.D, *ARRAY, max_batch=T)
+        if npeaks:
+            rdoa.set_peaks(npeaks, radius)
+        rdoa.set_refine(refine)
     udoa = None
     if subbands:
         udoa = b.Doa(NROWS, B, 1, ura.D, *ARRAY, max_batch=T)
@@ -171,6 +179,12 @@ def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None
             wpinned.copy_(pk, non_blocking=True)
             wdoa.fetch_subspace()
             torch.cuda.synchronize()
+
+    def run_r():
+        for _ in range(reps):
+            rdoa.submit(pk.data_ptr(), stride, off, T)
+            rdoa.fetch_directions() if npeaks else rdoa.fetch_peaks()
+            rdoa.fetch_refined()
 
     def run_u():
         for _ in range(reps):
@@ -231,6 +245,8 @@ def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None
         jobs["q"], jobs["h"] = (run_q, reps), (run_h, reps)
     for key, d in extra.items():
         jobs[key] = (run_extra(d), reps)
+    if rdoa is not None:
+        jobs["r"] = (run_r, reps)
     if udoa is not None:
         jobs["u"] = (run_u, reps)
     if vdoa is not None:
@@ -245,15 +261,18 @@ def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None
         print((time.perf_counter() - t0) / n, flush=True)
 
 
-def once(mode, npeaks=0, radius=1, beams=None, loading=1e-2, smooth=None, fb=False, order=None, subbands=None, window="rect", band_beams=None, spectrum=None):
+def once(mode, npeaks=0, radius=1, beams=None, loading=1e-2, smooth=None, fb=False, order=None, subbands=None, window="rect", band_beams=None, spectrum=None,
+         refine=0):
     mx, my = (8, 8) if mode == "q64" else (None, None)
     torch, ura, b, dev, pk, off, stride, _ = _setup(mx, my)
     mx, my = mx or ARRAY[0], my or ARRAY[1]
     d = b.Doa(1 + mx * my, B, 1, ura.D, mx, my, max_batch=T, flags=b.DOA_KEEP_SPECTRUM if mode == "c" else 0)
     if mode == "q64":
         npeaks, radius = 16, 1
-    if mode in ("p", "q", "q64") and npeaks:
+    if mode in ("p", "q", "q64", "r") and npeaks:
         d.set_peaks(npeaks, radius)
+    if mode == "r":
+        d.set_refine(refine or 5)
     if mode in ("q", "q64"):
         d.set_beams(BEAM_MODES[beams or "mvdr"], loading)
     if mode == "s":
@@ -279,7 +298,9 @@ def once(mode, npeaks=0, radius=1, beams=None, loading=1e-2, smooth=None, fb=Fal
         print("peak values of the first four, dB", np.round(10 * np.log10(out["peak_value"][:4]), 2).tolist())
     if mode == "s" and order:
         print("k", d.fetch_order()["k"].tolist())
-    if mode in ("p", "q", "q64") and npeaks:
+    if mode == "r":
+        print("refined offsets of the first", d.fetch_refined()["offsets"][0].tolist())
+    if mode in ("p", "q", "q64", "r") and npeaks:
         print("directions of the first", d.fetch_directions()["peaks"][0].tolist())
     if mode == "v":
         print("slots", d.nbandbeams, "band beam power of the first estimate", d.fetch_subband_beams(weights=False, beams=False)["power"][:d.nbands].tolist())
@@ -317,7 +338,8 @@ def _stat(xs):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--worker", choices=["perop", "doa"])
-    ap.add_argument("--once", choices=["b", "c", "p", "q", "q64", "s", "u", "v", "m"])
+    ap.add_argument("--once", choices=["b", "c", "p", "q", "q64", "s", "u", "v", "m", "r"])
+    ap.add_argument("--refine", type=int, default=0, metavar="L", help="(r): the directions refined off the grid by L levels (crsdr_doa_set_refine)")
     ap.add_argument("--spectrum", choices=sorted(SPECTRA), default=None, help="(m): this power map in the scan's place (crsdr_doa_set_spectrum, --loading for capon)")
     ap.add_argument("--array", default=None, metavar="MXxMY", help="the array, 2 <= MX MY <= 64 (default 7x3)")
     ap.add_argument("--subbands", default=None, metavar="NFFT:FIRST:COUNT[:WIDTH]", help="(u): a covariance per frequency band (crsdr_doa_set_subbands)")
@@ -340,11 +362,11 @@ def main():
     shape = ["--array", a.array] if a.array else []
     if a.worker:
         return worker_perop() if a.worker == "perop" else worker_doa(a.peaks, a.radius, a.reps, a.beams, a.loading, a.smooth, a.fb, a.order, a.subbands, a.window,
-                                                                           a.band_beams, a.spectrum)
+                                                                           a.band_beams, a.spectrum, a.refine)
     if a.band_beams and not a.subbands:
         ap.error("--band-beams needs --subbands")
     if a.once:
-        return once(a.once, a.peaks, a.radius, a.beams, a.loading, a.smooth, a.fb, a.order, a.subbands, a.window, a.band_beams, a.spectrum)
+        return once(a.once, a.peaks, a.radius, a.beams, a.loading, a.smooth, a.fb, a.order, a.subbands, a.window, a.band_beams, a.spectrum, a.refine)
     pargs = shape + ["--peaks", str(a.peaks), "--radius", str(a.radius), "--reps", str(a.reps), "--loading", str(a.loading)]
     if a.spectrum:
         pargs += ["--spectrum", a.spectrum]
@@ -360,7 +382,9 @@ def main():
         pargs += ["--subbands", a.subbands, "--window", a.window]
     if a.band_beams:
         pargs += ["--band-beams", a.band_beams]
-    legs = (["f"] if a.fb else []) + (["s"] if a.smooth else []) + (["o"] if a.order else []) + (["u"] if a.subbands else []) + (["v", "w"] if a.band_beams else []) + (["m"] if a.spectrum else [])
+    if a.refine:
+        pargs += ["--refine", str(a.refine)]
+    legs = (["f"] if a.fb else []) + (["s"] if a.smooth else []) + (["o"] if a.order else []) + (["u"] if a.subbands else []) + (["v", "w"] if a.band_beams else []) + (["m"] if a.spectrum else []) + (["r"] if a.refine else [])
     wa, wb = Worker("perop", a.perop_lib, extra=shape), Worker("doa", extra=pargs)
     wl = Worker("doa", a.doa_lib, extra=shape + ["--reps", str(a.reps)]) if a.doa_lib else None
     keys = ["a", "b", "c", "plan", "plan+doa"] + (["lib:b", "lib:c"] if wl else []) + (["p"] if a.peaks else []) + (["q", "h"] if a.beams else []) + legs
@@ -393,7 +417,7 @@ def main():
            "smoothing": {"sub_array": a.smooth, "fb": a.fb} if (a.smooth or a.fb) else None, "order": a.order,
            "subbands": dict(zip(("nfft", "first", "nbands", "width"), _bands(a.subbands)), window=a.window) if a.subbands else None,
            "band_beams": {"mode": a.band_beams, "loading": a.loading} if a.band_beams else None,
-           "spectrum": {"kind": a.spectrum, "loading": a.loading} if a.spectrum else None,
+           "spectrum": {"kind": a.spectrum, "loading": a.loading} if a.spectrum else None, "refine": a.refine or None,
            "ms_per_batch": {k: _stat([1e3 * x for x in v]) for k, v in sec.items()},
            "frames_per_s": {k: _stat([T / x for x in sec[k]]) for k in ("a", "b", "c") + (("u",) if a.subbands else ())}}
     if a.subbands:
@@ -407,7 +431,7 @@ def main():
              "f": "FB alone: submit + peaks", "s": f"{a.smooth}{' + FB' if a.fb else ''}: submit + peaks", "o": f"order {a.order}: submit + peaks",
              "u": f"subbands {a.subbands} {a.window}: submit + peaks + power",
              "v": f"subbands + {a.band_beams} band beams: submit + power", "w": "subbands: packets and vec to the host",
-             "m": f"{a.spectrum} map: submit + peaks"}
+             "m": f"{a.spectrum} map: submit + peaks", "r": f"refine {a.refine}: submit + directions + refined"}
     for k, s in rec["ms_per_batch"].items():
         fps = f"  {T / (1e-3 * s['median']):10.0f} frames/s" if k in rec["frames_per_s"] else ""
         print(f"({k}) {names[k]:34s} {s['median']:8.3f} ms per 64 blocks  [{s['min']:.3f} .. {s['max']:.3f}]{fps}")
@@ -421,6 +445,11 @@ def main():
     if a.band_beams:
         rec["v_over_w_ms"] = rec["ms_per_batch"]["v"]["median"] / rec["ms_per_batch"]["w"]["median"]
         print(f"(v) takes {rec['v_over_w_ms']:.2f} x the time of (w)")
+    if a.refine:
+        base = "p" if a.peaks else "b"
+        rec["r_adds_ms_per_batch_over"] = base
+        rec["r_adds_ms_per_batch"] = rec["ms_per_batch"]["r"]["median"] - rec["ms_per_batch"][base]["median"]
+        print(f"(r) adds {1e3 * rec['r_adds_ms_per_batch']:.0f} us to ({base}), the same submit without the refinement")
     if a.spectrum:
         rec["m_over_b_ms"] = rec["ms_per_batch"]["m"]["median"] / rec["ms_per_batch"]["b"]["median"]
         print(f"(m) takes {rec['m_over_b_ms']:.3f} x the time of (b), the MUSIC submit at k = 1; the scan's operation count is M / (M - 1) = {M / (M - 1):.3f} x")
