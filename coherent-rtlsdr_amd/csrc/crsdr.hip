@@ -338,7 +338,7 @@ static hipError_t launch_xcorr_lag14(hipStream_t s, char variant, const XcorrArg
     static long launches = 0;
     const int qspin = sw().qspin.at(launches++);
     const hipError_t e = launch_lds(x14p::k_xcorr_lag14q, dim3((unsigned)std::max(1, std::min(device_cus(), (items + 1) / 2))), dim3(2 * x14p::QG),
-                                    x14p::LDSQ_BYTES, s, a, twA, twB, row_count, waitflag, work, *work_base, qspin);
+                                    x14p::LDSQ14_BYTES, s, a, twA, twB, row_count, waitflag, work, *work_base, qspin);
     if (e == hipSuccess) *work_base += (unsigned)items;      // a launch that ran advances the device counter by exactly its item count (xcorr14q.hpp)
     return e;
 }

@@ -23,6 +23,12 @@ constexpr int QG = 256;                                       // threads per row
 // neighbour there); k_rows14_cf32q only uses the sync words
 constexpr int QSCR_BYTES = 64 + 4 * 2 * 64 * 4;
 constexpr int LDSQ_BYTES = LDS_ELEMS * 8 + 2 * QSCR_BYTES + 64;      // image + scratch per group + sync words (sizeof(QSync) <= 64)
+// k_xcorr_lag14q only: the middle passes' twiddle chains w[1..31] of the 16 columns n = tid & 15, built once per workgroup,
+// behind the sync words as [k - 1][n].  Conflict-free: a wave's ds_read_b64 of one k touches 16 consecutive 8-byte slots
+// (128 bytes = each of the 32 banks once), and the four lanes that share an n read the same address.
+constexpr int QTWB_BYTES = 31 * 16 * 8;
+constexpr int LDSQ14_BYTES = LDSQ_BYTES + QTWB_BYTES;
+static_assert(LDSQ14_BYTES <= 160 * 1024, "the two-row K1's image, scratch and twiddle table must fit a CU's LDS");
 constexpr int kQSpinLimit = 1 << 18;
 #ifndef Q_PRIO
 #define Q_PRIO 3
@@ -299,7 +305,15 @@ __global__ __launch_bounds__(2 * QG, 1) void k_xcorr_lag14q(XcorrArgs a, const f
     int *redi = reinterpret_cast<int *>(red);
     float *edge = red + 16;                                                                      // [wave][first lane, last lane][half * 32 + i]
     QSync *sy = reinterpret_cast<QSync *>(smem + (size_t)LDS_ELEMS * 8 + 2 * QSCR_BYTES);
+    c2 *twl = reinterpret_cast<c2 *>(smem + LDSQ_BYTES);      // [k - 1][n]: the P1 / P1' chain of column n, with the bits tw_load gave every row
     if (threadIdx.x == 0) { sy->owner = 0; sy->relcnt = 0; sy->bar[0] = 0; sy->bar[1] = 0; sy->err = 0; sy->next[0] = 0; sy->next[1] = 0; sy->spin_limit = spin_limit; sy->arrive[0] = 0; sy->arrive[1] = 0; }
+    if (threadIdx.x >= 64 && threadIdx.x < 80) {               // 16 lanes of a wave that does not write the sync words
+        const int n = threadIdx.x - 64;
+        c2 w[32];
+        tw_load(w, twB, TWB_STRIDE, n);
+#pragma unroll
+        for (int kk = 1; kk < 32; ++kk) twl[(kk - 1) * 16 + n] = w[kk];
+    }
     __syncthreads();
     int gen = 0;
 #ifdef CRSDR_QDEBUG
@@ -334,7 +348,13 @@ __global__ __launch_bounds__(2 * QG, 1) void k_xcorr_lag14q(XcorrArgs a, const f
             c2 v[32], v2[32];
             q_p0_compute(v, src, twA, a.xor80, vt0);      // no LDS yet: both halves run beside the other group's middle section
             q_p0_compute(v2, src, twA, a.xor80, vt1);
-            tw_load(wB, twB, TWB_STRIDE, tid & 15);       // P1 / P1' twiddles: table loads and product chain outside the ownership window
+            {
+                // P1 / P1' twiddles: from the workgroup's table (no chain per row), outside the ownership window
+                int nb = tid & 15;
+                asm volatile("" : "+v"(nb));
+#pragma unroll
+                for (int kk = 1; kk < 32; ++kk) wB[kk] = *(const volatile lds_c2 *)(twl + (kk - 1) * 16 + nb);      // ds_read_b64, not read2 (see pass1_forward)
+            }
             q_acquire(sy, 2 * k + g + 1);
             __builtin_amdgcn_s_setprio(Q_PRIO);                // the owner's window is what the pair's period is made of
             q_p0_store(A, v, vt0);

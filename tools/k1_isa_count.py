@@ -27,16 +27,27 @@ def compile_asm(out):
                    stderr=subprocess.DEVNULL)
 
 
-def kernel_bodies(txt):
-    """{mangled name: list of instruction mnemonics} for every kernel symbol in the assembly."""
+def kernel_bodies(txt, loops_only=False):
+    """{mangled name: list of instruction mnemonics} for every kernel symbol in the assembly.
+
+    loops_only: only the instructions of basic blocks that the assembly's block comments place in a loop (for
+    k_xcorr_lag14q: the row loop, without what a workgroup does once before and after it)."""
     out = {}
     for m in re.finditer(r"^(_Z\S+):\s*;\s*@\1\n(.*?)^\.Lfunc_end", txt, re.S | re.M):
         mn = []
+        in_loop = False
         for line in m.group(2).splitlines():
             s = line.strip()
+            if re.match(r"(\.LBB\d+_\d+:|; %bb\.\d+:)", s):        # a new block: its comment (and the lines below it) say whether it is in a loop
+                in_loop = "Loop" in s
+                continue
+            if s.startswith(";") and "Loop" in s and ("Header" in s or "Parent" in s):
+                in_loop = True
+                continue
             if not s or s.startswith((";", ".", "_")) or s.endswith(":"):
                 continue
-            mn.append(s.split()[0])
+            if in_loop or not loops_only:
+                mn.append(s.split()[0])
         out[m.group(1)] = mn
     return out
 
@@ -58,6 +69,8 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--asm", help="read this device assembly instead of compiling")
     ap.add_argument("--pattern", default=r"k_xcorr_lag14[pq]|k_ref_spectrum14p")
+    ap.add_argument("--loops", action="store_true",
+                    help="count only instructions inside loops (k_xcorr_lag14q: per row pair, without the workgroup's one-off prologue)")
     args = ap.parse_args()
     if args.asm:
         txt = open(args.asm).read()
@@ -66,7 +79,7 @@ def main():
             path = os.path.join(d, "crsdr.s")
             compile_asm(path)
             txt = open(path).read()
-    bodies, meta = kernel_bodies(txt), metadata(txt)
+    bodies, meta = kernel_bodies(txt, args.loops), metadata(txt)
     pat = re.compile(args.pattern)
     print(f"{'kernel':22s} {'VALU':>6s} {'packed':>6s} {'pk_add':>6s} {'pk_mul':>6s} {'pk_fma':>6s} {'SALU':>5s} "
           f"{'VGPR':>4s} {'SGPR':>4s} {'vspill':>6s} {'sspill':>6s} {'scratch':>7s}")

@@ -41,7 +41,7 @@ int main(int argc, char **argv)
     unsigned int *work; CK(hipMalloc(&work, 4)); CK(hipMemset(work, 0, 4));
     CK(hipFuncSetAttribute((const void *)x14::k_ref_spectrum14, hipFuncAttributeMaxDynamicSharedMemorySize, x14::LDS_BYTES));
     CK(hipFuncSetAttribute((const void *)x14p::k_xcorr_lag14p, hipFuncAttributeMaxDynamicSharedMemorySize, x14::LDS_BYTES));
-    CK(hipFuncSetAttribute((const void *)x14p::k_xcorr_lag14q, hipFuncAttributeMaxDynamicSharedMemorySize, x14p::LDSQ_BYTES));
+    CK(hipFuncSetAttribute((const void *)x14p::k_xcorr_lag14q, hipFuncAttributeMaxDynamicSharedMemorySize, x14p::LDSQ14_BYTES));
     hipLaunchKernelGGL(x14::k_ref_spectrum14, dim3(T), dim3(512), x14::LDS_BYTES, 0, d_rows, (size_t)rows * N, twA, twB, (float4 *)refspec, 0u);
     uint8_t *d_mask = nullptr;
     if (argc > 3 && atoi(argv[3])) {
@@ -69,7 +69,7 @@ int main(int argc, char **argv)
         if (hogs) { hipLaunchKernelGGL(k_hog, dim3(hogs), dim3(256), 0, hs, 1000000LL /* ~0.45 ms */, err); }
         unsigned long long *null = nullptr;
         CK(hipMemcpyToSymbol(HIP_SYMBOL(x14p::dbg__), rep == 7 ? &dbg : &null, sizeof(dbg)));
-        CK(hipEventRecord(e0)); hipLaunchKernelGGL(x14p::k_xcorr_lag14q, dim3(grid), dim3(512), x14p::LDSQ_BYTES, 0, xa, twA, twB, rows - 1, err, work, (unsigned)(rep * (rows - 1) * T), x14p::kQSpinLimit); CK(hipEventRecord(e1));
+        CK(hipEventRecord(e0)); hipLaunchKernelGGL(x14p::k_xcorr_lag14q, dim3(grid), dim3(512), x14p::LDSQ14_BYTES, 0, xa, twA, twB, rows - 1, err, work, (unsigned)(rep * (rows - 1) * T), x14p::kQSpinLimit); CK(hipEventRecord(e1));
         CK(hipEventSynchronize(e1)); CK(hipEventElapsedTime(&ms, e0, e1));
         if (rep && rep < 7) best = std::min(best, ms);
         CK(hipStreamSynchronize(hs));
