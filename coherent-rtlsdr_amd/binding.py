@@ -44,7 +44,12 @@ ABI_SYMBOLS = [
     "crsdr_doa_set_subband_beams", "crsdr_doa_fetch_subband_beams", "crsdr_doa_subband_beam_buffers", "crsdr_subband_beamform",
     "crsdr_doa_set_spectrum", "crsdr_spectrum2d",
     "crsdr_doa_set_refine", "crsdr_doa_fetch_refined", "crsdr_doa_refined_buffers", "crsdr_refine2d",
+    "crsdr_doa_set_esprit", "crsdr_doa_fetch_esprit", "crsdr_doa_esprit_buffers", "crsdr_esprit2d",
 ]
+ESPRIT_OFF, ESPRIT_BESIDE, ESPRIT_ONLY = 0, 1, 2
+ESPRIT_STATUS_ITERATIONS, ESPRIT_STATUS_PIVOT = 1, 2          # status bits 0 and 1
+ESPRIT_FLAG_BETA, ESPRIT_FLAG_ALPHA = 1, 2                    # flag bits 0 and 1: cos(beta), cos(alpha) clamped
+ESPRIT_MAX_K = 16
 DOA_KEEP_SPECTRUM, DOA_KEEP_RXX = 1, 2
 BEAM_OFF, BEAM_CONVENTIONAL, BEAM_MVDR = 0, 1, 2
 SMOOTH_FB = 1
@@ -210,6 +215,12 @@ def lib():
         L.crsdr_doa_refined_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int)]
         L.crsdr_refine2d.argtypes = [f32p, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, i32p,
                                      C.c_int, C.c_int, C.c_int]
+    if hasattr(L, "crsdr_doa_set_esprit"):           # (likewise: an older build has the scans alone)
+        f64p = C.POINTER(C.c_double)
+        L.crsdr_doa_set_esprit.argtypes = [vp, C.c_int]
+        L.crsdr_doa_fetch_esprit.argtypes = [vp, i32p, i32p, f64p, f32p, f32p, f32p, i32p]
+        L.crsdr_doa_esprit_buffers.argtypes = [vp] + [C.POINTER(vp)] * 7 + [C.POINTER(C.c_int)]
+        L.crsdr_esprit2d.argtypes = [i32p, i32p, f64p, f32p, f32p, f32p, i32p, f32p, f32p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int]
     _lib = L
     return L
 
@@ -407,6 +418,22 @@ def refine2d(vec, sv, kind, peaks, d, mx, my, ncx=100, ncy=100, k=1, loading=1e-
     _check(lib().crsdr_refine2d(_p(off, C.c_float), _p(ang, C.c_float), _p(val, C.c_float), _p(v.view(np.float32), C.c_float), _p(s, C.c_float), M, int(kind),
                                 int(k), C.c_float(loading), C.c_float(d), int(mx), int(my), int(ncx), int(ncy), _p(pk, C.c_int32), n, int(levels), MEM_HOST))
     return {"offsets": off, "angles": ang, "values": val}
+
+
+def esprit2d(vec, sv, k, d, mx, my):
+    """crsdr_esprit2d: the k directions of the subspace (vec, sv) of an mx x my array by 2-D ESPRIT, no grid.  found, status; phases [k][2]
+    float64 (mu, nu); angles [k][2] (alpha, beta) in radians; modulus [k][2]; power [k]; flags [k]."""
+    v = np.ascontiguousarray(vec, dtype=np.complex64)
+    s = np.ascontiguousarray(sv, dtype=np.float32)
+    M, n = v.shape[0], max(int(k), 0)
+    if v.shape != (M, M) or s.shape != (M,):
+        raise ValueError("vec must be [m][m] and sv [m]")
+    found, status = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+    ph, ang, mod = np.zeros((n, 2), dtype=np.float64), np.zeros((n, 2), dtype=np.float32), np.zeros((n, 2), dtype=np.float32)
+    pw, fl = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.int32)
+    _check(lib().crsdr_esprit2d(_p(found, C.c_int32), _p(status, C.c_int32), _p(ph, C.c_double), _p(ang, C.c_float), _p(mod, C.c_float), _p(pw, C.c_float),
+                                _p(fl, C.c_int32), _p(v.view(np.float32), C.c_float), _p(s, C.c_float), M, int(k), C.c_float(d), int(mx), int(my), MEM_HOST))
+    return {"found": int(found[0]), "status": int(status[0]), "phases": ph, "angles": ang, "modulus": mod, "power": pw, "flags": fl}
 
 
 def beamform(matrix, weights):
@@ -757,6 +784,7 @@ class Doa:
         self.mx, self.my, self.ms, self.order = int(mx), int(my), self.m, None      # ms: the subspace's size; order: (kmin, kmax)
         self.nbands = 0                                                             # set_subbands: bands per estimate (0: off)
         self.band_shape, self.nbandbeams = None, 0                                  # set_subbands: (J, width); set_subband_beams: slots
+        self.esprit = ESPRIT_OFF                                                    # set_esprit: the mode
 
     def _last(self):
         nest, launches = C.c_int(0), C.c_int(0)
@@ -780,11 +808,13 @@ class Doa:
         want_rxx = bool(self.flags & DOA_KEEP_RXX) if rxx is None else bool(rxx)
         peak, val = np.zeros((n, 2), dtype=np.int32), np.zeros(n, dtype=np.float32)
         sv, status = np.zeros((n, self.ms), dtype=np.float32), np.zeros(n, dtype=np.int32)
+        if self.esprit == ESPRIT_ONLY:                   # no scan ran: there is no peak, peak_value or pm to ask for
+            peak, val, want_pm = None, None, False
         pm = np.zeros((n, self.ncx, self.ncy), dtype=np.float32) if want_pm else None
         r = np.zeros((n, self.m, self.m), dtype=np.complex64) if want_rxx else None
         _check(lib().crsdr_doa_fetch(self._h, _p(peak, C.c_int32), _p(val, C.c_float), _p(sv, C.c_float), _p(status, C.c_int32),
                                      _p(pm, C.c_float), _p(None if r is None else r.view(np.float32), C.c_float)))
-        out = {"peak": peak, "peak_value": val, "sv": sv, "status": status}
+        out = {"peak": peak, "peak_value": val, "sv": sv, "status": status} if peak is not None else {"sv": sv, "status": status}
         if pm is not None:
             out["pm"] = pm
         if r is not None:
@@ -960,6 +990,36 @@ class Doa:
         M = np.asarray(vec).shape[0]
         sx, sy = (self.mx, self.my) if M == self.m else self._sub
         return refine2d(vec, sv, kind, peaks, self.d, sx, sy, self.ncx, self.ncy, k=self.k if k is None else k, loading=loading, levels=levels)
+
+    def set_esprit(self, mode: int = ESPRIT_BESIDE):
+        """crsdr_doa_set_esprit: from the next submit on the k directions of every matrix by 2-D ESPRIT, beside the scan (ESPRIT_BESIDE)
+        or in its place (ESPRIT_ONLY: no scan, peak, local peaks or refinement are issued).  ESPRIT_OFF: off.  Waits for the device if a
+        submit was made."""
+        _check(lib().crsdr_doa_set_esprit(self._h, int(mode)))
+        self.esprit = int(mode)
+
+    def fetch_esprit(self, want=None) -> dict:
+        """Waits for the last submit.  found, status [nest]; phases [nest][slots][2] float64 (mu, nu); angles [nest][slots][2] (alpha, beta
+        in radians); modulus [nest][slots][2]; power, flags [nest][slots]; empty slots hold (0, 0), (-1, -1), (-1, -1), -1 and 0.
+        want: the names to copy (a copy each), None: all seven."""
+        n, c = self._last()[0], self.esprit_buffers()["slots"]
+        shapes = (("found", (n,), np.int32, C.c_int32), ("status", (n,), np.int32, C.c_int32), ("phases", (n, c, 2), np.float64, C.c_double),
+                  ("angles", (n, c, 2), np.float32, C.c_float), ("modulus", (n, c, 2), np.float32, C.c_float), ("power", (n, c), np.float32, C.c_float),
+                  ("flags", (n, c), np.int32, C.c_int32))
+        out = {name: np.zeros(shape, dtype=dt) if want is None or name in want else None for name, shape, dt, _ in shapes}
+        _check(lib().crsdr_doa_fetch_esprit(self._h, *[_p(out[name], ct) for name, _, _, ct in shapes]))
+        return {name: a for name, a in out.items() if a is not None}
+
+    def esprit_buffers(self) -> dict:
+        ptrs, slots = [C.c_void_p() for _ in range(7)], C.c_int(0)
+        _check(lib().crsdr_doa_esprit_buffers(self._h, *[C.byref(p) for p in ptrs], C.byref(slots)))
+        return dict(zip(("found", "status", "phases", "angles", "modulus", "power", "flags"), [p.value for p in ptrs]), slots=slots.value)
+
+    def esprit2d(self, vec, sv, k=None) -> dict:
+        """crsdr_esprit2d with this object's geometry (the sub-arrays' while smoothing is on) on one matrix's vec and sv."""
+        M = np.asarray(vec).shape[0]
+        sx, sy = (self.mx, self.my) if M == self.m else self._sub
+        return esprit2d(vec, sv, self.k if k is None else k, self.d, sx, sy)
 
     def last_launches(self) -> int:
         return self._last()[1]

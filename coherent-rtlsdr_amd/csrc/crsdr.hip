@@ -10,6 +10,7 @@
 #include "subband_beams.hpp"
 #include "spectrum.hpp"
 #include "refine.hpp"
+#include "esprit.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -468,8 +469,8 @@ static hipError_t launch_frac_apply(hipStream_t s, int row_count, int nblocks, c
 namespace {
 struct OpCtx {
     std::mutex mu;
-    void *buf[6] = {};                                        // [3]: the tiled covariance's partial sums; [4], [5]: crsdr_refine2d's further arguments
-    size_t cap[6] = {};
+    void *buf[9] = {};                                        // [3]: the tiled covariance's partial sums; [4], [5]: crsdr_refine2d's further arguments; .. [8]: crsdr_esprit2d's
+    size_t cap[9] = {};
     float2 *tw[kMaxLog2 + 1] = {};
     int tw_dev[kMaxLog2 + 1] = {};
     int dev = -1;
@@ -481,7 +482,7 @@ int op_reserve(int slot, size_t bytes)
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     if (g_op.dev != dev) {
-        for (int i = 0; i < 6; ++i) { if (g_op.buf[i]) (void)hipFree(g_op.buf[i]); g_op.buf[i] = nullptr; g_op.cap[i] = 0; }
+        for (int i = 0; i < 9; ++i) { if (g_op.buf[i]) (void)hipFree(g_op.buf[i]); g_op.buf[i] = nullptr; g_op.cap[i] = 0; }
         for (int i = 0; i <= kMaxLog2; ++i) { if (g_op.tw[i]) (void)hipFree(g_op.tw[i]); g_op.tw[i] = nullptr; }
         g_op.dev = dev;
     }
@@ -2041,5 +2042,51 @@ extern "C" int crsdr_refine2d(float *offsets, float *angles, float *values, cons
     st.back(offsets, d_o, n2);
     st.back(angles, d_a, n2);
     st.back(values, d_f, n2 / 2);
+    return st.finish();
+}
+
+// ================================================================================================
+// (iv) continued: the gridless directions (esprit.hpp).  As above: the kernels' first use is here, behind every other kernel's
+// ================================================================================================
+static void doa_esprit_enqueue(unsigned nmat, hipStream_t S, const float2 *vec, const float *sv, int M, int k, const int32_t *korder, float d, int SX, int SY, int slots,
+                               int32_t *found, int32_t *status, double *phases, float *angles, float *modulus, float *power, int32_t *flags)
+{
+    hipLaunchKernelGGL(esprit::k_doa_esprit<esprit::ES_WAVES>, dim3(nmat), dim3(esprit::ES_THREADS), 0, S, vec, sv, M, k, korder, d, SX, SY, slots, found, status, phases, angles, modulus,
+                       power, flags);
+}
+
+extern "C" int crsdr_esprit2d(int32_t *found, int32_t *status, double *phases, float *angles, float *modulus, float *power, int32_t *flags, const float *vec,
+                              const float *sv, int m, int k, float d, int mx, int my, int mem_kind)
+{
+    if (!found || !status || !phases || !angles || !modulus || !power || !flags || !vec || !sv)
+        return fail(CRSDR_EINVAL, "esprit2d: need found, status, phases, angles, modulus, power, flags, vec, sv");
+    if (mx < 2 || my < 2 || m > esprit::MAX_M || (long long)mx * my != m)
+        return fail(CRSDR_EINVAL, "esprit2d: m = %d must be mx * my (%d x %d, each at least 2) and at most %d", m, mx, my, esprit::MAX_M);
+    if (k < 1 || k > esprit_rank_limit(mx, my))
+        return fail(CRSDR_EINVAL, "esprit2d: k = %d sources (1..%d: at most %d, and the rows a %d x %d array keeps when it drops a column or a row)", k,
+                    esprit_rank_limit(mx, my), esprit::MAX_K, mx, my);
+    OP_PROLOGUE_MEM("esprit2d", mem_kind);
+    const size_t mm = sizeof(float2) * (size_t)m * m, n = (size_t)k;
+    OpStage st(mem_kind);
+    const float2 *d_v = (const float2 *)st.in(0, vec, mm, 8);
+    const float *d_s = (const float *)st.in(1, sv, sizeof(float) * (size_t)m, 4);
+    double *d_ph = (double *)st.out(2, phases, sizeof(double) * 2 * n, 8);
+    float *d_an = (float *)st.out(3, angles, sizeof(float) * 2 * n, 4);
+    float *d_mo = (float *)st.out(4, modulus, sizeof(float) * 2 * n, 4);
+    float *d_pw = (float *)st.out(5, power, sizeof(float) * n, 4);
+    int32_t *d_fl = (int32_t *)st.out(6, flags, sizeof(int32_t) * n, 4);
+    int32_t *d_fo = (int32_t *)st.out(7, found, sizeof(int32_t), 4);
+    int32_t *d_st = (int32_t *)st.out(8, status, sizeof(int32_t), 4);
+    if (st.rc) return st.rc;
+    if (st.misaligned) return fail(CRSDR_EINVAL, "esprit2d: device vec and phases 8-byte, every other pointer 4-byte aligned");
+    hipLaunchKernelGGL(esprit::k_esprit2d<esprit::ES_WAVES>, dim3(1), dim3(esprit::ES_THREADS), 0, 0, d_v, d_s, m, k, d, mx, my, d_fo, d_st, d_ph, d_an, d_mo, d_pw, d_fl);
+    HIP_TRY(hipGetLastError());
+    st.back(phases, d_ph, sizeof(double) * 2 * n);
+    st.back(angles, d_an, sizeof(float) * 2 * n);
+    st.back(modulus, d_mo, sizeof(float) * 2 * n);
+    st.back(power, d_pw, sizeof(float) * n);
+    st.back(flags, d_fl, sizeof(int32_t) * n);
+    st.back(found, d_fo, sizeof(int32_t));
+    st.back(status, d_st, sizeof(int32_t));
     return st.finish();
 }

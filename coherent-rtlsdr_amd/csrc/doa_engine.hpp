@@ -11,6 +11,8 @@
 //      it: the beam weights per (estimate, band) and subband_beams.hpp's apply kernel on the rows' band spectra.  crsdr_doa_set_spectrum
 //      replaces the scan's kernel by spectrum.hpp's (the Bartlett or the Capon map): the same launches, nothing allocated.
 //      crsdr_doa_set_refine adds refine.hpp's launch behind the directions and ahead of the beams, which then steer off the grid.
+//      crsdr_doa_set_esprit adds esprit.hpp's launch between the source count and the scan (BESIDE), or puts it in the place of the
+//      scan, the peak, the local peaks and the refinement (ONLY).
 //
 // Shape of the host code.  A feature is a sub-struct of crsdr_doa: its parameters and its device buffers, each buffer owned by a
 // DevBuf, so that "off" is an assignment of {} and nothing is freed by a list kept by hand.  What the last submit left (DoaLast) is
@@ -112,14 +114,23 @@ struct DoaRefine {
     int levels = 0;
     DevBuf<float> offsets, angles, values;
 };
+// crsdr_doa_set_esprit: mode (0 = off); found, status [nmat]; phases, angles, modulus [nmat][slots][2]; power, flags [nmat][slots],
+// slots = k, or kmax with the source count on.  Allocated for the most matrices and slots there can be: no other setter resizes them
+struct DoaEsprit {
+    int mode = 0;
+    DevBuf<int32_t> found, status, flags;
+    DevBuf<double> phases;
+    DevBuf<float> angles, modulus, power;
+};
 // what the last submit left: where, how much, and which features ran (kRan*).  A setter clears its feature's bit: "nothing submitted
 // since"; without kRanBase nothing is left at all
-constexpr unsigned kRanBase = 1u, kRanPeaks = 2u, kRanBeams = 4u, kRanSmooth = 8u, kRanOrder = 16u, kRanRefine = 32u;
+constexpr unsigned kRanBase = 1u, kRanPeaks = 2u, kRanBeams = 4u, kRanSmooth = 8u, kRanOrder = 16u, kRanRefine = 32u, kRanEsprit = 64u, kRanScan = 128u;
 struct DoaLast {
     hipStream_t stream = nullptr;
     int nest = 0, nblocks = 0, ms = 0, launches = 0;
     unsigned ran = 0;
     int slots = 0;               // refined directions per matrix (the layout of that submit, whatever set_peaks says since)
+    int eslots = 0;              // ESPRIT slots per matrix, likewise
 };
 
 struct crsdr_doa {
@@ -137,6 +148,7 @@ struct crsdr_doa {
     DoaSmooth smooth;
     DoaOrder order;
     DoaRefine refine;
+    DoaEsprit esprit;
     int spectrum = CRSDR_SPECTRUM_MUSIC;           // crsdr_doa_set_spectrum: the map the scan computes, and CAPON's loading
     float spectrum_loading = 0.f;
     DoaLast last;
@@ -153,6 +165,11 @@ static int doa_lds_limits();               // (behind the stages, which name the
 static const void *doa_refine_kernel();
 static void doa_refine_enqueue(dim3 grid, hipStream_t S, const float2 *vec, const float *sv, int M, int kind, int k, const int32_t *korder, float loading, float d, int Mx,
                                int Cx, int Cy, const int32_t *dirs, const int32_t *found, int levels, float *offsets, float *angles, float *values);
+// esprit.hpp's kernel likewise
+static void doa_esprit_enqueue(unsigned nmat, hipStream_t S, const float2 *vec, const float *sv, int M, int k, const int32_t *korder, float d, int SX, int SY, int slots,
+                               int32_t *found, int32_t *status, double *phases, float *angles, float *modulus, float *power, int32_t *flags);
+// the most sources ESPRIT can place on an mx x my array: the rows left when a column or a row of elements is dropped, and the kernel's 16
+static int esprit_rank_limit(int mx, int my) { return std::min(std::min((mx - 1) * my, mx * (my - 1)), (int)esprit::MAX_K); }
 // k_doa_scan<false> is named here, ahead of the stages, to keep the code object's kernels in the order they have always had: a
 // device-only assembly of the translation unit then compares line by line with an earlier build's
 static const void *const kDoaPlainScan = (const void *)doa::k_doa_scan<false>;
@@ -311,7 +328,24 @@ static int doa_stage_subspace(crsdr_doa *q, DoaRun &r)
     return doa_run(r, doa::k_doa_subspace, dim3(r.nest), dim3(music::JT), 2 * sizeof(double2) * (size_t)r.M * r.M, cov, r.M, q->mat.sv.p, q->mat.vec.p, q->mat.info.p);
 }
 
-// the source count (if on), the scan with k or with the counts, the peak
+// ESPRIT's slots per matrix: k, or the most the source count can say
+static int doa_esprit_slots(const crsdr_doa *q) { return q->order.crit ? q->order.kmax : q->k; }
+
+// what a submit with ESPRIT on needs, known on the host: checked before any launch
+static int doa_esprit_ready(const crsdr_doa *q)
+{
+    const DoaEsprit &es = q->esprit;
+    if (!es.mode) return CRSDR_OK;
+    const int slots = doa_esprit_slots(q);
+    if (q->sx() < 2 || q->sy() < 2 || slots > esprit_rank_limit(q->sx(), q->sy()))
+        return fail(CRSDR_ESTATE, "doa_submit: ESPRIT is on (crsdr_doa_set_esprit): it needs an array of at least 2 x 2 (%d x %d) and at most %d sources (%d)", q->sx(), q->sy(),
+                    q->sx() >= 2 && q->sy() >= 2 ? esprit_rank_limit(q->sx(), q->sy()) : 0, slots);
+    if (es.mode == CRSDR_ESPRIT_ONLY && (q->peaks.count || q->refine.levels || (q->beams.mode && !q->beams.nfixed)))
+        return fail(CRSDR_ESTATE, "doa_submit: CRSDR_ESPRIT_ONLY runs no scan: peaks, the refinement and beams that follow the directions need one, turn them off first");
+    return CRSDR_OK;
+}
+
+// the source count (if on), ESPRIT (if on), the scan with k or with the counts, the peak
 static int doa_stage_scan(crsdr_doa *q, DoaRun &r)
 {
     const int M = r.M;
@@ -322,6 +356,15 @@ static int doa_stage_scan(crsdr_doa *q, DoaRun &r)
         const int rc = doa_run(r, smooth::k_doa_order, dim3(r.nest), dim3(64), 0, (const float *)q->mat.sv, M, doa_snapshots(q), q->order.crit, q->order.kmin,
                                q->order.kmax, q->order.k.p, q->order.values.p);
         if (rc) return rc;
+    }
+    if (q->esprit.mode) {
+        // the gridless directions: one wave per matrix on the subspace and the counts the scan would use
+        DoaEsprit &es = q->esprit;
+        doa_esprit_enqueue(r.nest, r.S, (const float2 *)q->mat.vec, (const float *)q->mat.sv, M, q->k, (const int32_t *)q->order.k, q->d, q->sx(), q->sy(),
+                           doa_esprit_slots(q), es.found.p, es.status.p, es.phases.p, es.angles.p, es.modulus.p, es.power.p, es.flags.p);
+        HIP_TRY(hipGetLastError());
+        ++r.launches;
+        if (es.mode == CRSDR_ESPRIT_ONLY) return CRSDR_OK;               // no scan, no peak
     }
     int rc;
     if (q->spectrum != CRSDR_SPECTRUM_MUSIC) {
@@ -390,14 +433,16 @@ static int doa_stage_beams(crsdr_doa *q, DoaRun &r)
 static int doa_launch(crsdr_doa *q, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nblocks, hipStream_t S)
 {
     DoaRun r{packets, packet_stride, matrix_offset, nblocks, S, (unsigned)(nblocks / q->frames), q->ms()};
-    int rc = CRSDR_OK;
+    int rc = doa_esprit_ready(q);
+    if (rc) return rc;
+    // (CRSDR_ESPRIT_ONLY: the scan stage ends behind ESPRIT; peaks and the refinement are off, doa_esprit_ready saw to it)
     if ((rc = doa_stage_covariance(q, r)) || (rc = doa_stage_subspace(q, r)) || (rc = doa_stage_scan(q, r)) || (rc = doa_stage_local_peaks(q, r)) ||
         (rc = doa_stage_refine(q, r)) || (rc = doa_stage_beams(q, r)))
         return rc;
     q->last = DoaLast{S, (int)r.nest, nblocks, r.M, r.launches,
                       kRanBase | (q->peaks.count ? kRanPeaks : 0u) | (q->beams.mode ? kRanBeams : 0u) | (q->smooth.on ? kRanSmooth : 0u) | (q->order.crit ? kRanOrder : 0u) |
-                          (q->refine.levels ? kRanRefine : 0u),
-                      q->refine.levels ? (q->peaks.count ? q->peaks.count : 1) : 0};
+                          (q->refine.levels ? kRanRefine : 0u) | (q->esprit.mode ? kRanEsprit : 0u) | (q->esprit.mode == CRSDR_ESPRIT_ONLY ? 0u : kRanScan),
+                      q->refine.levels ? (q->peaks.count ? q->peaks.count : 1) : 0, q->esprit.mode ? doa_esprit_slots(q) : 0};
     return CRSDR_OK;
 }
 
@@ -477,6 +522,8 @@ extern "C" int crsdr_doa_fetch(crsdr_doa *q, int32_t *peak, float *peak_value, f
     if (pm && !(q->flags & CRSDR_DOA_KEEP_SPECTRUM)) return fail(CRSDR_EINVAL, "doa_fetch: pm asked of a doa created without CRSDR_DOA_KEEP_SPECTRUM");
     if (rxx && !(q->flags & CRSDR_DOA_KEEP_RXX)) return fail(CRSDR_EINVAL, "doa_fetch: rxx asked of a doa created without CRSDR_DOA_KEEP_RXX");
     if (!(q->last.ran & kRanBase)) return fail(CRSDR_ESTATE, "doa_fetch: nothing submitted");
+    if ((peak || peak_value || pm) && !(q->last.ran & kRanScan))
+        return fail(CRSDR_ESTATE, "doa_fetch: the last submit ran no scan (CRSDR_ESPRIT_ONLY): no peak, peak_value or pm");
     const size_t nest = (size_t)q->last.nest, m = (size_t)q->m, ms = (size_t)q->last.ms;
     static_assert(kMaxDoaMatrices >= kMaxBatch, "status of every matrix of a submit");
     int info[2 * kMaxDoaMatrices];
@@ -540,6 +587,7 @@ extern "C" int crsdr_doa_fetch_directions(crsdr_doa *q, int32_t *found, int32_t 
     if (!q) return fail(CRSDR_EINVAL, "doa_fetch_directions: NULL doa");
     if (!q->peaks.count) return fail(CRSDR_ESTATE, "doa_fetch_directions: no crsdr_doa_set_peaks");
     if (!(q->last.ran & kRanPeaks)) return fail(CRSDR_ESTATE, "doa_fetch_directions: nothing submitted since crsdr_doa_set_peaks");
+    if (!(q->last.ran & kRanScan)) return fail(CRSDR_ESTATE, "doa_fetch_directions: the last submit ran no scan (CRSDR_ESPRIT_ONLY)");
     const size_t nest = (size_t)q->last.nest, c = (size_t)q->peaks.count;
     return DoaFetch(q).copy(found, q->peaks.found.p, nest).copy(peaks, q->peaks.dirs.p, nest * c * 2).copy(values, q->peaks.values.p, nest * c).wait();
 }
@@ -670,6 +718,7 @@ extern "C" int crsdr_doa_fetch_refined(crsdr_doa *q, float *offsets, float *angl
     if (!q) return fail(CRSDR_EINVAL, "doa_fetch_refined: NULL doa");
     if (!q->refine.levels) return fail(CRSDR_ESTATE, "doa_fetch_refined: no crsdr_doa_set_refine");
     if (!(q->last.ran & kRanRefine)) return fail(CRSDR_ESTATE, "doa_fetch_refined: nothing submitted since crsdr_doa_set_refine");
+    if (!(q->last.ran & kRanScan)) return fail(CRSDR_ESTATE, "doa_fetch_refined: the last submit ran no scan (CRSDR_ESPRIT_ONLY)");
     const size_t n = (size_t)q->last.nest * (size_t)q->last.slots;
     return DoaFetch(q).copy(offsets, q->refine.offsets.p, 2 * n).copy(angles, q->refine.angles.p, 2 * n).copy(values, q->refine.values.p, n).wait();
 }
@@ -681,6 +730,52 @@ extern "C" int crsdr_doa_refined_buffers(crsdr_doa *q, void **offsets, void **an
     if (angles) *angles = q->refine.angles;
     if (values) *values = q->refine.values;
     if (slots) *slots = q->refine.levels ? (q->last.ran & kRanRefine ? q->last.slots : q->peaks.count ? q->peaks.count : 1) : 0;
+    return CRSDR_OK;
+}
+
+// ---- the gridless directions (esprit.hpp) ----
+extern "C" int crsdr_doa_set_esprit(crsdr_doa *q, int mode)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_set_esprit: NULL doa");
+    if (mode != CRSDR_ESPRIT_OFF && mode != CRSDR_ESPRIT_BESIDE && mode != CRSDR_ESPRIT_ONLY) return fail(CRSDR_EINVAL, "doa_set_esprit: mode = %d", mode);
+    { const int rc = doa_quiesce(q); if (rc) return rc; }
+    q->esprit = {}; q->last.ran &= ~kRanEsprit;
+    if (mode == CRSDR_ESPRIT_OFF) return CRSDR_OK;
+    // the most matrices and slots any later setter can ask for
+    const size_t nmat = kMaxDoaMatrices, slots = nmat * esprit::MAX_K;
+    DoaEsprit &es = q->esprit;
+    if (es.found.alloc(nmat) || es.status.alloc(nmat) || es.flags.alloc(slots) || es.phases.alloc(2 * slots) || es.angles.alloc(2 * slots) || es.modulus.alloc(2 * slots) ||
+        es.power.alloc(slots)) {
+        q->esprit = {};
+        return fail(CRSDR_ENOMEM, "doa_set_esprit: %zu bytes of device memory", 8 * nmat + 40 * slots);
+    }
+    es.mode = mode;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_fetch_esprit(crsdr_doa *q, int32_t *found, int32_t *status, double *phases, float *angles, float *modulus, float *power, int32_t *flags)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_fetch_esprit: NULL doa");
+    if (!q->esprit.mode) return fail(CRSDR_ESTATE, "doa_fetch_esprit: no crsdr_doa_set_esprit");
+    if (!(q->last.ran & kRanBase) || !(q->last.ran & kRanEsprit)) return fail(CRSDR_ESTATE, "doa_fetch_esprit: nothing submitted since crsdr_doa_set_esprit");
+    const DoaEsprit &es = q->esprit;
+    const size_t nmat = (size_t)q->last.nest, n = nmat * (size_t)q->last.eslots;
+    return DoaFetch(q).copy(found, es.found.p, nmat).copy(status, es.status.p, nmat).copy(phases, es.phases.p, 2 * n).copy(angles, es.angles.p, 2 * n)
+                      .copy(modulus, es.modulus.p, 2 * n).copy(power, es.power.p, n).copy(flags, es.flags.p, n).wait();
+}
+
+extern "C" int crsdr_doa_esprit_buffers(crsdr_doa *q, void **found, void **status, void **phases, void **angles, void **modulus, void **power, void **flags, int *slots)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_esprit_buffers: NULL doa");
+    const DoaEsprit &es = q->esprit;
+    if (found) *found = es.found;
+    if (status) *status = es.status;
+    if (phases) *phases = es.phases;
+    if (angles) *angles = es.angles;
+    if (modulus) *modulus = es.modulus;
+    if (power) *power = es.power;
+    if (flags) *flags = es.flags;
+    if (slots) *slots = es.mode ? (q->last.ran & kRanEsprit ? q->last.eslots : doa_esprit_slots(q)) : 0;
     return CRSDR_OK;
 }
 

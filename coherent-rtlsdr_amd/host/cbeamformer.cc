@@ -131,6 +131,14 @@ int batch::set_refine(int levels)
     return rc;
 }
 
+int batch::set_esprit(int mode)
+{
+    int rc = doa ? crsdr_doa_set_esprit(doa, mode) : CRSDR_ESTATE;
+    if (!rc) esprit_mode = mode;
+    if (rc && doa) std::fprintf(stderr, "cbeamformer::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
 int batch::set_subband_beams(int mode, float loading, int nfixed, const float *fixed_angles)
 {
     int rc = doa ? crsdr_doa_set_subband_beams(doa, mode, loading, nfixed, fixed_angles) : CRSDR_ESTATE;
@@ -146,7 +154,18 @@ int batch::fetch(bool want_beams)
     if (!rc) {
         peak.assign(2 * (size_t)nest, 0); peak_value.assign(nest, 0.f); sv.assign((size_t)nest * ms, 0.f); status.assign(nest, 0);
         if (keep) pm.assign((size_t)nest * cx * cy, 0.f);
-        rc = crsdr_doa_fetch(doa, peak.data(), peak_value.data(), sv.data(), status.data(), keep ? pm.data() : nullptr, nullptr);
+        // CRSDR_ESPRIT_ONLY: no scan ran, peak and peak_value keep their zeros and pm is not asked for
+        const bool scan = esprit_mode != CRSDR_ESPRIT_ONLY;
+        rc = crsdr_doa_fetch(doa, scan ? peak.data() : nullptr, scan ? peak_value.data() : nullptr, sv.data(), status.data(), keep && scan ? pm.data() : nullptr, nullptr);
+    }
+    if (!rc && esprit_mode) {
+        rc = crsdr_doa_esprit_buffers(doa, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &nesprit);
+        const size_t n = (size_t)nest * nesprit;
+        esprit_found.assign(nest, 0); esprit_status.assign(nest, 0); esprit_phases.assign(2 * n, 0.0); esprit_angles.assign(2 * n, -1.f);
+        esprit_modulus.assign(2 * n, -1.f); esprit_power.assign(n, -1.f); esprit_flags.assign(n, 0);
+        if (!rc)
+            rc = crsdr_doa_fetch_esprit(doa, esprit_found.data(), esprit_status.data(), esprit_phases.data(), esprit_angles.data(), esprit_modulus.data(),
+                                        esprit_power.data(), esprit_flags.data());
     }
     if (!rc && nbands) {
         band_power.assign(nest, 0.f);

@@ -37,6 +37,7 @@ class batch {
     int m = 0, ms = 0, cx = 0, cy = 0, npeaks = 0, nbeams = 0, half = 0, nframes = 1;      // ms: the subspace's size (m, or a sub-array's)
     bool counted = false;
     int refining = 0, nrefined = 0;                  // set_refine: levels; slots per estimate of the last fetch
+    int esprit_mode = 0, nesprit = 0;                // set_esprit: the mode; slots per estimate of the last fetch
     bool keep = false;
     int nbands = 0;                                  // set_subbands: bands per estimate (0: off)
     int nbandbeams = 0, band_j = 0, band_width = 0;  // set_subband_beams: slots; set_subbands: segments per block, bins per band
@@ -82,6 +83,18 @@ public:
     // [estimates][slots][2] and the map's value there [estimates][slots]; empty slots hold (0, 0), (-1, -1) and -1
     int refined_slots() const { return nrefined; }
     std::vector<float> refined_offsets, refined_angles, refined_values;
+    // from the next submit on, the K directions of every estimate (its count's, with set_order) by 2-D ESPRIT on the signal subspace
+    // (crsdr_doa_set_esprit): no grid, no search.  CRSDR_ESPRIT_BESIDE: beside the scan; CRSDR_ESPRIT_ONLY: in its place (no peak, no
+    // spectrum; peaks, the refinement and beams that follow the directions must be off; the fetched angles can be the fixed_angles of
+    // set_beams).  CRSDR_ESPRIT_OFF: off.  Any time.
+    int set_esprit(int mode = CRSDR_ESPRIT_BESIDE);
+    // with set_esprit: per estimate the directions found and the status; per estimate and slot the phases (mu, nu) [estimates][slots][2],
+    // (alpha, beta) in radians [estimates][slots][2], (|lambda_x|, |lambda_y|) [estimates][slots][2] (about 1 for a plane wave), the
+    // conventional power and the flags [estimates][slots]; slots by descending power, empty ones hold (0, 0), (-1, -1), (-1, -1), -1, 0
+    int esprit_slots() const { return nesprit; }
+    std::vector<int32_t> esprit_found, esprit_status, esprit_flags;
+    std::vector<double> esprit_phases;
+    std::vector<float> esprit_angles, esprit_modulus, esprit_power;
     int bands() const { return nbands; }
     std::vector<float> band_power;                   // with set_subbands: [estimates]: Re trace(R_band) / M, the squelch of a band's direction
     // with set_subbands on: from the next submit on, a beam per band toward every direction of that band (crsdr_doa_set_subband_beams;

@@ -57,7 +57,7 @@ int main(int argc, char **argv)
     bool run_cdsp = false, servo = false, threads = false, music = false, servo_table = false, bench = false, batch_parity = false, batched = false;
     int batch = 16, engine_delay_ms = 0, pace_us_arg = -1, peaks = 0, peak_radius = 1, beam_mode = CRSDR_BEAM_OFF, band_beam_mode = CRSDR_BEAM_OFF;
     float beam_loading = 1e-2f;
-    int smooth_x = 0, smooth_y = 0, order_crit = CRSDR_ORDER_OFF, spectrum_kind = CRSDR_SPECTRUM_MUSIC, refine_levels = 0;
+    int smooth_x = 0, smooth_y = 0, order_crit = CRSDR_ORDER_OFF, spectrum_kind = CRSDR_SPECTRUM_MUSIC, refine_levels = 0, esprit_mode = CRSDR_ESPRIT_OFF;
     bool smooth_fb = false;
     int sb_nfft = 0, sb_first = 0, sb_count = 1, sb_width = 1, sb_window = CRSDR_WINDOW_RECT;
     bool engine_batches = false;
@@ -129,6 +129,12 @@ int main(int argc, char **argv)
         else if (a == "--refine") {
             refine_levels = 5;
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') refine_levels = std::atoi(argv[++i]);
+        }
+        // with --bench --music: every estimate's directions by 2-D ESPRIT (crsdr_doa_set_esprit) beside the scan, or with "only" in its
+        // place; their angles in degrees and power are printed beside the grid direction
+        else if (a == "--esprit") {
+            esprit_mode = CRSDR_ESPRIT_BESIDE;
+            if (i + 1 < argc && std::string(argv[i + 1]) == "only") { esprit_mode = CRSDR_ESPRIT_ONLY; ++i; }
         }
         else if (a == "--loading" && i + 1 < argc) beam_loading = (float)std::atof(argv[++i]);
         else if (a == "--batch-parity") batch_parity = true;   // the batched engine's packets == step()'s packets, bit for bit (own read counters, a masked row)
@@ -345,6 +351,7 @@ int main(int argc, char **argv)
                 return 1;
             }
             if (peaks && doa->set_peaks(peaks, peak_radius)) { std::printf("doa: --peaks %d --peak-radius %d refused\nDEMO FAILED\n", peaks, peak_radius); return 1; }
+            if (esprit_mode && doa->set_esprit(esprit_mode)) { std::printf("doa: --esprit refused\nDEMO FAILED\n"); return 1; }
             if (refine_levels && doa->set_refine(refine_levels)) { std::printf("doa: --refine %d refused (1..8 levels)\nDEMO FAILED\n", refine_levels); return 1; }
             if (beam_mode && doa->set_beams(beam_mode, beam_loading)) { std::printf("doa: --beams (conventional|mvdr) --loading %g refused\nDEMO FAILED\n", (double)beam_loading); return 1; }
             if (band_beam_mode && (!sb_nfft || doa->set_subband_beams(band_beam_mode, beam_loading))) {
@@ -359,6 +366,21 @@ int main(int argc, char **argv)
             if (!ok || !report) return;
             const int n = doa->estimates();
             const double deg = 180.0 / 3.14159265358979323846;
+            if (esprit_mode) {
+                // every matrix (estimate, or estimate and band): the grid direction, then the ESPRIT slots in order of power
+                const int ns = doa->esprit_slots();
+                for (int e = 0; e < n; ++e) {
+                    std::printf("doa: batch %d: esprit %d:", b, e);
+                    if (esprit_mode != CRSDR_ESPRIT_ONLY) std::printf(" grid (%d, %d)", doa->peak[2 * e], doa->peak[2 * e + 1]);
+                    std::printf(" found %d status %d:", doa->esprit_found[e], doa->esprit_status[e]);
+                    for (int s = 0; s < doa->esprit_found[e]; ++s) {
+                        const size_t x = (size_t)e * ns + s;
+                        std::printf(" (%.3f, %.3f) deg power %.4g", deg * doa->esprit_angles[2 * x], deg * doa->esprit_angles[2 * x + 1], (double)doa->esprit_power[x]);
+                    }
+                    std::printf("\n");
+                }
+                if (esprit_mode == CRSDR_ESPRIT_ONLY) { std::printf("doa: batch %d: %d estimates by ESPRIT alone\n", b, n); return; }
+            }
             if (doa->bands()) {
                 // every estimate's bands: the direction at that frequency and the power that says whether to trust it
                 const int nb_ = doa->bands();

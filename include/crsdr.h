@@ -770,6 +770,65 @@ int crsdr_doa_refined_buffers(crsdr_doa *doa, void **offsets, void **angles, voi
 int crsdr_refine2d(float *offsets, float *angles, float *values, const float *vec, const float *sv, int m, int kind, int k, float loading, float d, int mx,
                    int my, int ncx, int ncy, const int32_t *peaks, int npeaks, int levels, int mem_kind);
 
+/* Gridless directions: 2-D ESPRIT.  Every direction above comes from a scan over ncx x ncy grid points.  On a uniform rectangular
+ * array the k directions can be read from the shift invariance of the signal subspace instead: no grid, no search, no peak picking,
+ * k-by-k linear algebra per matrix whatever the grid is, and sources that merge into one local maximum of a map stay k directions.
+ * The definition, per matrix (an estimate, or an estimate and band).  Inputs: the published fp32 vec ([M][M], column r = v_r) and sv;
+ * the source count k_e (desc.k, or the matrix's count from crsdr_doa_set_order); the array SX x SY, M = SX SY (the sub-array while
+ * smoothing runs true sub-arrays, mx x my otherwise), element i = iy SX + ix; (double)d.  All arithmetic is fp64, its order not pinned.
+ *   1. E = the first k_e columns of vec, M x k
+ *   2. E1x = the rows of E with ix <= SX-2, E2x those with ix >= 1, paired (ix, iy) -> (ix+1, iy)
+ *   3. E1y, E2y likewise with iy <= SY-2 and iy >= 1
+ *   4. Gx = E1x^H E1x, Hx = E1x^H E2x (k x k), Psi_x = Gx^-1 Hx by Cholesky; Psi_y likewise
+ *   5. Psi_c = Psi_x + gamma Psi_y, gamma = (1 + j) / 2
+ *   6. Psi_c V = V diag(w), V the eigenvectors of Psi_c; lambda_x_i = (V^-1 Psi_x V)_ii, lambda_y_i = (V^-1 Psi_y V)_ii.  This pairs mu
+ *      with nu, and is unique for distinct w_i whatever the order or scaling of V (the diagonal of a Schur form's Q^H Psi_x Q is not)
+ *   7. mu_i = atan2(Im lambda_x_i, Re lambda_x_i), nu_i = atan2(Im lambda_y_i, Re lambda_y_i)
+ *   8. the angles in the scan's convention, a_i = exp(j (ix mu + iy nu)), mu = 2 pi d cos(alpha) sin(beta), nu = 2 pi d cos(beta):
+ *      cb = nu / (2 pi d), clamped to [-1, 1] with flag bit 0 if |cb| > 1;  sb = sqrt(1 - cb^2);  ca = sb > 0 ? mu / (2 pi d sb) : 0,
+ *      clamped with flag bit 1 if sb == 0 or |ca| > 1;  beta = acos(cb), alpha = acos(ca).  The covariance is X^H X, so this is the
+ *      direction at which MUSIC peaks for the same source (the mirrored one); nothing is conjugated.  For d > 1/2 the principal value
+ *      of mu and nu is the alias nearest broadside: a source beyond it is reported at that alias.
+ *   9. power_i = sum_r sv[r] |v_r^H a_i|^2 / M^2, a_i the fp64 steering vector of the beam weights at (alpha_i, beta_i): the
+ *      conventional power of crsdr_doa_set_beams
+ *  10. slots by descending power; equal powers by ascending mu, then nu
+ *  11. found = k_e; 0 if sv[0] == 0 (status 0), if a Cholesky pivot (the diagonal entry a column starts from) is <= 2^-40 (status bit 1),
+ *      or if the eigenvalue iteration did not finish within 40 k_e steps (status bit 0)
+ *  12. slots from found on hold phases (0, 0), angles (-1, -1), modulus (-1, -1), power -1 and flags 0
+ * Needs SX >= 2 and SY >= 2; slots = desc.k, or kmax with crsdr_doa_set_order; slots <= 16 and slots <= min((SX-1) SY, SX (SY-1)).
+ * These are checked when the feature is used (by a submit: CRSDR_ESTATE before any launch), not by other setters.
+ *
+ * crsdr_doa_set_esprit: CRSDR_ESPRIT_OFF; CRSDR_ESPRIT_BESIDE: one launch more per submit, between the source count and the scan,
+ * everything else unchanged; CRSDR_ESPRIT_ONLY: that launch, and the scan, the peak, the local peaks and the refinement are not issued.
+ * After an ONLY submit crsdr_doa_fetch with a non-NULL peak, peak_value or pm answers CRSDR_ESTATE, as do crsdr_doa_fetch_directions
+ * and crsdr_doa_fetch_refined; sv, status, rxx, the subspace, the smoothed matrix, the order and the band powers fetch as ever.  A
+ * submit in ONLY mode with crsdr_doa_set_peaks, crsdr_doa_set_refine or beams that follow the directions (nfixed = 0, wideband or band)
+ * on answers CRSDR_ESTATE before any launch; beams at fixed angles are fine (the fetched angles are in their convention).
+ * Any time: waits for the device if a submit was made; allocates for the most matrices and slots there can be, so no other setter
+ * refuses or is refused because of it.  CRSDR_EINVAL for another mode.  With OFF a submit issues the launches and computes the bits
+ * it did before the call.
+ * crsdr_doa_fetch_esprit (any pointer NULL = skip), per matrix of the last submit and its slots:
+ *   found, status [nest] int32;  phases [nest][slots][2] double (mu, nu);  angles [nest][slots][2] float (alpha, beta), rounded once;
+ *   modulus [nest][slots][2] float (|lambda_x|, |lambda_y|), about 1 for a plane wave: the quality figure;  power [nest][slots] float;
+ *   flags [nest][slots] int32
+ * CRSDR_ESTATE while off, or before the first submit after the setter.
+ * crsdr_doa_esprit_buffers: the device addresses (NULL while off) and the slots per matrix a fetch would read. */
+enum { CRSDR_ESPRIT_OFF = 0, CRSDR_ESPRIT_BESIDE = 1, CRSDR_ESPRIT_ONLY = 2 };
+int crsdr_doa_set_esprit(crsdr_doa *doa, int mode);
+int crsdr_doa_fetch_esprit(crsdr_doa *doa, int32_t *found, int32_t *status, double *phases /*[nest][slots][2] (mu, nu)*/,
+                           float *angles /*[nest][slots][2] (alpha, beta), rounded once*/, float *modulus /*(|lambda_x|, |lambda_y|)*/,
+                           float *power, int32_t *flags);
+int crsdr_doa_esprit_buffers(crsdr_doa *doa, void **found, void **status, void **phases, void **angles, void **modulus,
+                             void **power, void **flags, int *slots);
+
+/* The per-op form: the same arithmetic on one matrix, bit for bit; slots = k.
+ *   vec [m][m][2] and sv [m] as crsdr_noisesubspace writes them, m = mx * my <= 64, mx >= 2, my >= 2;  1 <= k <= 16 and
+ *   k <= min((mx-1) my, mx (my-1));  found, status one int32 each;  phases [k][2] double;  angles, modulus [k][2];  power, flags [k]
+ * Every argument is checked before a device is touched.  mem_kind: CRSDR_MEM_HOST (copied) or CRSDR_MEM_DEVICE (all on the device: vec
+ * and phases 8-byte, the others 4-byte aligned). */
+int crsdr_esprit2d(int32_t *found, int32_t *status, double *phases, float *angles, float *modulus, float *power, int32_t *flags,
+                   const float *vec, const float *sv, int m, int k, float d, int mx, int my, int mem_kind);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,8 @@
       against the MUSIC submit (b) of the same build and, with --doa-lib, of another (lib:b) in the same alternation.
   (r) with --refine L [--peaks COUNT --radius R]: crsdr_doa_set_refine(L) on an object like (p)'s (or (b)'s without --peaks), then the
       submit + directions (or peaks) + crsdr_doa_fetch_refined: against (p) (or (b)) of the same build in the same alternation.
+  (e) with --esprit beside|only [--subbands ...]: crsdr_doa_set_esprit on an object like (b)'s (or (u)'s with --subbands), then the
+      submit + crsdr_doa_fetch_esprit of the angles alone (beside: + the peaks): against the MUSIC submit (b) (or (u)) of the same build in the same alternation.
 --array MXxMY runs everything on another array than the 7 x 3 one (8x8: M = 64, the largest).
 
 --runs runs of each, alternating a, b, c in one session (two worker processes, both alive throughout); medians and ranges.
@@ -32,7 +34,8 @@ the same alternation, reported as lib:b and lib:c.  --reps N: every (b), (c), (p
 Also: what crsdr_doa_submit_plan + the peak fetch add to a 22-row, T = 64 plan batch (plan.submit + sync against
 plan.submit + doa.submit_plan + fetch).  --json FILE keeps the record; --once MODE runs three submit + fetch and exits (for a kernel trace): b, c, p, q as above, q64 = the
 beams at their largest shape (8 x 8 array, 16 slots: 65 rows x 16384, 64 blocks), s = --smooth / --fb / --order as given, all on one object,
-u = --subbands / --window as given, v = u with --peaks and --band-beams as given, m = --spectrum as given, r = --refine with --peaks as given."""
+u = --subbands / --window as given, v = u with --peaks and --band-beams as given, m = --spectrum as given, r = --refine with --peaks as given,
+e = --esprit (and --subbands) as given."""
 import argparse, importlib, json, os, subprocess, sys, time
 import numpy as np
 
@@ -42,6 +45,7 @@ ARRAY = (7, 3)                             # --array: (mx, my), NROWS = 1 + mx m
 SPECTRA = {"bartlett": 1, "capon": 2}
 BEAM_MODES = {"conventional": 1, "mvdr": 2}
 ORDER_MODES = {"mdl": 1, "aic": 2}
+ESPRIT_MODES = {"beside": 1, "only": 2}
 WINDOWS = {"rect": 0, "hann": 1}
 
 
@@ -111,7 +115,7 @@ def worker_perop():
 
 
 def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None, fb=False, order=None, subbands=None, window="rect", band_beams=None,
-               spectrum=None, refine=0):
+               spectrum=None, refine=0, esprit=None):
     """(b), (c), (p), (q), (h), (f), (s), (o) and the plan figures: 'b' / 'c' / 'p' / 'q' / 'h' / 'f' / 's' / 'o' / 'plan' / 'plan+doa' on
     stdin -> seconds of one batch of 64 on stdout."""
     torch, ura, b, dev, pk, off, stride, host = _setup()
@@ -156,6 +160,22 @@ def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None
     if subbands:
         udoa = b.Doa(NROWS, B, 1, ura.D, *ARRAY, max_batch=T)
         udoa.set_subbands(*_bands(subbands), WINDOWS[window])
+
+    edoa = None
+    if esprit:
+        edoa = b.Doa(NROWS, B, 1, ura.D, *ARRAY, max_batch=T)
+        if subbands:
+            edoa.set_subbands(*_bands(subbands), WINDOWS[window])
+        edoa.set_esprit(ESPRIT_MODES[esprit])
+
+    def run_e():
+        for _ in range(reps):
+            edoa.submit(pk.data_ptr(), stride, off, T)
+            if esprit == "beside":
+                edoa.fetch_peaks()
+            edoa.fetch_esprit(want=("angles",))          # like (b): the directions alone, one copy
+            if subbands:
+                edoa.fetch_subbands()
 
     vdoa = wdoa = None
     if subbands and band_beams:
@@ -249,6 +269,8 @@ def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None
         jobs["r"] = (run_r, reps)
     if udoa is not None:
         jobs["u"] = (run_u, reps)
+    if edoa is not None:
+        jobs["e"] = (run_e, reps)
     if vdoa is not None:
         jobs["v"], jobs["w"] = (run_v, reps), (run_w, reps)
     for f, _ in jobs.values():
@@ -262,7 +284,7 @@ def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None
 
 
 def once(mode, npeaks=0, radius=1, beams=None, loading=1e-2, smooth=None, fb=False, order=None, subbands=None, window="rect", band_beams=None, spectrum=None,
-         refine=0):
+         refine=0, esprit=None):
     mx, my = (8, 8) if mode == "q64" else (None, None)
     torch, ura, b, dev, pk, off, stride, _ = _setup(mx, my)
     mx, my = mx or ARRAY[0], my or ARRAY[1]
@@ -282,8 +304,10 @@ def once(mode, npeaks=0, radius=1, beams=None, loading=1e-2, smooth=None, fb=Fal
             d.set_order(ORDER_MODES[order], 1, d.ms - 1)
     if mode == "m":
         d.set_spectrum(SPECTRA[spectrum or "capon"], loading)
-    if mode in ("u", "v"):
+    if mode in ("u", "v") or (mode == "e" and subbands):
         d.set_subbands(*_bands(subbands), WINDOWS[window])
+    if mode == "e":
+        d.set_esprit(ESPRIT_MODES[esprit or "beside"])
     if mode == "v":
         if npeaks:
             d.set_peaks(npeaks, radius)
@@ -291,6 +315,11 @@ def once(mode, npeaks=0, radius=1, beams=None, loading=1e-2, smooth=None, fb=Fal
     for _ in range(3):
         d.submit(pk.data_ptr(), stride, off, T)
         out = d.fetch()
+    if mode == "e":
+        es = d.fetch_esprit()
+        print("esprit angles of the first four, degrees", np.round(np.degrees(es["angles"][:4, 0]), 3).tolist(), "found", es["found"][:4].tolist(), "launches", d.last_launches())
+        if esprit == "only":
+            return
     if mode in ("u", "v"):
         print("band power of the first estimate", np.round(d.fetch_subbands()[0], 5).tolist())
     print("peaks", out["peak"][:4].tolist(), "launches", d.last_launches())
@@ -338,7 +367,8 @@ def _stat(xs):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--worker", choices=["perop", "doa"])
-    ap.add_argument("--once", choices=["b", "c", "p", "q", "q64", "s", "u", "v", "m", "r"])
+    ap.add_argument("--once", choices=["b", "c", "p", "q", "q64", "s", "u", "v", "m", "r", "e"])
+    ap.add_argument("--esprit", choices=sorted(ESPRIT_MODES), default=None, help="(e): the directions by 2-D ESPRIT beside the scan or in its place (crsdr_doa_set_esprit)")
     ap.add_argument("--refine", type=int, default=0, metavar="L", help="(r): the directions refined off the grid by L levels (crsdr_doa_set_refine)")
     ap.add_argument("--spectrum", choices=sorted(SPECTRA), default=None, help="(m): this power map in the scan's place (crsdr_doa_set_spectrum, --loading for capon)")
     ap.add_argument("--array", default=None, metavar="MXxMY", help="the array, 2 <= MX MY <= 64 (default 7x3)")
@@ -362,11 +392,11 @@ def main():
     shape = ["--array", a.array] if a.array else []
     if a.worker:
         return worker_perop() if a.worker == "perop" else worker_doa(a.peaks, a.radius, a.reps, a.beams, a.loading, a.smooth, a.fb, a.order, a.subbands, a.window,
-                                                                           a.band_beams, a.spectrum, a.refine)
+                                                                           a.band_beams, a.spectrum, a.refine, a.esprit)
     if a.band_beams and not a.subbands:
         ap.error("--band-beams needs --subbands")
     if a.once:
-        return once(a.once, a.peaks, a.radius, a.beams, a.loading, a.smooth, a.fb, a.order, a.subbands, a.window, a.band_beams, a.spectrum, a.refine)
+        return once(a.once, a.peaks, a.radius, a.beams, a.loading, a.smooth, a.fb, a.order, a.subbands, a.window, a.band_beams, a.spectrum, a.refine, a.esprit)
     pargs = shape + ["--peaks", str(a.peaks), "--radius", str(a.radius), "--reps", str(a.reps), "--loading", str(a.loading)]
     if a.spectrum:
         pargs += ["--spectrum", a.spectrum]
@@ -384,7 +414,9 @@ def main():
         pargs += ["--band-beams", a.band_beams]
     if a.refine:
         pargs += ["--refine", str(a.refine)]
-    legs = (["f"] if a.fb else []) + (["s"] if a.smooth else []) + (["o"] if a.order else []) + (["u"] if a.subbands else []) + (["v", "w"] if a.band_beams else []) + (["m"] if a.spectrum else []) + (["r"] if a.refine else [])
+    if a.esprit:
+        pargs += ["--esprit", a.esprit]
+    legs = (["f"] if a.fb else []) + (["s"] if a.smooth else []) + (["o"] if a.order else []) + (["u"] if a.subbands else []) + (["v", "w"] if a.band_beams else []) + (["m"] if a.spectrum else []) + (["r"] if a.refine else []) + (["e"] if a.esprit else [])
     wa, wb = Worker("perop", a.perop_lib, extra=shape), Worker("doa", extra=pargs)
     wl = Worker("doa", a.doa_lib, extra=shape + ["--reps", str(a.reps)]) if a.doa_lib else None
     keys = ["a", "b", "c", "plan", "plan+doa"] + (["lib:b", "lib:c"] if wl else []) + (["p"] if a.peaks else []) + (["q", "h"] if a.beams else []) + legs
@@ -417,7 +449,7 @@ def main():
            "smoothing": {"sub_array": a.smooth, "fb": a.fb} if (a.smooth or a.fb) else None, "order": a.order,
            "subbands": dict(zip(("nfft", "first", "nbands", "width"), _bands(a.subbands)), window=a.window) if a.subbands else None,
            "band_beams": {"mode": a.band_beams, "loading": a.loading} if a.band_beams else None,
-           "spectrum": {"kind": a.spectrum, "loading": a.loading} if a.spectrum else None, "refine": a.refine or None,
+           "spectrum": {"kind": a.spectrum, "loading": a.loading} if a.spectrum else None, "refine": a.refine or None, "esprit": a.esprit,
            "ms_per_batch": {k: _stat([1e3 * x for x in v]) for k, v in sec.items()},
            "frames_per_s": {k: _stat([T / x for x in sec[k]]) for k in ("a", "b", "c") + (("u",) if a.subbands else ())}}
     if a.subbands:
@@ -431,7 +463,8 @@ def main():
              "f": "FB alone: submit + peaks", "s": f"{a.smooth}{' + FB' if a.fb else ''}: submit + peaks", "o": f"order {a.order}: submit + peaks",
              "u": f"subbands {a.subbands} {a.window}: submit + peaks + power",
              "v": f"subbands + {a.band_beams} band beams: submit + power", "w": "subbands: packets and vec to the host",
-             "m": f"{a.spectrum} map: submit + peaks", "r": f"refine {a.refine}: submit + directions + refined"}
+             "m": f"{a.spectrum} map: submit + peaks", "r": f"refine {a.refine}: submit + directions + refined",
+             "e": f"esprit {a.esprit}{' + subbands' if a.subbands else ''}: submit + esprit"}
     for k, s in rec["ms_per_batch"].items():
         fps = f"  {T / (1e-3 * s['median']):10.0f} frames/s" if k in rec["frames_per_s"] else ""
         print(f"({k}) {names[k]:34s} {s['median']:8.3f} ms per 64 blocks  [{s['min']:.3f} .. {s['max']:.3f}]{fps}")
@@ -450,6 +483,12 @@ def main():
         rec["r_adds_ms_per_batch_over"] = base
         rec["r_adds_ms_per_batch"] = rec["ms_per_batch"]["r"]["median"] - rec["ms_per_batch"][base]["median"]
         print(f"(r) adds {1e3 * rec['r_adds_ms_per_batch']:.0f} us to ({base}), the same submit without the refinement")
+    if a.esprit:
+        base = "u" if a.subbands else "b"
+        rec["e_over"] = base
+        rec["e_over_base_ms"] = rec["ms_per_batch"]["e"]["median"] / rec["ms_per_batch"][base]["median"]
+        rec["e_minus_base_ms"] = rec["ms_per_batch"]["e"]["median"] - rec["ms_per_batch"][base]["median"]
+        print(f"(e) takes {rec['e_over_base_ms']:.3f} x the time of ({base}), the MUSIC submit of the same build: {1e3 * rec['e_minus_base_ms']:+.0f} us")
     if a.spectrum:
         rec["m_over_b_ms"] = rec["ms_per_batch"]["m"]["median"] / rec["ms_per_batch"]["b"]["median"]
         print(f"(m) takes {rec['m_over_b_ms']:.3f} x the time of (b), the MUSIC submit at k = 1; the scan's operation count is M / (M - 1) = {M / (M - 1):.3f} x")
