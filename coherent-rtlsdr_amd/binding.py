@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "crsdr_doa_set_spectrum", "crsdr_spectrum2d",
     "crsdr_doa_set_refine", "crsdr_doa_fetch_refined", "crsdr_doa_refined_buffers", "crsdr_refine2d",
     "crsdr_doa_set_esprit", "crsdr_doa_fetch_esprit", "crsdr_doa_esprit_buffers", "crsdr_esprit2d",
+    "crsdr_doa_set_augment", "crsdr_doa_fetch_augmented", "crsdr_doa_augment_buffers", "crsdr_augment_covariance", "crsdr_augment_lags",
 ]
 ESPRIT_OFF, ESPRIT_BESIDE, ESPRIT_ONLY = 0, 1, 2
 ESPRIT_STATUS_ITERATIONS, ESPRIT_STATUS_PIVOT = 1, 2          # status bits 0 and 1
@@ -221,6 +222,12 @@ def lib():
         L.crsdr_doa_fetch_esprit.argtypes = [vp, i32p, i32p, f64p, f32p, f32p, f32p, i32p]
         L.crsdr_doa_esprit_buffers.argtypes = [vp] + [C.POINTER(vp)] * 7 + [C.POINTER(C.c_int)]
         L.crsdr_esprit2d.argtypes = [i32p, i32p, f64p, f32p, f32p, f32p, i32p, f32p, f32p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int]
+    if hasattr(L, "crsdr_doa_set_augment"):          # (likewise: an older build has no augmentation)
+        L.crsdr_doa_set_augment.argtypes = [vp, C.c_int, C.c_int, C.c_uint64]
+        L.crsdr_doa_fetch_augmented.argtypes = [vp, f32p]
+        L.crsdr_doa_augment_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.crsdr_augment_covariance.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int]
+        L.crsdr_augment_lags.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, i32p, C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -463,6 +470,46 @@ def smooth_covariance(rxx, mx, my, sx, sy, flags=0):
 def smooth_covariance_device(rs_ptr: int, rxx_ptr: int, mx, my, sx, sy, flags=0):
     """Same on device memory (both pointers on the current device); returns after the kernel finished."""
     _check(lib().crsdr_smooth_covariance(int(rs_ptr), int(rxx_ptr), int(mx), int(my), int(sx), int(sy), int(flags), MEM_DEVICE))
+
+
+def mask_bits(mask) -> int:
+    """The uint64 of an element mask: an int as it is, a string of '0' / '1' in element order (element i is character i), or an
+    iterable of the indices that are present.  0 / None / "": all elements."""
+    if mask is None:
+        return 0
+    if isinstance(mask, str):
+        if set(mask) - {"0", "1"}:
+            raise ValueError("a mask string holds only '0' and '1'")
+        return sum(1 << i for i, ch in enumerate(mask) if ch == "1")
+    if isinstance(mask, (int, np.integer)):
+        return int(mask)
+    return sum(1 << int(i) for i in mask)
+
+
+def augment_covariance(rxx, mx, my, vx, vy, mask=0):
+    """crsdr_augment_covariance: ra [vx vy][vx vy] complex64, the covariance of the filled vx x vy virtual array from the per-lag averages
+    of rxx [mx my][mx my] over the elements of `mask` (mask_bits; 0: all): the batched engine's augmentation on one matrix."""
+    r = np.ascontiguousarray(rxx, dtype=np.complex64)
+    if r.shape != (mx * my, mx * my):
+        raise ValueError("rxx must be [mx * my][mx * my]")
+    mv = max(int(vx) * int(vy), 0)
+    ra = np.empty((mv, mv), dtype=np.complex64)
+    _check(lib().crsdr_augment_covariance(ra.ctypes.data, r.ctypes.data, int(mx), int(my), int(vx), int(vy), mask_bits(mask), MEM_HOST))
+    return ra
+
+
+def augment_covariance_device(ra_ptr: int, rxx_ptr: int, mx, my, vx, vy, mask=0):
+    """Same on device memory (both pointers on the current device); returns after the kernel finished."""
+    _check(lib().crsdr_augment_covariance(int(ra_ptr), int(rxx_ptr), int(mx), int(my), int(vx), int(vy), mask_bits(mask), MEM_DEVICE))
+
+
+def augment_lags(mx, my, vx, vy, mask=0):
+    """crsdr_augment_lags (host arithmetic, no device): (counts [vy][2 vx - 1] int32 with c(u) at [uy][ux + vx - 1], the number of
+    uncovered half-plane lags)."""
+    counts = np.zeros((max(int(vy), 1), max(2 * int(vx) - 1, 1)), dtype=np.int32)
+    missing = C.c_int(0)
+    _check(lib().crsdr_augment_lags(int(mx), int(my), int(vx), int(vy), mask_bits(mask), _p(counts, C.c_int32), C.byref(missing)))
+    return counts, missing.value
 
 
 def source_order(sv, nsnap, criterion=ORDER_MDL, kmin=1, kmax=None):
@@ -893,6 +940,27 @@ class Doa:
         rs = np.zeros((self._last()[0], self.ms, self.ms), dtype=np.complex64)
         _check(lib().crsdr_doa_fetch_smoothed(self._h, _p(rs.view(np.float32), C.c_float)))
         return rs
+
+    def set_augment(self, vx: int, vy: int = 0, mask=0):
+        """crsdr_doa_set_augment: from the next submit on, the covariance of the filled vx x vy virtual array, rebuilt from the per-lag
+        averages over the elements of `mask` (mask_bits; 0: all), feeds the subspace; sv and vec then have vx * vy entries.  vx = 0: off.
+        Waits for the device if a submit was made, and discards that submit's results."""
+        _check(lib().crsdr_doa_set_augment(self._h, int(vx), int(vy), mask_bits(mask)))
+        if vx:
+            self.ms, self._sub = int(vx) * int(vy), (int(vx), int(vy))
+        else:
+            self.ms, self._sub = self.m, (self.mx, self.my)
+
+    def fetch_augmented(self) -> np.ndarray:
+        """ra [nest][mv][mv] complex64 of the last submit."""
+        ra = np.zeros((self._last()[0], self.ms, self.ms), dtype=np.complex64)
+        _check(lib().crsdr_doa_fetch_augmented(self._h, _p(ra.view(np.float32), C.c_float)))
+        return ra
+
+    def augment_buffers(self) -> dict:
+        p, vx, vy = C.c_void_p(), C.c_int(0), C.c_int(0)
+        _check(lib().crsdr_doa_augment_buffers(self._h, C.byref(p), C.byref(vx), C.byref(vy)))
+        return {"ra": p.value, "vx": vx.value, "vy": vy.value}
 
     def set_order(self, criterion: int, kmin: int = 1, kmax: int | None = None, limit_directions: bool = False):
         """crsdr_doa_set_order: from the next submit on, every estimate's source count k_e (ORDER_MDL / ORDER_AIC over kmin .. kmax,

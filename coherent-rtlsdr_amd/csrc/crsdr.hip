@@ -166,6 +166,60 @@ static bool smooth_shape_ok(int mx, int my, int sx, int sy, uint32_t flags)
            sx * sy >= 2 && !(flags & ~(uint32_t)CRSDR_SMOOTH_FB);
 }
 
+// Co-array augmentation (augment.hpp): sizes and mask, then c(u) of every half-plane lag.  counts [vy][2 vx - 1] (may be NULL) takes
+// c(u) at [uy][ux + vx - 1], row 0's negative ux the mirrored count; *uncovered the number of half-plane lags with c(u) = 0, (*fux, *fuy)
+// the first of them in the kernel's lag order (uy, then ux).  CRSDR_EINVAL for bad sizes or mask alone.
+static uint64_t augment_mask(int m, uint64_t mask) { return mask ? mask : (m >= 64 ? ~(uint64_t)0 : (((uint64_t)1 << m) - 1)); }
+
+static int augment_lag_counts(const char *who, int mx, int my, int vx, int vy, uint64_t mask, int32_t *counts, int *uncovered, int *fux, int *fuy)
+{
+    if (mx < 1 || my < 1 || (long long)mx * my < 2 || (long long)mx * my > music::MAX_M)
+        return fail(CRSDR_EINVAL, "%s: array of %d x %d elements (m = mx * my in [2, %d])", who, mx, my, music::MAX_M);
+    if (vx < 1 || vx > mx || vy < 1 || vy > my || vx * vy < 2)
+        return fail(CRSDR_EINVAL, "%s: virtual array of %d x %d in an array of %d x %d (1 <= vx <= mx, 1 <= vy <= my, vx * vy >= 2)", who, vx, vy, mx, my);
+    const int m = mx * my;
+    if (mask && ((m < 64 && (mask >> m)) || !(mask & (mask - 1))))
+        return fail(CRSDR_EINVAL, "%s: mask = 0x%llx (0 = all %d elements; else no bit from %d on and at least two bits set)", who, (unsigned long long)mask, m, m);
+    const uint64_t present = augment_mask(m, mask);
+    int missing = 0;
+    for (int uy = 0; uy < vy; ++uy)
+        for (int ux = uy ? -(vx - 1) : 0; ux < vx; ++ux) {
+            int c = 0;
+            for (int p = 0; p < m; ++p) {
+                const int ixq = p % mx + ux, iyq = p / mx + uy;
+                if (ixq < 0 || ixq >= mx || iyq >= my) continue;
+                if (((present >> p) & 1u) && ((present >> (iyq * mx + ixq)) & 1u)) ++c;
+            }
+            if (counts) {
+                counts[uy * (2 * vx - 1) + ux + vx - 1] = c;
+                if (uy == 0) counts[vx - 1 - ux] = c;
+            }
+            if (c == 0 && missing++ == 0) {
+                if (fux) *fux = ux;
+                if (fuy) *fuy = uy;
+            }
+        }
+    if (uncovered) *uncovered = missing;
+    return CRSDR_OK;
+}
+
+// what crsdr_doa_set_augment and crsdr_augment_covariance ask: the above, and every lag covered
+static int augment_args_ok(const char *who, int mx, int my, int vx, int vy, uint64_t mask)
+{
+    int missing = 0, ux = 0, uy = 0;
+    const int rc = augment_lag_counts(who, mx, my, vx, vy, mask, nullptr, &missing, &ux, &uy);
+    if (rc) return rc;
+    if (missing)
+        return fail(CRSDR_EINVAL, "%s: no pair of present receivers at lag (ux, uy) = (%d, %d), the first of %d uncovered lags of the %d x %d virtual array", who, ux, uy,
+                    missing, vx, vy);
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_augment_lags(int mx, int my, int vx, int vy, uint64_t mask, int32_t *counts, int *uncovered)
+{
+    return augment_lag_counts("augment_lags", mx, my, vx, vy, mask, counts, uncovered, nullptr, nullptr);
+}
+
 static int subband_args_ok(const char *who, int blocksize, int nfft, int first, int nbands, int width, int window)
 {
     if (nfft < (1 << subband::SB_MIN_LOG2) || nfft > (1 << subband::SB_MAX_LOG2) || (nfft & (nfft - 1)))
@@ -2088,5 +2142,33 @@ extern "C" int crsdr_esprit2d(int32_t *found, int32_t *status, double *phases, f
     st.back(flags, d_fl, sizeof(int32_t) * n);
     st.back(found, d_fo, sizeof(int32_t));
     st.back(status, d_st, sizeof(int32_t));
+    return st.finish();
+}
+
+// ================================================================================================
+// (iv) continued: co-array augmentation (augment.hpp).  As above: the kernels are defined and first used here, behind every other
+// kernel, so that the code object's other kernels stay where they were
+// ================================================================================================
+#include "augment.hpp"
+
+static void doa_augment_enqueue(unsigned nmat, hipStream_t S, const float2 *rxx, int mx, int my, int vx, int vy, uint64_t mask, float2 *ra)
+{
+    hipLaunchKernelGGL(augment::k_doa_augment<augment::AG_THREADS>, dim3(nmat), dim3(augment::AG_THREADS), 0, S, rxx, mx, my, vx, vy, augment_mask(mx * my, mask), ra);
+}
+
+extern "C" int crsdr_augment_covariance(float *ra, const float *rxx, int mx, int my, int vx, int vy, uint64_t mask, int mem_kind)
+{
+    if (!ra || !rxx) return fail(CRSDR_EINVAL, "augment_covariance: need ra, rxx");
+    { const int rc_ = augment_args_ok("augment_covariance", mx, my, vx, vy, mask); if (rc_) return rc_; }
+    OP_PROLOGUE_MEM("augment_covariance", mem_kind);
+    const size_t m = (size_t)mx * my, mv = (size_t)vx * vy, mm = sizeof(float2) * m * m, vb = sizeof(float2) * mv * mv;
+    OpStage st(mem_kind);
+    const float2 *d_r = (const float2 *)st.in(0, rxx, mm, 8);
+    float2 *d_a = (float2 *)st.out(1, ra, vb, 8);
+    if (st.rc) return st.rc;
+    if (st.misaligned) return fail(CRSDR_EINVAL, "augment_covariance: device rxx and ra 8-byte aligned");
+    hipLaunchKernelGGL(augment::k_augment_covariance<augment::AG_THREADS>, dim3(1), dim3(augment::AG_THREADS), 0, 0, d_r, mx, my, vx, vy, augment_mask((int)m, mask), d_a);
+    HIP_TRY(hipGetLastError());
+    st.back(ra, d_a, vb);
     return st.finish();
 }

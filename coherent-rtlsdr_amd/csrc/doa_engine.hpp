@@ -12,7 +12,8 @@
 //      replaces the scan's kernel by spectrum.hpp's (the Bartlett or the Capon map): the same launches, nothing allocated.
 //      crsdr_doa_set_refine adds refine.hpp's launch behind the directions and ahead of the beams, which then steer off the grid.
 //      crsdr_doa_set_esprit adds esprit.hpp's launch between the source count and the scan (BESIDE), or puts it in the place of the
-//      scan, the peak, the local peaks and the refinement (ONLY).
+//      scan, the peak, the local peaks and the refinement (ONLY).  crsdr_doa_set_augment puts augment.hpp's launch where smoothing's
+//      would be: the covariance of a filled virtual array from the receivers that are present.
 //
 // Shape of the host code.  A feature is a sub-struct of crsdr_doa: its parameters and its device buffers, each buffer owned by a
 // DevBuf, so that "off" is an assignment of {} and nothing is freed by a list kept by hand.  What the last submit left (DoaLast) is
@@ -101,6 +102,14 @@ struct DoaSmooth {
     uint32_t flags = 0;
     DevBuf<float2> rs;
 };
+// crsdr_doa_set_augment: a virtual array of vx x vy elements from the elements of `mask` (0 = all), the augmented covariances
+// [nmat][vx vy][vx vy]
+struct DoaAugment {
+    bool on = false;
+    int vx = 0, vy = 0;
+    uint64_t mask = 0;
+    DevBuf<float2> ra;
+};
 // crsdr_doa_set_order: criterion (0 = off), the candidates kmin .. kmax, whether the directions are capped by the count;
 // k [nest], criterion values [nest][kmax - kmin + 1]
 struct DoaOrder {
@@ -124,7 +133,7 @@ struct DoaEsprit {
 };
 // what the last submit left: where, how much, and which features ran (kRan*).  A setter clears its feature's bit: "nothing submitted
 // since"; without kRanBase nothing is left at all
-constexpr unsigned kRanBase = 1u, kRanPeaks = 2u, kRanBeams = 4u, kRanSmooth = 8u, kRanOrder = 16u, kRanRefine = 32u, kRanEsprit = 64u, kRanScan = 128u;
+constexpr unsigned kRanBase = 1u, kRanPeaks = 2u, kRanBeams = 4u, kRanSmooth = 8u, kRanOrder = 16u, kRanRefine = 32u, kRanEsprit = 64u, kRanScan = 128u, kRanAugment = 256u;
 struct DoaLast {
     hipStream_t stream = nullptr;
     int nest = 0, nblocks = 0, ms = 0, launches = 0;
@@ -146,15 +155,17 @@ struct crsdr_doa {
     DoaPeaks peaks;
     DoaBeams beams;
     DoaSmooth smooth;
+    DoaAugment augment;
     DoaOrder order;
     DoaRefine refine;
     DoaEsprit esprit;
     int spectrum = CRSDR_SPECTRUM_MUSIC;           // crsdr_doa_set_spectrum: the map the scan computes, and CAPON's loading
     float spectrum_loading = 0.f;
     DoaLast last;
-    // what the subspace, the order, the scan and the peaks work on: the sub-arrays while smoothing is on, the array otherwise
-    int sx() const { return smooth.on ? smooth.sx : mx; }
-    int sy() const { return smooth.on ? smooth.sy : my; }
+    // what the subspace, the order, the scan and the peaks work on: the virtual array while augmentation is on, the sub-arrays while
+    // smoothing is (the two exclude each other), the array otherwise
+    int sx() const { return augment.on ? augment.vx : smooth.on ? smooth.sx : mx; }
+    int sy() const { return augment.on ? augment.vy : smooth.on ? smooth.sy : my; }
     int ms() const { return sx() * sy(); }
 };
 constexpr int kMaxDoaMatrices = 4096;      // (max_batch / frames) * nbands
@@ -169,6 +180,8 @@ static void doa_refine_enqueue(dim3 grid, hipStream_t S, const float2 *vec, cons
 static void doa_esprit_enqueue(unsigned nmat, hipStream_t S, const float2 *vec, const float *sv, int M, int k, const int32_t *korder, float d, int SX, int SY, int slots,
                                int32_t *found, int32_t *status, double *phases, float *angles, float *modulus, float *power, int32_t *flags);
 // the most sources ESPRIT can place on an mx x my array: the rows left when a column or a row of elements is dropped, and the kernel's 16
+// augment.hpp's kernel likewise
+static void doa_augment_enqueue(unsigned nmat, hipStream_t S, const float2 *rxx, int mx, int my, int vx, int vy, uint64_t mask, float2 *ra);
 static int esprit_rank_limit(int mx, int my) { return std::min(std::min((mx - 1) * my, mx * (my - 1)), (int)esprit::MAX_K); }
 // k_doa_scan<false> is named here, ahead of the stages, to keep the code object's kernels in the order they have always had: a
 // device-only assembly of the translation unit then compares line by line with an earlier build's
@@ -315,7 +328,8 @@ static int doa_stage_covariance(crsdr_doa *q, DoaRun &r)
                    q->nrows, q->B, q->frames, q->mat.rxx.p);
 }
 
-// smoothing on: subspace, order, scan and peaks work on rs, an sx x sy array of M = ms elements (off: sx = mx, sy = my, M = m)
+// smoothing on: subspace, order, scan and peaks work on rs, an sx x sy array of M = ms elements (off: sx = mx, sy = my, M = m);
+// augmentation on: on ra, a vx x vy array of M = mv elements
 static int doa_stage_subspace(crsdr_doa *q, DoaRun &r)
 {
     const float2 *cov = q->mat.rxx;
@@ -324,6 +338,11 @@ static int doa_stage_subspace(crsdr_doa *q, DoaRun &r)
                                q->smooth.flags, q->smooth.rs.p);
         if (rc) return rc;
         cov = q->smooth.rs;
+    } else if (q->augment.on) {
+        doa_augment_enqueue(r.nest, r.S, (const float2 *)q->mat.rxx, q->mx, q->my, q->augment.vx, q->augment.vy, q->augment.mask, q->augment.ra.p);
+        HIP_TRY(hipGetLastError());
+        ++r.launches;
+        cov = q->augment.ra;
     }
     return doa_run(r, doa::k_doa_subspace, dim3(r.nest), dim3(music::JT), 2 * sizeof(double2) * (size_t)r.M * r.M, cov, r.M, q->mat.sv.p, q->mat.vec.p, q->mat.info.p);
 }
@@ -440,7 +459,7 @@ static int doa_launch(crsdr_doa *q, const int8_t *packets, size_t packet_stride,
         (rc = doa_stage_refine(q, r)) || (rc = doa_stage_beams(q, r)))
         return rc;
     q->last = DoaLast{S, (int)r.nest, nblocks, r.M, r.launches,
-                      kRanBase | (q->peaks.count ? kRanPeaks : 0u) | (q->beams.mode ? kRanBeams : 0u) | (q->smooth.on ? kRanSmooth : 0u) | (q->order.crit ? kRanOrder : 0u) |
+                      kRanBase | (q->peaks.count ? kRanPeaks : 0u) | (q->beams.mode ? kRanBeams : 0u) | (q->smooth.on ? kRanSmooth : 0u) | (q->augment.on ? kRanAugment : 0u) | (q->order.crit ? kRanOrder : 0u) |
                           (q->refine.levels ? kRanRefine : 0u) | (q->esprit.mode ? kRanEsprit : 0u) | (q->esprit.mode == CRSDR_ESPRIT_ONLY ? 0u : kRanScan),
                       q->refine.levels ? (q->peaks.count ? q->peaks.count : 1) : 0, q->esprit.mode ? doa_esprit_slots(q) : 0};
     return CRSDR_OK;
@@ -620,6 +639,9 @@ static int doa_set_beams(crsdr_doa *q, const char *who, bool band, int mode, flo
         return fail(CRSDR_ESTATE, "%s: subbands are on (crsdr_doa_set_subbands): a band's weights applied to the wideband samples mean nothing", who);
     if (mode != CRSDR_BEAM_OFF && band && !q->sub.nfft)
         return fail(CRSDR_ESTATE, "%s: subbands are off (crsdr_doa_set_subbands): the wideband beams are crsdr_doa_set_beams", who);
+    if (mode != CRSDR_BEAM_OFF && q->augment.on)
+        return fail(CRSDR_ESTATE, "%s: augmentation is on (crsdr_doa_set_augment): the subspace is the %d x %d virtual array's, and weights from it are not the physical rows'", who,
+                    q->sx(), q->sy());
     if (mode != CRSDR_BEAM_OFF && q->ms() < q->m)
         return fail(CRSDR_ESTATE, "%s: smoothing over %d x %d sub-arrays is on (crsdr_doa_set_smoothing): the weights are %d-vectors and there is no %d x %d subspace", who,
                     q->sx(), q->sy(), q->m, q->m, q->m);
@@ -787,6 +809,9 @@ extern "C" int crsdr_doa_set_smoothing(crsdr_doa *q, int sx, int sy, uint32_t fl
         return fail(CRSDR_EINVAL, "doa_set_smoothing: sub-arrays of %d x %d in an array of %d x %d, flags = 0x%x (1 <= sx <= mx, 1 <= sy <= my, sx * sy >= 2, CRSDR_SMOOTH_FB)", sx,
                     sy, q->mx, q->my, flags);
     const int ms = sx * sy;
+    if (q->augment.on && (ms < q->m || flags))
+        return fail(CRSDR_ESTATE, "doa_set_smoothing: augmentation is on (crsdr_doa_set_augment): its matrix is Hermitian block-Toeplitz, all its sub-array blocks are equal and it is "
+                                  "persymmetric already, so smoothing it changes nothing: turn augmentation off first");
     if (q->k >= ms) return fail(CRSDR_EINVAL, "doa_set_smoothing: k = %d sources need sub-arrays of more than %d elements (%d x %d)", q->k, q->k, sx, sy);
     if (q->order.crit && q->order.kmax >= ms)
         return fail(CRSDR_EINVAL, "doa_set_smoothing: the order range ends at kmax = %d, sub-arrays of %d x %d have %d elements", q->order.kmax, sx, sy, ms);
@@ -810,6 +835,51 @@ extern "C" int crsdr_doa_fetch_smoothed(crsdr_doa *q, float *rs)
     if (!q->smooth.on) return fail(CRSDR_ESTATE, "doa_fetch_smoothed: no crsdr_doa_set_smoothing");
     if (!(q->last.ran & kRanSmooth)) return fail(CRSDR_ESTATE, "doa_fetch_smoothed: nothing submitted since crsdr_doa_set_smoothing");
     return DoaFetch(q).copy(rs, q->smooth.rs.p, (size_t)q->last.nest * (size_t)q->ms() * q->ms()).wait();
+}
+
+// ---- co-array augmentation (augment.hpp) ----
+extern "C" int crsdr_doa_set_augment(crsdr_doa *q, int vx, int vy, uint64_t mask)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_set_augment: NULL doa");
+    if (vx != 0) {
+        const int rc = augment_args_ok("doa_set_augment", q->mx, q->my, vx, vy, mask);
+        if (rc) return rc;
+        const int mv = vx * vy;
+        if (q->k >= mv) return fail(CRSDR_EINVAL, "doa_set_augment: k = %d sources need a virtual array of more than %d elements (%d x %d)", q->k, q->k, vx, vy);
+        if (q->order.crit && q->order.kmax >= mv)
+            return fail(CRSDR_EINVAL, "doa_set_augment: the order range ends at kmax = %d, the virtual array of %d x %d has %d elements", q->order.kmax, vx, vy, mv);
+        if (q->smooth.on)
+            return fail(CRSDR_ESTATE, "doa_set_augment: smoothing is on (crsdr_doa_set_smoothing): the augmented matrix is block-Toeplitz and persymmetric already, smoothing it "
+                                      "changes nothing: turn smoothing off first");
+        if (q->beams.mode)
+            return fail(CRSDR_ESTATE, "doa_set_augment: beams are on (crsdr_doa_set_beams or _set_subband_beams): the subspace would be the virtual array's, and weights from it are not "
+                                      "the physical rows': turn them off first");
+    }
+    { const int rc = doa_quiesce(q); if (rc) return rc; }
+    // sv and vec change their shape and every direction its array: nothing the last submit left stays
+    q->augment = {}; q->last.ran = 0;
+    if (vx == 0) return CRSDR_OK;
+    const size_t nmat = doa_capacity(q), mv = (size_t)vx * vy;
+    if (q->augment.ra.alloc(nmat * mv * mv)) return fail(CRSDR_ENOMEM, "doa_set_augment: %zu bytes of device memory", sizeof(float2) * nmat * mv * mv);
+    q->augment.on = true; q->augment.vx = vx; q->augment.vy = vy; q->augment.mask = mask;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_doa_fetch_augmented(crsdr_doa *q, float *ra)
+{
+    if (!q || !ra) return fail(CRSDR_EINVAL, "doa_fetch_augmented: NULL doa or ra");
+    if (!q->augment.on) return fail(CRSDR_ESTATE, "doa_fetch_augmented: no crsdr_doa_set_augment");
+    if (!(q->last.ran & kRanAugment)) return fail(CRSDR_ESTATE, "doa_fetch_augmented: nothing submitted since crsdr_doa_set_augment");
+    return DoaFetch(q).copy(ra, q->augment.ra.p, (size_t)q->last.nest * (size_t)q->ms() * q->ms()).wait();
+}
+
+extern "C" int crsdr_doa_augment_buffers(crsdr_doa *q, void **ra, int *vx, int *vy)
+{
+    if (!q) return fail(CRSDR_EINVAL, "doa_augment_buffers: NULL doa");
+    if (ra) *ra = q->augment.ra;
+    if (vx) *vx = q->augment.vx;
+    if (vy) *vy = q->augment.vy;
+    return CRSDR_OK;
 }
 
 extern "C" int crsdr_doa_set_order(crsdr_doa *q, int criterion, int kmin, int kmax, int limit_directions)
@@ -869,6 +939,8 @@ extern "C" int crsdr_doa_set_subbands(crsdr_doa *q, int nfft, int first, int nba
     }
     if (q->peaks.count || q->beams.mode || q->smooth.on || q->order.crit)
         return fail(CRSDR_ESTATE, "doa_set_subbands: peaks, beams, smoothing or the source count are on: their buffers are sized by the bands, turn them off first");
+    if (q->augment.on)
+        return fail(CRSDR_ESTATE, "doa_set_subbands: augmentation is on (crsdr_doa_set_augment): its buffer is sized by the bands, turn it off first");
     { const int rc = doa_quiesce(q); if (rc) return rc; }
     q->last = {};                                        // the matrices change their number: what the last submit left is gone
     q->mat = {};

@@ -100,6 +100,19 @@ int batch::set_smoothing(int sx, int sy, bool fb)
     return rc;
 }
 
+int batch::set_augment(int vx, int vy, uint64_t mask)
+{
+    int rc = doa ? crsdr_doa_set_augment(doa, vx, vy, mask) : CRSDR_ESTATE;
+    if (!rc) {
+        ms = vx ? vx * vy : m;
+        aug_x = vx; aug_y = vx ? vy : 0;
+        aug_receivers = 0;
+        for (int i = 0; vx && i < m; ++i) aug_receivers += mask ? (int)((mask >> i) & 1u) : 1;
+    }
+    if (rc && doa) std::fprintf(stderr, "cbeamformer::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
 int batch::set_order(int criterion, int kmin, int kmax, bool limit_directions)
 {
     int rc = doa ? crsdr_doa_set_order(doa, criterion, kmin, kmax > 0 ? kmax : ms - 1, limit_directions ? 1 : 0) : CRSDR_ESTATE;

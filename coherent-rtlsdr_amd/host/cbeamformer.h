@@ -41,6 +41,7 @@ class batch {
     bool keep = false;
     int nbands = 0;                                  // set_subbands: bands per estimate (0: off)
     int nbandbeams = 0, band_j = 0, band_width = 0;  // set_subband_beams: slots; set_subbands: segments per block, bins per band
+    int aug_x = 0, aug_y = 0, aug_receivers = 0;     // set_augment: the virtual array (0: off), the receivers it is built from
 public:
     // nrows x blocksize: the packets' geometry (1 + Mx * My rows); keep_spectrum: fetch() also fills pm
     batch(int nrows, int blocksize, int max_batch, int K = 1, int frames = 1, bool keep_spectrum = false, float d = D, int Mx = MX, int My = MY,
@@ -65,6 +66,14 @@ public:
     // from the next submit on, every estimate's source count (crsdr_doa_set_order: CRSDR_ORDER_MDL / CRSDR_ORDER_AIC over kmin .. kmax)
     // replaces K in its scan; limit_directions: set_peaks reports at most that many.  CRSDR_ORDER_OFF: off.
     int set_order(int criterion, int kmin = 1, int kmax = 0, bool limit_directions = false);      // kmax = 0: the largest, size - 1
+    // from the next submit on, the covariance of a filled vx x vy virtual array, rebuilt from the per-lag averages over the receivers
+    // of `mask` (bit i: element i is present; 0: all), feeds the subspace (crsdr_doa_set_augment: thinned arrays, dead receivers); sv then
+    // has vx * vy entries per estimate and every direction is the virtual array's.  vx = 0: off.  Discards the last submit's results.
+    // Refused while smoothing or beams are on, and for a mask that leaves a lag of the virtual array without a pair of receivers.
+    int set_augment(int vx, int vy, uint64_t mask = 0);
+    int virtual_x() const { return aug_x; }
+    int virtual_y() const { return aug_y; }
+    int receivers() const { return aug_receivers; }  // with set_augment: the receivers used
     // from the next submit on, one covariance per (estimate, band) in place of the time-domain one (crsdr_doa_set_subbands): band i is
     // `width` bins of an nfft-point transform from bin first + i * width on (FFT order, wrapping), window CRSDR_WINDOW_*.  Every vector
     // below then holds estimates() = blocks / frames * bands() entries, estimate e's band i at e * bands() + i, and band_power is

@@ -59,6 +59,8 @@ int main(int argc, char **argv)
     float beam_loading = 1e-2f;
     int smooth_x = 0, smooth_y = 0, order_crit = CRSDR_ORDER_OFF, spectrum_kind = CRSDR_SPECTRUM_MUSIC, refine_levels = 0, esprit_mode = CRSDR_ESPRIT_OFF;
     bool smooth_fb = false;
+    int augment_x = 0, augment_y = 0;
+    std::string augment_mask;
     int sb_nfft = 0, sb_first = 0, sb_count = 1, sb_width = 1, sb_window = CRSDR_WINDOW_RECT;
     bool engine_batches = false;
     int ranks = 1, rank = 0, device = 0;
@@ -98,6 +100,10 @@ int main(int argc, char **argv)
         // count per estimate (crsdr_doa_set_order), printed as k
         else if (a == "--smooth" && i + 1 < argc) { if (std::sscanf(argv[++i], "%dx%d", &smooth_x, &smooth_y) != 2) smooth_x = smooth_y = -1; }
         else if (a == "--fb") smooth_fb = true;
+        // with --bench --music: the covariance of a filled VX x VY virtual array from the receivers of --mask (crsdr_doa_set_augment): BITS is
+        // one character '0' / '1' per signal channel in element order, element i = character i; without --mask every receiver is used
+        else if (a == "--augment" && i + 1 < argc) { if (std::sscanf(argv[++i], "%dx%d", &augment_x, &augment_y) != 2) augment_x = augment_y = -1; }
+        else if (a == "--mask" && i + 1 < argc) augment_mask = argv[++i];
         else if (a == "--order" && i + 1 < argc) {
             const std::string c = argv[++i];
             order_crit = c == "mdl" ? CRSDR_ORDER_MDL : c == "aic" ? CRSDR_ORDER_AIC : -1;
@@ -345,6 +351,21 @@ int main(int argc, char **argv)
                 const int sx = smooth_x ? smooth_x : cbeamformer::MX, sy = smooth_x ? smooth_y : cbeamformer::MY;
                 if (doa->set_smoothing(sx, sy, smooth_fb)) { std::printf("doa: --smooth %dx%d%s refused\nDEMO FAILED\n", sx, sy, smooth_fb ? " --fb" : ""); return 1; }
             }
+            if (augment_x || !augment_mask.empty()) {
+                uint64_t mask = 0;
+                bool bits_ok = augment_x != 0 && (augment_mask.empty() || (int)augment_mask.size() == nsig);
+                for (size_t i = 0; bits_ok && i < augment_mask.size(); ++i) {
+                    if (augment_mask[i] == '1') mask |= (uint64_t)1 << i;
+                    else if (augment_mask[i] != '0') bits_ok = false;
+                }
+                if (!bits_ok) { std::printf("doa: --augment VXxVY [--mask BITS]: BITS is %d characters 0 / 1, one per receiver\nDEMO FAILED\n", nsig); return 1; }
+                if (doa->set_augment(augment_x, augment_y, mask)) {
+                    std::printf("doa: --augment %dx%d --mask %s refused: %s\nDEMO FAILED\n", augment_x, augment_y, augment_mask.empty() ? "(all)" : augment_mask.c_str(),
+                                crsdr_last_error());
+                    return 1;
+                }
+                std::printf("doa: augment: %d receivers of %d -> %d x %d virtual array\n", doa->receivers(), nsig, doa->virtual_x(), doa->virtual_y());
+            }
             if (order_crit && doa->set_order(order_crit)) { std::printf("doa: --order (mdl|aic) refused\nDEMO FAILED\n"); return 1; }
             if (spectrum_kind && doa->set_spectrum(spectrum_kind, beam_loading)) {
                 std::printf("doa: --spectrum (music|bartlett|capon) --loading %g refused\nDEMO FAILED\n", (double)beam_loading);
@@ -365,6 +386,8 @@ int main(int argc, char **argv)
             ok = doa->submit(coherent.engine_plan()) == CRSDR_OK && doa->fetch() == CRSDR_OK;
             if (!ok || !report) return;
             const int n = doa->estimates();
+            if (doa->virtual_x())
+                std::printf("doa: batch %d: the directions below are from %d receivers on the %d x %d virtual array\n", b, doa->receivers(), doa->virtual_x(), doa->virtual_y());
             const double deg = 180.0 / 3.14159265358979323846;
             if (esprit_mode) {
                 // every matrix (estimate, or estimate and band): the grid direction, then the ESPRIT slots in order of power

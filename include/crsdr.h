@@ -547,7 +547,8 @@ int crsdr_doa_fetch_beams(crsdr_doa *doa, float *weights, float *power, float *b
  * while beams are off) and the slot count, for consumers on the same stream.  They change with every crsdr_doa_set_beams. */
 int crsdr_doa_beam_buffers(crsdr_doa *doa, void **weights, void **power, void **beams, int *nbeams);
 
-/* vec [nest][m][m][2] of the last submit, as crsdr_noisesubspace writes it ([nest][ms][ms][2] with crsdr_doa_set_smoothing on).
+/* vec [nest][m][m][2] of the last submit, as crsdr_noisesubspace writes it ([nest][ms][ms][2] with crsdr_doa_set_smoothing on, [nest][mv][mv][2]
+ * with crsdr_doa_set_augment).
  * CRSDR_ESTATE before the first submit. */
 int crsdr_doa_fetch_subspace(crsdr_doa *doa, float *vec);
 
@@ -828,6 +829,57 @@ int crsdr_doa_esprit_buffers(crsdr_doa *doa, void **found, void **status, void *
  * and phases 8-byte, the others 4-byte aligned). */
 int crsdr_esprit2d(int32_t *found, int32_t *status, double *phases, float *angles, float *modulus, float *power, int32_t *flags,
                    const float *vec, const float *sv, int m, int k, float d, int mx, int my, int mem_kind);
+
+/* Co-array augmentation, between the covariance and the subspace: thinned arrays and dead receivers.  Every step behind the
+ * covariance assumes a filled mx x my array whose receivers all work.  From the receivers that are present, the covariance is averaged
+ * per spatial lag, and the covariance of a filled virtual array is rebuilt from the averages; everything downstream runs on that.
+ * With all receivers present it is the redundancy-averaged (block-Toeplitz) covariance estimate.
+ *   Physical array  mx x my, element i = iy * mx + ix, m = mx * my <= 64.
+ *   Mask            bit i set: element i is present.  mask == 0: all m elements.  Otherwise no bit from m on, at least two bits set.
+ *   Virtual array   vx x vy, 1 <= vx <= mx, 1 <= vy <= my, mv = vx * vy >= 2, element j = jy * vx + jx.
+ *   Lags            u = (ux, uy) of the half-plane: uy > 0, or uy == 0 and ux >= 0, with |ux| < vx and uy < vy.  For virtual indices
+ *                   a <= b the lag pos_b - pos_a always lies in it.  P(u) = the pairs (p, q) of present physical elements with
+ *                   (ix_q - ix_p, iy_q - iy_p) = u, by ascending p (q is then determined, and q >= p: only the upper triangle of rxx
+ *                   is read); c(u) = |P(u)|.  Every half-plane lag needs c(u) >= 1: otherwise CRSDR_EINVAL, the text naming the first
+ *                   uncovered lag.
+ * In fp64 from the fp32 rxx, in that order:
+ *     r(u)     = (1 / c(u)) sum_{(p, q) in P(u)} rxx[p][q]
+ *     ra[a][b] = r(pos_b - pos_a)        for a <= b
+ * each value rounded once to fp32, the diagonal's imaginary part exactly 0, ra[b][a] written as the conjugate.  Rows and columns of
+ * absent elements are never read: they may hold anything.
+ * For R = A P A^H + sigma^2 I with diagonal P (incoherent sources) the result is exactly the covariance of the filled vx x vy array,
+ * whatever the mask.  Coherent sources need smoothing instead, and the two do not combine (below).  The matrix is Hermitian
+ * block-Toeplitz but not guaranteed positive semidefinite: the subspace step takes singular values (in the 7 x 3 scenes of the tests
+ * the most negative eigenvalue stays below 0.6 % of the last signal value).  Spatially smoothing the co-array vector would give
+ * ra^2 / P, which has the same vectors: that is why this is the whole step.  (The upstream clients' DA2D orders the 2-D lags along one
+ * dimension and fills a Toeplitz matrix, which is the covariance of no array: parity unpinned.)
+ *
+ * crsdr_doa_set_augment: vx = 0 turns it off (the other arguments are then ignored).  On: from the next submit one launch more, and
+ * the subspace, sv, vec, the source count (M = mv, the raw N: a definition, as on smoothing's sub-arrays), every map, peak, the
+ * directions, the refinement and ESPRIT work on ra as a vx x vy array of M = mv elements with the same d: crsdr_doa_fetch's sv is
+ * [nest][mv], vec [nest][mv][mv][2]; rxx (CRSDR_DOA_KEEP_RXX) stays the raw [m][m].  With subbands on it runs per (estimate, band).
+ * Any time: waits for the device if a submit was made, allocates ra, and discards what the last submit left (every fetch answers
+ * CRSDR_ESTATE until the next submit).  CRSDR_EINVAL for bad sizes, a bad mask, an uncovered lag, desc.k >= mv, or with
+ * crsdr_doa_set_order on and its kmax >= mv.  CRSDR_ESTATE, both ways round, with crsdr_doa_set_smoothing (a Hermitian block-Toeplitz
+ * matrix is persymmetric already and all its sub-array blocks are equal: smoothing it is a no-op) and with crsdr_doa_set_beams /
+ * _set_subband_beams (the subspace is the virtual array's: weights from it are not the physical rows').  crsdr_doa_set_subbands answers
+ * CRSDR_ESTATE while it is on: ra is sized by the bands.
+ * crsdr_doa_fetch_augmented: ra [nest][mv][mv][2] of the last submit; CRSDR_ESTATE while off or before the first submit after the setter.
+ * crsdr_doa_augment_buffers: the device address of ra (NULL while off) and the virtual shape (0, 0 while off). */
+int crsdr_doa_set_augment(crsdr_doa *doa, int vx, int vy, uint64_t mask);
+int crsdr_doa_fetch_augmented(crsdr_doa *doa, float *ra);
+int crsdr_doa_augment_buffers(crsdr_doa *doa, void **ra, int *vx, int *vy);
+
+/* The per-op form: the same device function, bit for bit.  rxx [mx*my][mx*my][2] -> ra [vx*vy][vx*vy][2], sizes and mask as above.
+ * Every argument is checked before a device is touched.  mem_kind: CRSDR_MEM_HOST (copied) or CRSDR_MEM_DEVICE (both on the device,
+ * 8-byte aligned). */
+int crsdr_augment_covariance(float *ra, const float *rxx, int mx, int my, int vx, int vy, uint64_t mask, int mem_kind);
+
+/* The lag counts, pure host arithmetic (no device needed): to plan a thinning, or to decide whether the array survives a dead receiver.
+ * counts [vy][2 vx - 1] (may be NULL) takes c(u) at [uy][ux + vx - 1]; row 0's negative ux hold the mirrored count c(-ux, 0).
+ * *uncovered (may be NULL) = the number of half-plane lags with c(u) = 0: the call itself returns CRSDR_OK then, CRSDR_EINVAL only for
+ * bad sizes or a bad mask.  The setter and the per-op call check with the same function. */
+int crsdr_augment_lags(int mx, int my, int vx, int vy, uint64_t mask, int32_t *counts /* [vy][2vx-1], may be NULL */, int *uncovered);
 
 #ifdef __cplusplus
 }

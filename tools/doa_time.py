@@ -26,6 +26,9 @@
       submit + directions (or peaks) + crsdr_doa_fetch_refined: against (p) (or (b)) of the same build in the same alternation.
   (e) with --esprit beside|only [--subbands ...]: crsdr_doa_set_esprit on an object like (b)'s (or (u)'s with --subbands), then the
       submit + crsdr_doa_fetch_esprit of the angles alone (beside: + the peaks): against the MUSIC submit (b) (or (u)) of the same build in the same alternation.
+  (g) with --augment VXxVY [--mask BITS]: crsdr_doa_set_augment (the filled VX x VY virtual array from the receivers of BITS, one
+      character '0' / '1' per element in element order; without --mask all of them), then the (b) submit + peaks: against (b), the same
+      submit without it, in the same alternation; reported with its frames/s.
 --array MXxMY runs everything on another array than the 7 x 3 one (8x8: M = 64, the largest).
 
 --runs runs of each, alternating a, b, c in one session (two worker processes, both alive throughout); medians and ranges.
@@ -115,7 +118,7 @@ def worker_perop():
 
 
 def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None, fb=False, order=None, subbands=None, window="rect", band_beams=None,
-               spectrum=None, refine=0, esprit=None):
+               spectrum=None, refine=0, esprit=None, augment=None, mask=None):
     """(b), (c), (p), (q), (h), (f), (s), (o) and the plan figures: 'b' / 'c' / 'p' / 'q' / 'h' / 'f' / 's' / 'o' / 'plan' / 'plan+doa' on
     stdin -> seconds of one batch of 64 on stdout."""
     torch, ura, b, dev, pk, off, stride, host = _setup()
@@ -150,6 +153,9 @@ def worker_doa(npeaks=0, radius=1, reps=1, beams=None, loading=1e-2, smooth=None
     if spectrum:
         extra["m"] = b.Doa(NROWS, B, 1, ura.D, *ARRAY, max_batch=T)
         extra["m"].set_spectrum(SPECTRA[spectrum], loading)
+    if augment:
+        extra["g"] = b.Doa(NROWS, B, 1, ura.D, *ARRAY, max_batch=T)
+        extra["g"].set_augment(*_sub_array(augment), mask or 0)
     rdoa = None
     if refine:
         rdoa = b.Doa(NROWS, B, 1, ura.D, *ARRAY, max_batch=T)
@@ -376,6 +382,8 @@ def main():
     ap.add_argument("--window", choices=sorted(WINDOWS), default="rect", help="(u): the segments' window")
     ap.add_argument("--smooth", default=None, metavar="SXxSY", help="(s): sub-arrays of SX x SY elements (crsdr_doa_set_smoothing)")
     ap.add_argument("--fb", action="store_true", help="(f): forward-backward averaging alone; with --smooth: (s) averages backward as well")
+    ap.add_argument("--augment", default=None, metavar="VXxVY", help="(g): the covariance of a filled VX x VY virtual array (crsdr_doa_set_augment)")
+    ap.add_argument("--mask", default=None, metavar="BITS", help="(g): the receivers that are present, one character 0 / 1 per element (default: all)")
     ap.add_argument("--order", choices=sorted(ORDER_MODES), default=None, help="(o): the source count per estimate (crsdr_doa_set_order)")
     ap.add_argument("--beams", choices=sorted(BEAM_MODES), default=None, help="(q), (h): beams toward the directions, this mode")
     ap.add_argument("--band-beams", choices=sorted(BEAM_MODES), default=None, help="(v), (w): with --subbands, a beam per band toward its directions, this mode")
@@ -392,7 +400,7 @@ def main():
     shape = ["--array", a.array] if a.array else []
     if a.worker:
         return worker_perop() if a.worker == "perop" else worker_doa(a.peaks, a.radius, a.reps, a.beams, a.loading, a.smooth, a.fb, a.order, a.subbands, a.window,
-                                                                           a.band_beams, a.spectrum, a.refine, a.esprit)
+                                                                           a.band_beams, a.spectrum, a.refine, a.esprit, a.augment, a.mask)
     if a.band_beams and not a.subbands:
         ap.error("--band-beams needs --subbands")
     if a.once:
@@ -416,7 +424,9 @@ def main():
         pargs += ["--refine", str(a.refine)]
     if a.esprit:
         pargs += ["--esprit", a.esprit]
-    legs = (["f"] if a.fb else []) + (["s"] if a.smooth else []) + (["o"] if a.order else []) + (["u"] if a.subbands else []) + (["v", "w"] if a.band_beams else []) + (["m"] if a.spectrum else []) + (["r"] if a.refine else []) + (["e"] if a.esprit else [])
+    if a.augment:
+        pargs += ["--augment", a.augment] + (["--mask", a.mask] if a.mask else [])
+    legs = (["f"] if a.fb else []) + (["s"] if a.smooth else []) + (["o"] if a.order else []) + (["u"] if a.subbands else []) + (["v", "w"] if a.band_beams else []) + (["m"] if a.spectrum else []) + (["r"] if a.refine else []) + (["e"] if a.esprit else []) + (["g"] if a.augment else [])
     wa, wb = Worker("perop", a.perop_lib, extra=shape), Worker("doa", extra=pargs)
     wl = Worker("doa", a.doa_lib, extra=shape + ["--reps", str(a.reps)]) if a.doa_lib else None
     keys = ["a", "b", "c", "plan", "plan+doa"] + (["lib:b", "lib:c"] if wl else []) + (["p"] if a.peaks else []) + (["q", "h"] if a.beams else []) + legs
@@ -450,8 +460,9 @@ def main():
            "subbands": dict(zip(("nfft", "first", "nbands", "width"), _bands(a.subbands)), window=a.window) if a.subbands else None,
            "band_beams": {"mode": a.band_beams, "loading": a.loading} if a.band_beams else None,
            "spectrum": {"kind": a.spectrum, "loading": a.loading} if a.spectrum else None, "refine": a.refine or None, "esprit": a.esprit,
+           "augment": {"virtual": a.augment, "mask": a.mask} if a.augment else None,
            "ms_per_batch": {k: _stat([1e3 * x for x in v]) for k, v in sec.items()},
-           "frames_per_s": {k: _stat([T / x for x in sec[k]]) for k in ("a", "b", "c") + (("u",) if a.subbands else ())}}
+           "frames_per_s": {k: _stat([T / x for x in sec[k]]) for k in ("a", "b", "c") + (("u",) if a.subbands else ()) + (("g",) if a.augment else ())}}
     if a.subbands:
         rec["u_over_b_ms"] = rec["ms_per_batch"]["u"]["median"] / rec["ms_per_batch"]["b"]["median"]
     rec["b_faster_than_a_ranges_disjoint"] = rec["ms_per_batch"]["b"]["max"] < rec["ms_per_batch"]["a"]["min"]
@@ -464,6 +475,7 @@ def main():
              "u": f"subbands {a.subbands} {a.window}: submit + peaks + power",
              "v": f"subbands + {a.band_beams} band beams: submit + power", "w": "subbands: packets and vec to the host",
              "m": f"{a.spectrum} map: submit + peaks", "r": f"refine {a.refine}: submit + directions + refined",
+             "g": f"augment {a.augment}{' mask ' + a.mask if a.mask else ''}: submit + peaks",
              "e": f"esprit {a.esprit}{' + subbands' if a.subbands else ''}: submit + esprit"}
     for k, s in rec["ms_per_batch"].items():
         fps = f"  {T / (1e-3 * s['median']):10.0f} frames/s" if k in rec["frames_per_s"] else ""
@@ -489,6 +501,10 @@ def main():
         rec["e_over_base_ms"] = rec["ms_per_batch"]["e"]["median"] / rec["ms_per_batch"][base]["median"]
         rec["e_minus_base_ms"] = rec["ms_per_batch"]["e"]["median"] - rec["ms_per_batch"][base]["median"]
         print(f"(e) takes {rec['e_over_base_ms']:.3f} x the time of ({base}), the MUSIC submit of the same build: {1e3 * rec['e_minus_base_ms']:+.0f} us")
+    if a.augment:
+        rec["g_over_b_ms"] = rec["ms_per_batch"]["g"]["median"] / rec["ms_per_batch"]["b"]["median"]
+        print(f"(g) {rec['frames_per_s']['g']['median']:.0f} frames/s with augmentation, (b) {rec['frames_per_s']['b']['median']:.0f} frames/s without it: "
+              f"{rec['g_over_b_ms']:.3f} x the time")
     if a.spectrum:
         rec["m_over_b_ms"] = rec["ms_per_batch"]["m"]["median"] / rec["ms_per_batch"]["b"]["median"]
         print(f"(m) takes {rec['m_over_b_ms']:.3f} x the time of (b), the MUSIC submit at k = 1; the scan's operation count is M / (M - 1) = {M / (M - 1):.3f} x")
