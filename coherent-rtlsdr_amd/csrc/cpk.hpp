@@ -64,6 +64,127 @@ __device__ __forceinline__ c2 twice_minus(c2 p, c2 s)
     return r;
 }
 
+// ---- grouped forms: the same instructions for 2..4 independent values, breadth-first in ONE asm statement ----------------
+// On gfx950 hipcc keeps one wait state (s_nop 0, an issue slot like any VALU instruction) between a packed instruction and
+// a reader right behind it, and -- because it counts an asm statement as no wait state at all -- in front of any asm
+// statement that reads what ANY asm statement wrote since the last instruction of its own ("wait
+// states").  The single forms above put every product's second half right behind its first: a pad per product.  Here all
+// first halves come before all second halves, so inside a statement no instruction reads what the one before it wrote (the
+// author owns that: nothing pads inside the string; tools/k1_isa_count.py --hazards checks it), and the compiler's pad, if
+// any, is one per statement.  Outputs are early-clobber (written before the last input is read) and double as the temp of
+// their own value, so a group of n pins n output pairs beside its inputs.  Bits: tools/pk_check.hip, against the single forms.
+#ifndef CRSDR_PK_GROUPS
+#define CRSDR_PK_GROUPS 1      // 0: every grouped call runs the single forms one after the other (tools/pk_wait.hip's base arm)
+#endif
+#define CPK_MUL1(r, a, b) "v_pk_mul_f32 %" #r ", %" #a ", %" #b " op_sel:[1,1] op_sel_hi:[1,0]\n\t"
+#define CPK_MUL2(r, a, b) "v_pk_fma_f32 %" #r ", %" #a ", %" #b ", %" #r " op_sel_hi:[0,1,1] neg_lo:[0,0,1]\n\t"
+#define CPK_MULC1(r, a, b) "v_pk_mul_f32 %" #r ", %" #a ", %" #b " op_sel:[1,1] op_sel_hi:[0,1]\n\t"
+#define CPK_MULC2(r, a, b) "v_pk_fma_f32 %" #r ", %" #a ", %" #b ", %" #r " op_sel_hi:[1,0,1] neg_hi:[0,0,1]\n\t"
+// r[i] = a[i] * b[i] (CONJ: a[i] * conj(b[i])), i < 2 / 3 / 4
+template <bool CONJ>
+__device__ __forceinline__ void cmul_g2(c2 &r0, c2 &r1, c2 a0, c2 a1, c2 b0, c2 b1)
+{
+#if CRSDR_PK_GROUPS
+    if constexpr (CONJ)
+        asm(CPK_MULC1(0, 2, 4) CPK_MULC1(1, 3, 5) CPK_MULC2(0, 2, 4) CPK_MULC2(1, 3, 5)
+            : "=&v"(r0), "=&v"(r1) : "v"(a0), "v"(a1), "v"(b0), "v"(b1));
+    else
+        asm(CPK_MUL1(0, 2, 4) CPK_MUL1(1, 3, 5) CPK_MUL2(0, 2, 4) CPK_MUL2(1, 3, 5)
+            : "=&v"(r0), "=&v"(r1) : "v"(a0), "v"(a1), "v"(b0), "v"(b1));
+#else
+    r0 = CONJ ? cmulc(a0, b0) : cmul(a0, b0);
+    r1 = CONJ ? cmulc(a1, b1) : cmul(a1, b1);
+#endif
+}
+template <bool CONJ>
+__device__ __forceinline__ void cmul_g3(c2 &r0, c2 &r1, c2 &r2, c2 a0, c2 a1, c2 a2, c2 b0, c2 b1, c2 b2)
+{
+#if CRSDR_PK_GROUPS
+    if constexpr (CONJ)
+        asm(CPK_MULC1(0, 3, 6) CPK_MULC1(1, 4, 7) CPK_MULC1(2, 5, 8) CPK_MULC2(0, 3, 6) CPK_MULC2(1, 4, 7) CPK_MULC2(2, 5, 8)
+            : "=&v"(r0), "=&v"(r1), "=&v"(r2) : "v"(a0), "v"(a1), "v"(a2), "v"(b0), "v"(b1), "v"(b2));
+    else
+        asm(CPK_MUL1(0, 3, 6) CPK_MUL1(1, 4, 7) CPK_MUL1(2, 5, 8) CPK_MUL2(0, 3, 6) CPK_MUL2(1, 4, 7) CPK_MUL2(2, 5, 8)
+            : "=&v"(r0), "=&v"(r1), "=&v"(r2) : "v"(a0), "v"(a1), "v"(a2), "v"(b0), "v"(b1), "v"(b2));
+#else
+    r0 = CONJ ? cmulc(a0, b0) : cmul(a0, b0);
+    r1 = CONJ ? cmulc(a1, b1) : cmul(a1, b1);
+    r2 = CONJ ? cmulc(a2, b2) : cmul(a2, b2);
+#endif
+}
+template <bool CONJ>
+__device__ __forceinline__ void cmul_g4(c2 &r0, c2 &r1, c2 &r2, c2 &r3, c2 a0, c2 a1, c2 a2, c2 a3, c2 b0, c2 b1, c2 b2, c2 b3)
+{
+#if CRSDR_PK_GROUPS
+    if constexpr (CONJ)
+        asm(CPK_MULC1(0, 4, 8) CPK_MULC1(1, 5, 9) CPK_MULC1(2, 6, 10) CPK_MULC1(3, 7, 11)
+            CPK_MULC2(0, 4, 8) CPK_MULC2(1, 5, 9) CPK_MULC2(2, 6, 10) CPK_MULC2(3, 7, 11)
+            : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3) : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(b0), "v"(b1), "v"(b2), "v"(b3));
+    else
+        asm(CPK_MUL1(0, 4, 8) CPK_MUL1(1, 5, 9) CPK_MUL1(2, 6, 10) CPK_MUL1(3, 7, 11)
+            CPK_MUL2(0, 4, 8) CPK_MUL2(1, 5, 9) CPK_MUL2(2, 6, 10) CPK_MUL2(3, 7, 11)
+            : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3) : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(b0), "v"(b1), "v"(b2), "v"(b3));
+#else
+    r0 = CONJ ? cmulc(a0, b0) : cmul(a0, b0);
+    r1 = CONJ ? cmulc(a1, b1) : cmul(a1, b1);
+    r2 = CONJ ? cmulc(a2, b2) : cmul(a2, b2);
+    r3 = CONJ ? cmulc(a3, b3) : cmul(a3, b3);
+#endif
+}
+// v[pos(K + i)] *= w[K + i] (CONJ: its conjugate) for K <= K + i < END, four at a time
+template <bool CONJ, int K, int END, class POS>
+__device__ __forceinline__ void cmul_run(c2 *v, const c2 *w, POS pos)
+{
+    if constexpr (END - K >= 4) {
+        c2 r0, r1, r2, r3;
+        cmul_g4<CONJ>(r0, r1, r2, r3, v[pos(K)], v[pos(K + 1)], v[pos(K + 2)], v[pos(K + 3)], w[K], w[K + 1], w[K + 2], w[K + 3]);
+        v[pos(K)] = r0; v[pos(K + 1)] = r1; v[pos(K + 2)] = r2; v[pos(K + 3)] = r3;
+        cmul_run<CONJ, K + 4, END>(v, w, pos);
+    } else if constexpr (END - K == 3) {
+        c2 r0, r1, r2;
+        cmul_g3<CONJ>(r0, r1, r2, v[pos(K)], v[pos(K + 1)], v[pos(K + 2)], w[K], w[K + 1], w[K + 2]);
+        v[pos(K)] = r0; v[pos(K + 1)] = r1; v[pos(K + 2)] = r2;
+    } else if constexpr (END - K == 2) {
+        c2 r0, r1;
+        cmul_g2<CONJ>(r0, r1, v[pos(K)], v[pos(K + 1)], w[K], w[K + 1]);
+        v[pos(K)] = r0; v[pos(K + 1)] = r1;
+    } else if constexpr (END - K == 1) {
+        v[pos(K)] = CONJ ? cmulc(v[pos(K)], w[K]) : cmul(v[pos(K)], w[K]);
+    }
+}
+
+// The head of an inverse pass for two independent values: p = a w (CONJ: a conj(w)), s = p + b x (b conj(x)) as two fused
+// multiply-adds, t = 2 p - s -- cmul / cmul_add / twice_minus (cmulc / cmulc_add / twice_minus) instruction for instruction,
+// five deep and two wide.  p lives in t's registers.
+#define CPK_ADD1(r, a, b, c) "v_pk_fma_f32 %" #r ", %" #a ", %" #b ", %" #c " op_sel_hi:[1,0,1]\n\t"
+#define CPK_ADD2(r, a, b) "v_pk_fma_f32 %" #r ", %" #a ", %" #b ", %" #r " op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0]\n\t"
+#define CPK_ADDC2(r, a, b) "v_pk_fma_f32 %" #r ", %" #a ", %" #b ", %" #r " op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_hi:[1,0,0]\n\t"
+#define CPK_TWM(r, s) "v_pk_fma_f32 %" #r ", %" #r ", 2.0, %" #s " op_sel_hi:[1,0,1] neg_lo:[0,0,1] neg_hi:[0,0,1]\n\t"
+template <bool CONJ>
+__device__ __forceinline__ void head_g2(c2 &s0, c2 &s1, c2 &t0, c2 &t1, c2 a0, c2 a1, c2 w0, c2 w1, c2 b0, c2 b1, c2 x0, c2 x1)
+{
+#if CRSDR_PK_GROUPS
+    //                 %0 %1 %2 %3        %4 %5 %6 %7 %8 %9 %10 %11
+    if constexpr (CONJ)
+        asm(CPK_MULC1(2, 4, 6) CPK_MULC1(3, 5, 7) CPK_MULC2(2, 4, 6) CPK_MULC2(3, 5, 7)
+            CPK_ADD1(0, 8, 10, 2) CPK_ADD1(1, 9, 11, 3) CPK_ADDC2(0, 8, 10) CPK_ADDC2(1, 9, 11) CPK_TWM(2, 0) CPK_TWM(3, 1)
+            : "=&v"(s0), "=&v"(s1), "=&v"(t0), "=&v"(t1)
+            : "v"(a0), "v"(a1), "v"(w0), "v"(w1), "v"(b0), "v"(b1), "v"(x0), "v"(x1));
+    else
+        asm(CPK_MUL1(2, 4, 6) CPK_MUL1(3, 5, 7) CPK_MUL2(2, 4, 6) CPK_MUL2(3, 5, 7)
+            CPK_ADD1(0, 8, 10, 2) CPK_ADD1(1, 9, 11, 3) CPK_ADD2(0, 8, 10) CPK_ADD2(1, 9, 11) CPK_TWM(2, 0) CPK_TWM(3, 1)
+            : "=&v"(s0), "=&v"(s1), "=&v"(t0), "=&v"(t1)
+            : "v"(a0), "v"(a1), "v"(w0), "v"(w1), "v"(b0), "v"(b1), "v"(x0), "v"(x1));
+#else
+    const c2 p0 = CONJ ? cmulc(a0, w0) : cmul(a0, w0);
+    s0 = CONJ ? cmulc_add(p0, b0, x0) : cmul_add(p0, b0, x0);
+    t0 = twice_minus(p0, s0);
+    const c2 p1 = CONJ ? cmulc(a1, w1) : cmul(a1, w1);
+    s1 = CONJ ? cmulc_add(p1, b1, x1) : cmul_add(p1, b1, x1);
+    t1 = twice_minus(p1, s1);
+#endif
+}
+
 // a + (-i) x = (a.x + x.y, a.y - x.x)      a - (-i) x = (a.x - x.y, a.y + x.x)
 __device__ __forceinline__ c2 add_mi(c2 a, c2 x)
 {
@@ -174,8 +295,8 @@ __device__ __forceinline__ void dft16(c2 *v)
 // multiply-adds), t1 = a ra - c rc = 2 p - t0 -- 10 packed instructions per radix-4 butterfly head instead of 12.
 __device__ __forceinline__ void dft4_inv_mul(c2 &a, c2 &b, c2 &c, c2 &d, c2 ra, c2 rb, c2 rc, c2 rd)
 {
-    const c2 pa = cmul(a, ra), t0 = cmul_add(pa, c, rc), t1 = twice_minus(pa, t0);
-    const c2 pb = cmul(b, rb), t2 = cmul_add(pb, d, rd), u = twice_minus(pb, t2);
+    c2 t0, t1, t2, u;      // pa = a ra, t0 = pa + c rc, t1 = 2 pa - t0;  pb = b rb, t2 = pb + d rd, u = 2 pb - t2
+    head_g2<false>(t0, t2, t1, u, a, b, ra, rb, c, d, rc, rd);
     a = t0 + t2;
     c = t0 - t2;
     b = add_j<+1>(t1, u);

@@ -111,14 +111,23 @@ __device__ __forceinline__ void dft32s_pruned(c2 *v)
 }
 
 // twiddles w[k] = w1^k, k in [1,32), from the five table values (product depth <= 4)
-template <int K>
+// the products of one level, w[HB + j] = w[j] w[HB] for 1 <= j < HB, are independent of each other: grouped (cpk.hpp)
+template <int HB, int J>
+__device__ __forceinline__ void tw_level(c2 *w)
+{
+    if constexpr (HB - J >= 4) {
+        cmul_g4<false>(w[HB + J], w[HB + J + 1], w[HB + J + 2], w[HB + J + 3], w[J], w[J + 1], w[J + 2], w[J + 3], w[HB], w[HB], w[HB], w[HB]);
+        tw_level<HB, J + 4>(w);
+    } else if constexpr (HB - J == 3) cmul_g3<false>(w[HB + J], w[HB + J + 1], w[HB + J + 2], w[J], w[J + 1], w[J + 2], w[HB], w[HB], w[HB]);
+    else if constexpr (HB - J == 2) cmul_g2<false>(w[HB + J], w[HB + J + 1], w[J], w[J + 1], w[HB], w[HB]);
+    else if constexpr (HB - J == 1) w[HB + J] = cmul(w[J], w[HB]);
+}
 __device__ __forceinline__ void tw_chain(c2 *w)
 {
-    if constexpr (K < 32) {
-        constexpr int hb = (K >= 16) ? 16 : (K >= 8) ? 8 : (K >= 4) ? 4 : (K >= 2) ? 2 : 1;
-        if constexpr (K != hb) w[K] = cmul(w[K - hb], w[hb]);
-        tw_chain<K + 1>(w);
-    }
+    tw_level<2, 1>(w);
+    tw_level<4, 1>(w);
+    tw_level<8, 1>(w);
+    tw_level<16, 1>(w);
 }
 __device__ __forceinline__ void tw_load(c2 *w, const c2 *__restrict__ tab, int stride, int idx)
 {
@@ -127,17 +136,14 @@ __device__ __forceinline__ void tw_load(c2 *w, const c2 *__restrict__ tab, int s
     w[4] = tab[2 * stride + idx];
     w[8] = tab[3 * stride + idx];
     w[16] = tab[4 * stride + idx];
-    tw_chain<3>(w);
+    tw_chain(w);
 }
+// DIF: the value for output k sits at xpos(k); DIT: input k sits at k
+template <bool DIF_LAYOUT> struct TwPos { constexpr int operator()(int k) const { return DIF_LAYOUT ? xpos(k) : k; } };
 template <int DIR, bool DIF_LAYOUT, int K>
 __device__ __forceinline__ void tw_apply(c2 *v, const c2 *w)
 {
-    if constexpr (K < 32) {
-        // DIF: the value for output k sits at xpos(k); DIT: input k sits at k
-        constexpr int pos = DIF_LAYOUT ? xpos(K) : K;
-        v[pos] = ctw<DIR>(v[pos], w[K]);
-        tw_apply<DIR, DIF_LAYOUT, K + 1>(v, w);
-    }
+    cmul_run<(DIR > 0), K, 32>(v, w, TwPos<DIF_LAYOUT>{});      // 31 independent products, four to a statement
 }
 
 // Inverse-pass head: the input twiddles (conjugated) folded into the first radix-2 stage of the 32-point transform.
@@ -163,13 +169,28 @@ __device__ __forceinline__ void tw_stage1_inv(c2 *v, const c2 *w)
 template <int I>
 __device__ __forceinline__ void tw_stage1s_inv(c2 *v, const c2 *w)
 {
-    if constexpr (I < 16) {
-        const c2 p = (I == 0) ? v[0] : cmulc(v[I], w[I]);
+    if constexpr (I == 0) {
+        const c2 p = v[0];
+        const c2 s = cmulc_add(p, v[16], w[16]);
+        const c2 t = twice_minus(p, s);
+        v[0] = s;
+        v[16] = fnet::w32b<+1, 0>(t);
+        tw_stage1s_inv<1>(v, w);
+    } else if constexpr (I == 15) {
+        const c2 p = cmulc(v[I], w[I]);
         const c2 s = cmulc_add(p, v[I + 16], w[I + 16]);
         const c2 t = twice_minus(p, s);
         v[I] = s;
         v[I + 16] = fnet::w32b<+1, I>(t);
-        tw_stage1s_inv<I + 1>(v, w);
+    } else if constexpr (I < 15) {
+        // two of the 16 independent heads at a time, breadth-first (cpk.hpp head_g2); the brackets follow on their own
+        c2 s0, s1, t0, t1;
+        head_g2<true>(s0, s1, t0, t1, v[I], v[I + 1], w[I], w[I + 1], v[I + 16], v[I + 17], w[I + 16], w[I + 17]);
+        v[I] = s0;
+        v[I + 1] = s1;
+        v[I + 16] = fnet::w32b<+1, I>(t0);
+        v[I + 17] = fnet::w32b<+1, I + 1>(t1);
+        tw_stage1s_inv<I + 2>(v, w);
     }
 }
 // v[k] = input k (natural order) -> inverse 32-point DFT of (v[k] conj(w[k])), outputs as dft32 leaves them (xpos)

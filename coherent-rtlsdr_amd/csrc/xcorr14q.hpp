@@ -204,6 +204,27 @@ __device__ __forceinline__ float q_wave_max63(float wm)
     return wm;      // valid in lane 63
 }
 
+// Four steps of the first-index search, bi = (m == wm) ? idx : bi for (ma, ia) .. (md, id) in this order: the same four
+// v_cmp_eq_f32 (ordered: a NaN never matches) and four v_cndmask_b32 as the plain loop gives, but the compares go to four
+// mask registers of their own before the first select.  Through VCC every select sits right behind its compare and waits
+// two states for the mask (s_nop 1: 128 wait states per row pair); here each mask is three instructions old when it is read.
+__device__ __forceinline__ int q_first4(int bi, float wm, float ma, float mb, float mc, float md, int ia, int ib, int ic, int id)
+{
+#if CRSDR_PK_GROUPS
+    unsigned long long k0, k1, k2, k3;
+    asm("v_cmp_eq_f32_e64 %1, %5, %6\n\tv_cmp_eq_f32_e64 %2, %5, %7\n\tv_cmp_eq_f32_e64 %3, %5, %8\n\tv_cmp_eq_f32_e64 %4, %5, %9\n\t"
+        "v_cndmask_b32_e64 %0, %0, %10, %1\n\tv_cndmask_b32_e64 %0, %0, %11, %2\n\tv_cndmask_b32_e64 %0, %0, %12, %3\n\tv_cndmask_b32_e64 %0, %0, %13, %4"
+        : "+v"(bi), "=&s"(k0), "=&s"(k1), "=&s"(k2), "=&s"(k3)
+        : "s"(wm), "v"(ma), "v"(mb), "v"(mc), "v"(md), "v"(ia), "v"(ib), "v"(ic), "v"(id));
+#else
+    bi = (ma == wm) ? ia : bi;
+    bi = (mb == wm) ? ib : bi;
+    bi = (mc == wm) ? ic : bi;
+    bi = (md == wm) ? id : bi;
+#endif
+    return bi;
+}
+
 // minimum of v over the 64 lanes (wave-uniform result): the same six DPP steps as q_wave_max63, then lane 63 read back
 __device__ __forceinline__ int q_wave_min(int v)
 {
@@ -410,10 +431,8 @@ __global__ __launch_bounds__(2 * QG, 1) void k_xcorr_lag14q(XcorrArgs a, const f
         int bi = 0x7fffffff;
         if (tm == wm) {
 #pragma unroll
-            for (int i = 31; i >= 0; --i) {
-                bi = (m1[i] == wm) ? i * 512 + vt1 : bi;
-                bi = (m0[i] == wm) ? i * 512 + vt0 : bi;      // vt0 < vt1: the lower index wins at the same i
-            }
+            for (int i = 31; i >= 1; i -= 2)                  // vt0 < vt1: the lower index wins at the same i
+                bi = q_first4(bi, wm, m1[i], m0[i], m1[i - 1], m0[i - 1], i * 512 + vt1, i * 512 + vt0, (i - 1) * 512 + vt1, (i - 1) * 512 + vt0);
         }
         const int wbi = q_wave_min(bi);                       // wave-uniform; 0x7fffffff: no lane compared equal (an all-NaN wave)
         if (lane == 0 || lane == 63) {
