@@ -109,40 +109,70 @@ __device__ __forceinline__ void q_release(QSync *s)
     }
 }
 
+// A global load from a group-uniform base (row, block and table bases are scalar: one item per group) at a 32-bit per-lane
+// byte offset: the scalar-base form of global_load (SGPR pair + VGPR offset + immediate).  Through a 64-bit per-lane pointer
+// every access costs a v_add_co / v_addc pair and the wait state between them.
+template <typename T>
+__device__ __forceinline__ T q_ldg(const void *__restrict__ sbase, uint32_t voff)
+{
+    return *reinterpret_cast<const T *>(static_cast<const char *>(sbase) + voff);
+}
+// tw_load of xcorr14p.hpp with the five seeds read that way
+__device__ __forceinline__ void q_tw_load(c2 *w, const c2 *__restrict__ tab, int stride, int idx)
+{
+    // the stride (4096 bytes at K1's 512 columns) is one more than the immediate field holds: four offsets formed here
+    const uint32_t off = (uint32_t)idx * 8u, sb = (uint32_t)stride * 8u;
+    w[1] = q_ldg<c2>(tab, off);
+    w[2] = q_ldg<c2>(tab, off + sb);
+    w[4] = q_ldg<c2>(tab, off + 2 * sb);
+    w[8] = q_ldg<c2>(tab, off + 3 * sb);
+    w[16] = q_ldg<c2>(tab, off + 4 * sb);
+    tw_chain(w);
+}
 // P0 of one virtual thread without the stores (pass0_forward<false> of xcorr14p.hpp)
 __device__ __forceinline__ void q_p0_compute(c2 *v, const int8_t *__restrict__ row, const c2 *__restrict__ twA, uint32_t xor80, int vt)
 {
-    const uint16_t *src = reinterpret_cast<const uint16_t *>(row);
     const uint32_t x16 = xor80 & 0xFFFFu;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-        const uint32_t u = (uint32_t)src[i * 512 + vt] ^ x16;
+        // 1024-byte steps: four to an offset (immediates 0 .. 3072), the offset moved on by 4096 three times
+        const uint32_t u = (uint32_t)q_ldg<uint16_t>(row + (i & 3) * 1024, (uint32_t)vt * 2u + (uint32_t)(i >> 2) * 4096u) ^ x16;
         v[i] = mk((float)sext8(u, 0), (float)sext8(u, 1));
     }
     dft32s_pruned<false>(v);
     c2 w[32];
-    tw_load(w, twA, TWA_STRIDE, vt);
+    q_tw_load(w, twA, TWA_STRIDE, vt);
     tw_apply<-1, true, 1>(v, w);
 }
 __device__ __forceinline__ void q_p0_store(c2 *A, const c2 *v, int vt)
 {
     int base = p0_base(vt);
     asm volatile("" : "+v"(base));       // formed here, not hoisted out of the row loop and kept (spilled) as 32 addresses
+    // k >= 16 lies beyond the 16-bit offset field of a DS instruction (16 * 528 * 8 = 67584 bytes): from one base the compiler
+    // adds a 32-bit literal per access; from a second opaque base every access is base + immediate
+    int hi = base + 16 * 528;
+    asm volatile("" : "+v"(hi));
 #pragma unroll
-    for (int k = 0; k < 32; ++k) A[base + k * 528] = v[xpos(k)];
+    for (int k = 0; k < 16; ++k) A[base + k * 528] = v[xpos(k)];
+#pragma unroll
+    for (int k = 16; k < 32; ++k) A[hi + (k - 16) * 528] = v[xpos(k)];
 }
 // P0' of one virtual thread: loads, then (separately) the arithmetic down to |.|^2
 __device__ __forceinline__ void q_p0i_load(c2 *v, const c2 *A, int vt)
 {
     int base = p0_base(vt);
     asm volatile("" : "+v"(base));
+    int hi = base + 16 * 528;            // second base for k >= 16 (see q_p0_store)
+    asm volatile("" : "+v"(hi));
 #pragma unroll
-    for (int k = 0; k < 32; ++k) v[k] = A[base + k * 528];
+    for (int k = 0; k < 16; ++k) v[k] = A[base + k * 528];
+#pragma unroll
+    for (int k = 16; k < 32; ++k) v[k] = A[hi + (k - 16) * 528];
 }
 __device__ __forceinline__ void q_p0i_compute(float *m, c2 *v, const c2 *__restrict__ twA, int vt)
 {
     c2 w[32];
-    tw_load(w, twA, TWA_STRIDE, vt);
+    q_tw_load(w, twA, TWA_STRIDE, vt);
     tw_dft32_inv<true>(v, w);
 #pragma unroll
     for (int i = 0; i < 32; ++i) {
@@ -155,19 +185,25 @@ __device__ __forceinline__ void q_refspec_load(float4 *r, const float4 *__restri
 {
     const int g = ((vt >> 6) << 7) + 64 * h + (vt & 63);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = refspec4[j * 1024 + g];
+    for (int j = 0; j < 8; ++j) r[j] = q_ldg<float4>(refspec4, (uint32_t)g * 16u + (uint32_t)j * 16384u);      // 16 KiB steps: an offset each
 }
 // FMA: the FMA-form transforms of K1 (k_xcorr_lag14q); otherwise the product form (k_rows14_cf32q)
+typedef float q_f4 __attribute__((ext_vector_type(4)));      // float4 is a class: no LDS-qualified copies of it
+typedef __attribute__((address_space(3))) q_f4 lds_f4;
 template <bool FMA>
 __device__ __forceinline__ void q_junction_half(float4 *A4, const float4 *r, int vt, int h)
 {
     const int g = ((vt >> 6) << 7) + 64 * h + (vt & 63), key = g & 7;
-    int base = j_base(g);
+    // slot j lives at j_base(g) + (j ^ key).  j_base is a multiple of 8 and j, key < 8, so that is (j_base(g) + key) ^ j:
+    // one exclusive-or with a constant per slot from one opaque value, where the sum wants the eight (j ^ key) << 4 kept
+    // (and re-formed for the second virtual thread) and an add per slot.  On the LDS byte address, so that no shift follows
+    // the exclusive-or: the image's base must be a multiple of 128 bytes (the two-row kernels declare it so).
+    uint32_t base = (uint32_t)(uintptr_t)(lds_f4 *)(A4 + j_base(g) + key);
     asm volatile("" : "+v"(base));
     c2 u[16];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        float4 q = A4[base + (j ^ key)];
+        const q_f4 q = *(const lds_f4 *)(uintptr_t)(base ^ (uint32_t)(j * 16));
         u[2 * j] = mk(q.x, q.y);
         u[2 * j + 1] = mk(q.z, q.w);
     }
@@ -190,11 +226,37 @@ __device__ __forceinline__ void q_junction_half(float4 *A4, const float4 *r, int
 #endif
 #pragma unroll
     for (int j = 0; j < 8; ++j)
-        A4[base + (j ^ key)] = make_float4(u[2 * j].x, u[2 * j].y, u[2 * j + 1].x, u[2 * j + 1].y);
+        *(lds_f4 *)(uintptr_t)(base ^ (uint32_t)(j * 16)) = q_f4{u[2 * j].x, u[2 * j].y, u[2 * j + 1].x, u[2 * j + 1].y};
+}
+
+// fmaxf(a, fmaxf(b, c)) as one instruction.  Left to the optimiser, the lane maximum of the 64 magnitudes is regrouped into
+// pairs (v_max_f32) that are then joined three at a time: 49 instructions where 32 do.  The operands are results of
+// arithmetic, so a NaN among them is a quiet one and is passed over exactly as fmaxf passes over it; the maximum of
+// non-NaN values does not depend on the grouping.
+__device__ __forceinline__ float q_max3(float a, float b, float c)
+{
+    float r;
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
 }
 
 __device__ __forceinline__ float q_wave_max63(float wm)
 {
+#if CRSDR_PK_GROUPS
+    // The six steps below as six v_max_f32 whose first source is the DPP one.  From the builtin each step is a copy (the value
+    // a lane keeps when its source lane lies outside the row or the mask), the DPP move, a v_max x, x, x that quiets a NaN
+    // the optimiser cannot rule out, and the maximum: 24 instructions.  A lane that the row mask or the row's edge leaves out
+    // is not written and keeps wm, as update_dpp(wm, wm, ...) has it; the magnitudes are arithmetic results, never signalling.
+    // A DPP source written by the instruction before wants two wait states (the compiler pads them outside asm: s_nop 1).
+    asm("s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+        "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf"
+        : "+v"(wm));
+    return wm;      // valid in lane 63
+#else
     wm = fmaxf(wm, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(wm), __float_as_int(wm), 0x111, 0xf, 0xf, false)));
     wm = fmaxf(wm, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(wm), __float_as_int(wm), 0x112, 0xf, 0xf, false)));
     wm = fmaxf(wm, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(wm), __float_as_int(wm), 0x114, 0xf, 0xf, false)));
@@ -202,6 +264,7 @@ __device__ __forceinline__ float q_wave_max63(float wm)
     wm = fmaxf(wm, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(wm), __float_as_int(wm), 0x142, 0xa, 0xf, false)));
     wm = fmaxf(wm, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(wm), __float_as_int(wm), 0x143, 0xc, 0xf, false)));
     return wm;      // valid in lane 63
+#endif
 }
 
 // Four steps of the first-index search, bi = (m == wm) ? idx : bi for (ma, ia) .. (md, id) in this order: the same four
@@ -317,7 +380,10 @@ __global__ __launch_bounds__(2 * QG, 1) void k_xcorr_lag14q(XcorrArgs a, const f
                                                            int row_count, int *__restrict__ errflag, unsigned int *__restrict__ work,
                                                            unsigned int work_base, int spin_limit)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // 128-byte aligned (a symbol of its own: the alignment is this kernel's alone): q_junction_half addresses the image's
+    // 16-byte slots by exclusive-or on the LDS byte address, which takes bits 4-6 of the image's base to be clear
+    extern __shared__ __attribute__((aligned(128))) unsigned char smemq[];
+    unsigned char *const smem = smemq;
     const c2 *twA = reinterpret_cast<const c2 *>(twA_), *twB = reinterpret_cast<const c2 *>(twB_);
     c2 *A = reinterpret_cast<c2 *>(smem);
     float4 *A4 = reinterpret_cast<float4 *>(smem);
@@ -371,10 +437,12 @@ __global__ __launch_bounds__(2 * QG, 1) void k_xcorr_lag14q(XcorrArgs a, const f
             q_p0_compute(v2, src, twA, a.xor80, vt1);
             {
                 // P1 / P1' twiddles: from the workgroup's table (no chain per row), outside the ownership window
-                int nb = tid & 15;
-                asm volatile("" : "+v"(nb));
+                // one opaque LDS pointer per row (the table lies beyond the offset field when addressed from the image's base),
+                // then 31 reads at immediates (kk - 1) * 128
+                const lds_c2 *tb = (const lds_c2 *)(twl + (tid & 15));
+                asm volatile("" : "+v"(tb));
 #pragma unroll
-                for (int kk = 1; kk < 32; ++kk) wB[kk] = *(const volatile lds_c2 *)(twl + (kk - 1) * 16 + nb);      // ds_read_b64, not read2 (see pass1_forward)
+                for (int kk = 1; kk < 32; ++kk) wB[kk] = *(const volatile lds_c2 *)(tb + (kk - 1) * 16);      // ds_read_b64, not read2 (see pass1_forward)
             }
             q_acquire(sy, 2 * k + g + 1);
             __builtin_amdgcn_s_setprio(Q_PRIO);                // the owner's window is what the pair's period is made of
@@ -425,7 +493,7 @@ __global__ __launch_bounds__(2 * QG, 1) void k_xcorr_lag14q(XcorrArgs a, const f
         // the finisher has read it: the next row's epilogue lies behind that row's two window barriers, which the finisher joins.
         float tm = fmaxf(m0[0], m1[0]);
 #pragma unroll
-        for (int i = 1; i < 32; ++i) tm = fmaxf(tm, fmaxf(m0[i], m1[i]));
+        for (int i = 1; i < 32; ++i) tm = q_max3(tm, m0[i], m1[i]);
         const int lane = tid & 63, wv = tid >> 6;
         const float wm = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q_wave_max63(tm)), 63));
         int bi = 0x7fffffff;
@@ -522,17 +590,21 @@ __device__ __forceinline__ void q_p0_store2(c2 *A, const c2 *v, const c2 *v2, in
 {
     int base = p0_base(2 * m);            // even: the pair is 16-byte aligned in the image
     asm volatile("" : "+v"(base));
+    int hi = base + 16 * 528;             // second base for k >= 16 (see q_p0_store)
+    asm volatile("" : "+v"(hi));
 #pragma unroll
     for (int k = 0; k < 32; ++k)
-        *reinterpret_cast<float4 *>(A + base + k * 528) = make_float4(v[xpos(k)].x, v[xpos(k)].y, v2[xpos(k)].x, v2[xpos(k)].y);
+        *reinterpret_cast<float4 *>(A + (k < 16 ? base + k * 528 : hi + (k - 16) * 528)) = make_float4(v[xpos(k)].x, v[xpos(k)].y, v2[xpos(k)].x, v2[xpos(k)].y);
 }
 __device__ __forceinline__ void q_p0i_load2(c2 *v, c2 *v2, const c2 *A, int m)
 {
     int base = p0_base(2 * m);
     asm volatile("" : "+v"(base));
+    int hi = base + 16 * 528;
+    asm volatile("" : "+v"(hi));
 #pragma unroll
     for (int k = 0; k < 32; ++k) {
-        const float4 x = *reinterpret_cast<const float4 *>(A + base + k * 528);
+        const float4 x = *reinterpret_cast<const float4 *>(A + (k < 16 ? base + k * 528 : hi + (k - 16) * 528));
         v[k] = mk(x.x, x.y);
         v2[k] = mk(x.z, x.w);
     }
@@ -563,7 +635,10 @@ __global__ __launch_bounds__(2 * QG, 1) void k_rows14_cf32q(c2 *__restrict__ Y, 
                                                            const float4 *__restrict__ refspec_base, int n1, int rows, int nq, int *__restrict__ errflag,
                                                            int spin_limit, RampArgs ra, c2 *__restrict__ Yout)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // 128-byte aligned (a symbol of its own: the alignment is this kernel's alone): q_junction_half addresses the image's
+    // 16-byte slots by exclusive-or on the LDS byte address, which takes bits 4-6 of the image's base to be clear
+    extern __shared__ __attribute__((aligned(128))) unsigned char smemq[];
+    unsigned char *const smem = smemq;
     c2 *A = reinterpret_cast<c2 *>(smem);
     float4 *A4 = reinterpret_cast<float4 *>(smem);
     const int g = threadIdx.x >> 8, tid = threadIdx.x & (QG - 1);

@@ -155,6 +155,34 @@ def metadata(txt):
     return res
 
 
+COLUMNS = ("VALU", "packed", "pk_add", "pk_mul", "pk_fma", "SALU", "nop", "wait", "VGPR", "SGPR", "vspill", "sspill", "scratch")
+
+
+def table(txt, pattern, loops=False):
+    """The table's rows as dicts (the kernel's short name under "kernel", then COLUMNS; the metadata columns are strings),
+    in the order they are printed."""
+    bodies, meta = kernel_bodies(txt, loops), metadata(txt)
+    pat = re.compile(pattern)
+    rows = []
+    for name, mn in sorted(bodies.items()):
+        if not pat.search(name):
+            continue
+        short = re.search(r"\d+(k_\w+?)E", name)
+        short = short.group(1) if short else name[:22]
+        pk = {k: sum(1 for x in mn if x.startswith("v_pk_" + k + "_f32")) for k in ("add", "mul", "fma")}
+        salu = sum(1 for x in mn if x.startswith("s_") and not x.startswith(("s_waitcnt", "s_nop", "s_barrier",
+                                                                             "s_cbranch", "s_branch", "s_setprio",
+                                                                             "s_sleep", "s_endpgm")))
+        nops = [int(x.split(":")[1], 0) + 1 for x in mn if x.startswith("s_nop")]
+        md = meta.get(name, {})
+        rows.append({"kernel": short, "VALU": sum(1 for x in mn if x.startswith("v_")), "packed": sum(pk.values()),
+                     "pk_add": pk["add"], "pk_mul": pk["mul"], "pk_fma": pk["fma"], "SALU": salu, "nop": len(nops),
+                     "wait": sum(nops), "VGPR": md.get("vgpr_count", "?"), "SGPR": md.get("sgpr_count", "?"),
+                     "vspill": md.get("vgpr_spill_count", "?"), "sspill": md.get("sgpr_spill_count", "?"),
+                     "scratch": md.get("private_segment_fixed_size", "?")})
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--asm", help="read this device assembly instead of compiling")
@@ -182,25 +210,11 @@ def main():
                 print(f"    [{i}] {kind}: {a}  ->  {b}")
         print(f"total {total}")
         return 1 if total else 0
-    bodies, meta = kernel_bodies(txt, args.loops), metadata(txt)
-    pat = re.compile(args.pattern)
     print(f"{'kernel':22s} {'VALU':>6s} {'packed':>6s} {'pk_add':>6s} {'pk_mul':>6s} {'pk_fma':>6s} {'SALU':>5s} {'nop':>4s} {'wait':>5s} "
           f"{'VGPR':>4s} {'SGPR':>4s} {'vspill':>6s} {'sspill':>6s} {'scratch':>7s}")
-    for name, mn in sorted(bodies.items()):
-        if not pat.search(name):
-            continue
-        short = re.search(r"\d+(k_\w+?)E", name)
-        short = short.group(1) if short else name[:22]
-        valu = sum(1 for x in mn if x.startswith("v_"))
-        pk = {k: sum(1 for x in mn if x.startswith("v_pk_" + k + "_f32")) for k in ("add", "mul", "fma")}
-        salu = sum(1 for x in mn if x.startswith("s_") and not x.startswith(("s_waitcnt", "s_nop", "s_barrier",
-                                                                             "s_cbranch", "s_branch", "s_setprio",
-                                                                             "s_sleep", "s_endpgm")))
-        nops = [int(x.split(":")[1], 0) + 1 for x in mn if x.startswith("s_nop")]
-        md = meta.get(name, {})
-        print(f"{short:22s} {valu:6d} {sum(pk.values()):6d} {pk['add']:6d} {pk['mul']:6d} {pk['fma']:6d} {salu:5d} {len(nops):4d} {sum(nops):5d} "
-              f"{md.get('vgpr_count', '?'):>4s} {md.get('sgpr_count', '?'):>4s} {md.get('vgpr_spill_count', '?'):>6s} "
-              f"{md.get('sgpr_spill_count', '?'):>6s} {md.get('private_segment_fixed_size', '?'):>7s}")
+    for r in table(txt, args.pattern, args.loops):
+        print(f"{r['kernel']:22s} {r['VALU']:6d} {r['packed']:6d} {r['pk_add']:6d} {r['pk_mul']:6d} {r['pk_fma']:6d} {r['SALU']:5d} {r['nop']:4d} {r['wait']:5d} "
+              f"{r['VGPR']:>4s} {r['SGPR']:>4s} {r['vspill']:>6s} {r['sspill']:>6s} {r['scratch']:>7s}")
     return 0
 
 
