@@ -210,6 +210,11 @@ int crsdr_plan_fetch_block(crsdr_plan *plan, int block, int32_t *lag, float *mag
  * With it on, row k of the matrix is the row advanced by lag_k + D_k samples -- a circular advance of the zero-padded row in
  * the frequency domain: X[f] * exp(+2 pi i f_s (lag_k + D_k) / B), f_s the signed bin index -- then rotated by the phasor
  * and quantised like cdsp::convto8bit; for D = 0 that is the digital mode's zero-filled integer shift.
+ *   The advance is CIRCULAR over the 2 L samples of the zero-padded row (L = blocksize / 2 complex samples, B = 2 L bins): output
+ *   sample n is the band-limited interpolation of the padded row at (n + lag_k + D_k) mod 2 L.  For |lag_k + D_k| <= L the samples
+ *   that leave the row are lost into the padding; for |lag_k + D_k| > L -- a lag at the end of its range, |lag_k| >= L - 64, with
+ *   a D_k of the same sign -- the advance wraps: |lag_k + D_k| - L samples re-enter from the OTHER end of the row (lag_k = -L,
+ *   the all-zero row's lag, with D_k < 0 brings the row's last samples in first).  Nothing is zeroed beyond what the padding gives.
  *   D_k = frac_override[k] if given (host [nrows], copied; entry 0 ignored), else gain * frac_k (this block's estimate).
  *   Bounds: |gain| <= 128 and |frac_override[k]| <= 64 samples (CRSDR_EINVAL otherwise): the response's phase is formed in fp32 and
  *   keeps 1e-5 rad up to there; a proper peak's estimate is |frac| <= 1/2.  Larger delays belong in the integer lag.
