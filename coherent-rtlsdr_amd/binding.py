@@ -46,7 +46,10 @@ ABI_SYMBOLS = [
     "crsdr_doa_set_refine", "crsdr_doa_fetch_refined", "crsdr_doa_refined_buffers", "crsdr_refine2d",
     "crsdr_doa_set_esprit", "crsdr_doa_fetch_esprit", "crsdr_doa_esprit_buffers", "crsdr_esprit2d",
     "crsdr_doa_set_augment", "crsdr_doa_fetch_augmented", "crsdr_doa_augment_buffers", "crsdr_augment_covariance", "crsdr_augment_lags",
+    "crsdr_plan_set_refcancel", "crsdr_plan_fetch_refcancel", "crsdr_plan_refcancel_buffers", "crsdr_refcancel",
 ]
+REFCANCEL_SINGULAR, REFCANCEL_IDLE = 1, 2                     # status bit 0: the solve failed (g = 0); 2: the pass did not run
+REFCANCEL_MAX_TAPS = 9
 ESPRIT_OFF, ESPRIT_BESIDE, ESPRIT_ONLY = 0, 1, 2
 ESPRIT_STATUS_ITERATIONS, ESPRIT_STATUS_PIVOT = 1, 2          # status bits 0 and 1
 ESPRIT_FLAG_BETA, ESPRIT_FLAG_ALPHA = 1, 2                    # flag bits 0 and 1: cos(beta), cos(alpha) clamped
@@ -228,6 +231,11 @@ def lib():
         L.crsdr_doa_augment_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.crsdr_augment_covariance.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int]
         L.crsdr_augment_lags.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, i32p, C.POINTER(C.c_int)]
+    if hasattr(L, "crsdr_plan_set_refcancel"):       # (likewise: an older build has no reference-noise canceller)
+        L.crsdr_plan_set_refcancel.argtypes = [vp, C.c_int]
+        L.crsdr_plan_fetch_refcancel.argtypes = [vp, C.c_int, f32p, f32p, i32p]
+        L.crsdr_plan_refcancel_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int)]
+        L.crsdr_refcancel.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_uint32, C.c_int]
     _lib = L
     return L
 
@@ -359,6 +367,31 @@ def covariance(matrix):
     out = np.empty((nrows - 1, nrows - 1), dtype=np.complex64)
     _check(lib().crsdr_covariance(_p(out.view(np.float32), C.c_float), _p(m, C.c_int8), nrows, B, MEM_HOST))
     return out
+
+
+def refcancel(rows, lag, phasor, taps, flags=0):
+    """crsdr_refcancel: the reference-noise canceller on one block rows [nrows][B] (int8, or uint8 with OFFSET_BINARY) with the lags
+    [nrows] and phasors [nrows] given.  Returns dict(out [nrows][B] int8, coef [nrows][taps] complex64, residual [nrows], status [nrows])."""
+    r = np.ascontiguousarray(rows)
+    if r.dtype not in (np.int8, np.uint8) or r.ndim != 2:
+        raise TypeError("rows must be int8 (or offset-binary uint8) [nrows][B]")
+    nrows, B = r.shape
+    lg = np.ascontiguousarray(lag, dtype=np.int32)
+    ph = np.ascontiguousarray(phasor, dtype=np.complex64)
+    if lg.shape != (nrows,) or ph.shape != (nrows,):
+        raise ValueError("lag and phasor must be [nrows]")
+    out = np.zeros((nrows, B), dtype=np.int8)
+    coef = np.zeros((nrows, max(int(taps), 1)), dtype=np.complex64)
+    res, st = np.zeros(nrows, dtype=np.float32), np.zeros(nrows, dtype=np.int32)
+    _check(lib().crsdr_refcancel(out.ctypes.data, coef.ctypes.data, res.ctypes.data, st.ctypes.data, r.ctypes.data, nrows, B, lg.ctypes.data,
+                                 ph.ctypes.data, int(taps), int(flags), MEM_HOST))
+    return dict(out=out, coef=coef, residual=res, status=st)
+
+
+def refcancel_device(out_ptr, coef_ptr, residual_ptr, status_ptr, rows_ptr, nrows, B, lag_ptr, phasor_ptr, taps, flags=0):
+    """Same on device memory (every pointer on the current device); returns after the kernels finished."""
+    _check(lib().crsdr_refcancel(int(out_ptr), int(coef_ptr), int(residual_ptr), int(status_ptr), int(rows_ptr), int(nrows), int(B), int(lag_ptr),
+                                 int(phasor_ptr), int(taps), int(flags), MEM_DEVICE))
 
 
 def covariance_device(rxx_ptr: int, matrix_ptr: int, nrows: int, B: int):
@@ -778,6 +811,25 @@ class Plan:
         ov = None if frac_override is None else np.ascontiguousarray(frac_override, dtype=np.float32)
         # enable: False / 0 off, True / 1 on, 2 on without the second work area (the pass repeats its first stage)
         _check(lib().crsdr_plan_set_frac_apply(self._h, int(enable), C.c_float(gain), _p(ov, C.c_float)))
+
+    def set_refcancel(self, taps):
+        """crsdr_plan_set_refcancel: the reference-noise canceller with `taps` taps (1, 3, 5, 7, 9); 0 / False turns it off."""
+        _check(lib().crsdr_plan_set_refcancel(self._h, int(taps)))
+        self.refcancel_taps = int(taps)
+
+    def fetch_refcancel(self, block=-1):
+        """crsdr_plan_fetch_refcancel: dict(coef [nrows][taps] complex64, residual [nrows], status [nrows]) of a block of the last batch."""
+        n, taps = self.nrows, max(getattr(self, "refcancel_taps", 0), 1)
+        coef = np.zeros((n, taps), dtype=np.complex64)
+        res, st = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.int32)
+        _check(lib().crsdr_plan_fetch_refcancel(self._h, int(block), _p(coef.view(np.float32), C.c_float), _p(res, C.c_float), _p(st, C.c_int32)))
+        return dict(coef=coef, residual=res, status=st)
+
+    def refcancel_buffers(self):
+        ptrs = [C.c_void_p() for _ in range(3)]
+        taps = C.c_int(0)
+        _check(lib().crsdr_plan_refcancel_buffers(self._h, *[C.byref(p) for p in ptrs], C.byref(taps)))
+        return dict(zip(("coef", "residual", "status"), [p.value for p in ptrs]), taps=taps.value)
 
     def bind_slab_ex(self, device_ptr: int | None, slab_stride: int = 0, hdr_first: int = 0, hdr_count: int = 0, tail_offset: int = 0):
         """crsdr_plan_bind_slab_ex: slab output with the per-row {lag, mag, frac, phasor} tail behind the rows of every slot."""

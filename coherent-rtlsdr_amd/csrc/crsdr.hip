@@ -11,6 +11,7 @@
 #include "spectrum.hpp"
 #include "refine.hpp"
 #include "esprit.hpp"
+#include "refcancel_solve.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -938,6 +939,15 @@ struct crsdr_plan {
     bool frac_generic = false;          // CRSDR_FRAC_GENERIC=1: B = 16384 takes the generic fractional-delay kernel too (A/B, tests)
     float2 *d_Z = nullptr;              // second work area (set_frac_apply): the correlation pass's stage B writes here, so that the apply pass finds stage A's output still in d_Y
     float4 *d_rowspec = nullptr;        // [row_count][8192] the rows' responses G(k2) in the junction's order (k_ramp_rowspec); allocated by set_frac_apply
+    // reference-noise canceller (crsdr_plan_set_refcancel; LDS-resident blocks, digital mode): everything below is allocated by the setter
+    int cancel_taps = 0;                // 0: off
+    float2 *d_cancel_coef = nullptr;    // [max_batch][nrows][9] g_j of the last batch, j ascending
+    float *d_cancel_res = nullptr;      // [max_batch][nrows]
+    int32_t *d_cancel_status = nullptr; // [max_batch][nrows]
+    int32_t *d_cancel_gram = nullptr;   // [max_batch][90] the blocks' integer Gram sums
+    rc::cd *d_cancel_chol = nullptr;    // [max_batch][45] their Cholesky factors
+    int32_t *d_cancel_bstat = nullptr;  // [max_batch] 0 or STATUS_SINGULAR per block
+    int cancel_idle = 0;                // leading blocks whose outputs hold the "pass did not run" values (status 2)
     // pinned staging ring for the small per-batch host arrays
     uint32_t *h_readcnt = nullptr;
     uint8_t *h_mask = nullptr;
@@ -1108,7 +1118,7 @@ static void plan_free(crsdr_plan *p)
     if (p->aux) (void)hipStreamSynchronize(p->aux);
     if (p->cs) { (void)hipStreamSynchronize(p->cs); (void)hipStreamDestroy(p->cs); }
     for (auto e : p->ev_copydone) if (e) (void)hipEventDestroy(e);
-    void *bufs[] = {p->d_Z, p->d_rowspec, p->d_frac_override, p->d_k2tab, p->d_wc, p->d_wf, p->d_tw1, p->d_Y, p->d_Yref, p->d_part, p->d_tw, p->d_twA, p->d_twB, p->d_refspec[0], p->d_refspec[1], p->d_rows, p->d_packet_alloc, p->d_readcnt,
+    void *bufs[] = {p->d_cancel_coef, p->d_cancel_res, p->d_cancel_status, p->d_cancel_gram, p->d_cancel_chol, p->d_cancel_bstat, p->d_Z, p->d_rowspec, p->d_frac_override, p->d_k2tab, p->d_wc, p->d_wf, p->d_tw1, p->d_Y, p->d_Yref, p->d_part, p->d_tw, p->d_twA, p->d_twB, p->d_refspec[0], p->d_refspec[1], p->d_rows, p->d_packet_alloc, p->d_readcnt,
                     p->d_mask, p->d_lag, p->d_mag, p->d_frac, p->d_phasor, p->d_corr, p->d_sync, p->d_state, p->d_state_snap, p->d_refflag};
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (p->h_k1flag) (void)hipHostFree(p->h_k1flag);
@@ -1274,6 +1284,8 @@ extern "C" int crsdr_plan_set_frac_apply(crsdr_plan *p, int enable, float gain, 
     }
     if (p->mode != CRSDR_MODE_DIGITAL)
         return fail(CRSDR_EINVAL, "plan_set_frac_apply: needs a plan in CRSDR_MODE_DIGITAL (the faithful mode never shifts samples)");
+    if (p->cancel_taps)
+        return fail(CRSDR_ESTATE, "plan_set_frac_apply: the reference-noise canceller is on (crsdr_plan_set_refcancel): the correction re-reads the raw row, the two do not compose");
     // |D| is bounded: the response's phase k_s D / B is formed in fp32 (cis2pi), whose argument loses 6e-8 of its size per ulp --
     // at |D| <= 64 samples the phase stays within 1e-5 rad.  A proper peak's parabolic estimate is |frac| <= 1/2, so D = gain * frac
     // needs |gain| <= 128; caller-supplied delays beyond the bound belong in the integer lag (the resampler servo's business).
@@ -1345,6 +1357,7 @@ struct Batch {
     bool vec16;                        // 16-byte accesses
     int chunks;                        // long rows: 16 KiB of the row per workgroup
     bool fused;                        // the fused phase path
+    bool cancel;                       // the reference-noise canceller writes this batch's rows (cancel_pass)
     bool kept_fwd;                     // long blocks: stage A's output survived the correlation pass (in d_Y; stage B wrote d_Z)
     bool corr_zeroed;                  // k_long_finalize zeroed the three-kernel path's integer sums
 };
@@ -1438,7 +1451,9 @@ static void setup_outputs(crsdr_plan *p, Batch &b, uint32_t seq, uint32_t flags)
               (p->packet_stride % 16 == 0 || b.nblocks == 1) &&
               (!p->d_slab || ((uintptr_t)p->d_slab % 16 == 0 && p->slab_stride % 16 == 0));
     b.chunks = p->B > 16384 ? p->B / 16384 : 1;
-    b.fused = p->fused_k2 && b.vec16 && b.chunks == 1;
+    b.cancel = p->cancel_taps && aa.refnoise && aa.digital;
+    // (the canceller writes the owned rows itself, behind the three-kernel path's estimate)
+    b.fused = p->fused_k2 && b.vec16 && b.chunks == 1 && !b.cancel;
 }
 
 // K0 on the aux stream into reference-spectrum slot `slot`, then the main stream's wait for it.  K0 goes behind the main
@@ -1597,6 +1612,7 @@ static int k1_short(crsdr_plan *p, Batch &b)
 // they first name their kernels (fused phase kernel, fractional-delay kernels, three-kernel path, long-block apply pass): that order
 // is the order of the kernels in the code object.
 static int frac_pass(crsdr_plan *p, const Batch &b);
+static int cancel_pass(crsdr_plan *p, const Batch &b);      // the reference-noise canceller: section (v) at the end of this file
 
 // Fused phase path: every row is read once (k_align_fused); timed under CRSDR_KERNEL_ALIGN_QUANT
 static int phase_fused(crsdr_plan *p, const Batch &b)
@@ -1632,6 +1648,7 @@ static int phase_fused(crsdr_plan *p, const Batch &b)
     else hipLaunchKernelGGL((k_align_fused<false, true>), grid, dim3(kAlignThreads), 0, S, b.aa, fs);
     HIP_TRY(hipGetLastError());
     { int rc = frac_pass(p, b); if (rc) return rc; }
+    { int rc = cancel_pass(p, b); if (rc) return rc; }
     if (pe) HIP_TRY(hipEventRecord(pe[1], S));
     return CRSDR_OK;
 }
@@ -1675,12 +1692,14 @@ static int phase_three(crsdr_plan *p, Batch &b)
     }
     hipEvent_t *pe = prof_pair(p, CRSDR_KERNEL_ALIGN_QUANT);
     if (pe) HIP_TRY(hipEventRecord(pe[0], S));
-    // with the fractional-delay correction on, the rows come from the apply pass (frac_pass): here only header + readcnt + row 0
-    const unsigned gx = apply ? 1u : 1u + (unsigned)p->row_count;
+    // with the fractional-delay correction on, the rows come from the apply pass (frac_pass), with the reference-noise canceller from
+    // cancel_pass: here only header + readcnt + row 0
+    const unsigned gx = (apply || b.cancel) ? 1u : 1u + (unsigned)p->row_count;
     if (b.vec16) hipLaunchKernelGGL(k_align_quant<true>, dim3(gx, nblocks, chunks), dim3(kAlignThreads), 0, S, aa);
     else hipLaunchKernelGGL(k_align_quant<false>, dim3(gx, nblocks, chunks), dim3(kAlignThreads), 0, S, aa);
     HIP_TRY(hipGetLastError());
     { int rc = frac_pass(p, b); if (rc) return rc; }
+    { int rc = cancel_pass(p, b); if (rc) return rc; }
     if (pe) HIP_TRY(hipEventRecord(pe[1], S));
     return CRSDR_OK;
 }
@@ -2170,5 +2189,178 @@ extern "C" int crsdr_augment_covariance(float *ra, const float *rxx, int mx, int
     hipLaunchKernelGGL(augment::k_augment_covariance<augment::AG_THREADS>, dim3(1), dim3(augment::AG_THREADS), 0, 0, d_r, mx, my, vx, vy, augment_mask((int)m, mask), d_a);
     HIP_TRY(hipGetLastError());
     st.back(ra, d_a, vb);
+    return st.finish();
+}
+
+// ================================================================================================
+// (v) reference-noise canceller (crsdr_plan_set_refcancel, crsdr_refcancel)
+// ================================================================================================
+// Its kernels are named here for the first time, behind everything else: the existing kernels keep their places in the code object.
+#include "refcancel.hpp"
+
+// Reference-noise canceller (crsdr_plan_set_refcancel), behind the three-kernel phase path and inside its CRSDR_KERNEL_ALIGN_QUANT
+// event pair: the blocks' Gram sums and factors, the rows' sums and coefficients, the rows themselves (refcancel.hpp).  A batch
+// submitted without CRSDR_REFNOISE_ENABLED keeps its phase path; its blocks' outputs are marked "did not run" once.
+static rc::CancelArgs cancel_args(const crsdr_plan *p, const Batch &b)
+{
+    rc::CancelArgs ca{};
+    ca.rows = b.d_in; ca.block_stride = b.d_stride;
+    if (p->d_slab) { ca.orows = p->d_slab; ca.orows_stride = p->slab_stride; ca.orow_first = p->row_begin; }
+    else { ca.orows = p->d_packet + p->matrix_off; ca.orows_stride = p->packet_stride; ca.orow_first = 0; }
+    ca.lag = b.o_lag; ca.phasor = p->d_phasor;
+    ca.coef = p->d_cancel_coef; ca.coef_pitch = rc::MAX_TAPS; ca.residual = p->d_cancel_res; ca.status = p->d_cancel_status;
+    ca.gram = p->d_cancel_gram; ca.chol = p->d_cancel_chol; ca.block_status = p->d_cancel_bstat;
+    ca.nrows = p->nrows; ca.B = p->B; ca.row_begin = p->row_begin; ca.taps = p->cancel_taps; ca.xor80 = b.xor80;
+    return ca;
+}
+
+static int cancel_pass(crsdr_plan *p, const Batch &b)
+{
+    if (!p->cancel_taps) return CRSDR_OK;
+    const rc::CancelArgs ca = cancel_args(p, b);
+    if (!b.cancel) {
+        if (p->cancel_idle >= b.nblocks) return CRSDR_OK;
+        hipLaunchKernelGGL(rc::k_refcancel_idle, dim3((unsigned)((p->row_count + 255) / 256), (unsigned)b.nblocks), dim3(256), 0, p->stream, ca, p->row_count);
+        HIP_TRY(hipGetLastError());
+        p->cancel_idle = std::max(p->cancel_idle, b.nblocks);
+        return CRSDR_OK;
+    }
+    p->cancel_idle = 0;
+    // (the lags come from this batch's {lag, mag, frac} buffer: k_phase_chain has republished the carried ones for a batch without K1)
+    HIP_TRY(rc::launch_refcancel(p->stream, ca, p->row_count, b.nblocks, b.vec16));
+    return CRSDR_OK;
+}
+
+// ---- reference-noise canceller: setter, fetch, device buffers, the per-op form (kernels: refcancel.hpp; dispatch: cancel_pass) ----
+static void cancel_free(crsdr_plan *p)
+{
+    void **bufs[] = {(void **)&p->d_cancel_coef, (void **)&p->d_cancel_res, (void **)&p->d_cancel_status, (void **)&p->d_cancel_gram, (void **)&p->d_cancel_chol,
+                     (void **)&p->d_cancel_bstat};
+    for (void **b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+    p->cancel_taps = 0; p->cancel_idle = 0;
+}
+
+static bool refcancel_taps_ok(int taps) { return taps >= 1 && taps <= rc::MAX_TAPS && (taps & 1); }
+
+extern "C" int crsdr_plan_set_refcancel(crsdr_plan *p, int taps)
+{
+    if (!p) return fail(CRSDR_EINVAL, "plan_set_refcancel: NULL plan");
+    if (taps != 0 && !refcancel_taps_ok(taps)) return fail(CRSDR_EINVAL, "plan_set_refcancel: taps = %d (0 off; 1, 3, 5, 7 or 9)", taps);
+    if (taps == 0) {
+        if (p->d_cancel_coef) {
+            HIP_TRY(hipSetDevice(p->device));
+            int rc = crsdr_plan_sync(p);
+            if (rc) return rc;
+            cancel_free(p);
+        }
+        p->cancel_taps = 0;
+        return CRSDR_OK;
+    }
+    if (p->mode != CRSDR_MODE_DIGITAL)
+        return fail(CRSDR_EINVAL, "plan_set_refcancel: needs a plan in CRSDR_MODE_DIGITAL (the canceller acts on the shifted row)");
+    if (p->longblock) return fail(CRSDR_EINVAL, "plan_set_refcancel: blocksize = %d (the canceller takes blocks up to 16384)", p->B);
+    if (p->frac_apply)
+        return fail(CRSDR_ESTATE, "plan_set_refcancel: the fractional-delay correction is on (crsdr_plan_set_frac_apply): it re-reads the raw row, the two do not compose");
+    HIP_TRY(hipSetDevice(p->device));
+    { int rc = crsdr_plan_sync(p); if (rc) return rc; }
+    const size_t n = (size_t)p->nrows, T = (size_t)p->max_batch;
+    if (!p->d_cancel_coef) {
+        const hipError_t e[] = {hipMalloc((void **)&p->d_cancel_coef, sizeof(float2) * rc::MAX_TAPS * n * T), hipMalloc((void **)&p->d_cancel_res, sizeof(float) * n * T),
+                                hipMalloc((void **)&p->d_cancel_status, sizeof(int32_t) * n * T), hipMalloc((void **)&p->d_cancel_gram, sizeof(int32_t) * rc::GRAM_INTS * T),
+                                hipMalloc((void **)&p->d_cancel_chol, sizeof(rc::cd) * rc::GRAM_PAIRS * T), hipMalloc((void **)&p->d_cancel_bstat, sizeof(int32_t) * T)};
+        for (hipError_t x : e)
+            if (x != hipSuccess) { cancel_free(p); (void)hipGetLastError(); return fail(CRSDR_ENOMEM, "plan_set_refcancel: %s", hipGetErrorString(x)); }
+    }
+    // rows outside the slab and row 0 hold zeros, and so do the coefficients beyond the tap count
+    HIP_TRY(hipMemset(p->d_cancel_coef, 0, sizeof(float2) * rc::MAX_TAPS * n * T));
+    HIP_TRY(hipMemset(p->d_cancel_res, 0, sizeof(float) * n * T));
+    HIP_TRY(hipMemset(p->d_cancel_status, 0, sizeof(int32_t) * n * T));
+    HIP_TRY(hipMemset(p->d_cancel_gram, 0, sizeof(int32_t) * rc::GRAM_INTS * T));
+    HIP_TRY(hipMemset(p->d_cancel_chol, 0, sizeof(rc::cd) * rc::GRAM_PAIRS * T));
+    HIP_TRY(hipMemset(p->d_cancel_bstat, 0, sizeof(int32_t) * T));
+    HIP_TRY(hipDeviceSynchronize());        // the plan's streams are non-blocking: no implicit order with the null stream
+    p->cancel_taps = taps; p->cancel_idle = 0;
+    return CRSDR_OK;
+}
+
+static int check_fused_status(crsdr_plan *p);
+extern "C" int crsdr_plan_fetch_refcancel(crsdr_plan *p, int block, float *coef, float *residual, int32_t *status)
+{
+    if (!p) return fail(CRSDR_EINVAL, "plan_fetch_refcancel: NULL plan");
+    if (!p->cancel_taps) return fail(CRSDR_ESTATE, "plan_fetch_refcancel: the canceller is off (crsdr_plan_set_refcancel)");
+    if (!p->submitted) return fail(CRSDR_ESTATE, "plan_fetch_refcancel: nothing submitted");
+    if (block < 0) block = p->last_nblocks - 1;
+    if (block >= p->last_nblocks) return fail(CRSDR_EINVAL, "plan_fetch_refcancel: block %d of a batch of %d", block, p->last_nblocks);
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    { int rc_ = check_fused_status(p); if (rc_) return rc_; }
+    const size_t n = (size_t)p->nrows, o = (size_t)block * n;
+    if (coef) {
+        std::vector<float2> all(n * rc::MAX_TAPS);
+        HIP_TRY(hipMemcpy(all.data(), p->d_cancel_coef + o * rc::MAX_TAPS, sizeof(float2) * all.size(), hipMemcpyDeviceToHost));
+        for (size_t r = 0; r < n; ++r) memcpy(coef + 2 * r * (size_t)p->cancel_taps, &all[r * rc::MAX_TAPS], sizeof(float2) * (size_t)p->cancel_taps);
+    }
+    if (residual) HIP_TRY(hipMemcpy(residual, p->d_cancel_res + o, sizeof(float) * n, hipMemcpyDeviceToHost));
+    if (status) HIP_TRY(hipMemcpy(status, p->d_cancel_status + o, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_plan_refcancel_buffers(crsdr_plan *p, void **coef, void **residual, void **status, int *taps)
+{
+    if (!p) return fail(CRSDR_EINVAL, "plan_refcancel_buffers: NULL plan");
+    if (!p->cancel_taps) return fail(CRSDR_ESTATE, "plan_refcancel_buffers: the canceller is off (crsdr_plan_set_refcancel)");
+    if (coef) *coef = p->d_cancel_coef;
+    if (residual) *residual = p->d_cancel_res;
+    if (status) *status = p->d_cancel_status;
+    if (taps) *taps = p->cancel_taps;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_refcancel(int8_t *out, float *coef, float *residual, int32_t *status, const int8_t *rows, int nrows, int blocksize, const int32_t *lag,
+                               const float *phasor, int taps, uint32_t flags, int mem_kind)
+{
+    if (!out || !coef || !residual || !status || !rows || !lag || !phasor || (const int8_t *)out == rows)
+        return fail(CRSDR_EINVAL, "refcancel: need out, coef, residual, status, rows, lag and phasor (out apart from rows)");
+    const int l2 = ilog2_exact(blocksize);
+    if (nrows < 2 || l2 < kMinLog2 || l2 > kMaxLog2) return fail(CRSDR_EINVAL, "refcancel: nrows = %d, blocksize = %d (nrows >= 2, a power of two in [16, 16384])", nrows, blocksize);
+    if (!refcancel_taps_ok(taps)) return fail(CRSDR_EINVAL, "refcancel: taps = %d (1, 3, 5, 7 or 9)", taps);
+    if (flags & ~(uint32_t)CRSDR_OFFSET_BINARY) return fail(CRSDR_EINVAL, "refcancel: flags = 0x%x (CRSDR_OFFSET_BINARY or 0)", flags);
+    const int L = blocksize / 2;
+    if (mem_kind == CRSDR_MEM_HOST)
+        for (int r = 1; r < nrows; ++r)
+            if (lag[r] < -L || lag[r] > L) return fail(CRSDR_EINVAL, "refcancel: lag[%d] = %d (|lag| <= %d)", r, lag[r], L);
+    if (mem_kind == CRSDR_MEM_DEVICE && ((uintptr_t)out % 4 || (uintptr_t)rows % 4 || (uintptr_t)coef % 8 || (uintptr_t)phasor % 8 || (uintptr_t)lag % 4 ||
+                                         (uintptr_t)residual % 4 || (uintptr_t)status % 4))
+        return fail(CRSDR_EINVAL, "refcancel: device rows and out 4-byte aligned (16-byte for the vector kernels), coef and phasor 8-byte");
+    OP_PROLOGUE_MEM("refcancel", mem_kind);
+    const size_t n = (size_t)nrows, mb = n * (size_t)blocksize;
+    OpStage st(mem_kind);
+    rc::CancelArgs ca{};
+    ca.rows = (const int8_t *)st.in(0, rows, mb);
+    ca.orows = (int8_t *)st.out(1, out, mb);
+    ca.lag = (const int32_t *)st.in(2, lag, sizeof(int32_t) * n);
+    ca.phasor = (const float2 *)st.in(3, phasor, sizeof(float2) * n);
+    ca.coef = (float2 *)st.out(4, coef, sizeof(float2) * n * (size_t)taps);
+    ca.residual = (float *)st.out(5, residual, sizeof(float) * n);
+    ca.status = (int32_t *)st.out(6, status, sizeof(int32_t) * n);
+    if (st.rc) return st.rc;
+    OP_RESERVE(7, sizeof(int32_t) * rc::GRAM_INTS + sizeof(rc::cd) * rc::GRAM_PAIRS + 16);
+    ca.chol = (rc::cd *)g_op.buf[7];
+    ca.gram = (int32_t *)(ca.chol + rc::GRAM_PAIRS);
+    ca.block_status = ca.gram + rc::GRAM_INTS;
+    ca.block_stride = mb; ca.orows_stride = mb; ca.orow_first = 0; ca.coef_pitch = taps;
+    ca.nrows = nrows; ca.B = blocksize; ca.row_begin = 1; ca.taps = taps; ca.xor80 = (flags & CRSDR_OFFSET_BINARY) ? 0x80808080u : 0u;
+    // row 0 holds zeros in the three per-row outputs
+    HIP_TRY(hipMemsetAsync(ca.coef, 0, sizeof(float2) * (size_t)taps, 0));
+    HIP_TRY(hipMemsetAsync(ca.residual, 0, sizeof(float), 0));
+    HIP_TRY(hipMemsetAsync(ca.status, 0, sizeof(int32_t), 0));
+    hipLaunchKernelGGL(rc::k_refcancel_row0, grid1d((size_t)blocksize / 4), dim3(256), 0, 0, (uint32_t *)ca.orows, (const uint32_t *)ca.rows, blocksize / 4, ca.xor80);
+    HIP_TRY(hipGetLastError());
+    const bool vec = (uintptr_t)ca.rows % 16 == 0 && (uintptr_t)ca.orows % 16 == 0;
+    HIP_TRY(rc::launch_refcancel(0, ca, nrows - 1, 1, vec));
+    st.back(out, ca.orows, mb);
+    st.back(coef, ca.coef, sizeof(float2) * n * (size_t)taps);
+    st.back(residual, ca.residual, sizeof(float) * n);
+    st.back(status, ca.status, sizeof(int32_t) * n);
     return st.finish();
 }

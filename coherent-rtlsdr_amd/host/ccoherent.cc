@@ -217,6 +217,8 @@ bool ccoherent::collect_batch(int slot)
 }
 
 void ccoherent::clearlagqueue() { lagqueue.clear(); }
+int ccoherent::set_refcancel(int taps) { return plan ? crsdr_plan_set_refcancel(plan, taps) : CRSDR_ESTATE; }
+
 size_t ccoherent::lagqueuesize() { return lagqueue.size(); }
 void ccoherent::queuelag(csdrdevice *d) { lagqueue.push_back(d); }   // src/ccoherent.cc:123-142 (no copy, no cap)
 

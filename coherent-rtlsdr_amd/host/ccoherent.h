@@ -72,6 +72,10 @@ public:
     bool ok() const { return plan != nullptr; }
     crsdr_plan *engine_plan() const { return plan; }       // for consumers of the device-resident packets (cbeamformer::batch)
     bool sharded() const { return xchg != nullptr; }
+    // the plan's reference-noise canceller (crsdr_plan_set_refcancel): taps = 1, 3, 5, 7, 9, or 0 for off; the CRSDR_* code.  With it on,
+    // blocks made while the noise source is enabled carry rows with the noise projected out: the enable / disable dance of the
+    // console (crefnoise) becomes optional
+    int set_refcancel(int taps);
     int batch_rooted_first(int slot) const { return brooted_first[slot]; }     // sharded: the blocks of the slot's batch this rank assembled
     int batch_rooted_count(int slot) const { return brooted_count[slot]; }
     ~ccoherent();

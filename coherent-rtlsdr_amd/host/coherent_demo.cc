@@ -59,7 +59,7 @@ int main(int argc, char **argv)
     float beam_loading = 1e-2f;
     int smooth_x = 0, smooth_y = 0, order_crit = CRSDR_ORDER_OFF, spectrum_kind = CRSDR_SPECTRUM_MUSIC, refine_levels = 0, esprit_mode = CRSDR_ESPRIT_OFF;
     bool smooth_fb = false;
-    int augment_x = 0, augment_y = 0;
+    int augment_x = 0, augment_y = 0, refcancel = 0;
     std::string augment_mask;
     int sb_nfft = 0, sb_first = 0, sb_count = 1, sb_width = 1, sb_window = CRSDR_WINDOW_RECT;
     bool engine_batches = false;
@@ -89,6 +89,9 @@ int main(int argc, char **argv)
         else if (a == "--fs") val(table_fs);
         else if (a == "--bench") bench = true;      // pipelined batched engine over PCIe: blocks/s from C++, no Python in the loop
         else if (a == "--batch") val(batch);
+        // with --bench: the reference-noise canceller with TAPS taps (crsdr_plan_set_refcancel); prints the mean residual share of every
+        // timed batch in dB (read behind the batch's submit: that read waits for the batch, so the run is no longer fully pipelined)
+        else if (a == "--refcancel") val(refcancel);
         else if (a == "--peaks") val(peaks);                   // with --bench --music: that many directions per estimate (crsdr_doa_set_peaks)
         else if (a == "--peak-radius") val(peak_radius);
         // with --bench --music: a beam toward every direction (crsdr_doa_set_beams), its power printed beside the direction
@@ -335,6 +338,18 @@ int main(int argc, char **argv)
         const int nb = std::max(3, blocks / batch);
         const uint32_t fl = CRSDR_REFNOISE_ENABLED;
         bool ok = true;
+        if (refcancel && coherent.set_refcancel(refcancel)) { std::printf("bench: --refcancel %d refused: %s\nDEMO FAILED\n", refcancel, crsdr_last_error()); return 1; }
+        bool residuals = false;
+        auto residual = [&](int b) {
+            if (!refcancel || !residuals || !ok) return;
+            std::vector<float> res((size_t)(1 + nsig));
+            double sum = 0.0;
+            for (int t = 0; t < batch; ++t) {
+                if (crsdr_plan_fetch_refcancel(coherent.engine_plan(), t, nullptr, res.data(), nullptr) != CRSDR_OK) { ok = false; return; }
+                for (int k = 1; k <= nsig; ++k) sum += res[(size_t)k];
+            }
+            std::printf("refcancel: batch %d: %d taps, mean residual %.2f dB\n", b, refcancel, 10.0 * std::log10(sum / ((double)batch * nsig)));
+        };
         // --bench --music: a direction per block from the packets where the plan left them (cbeamformer::batch over crsdr_doa), enqueued
         // behind every batch on the plan's stream; the peaks are the only thing fetched.  The synthetic channels all carry the reference
         // noise: once aligned, one source at broadside, grid point (50, 50).
@@ -457,15 +472,18 @@ int main(int argc, char **argv)
         auto run = [&](int n) {
             ok = ok && coherent.submit_batch(0, batch, fl);
             directions(0);
+            residual(0);
             for (int b = 1; b < n && ok; ++b) {
                 ok = ok && coherent.submit_batch(b & 1, batch, fl);       // upload of batch b overlaps the download of batch b - 1
                 directions(b);
+                residual(b);
                 ok = ok && coherent.collect_batch((b - 1) & 1);
             }
             ok = ok && coherent.collect_batch((n - 1) & 1);
         };
         run(3);                                                           // warm-up: allocations, code objects, link
         report = true;
+        residuals = true;
         const auto t0 = std::chrono::steady_clock::now();
         run(nb);
         const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

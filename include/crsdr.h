@@ -226,6 +226,50 @@ int crsdr_plan_fetch_block(crsdr_plan *plan, int block, int32_t *lag, float *mag
  *   enable = 0: off; both buffers are freed (after a sync). */
 int crsdr_plan_set_frac_apply(crsdr_plan *plan, int enable, float gain, const float *frac_override);
 
+/* Reference-noise canceller.  The reference switches its noise source on to calibrate and off to measure (src/ccoherent.cc:271, the
+ * crefnoise gate; CRSDR_REFNOISE_ENABLED here): with the source on every signal row carries the noise far above any emitter.  With
+ * the canceller on, the owned signal rows of blocks submitted with CRSDR_REFNOISE_ENABLED have the reference row projected out by a
+ * short least-squares FIR before they are rotated and quantised, so that a host may calibrate and measure on the same block.
+ * CRSDR_MODE_DIGITAL plans with blocksize <= 16384; taps = 2 K + 1 odd in 1 .. 9; off by default.  A batch submitted without the
+ * flag does not run the pass: its packets have the bits of a plan with the canceller off, status is 2 for every owned row, the
+ * coefficients are 0 (and the residual 1).  No state is carried from block to block.
+ * Per owned row and block, L = blocksize / 2, all values signed int8 counts (offset-binary input is ^ 0x80 first):
+ *   1. y[n] = s[n + d] for 0 <= n + d < L, zero elsewhere; d the lag the digital mode shifts the row by: the row the phase path uses.
+ *   2. r_j[n] = r[n - j] for 0 <= n - j < L, zero elsewhere, j = -K .. K; r the block's reference row.
+ *   3. exact integer sums  c_j = sum_n y[n] conj(r_j[n]),  G_ij = sum_n conj(r_i[n]) r_j[n]  (the full Hermitian Gram with the
+ *      zero-filled edges, not its Toeplitz approximation),  E = sum_n |y[n]|^2.  c_0 is the sum the phasor is formed from: the phase
+ *      estimate, the EMA chain and the outputs lag / mag / frac / phasor keep their bits.
+ *   4. G g = c solved in fp64 by Cholesky (operation order not pinned).  A pivot <= 2^-40 G_00 (G_00 the centre entry sum |r|^2) is a
+ *      failure -- an all-zero or rank-deficient reference row: g = 0 and status bit 0 is set.  g is published rounded once to fp32,
+ *      j ascending.  residual = clamp((E - Re sum_j conj(g_j) c_j) / E, 0, 1), formed in fp64 with the unrounded g and rounded once;
+ *      1 if E == 0: the share of the row's power that stays.
+ *   5. z[n] = y[n] - sum_j g_j r_j[n];  w = p z, p the block's phasor as published;  out = clip(rint(w), -128, 127), ties to even,
+ *      I and Q each.  The published g and p are used in fp32 arithmetic whose order is not pinned; there is no 1/127 round trip.  With
+ *      g = 0 this is the plain rotation; it is not promised to match the phase path's bits on ties.  The row lands where the phase
+ *      path would have put it (packet matrix, bound packet or bound slab); header, read counters and row 0 are untouched.
+ * crsdr_plan_set_refcancel: taps = 0 turns it off and frees what the call allocated (after a sync); 1, 3, 5, 7, 9 turn it on and
+ *   allocate everything here ([max_batch][nrows][9][2] fp32 coefficients, [max_batch][nrows] residual and status, the blocks' Grams):
+ *   nothing is allocated per submit.  CRSDR_EINVAL for another count, a CRSDR_MODE_FAITHFUL plan or blocksize > 16384; CRSDR_ESTATE
+ *   while crsdr_plan_set_frac_apply is on, and that call answers CRSDR_ESTATE while this is on (its pass re-reads the raw row: the two
+ *   do not compose).  A batch that runs the pass takes the three-kernel phase path in front of it.
+ * crsdr_plan_fetch_refcancel: waits and reports kernel-side errors as crsdr_plan_fetch_block does; block -1 = the last block.  coef
+ *   [nrows][taps][2], residual [nrows], status [nrows] (any may be NULL); rows outside the slab and row 0 hold zeros.
+ * crsdr_plan_refcancel_buffers: the device arrays for consumers on the plan's stream -- coef [max_batch][nrows][9][2] (a row's taps
+ *   first, zeros behind), residual and status [max_batch][nrows] -- and the tap count.  CRSDR_ESTATE while off. */
+int crsdr_plan_set_refcancel(crsdr_plan *plan, int taps);
+int crsdr_plan_fetch_refcancel(crsdr_plan *plan, int block, float *coef /* [nrows][taps][2] */, float *residual /* [nrows] */,
+                               int32_t *status /* [nrows] */);
+int crsdr_plan_refcancel_buffers(crsdr_plan *plan, void **coef, void **residual, void **status, int *taps);
+
+/* The per-op form: one block with the lags and phasors given, the same device functions, bit for bit.  rows [nrows][blocksize] (row 0
+ * the reference), lag [nrows], phasor [nrows][2] (entry 0 of both ignored) -> out [nrows][blocksize] (row 0 copied, as two's
+ * complement), coef [nrows][taps][2], residual [nrows], status [nrows] (row 0: zeros).  blocksize a power of two in 16 .. 16384, taps
+ * as above, |lag| <= blocksize / 2 (lag = -L or L: the all-zero row), flags CRSDR_OFFSET_BINARY or 0, out apart from rows.  Every
+ * argument is checked before a device is touched (a lag in device memory is clamped to the range instead).  mem_kind: CRSDR_MEM_HOST
+ * (copied) or CRSDR_MEM_DEVICE (all on the device: rows and out 4-byte aligned, 16-byte for the vector kernels; coef and phasor 8-byte). */
+int crsdr_refcancel(int8_t *out, float *coef, float *residual, int32_t *status, const int8_t *rows, int nrows, int blocksize,
+                    const int32_t *lag, const float *phasor, int taps, uint32_t flags, int mem_kind);
+
 /* Pipelined fetch of the LAST submitted batch into page-locked host memory (crsdr_host_alloc): the device-to-host copies
  * run on the plan's copy stream as soon as the batch's kernels have finished -- while the NEXT submit's host-to-device copies
  * use the other direction of the link; the next submit's kernels wait on the device for these copies, so the plan's output
