@@ -47,6 +47,8 @@ ABI_SYMBOLS = [
     "crsdr_doa_set_esprit", "crsdr_doa_fetch_esprit", "crsdr_doa_esprit_buffers", "crsdr_esprit2d",
     "crsdr_doa_set_augment", "crsdr_doa_fetch_augmented", "crsdr_doa_augment_buffers", "crsdr_augment_covariance", "crsdr_augment_lags",
     "crsdr_plan_set_refcancel", "crsdr_plan_fetch_refcancel", "crsdr_plan_refcancel_buffers", "crsdr_refcancel",
+    "crsdr_spectra_create", "crsdr_spectra_destroy", "crsdr_spectra_submit", "crsdr_spectra_submit_plan", "crsdr_spectra_fetch",
+    "crsdr_spectra_device_buffers", "crsdr_spectra_last_submit", "crsdr_welch",
 ]
 REFCANCEL_SINGULAR, REFCANCEL_IDLE = 1, 2                     # status bit 0: the solve failed (g = 0); 2: the pass did not run
 REFCANCEL_MAX_TAPS = 9
@@ -96,6 +98,11 @@ class DoaDesc(C.Structure):
     _fields_ = [("nrows", C.c_int32), ("blocksize", C.c_int32), ("device", C.c_int32), ("max_batch", C.c_int32), ("frames", C.c_int32),
                 ("k", C.c_int32), ("mx", C.c_int32), ("my", C.c_int32), ("ncx", C.c_int32), ("ncy", C.c_int32), ("d", C.c_float),
                 ("flags", C.c_uint32)]
+
+
+class SpectraDesc(C.Structure):
+    _fields_ = [("nrows", C.c_int32), ("blocksize", C.c_int32), ("device", C.c_int32), ("max_batch", C.c_int32), ("frames", C.c_int32),
+                ("nfft", C.c_int32), ("overlap", C.c_int32), ("window", C.c_int32), ("band_lo", C.c_int32), ("band_hi", C.c_int32)]
 
 
 _lib = None
@@ -236,6 +243,15 @@ def lib():
         L.crsdr_plan_fetch_refcancel.argtypes = [vp, C.c_int, f32p, f32p, i32p]
         L.crsdr_plan_refcancel_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int)]
         L.crsdr_refcancel.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_uint32, C.c_int]
+    if hasattr(L, "crsdr_spectra_create"):           # (likewise: an older build has no spectra)
+        L.crsdr_spectra_create.argtypes = [C.POINTER(vp), C.POINTER(SpectraDesc)]
+        L.crsdr_spectra_destroy.argtypes = [vp]
+        L.crsdr_spectra_submit.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp]
+        L.crsdr_spectra_submit_plan.argtypes = [vp, vp]
+        L.crsdr_spectra_fetch.argtypes = [vp, f32p, f32p, f32p]
+        L.crsdr_spectra_device_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        L.crsdr_spectra_last_submit.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.crsdr_welch.argtypes = [f32p, f32p, f32p, i8p] + [C.c_int] * 8
     _lib = L
     return L
 
@@ -578,6 +594,27 @@ def subband_covariance_device(rbands_ptr: int, power_ptr: int, matrix_ptr: int, 
     cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
     _check(lib().crsdr_subband_covariance(cast(rbands_ptr, C.c_float), cast(power_ptr, C.c_float), cast(matrix_ptr, C.c_int8), int(nrows), int(B),
                                           int(nfft), int(first), int(nbands), int(width), int(window), MEM_DEVICE))
+
+
+def welch(matrix, nfft, overlap=0, window=WINDOW_RECT, band=None):
+    """crsdr_welch: (psd [nrows][nfft] float32, cross [nrows][nfft] complex64, align [nrows][4] float32 = delay, phase, gain, coherence)
+    of one packet's int8 matrix [nrows][B], row 0 included; band = (lo, hi) signed bins of the alignment figures (default +-nfft/4).
+    The batched engine (Spectra) on one line of one packet, bit for bit."""
+    m = np.ascontiguousarray(matrix, dtype=np.int8)
+    nrows, B = m.shape
+    lo, hi = band if band is not None else (-(int(nfft) // 4), int(nfft) // 4)
+    n = max(int(nfft), 0)
+    psd, cross, al = np.empty((nrows, n), dtype=np.float32), np.empty((nrows, n), dtype=np.complex64), np.empty((nrows, 4), dtype=np.float32)
+    _check(lib().crsdr_welch(_p(psd, C.c_float), _p(cross.view(np.float32), C.c_float), _p(al, C.c_float), _p(m, C.c_int8), nrows, B, int(nfft), int(overlap),
+                             int(window), int(lo), int(hi), MEM_HOST))
+    return psd, cross, al
+
+
+def welch_device(psd_ptr: int, cross_ptr: int, align_ptr: int, matrix_ptr: int, nrows, B, nfft, overlap, window, band_lo, band_hi):
+    """Same on device memory (any output pointer, not all, may be 0); returns after the kernels finished."""
+    cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
+    _check(lib().crsdr_welch(cast(psd_ptr, C.c_float), cast(cross_ptr, C.c_float), cast(align_ptr, C.c_float), cast(matrix_ptr, C.c_int8), int(nrows), int(B),
+                             int(nfft), int(overlap), int(window), int(band_lo), int(band_hi), MEM_DEVICE))
 
 
 def subband_beamform(matrix, weights, nfft, first=0, nbands=1, width=1, window=WINDOW_RECT):
@@ -1147,6 +1184,62 @@ class Doa:
     def close(self):
         if self._h:
             lib().crsdr_doa_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Spectra:
+    """crsdr_spectra: per line of `frames` consecutive device-resident packets the Welch auto-spectrum of every row, every row's
+    cross-spectrum against row 0 and four alignment figures per row.  submit* only enqueue; fetch() waits and returns numpy arrays."""
+
+    def __init__(self, nrows, blocksize, nfft, overlap=0, window=WINDOW_RECT, band=None, max_batch=1, frames=1, device=0):
+        lo, hi = band if band is not None else (-(int(nfft) // 4), int(nfft) // 4)
+        desc = SpectraDesc(int(nrows), int(blocksize), int(device), int(max_batch), int(frames), int(nfft), int(overlap), int(window), int(lo), int(hi))
+        h = C.c_void_p()
+        _check(lib().crsdr_spectra_create(C.byref(h), C.byref(desc)))
+        self._h = h
+        self.nrows, self.B, self.nfft, self.overlap, self.window, self.band = int(nrows), int(blocksize), int(nfft), int(overlap), int(window), (int(lo), int(hi))
+        self.max_batch, self.frames = max(1, int(max_batch)), max(1, int(frames))
+
+    def _last(self):
+        nest, launches = C.c_int(0), C.c_int(0)
+        _check(lib().crsdr_spectra_last_submit(self._h, C.byref(nest), C.byref(launches)))
+        return nest.value, launches.value
+
+    def submit(self, packets_ptr: int, packet_stride: int, matrix_offset: int, nblocks: int, stream: int | None = None):
+        """nblocks packets on the device: packet t at packets_ptr + t * packet_stride, its matrix at + matrix_offset."""
+        _check(lib().crsdr_spectra_submit(self._h, C.c_void_p(int(packets_ptr)), int(packet_stride), int(matrix_offset), int(nblocks),
+                                          C.c_void_p(stream or 0)))
+
+    def submit_plan(self, plan: "Plan"):
+        """The plan's last submitted batch, where its packets are, on the plan's stream."""
+        _check(lib().crsdr_spectra_submit_plan(self._h, plan._h))
+
+    def fetch(self, psd=True, cross=True, align=True) -> dict:
+        """Waits for the last submit.  psd [nest][nrows][nfft], cross [nest][nrows][nfft] complex64, align [nest][nrows][4]."""
+        n = self._last()[0]
+        p = np.zeros((n, self.nrows, self.nfft), dtype=np.float32) if psd else None
+        c = np.zeros((n, self.nrows, self.nfft), dtype=np.complex64) if cross else None
+        a = np.zeros((n, self.nrows, 4), dtype=np.float32) if align else None
+        _check(lib().crsdr_spectra_fetch(self._h, _p(p, C.c_float), _p(None if c is None else c.view(np.float32), C.c_float), _p(a, C.c_float)))
+        return {k: v for k, v in (("psd", p), ("cross", c), ("align", a)) if v is not None}
+
+    def device_buffers(self) -> dict:
+        ptrs = [C.c_void_p() for _ in range(3)]
+        _check(lib().crsdr_spectra_device_buffers(self._h, *[C.byref(p) for p in ptrs]))
+        return dict(zip(("psd", "cross", "align"), [p.value for p in ptrs]))
+
+    def last_launches(self) -> int:
+        return self._last()[1]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().crsdr_spectra_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -2364,3 +2364,9 @@ extern "C" int crsdr_refcancel(int8_t *out, float *coef, float *residual, int32_
     st.back(status, ca.status, sizeof(int32_t) * n);
     return st.finish();
 }
+
+// ================================================================================================
+// (vi) Welch spectra and reference cross-spectra of the packets (crsdr_spectra, crsdr_welch)
+// ================================================================================================
+// Its kernels are named here for the first time, behind everything else: the existing kernels keep their places in the code object.
+#include "spectra_engine.hpp"

@@ -17,6 +17,7 @@
 #include "cbeamformer.h"
 #include "ccoherent.h"
 #include "ccontrol.h"
+#include "cspectra.h"
 
 static int cdsp_selftest()
 {
@@ -62,6 +63,8 @@ int main(int argc, char **argv)
     int augment_x = 0, augment_y = 0, refcancel = 0;
     std::string augment_mask;
     int sb_nfft = 0, sb_first = 0, sb_count = 1, sb_width = 1, sb_window = CRSDR_WINDOW_RECT;
+    int sp_nfft = 0, sp_band_lo = 0, sp_band_hi = 0;
+    bool sp_half = false;
     bool engine_batches = false;
     int ranks = 1, rank = 0, device = 0;
     std::string idfile;
@@ -118,6 +121,17 @@ int main(int argc, char **argv)
             if (n < 3) sb_nfft = -1;
             if (n == 3) sb_width = 1;
         }
+        // with --bench: per batch and packet the Welch spectra of every row and its alignment against row 0 (crsdr_spectra) on the packets
+        // where the plan left them: NFFT-point segments, ":half" for half-overlapping ones, --window as for --subbands, --band LO:HI the
+        // signed bins of the alignment figures (default +-NFFT/4).  One line per row: delay, phase, gain, coherence, strongest bin.
+        else if (a == "--spectra" && i + 1 < argc) {
+            const std::string s = argv[++i];
+            sp_nfft = std::atoi(s.c_str());
+            const size_t colon = s.find(':');
+            sp_half = colon != std::string::npos && s.substr(colon + 1) == "half";
+            if (sp_nfft <= 0 || (colon != std::string::npos && !sp_half)) sp_nfft = -1;
+        }
+        else if (a == "--band" && i + 1 < argc) { if (std::sscanf(argv[++i], "%d:%d", &sp_band_lo, &sp_band_hi) != 2) sp_nfft = -1; }
         else if (a == "--window" && i + 1 < argc) {
             const std::string w = argv[++i];
             sb_window = w == "rect" ? CRSDR_WINDOW_RECT : w == "hann" ? CRSDR_WINDOW_HANN : -1;
@@ -469,13 +483,35 @@ int main(int argc, char **argv)
             std::printf("doa: batch %d: %d directions, first (%d, %d), last (%d, %d), %d at broadside\n", b, n, doa->peak[0], doa->peak[1], doa->peak[2 * n - 2],
                         doa->peak[2 * n - 1], broadside);
         };
+        // --bench --spectra: cspectra::batch over crsdr_spectra, enqueued behind every batch on the plan's stream like the directions.  The
+        // synthetic channels all carry the reference noise and the plan has taken the integer lag out: what is left is under a sample.
+        std::unique_ptr<cspectra::batch> spectra;
+        if (sp_nfft && !coherent.sharded()) {
+            if (sp_nfft > 0) spectra.reset(new cspectra::batch(1 + nsig, B, batch, sp_nfft, sp_half, sb_window, sp_band_lo, sp_band_hi));
+            if (!spectra || !spectra->ok()) { std::printf("spectra: --spectra NFFT[:half] [--window rect|hann] [--band LO:HI] refused\nDEMO FAILED\n"); return 1; }
+        }
+        auto alignment = [&](int b) {
+            if (!spectra || !ok) return;
+            ok = spectra->submit(coherent.engine_plan()) == CRSDR_OK && spectra->fetch() == CRSDR_OK;
+            if (!ok || !report) return;
+            for (int e = 0; e < spectra->lines(); ++e)
+                for (int c = 0; c < spectra->nrows(); ++c) {
+                    const float *f = &spectra->align[4 * ((size_t)e * spectra->nrows() + c)];
+                    double db = 0.0;
+                    const int bin = spectra->strongest_bin(e, c, &db);
+                    std::printf("spectra: batch %d line %d row %d: delay %.6f phase %.6f gain %.6f coherence %.6f peak bin %d power %.2f dB\n", b, e, c, (double)f[0],
+                                (double)f[1], (double)f[2], (double)f[3], bin, db);
+                }
+        };
         auto run = [&](int n) {
             ok = ok && coherent.submit_batch(0, batch, fl);
             directions(0);
+            alignment(0);
             residual(0);
             for (int b = 1; b < n && ok; ++b) {
                 ok = ok && coherent.submit_batch(b & 1, batch, fl);       // upload of batch b overlaps the download of batch b - 1
                 directions(b);
+                alignment(b);
                 residual(b);
                 ok = ok && coherent.collect_batch((b - 1) & 1);
             }

@@ -930,6 +930,94 @@ int crsdr_augment_covariance(float *ra, const float *rxx, int mx, int my, int vx
  * bad sizes or a bad mask.  The setter and the per-op call check with the same function. */
 int crsdr_augment_lags(int mx, int my, int vx, int vy, uint64_t mask, int32_t *counts /* [vy][2vx-1], may be NULL */, int *uncovered);
 
+/* ------------------------------------------------------------------------------------------
+ * (v) Welch spectra and reference cross-spectra of the packets: a third packet consumer, beside the plan's fetches and crsdr_doa
+ * ---------------------------------------------------------------------------------------- */
+
+/* What the reference's clients do beside MUSIC (matlabclient/testchannels.m: a power spectrum per channel;
+ * matlabclient/seqnum_and_correlation.m: every column against column 1), on the device and on the packets AS PUBLISHED -- behind
+ * the shift, the rotation, the fractional-delay pass and the canceller.  For any number of rows; row 0, the reference channel, is a row
+ * like every other here.
+ *
+ * Input.  A packet's matrix is [nrows][B] int8; row c holds L = B / 2 samples x_c[n] = (I + jQ) / 127, c = 0 .. nrows - 1.  N = nfft, the
+ * hop is H = N (overlap 0) or H = N / 2 (overlap 1); a packet has J = (L - N) / H + 1 segments, segment j starting at sample jH:
+ * segments never cross packets.  A line e is `frames` consecutive packets, J' = frames * J segments.
+ * Window.  w = CRSDR_WINDOW_RECT or CRSDR_WINDOW_HANN (periodic, as in crsdr_doa_set_subbands).
+ * Spectra.
+ *     X_c[t][j][f] = sum_n w[n] x_c[jH + n] exp(-2 pi i f n / N)             (crsdr_fft's forward transform, FFT bin order)
+ *     P_c[f] = 1 / (J' N sum w^2) * sum_{t,j} |X_c[t][j][f]|^2                  psd   [nest][nrows][N]    float
+ *     S_c[f] = 1 / (J' N sum w^2) * sum_{t,j} conj(X_0[t][j][f]) X_c[t][j][f]   cross [nest][nrows][N][2] float
+ * the X^H X convention and the normalisation of crsdr_doa_set_subbands (P_c[f] is the diagonal of its R_f).  No mean is removed: DC
+ * lands in bin 0.  S_0[f] = (P_0[f], 0), the imaginary part written as exactly 0.
+ * Alignment figures, over the band of signed bins s_i = band_lo + i, i < K = band_hi - band_lo + 1, bin f_i = s_i mod N; all in fp64
+ * from the published fp32 P and S, each figure rounded once to fp32 (the order of the fp64 operations is not pinned):
+ *     A         = sum_{i < K-1} S_c[f_{i+1}] conj(S_c[f_i])
+ *     delay     = -atan2(Im A, Re A) * N / (2 pi)                  samples; 0 if A == 0     (row c = row 0 delayed by `delay`)
+ *     z         = sum_i S_c[f_i] exp(+2 pi i s_i delay / N)
+ *     phase     = atan2(Im z, Re z)                                 radians at DC with the delay taken out
+ *     gain      = |z| / sum_i P_0[f_i]                              0 if the denominator is 0
+ *     coherence = min(1, sum_i |S_c[f_i]|^2 / sum_i P_0[f_i] P_c[f_i])   0 if the denominator is 0; it is 1 for J' = 1 (one segment
+ *                                                                   is coherent with anything): average over segments to learn something
+ *     align [nest][nrows][4] float = (delay, phase, gain, coherence)
+ * Row 0 is computed like every other row and gives (0, 0, 1, 1) for a non-zero reference.  An all-zero packet gives zeros everywhere,
+ * never a NaN.  (Parity: unpinned by the reference, whose script only plots correlations.)
+ * Bits.  The sums over a packet's segments run in fp32 chains of at most 32 terms whose split depends on (blocksize, nfft, overlap)
+ * alone; the chains, the packets of a line and the scale are fp64 with one rounding.  Hence a line has the same bits wherever it
+ * sits in a batch and whatever nblocks is, and crsdr_welch equals the batched engine bit for bit.
+ *
+ * Limits, all CRSDR_EINVAL and all checked before a device is touched: nfft a power of two in 16 .. 4096; blocksize a multiple of
+ * 2 nfft (up to 2^22, as a plan's); nrows >= 2; 1 <= frames <= max_batch <= 64 (0 = 1 for both); (max_batch / frames) * nrows * nfft
+ * <= 2^24; overlap 0 or 1; a valid window; -nfft/2 <= band_lo < band_hi <= nfft/2 - 1.
+ *
+ * Every buffer is allocated by crsdr_spectra_create.  A submit is asynchronous on its stream: three kernel launches whatever the
+ * number of blocks, no allocation, no process-wide lock, nothing that waits for the device. */
+typedef struct crsdr_spectra crsdr_spectra;
+
+typedef struct crsdr_spectra_desc {
+    int32_t nrows, blocksize; /* of the packets it reads (as in crsdr_plan_desc) */
+    int32_t device;
+    int32_t max_batch;        /* blocks per submit, 1..64 (0 = 1) */
+    int32_t frames;           /* consecutive blocks per line, 1..max_batch (0 = 1) */
+    int32_t nfft;
+    int32_t overlap;          /* 0: hop nfft, 1: hop nfft / 2 */
+    int32_t window;           /* CRSDR_WINDOW_* */
+    int32_t band_lo, band_hi; /* the alignment figures' band, signed bins */
+} crsdr_spectra_desc;
+
+int crsdr_spectra_create(crsdr_spectra **spectra, const crsdr_spectra_desc *desc);
+int crsdr_spectra_destroy(crsdr_spectra *spectra);
+
+/* nblocks packets on the object's device, packet t at device_packets + t * packet_stride, its matrix [nrows][blocksize] int8 at
+ * + matrix_offset (4-byte aligned, like packet_stride); 1 <= nblocks <= max_batch, nblocks % frames == 0.  Asynchronous on hip_stream
+ * (NULL = the object's own stream); the packets must stay valid until the work has run.  One submit at a time: the next one reuses
+ * the buffers of this one, so fetch (or order the streams) in between. */
+int crsdr_spectra_submit(crsdr_spectra *spectra, const void *device_packets, size_t packet_stride, size_t matrix_offset, int nblocks,
+                         void *hip_stream);
+
+/* The plan's last submitted batch, where its packets are (own buffer or crsdr_plan_bind_packet), on the plan's stream: ordered
+ * behind that batch by the stream alone, no host wait in between.  CRSDR_ESTATE for a plan with nothing submitted or with a slab
+ * bound (the matrix is then not in the packet); CRSDR_EINVAL for another geometry or device, or a batch that is not a multiple of
+ * `frames` or exceeds max_batch. */
+int crsdr_spectra_submit_plan(crsdr_spectra *spectra, crsdr_plan *plan);
+
+/* Waits for the last submit and copies out what is asked for (any pointer may be NULL); nest = nblocks / frames.  psd, cross and align
+ * as laid out above.  CRSDR_ESTATE before the first submit. */
+int crsdr_spectra_fetch(crsdr_spectra *spectra, float *psd, float *cross, float *align);
+
+/* Device addresses of the results ([max_batch / frames] lines each, laid out as above), for consumers on the same stream. */
+int crsdr_spectra_device_buffers(crsdr_spectra *spectra, void **psd, void **cross, void **align);
+
+/* Of the last submit: the number of lines (what crsdr_spectra_fetch will write) and the kernel launches it issued (the same for
+ * every nblocks).  Either pointer may be NULL.  CRSDR_ESTATE before the first submit. */
+int crsdr_spectra_last_submit(crsdr_spectra *spectra, int *nest, int *launches);
+
+/* The per-op form on one packet's matrix [nrows][blocksize] (frames = 1): the same kernels on the same arguments, bit for bit.
+ * psd [nrows][nfft], cross [nrows][nfft][2], align [nrows][4]; any of the three may be NULL, not all.  nrows * nfft <= 2^24.
+ * mem_kind: CRSDR_MEM_HOST (copied) or CRSDR_MEM_DEVICE (every pointer on the device; matrix, psd and align 4-byte, cross 8-byte
+ * aligned). */
+int crsdr_welch(float *psd, float *cross, float *align, const int8_t *matrix, int nrows, int blocksize, int nfft, int overlap, int window,
+                int band_lo, int band_hi, int mem_kind);
+
 #ifdef __cplusplus
 }
 #endif
