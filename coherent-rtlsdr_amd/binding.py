@@ -49,6 +49,8 @@ ABI_SYMBOLS = [
     "crsdr_plan_set_refcancel", "crsdr_plan_fetch_refcancel", "crsdr_plan_refcancel_buffers", "crsdr_refcancel",
     "crsdr_spectra_create", "crsdr_spectra_destroy", "crsdr_spectra_submit", "crsdr_spectra_submit_plan", "crsdr_spectra_fetch",
     "crsdr_spectra_device_buffers", "crsdr_spectra_last_submit", "crsdr_welch",
+    "crsdr_caf_create", "crsdr_caf_destroy", "crsdr_caf_submit", "crsdr_caf_submit_plan", "crsdr_caf_fetch",
+    "crsdr_caf_device_buffers", "crsdr_caf_last_submit", "crsdr_ambiguity",
 ]
 REFCANCEL_SINGULAR, REFCANCEL_IDLE = 1, 2                     # status bit 0: the solve failed (g = 0); 2: the pass did not run
 REFCANCEL_MAX_TAPS = 9
@@ -103,6 +105,11 @@ class DoaDesc(C.Structure):
 class SpectraDesc(C.Structure):
     _fields_ = [("nrows", C.c_int32), ("blocksize", C.c_int32), ("device", C.c_int32), ("max_batch", C.c_int32), ("frames", C.c_int32),
                 ("nfft", C.c_int32), ("overlap", C.c_int32), ("window", C.c_int32), ("band_lo", C.c_int32), ("band_hi", C.c_int32)]
+
+
+class CafDesc(C.Structure):
+    _fields_ = [("nrows", C.c_int32), ("blocksize", C.c_int32), ("device", C.c_int32), ("max_batch", C.c_int32), ("frames", C.c_int32),
+                ("seg", C.c_int32), ("nlags", C.c_int32), ("ref_row", C.c_int32), ("window", C.c_int32), ("guard", C.c_int32)]
 
 
 _lib = None
@@ -252,6 +259,15 @@ def lib():
         L.crsdr_spectra_device_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.crsdr_spectra_last_submit.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.crsdr_welch.argtypes = [f32p, f32p, f32p, i8p] + [C.c_int] * 8
+    if hasattr(L, "crsdr_caf_create"):               # (likewise: an older build has no range-Doppler maps)
+        L.crsdr_caf_create.argtypes = [C.POINTER(vp), C.POINTER(CafDesc)]
+        L.crsdr_caf_destroy.argtypes = [vp]
+        L.crsdr_caf_submit.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp]
+        L.crsdr_caf_submit_plan.argtypes = [vp, vp]
+        L.crsdr_caf_fetch.argtypes = [vp, f32p, f32p, f32p]
+        L.crsdr_caf_device_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        L.crsdr_caf_last_submit.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.crsdr_ambiguity.argtypes = [f32p, f32p, f32p, i8p] + [C.c_int] * 8
     _lib = L
     return L
 
@@ -615,6 +631,26 @@ def welch_device(psd_ptr: int, cross_ptr: int, align_ptr: int, matrix_ptr: int, 
     cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
     _check(lib().crsdr_welch(cast(psd_ptr, C.c_float), cast(cross_ptr, C.c_float), cast(align_ptr, C.c_float), cast(matrix_ptr, C.c_int8), int(nrows), int(B),
                              int(nfft), int(overlap), int(window), int(band_lo), int(band_hi), MEM_DEVICE))
+
+
+def ambiguity(matrix, seg, nlags, ref_row=0, window=WINDOW_RECT, guard=0):
+    """crsdr_ambiguity: (chi [nrows][nd][nlags] complex64, map [nd][nlags] float32, peak [nrows + 1][6] float32 = lag, doppler, power,
+    ratio, dlag, ddop) of one packet's int8 matrix [nrows][B] against its row ref_row, nd = B / (2 seg) Doppler bins in FFT order.
+    The batched engine (Caf) on one line of one packet, bit for bit."""
+    m = np.ascontiguousarray(matrix, dtype=np.int8)
+    nrows, B = m.shape
+    nd, R = max(B // (2 * max(int(seg), 1)), 0), max(int(nlags), 0)
+    chi, mp, pk = np.empty((nrows, nd, R), dtype=np.complex64), np.empty((nd, R), dtype=np.float32), np.empty((nrows + 1, 6), dtype=np.float32)
+    _check(lib().crsdr_ambiguity(_p(chi.view(np.float32), C.c_float), _p(mp, C.c_float), _p(pk, C.c_float), _p(m, C.c_int8), nrows, B, int(seg), int(nlags),
+                                 int(ref_row), int(window), int(guard), MEM_HOST))
+    return chi, mp, pk
+
+
+def ambiguity_device(chi_ptr: int, map_ptr: int, peak_ptr: int, matrix_ptr: int, nrows, B, seg, nlags, ref_row, window, guard):
+    """Same on device memory (any output pointer, not all, may be 0); returns after the kernels finished."""
+    cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
+    _check(lib().crsdr_ambiguity(cast(chi_ptr, C.c_float), cast(map_ptr, C.c_float), cast(peak_ptr, C.c_float), cast(matrix_ptr, C.c_int8), int(nrows), int(B),
+                                 int(seg), int(nlags), int(ref_row), int(window), int(guard), MEM_DEVICE))
 
 
 def subband_beamform(matrix, weights, nfft, first=0, nbands=1, width=1, window=WINDOW_RECT):
@@ -1240,6 +1276,61 @@ class Spectra:
     def close(self):
         if getattr(self, "_h", None):
             lib().crsdr_spectra_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Caf:
+    """crsdr_caf: per line of `frames` consecutive device-resident packets every row's range-Doppler map (cross-ambiguity function)
+    against row ref_row, the array map and the peak figures.  submit* only enqueue; fetch() waits and returns numpy arrays."""
+
+    def __init__(self, nrows, blocksize, seg, nlags, ref_row=0, window=WINDOW_RECT, guard=0, max_batch=1, frames=1, device=0):
+        desc = CafDesc(int(nrows), int(blocksize), int(device), int(max_batch), int(frames), int(seg), int(nlags), int(ref_row), int(window), int(guard))
+        h = C.c_void_p()
+        _check(lib().crsdr_caf_create(C.byref(h), C.byref(desc)))
+        self._h = h
+        self.nrows, self.B, self.seg, self.nlags, self.ref_row, self.window, self.guard = int(nrows), int(blocksize), int(seg), int(nlags), int(ref_row), int(window), int(guard)
+        self.max_batch, self.frames = max(1, int(max_batch)), max(1, int(frames))
+        self.nd = self.frames * (self.B // (2 * self.seg))
+
+    def _last(self):
+        nest, launches = C.c_int(0), C.c_int(0)
+        _check(lib().crsdr_caf_last_submit(self._h, C.byref(nest), C.byref(launches)))
+        return nest.value, launches.value
+
+    def submit(self, packets_ptr: int, packet_stride: int, matrix_offset: int, nblocks: int, stream: int | None = None):
+        """nblocks packets on the device: packet t at packets_ptr + t * packet_stride, its matrix at + matrix_offset."""
+        _check(lib().crsdr_caf_submit(self._h, C.c_void_p(int(packets_ptr)), int(packet_stride), int(matrix_offset), int(nblocks), C.c_void_p(stream or 0)))
+
+    def submit_plan(self, plan: "Plan"):
+        """The plan's last submitted batch, where its packets are, on the plan's stream."""
+        _check(lib().crsdr_caf_submit_plan(self._h, plan._h))
+
+    def fetch(self, chi=True, map=True, peak=True) -> dict:
+        """Waits for the last submit.  chi [nest][nrows][nd][nlags] complex64, map [nest][nd][nlags], peak [nest][nrows + 1][6]."""
+        n = self._last()[0]
+        c = np.zeros((n, self.nrows, self.nd, self.nlags), dtype=np.complex64) if chi else None
+        m = np.zeros((n, self.nd, self.nlags), dtype=np.float32) if map else None
+        p = np.zeros((n, self.nrows + 1, 6), dtype=np.float32) if peak else None
+        _check(lib().crsdr_caf_fetch(self._h, _p(None if c is None else c.view(np.float32), C.c_float), _p(m, C.c_float), _p(p, C.c_float)))
+        return {k: v for k, v in (("chi", c), ("map", m), ("peak", p)) if v is not None}
+
+    def device_buffers(self) -> dict:
+        ptrs = [C.c_void_p() for _ in range(3)]
+        _check(lib().crsdr_caf_device_buffers(self._h, *[C.byref(p) for p in ptrs]))
+        return dict(zip(("chi", "map", "peak"), [p.value for p in ptrs]))
+
+    def last_launches(self) -> int:
+        return self._last()[1]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().crsdr_caf_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -1,0 +1,210 @@
+// caf.hpp -- range-Doppler maps (the cross-ambiguity function) of a packet's rows against one of them: crsdr_caf / crsdr_ambiguity.
+//
+// Definition (include/crsdr.h, section (w); tests/caf_model.py is the fp64 statement of it).  Row c of a packet's matrix [nrows][B] int8
+// holds L = B / 2 samples, here the integers X_c[n] = I + jQ.  Ls = seg, a packet has J = L / Ls segments, a line is `frames` packets,
+// slow time k = t J + j < nd = frames J, R = nlags, r = ref_row:
+//     y_c[k][tau]   = sum_{n < Ls} X_c[t][j Ls + n] conj(X_r[t][j Ls + n - tau])         int32, exact; X_r[t][m] = 0 for m < 0
+//     chi_c[d][tau] = 1 / (127^2 Ls sum w) * sum_k w[k] y_c[k][tau] exp(-2 pi i d k / nd)      chi [nest][nrows][nd][R] float2
+//     map[d][tau]   = sum_{c != r} |chi_c[d][tau]|^2                                            map [nest][nd][R] float
+// and the peak figures of every row's |chi|^2 and of map: caf_peak.hpp.
+//
+//   k_caf<LG>     grid (row * tiles + tile, line), 256 threads: ONE (line, row, tile of T = min(16, 4096 / nd) lags) per workgroup, both
+//                 stages in it, nothing between workgroups.
+//                 Range stage.  The line's row goes through LDS in chunks of 1024 words (a word = two samples, I0 Q0 I1 Q1): the row's
+//                 words and, in front of the reference's, the `pre` words the tile's largest lag reaches back -- zeros in front of the
+//                 packet's first sample, so a chunk never reads another packet.  Plain 4-byte loads: a matrix row is only 4-byte
+//                 aligned.  An item is (piece of 8 words, an even lag and the odd lag behind it): both read the same row words and the same
+//                 nine reference words.  Per word, with x = r[i + 1] for the even lag and w = v_alignbit(r[i + 1], r[i], 16) for the odd one
+//                 (its reference straddles two words), for each of the two:
+//                     re = sdot4(s, w)                                     I I + Q Q
+//                     p  = sdot4(swap(s), w)                               Q_s I_r + I_s Q_r         swap: v_perm, bytes (Q0 I0 Q1 I1)
+//                     e  = sdot4(swap(s), w & 0x00ff00ff)                  Q_s I_r                   the even-byte mask
+//                 and Im = Q_s I_r - I_s Q_r = 2 e - p: the odd-byte product is p - e, so its mask and a fourth product are not needed.
+//                 Ten instructions per word and pair, the swap and the realignment included: five per word and lag.  A wave's 64 items
+//                 are 8 pieces by 8 pairs: the row's words are one broadcast address per piece and neighbouring pairs read neighbouring
+//                 reference words.  The piece's four int32 sums go into ACC [nd][T][2] in LDS by ds_add (integers: any order gives the
+//                 same bits), lag fastest, so that a wave's adds fall on consecutive words.  At nd = 4096 a tile is one lag of either
+//                 parity: an item is then (piece, lag), the shift of v_alignbit 0 or 16.
+//                 Doppler stage.  ACC is read into registers, converted with one rounding, multiplied by the window and written back over
+//                 it as A [T][nd] float2 in spectra.hpp's padded layout; the twiddles take the place of the staged words; the T transforms
+//                 run as one chunk of spectra.hpp's network (sp_pass); scale, digit reversal, and the store with tau fastest.
+//                 LDS: A 34 KiB (32 KiB at nd = 4096, unpadded as in spectra.hpp) + max(twiddles, staged words) <= 64 KiB static.
+//   k_caf_map     grid (cells / 32, line): the fp64 sum of |chi|^2 over the rows but r, eight interleaved parts of the rows added in a
+//                 fixed order, rounded once.
+//   k_caf_peak    grid (entry, line), 256 threads: caf_peak.hpp's search, one part per thread, merged by a tree in LDS.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "caf_peak.hpp"
+#include "fft_lds.hpp"
+#include "spectra.hpp"
+
+namespace crsdr {
+namespace caf {
+
+constexpr int CAF_THREADS = 256, CAF_POINTS = 4096, CAF_TILE = 16;
+constexpr int CAF_MIN_LOG2 = 3, CAF_MAX_LOG2 = 12;                     // log2 nd
+constexpr int CAF_MIN_SEG_LOG2 = 4, CAF_MAX_SEG_LOG2 = 12, CAF_MAX_LAGS = 1024;
+constexpr int CAF_CHUNK = 1024, CAF_PIECE = 8;                         // words
+constexpr int CAF_PRE_MAX = CAF_MAX_LAGS / 2;                          // ((R - 1) >> 1) + 1 <= 512 words in front of a chunk
+// the row's chunk, the reference's chunk with its prefix, and the word an even lag's last v_alignbit names without using it
+constexpr int CAF_STAGE_WORDS = CAF_CHUNK + CAF_PRE_MAX + CAF_CHUNK + CAF_PIECE;
+
+__host__ __device__ constexpr int caf_log2_tile(int lg) { return lg <= 8 ? 4 : 12 - lg; }
+__host__ __device__ constexpr int caf_tile(int lg) { return 1 << caf_log2_tile(lg); }
+__host__ __device__ constexpr int caf_tiles(int lg, int nlags) { return (nlags + caf_tile(lg) - 1) >> caf_log2_tile(lg); }
+template <int LG>
+constexpr int caf_u_words() { return 2 * (1 << LG) > CAF_STAGE_WORDS ? 2 * (1 << LG) : CAF_STAGE_WORDS; }
+
+// Packet t of the batch at packets + t * packet_stride, its matrix [nrows][B] int8 at + matrix_off (4-byte aligned).
+// tw_g, win: spectra::k_spectra_tables at N = nd.  scale = fp32(1 / (127^2 Ls sum w)).
+template <int LG>
+__global__ __launch_bounds__(CAF_THREADS) void k_caf(const int8_t *__restrict__ packets, size_t packet_stride, size_t matrix_off, int nrows, int B, int frames,
+                                                     int lgseg, int nlags, int ref_row, const float2 *__restrict__ tw_g, const float *__restrict__ win, float scale,
+                                                     float2 *__restrict__ chi)
+{
+    constexpr int ND = 1 << LG, LT = caf_log2_tile(LG), T = 1 << LT, CELLS = ND * T, PER = CELLS >= CAF_THREADS ? CELLS / CAF_THREADS : 1;
+    __shared__ float2 A[spectra::sp_lds_points<LG>()];
+    __shared__ uint32_t U[caf_u_words<LG>()];
+    int *ACC = reinterpret_cast<int *>(A);
+    uint32_t *SW = U, *RW = U + CAF_CHUNK;
+    const int tid = threadIdx.x, tiles = caf_tiles(LG, nlags), row = blockIdx.x / tiles, tile = blockIdx.x - row * tiles, e = blockIdx.y;
+    const int lag0 = tile << LT, tt = min(T, nlags - lag0), pre = ((lag0 + tt - 1) >> 1) + 1;
+    const int words = B >> 2, J = (B >> 1) >> lgseg, nchunks = (words + CAF_CHUNK - 1) / CAF_CHUNK;
+
+    for (int i = tid; i < 2 * CELLS; i += CAF_THREADS) ACC[i] = 0;
+    for (int f = 0; f < frames; ++f) {
+        const int8_t *m = packets + (size_t)(e * frames + f) * packet_stride + matrix_off;
+        const uint32_t *srow = reinterpret_cast<const uint32_t *>(m + (size_t)row * B), *rrow = reinterpret_cast<const uint32_t *>(m + (size_t)ref_row * B);
+        for (int c = 0; c < nchunks; ++c) {
+            const int w0 = c * CAF_CHUNK, cw = min(CAF_CHUNK, words - w0);
+            __syncthreads();                                         // (the chunk before is read; the first time: ACC is zero)
+            for (int i = tid; i < cw; i += CAF_THREADS) SW[i] = srow[w0 + i];
+            for (int i = tid; i < pre + cw; i += CAF_THREADS) {
+                const int g = w0 - pre + i;
+                RW[i] = g >= 0 ? rrow[g] : 0u;                       // X_r = 0 in front of the packet
+            }
+            __syncthreads();
+            if constexpr (T >= 2) {
+                // an even lag and the odd one behind it per item: the same row words, swaps and reference words serve both
+                for (int it = tid; it < (cw / CAF_PIECE) << (LT - 1); it += CAF_THREADS) {
+                    const int l = (it & (T / 2 - 1)) * 2, p = it >> (LT - 1);
+                    if (l >= tt) continue;
+                    const uint32_t *r = RW + pre + p * CAF_PIECE - ((lag0 + l) >> 1) - 1, *s = SW + p * CAF_PIECE;      // (lag0 is even)
+                    int re0 = 0, pp0 = 0, ee0 = 0, re1 = 0, pp1 = 0, ee1 = 0;
+                    uint32_t x0 = r[0];
+#pragma unroll
+                    for (int i = 0; i < CAF_PIECE; ++i) {
+                        const uint32_t x1 = r[i + 1], w = __builtin_amdgcn_alignbit(x1, x0, 16), sv = s[i], sx = __builtin_amdgcn_perm(sv, sv, 0x02030001u);
+                        x0 = x1;
+                        re0 = __builtin_amdgcn_sdot4((int)sv, (int)x1, re0, false);
+                        pp0 = __builtin_amdgcn_sdot4((int)sx, (int)x1, pp0, false);
+                        ee0 = __builtin_amdgcn_sdot4((int)sx, (int)(x1 & 0x00ff00ffu), ee0, false);
+                        re1 = __builtin_amdgcn_sdot4((int)sv, (int)w, re1, false);
+                        pp1 = __builtin_amdgcn_sdot4((int)sx, (int)w, pp1, false);
+                        ee1 = __builtin_amdgcn_sdot4((int)sx, (int)(w & 0x00ff00ffu), ee1, false);
+                    }
+                    const int k = f * J + ((2 * (w0 + p * CAF_PIECE)) >> lgseg);
+                    int *a = &ACC[((k << LT) + l) * 2];
+                    atomicAdd(a, re0);
+                    atomicAdd(a + 1, 2 * ee0 - pp0);
+                    if (l + 1 < tt) {                                // (a tile's tail may end on the even lag)
+                        atomicAdd(a + 2, re1);
+                        atomicAdd(a + 3, 2 * ee1 - pp1);
+                    }
+                }
+            } else {                                                 // nd = 4096: one lag a tile, of either parity
+                for (int it = tid; it < (cw / CAF_PIECE) << LT; it += CAF_THREADS) {
+                    const int l = it & (T - 1), p = it >> LT;
+                    if (l >= tt) continue;
+                    const int lag = lag0 + l, odd = lag & 1;
+                    const uint32_t *r = RW + pre + p * CAF_PIECE - (lag >> 1) - odd, *s = SW + p * CAF_PIECE;
+                    const uint32_t sh = (uint32_t)odd << 4;
+                    int re = 0, pp = 0, ee = 0;
+                    uint32_t x0 = r[0];
+#pragma unroll
+                    for (int i = 0; i < CAF_PIECE; ++i) {
+                        const uint32_t x1 = r[i + 1], w = __builtin_amdgcn_alignbit(x1, x0, sh), sv = s[i], sx = __builtin_amdgcn_perm(sv, sv, 0x02030001u);
+                        x0 = x1;
+                        re = __builtin_amdgcn_sdot4((int)sv, (int)w, re, false);
+                        pp = __builtin_amdgcn_sdot4((int)sx, (int)w, pp, false);
+                        ee = __builtin_amdgcn_sdot4((int)sx, (int)(w & 0x00ff00ffu), ee, false);
+                    }
+                    const int k = f * J + ((2 * (w0 + p * CAF_PIECE)) >> lgseg);
+                    atomicAdd(&ACC[((k << LT) + l) * 2], re);
+                    atomicAdd(&ACC[((k << LT) + l) * 2 + 1], 2 * ee - pp);
+                }
+            }
+        }
+    }
+    __syncthreads();
+
+    int yr[PER], yi[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const int i = tid + j * CAF_THREADS;
+        yr[j] = i < CELLS ? ACC[2 * i] : 0;
+        yi[j] = i < CELLS ? ACC[2 * i + 1] : 0;
+    }
+    float2 *tw = reinterpret_cast<float2 *>(U);
+    for (int t = tid; t < ND; t += CAF_THREADS) tw[t] = tw_g[t];
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const int i = tid + j * CAF_THREADS, k = i >> LT, l = i & (T - 1);
+        if (i < CELLS) {
+            const float w = win[k];
+            A[spectra::sp_pad<LG>(l * ND + k)] = make_float2((float)yr[j] * w, (float)yi[j] * w);
+        }
+    }
+    __syncthreads();
+    spectra::sp_pass<LG, 0>(A, tw, tt, tid);                         // (a barrier ends it)
+
+    float2 *out = chi + ((size_t)e * nrows + row) * ND * (size_t)nlags + lag0;
+    for (int it = tid; it < CELLS; it += CAF_THREADS) {
+        const int l = it & (T - 1), slot = it >> LT;
+        if (l >= tt) continue;
+        const float2 x = A[spectra::sp_pad<LG>(l * ND + slot)];
+        out[(size_t)digit_reverse<LG>(slot) * nlags + l] = make_float2(x.x * scale, x.y * scale);
+    }
+}
+
+// grid (ceil(nd R / 32), nest), 256 threads = 32 cells x 8 parts: part q adds rows q, q + 8, ... in fp64, the parts are added in part
+// order.  (One thread per cell over all the rows left a line of 1025 rows to 63 workgroups of 1024 dependent loads each: 0.30 ms.)
+constexpr int CAF_MAP_CELLS = 32, CAF_MAP_PARTS = CAF_THREADS / CAF_MAP_CELLS;
+__global__ __launch_bounds__(CAF_THREADS) void k_caf_map(const float2 *__restrict__ chi, int nrows, int cells, int ref_row, float *__restrict__ map)
+{
+    __shared__ double part[CAF_MAP_PARTS][CAF_MAP_CELLS];
+    const int l = threadIdx.x % CAF_MAP_CELLS, q = threadIdx.x / CAF_MAP_CELLS, i = blockIdx.x * CAF_MAP_CELLS + l, e = blockIdx.y;
+    const float *c = reinterpret_cast<const float *>(chi + (size_t)e * nrows * cells);
+    double s = 0.0;
+    if (i < cells)
+        for (int row = q; row < nrows; row += CAF_MAP_PARTS)
+            if (row != ref_row) s += cafp::power(c + (size_t)row * cells * 2, 2, i);
+    part[q][l] = s;
+    __syncthreads();
+    if (q != 0 || i >= cells) return;
+    for (int k = 1; k < CAF_MAP_PARTS; ++k) s += part[k][l];
+    map[(size_t)e * cells + i] = (float)s;
+}
+
+// grid (nrows + 1, nest).  peak [nest][nrows + 1][6]: the rows' |chi|^2, then map
+__global__ __launch_bounds__(CAF_THREADS) void k_caf_peak(const float2 *__restrict__ chi, const float *__restrict__ map, int nrows, int nd, int R, int guard,
+                                                          float *__restrict__ peak)
+{
+    __shared__ cafp::Part parts[CAF_THREADS];
+    const int entry = blockIdx.x, e = blockIdx.y, tid = threadIdx.x, comps = entry < nrows ? 2 : 1;
+    const size_t cells = (size_t)nd * R;
+    const float *src = entry < nrows ? reinterpret_cast<const float *>(chi + ((size_t)e * nrows + entry) * cells) : map + (size_t)e * cells;
+    parts[tid] = cafp::part(src, comps, nd, R, guard, tid, CAF_THREADS);
+    __syncthreads();
+    for (int h = CAF_THREADS / 2; h >= 1; h >>= 1) {
+        if (tid < h) cafp::merge(parts[tid], parts[tid + h]);
+        __syncthreads();
+    }
+    if (tid == 0) cafp::figures(src, comps, nd, R, guard, parts[0], peak + ((size_t)e * (nrows + 1) + entry) * 6);
+}
+
+} // namespace caf
+} // namespace crsdr

@@ -1,0 +1,223 @@
+// caf_engine.hpp -- the crsdr_caf object behind include/crsdr.h, and its per-op form crsdr_ambiguity.  Part of crsdr.hip's translation
+// unit: included at its very end, behind spectra_engine.hpp, so that the existing kernels keep their places in the code object.
+// (w) Range-Doppler maps (crsdr_caf): per line of `frames` packets every row's cross-ambiguity function against row ref_row, the array
+//     map and the peak figures (caf.hpp, caf_peak.hpp).  Every buffer, the twiddle and window tables included, is made at create; a
+//     submit is three launches on one stream whatever the batch size (rows, map, peaks), no lock, no allocation, no synchronisation.
+#pragma once
+
+#include "caf.hpp"
+
+// `launch` with LG = log2 nd, 3 .. 12
+#define CAF_DISPATCH(lg, launch)                                                    \
+    switch (lg) {                                                                   \
+    case 3: { constexpr int LG = 3; launch; } break;                                \
+    case 4: { constexpr int LG = 4; launch; } break;                                \
+    case 5: { constexpr int LG = 5; launch; } break;                                \
+    case 6: { constexpr int LG = 6; launch; } break;                                \
+    case 7: { constexpr int LG = 7; launch; } break;                                \
+    case 8: { constexpr int LG = 8; launch; } break;                                \
+    case 9: { constexpr int LG = 9; launch; } break;                                \
+    case 10: { constexpr int LG = 10; launch; } break;                              \
+    case 11: { constexpr int LG = 11; launch; } break;                              \
+    default: { constexpr int LG = 12; launch; } break;                              \
+    }
+
+constexpr int kCafLaunches = 3;
+constexpr long long kCafMaxCells = 1ll << 24;           // (max_batch / frames) * nrows * nd * nlags
+
+struct crsdr_caf {
+    DoaStream own;
+    int nrows = 0, B = 0, device = 0, max_batch = 1, frames = 1, seg = 0, nlags = 0, ref_row = 0, window = 0, guard = 0, nd = 0;
+    DevBuf<float2> tw, chi;
+    DevBuf<float> win, map, peak;
+    hipStream_t last_stream = nullptr;
+    int last_nest = 0;
+    bool submitted = false;
+};
+
+// every limit of section (w), for crsdr_caf_create and crsdr_ambiguity (max_batch = frames = 1)
+static int caf_args_ok(const char *who, int nrows, int blocksize, int max_batch, int frames, int seg, int nlags, int ref_row, int window, int guard)
+{
+    const int lgs = ilog2_exact(seg);
+    if (lgs < caf::CAF_MIN_SEG_LOG2 || lgs > caf::CAF_MAX_SEG_LOG2) return fail(CRSDR_EINVAL, "%s: seg = %d (a power of two in [16, 4096])", who, seg);
+    if (nrows < 2) return fail(CRSDR_EINVAL, "%s: nrows = %d (at least 2: the reference row and another)", who, nrows);
+    if (blocksize < 2 * seg || blocksize % (2 * seg) || blocksize > (1 << kMaxLog2Plan))
+        return fail(CRSDR_EINVAL, "%s: blocksize = %d (a multiple of 2 seg = %d, up to %d)", who, blocksize, 2 * seg, 1 << kMaxLog2Plan);
+    if (ref_row < 0 || ref_row >= nrows) return fail(CRSDR_EINVAL, "%s: ref_row = %d (0..%d)", who, ref_row, nrows - 1);
+    if (nlags < 1 || nlags > seg || nlags > caf::CAF_MAX_LAGS) return fail(CRSDR_EINVAL, "%s: nlags = %d (1..min(seg, %d))", who, nlags, caf::CAF_MAX_LAGS);
+    if (max_batch < 1 || max_batch > kMaxBatch) return fail(CRSDR_EINVAL, "%s: max_batch = %d (1..%d)", who, max_batch, kMaxBatch);
+    if (frames < 1 || frames > max_batch) return fail(CRSDR_EINVAL, "%s: frames = %d (1..max_batch = %d)", who, frames, max_batch);
+    const long long nd = (long long)frames * (blocksize / (2 * seg));
+    const int lgd = nd <= (1 << caf::CAF_MAX_LOG2) ? ilog2_exact((int)nd) : -1;
+    if (lgd < caf::CAF_MIN_LOG2 || lgd > caf::CAF_MAX_LOG2)
+        return fail(CRSDR_EINVAL, "%s: nd = frames * blocksize / (2 seg) = %lld (a power of two in [8, 4096])", who, nd);
+    if ((long long)(max_batch / frames) * nrows * nd * nlags > kCafMaxCells)
+        return fail(CRSDR_EINVAL, "%s: (max_batch / frames) * nrows * nd * nlags = %lld (at most 2^24)", who, (long long)(max_batch / frames) * nrows * nd * nlags);
+    if (window != CRSDR_WINDOW_RECT && window != CRSDR_WINDOW_HANN) return fail(CRSDR_EINVAL, "%s: window = %d", who, window);
+    if (guard < 0 || guard > nd / 2) return fail(CRSDR_EINVAL, "%s: guard = %d (0..nd / 2 = %lld)", who, guard, nd / 2);
+    return CRSDR_OK;
+}
+
+// the three launches, for the object and for crsdr_ambiguity: the same kernels on the same arguments, so the same bits
+static int caf_enqueue(hipStream_t S, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nblocks, int nrows, int B, int frames, int seg, int nlags,
+                       int ref_row, int window, int guard, const float2 *tw, const float *win, float2 *chi, float *map, float *peak)
+{
+    const int nest = nblocks / frames, nd = frames * (B / (2 * seg)), lg = ilog2_exact(nd), lgseg = ilog2_exact(seg), cells = nd * nlags;
+    // sum w: nd (rect), nd / 2 (periodic Hann)
+    const float scale = (float)(1.0 / (127.0 * 127.0 * (double)seg * (window == CRSDR_WINDOW_HANN ? 0.5 * (double)nd : (double)nd)));
+    const dim3 grow((unsigned)(nrows * caf::caf_tiles(lg, nlags)), (unsigned)nest);
+    CAF_DISPATCH(lg, hipLaunchKernelGGL((caf::k_caf<LG>), grow, dim3(caf::CAF_THREADS), 0, S, packets, packet_stride, matrix_offset, nrows, B, frames, lgseg, nlags, ref_row,
+                                        tw, win, scale, chi));
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(caf::k_caf_map, dim3((unsigned)((cells + caf::CAF_MAP_CELLS - 1) / caf::CAF_MAP_CELLS), (unsigned)nest), dim3(caf::CAF_THREADS), 0, S,
+                       (const float2 *)chi, nrows, cells, ref_row, map);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(caf::k_caf_peak, dim3((unsigned)(nrows + 1), (unsigned)nest), dim3(caf::CAF_THREADS), 0, S, (const float2 *)chi, (const float *)map, nrows, nd, nlags,
+                       guard, peak);
+    HIP_TRY(hipGetLastError());
+    return CRSDR_OK;
+}
+
+static void caf_free(crsdr_caf *q)
+{
+    if (!q) return;
+    (void)hipSetDevice(q->device);
+    if (q->submitted) (void)hipDeviceSynchronize();      // (the last submit's stream may be the caller's, and gone)
+    delete q;                                            // the buffers, then the stream
+}
+
+extern "C" int crsdr_caf_create(crsdr_caf **caf, const crsdr_caf_desc *desc)
+{
+    if (!caf || !desc) return fail(CRSDR_EINVAL, "caf_create: NULL argument");
+    *caf = nullptr;
+    const int mb = desc->max_batch ? desc->max_batch : 1, F = desc->frames ? desc->frames : 1;
+    { const int rc_ = caf_args_ok("caf_create", desc->nrows, desc->blocksize, mb, F, desc->seg, desc->nlags, desc->ref_row, desc->window, desc->guard); if (rc_) return rc_; }
+    { int rc = require_device(); if (rc) return rc; }
+    int ndev = 0;
+    (void)crsdr_device_count(&ndev);
+    if (desc->device < 0 || desc->device >= ndev) return fail(CRSDR_ENODEV, "caf_create: device %d of %d", desc->device, ndev);
+
+    crsdr_caf *q = new (std::nothrow) crsdr_caf();
+    if (!q) return fail(CRSDR_ENOMEM, "caf_create: out of host memory");
+    q->nrows = desc->nrows; q->B = desc->blocksize; q->device = desc->device; q->max_batch = mb; q->frames = F; q->seg = desc->seg; q->nlags = desc->nlags;
+    q->ref_row = desc->ref_row; q->window = desc->window; q->guard = desc->guard; q->nd = F * (q->B / (2 * q->seg));
+    const size_t lines = (size_t)(mb / F), cells = (size_t)q->nd * (size_t)q->nlags;
+    int rc = [&]() -> int {
+        HIP_TRY(hipSetDevice(q->device));
+        HIP_TRY(hipStreamCreateWithFlags(&q->own.s, hipStreamNonBlocking));
+        int r = CRSDR_OK;
+        if ((r = q->tw.alloc((size_t)q->nd)) || (r = q->win.alloc((size_t)q->nd)) || (r = q->chi.alloc(lines * (size_t)q->nrows * cells)) || (r = q->map.alloc(lines * cells)) ||
+            (r = q->peak.alloc(lines * (size_t)(q->nrows + 1) * 6)))
+            return r;
+        if ((r = spectra_tables(q->own.s, q->nd, q->window, q->tw, q->win))) return r;
+        HIP_TRY(hipStreamSynchronize(q->own.s));         // a submit may come on any stream
+        return CRSDR_OK;
+    }();
+    if (rc) { caf_free(q); return rc; }
+    *caf = q;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_destroy(crsdr_caf *caf)
+{
+    if (!caf) return fail(CRSDR_EINVAL, "caf_destroy: NULL caf");
+    caf_free(caf);
+    return CRSDR_OK;
+}
+
+static int caf_launch(crsdr_caf *q, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nblocks, hipStream_t S)
+{
+    const int rc = caf_enqueue(S, packets, packet_stride, matrix_offset, nblocks, q->nrows, q->B, q->frames, q->seg, q->nlags, q->ref_row, q->window, q->guard, q->tw, q->win,
+                               q->chi, q->map, q->peak);
+    if (rc) return rc;
+    q->last_stream = S; q->last_nest = nblocks / q->frames; q->submitted = true;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_submit(crsdr_caf *q, const void *device_packets, size_t packet_stride, size_t matrix_offset, int nblocks, void *hip_stream)
+{
+    if (!q || !device_packets) return fail(CRSDR_EINVAL, "caf_submit: NULL caf or packets");
+    if (nblocks < 1 || nblocks > q->max_batch || nblocks % q->frames)
+        return fail(CRSDR_EINVAL, "caf_submit: nblocks = %d (1..max_batch = %d, a multiple of frames = %d)", nblocks, q->max_batch, q->frames);
+    if (((uintptr_t)device_packets + matrix_offset) % 4 || packet_stride % 4)
+        return fail(CRSDR_EINVAL, "caf_submit: matrix start and packet stride must be 4-byte aligned");
+    if (nblocks > 1 && packet_stride < (size_t)q->nrows * (size_t)q->B)
+        return fail(CRSDR_EINVAL, "caf_submit: packet_stride = %zu is smaller than a matrix of %d x %d", packet_stride, q->nrows, q->B);
+    HIP_TRY(hipSetDevice(q->device));
+    return caf_launch(q, (const int8_t *)device_packets, packet_stride, matrix_offset, nblocks, hip_stream ? (hipStream_t)hip_stream : q->own.s);
+}
+
+extern "C" int crsdr_caf_submit_plan(crsdr_caf *q, crsdr_plan *p)
+{
+    if (!q || !p) return fail(CRSDR_EINVAL, "caf_submit_plan: NULL argument");
+    if (p->nrows != q->nrows || p->B != q->B || p->device != q->device)
+        return fail(CRSDR_EINVAL, "caf_submit_plan: plan is %d x %d on device %d, caf %d x %d on device %d", p->nrows, p->B, p->device, q->nrows, q->B, q->device);
+    if (p->d_slab) return fail(CRSDR_ESTATE, "caf_submit_plan: the plan writes slabs (crsdr_plan_bind_slab): its packets hold no matrix");
+    if (!p->submitted || p->last_nblocks < 1) return fail(CRSDR_ESTATE, "caf_submit_plan: the plan has no submitted batch");
+    if (p->last_nblocks > q->max_batch || p->last_nblocks % q->frames)
+        return fail(CRSDR_EINVAL, "caf_submit_plan: the plan's batch of %d blocks (caf: at most %d, a multiple of frames = %d)", p->last_nblocks, q->max_batch, q->frames);
+    HIP_TRY(hipSetDevice(q->device));
+    // the batch's last kernel is on p->stream: stream order alone puts the maps behind it
+    return caf_launch(q, p->d_packet, p->packet_stride, p->matrix_off, p->last_nblocks, p->stream);
+}
+
+extern "C" int crsdr_caf_last_submit(crsdr_caf *q, int *nest, int *launches)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_last_submit: NULL caf");
+    if (!q->submitted) return fail(CRSDR_ESTATE, "caf_last_submit: nothing submitted");
+    if (nest) *nest = q->last_nest;
+    if (launches) *launches = kCafLaunches;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_fetch(crsdr_caf *q, float *chi, float *map, float *peak)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_fetch: NULL caf");
+    if (!q->submitted) return fail(CRSDR_ESTATE, "caf_fetch: nothing submitted");
+    HIP_TRY(hipSetDevice(q->device));
+    const size_t lines = (size_t)q->last_nest, cells = (size_t)q->nd * (size_t)q->nlags;
+    if (chi) HIP_TRY(hipMemcpyAsync(chi, q->chi.p, sizeof(float2) * lines * (size_t)q->nrows * cells, hipMemcpyDeviceToHost, q->last_stream));
+    if (map) HIP_TRY(hipMemcpyAsync(map, q->map.p, sizeof(float) * lines * cells, hipMemcpyDeviceToHost, q->last_stream));
+    if (peak) HIP_TRY(hipMemcpyAsync(peak, q->peak.p, sizeof(float) * lines * (size_t)(q->nrows + 1) * 6, hipMemcpyDeviceToHost, q->last_stream));
+    HIP_TRY(hipStreamSynchronize(q->last_stream));
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_device_buffers(crsdr_caf *q, void **chi, void **map, void **peak)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_device_buffers: NULL caf");
+    if (chi) *chi = q->chi;
+    if (map) *map = q->map;
+    if (peak) *peak = q->peak;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_ambiguity(float *chi, float *map, float *peak, const int8_t *matrix, int nrows, int blocksize, int seg, int nlags, int ref_row, int window, int guard,
+                               int mem_kind)
+{
+    if (!matrix || (!chi && !map && !peak)) return fail(CRSDR_EINVAL, "ambiguity: need matrix and at least one of chi, map, peak");
+    { const int rc_ = caf_args_ok("ambiguity", nrows, blocksize, 1, 1, seg, nlags, ref_row, window, guard); if (rc_) return rc_; }
+    OP_PROLOGUE_MEM("ambiguity", mem_kind);
+    const size_t nd = (size_t)(blocksize / (2 * seg)), cells = nd * (size_t)nlags, mb = (size_t)nrows * (size_t)blocksize;
+    const size_t cb = sizeof(float2) * (size_t)nrows * cells, pb = sizeof(float) * cells, kb = sizeof(float) * 6 * (size_t)(nrows + 1);
+    OpStage st(mem_kind);
+    const int8_t *d_m = (const int8_t *)st.in(0, matrix, mb, 4);
+    float2 *d_c = (float2 *)st.out(1, chi, cb, 8);
+    float *d_p = (float *)st.out(2, map, pb, 4);
+    float *d_k = (float *)st.out(3, peak, kb, 4);
+    if (st.rc) return st.rc;
+    if (st.misaligned) return fail(CRSDR_EINVAL, "ambiguity: device matrix, map and peak 4-byte, chi 8-byte aligned");
+    // (device memory and an output not asked for: the kernels write it all the same)
+    if (!d_c) { OP_RESERVE(1, cb); d_c = (float2 *)g_op.buf[1]; }
+    if (!d_p) { OP_RESERVE(2, pb); d_p = (float *)g_op.buf[2]; }
+    if (!d_k) { OP_RESERVE(3, kb); d_k = (float *)g_op.buf[3]; }
+    OP_RESERVE(4, sizeof(float2) * nd + sizeof(float) * nd);
+    float2 *tw = (float2 *)g_op.buf[4];
+    float *win = (float *)(tw + nd);
+    { const int rc_ = spectra_tables(0, (int)nd, window, tw, win); if (rc_) return rc_; }
+    { const int rc_ = caf_enqueue(0, d_m, mb, 0, 1, nrows, blocksize, 1, seg, nlags, ref_row, window, guard, tw, win, d_c, d_p, d_k); if (rc_) return rc_; }
+    st.back(chi, d_c, cb);
+    st.back(map, d_p, pb);
+    st.back(peak, d_k, kb);
+    return st.finish();
+}

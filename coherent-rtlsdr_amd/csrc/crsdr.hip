@@ -2370,3 +2370,9 @@ extern "C" int crsdr_refcancel(int8_t *out, float *coef, float *residual, int32_
 // ================================================================================================
 // Its kernels are named here for the first time, behind everything else: the existing kernels keep their places in the code object.
 #include "spectra_engine.hpp"
+
+// ================================================================================================
+// (vii) Range-Doppler maps of the packets against a chosen row (crsdr_caf, crsdr_ambiguity)
+// ================================================================================================
+// Behind the spectra, for the same reason.
+#include "caf_engine.hpp"

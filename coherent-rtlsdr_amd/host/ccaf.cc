@@ -1,0 +1,54 @@
+#include "ccaf.h"
+
+#include <cmath>
+#include <cstdio>
+
+namespace ccaf {
+
+static_assert(sizeof(peak_t) == 6 * sizeof(float), "peak_t is crsdr_caf's six floats");
+
+double peak_t::power_db() const { return power > 0.f ? 10.0 * std::log10((double)power) : -INFINITY; }
+double peak_t::ratio_db() const { return ratio > 0.f ? 10.0 * std::log10((double)ratio) : -INFINITY; }
+
+batch::batch(int nrows, int blocksize, int max_batch, int seg, int nlags, int ref_row, int window, int guard, int frames, int device)
+    : rows(nrows), bins(seg > 0 ? (frames > 0 ? frames : 1) * (blocksize / (2 * seg)) : 0), lags(nlags)
+{
+    crsdr_caf_desc desc = {};
+    desc.nrows = nrows; desc.blocksize = blocksize; desc.device = device; desc.max_batch = max_batch; desc.frames = frames; desc.seg = seg; desc.nlags = nlags;
+    desc.ref_row = ref_row; desc.window = window; desc.guard = guard;
+    if (crsdr_caf_create(&cf, &desc)) { std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error()); cf = nullptr; }
+}
+
+batch::~batch()
+{
+    if (cf) crsdr_caf_destroy(cf);
+}
+
+int batch::submit(crsdr_plan *plan)
+{
+    int rc = cf ? crsdr_caf_submit_plan(cf, plan) : CRSDR_ESTATE;
+    if (rc && cf) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::submit(const void *device_packets, size_t packet_stride, size_t matrix_offset, int nblocks, void *hip_stream)
+{
+    int rc = cf ? crsdr_caf_submit(cf, device_packets, packet_stride, matrix_offset, nblocks, hip_stream) : CRSDR_ESTATE;
+    if (rc && cf) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::fetch(bool want_chi, bool want_map)
+{
+    int nest = 0;
+    int rc = cf ? crsdr_caf_last_submit(cf, &nest, nullptr) : CRSDR_ESTATE;
+    if (!rc) {
+        const size_t cells = (size_t)nest * bins * lags;
+        chi.assign(want_chi ? 2 * cells * rows : 0, 0.f); map.assign(want_map ? cells : 0, 0.f); peak.assign((size_t)nest * (rows + 1), peak_t{});
+        rc = crsdr_caf_fetch(cf, want_chi ? chi.data() : nullptr, want_map ? map.data() : nullptr, &peak[0].lag);
+    }
+    if (!rc) nlines = nest;
+    if (rc && cf) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+}

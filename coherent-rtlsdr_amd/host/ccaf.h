@@ -1,0 +1,51 @@
+// ccaf -- range-Doppler maps of the packets: a small class over crsdr_caf (include/crsdr.h, section (w)), as cspectra::batch is over
+// crsdr_spectra.  Passive radar's front end, on the device and on the packets as published: every row against a reference row over
+// delay and Doppler, the array map, and where each map peaks.
+#ifndef CCAF_H
+#define CCAF_H
+#include <cstddef>
+#include <vector>
+
+#include "../../include/crsdr.h"
+
+namespace ccaf {
+
+// (lag, doppler, power, ratio, dlag, ddop) of one map, as crsdr_caf lays them out
+struct peak_t {
+    float lag, doppler, power, ratio, dlag, ddop;
+    double power_db() const;                         // of full scale, ((I + jQ) / 127)^2 = 1 against itself; -inf for 0
+    double ratio_db() const;                         // the peak above the mean of the searched cells; -inf for 0
+};
+
+// One line per `frames` consecutive packets of a submit: chi [nrows][nd][nlags] of every row against row ref_row over seg-sample
+// segments, the array map [nd][nlags], and nrows + 1 peaks (the rows', then the map's) searched outside |Doppler| < guard.
+class batch {
+    crsdr_caf *cf = nullptr;
+    int rows, bins, lags;
+
+public:
+    batch(int nrows, int blocksize, int max_batch, int seg, int nlags, int ref_row = 0, int window = CRSDR_WINDOW_RECT, int guard = 0, int frames = 1, int device = 0);
+    ~batch();
+    batch(const batch &) = delete;
+    batch &operator=(const batch &) = delete;
+    bool ok() const { return cf != nullptr; }
+    // the plan's last batch, behind it on the plan's stream; or packets anywhere on the device.  Asynchronous.
+    int submit(crsdr_plan *plan);
+    int submit(const void *device_packets, size_t packet_stride, size_t matrix_offset, int nblocks, void *hip_stream = nullptr);
+    // waits, and fills the peaks and what else is asked for
+    int fetch(bool want_chi = false, bool want_map = false);
+    int lines() const { return nlines; }
+    int nrows() const { return rows; }
+    int nd() const { return bins; }
+    int nlags() const { return lags; }
+    std::vector<float> chi;                          // [lines][nrows][nd][nlags][2]
+    std::vector<float> map;                          // [lines][nd][nlags]
+    std::vector<peak_t> peak;                        // [lines][nrows + 1]
+    // of line e: entry c < nrows is row c's peak, entry nrows the array map's
+    const peak_t &at(int e, int c) const { return peak[(size_t)e * (rows + 1) + c]; }
+
+private:
+    int nlines = 0;
+};
+}
+#endif

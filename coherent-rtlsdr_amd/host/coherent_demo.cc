@@ -17,6 +17,7 @@
 #include "cbeamformer.h"
 #include "ccoherent.h"
 #include "ccontrol.h"
+#include "ccaf.h"
 #include "cspectra.h"
 
 static int cdsp_selftest()
@@ -65,6 +66,7 @@ int main(int argc, char **argv)
     int sb_nfft = 0, sb_first = 0, sb_count = 1, sb_width = 1, sb_window = CRSDR_WINDOW_RECT;
     int sp_nfft = 0, sp_band_lo = 0, sp_band_hi = 0;
     bool sp_half = false;
+    int caf_seg = 0, caf_lags = 0, caf_ref = 0, caf_frames = 1, caf_guard = 0;
     bool engine_batches = false;
     int ranks = 1, rank = 0, device = 0;
     std::string idfile;
@@ -131,6 +133,15 @@ int main(int argc, char **argv)
             sp_half = colon != std::string::npos && s.substr(colon + 1) == "half";
             if (sp_nfft <= 0 || (colon != std::string::npos && !sp_half)) sp_nfft = -1;
         }
+        // with --bench: per batch, line and row the peak of the row's range-Doppler map against row REF (crsdr_caf) on the packets where the
+        // plan left them: SEG-sample segments, LAGS lags, --caf-frames packets a line, --window as for --subbands over slow time, --guard G
+        // to search outside |Doppler| < G.  One line per row and one for the array map: lag, Doppler bin, sub-cell offsets, power, ratio.
+        else if (a == "--caf" && i + 1 < argc) {
+            const int n = std::sscanf(argv[++i], "%d:%d:%d", &caf_seg, &caf_lags, &caf_ref);
+            if (n < 2 || caf_seg <= 0) caf_seg = -1;
+        }
+        else if (a == "--caf-frames") val(caf_frames);
+        else if (a == "--guard") val(caf_guard);
         else if (a == "--band" && i + 1 < argc) { if (std::sscanf(argv[++i], "%d:%d", &sp_band_lo, &sp_band_hi) != 2) sp_nfft = -1; }
         else if (a == "--window" && i + 1 < argc) {
             const std::string w = argv[++i];
@@ -503,15 +514,38 @@ int main(int argc, char **argv)
                                 (double)f[1], (double)f[2], (double)f[3], bin, db);
                 }
         };
+        // --bench --caf: ccaf::batch over crsdr_caf, behind every batch on the plan's stream like the spectra.  The synthetic channels are
+        // copies of the reference noise with the integer lag taken out: with --guard 0 every row peaks at lag 0, Doppler 0.
+        std::unique_ptr<ccaf::batch> caf;
+        if (caf_seg && !coherent.sharded()) {
+            if (caf_seg > 0) caf.reset(new ccaf::batch(1 + nsig, B, batch, caf_seg, caf_lags, caf_ref, sb_window, caf_guard, caf_frames));
+            if (!caf || !caf->ok()) { std::printf("caf: --caf SEG:LAGS[:REF] [--caf-frames F] [--guard G] [--window rect|hann] refused\nDEMO FAILED\n"); return 1; }
+        }
+        auto ambiguity = [&](int b) {
+            if (!caf || !ok) return;
+            ok = caf->submit(coherent.engine_plan()) == CRSDR_OK && caf->fetch() == CRSDR_OK;
+            if (!ok || !report) return;
+            for (int e = 0; e < caf->lines(); ++e)
+                for (int c = 0; c <= caf->nrows(); ++c) {
+                    const ccaf::peak_t &k = caf->at(e, c);
+                    char who[32];
+                    if (c < caf->nrows()) std::snprintf(who, sizeof who, "row %d", c);
+                    else std::snprintf(who, sizeof who, "map");
+                    std::printf("caf: batch %d line %d %s: lag %d%+.3f doppler %d%+.3f power %.2f dB ratio %.2f dB\n", b, e, who, (int)k.lag, (double)k.dlag, (int)k.doppler,
+                                (double)k.ddop, k.power_db(), k.ratio_db());
+                }
+        };
         auto run = [&](int n) {
             ok = ok && coherent.submit_batch(0, batch, fl);
             directions(0);
             alignment(0);
+            ambiguity(0);
             residual(0);
             for (int b = 1; b < n && ok; ++b) {
                 ok = ok && coherent.submit_batch(b & 1, batch, fl);       // upload of batch b overlaps the download of batch b - 1
                 directions(b);
                 alignment(b);
+                ambiguity(b);
                 residual(b);
                 ok = ok && coherent.collect_batch((b - 1) & 1);
             }

@@ -1018,6 +1018,97 @@ int crsdr_spectra_last_submit(crsdr_spectra *spectra, int *nest, int *launches);
 int crsdr_welch(float *psd, float *cross, float *align, const int8_t *matrix, int nrows, int blocksize, int nfft, int overlap, int window,
                 int band_lo, int band_hi, int mem_kind);
 
+/* ------------------------------------------------------------------------------------------
+ * (w) Range-Doppler maps of the packets against a chosen row: a fourth packet consumer (passive radar)
+ * ---------------------------------------------------------------------------------------- */
+
+/* Sections (iii) and (v) treat the rows as stationary: a direction, a spectrum, one residual delay per row.  This one takes one row as
+ * an illuminator's reference and correlates every row against it over delay AND Doppler (the cross-ambiguity function), on the device
+ * and on the packets AS PUBLISHED, behind the plan by stream order alone, as (v) does.  The complex value of one cell across the rows
+ * is the snapshot a per-target direction estimate needs.
+ *
+ * Input.  As in (v): a packet's matrix is [nrows][B] int8; row c holds L = B / 2 samples, used here as the INTEGERS X_c[n] = I + jQ.
+ * Parameters.  seg = Ls, nlags = R, ref_row = r (any row; row 0 is a row like every other), frames, window, guard.
+ * Segments.  A packet has J = L / Ls segments; segments never cross packets.  A line is `frames` consecutive packets; the slow-time
+ * index is k = t J + j < nd = frames J.
+ * Range stage, exact in int32 on the real and imaginary parts:
+ *     y_c[k][tau] = sum_{n < Ls} X_c[t][j Ls + n] conj(X_r[t][j Ls + n - tau]),   tau = 0 .. R - 1,   X_r[t][m] = 0 for m < 0
+ * The reference never reaches into the previous packet: only the first segment of a packet sees the zeros.  |y| <= 2^15 Ls <= 2^27,
+ * so it cannot overflow, with every byte -128 included.
+ * Doppler stage.  w is CRSDR_WINDOW_RECT or CRSDR_WINDOW_HANN (periodic) OVER k, as in crsdr_doa_set_subbands; the forward transform
+ * is that of crsdr_fft, in FFT bin order.  The integers are converted to fp32 with one rounding, multiplied by the fp32 window and
+ * transformed in fp32; the scale is applied once:
+ *     chi_c[d][tau] = 1 / (127^2 Ls sum_k w[k]) * sum_k w[k] y_c[k][tau] exp(-2 pi i d k / nd)     chi [nest][nrows][nd][R][2] float, tau fastest
+ * Array map.  map [nest][nd][R] float = sum_{c != r} |chi_c[d][tau]|^2, from the published fp32 chi in fp64, rounded once; the order of
+ * the sum is not pinned.
+ * Peaks.  peak [nest][nrows + 1][6] float.  Entry c < nrows is taken from P_c = re^2 + im^2 of the published fp32 chi, evaluated in
+ * fp64; entry nrows from the published map.  s(d) = d for d < nd / 2, else d - nd.  The searched set is S = {(d, tau): |s(d)| >= guard}:
+ * guard = 0 searches everything, guard = g cuts the zero-Doppler ridge of width 2 g - 1.  The six figures, each rounded once to fp32:
+ *     lag, doppler = tau*, s(d*)      the first maximum in the order of the linear index d R + tau
+ *     power        = P*
+ *     ratio        = P* / mean of P over S                                    0 if that mean is 0
+ *     dlag         = 0.5 (P- - P+) / (P- - 2 P* + P+) from the cells (d*, tau* -+ 1); 0 when tau* is 0 or R - 1, 0 when the denominator
+ *                    is >= 0; clamped to [-0.5, 0.5]
+ *     ddop         = the same formula from the cells (d* -+ 1 mod nd, tau*); 0 if either neighbour is outside S, 0 when the
+ *                    denominator is >= 0
+ * Where P* = 0 (every searched cell is zero) the position means nothing and all six figures are 0: an all-zero packet gives zeros
+ * everywhere, never a NaN.  (Parity: unpinned by the reference, which has no such client.)
+ * Bits.  Nothing in a line depends on the other lines or on nblocks: a line has the same bits wherever it sits in a batch, and
+ * crsdr_ambiguity launches the same kernels on the same arguments and equals the engine bit for bit.
+ *
+ * Limits, all CRSDR_EINVAL and all checked before a device is touched, by one function for the engine and the per-op call: seg a power
+ * of two in 16 .. 4096; blocksize a multiple of 2 seg (up to 2^22, as a plan's); nrows >= 2; 0 <= ref_row < nrows;
+ * 1 <= nlags <= min(seg, 1024); 1 <= frames <= max_batch <= 64 (0 = 1 for both); nd a power of two in 8 .. 4096;
+ * (max_batch / frames) * nrows * nd * nlags <= 2^24; a valid window; 0 <= guard <= nd / 2.
+ *
+ * Every buffer and table is made by crsdr_caf_create.  A submit is asynchronous on its stream: three kernel launches whatever the
+ * number of blocks, no allocation, no process-wide lock, nothing that waits for the device. */
+typedef struct crsdr_caf crsdr_caf;
+
+typedef struct crsdr_caf_desc {
+    int32_t nrows, blocksize; /* of the packets it reads (as in crsdr_plan_desc) */
+    int32_t device;
+    int32_t max_batch;        /* blocks per submit, 1..64 (0 = 1) */
+    int32_t frames;           /* consecutive blocks per line, 1..max_batch (0 = 1) */
+    int32_t seg;              /* samples per segment (fast time) */
+    int32_t nlags;            /* lags 0 .. nlags - 1 */
+    int32_t ref_row;          /* the row every row is correlated against */
+    int32_t window;           /* CRSDR_WINDOW_*, over slow time */
+    int32_t guard;            /* the peak search skips |Doppler| < guard */
+} crsdr_caf_desc;
+
+int crsdr_caf_create(crsdr_caf **caf, const crsdr_caf_desc *desc);
+int crsdr_caf_destroy(crsdr_caf *caf);
+
+/* nblocks packets on the object's device, packet t at device_packets + t * packet_stride, its matrix [nrows][blocksize] int8 at
+ * + matrix_offset (4-byte aligned, like packet_stride); 1 <= nblocks <= max_batch, nblocks % frames == 0.  Asynchronous on hip_stream
+ * (NULL = the object's own stream); the packets must stay valid until the work has run.  One submit at a time: the next one reuses
+ * the buffers of this one, so fetch (or order the streams) in between. */
+int crsdr_caf_submit(crsdr_caf *caf, const void *device_packets, size_t packet_stride, size_t matrix_offset, int nblocks, void *hip_stream);
+
+/* The plan's last submitted batch, where its packets are, on the plan's stream: ordered behind that batch by the stream alone.
+ * CRSDR_ESTATE for a plan with nothing submitted or with a slab bound (the matrix is then not in the packet); CRSDR_EINVAL for
+ * another geometry or device, or a batch that is not a multiple of `frames` or exceeds max_batch. */
+int crsdr_caf_submit_plan(crsdr_caf *caf, crsdr_plan *plan);
+
+/* Waits for the last submit and copies out what is asked for (any pointer may be NULL); nest = nblocks / frames.  chi, map and peak
+ * as laid out above.  CRSDR_ESTATE before the first submit. */
+int crsdr_caf_fetch(crsdr_caf *caf, float *chi, float *map, float *peak);
+
+/* Device addresses of the results ([max_batch / frames] lines each, laid out as above), for consumers on the same stream. */
+int crsdr_caf_device_buffers(crsdr_caf *caf, void **chi, void **map, void **peak);
+
+/* Of the last submit: the number of lines (what crsdr_caf_fetch will write) and the kernel launches it issued (the same for every
+ * nblocks).  Either pointer may be NULL.  CRSDR_ESTATE before the first submit. */
+int crsdr_caf_last_submit(crsdr_caf *caf, int *nest, int *launches);
+
+/* The per-op form on one packet's matrix [nrows][blocksize] (frames = 1, so nd = blocksize / (2 seg)): the same kernels on the same
+ * arguments, bit for bit.  chi [nrows][nd][nlags][2], map [nd][nlags], peak [nrows + 1][6]; any of the three may be NULL, not all.
+ * mem_kind: CRSDR_MEM_HOST (copied) or CRSDR_MEM_DEVICE (every pointer on the device; matrix, map and peak 4-byte, chi 8-byte
+ * aligned). */
+int crsdr_ambiguity(float *chi, float *map, float *peak, const int8_t *matrix, int nrows, int blocksize, int seg, int nlags, int ref_row,
+                    int window, int guard, int mem_kind);
+
 #ifdef __cplusplus
 }
 #endif

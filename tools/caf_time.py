@@ -1,0 +1,149 @@
+#!/usr/bin/env python3
+"""What a range-Doppler submit (crsdr_caf) adds behind a plan submit: (21 + 1) rows x blocksize 16384 at a batch of 64 blocks and
+(1024 + 1) rows at a batch of 4; seg 128 and 4 packets a line (nd = 256), Hann over slow time, guard 2.  The 22-row case computes 64
+lags; with 1025 rows one line of 256 x 64 cells is 2^14 cells over the engine's bound of 2^24, so that case computes 63.
+
+  plan       plan.submit of the batch + sync (digital mode, CRSDR_REFNOISE_ENABLED | CRSDR_NO_LAG: the phase path)
+  +caf       plan.submit + caf.submit_plan + a fetch of the peaks only (chi and map stay on the device)
+  caf        caf.submit on the packets the plan left + the same fetch: the three launches by themselves, the achieved bytes/s of the chi
+             store (8 bytes a cell) and the int8 complex multiply-adds per second of the range stage
+  +spectra   for scale: plan.submit + spectra.submit_plan (nfft 256, half-overlapping Hann segments) + a fetch of its figures
+  spectra    the spectra's three launches by themselves
+  host       what a user has without the engine: the batch's packets fetched to page-locked host memory
+  host+model that fetch and tests/caf_model.py (numpy, fp64) on ONE line of the batch -- measured once, not per round
+
+Every figure is the mean of --reps back-to-back rounds closed by one wait; --runs rounds alternate all variants in one session, medians
+and ranges are reported.  --json FILE keeps the record."""
+import argparse, importlib, json, os, statistics, sys, time
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+B, SEG, FRAMES, GUARD = 16384, 128, 4, 2
+SHAPES = {22: (64, 64), 1025: (4, 63)}           # nrows: (batch, lags)
+
+
+def _blocks(T, nrows, rng):
+    """T blocks on the host: every row carries the block's reference noise (at lag 0) and noise of its own"""
+    rows = np.empty((T, nrows, B), dtype=np.int8)
+    for t in range(T):
+        ref = rng.normal(0, 25, B).astype(np.float32)
+        own = rng.standard_normal((nrows, B), dtype=np.float32) * np.float32(6)
+        rows[t] = np.clip(np.rint(0.7 * ref + own), -128, 127)
+        rows[t, 0] = np.clip(np.rint(ref), -128, 127)
+    return rows
+
+
+def _mean(fn, wait, reps):
+    t0 = time.perf_counter()
+    for i in range(reps):
+        fn(i)
+    wait()
+    return (time.perf_counter() - t0) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, nargs="*", default=[22, 1025])
+    ap.add_argument("--runs", type=int, default=7)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--no-model", action="store_true", help="skip the numpy model on one line")
+    ap.add_argument("--json")
+    a = ap.parse_args()
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import torch
+    b = importlib.import_module("coherent-rtlsdr_amd.binding")
+    rng = np.random.default_rng(1)
+    out = {"blocksize": B, "seg": SEG, "frames": FRAMES, "runs": a.runs, "reps": a.reps, "shapes": []}
+    for nrows in a.rows:
+        T, lags = SHAPES.get(nrows, (FRAMES, 16))
+        nd = FRAMES * B // (2 * SEG)
+        d_in = torch.from_numpy(_blocks(T, nrows, rng).view(np.uint8).reshape(T, -1)).to(torch.device("cuda", 0))
+        torch.cuda.synchronize()
+        plan = b.Plan(nrows, B, b.MODE_DIGITAL, max_batch=T)
+        flags = b.REFNOISE_ENABLED | b.NO_LAG
+        submit = lambda i: plan.submit(d_in.data_ptr(), seq=i * T, flags=flags, nblocks=T, block_stride=nrows * B)
+        cf = b.Caf(nrows, B, SEG, lags, 0, b.WINDOW_HANN, GUARD, max_batch=T, frames=FRAMES)
+        sp = b.Spectra(nrows, B, 256, 1, b.WINDOW_HANN, band=(-25, 25), max_batch=T, frames=FRAMES)
+        pk = plan.device_buffers()["packet"]
+        host = b.PinnedArray((T, plan.packet_stride), np.int8)
+
+        def with_caf(i):
+            submit(i)
+            cf.submit_plan(plan)
+            cf.fetch(chi=False, map=False)
+
+        def caf_alone(i):
+            cf.submit(pk, plan.packet_stride, plan.matrix_offset, T)
+            cf.fetch(chi=False, map=False)
+
+        def with_spectra(i):
+            submit(i)
+            sp.submit_plan(plan)
+            sp.fetch(psd=False, cross=False)
+
+        def spectra_alone(i):
+            sp.submit(pk, plan.packet_stride, plan.matrix_offset, T)
+            sp.fetch(psd=False, cross=False)
+
+        def to_host(i):
+            plan.fetch_batch_async(packets=host.array, host_packet_stride=plan.packet_stride)
+            plan.fetch_wait()
+
+        variants = {
+            "plan": lambda: _mean(submit, plan.sync, a.reps),
+            "+caf": lambda: _mean(with_caf, plan.sync, a.reps),
+            "caf": lambda: _mean(caf_alone, lambda: None, a.reps),
+            "+spectra": lambda: _mean(with_spectra, plan.sync, a.reps),
+            "spectra": lambda: _mean(spectra_alone, lambda: None, a.reps),
+            "host": lambda: _mean(to_host, lambda: None, a.reps),
+        }
+        plan.submit(d_in.data_ptr(), seq=0, flags=b.REFNOISE_ENABLED, nblocks=T, block_stride=nrows * B)      # lags and phasors for the locked submits
+        plan.sync()
+        for fn in variants.values():             # warm-up: code objects, allocations
+            fn()
+        rec = {k: [] for k in variants}
+        for _ in range(a.runs):
+            for k, fn in variants.items():
+                rec[k].append(fn())
+        shape = {"nrows": nrows, "batch": T, "lags": lags, "nd": nd, "ms": {}}
+        base = statistics.median(rec["plan"])
+        cells = (T // FRAMES) * nrows * nd * lags
+        macs = T * nrows * (B // 2) * lags
+        for k, v in rec.items():
+            ms = [1e3 * x for x in v]
+            med = statistics.median(ms)
+            shape["ms"][k] = {"median": med, "min": min(ms), "max": max(ms)}
+            note = ""
+            if k.startswith("+"):
+                note = f"  (+{med - 1e3 * base:.3f} ms behind the plan)"
+            if k == "caf":
+                note = f"  ({8 * cells / (med * 1e-3) / 1e9:.1f} GB/s of chi stored, {macs / (med * 1e-3) / 1e12:.2f} T complex int8 MAC/s)"
+            if k == "host":
+                note = f"  ({T * plan.packet_stride / (med * 1e-3) / 1e9:.1f} GB/s)"
+            print(f"rows {nrows:5d} batch {T:2d} {k:>10}: {med:9.3f} ms ({min(ms):.3f} .. {max(ms):.3f}){note}")
+        if not a.no_model:
+            import caf_model as M
+            t0 = time.perf_counter()
+            to_host(0)
+            off = plan.matrix_offset
+            line = [host.array[t, off:off + nrows * B].reshape(nrows, B) for t in range(FRAMES)]
+            chi, _ = M.caf(line, SEG, lags, 0, M.WINDOW_HANN)
+            M.all_peaks(chi.astype(np.complex64), M.array_map(chi.astype(np.complex64), 0)[0], GUARD)
+            dt = 1e3 * (time.perf_counter() - t0)
+            shape["ms"]["host+model"] = {"median": dt, "min": dt, "max": dt}
+            print(f"rows {nrows:5d} batch {T:2d} host+model: {dt:9.1f} ms for ONE line of {T // FRAMES} (numpy, fp64)")
+        out["shapes"].append(shape)
+        cf.close()
+        sp.close()
+        host.close()
+        plan.close()
+        del d_in
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
