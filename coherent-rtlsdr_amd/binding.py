@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "crsdr_spectra_device_buffers", "crsdr_spectra_last_submit", "crsdr_welch",
     "crsdr_caf_create", "crsdr_caf_destroy", "crsdr_caf_submit", "crsdr_caf_submit_plan", "crsdr_caf_fetch",
     "crsdr_caf_device_buffers", "crsdr_caf_last_submit", "crsdr_ambiguity",
+    "crsdr_caf_set_cfar", "crsdr_caf_fetch_cfar", "crsdr_caf_cfar_device_buffers", "crsdr_cfar", "crsdr_cfar_alpha",
 ]
 REFCANCEL_SINGULAR, REFCANCEL_IDLE = 1, 2                     # status bit 0: the solve failed (g = 0); 2: the pass did not run
 REFCANCEL_MAX_TAPS = 9
@@ -110,6 +111,13 @@ class SpectraDesc(C.Structure):
 class CafDesc(C.Structure):
     _fields_ = [("nrows", C.c_int32), ("blocksize", C.c_int32), ("device", C.c_int32), ("max_batch", C.c_int32), ("frames", C.c_int32),
                 ("seg", C.c_int32), ("nlags", C.c_int32), ("ref_row", C.c_int32), ("window", C.c_int32), ("guard", C.c_int32)]
+
+
+class CfarDesc(C.Structure):
+    """crsdr_cfar_desc: guard (gd, gr) and training (td, tr) half-widths over Doppler and lag, the threshold factor, the fewest
+    training cells a detection needs, and K detections kept per map."""
+    _fields_ = [("gd", C.c_int32), ("gr", C.c_int32), ("td", C.c_int32), ("tr", C.c_int32), ("alpha", C.c_float), ("min_train", C.c_int32),
+                ("max_det", C.c_int32)]
 
 
 _lib = None
@@ -268,6 +276,12 @@ def lib():
         L.crsdr_caf_device_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.crsdr_caf_last_submit.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.crsdr_ambiguity.argtypes = [f32p, f32p, f32p, i8p] + [C.c_int] * 8
+    if hasattr(L, "crsdr_cfar"):                     # (likewise: an older build has no detector)
+        L.crsdr_caf_set_cfar.argtypes = [vp, C.POINTER(CfarDesc)]
+        L.crsdr_caf_fetch_cfar.argtypes = [vp, f32p, i32p, f32p]
+        L.crsdr_caf_cfar_device_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        L.crsdr_cfar.argtypes = [f32p, i32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CfarDesc), C.c_int]
+        L.crsdr_cfar_alpha.argtypes = [C.c_double, C.c_int, f32p]
     _lib = L
     return L
 
@@ -644,6 +658,35 @@ def ambiguity(matrix, seg, nlags, ref_row=0, window=WINDOW_RECT, guard=0):
     _check(lib().crsdr_ambiguity(_p(chi.view(np.float32), C.c_float), _p(mp, C.c_float), _p(pk, C.c_float), _p(m, C.c_int8), nrows, B, int(seg), int(nlags),
                                  int(ref_row), int(window), int(guard), MEM_HOST))
     return chi, mp, pk
+
+
+def cfar_desc(alpha, gd=1, gr=1, td=3, tr=4, min_train=1, max_det=16):
+    return CfarDesc(int(gd), int(gr), int(td), int(tr), float(alpha), int(min_train), int(max_det))
+
+
+def cfar_alpha(pfa, ntrain):
+    """crsdr_cfar_alpha: ntrain (pfa^(-1 / ntrain) - 1) as a float32, the cell-averaging factor of one row's map."""
+    a = C.c_float(0.0)
+    _check(lib().crsdr_cfar_alpha(float(pfa), int(ntrain), C.byref(a)))
+    return np.float32(a.value)
+
+
+def cfar(src, guard, desc):
+    """crsdr_cfar on ONE map: src [nd][R] float32 (a map) or complex64 (a chi) -> (det [K][8] float32 = lag, doppler, power, snr, noise,
+    dlag, ddop, ntrain; count).  The engine's detector (Caf.set_cfar) on one map, bit for bit."""
+    comps = 2 if np.iscomplexobj(src) else 1
+    a = np.ascontiguousarray(src, dtype=np.complex64 if comps == 2 else np.float32)
+    nd, R = a.shape
+    det, count = np.zeros((desc.max_det, 8), dtype=np.float32), np.zeros(1, dtype=np.int32)
+    _check(lib().crsdr_cfar(_p(det, C.c_float), _p(count, C.c_int32), _p(a.view(np.float32), C.c_float), comps, nd, R, int(guard), C.byref(desc), MEM_HOST))
+    return det, int(count[0])
+
+
+def cfar_device(det_ptr: int, count_ptr: int, src_ptr: int, comps, nd, R, guard, desc):
+    """crsdr_cfar with CRSDR_MEM_DEVICE: every pointer on the device."""
+    cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
+    _check(lib().crsdr_cfar(cast(det_ptr, C.c_float), cast(count_ptr, C.c_int32), cast(src_ptr, C.c_float), int(comps), int(nd), int(R), int(guard), C.byref(desc),
+                            MEM_DEVICE))
 
 
 def ambiguity_device(chi_ptr: int, map_ptr: int, peak_ptr: int, matrix_ptr: int, nrows, B, seg, nlags, ref_row, window, guard):
@@ -1324,6 +1367,25 @@ class Caf:
         ptrs = [C.c_void_p() for _ in range(3)]
         _check(lib().crsdr_caf_device_buffers(self._h, *[C.byref(p) for p in ptrs]))
         return dict(zip(("chi", "map", "peak"), [p.value for p in ptrs]))
+
+    def set_cfar(self, desc: "CfarDesc | None"):
+        """crsdr_caf_set_cfar: the CFAR detector behind every submit (None: off).  Between submits."""
+        _check(lib().crsdr_caf_set_cfar(self._h, None if desc is None else C.byref(desc)))
+        self.max_det = 0 if desc is None else int(desc.max_det)
+
+    def fetch_cfar(self, det=True, count=True, snap=True) -> dict:
+        """Waits for the last submit.  det [nest][nrows + 1][K][8], count [nest][nrows + 1] int32, snap [nest][K][nrows] complex64."""
+        n, K = self._last()[0], max(1, getattr(self, "max_det", 0))
+        d = np.zeros((n, self.nrows + 1, K, 8), dtype=np.float32) if det else None
+        c = np.zeros((n, self.nrows + 1), dtype=np.int32) if count else None
+        s = np.zeros((n, K, self.nrows), dtype=np.complex64) if snap else None
+        _check(lib().crsdr_caf_fetch_cfar(self._h, _p(d, C.c_float), _p(c, C.c_int32), _p(None if s is None else s.view(np.float32), C.c_float)))
+        return {k: v for k, v in (("det", d), ("count", c), ("snap", s)) if v is not None}
+
+    def cfar_device_buffers(self) -> dict:
+        ptrs = [C.c_void_p() for _ in range(3)]
+        _check(lib().crsdr_caf_cfar_device_buffers(self._h, *[C.byref(p) for p in ptrs]))
+        return dict(zip(("det", "count", "snap"), [p.value for p in ptrs]))
 
     def last_launches(self) -> int:
         return self._last()[1]

@@ -3,9 +3,12 @@
 // (w) Range-Doppler maps (crsdr_caf): per line of `frames` packets every row's cross-ambiguity function against row ref_row, the array
 //     map and the peak figures (caf.hpp, caf_peak.hpp).  Every buffer, the twiddle and window tables included, is made at create; a
 //     submit is three launches on one stream whatever the batch size (rows, map, peaks), no lock, no allocation, no synchronisation.
+//     With a detector set (crsdr_caf_set_cfar; caf_cfar.hpp, caf_cfar_kernels.hpp) two more: the tiles' candidates, and their merge into
+//     the detection lists and the array map's snapshots.  Its buffers are made by set_cfar, between submits.
 #pragma once
 
 #include "caf.hpp"
+#include "caf_cfar_kernels.hpp"
 
 // `launch` with LG = log2 nd, 3 .. 12
 #define CAF_DISPATCH(lg, launch)                                                    \
@@ -22,7 +25,7 @@
     default: { constexpr int LG = 12; launch; } break;                              \
     }
 
-constexpr int kCafLaunches = 3;
+constexpr int kCafLaunches = 3, kCafCfarLaunches = 2;
 constexpr long long kCafMaxCells = 1ll << 24;           // (max_batch / frames) * nrows * nd * nlags
 
 struct crsdr_caf {
@@ -30,8 +33,17 @@ struct crsdr_caf {
     int nrows = 0, B = 0, device = 0, max_batch = 1, frames = 1, seg = 0, nlags = 0, ref_row = 0, window = 0, guard = 0, nd = 0;
     DevBuf<float2> tw, chi;
     DevBuf<float> win, map, peak;
+    // crsdr_caf_set_cfar: on (false = off), the tiles' candidates [lines][nrows + 1][tiles][keep] and counts, and the results
+    struct Cfar {
+        bool on = false, submitted = false;
+        cfar::Params prm{};
+        int keep = 0;
+        DevBuf<cfar::Cand> slots;
+        DevBuf<int32_t> tcount, count;
+        DevBuf<float> det, snap;
+    } cf;
     hipStream_t last_stream = nullptr;
-    int last_nest = 0;
+    int last_nest = 0, last_launches = 0;
     bool submitted = false;
 };
 
@@ -74,6 +86,37 @@ static int caf_enqueue(hipStream_t S, const int8_t *packets, size_t packet_strid
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(caf::k_caf_peak, dim3((unsigned)(nrows + 1), (unsigned)nest), dim3(caf::CAF_THREADS), 0, S, (const float2 *)chi, (const float *)map, nrows, nd, nlags,
                        guard, peak);
+    HIP_TRY(hipGetLastError());
+    return CRSDR_OK;
+}
+
+// every limit of the detector of section (w), for crsdr_caf_set_cfar and crsdr_cfar
+static int cfar_args_ok(const char *who, int nd, const crsdr_cfar_desc *d, cfar::Params *prm)
+{
+    *prm = cfar::Params{d->gd, d->gr, d->td, d->tr, d->alpha, d->min_train, d->max_det};
+    switch (cfar::bad_limit(nd, *prm)) {
+    case 0: return CRSDR_OK;
+    case 1: return fail(CRSDR_EINVAL, "%s: gd, gr, td, tr = %d, %d, %d, %d (none negative)", who, d->gd, d->gr, d->td, d->tr);
+    case 2: return fail(CRSDR_EINVAL, "%s: gd + td = %d + %d (at most %d)", who, d->gd, d->td, cfar::MAX_HD);
+    case 3: return fail(CRSDR_EINVAL, "%s: gr + tr = %d + %d (at most %d)", who, d->gr, d->tr, cfar::MAX_HR);
+    case 4: return fail(CRSDR_EINVAL, "%s: td + tr = 0 (no training cells)", who);
+    case 5: return fail(CRSDR_EINVAL, "%s: 2 (gd + td) + 1 = %d exceeds nd = %d", who, 2 * (d->gd + d->td) + 1, nd);
+    case 6: return fail(CRSDR_EINVAL, "%s: alpha = %g (finite and greater than 0)", who, (double)d->alpha);
+    case 7: return fail(CRSDR_EINVAL, "%s: min_train = %d (at least 1)", who, d->min_train);
+    default: return fail(CRSDR_EINVAL, "%s: max_det = %d (1..%d)", who, d->max_det, cfar::MAX_DET);
+    }
+}
+
+// the detector's two launches, for the object and for crsdr_cfar: the same kernels on the same arguments, so the same bits
+static int cfar_enqueue(hipStream_t S, const float2 *chi, const float *map, int nest, int nrows, int entries, int nd, int R, int guard, const cfar::Params &prm, int keep,
+                        cfar::Cand *slots, int32_t *tcount, float *det, int32_t *count, float *snap)
+{
+    const int tiles = cfar::tiles_of(nd, R);
+    hipLaunchKernelGGL(cfar::k_caf_cfar, dim3((unsigned)(entries * tiles), (unsigned)nest), dim3(cfar::THREADS), 0, S, chi, map, nrows, entries, nd, R, guard, prm, keep, slots,
+                       tcount);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cfar::k_caf_cfar_merge, dim3((unsigned)entries, (unsigned)nest), dim3(cfar::THREADS), 0, S, chi, map, nrows, entries, nd, R, guard, prm, keep,
+                       (const cfar::Cand *)slots, (const int32_t *)tcount, det, count, snap);
     HIP_TRY(hipGetLastError());
     return CRSDR_OK;
 }
@@ -130,7 +173,12 @@ static int caf_launch(crsdr_caf *q, const int8_t *packets, size_t packet_stride,
     const int rc = caf_enqueue(S, packets, packet_stride, matrix_offset, nblocks, q->nrows, q->B, q->frames, q->seg, q->nlags, q->ref_row, q->window, q->guard, q->tw, q->win,
                                q->chi, q->map, q->peak);
     if (rc) return rc;
-    q->last_stream = S; q->last_nest = nblocks / q->frames; q->submitted = true;
+    q->last_stream = S; q->last_nest = nblocks / q->frames; q->submitted = true; q->last_launches = kCafLaunches;
+    if (!q->cf.on) return CRSDR_OK;
+    const int rc2 = cfar_enqueue(S, q->chi, q->map, q->last_nest, q->nrows, q->nrows + 1, q->nd, q->nlags, q->guard, q->cf.prm, q->cf.keep, q->cf.slots, q->cf.tcount,
+                                 q->cf.det, q->cf.count, q->cf.snap);
+    if (rc2) return rc2;
+    q->cf.submitted = true; q->last_launches += kCafCfarLaunches;
     return CRSDR_OK;
 }
 
@@ -166,7 +214,7 @@ extern "C" int crsdr_caf_last_submit(crsdr_caf *q, int *nest, int *launches)
     if (!q) return fail(CRSDR_EINVAL, "caf_last_submit: NULL caf");
     if (!q->submitted) return fail(CRSDR_ESTATE, "caf_last_submit: nothing submitted");
     if (nest) *nest = q->last_nest;
-    if (launches) *launches = kCafLaunches;
+    if (launches) *launches = q->last_launches;
     return CRSDR_OK;
 }
 
@@ -190,6 +238,93 @@ extern "C" int crsdr_caf_device_buffers(crsdr_caf *q, void **chi, void **map, vo
     if (map) *map = q->map;
     if (peak) *peak = q->peak;
     return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_set_cfar(crsdr_caf *q, const crsdr_cfar_desc *desc)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_set_cfar: NULL caf");
+    cfar::Params prm{};
+    if (desc) { const int rc_ = cfar_args_ok("caf_set_cfar", q->nd, desc, &prm); if (rc_) return rc_; }
+    HIP_TRY(hipSetDevice(q->device));
+    if (q->submitted) HIP_TRY(hipDeviceSynchronize());      // the last submit may still write the buffers let go here (its stream may be the caller's, and gone)
+    q->cf = crsdr_caf::Cfar();
+    if (!desc) return CRSDR_OK;
+    const size_t maps = (size_t)(q->max_batch / q->frames) * (size_t)(q->nrows + 1), lines = (size_t)(q->max_batch / q->frames), K = (size_t)prm.max_det;
+    const size_t tiles = (size_t)cfar::tiles_of(q->nd, q->nlags);
+    const int keep = cfar::tile_keep(prm.max_det, q->nd, q->nlags);
+    int r = CRSDR_OK;
+    if ((r = q->cf.slots.alloc(maps * tiles * (size_t)keep)) || (r = q->cf.tcount.alloc(maps * tiles)) || (r = q->cf.count.alloc(maps)) || (r = q->cf.det.alloc(maps * K * 8)) ||
+        (r = q->cf.snap.alloc(lines * K * (size_t)q->nrows * 2))) {
+        q->cf = crsdr_caf::Cfar();
+        return r;
+    }
+    q->cf.prm = prm; q->cf.keep = keep; q->cf.on = true;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_fetch_cfar(crsdr_caf *q, float *det, int32_t *count, float *snap)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_fetch_cfar: NULL caf");
+    if (!q->cf.on) return fail(CRSDR_ESTATE, "caf_fetch_cfar: no detector set (crsdr_caf_set_cfar)");
+    if (!q->cf.submitted) return fail(CRSDR_ESTATE, "caf_fetch_cfar: nothing submitted since the detector was set");
+    HIP_TRY(hipSetDevice(q->device));
+    const size_t lines = (size_t)q->last_nest, maps = lines * (size_t)(q->nrows + 1), K = (size_t)q->cf.prm.max_det;
+    if (det) HIP_TRY(hipMemcpyAsync(det, q->cf.det.p, sizeof(float) * maps * K * 8, hipMemcpyDeviceToHost, q->last_stream));
+    if (count) HIP_TRY(hipMemcpyAsync(count, q->cf.count.p, sizeof(int32_t) * maps, hipMemcpyDeviceToHost, q->last_stream));
+    if (snap) HIP_TRY(hipMemcpyAsync(snap, q->cf.snap.p, sizeof(float) * lines * K * (size_t)q->nrows * 2, hipMemcpyDeviceToHost, q->last_stream));
+    HIP_TRY(hipStreamSynchronize(q->last_stream));
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_cfar_device_buffers(crsdr_caf *q, void **det, void **count, void **snap)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_cfar_device_buffers: NULL caf");
+    if (!q->cf.on) return fail(CRSDR_ESTATE, "caf_cfar_device_buffers: no detector set (crsdr_caf_set_cfar)");
+    if (det) *det = q->cf.det;
+    if (count) *count = q->cf.count;
+    if (snap) *snap = q->cf.snap;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_cfar_alpha(double pfa, int ntrain, float *alpha)
+{
+    if (!alpha) return fail(CRSDR_EINVAL, "cfar_alpha: NULL alpha");
+    if (!(pfa > 0.0 && pfa < 1.0)) return fail(CRSDR_EINVAL, "cfar_alpha: pfa = %g (inside (0, 1))", pfa);
+    if (ntrain < 1) return fail(CRSDR_EINVAL, "cfar_alpha: ntrain = %d (at least 1)", ntrain);
+    *alpha = (float)((double)ntrain * (pow(pfa, -1.0 / (double)ntrain) - 1.0));
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_cfar(float *det, int32_t *count, const float *src, int comps, int nd, int R, int guard, const crsdr_cfar_desc *desc, int mem_kind)
+{
+    if (!src || !desc || (!det && !count)) return fail(CRSDR_EINVAL, "cfar: need src, a descriptor and at least one of det, count");
+    if (comps != 1 && comps != 2) return fail(CRSDR_EINVAL, "cfar: comps = %d (1: a map, 2: a chi)", comps);
+    const int lgd = nd >= 1 && nd <= (1 << caf::CAF_MAX_LOG2) ? ilog2_exact(nd) : -1;
+    if (lgd < caf::CAF_MIN_LOG2) return fail(CRSDR_EINVAL, "cfar: nd = %d (a power of two in [8, 4096])", nd);
+    if (R < 1 || R > caf::CAF_MAX_LAGS) return fail(CRSDR_EINVAL, "cfar: R = %d (1..%d)", R, caf::CAF_MAX_LAGS);
+    if (guard < 0 || guard > nd / 2) return fail(CRSDR_EINVAL, "cfar: guard = %d (0..nd / 2 = %d)", guard, nd / 2);
+    cfar::Params prm{};
+    { const int rc_ = cfar_args_ok("cfar", nd, desc, &prm); if (rc_) return rc_; }
+    OP_PROLOGUE_MEM("cfar", mem_kind);
+    const size_t cells = (size_t)nd * (size_t)R, K = (size_t)prm.max_det, tiles = (size_t)cfar::tiles_of(nd, R);
+    const size_t sb = sizeof(float) * cells * (size_t)comps, db = sizeof(float) * K * 8, nb = sizeof(int32_t);
+    const int keep = cfar::tile_keep(prm.max_det, nd, R);
+    OpStage st(mem_kind);
+    const float *d_s = (const float *)st.in(0, src, sb, comps == 2 ? 8 : 4);
+    float *d_d = (float *)st.out(1, det, db, 4);
+    int32_t *d_n = (int32_t *)st.out(2, count, nb, 4);
+    if (st.rc) return st.rc;
+    if (st.misaligned) return fail(CRSDR_EINVAL, "cfar: device det, count and a map 4-byte, a chi 8-byte aligned");
+    // (device memory and an output not asked for: the kernels write it all the same)
+    if (!d_d) { OP_RESERVE(1, db); d_d = (float *)g_op.buf[1]; }
+    if (!d_n) { OP_RESERVE(2, nb); d_n = (int32_t *)g_op.buf[2]; }
+    OP_RESERVE(3, sizeof(cfar::Cand) * tiles * (size_t)keep);
+    OP_RESERVE(4, sizeof(int32_t) * tiles);
+    { const int rc_ = cfar_enqueue(0, comps == 2 ? (const float2 *)d_s : nullptr, comps == 1 ? d_s : nullptr, 1, comps == 2 ? 1 : 0, 1, nd, R, guard, prm, keep,
+                                   (cfar::Cand *)g_op.buf[3], (int32_t *)g_op.buf[4], d_d, d_n, nullptr); if (rc_) return rc_; }
+    st.back(det, d_d, db);
+    st.back(count, d_n, nb);
+    return st.finish();
 }
 
 extern "C" int crsdr_ambiguity(float *chi, float *map, float *peak, const int8_t *matrix, int nrows, int blocksize, int seg, int nlags, int ref_row, int window, int guard,

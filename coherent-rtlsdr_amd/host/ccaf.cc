@@ -7,6 +7,9 @@ namespace ccaf {
 
 static_assert(sizeof(peak_t) == 6 * sizeof(float), "peak_t is crsdr_caf's six floats");
 
+static_assert(sizeof(det_t) == 8 * sizeof(float), "det_t is the detector's eight floats");
+
+double det_t::snr_db() const { return snr > 0.f ? 10.0 * std::log10((double)snr) : -INFINITY; }
 double peak_t::power_db() const { return power > 0.f ? 10.0 * std::log10((double)power) : -INFINITY; }
 double peak_t::ratio_db() const { return ratio > 0.f ? 10.0 * std::log10((double)ratio) : -INFINITY; }
 
@@ -35,6 +38,28 @@ int batch::submit(const void *device_packets, size_t packet_stride, size_t matri
 {
     int rc = cf ? crsdr_caf_submit(cf, device_packets, packet_stride, matrix_offset, nblocks, hip_stream) : CRSDR_ESTATE;
     if (rc && cf) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::set_cfar(const crsdr_cfar_desc *desc)
+{
+    int rc = cf ? crsdr_caf_set_cfar(cf, desc) : CRSDR_ESTATE;
+    if (!rc) { kdet = desc ? desc->max_det : 0; det.clear(); count.clear(); snap.clear(); }
+    if (rc && cf) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::fetch_cfar(bool want_snap)
+{
+    int nest = 0;
+    int rc = !cf || !kdet ? CRSDR_ESTATE : crsdr_caf_last_submit(cf, &nest, nullptr);
+    if (!rc) {
+        const size_t maps = (size_t)nest * (rows + 1);
+        det.assign(maps * kdet, det_t{}); count.assign(maps, 0); snap.assign(want_snap ? (size_t)nest * kdet * rows * 2 : 0, 0.f);
+        rc = crsdr_caf_fetch_cfar(cf, &det[0].lag, count.data(), want_snap ? snap.data() : nullptr);
+    }
+    if (!rc) nlines = nest;
+    if (rc && cf && kdet) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
     return rc;
 }
 

@@ -4,6 +4,7 @@
 #ifndef CCAF_H
 #define CCAF_H
 #include <cstddef>
+#include <cstdint>
 #include <vector>
 
 #include "../../include/crsdr.h"
@@ -17,11 +18,17 @@ struct peak_t {
     double ratio_db() const;                         // the peak above the mean of the searched cells; -inf for 0
 };
 
+// (lag, doppler, power, snr, noise, dlag, ddop, ntrain) of one detection, as crsdr_caf's detector lays them out
+struct det_t {
+    float lag, doppler, power, snr, noise, dlag, ddop, ntrain;
+    double snr_db() const;                           // the cell above its training cells' mean; -inf for 0
+};
+
 // One line per `frames` consecutive packets of a submit: chi [nrows][nd][nlags] of every row against row ref_row over seg-sample
 // segments, the array map [nd][nlags], and nrows + 1 peaks (the rows', then the map's) searched outside |Doppler| < guard.
 class batch {
     crsdr_caf *cf = nullptr;
-    int rows, bins, lags;
+    int rows, bins, lags, kdet = 0;
 
 public:
     batch(int nrows, int blocksize, int max_batch, int seg, int nlags, int ref_row = 0, int window = CRSDR_WINDOW_RECT, int guard = 0, int frames = 1, int device = 0);
@@ -34,6 +41,11 @@ public:
     int submit(const void *device_packets, size_t packet_stride, size_t matrix_offset, int nblocks, void *hip_stream = nullptr);
     // waits, and fills the peaks and what else is asked for
     int fetch(bool want_chi = false, bool want_map = false);
+    // the CFAR detector behind every later submit (crsdr_caf_set_cfar; NULL: off).  Between submits: it waits for the last one.
+    int set_cfar(const crsdr_cfar_desc *desc);
+    // waits, and fills count and det, and snap if asked for; CRSDR_ESTATE with the detector off
+    int fetch_cfar(bool want_snap = true);
+    int max_det() const { return kdet; }
     int lines() const { return nlines; }
     int nrows() const { return rows; }
     int nd() const { return bins; }
@@ -43,6 +55,14 @@ public:
     std::vector<peak_t> peak;                        // [lines][nrows + 1]
     // of line e: entry c < nrows is row c's peak, entry nrows the array map's
     const peak_t &at(int e, int c) const { return peak[(size_t)e * (rows + 1) + c]; }
+    std::vector<det_t> det;                          // [lines][nrows + 1][max_det]: the strongest first, zeros behind the last
+    std::vector<int32_t> count;                      // [lines][nrows + 1]: detected cells, which may be more than max_det
+    std::vector<float> snap;                         // [lines][max_det][nrows][2]: chi of every row at the array map's detections
+    // of line e and entry c: the number of detections held (at most max_det), and detection k of them
+    int held(int e, int c) const { const int n = count[(size_t)e * (rows + 1) + c]; return n < kdet ? n : kdet; }
+    const det_t &detection(int e, int c, int k) const { return det[((size_t)e * (rows + 1) + c) * kdet + k]; }
+    // of line e: row c's chi (re, im) at the array map's detection k
+    const float *snapshot(int e, int k, int c) const { return &snap[2 * (((size_t)e * kdet + k) * rows + c)]; }
 
 private:
     int nlines = 0;

@@ -67,6 +67,9 @@ int main(int argc, char **argv)
     int sp_nfft = 0, sp_band_lo = 0, sp_band_hi = 0;
     bool sp_half = false;
     int caf_seg = 0, caf_lags = 0, caf_ref = 0, caf_frames = 1, caf_guard = 0;
+    bool cfar_on = false;
+    double cfar_db = 0.0;
+    crsdr_cfar_desc cfar = {1, 1, 3, 4, 0.f, 1, 16};
     bool engine_batches = false;
     int ranks = 1, rank = 0, device = 0;
     std::string idfile;
@@ -141,6 +144,15 @@ int main(int argc, char **argv)
             if (n < 2 || caf_seg <= 0) caf_seg = -1;
         }
         else if (a == "--caf-frames") val(caf_frames);
+        // with --caf: a cell-averaging CFAR detector over every map (crsdr_caf_set_cfar): a cell is detected SNR_DB above the mean of its
+        // training cells, GD, GR guard and TD, TR training half-widths over Doppler and lag (default 1:1:3:4), --max-det K detections kept
+        // per map.  One line per detection of the array map: lag, Doppler bin, sub-cell offsets, snr, and the map's count.
+        else if (a == "--cfar" && i + 1 < argc) {
+            const int n = std::sscanf(argv[++i], "%lf:%d:%d:%d:%d", &cfar_db, &cfar.gd, &cfar.gr, &cfar.td, &cfar.tr);
+            cfar_on = true;
+            cfar.alpha = n == 1 || n == 5 ? (float)std::pow(10.0, cfar_db / 10.0) : -1.f;      // (refused below with the rest)
+        }
+        else if (a == "--max-det") val(cfar.max_det);
         else if (a == "--guard") val(caf_guard);
         else if (a == "--band" && i + 1 < argc) { if (std::sscanf(argv[++i], "%d:%d", &sp_band_lo, &sp_band_hi) != 2) sp_nfft = -1; }
         else if (a == "--window" && i + 1 < argc) {
@@ -520,11 +532,18 @@ int main(int argc, char **argv)
         if (caf_seg && !coherent.sharded()) {
             if (caf_seg > 0) caf.reset(new ccaf::batch(1 + nsig, B, batch, caf_seg, caf_lags, caf_ref, sb_window, caf_guard, caf_frames));
             if (!caf || !caf->ok()) { std::printf("caf: --caf SEG:LAGS[:REF] [--caf-frames F] [--guard G] [--window rect|hann] refused\nDEMO FAILED\n"); return 1; }
+            if (cfar_on && caf->set_cfar(&cfar)) { std::printf("cfar: --cfar SNR_DB[:GD:GR:TD:TR] [--max-det K] refused\nDEMO FAILED\n"); return 1; }
         }
         auto ambiguity = [&](int b) {
             if (!caf || !ok) return;
-            ok = caf->submit(coherent.engine_plan()) == CRSDR_OK && caf->fetch() == CRSDR_OK;
+            ok = caf->submit(coherent.engine_plan()) == CRSDR_OK && caf->fetch() == CRSDR_OK && (!cfar_on || caf->fetch_cfar() == CRSDR_OK);
             if (!ok || !report) return;
+            for (int e = 0; cfar_on && e < caf->lines(); ++e)
+                for (int k = 0; k < caf->held(e, caf->nrows()); ++k) {
+                    const ccaf::det_t &d = caf->detection(e, caf->nrows(), k);
+                    std::printf("cfar: batch %d line %d det %d of %d: lag %d%+.3f doppler %d%+.3f snr %.2f dB\n", b, e, k, (int)caf->count[(size_t)e * (caf->nrows() + 1) + caf->nrows()],
+                                (int)d.lag, (double)d.dlag, (int)d.doppler, (double)d.ddop, d.snr_db());
+                }
             for (int e = 0; e < caf->lines(); ++e)
                 for (int c = 0; c <= caf->nrows(); ++c) {
                     const ccaf::peak_t &k = caf->at(e, c);

@@ -1109,6 +1109,67 @@ int crsdr_caf_last_submit(crsdr_caf *caf, int *nest, int *launches);
 int crsdr_ambiguity(float *chi, float *map, float *peak, const int8_t *matrix, int nrows, int blocksize, int seg, int nlags, int ref_row,
                     int window, int guard, int mem_kind);
 
+/* Detections.  The peak figures name the largest cell of a map whether or not it is a target, and a map holds any number of targets or
+ * none.  A cell-averaging CFAR (constant false-alarm rate) detector over every map of a line, on the device, leaves a short detection
+ * list per map and, for the array map's detections, the complex snapshot across the rows: a few hundred bytes per line for the host in
+ * place of chi.  It is off until crsdr_caf_set_cfar; off, a submit is the same three launches and the same bits.
+ *
+ * A map P [nd][R] is the published array map, or re re + im im of a row's published fp32 chi evaluated in fp64 (two products of
+ * converted floats, exact in fp64, and one addition: the same bits with or without contraction).  s(d), S, guard and the linear index
+ * i = d R + tau are those of the peaks above.  Hd = gd + td, Hr = gr + tr.
+ * Training set of a cell (d, tau) of S: the cells (d + a mod nd, tau + b) with
+ *     |a| <= Hd and |b| <= Hr;   NOT (|a| <= gd and |b| <= gr);   0 <= tau + b < R;   the Doppler bin in S.
+ * Doppler wraps and lag does not; the zero-Doppler ridge that guard cuts out of the search is cut out of the training cells as well.
+ * N is the size of the set, Z the fp64 sum of P over it (the order is not pinned; it is never formed by subtracting a guard block from
+ * a full box, which would carry the cancelled target's rounding error).
+ * A cell of S is detected if and only if
+ *     N >= min_train;   Z > 0;   P > t,  noise = Z / (double)N,  t = (double)alpha * noise  (one division, one multiplication, so);
+ *     it is the maximum of its 3 x 3 neighbourhood: neighbour Doppler wraps, neighbours outside 0 .. R - 1 or outside S are ignored,
+ *     and against a neighbour q the test is P > P_q, or P == P_q with i < i_q.
+ * One target spread over a Hann main lobe gives one detection, a plateau its first cell, an all-zero map none and no NaN.
+ * Outputs per (line, entry), entries 0 .. nrows as peak has them, K = max_det:
+ *     count [nest][nrows + 1] int32      the number of detected cells; may exceed K
+ *     det   [nest][nrows + 1][K][8]      the K detections of largest P, ties by smaller i, in that order; unused slots zero.  A detection is
+ *                                        (lag, doppler = s(d), power = P, snr = P / noise, noise, dlag, ddop, ntrain = N), each rounded once
+ *                                        to fp32; dlag and ddop are the two parabolas of the peaks, with the same edge rules
+ *     snap  [nest][K][nrows][2]          for the array map's detections (entry nrows) only: chi_c[d*][tau*] of every row, the reference
+ *                                        row included, copied bit for bit; unused slots zero
+ * Bits.  Nothing depends on the order in which workgroups run: the same input gives the same bytes, a line has the same bits wherever
+ * it sits in a batch, and crsdr_cfar launches the same kernels on the same arguments.
+ * Limits, all CRSDR_EINVAL and all checked before a device is touched, by one function for the engine and the per-op call:
+ * gd, gr, td, tr >= 0; Hd <= 8; Hr <= 16; td + tr >= 1; 2 Hd + 1 <= nd; alpha finite and > 0; min_train >= 1; 1 <= max_det <= 64. */
+typedef struct crsdr_cfar_desc {
+    int32_t gd, gr;           /* guard half-widths over Doppler and lag */
+    int32_t td, tr;           /* training half-widths beyond the guard */
+    float alpha;              /* threshold = alpha * the training cells' mean */
+    int32_t min_train;        /* a cell with fewer training cells is never detected */
+    int32_t max_det;          /* K: detections kept per map, 1..64 */
+} crsdr_cfar_desc;
+
+/* Sets the detector (NULL: off).  Between submits only: it waits for the last one and allocates here, never in a submit; what a
+ * fetch_cfar would have returned is gone.  With it on a submit is five launches whatever the number of blocks (crsdr_caf_last_submit). */
+int crsdr_caf_set_cfar(crsdr_caf *caf, const crsdr_cfar_desc *desc);
+
+/* Waits for the last submit and copies out what is asked for (any pointer may be NULL), laid out as above.  CRSDR_ESTATE with the
+ * detector off, or before the first submit since it was set. */
+int crsdr_caf_fetch_cfar(crsdr_caf *caf, float *det, int32_t *count, float *snap);
+
+/* Device addresses of det, count and snap ([max_batch / frames] lines each), for consumers on the same stream -- a direction per
+ * detection from snap, say.  They change with every crsdr_caf_set_cfar.  CRSDR_ESTATE with the detector off. */
+int crsdr_caf_cfar_device_buffers(crsdr_caf *caf, void **det, void **count, void **snap);
+
+/* The per-op form on ONE map: comps = 1 reads a map [nd][R], comps = 2 a chi [nd][R][2].  det [K][8], count [1]; either may be NULL, not
+ * both.  nd a power of two in 8 .. 4096, 1 <= R <= 1024, 0 <= guard <= nd / 2.  The same two kernels on the same arguments, bit for bit.
+ * mem_kind: CRSDR_MEM_HOST (copied) or CRSDR_MEM_DEVICE (every pointer on the device; det, count and a map 4-byte, a chi 8-byte
+ * aligned). */
+int crsdr_cfar(float *det, int32_t *count, const float *src, int comps, int nd, int R, int guard, const crsdr_cfar_desc *desc, int mem_kind);
+
+/* Host only: alpha = N (pfa^(-1 / N) - 1), the cell-averaging factor that gives a false-alarm probability pfa per cell on ONE row's
+ * map under exponentially distributed noise power and N = ntrain training cells.  The array map is a sum of nrows - 1 such terms
+ * (a gamma variate, not an exponential one): it takes a caller's own alpha.  Cells near the lag edges, or near the guard with one
+ * set, train on fewer than ntrain cells and so run at a somewhat higher rate.  CRSDR_EINVAL for pfa outside (0, 1) or ntrain < 1. */
+int crsdr_cfar_alpha(double pfa, int ntrain, float *alpha);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,12 @@ lags; with 1025 rows one line of 256 x 64 cells is 2^14 cells over the engine's 
   spectra    the spectra's three launches by themselves
   host       what a user has without the engine: the batch's packets fetched to page-locked host memory
   host+model that fetch and tests/caf_model.py (numpy, fp64) on ONE line of the batch -- measured once, not per round
+with --cfar, on a second engine with the CFAR detector set (crsdr_caf_set_cfar: guard 1 x 1, training 3 x 4, alpha for 1e-6 at 90 cells,
+16 detections a map):
+  caf+cfar   as caf with the detector's two launches behind the three, + a fetch of det, count and snap as well
+  get chi    the fetch of chi (pageable host memory, as Caf.fetch returns it) that the detection lists stand in for
+  get cfar   the fetch of det + count + snap
+and the bytes of P the detector reads per submit (8 a cell of chi, 4 a cell of map), to set against its kernels' time from a profiler.
 
 Every figure is the mean of --reps back-to-back rounds closed by one wait; --runs rounds alternate all variants in one session, medians
 and ranges are reported.  --json FILE keeps the record."""
@@ -47,6 +53,7 @@ def main():
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-model", action="store_true", help="skip the numpy model on one line")
+    ap.add_argument("--cfar", action="store_true", help="add the CFAR detector's variants")
     ap.add_argument("--json")
     a = ap.parse_args()
     sys.path.insert(0, ROOT)
@@ -90,6 +97,16 @@ def main():
             plan.fetch_batch_async(packets=host.array, host_packet_stride=plan.packet_stride)
             plan.fetch_wait()
 
+        cfd = None
+        if a.cfar:
+            cfd = b.Caf(nrows, B, SEG, lags, 0, b.WINDOW_HANN, GUARD, max_batch=T, frames=FRAMES)
+            cfd.set_cfar(b.cfar_desc(alpha=b.cfar_alpha(1e-6, 90), gd=1, gr=1, td=3, tr=4, max_det=16))
+
+        def caf_cfar(i):
+            cfd.submit(pk, plan.packet_stride, plan.matrix_offset, T)
+            cfd.fetch(chi=False, map=False)
+            cfd.fetch_cfar()
+
         variants = {
             "plan": lambda: _mean(submit, plan.sync, a.reps),
             "+caf": lambda: _mean(with_caf, plan.sync, a.reps),
@@ -98,6 +115,10 @@ def main():
             "spectra": lambda: _mean(spectra_alone, lambda: None, a.reps),
             "host": lambda: _mean(to_host, lambda: None, a.reps),
         }
+        if a.cfar:
+            variants["caf+cfar"] = lambda: _mean(caf_cfar, lambda: None, a.reps)
+            variants["get chi"] = lambda: _mean(lambda i: cf.fetch(map=False, peak=False), lambda: None, a.reps)
+            variants["get cfar"] = lambda: _mean(lambda i: cfd.fetch_cfar(), lambda: None, a.reps)
         plan.submit(d_in.data_ptr(), seq=0, flags=b.REFNOISE_ENABLED, nblocks=T, block_stride=nrows * B)      # lags and phasors for the locked submits
         plan.sync()
         for fn in variants.values():             # warm-up: code objects, allocations
@@ -119,6 +140,12 @@ def main():
                 note = f"  (+{med - 1e3 * base:.3f} ms behind the plan)"
             if k == "caf":
                 note = f"  ({8 * cells / (med * 1e-3) / 1e9:.1f} GB/s of chi stored, {macs / (med * 1e-3) / 1e12:.2f} T complex int8 MAC/s)"
+            if k == "caf+cfar":
+                note = f"  (+{med - shape['ms']['caf']['median']:.3f} ms behind caf; the detector reads {(T // FRAMES) * nd * lags * (8 * nrows + 4) / 1e6:.1f} MB of P)"
+            if k == "get chi":
+                note = f"  ({8 * cells / 1e6:.1f} MB)"
+            if k == "get cfar":
+                note = f"  ({(T // FRAMES) * ((nrows + 1) * (16 * 32 + 4) + 16 * nrows * 8) / 1e3:.1f} kB)"
             if k == "host":
                 note = f"  ({T * plan.packet_stride / (med * 1e-3) / 1e9:.1f} GB/s)"
             print(f"rows {nrows:5d} batch {T:2d} {k:>10}: {med:9.3f} ms ({min(ms):.3f} .. {max(ms):.3f}){note}")
@@ -135,6 +162,8 @@ def main():
             print(f"rows {nrows:5d} batch {T:2d} host+model: {dt:9.1f} ms for ONE line of {T // FRAMES} (numpy, fp64)")
         out["shapes"].append(shape)
         cf.close()
+        if cfd:
+            cfd.close()
         sp.close()
         host.close()
         plan.close()
