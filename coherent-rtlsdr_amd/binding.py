@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "crsdr_caf_create", "crsdr_caf_destroy", "crsdr_caf_submit", "crsdr_caf_submit_plan", "crsdr_caf_fetch",
     "crsdr_caf_device_buffers", "crsdr_caf_last_submit", "crsdr_ambiguity",
     "crsdr_caf_set_cfar", "crsdr_caf_fetch_cfar", "crsdr_caf_cfar_device_buffers", "crsdr_cfar", "crsdr_cfar_alpha",
+    "crsdr_caf_set_cancel", "crsdr_caf_fetch_cancel", "crsdr_caf_cancel_device_buffers", "crsdr_ambiguity_cancel",
 ]
 REFCANCEL_SINGULAR, REFCANCEL_IDLE = 1, 2                     # status bit 0: the solve failed (g = 0); 2: the pass did not run
 REFCANCEL_MAX_TAPS = 9
@@ -118,6 +119,11 @@ class CfarDesc(C.Structure):
     training cells a detection needs, and K detections kept per map."""
     _fields_ = [("gd", C.c_int32), ("gr", C.c_int32), ("td", C.c_int32), ("tr", C.c_int32), ("alpha", C.c_float), ("min_train", C.c_int32),
                 ("max_det", C.c_int32)]
+
+
+class CancelDesc(C.Structure):
+    """crsdr_caf_cancel_desc: the reference's delays 0 .. taps - 1, each shifted by -dopp .. dopp Doppler bins."""
+    _fields_ = [("taps", C.c_int32), ("dopp", C.c_int32)]
 
 
 _lib = None
@@ -282,6 +288,11 @@ def lib():
         L.crsdr_caf_cfar_device_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.crsdr_cfar.argtypes = [f32p, i32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CfarDesc), C.c_int]
         L.crsdr_cfar_alpha.argtypes = [C.c_double, C.c_int, f32p]
+    if hasattr(L, "crsdr_ambiguity_cancel"):         # (likewise: an older build has no canceller)
+        L.crsdr_caf_set_cancel.argtypes = [vp, C.POINTER(CancelDesc)]
+        L.crsdr_caf_fetch_cancel.argtypes = [vp, f32p, f32p]
+        L.crsdr_caf_cancel_device_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+        L.crsdr_ambiguity_cancel.argtypes = [f32p, f32p, f32p, C.POINTER(C.c_int8)] + [C.c_int] * 10 + [f32p, f32p]
     _lib = L
     return L
 
@@ -694,6 +705,29 @@ def ambiguity_device(chi_ptr: int, map_ptr: int, peak_ptr: int, matrix_ptr: int,
     cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
     _check(lib().crsdr_ambiguity(cast(chi_ptr, C.c_float), cast(map_ptr, C.c_float), cast(peak_ptr, C.c_float), cast(matrix_ptr, C.c_int8), int(nrows), int(B),
                                  int(seg), int(nlags), int(ref_row), int(window), int(guard), MEM_DEVICE))
+
+
+def ambiguity_cancel(matrix, seg, nlags, taps, dopp=0, ref_row=0, window=WINDOW_RECT, guard=0):
+    """crsdr_ambiguity_cancel: ambiguity() with the reference's first `taps` delays, each at -dopp .. dopp Doppler bins, projected out of
+    every row but ref_row -> (chi, map, peak, coef [nrows][taps (2 dopp + 1)] complex64, cinfo [nrows][2] float32 = residual share,
+    status).  The engine (Caf.set_cancel) on one line of one packet, bit for bit."""
+    m = np.ascontiguousarray(matrix, dtype=np.int8)
+    nrows, B = m.shape
+    nd, R, n = max(B // (2 * max(int(seg), 1)), 0), max(int(nlags), 0), max(int(taps) * (2 * int(dopp) + 1), 0)
+    chi, mp, pk = np.empty((nrows, nd, R), dtype=np.complex64), np.empty((nd, R), dtype=np.float32), np.empty((nrows + 1, 6), dtype=np.float32)
+    coef, cinfo = np.empty((nrows, n), dtype=np.complex64), np.empty((nrows, 2), dtype=np.float32)
+    _check(lib().crsdr_ambiguity_cancel(_p(chi.view(np.float32), C.c_float), _p(mp, C.c_float), _p(pk, C.c_float), _p(m, C.c_int8), nrows, B, int(seg), int(nlags),
+                                        int(ref_row), int(window), int(guard), MEM_HOST, int(taps), int(dopp), _p(coef.view(np.float32), C.c_float), _p(cinfo, C.c_float)))
+    return chi, mp, pk, coef, cinfo
+
+
+def ambiguity_cancel_device(chi_ptr: int, map_ptr: int, peak_ptr: int, matrix_ptr: int, nrows, B, seg, nlags, ref_row, window, guard, taps, dopp, coef_ptr: int,
+                            cinfo_ptr: int):
+    """Same on device memory (any output pointer, not all, may be 0); returns after the kernels finished."""
+    cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
+    _check(lib().crsdr_ambiguity_cancel(cast(chi_ptr, C.c_float), cast(map_ptr, C.c_float), cast(peak_ptr, C.c_float), cast(matrix_ptr, C.c_int8), int(nrows), int(B),
+                                        int(seg), int(nlags), int(ref_row), int(window), int(guard), MEM_DEVICE, int(taps), int(dopp), cast(coef_ptr, C.c_float),
+                                        cast(cinfo_ptr, C.c_float)))
 
 
 def subband_beamform(matrix, weights, nfft, first=0, nbands=1, width=1, window=WINDOW_RECT):
@@ -1386,6 +1420,25 @@ class Caf:
         ptrs = [C.c_void_p() for _ in range(3)]
         _check(lib().crsdr_caf_cfar_device_buffers(self._h, *[C.byref(p) for p in ptrs]))
         return dict(zip(("det", "count", "snap"), [p.value for p in ptrs]))
+
+    def set_cancel(self, taps: "int | None", dopp: int = 0):
+        """crsdr_caf_set_cancel: the canceller in front of every submit's Doppler stage (taps None: off).  Between submits."""
+        desc = None if taps is None else CancelDesc(int(taps), int(dopp))
+        _check(lib().crsdr_caf_set_cancel(self._h, None if desc is None else C.byref(desc)))
+        self.basis = 0 if desc is None else int(taps) * (2 * int(dopp) + 1)
+
+    def fetch_cancel(self, coef=True, cinfo=True) -> dict:
+        """Waits for the last submit.  coef [nest][nrows][n] complex64, cinfo [nest][nrows][2] = residual share, status."""
+        n, b = self._last()[0] if getattr(self, "basis", 0) else 0, max(1, getattr(self, "basis", 0))
+        c = np.zeros((n, self.nrows, b), dtype=np.complex64) if coef else None
+        i = np.zeros((n, self.nrows, 2), dtype=np.float32) if cinfo else None
+        _check(lib().crsdr_caf_fetch_cancel(self._h, _p(None if c is None else c.view(np.float32), C.c_float), _p(i, C.c_float)))
+        return {k: v for k, v in (("coef", c), ("cinfo", i)) if v is not None}
+
+    def cancel_device_buffers(self) -> dict:
+        ptrs = [C.c_void_p() for _ in range(2)]
+        _check(lib().crsdr_caf_cancel_device_buffers(self._h, *[C.byref(p) for p in ptrs]))
+        return dict(zip(("coef", "cinfo"), [p.value for p in ptrs]))
 
     def last_launches(self) -> int:
         return self._last()[1]

@@ -29,6 +29,9 @@
 //                 it as A [T][nd] float2 in spectra.hpp's padded layout; the twiddles take the place of the staged words; the T transforms
 //                 run as one chunk of spectra.hpp's network (sp_pass); scale, digit reversal, and the store with tau fastest.
 //                 LDS: A 34 KiB (32 KiB at nd = 4096, unpadded as in spectra.hpp) + max(twiddles, staged words) <= 64 KiB static.
+//                 k_caf<LG, 1> and k_caf<LG, 2> are the canceller's two passes around the same range stage (CancelArgs below,
+//                 caf_cancel.hpp): the sums of the first lags and the row's energy, and the rows with the reference's part taken out
+//                 of ACC in fp64 before the Doppler stage.  k_caf<LG> itself compiles to the instructions it had without them.
 //   k_caf_map     grid (cells / 32, line): the fp64 sum of |chi|^2 over the rows but r, eight interleaved parts of the rows added in a
 //                 fixed order, rounded once.
 //   k_caf_peak    grid (entry, line), 256 threads: caf_peak.hpp's search, one part per thread, merged by a tree in LDS.
@@ -59,10 +62,26 @@ constexpr int caf_u_words() { return 2 * (1 << LG) > CAF_STAGE_WORDS ? 2 * (1 <<
 
 // Packet t of the batch at packets + t * packet_stride, its matrix [nrows][B] int8 at + matrix_off (4-byte aligned).
 // tw_g, win: spectra::k_spectra_tables at N = nd.  scale = fp32(1 / (127^2 Ls sum w)).
-template <int LG>
+// MODE 0 is crsdr_caf's kernel with the canceller off.  The canceller's two passes (caf_cancel.hpp) are the same code around the same
+// range stage: MODE 1 stops behind it and leaves the sums of the lags < nlags (there: taps) and the row's energy; MODE 2 takes the
+// reference's part out of ACC, in fp64 with one rounding, before the Doppler stage reads it.
+struct CancelArgs {
+    int taps = 0, dopp = 0, nlags = 0;             // nlags: G's (the map's), which MODE 1 does not get as its own
+    const int2 *G = nullptr;                       // [nest][nd][taps][nlags]
+    const double2 *h = nullptr, *ph = nullptr;     // [nest][nrows][n] fp64 coefficients; exp(2 pi i j / nd), j < nd
+    const int *status = nullptr;                   // [nest]
+    int2 *Y = nullptr;                             // [nest][nrows][nd][taps]
+    long long *E = nullptr;                        // [nest][nrows]
+};
+
+template <typename T>
+__device__ __forceinline__ const T &caf_only(const T &t) { return t; }
+
+// MODE 0 takes no further argument; MODE 1 and 2 one CancelArgs.
+template <int LG, int MODE = 0, typename... CN>
 __global__ __launch_bounds__(CAF_THREADS) void k_caf(const int8_t *__restrict__ packets, size_t packet_stride, size_t matrix_off, int nrows, int B, int frames,
                                                      int lgseg, int nlags, int ref_row, const float2 *__restrict__ tw_g, const float *__restrict__ win, float scale,
-                                                     float2 *__restrict__ chi)
+                                                     float2 *__restrict__ chi, const CN... cna)
 {
     constexpr int ND = 1 << LG, LT = caf_log2_tile(LG), T = 1 << LT, CELLS = ND * T, PER = CELLS >= CAF_THREADS ? CELLS / CAF_THREADS : 1;
     __shared__ float2 A[spectra::sp_lds_points<LG>()];
@@ -73,6 +92,8 @@ __global__ __launch_bounds__(CAF_THREADS) void k_caf(const int8_t *__restrict__ 
     const int lag0 = tile << LT, tt = min(T, nlags - lag0), pre = ((lag0 + tt - 1) >> 1) + 1;
     const int words = B >> 2, J = (B >> 1) >> lgseg, nchunks = (words + CAF_CHUNK - 1) / CAF_CHUNK;
 
+    if constexpr (MODE == 1) if (row == ref_row) return;            // (the whole workgroup: nothing of row r is solved for)
+    [[maybe_unused]] long long energy = 0;
     for (int i = tid; i < 2 * CELLS; i += CAF_THREADS) ACC[i] = 0;
     for (int f = 0; f < frames; ++f) {
         const int8_t *m = packets + (size_t)(e * frames + f) * packet_stride + matrix_off;
@@ -86,6 +107,9 @@ __global__ __launch_bounds__(CAF_THREADS) void k_caf(const int8_t *__restrict__ 
                 RW[i] = g >= 0 ? rrow[g] : 0u;                       // X_r = 0 in front of the packet
             }
             __syncthreads();
+            if constexpr (MODE == 1)
+                if (tile == 0)
+                    for (int i = tid; i < cw; i += CAF_THREADS) energy += __builtin_amdgcn_sdot4((int)SW[i], (int)SW[i], 0, false);
             if constexpr (T >= 2) {
                 // an even lag and the odd one behind it per item: the same row words, swaps and reference words serve both
                 for (int it = tid; it < (cw / CAF_PIECE) << (LT - 1); it += CAF_THREADS) {
@@ -140,6 +164,60 @@ __global__ __launch_bounds__(CAF_THREADS) void k_caf(const int8_t *__restrict__ 
     }
     __syncthreads();
 
+    if constexpr (MODE == 1) {
+        const CancelArgs &cn = caf_only(cna...);
+        // the sums of the lags < taps as they are, and E = sum |X_c|^2 over the line: integers, so any order gives the same bits
+        int2 *Y = cn.Y + ((size_t)e * nrows + row) * ND * (size_t)nlags + lag0;
+        for (int it = tid; it < CELLS; it += CAF_THREADS) {
+            const int l = it & (T - 1), k = it >> LT;
+            if (l < tt) Y[(size_t)k * nlags + l] = make_int2(ACC[2 * it], ACC[2 * it + 1]);
+        }
+        if (tile != 0) return;
+        __syncthreads();                                             // (ACC is read: its place serves the tree, 8-byte aligned as U need not be)
+        long long *red = reinterpret_cast<long long *>(A);
+        red[tid] = energy;
+        __syncthreads();
+        for (int h = CAF_THREADS / 2; h >= 1; h >>= 1) {
+            if (tid < h) red[tid] += red[tid + h];
+            __syncthreads();
+        }
+        if (tid == 0) cn.E[(size_t)e * nrows + row] = red[0];
+        return;
+    }
+    if constexpr (MODE == 2) {
+        // y' = y - sum_(m,p) h_(m,p) phi_p[k] G[k][m][tau]: fp64 from the integers, one rounding; its bits take y's place in ACC.
+        // Row r and a singular line keep y: (float)(double)y is (float)y.
+        const CancelArgs &cn = caf_only(cna...);
+        const bool on = row != ref_row && cn.status[e] == 0;
+        const int K = cn.taps, P = cn.dopp, Rg = cn.nlags;
+        const double2 *h = cn.h + ((size_t)e * nrows + row) * (size_t)(K * (2 * P + 1));
+        const int2 *G = cn.G + (size_t)e * ND * (size_t)K * Rg + lag0;
+#pragma unroll 1
+        for (int it = tid; it < CELLS; it += CAF_THREADS) {
+            const int l = it & (T - 1), k = it >> LT;
+            double re = (double)ACC[2 * it], im = (double)ACC[2 * it + 1];
+            if (on && l < tt) {
+                const int2 *g = G + (size_t)k * K * Rg + l;
+                for (int p = -P; p <= P; ++p) {
+                    double ar = 0.0, ai = 0.0;                        // sum_m h_(m,p) G[k][m][tau]
+                    const double2 *hp = h + (p + P) * K;
+                    for (int m = 0; m < K; ++m) {
+                        const int2 gi = g[(size_t)m * Rg];
+                        const double gr = (double)gi.x, gq = (double)gi.y;
+                        ar = fma(hp[m].x, gr, ar); ar = fma(-hp[m].y, gq, ar);
+                        ai = fma(hp[m].x, gq, ai); ai = fma(hp[m].y, gr, ai);
+                    }
+                    const double2 f = cn.ph[(p * k) & (ND - 1)];
+                    re = fma(-f.x, ar, re); re = fma(f.y, ai, re);
+                    im = fma(-f.x, ai, im); im = fma(-f.y, ar, im);
+                }
+            }
+            ACC[2 * it] = __float_as_int((float)re);
+            ACC[2 * it + 1] = __float_as_int((float)im);
+        }
+        __syncthreads();
+    }
+
     int yr[PER], yi[PER];
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
@@ -155,7 +233,8 @@ __global__ __launch_bounds__(CAF_THREADS) void k_caf(const int8_t *__restrict__ 
         const int i = tid + j * CAF_THREADS, k = i >> LT, l = i & (T - 1);
         if (i < CELLS) {
             const float w = win[k];
-            A[spectra::sp_pad<LG>(l * ND + k)] = make_float2((float)yr[j] * w, (float)yi[j] * w);
+            if constexpr (MODE == 2) A[spectra::sp_pad<LG>(l * ND + k)] = make_float2(__int_as_float(yr[j]) * w, __int_as_float(yi[j]) * w);
+            else A[spectra::sp_pad<LG>(l * ND + k)] = make_float2((float)yr[j] * w, (float)yi[j] * w);
         }
     }
     __syncthreads();

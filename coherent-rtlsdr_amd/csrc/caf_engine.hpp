@@ -5,9 +5,12 @@
 //     submit is three launches on one stream whatever the batch size (rows, map, peaks), no lock, no allocation, no synchronisation.
 //     With a detector set (crsdr_caf_set_cfar; caf_cfar.hpp, caf_cfar_kernels.hpp) two more: the tiles' candidates, and their merge into
 //     the detection lists and the array map's snapshots.  Its buffers are made by set_cfar, between submits.
+//     With a canceller set (crsdr_caf_set_cancel; caf_cancel.hpp, caf_cancel_solve.hpp) five launches take the place of the rows' one:
+//     the reference's sums, the rows' first lags, the normal equations' sums, factor and solves, and the rows with the subtraction.
 #pragma once
 
 #include "caf.hpp"
+#include "caf_cancel.hpp"
 #include "caf_cfar_kernels.hpp"
 
 // `launch` with LG = log2 nd, 3 .. 12
@@ -25,8 +28,18 @@
     default: { constexpr int LG = 12; launch; } break;                              \
     }
 
-constexpr int kCafLaunches = 3, kCafCfarLaunches = 2;
+constexpr int kCafLaunches = 3, kCafCfarLaunches = 2, kCafCancelLaunches = 4;      // (the canceller's five take the place of one)
 constexpr long long kCafMaxCells = 1ll << 24;           // (max_batch / frames) * nrows * nd * nlags
+
+// the canceller's device memory for `lines` lines: the engine's own buffers, or parts of one per-op slot
+struct CancelBufs {
+    int taps = 0, dopp = 0;
+    int2 *G = nullptr, *Y = nullptr;
+    double2 *ph = nullptr, *S = nullptr, *C = nullptr, *W = nullptr, *h = nullptr;
+    long long *E = nullptr;
+    int *status = nullptr;
+    float *coef = nullptr, *cinfo = nullptr;
+};
 
 struct crsdr_caf {
     DoaStream own;
@@ -42,6 +55,17 @@ struct crsdr_caf {
         DevBuf<int32_t> tcount, count;
         DevBuf<float> det, snap;
     } cf;
+    // crsdr_caf_set_cancel: on (false = off) and what CancelBufs names
+    struct Cancel {
+        bool on = false, submitted = false;
+        int taps = 0, dopp = 0;
+        DevBuf<int2> G, Y;
+        DevBuf<double2> ph, S, C, W, h;
+        DevBuf<long long> E;
+        DevBuf<int> status;
+        DevBuf<float> coef, cinfo;
+        CancelBufs bufs() const { return CancelBufs{taps, dopp, G, Y, ph, S, C, W, h, E, status, coef, cinfo}; }
+    } cn;
     hipStream_t last_stream = nullptr;
     int last_nest = 0, last_launches = 0;
     bool submitted = false;
@@ -70,17 +94,70 @@ static int caf_args_ok(const char *who, int nrows, int blocksize, int max_batch,
     return CRSDR_OK;
 }
 
-// the three launches, for the object and for crsdr_ambiguity: the same kernels on the same arguments, so the same bits
+// every limit of the canceller of section (w), for crsdr_caf_set_cancel and crsdr_ambiguity_cancel
+static int cancel_args_ok(const char *who, int nd, int nlags, long long lines, const crsdr_caf_cancel_desc *d)
+{
+    switch (cc::bad_limit(nd, nlags, lines, d->taps, d->dopp)) {
+    case 0: return CRSDR_OK;
+    case 1: return fail(CRSDR_EINVAL, "%s: dopp = %d (0..%d)", who, d->dopp, cc::MAX_DOPP);
+    case 2: return fail(CRSDR_EINVAL, "%s: taps = %d (1..min(nlags = %d, %d))", who, d->taps, nlags, cc::MAX_TAPS);
+    case 3: return fail(CRSDR_EINVAL, "%s: taps (2 dopp + 1) = %d (at most %d)", who, cc::basis(d->taps, d->dopp), cc::MAX_BASIS);
+    case 4: return fail(CRSDR_EINVAL, "%s: 2 dopp + 1 = %d exceeds nd = %d", who, 2 * d->dopp + 1, nd);
+    default: return fail(CRSDR_EINVAL, "%s: (max_batch / frames) * nd * taps * nlags = %lld (at most 2^24)", who, lines * nd * d->taps * nlags);
+    }
+}
+
+// the phase table of the canceller, exp(2 pi i j / nd): at set_cancel, and per call for crsdr_ambiguity_cancel
+static int cancel_table(hipStream_t S, int nd, double2 *ph)
+{
+    hipLaunchKernelGGL(cancel::k_cancel_phase, dim3((unsigned)((nd + cancel::THREADS - 1) / cancel::THREADS)), dim3(cancel::THREADS), 0, S, nd, ph);
+    HIP_TRY(hipGetLastError());
+    return CRSDR_OK;
+}
+
+// the rows with the canceller: five launches in the place of k_caf's one
+static int cancel_enqueue(hipStream_t S, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nest, int nrows, int B, int frames, int lg, int lgseg,
+                          int nlags, int ref_row, const float2 *tw, const float *win, float scale, float2 *chi, const CancelBufs &c)
+{
+    const int nd = 1 << lg, K = c.taps, P = c.dopp, n = cc::basis(K, P), entries = (4 * P + 1) * K * K + nrows * n;
+    hipLaunchKernelGGL(cancel::k_cancel_g, dim3((unsigned)((nd * (nlags + K - 1) + cancel::THREADS - 1) / cancel::THREADS), (unsigned)nest), dim3(cancel::THREADS), 0, S,
+                       packets, packet_stride, matrix_offset, B, frames, lgseg, nd, nlags, K, ref_row, c.G);
+    HIP_TRY(hipGetLastError());
+    caf::CancelArgs a1, a2;
+    a1.Y = c.Y; a1.E = c.E;
+    a2.taps = K; a2.dopp = P; a2.nlags = nlags; a2.G = c.G; a2.h = c.h; a2.ph = c.ph; a2.status = c.status;
+    CAF_DISPATCH(lg, hipLaunchKernelGGL((caf::k_caf<LG, 1>), dim3((unsigned)(nrows * caf::caf_tiles(lg, K)), (unsigned)nest), dim3(caf::CAF_THREADS), 0, S, packets,
+                                        packet_stride, matrix_offset, nrows, B, frames, lgseg, K, ref_row, tw, win, scale, chi, a1));
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cancel::k_cancel_sums, dim3((unsigned)((entries + cancel::SUM_ENTRIES - 1) / cancel::SUM_ENTRIES), (unsigned)nest), dim3(cancel::THREADS), 0, S,
+                       (const int2 *)c.G, (const int2 *)c.Y, (const double2 *)c.ph, nrows, nd, nlags, K, P, ref_row, c.S, c.C);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cancel::k_cancel_solve, dim3((unsigned)nest, (unsigned)((nrows + cancel::SOLVE_ROWS - 1) / cancel::SOLVE_ROWS)), dim3(cancel::THREADS), 0, S, (const double2 *)c.S, (const double2 *)c.C, (const long long *)c.E, nrows,
+                       K, P, ref_row, c.W, c.h, c.status, c.coef, c.cinfo);
+    HIP_TRY(hipGetLastError());
+    CAF_DISPATCH(lg, hipLaunchKernelGGL((caf::k_caf<LG, 2>), dim3((unsigned)(nrows * caf::caf_tiles(lg, nlags)), (unsigned)nest), dim3(caf::CAF_THREADS), 0, S,
+                                        packets, packet_stride, matrix_offset, nrows, B, frames, lgseg, nlags, ref_row, tw, win, scale, chi, a2));
+    HIP_TRY(hipGetLastError());
+    return CRSDR_OK;
+}
+
+// the three launches, for the object and for crsdr_ambiguity: the same kernels on the same arguments, so the same bits.  cn: the
+// canceller's buffers, or NULL with it off.
 static int caf_enqueue(hipStream_t S, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nblocks, int nrows, int B, int frames, int seg, int nlags,
-                       int ref_row, int window, int guard, const float2 *tw, const float *win, float2 *chi, float *map, float *peak)
+                       int ref_row, int window, int guard, const float2 *tw, const float *win, float2 *chi, float *map, float *peak, const CancelBufs *cn = nullptr)
 {
     const int nest = nblocks / frames, nd = frames * (B / (2 * seg)), lg = ilog2_exact(nd), lgseg = ilog2_exact(seg), cells = nd * nlags;
     // sum w: nd (rect), nd / 2 (periodic Hann)
     const float scale = (float)(1.0 / (127.0 * 127.0 * (double)seg * (window == CRSDR_WINDOW_HANN ? 0.5 * (double)nd : (double)nd)));
     const dim3 grow((unsigned)(nrows * caf::caf_tiles(lg, nlags)), (unsigned)nest);
-    CAF_DISPATCH(lg, hipLaunchKernelGGL((caf::k_caf<LG>), grow, dim3(caf::CAF_THREADS), 0, S, packets, packet_stride, matrix_offset, nrows, B, frames, lgseg, nlags, ref_row,
-                                        tw, win, scale, chi));
-    HIP_TRY(hipGetLastError());
+    if (cn) {
+        const int rc = cancel_enqueue(S, packets, packet_stride, matrix_offset, nest, nrows, B, frames, lg, lgseg, nlags, ref_row, tw, win, scale, chi, *cn);
+        if (rc) return rc;
+    } else {
+        CAF_DISPATCH(lg, hipLaunchKernelGGL((caf::k_caf<LG>), grow, dim3(caf::CAF_THREADS), 0, S, packets, packet_stride, matrix_offset, nrows, B, frames, lgseg, nlags,
+                                            ref_row, tw, win, scale, chi));
+        HIP_TRY(hipGetLastError());
+    }
     hipLaunchKernelGGL(caf::k_caf_map, dim3((unsigned)((cells + caf::CAF_MAP_CELLS - 1) / caf::CAF_MAP_CELLS), (unsigned)nest), dim3(caf::CAF_THREADS), 0, S,
                        (const float2 *)chi, nrows, cells, ref_row, map);
     HIP_TRY(hipGetLastError());
@@ -170,10 +247,12 @@ extern "C" int crsdr_caf_destroy(crsdr_caf *caf)
 
 static int caf_launch(crsdr_caf *q, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nblocks, hipStream_t S)
 {
+    const CancelBufs cb = q->cn.bufs();
     const int rc = caf_enqueue(S, packets, packet_stride, matrix_offset, nblocks, q->nrows, q->B, q->frames, q->seg, q->nlags, q->ref_row, q->window, q->guard, q->tw, q->win,
-                               q->chi, q->map, q->peak);
+                               q->chi, q->map, q->peak, q->cn.on ? &cb : nullptr);
     if (rc) return rc;
     q->last_stream = S; q->last_nest = nblocks / q->frames; q->submitted = true; q->last_launches = kCafLaunches;
+    if (q->cn.on) { q->cn.submitted = true; q->last_launches += kCafCancelLaunches; }
     if (!q->cf.on) return CRSDR_OK;
     const int rc2 = cfar_enqueue(S, q->chi, q->map, q->last_nest, q->nrows, q->nrows + 1, q->nd, q->nlags, q->guard, q->cf.prm, q->cf.keep, q->cf.slots, q->cf.tcount,
                                  q->cf.det, q->cf.count, q->cf.snap);
@@ -286,6 +365,50 @@ extern "C" int crsdr_caf_cfar_device_buffers(crsdr_caf *q, void **det, void **co
     return CRSDR_OK;
 }
 
+extern "C" int crsdr_caf_set_cancel(crsdr_caf *q, const crsdr_caf_cancel_desc *desc)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_set_cancel: NULL caf");
+    const size_t lines = (size_t)(q->max_batch / q->frames);
+    if (desc) { const int rc_ = cancel_args_ok("caf_set_cancel", q->nd, q->nlags, (long long)lines, desc); if (rc_) return rc_; }
+    HIP_TRY(hipSetDevice(q->device));
+    if (q->submitted) HIP_TRY(hipDeviceSynchronize());      // the last submit may still use the buffers let go here
+    q->cn = crsdr_caf::Cancel();
+    if (!desc) return CRSDR_OK;
+    const size_t K = (size_t)desc->taps, P = (size_t)desc->dopp, n = K * (2 * P + 1), rows = lines * (size_t)q->nrows, nd = (size_t)q->nd;
+    crsdr_caf::Cancel &c = q->cn;
+    int r = CRSDR_OK;
+    if ((r = c.G.alloc(lines * nd * K * (size_t)q->nlags)) || (r = c.Y.alloc(rows * nd * K)) || (r = c.ph.alloc(nd)) || (r = c.S.alloc(lines * (4 * P + 1) * K * K)) ||
+        (r = c.C.alloc(rows * n)) || (r = c.W.alloc(rows * n)) || (r = c.h.alloc(rows * n)) || (r = c.E.alloc(rows)) || (r = c.status.alloc(lines)) ||
+        (r = c.coef.alloc(rows * n * 2)) || (r = c.cinfo.alloc(rows * 2)) || (r = cancel_table(q->own.s, q->nd, c.ph)) || (r = HIP_RC(hipStreamSynchronize(q->own.s)))) {
+        q->cn = crsdr_caf::Cancel();
+        return r;
+    }
+    c.taps = desc->taps; c.dopp = desc->dopp; c.on = true;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_fetch_cancel(crsdr_caf *q, float *coef, float *cinfo)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_fetch_cancel: NULL caf");
+    if (!q->cn.on) return fail(CRSDR_ESTATE, "caf_fetch_cancel: no canceller set (crsdr_caf_set_cancel)");
+    if (!q->cn.submitted) return fail(CRSDR_ESTATE, "caf_fetch_cancel: nothing submitted since the canceller was set");
+    HIP_TRY(hipSetDevice(q->device));
+    const size_t rows = (size_t)q->last_nest * (size_t)q->nrows, n = (size_t)cc::basis(q->cn.taps, q->cn.dopp);
+    if (coef) HIP_TRY(hipMemcpyAsync(coef, q->cn.coef.p, sizeof(float) * rows * n * 2, hipMemcpyDeviceToHost, q->last_stream));
+    if (cinfo) HIP_TRY(hipMemcpyAsync(cinfo, q->cn.cinfo.p, sizeof(float) * rows * 2, hipMemcpyDeviceToHost, q->last_stream));
+    HIP_TRY(hipStreamSynchronize(q->last_stream));
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_cancel_device_buffers(crsdr_caf *q, void **coef, void **cinfo)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_cancel_device_buffers: NULL caf");
+    if (!q->cn.on) return fail(CRSDR_ESTATE, "caf_cancel_device_buffers: no canceller set (crsdr_caf_set_cancel)");
+    if (coef) *coef = q->cn.coef;
+    if (cinfo) *cinfo = q->cn.cinfo;
+    return CRSDR_OK;
+}
+
 extern "C" int crsdr_cfar_alpha(double pfa, int ntrain, float *alpha)
 {
     if (!alpha) return fail(CRSDR_EINVAL, "cfar_alpha: NULL alpha");
@@ -327,11 +450,13 @@ extern "C" int crsdr_cfar(float *det, int32_t *count, const float *src, int comp
     return st.finish();
 }
 
-extern "C" int crsdr_ambiguity(float *chi, float *map, float *peak, const int8_t *matrix, int nrows, int blocksize, int seg, int nlags, int ref_row, int window, int guard,
-                               int mem_kind)
+// crsdr_ambiguity (cd = NULL) and crsdr_ambiguity_cancel
+static int ambiguity(float *chi, float *map, float *peak, const int8_t *matrix, int nrows, int blocksize, int seg, int nlags, int ref_row, int window, int guard, int mem_kind,
+                     const crsdr_caf_cancel_desc *cd, float *coef, float *cinfo)
 {
-    if (!matrix || (!chi && !map && !peak)) return fail(CRSDR_EINVAL, "ambiguity: need matrix and at least one of chi, map, peak");
+    if (!matrix || (!chi && !map && !peak && !coef && !cinfo)) return fail(CRSDR_EINVAL, "ambiguity: need matrix and at least one output");
     { const int rc_ = caf_args_ok("ambiguity", nrows, blocksize, 1, 1, seg, nlags, ref_row, window, guard); if (rc_) return rc_; }
+    if (cd) { const int rc_ = cancel_args_ok("ambiguity_cancel", blocksize / (2 * seg), nlags, 1, cd); if (rc_) return rc_; }
     OP_PROLOGUE_MEM("ambiguity", mem_kind);
     const size_t nd = (size_t)(blocksize / (2 * seg)), cells = nd * (size_t)nlags, mb = (size_t)nrows * (size_t)blocksize;
     const size_t cb = sizeof(float2) * (size_t)nrows * cells, pb = sizeof(float) * cells, kb = sizeof(float) * 6 * (size_t)(nrows + 1);
@@ -340,8 +465,10 @@ extern "C" int crsdr_ambiguity(float *chi, float *map, float *peak, const int8_t
     float2 *d_c = (float2 *)st.out(1, chi, cb, 8);
     float *d_p = (float *)st.out(2, map, pb, 4);
     float *d_k = (float *)st.out(3, peak, kb, 4);
+    const size_t K = cd ? (size_t)cd->taps : 0, P = cd ? (size_t)cd->dopp : 0, n = K * (2 * P + 1), fb = sizeof(float) * 2 * (size_t)nrows * n, ib = sizeof(float) * 2 * (size_t)nrows;
+    float *d_f = cd ? (float *)st.out(5, coef, fb, 4) : nullptr, *d_i = cd ? (float *)st.out(6, cinfo, ib, 4) : nullptr;
     if (st.rc) return st.rc;
-    if (st.misaligned) return fail(CRSDR_EINVAL, "ambiguity: device matrix, map and peak 4-byte, chi 8-byte aligned");
+    if (st.misaligned) return fail(CRSDR_EINVAL, "ambiguity: device matrix, map, peak, coef and cinfo 4-byte, chi 8-byte aligned");
     // (device memory and an output not asked for: the kernels write it all the same)
     if (!d_c) { OP_RESERVE(1, cb); d_c = (float2 *)g_op.buf[1]; }
     if (!d_p) { OP_RESERVE(2, pb); d_p = (float *)g_op.buf[2]; }
@@ -350,9 +477,37 @@ extern "C" int crsdr_ambiguity(float *chi, float *map, float *peak, const int8_t
     float2 *tw = (float2 *)g_op.buf[4];
     float *win = (float *)(tw + nd);
     { const int rc_ = spectra_tables(0, (int)nd, window, tw, win); if (rc_) return rc_; }
-    { const int rc_ = caf_enqueue(0, d_m, mb, 0, 1, nrows, blocksize, 1, seg, nlags, ref_row, window, guard, tw, win, d_c, d_p, d_k); if (rc_) return rc_; }
+    CancelBufs c;
+    if (cd) {
+        if (!d_f) { OP_RESERVE(5, fb); d_f = (float *)g_op.buf[5]; }
+        if (!d_i) { OP_RESERVE(6, ib); d_i = (float *)g_op.buf[6]; }
+        // one slot for the rest, the 16-byte types first
+        const size_t nph = nd, nS = (4 * P + 1) * K * K, nC = (size_t)nrows * n, nG = nd * K * (size_t)nlags, nY = (size_t)nrows * nd * K;
+        OP_RESERVE(7, sizeof(double2) * (nph + nS + 3 * nC) + sizeof(long long) * (size_t)nrows + sizeof(int2) * (nG + nY) + sizeof(int));
+        c.taps = cd->taps; c.dopp = cd->dopp;
+        c.ph = (double2 *)g_op.buf[7]; c.S = c.ph + nph; c.C = c.S + nS; c.W = c.C + nC; c.h = c.W + nC;
+        c.E = (long long *)(c.h + nC); c.G = (int2 *)(c.E + nrows); c.Y = c.G + nG; c.status = (int *)(c.Y + nY);
+        c.coef = d_f; c.cinfo = d_i;
+        { const int rc_ = cancel_table(0, (int)nd, c.ph); if (rc_) return rc_; }
+    }
+    { const int rc_ = caf_enqueue(0, d_m, mb, 0, 1, nrows, blocksize, 1, seg, nlags, ref_row, window, guard, tw, win, d_c, d_p, d_k, cd ? &c : nullptr); if (rc_) return rc_; }
+    st.back(coef, d_f, fb);
+    st.back(cinfo, d_i, ib);
     st.back(chi, d_c, cb);
     st.back(map, d_p, pb);
     st.back(peak, d_k, kb);
     return st.finish();
+}
+
+extern "C" int crsdr_ambiguity(float *chi, float *map, float *peak, const int8_t *matrix, int nrows, int blocksize, int seg, int nlags, int ref_row, int window, int guard,
+                               int mem_kind)
+{
+    return ambiguity(chi, map, peak, matrix, nrows, blocksize, seg, nlags, ref_row, window, guard, mem_kind, nullptr, nullptr, nullptr);
+}
+
+extern "C" int crsdr_ambiguity_cancel(float *chi, float *map, float *peak, const int8_t *matrix, int nrows, int blocksize, int seg, int nlags, int ref_row, int window,
+                                      int guard, int mem_kind, int taps, int dopp, float *coef, float *cinfo)
+{
+    const crsdr_caf_cancel_desc cd{taps, dopp};
+    return ambiguity(chi, map, peak, matrix, nrows, blocksize, seg, nlags, ref_row, window, guard, mem_kind, &cd, coef, cinfo);
 }

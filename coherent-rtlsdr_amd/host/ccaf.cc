@@ -63,6 +63,27 @@ int batch::fetch_cfar(bool want_snap)
     return rc;
 }
 
+int batch::set_cancel(const crsdr_caf_cancel_desc *desc)
+{
+    int rc = cf ? crsdr_caf_set_cancel(cf, desc) : CRSDR_ESTATE;
+    if (!rc) { nbasis = desc ? desc->taps * (2 * desc->dopp + 1) : 0; coef.clear(); cinfo.clear(); }
+    if (rc && cf) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::fetch_cancel(bool want_coef)
+{
+    int nest = 0;
+    int rc = !cf || !nbasis ? CRSDR_ESTATE : crsdr_caf_last_submit(cf, &nest, nullptr);
+    if (!rc) {
+        coef.assign(want_coef ? (size_t)nest * rows * nbasis * 2 : 0, 0.f); cinfo.assign((size_t)nest * rows * 2, 0.f);
+        rc = crsdr_caf_fetch_cancel(cf, want_coef ? coef.data() : nullptr, cinfo.data());
+    }
+    if (!rc) nlines = nest;
+    if (rc && cf && nbasis) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
 int batch::fetch(bool want_chi, bool want_map)
 {
     int nest = 0;

@@ -28,7 +28,7 @@ struct det_t {
 // segments, the array map [nd][nlags], and nrows + 1 peaks (the rows', then the map's) searched outside |Doppler| < guard.
 class batch {
     crsdr_caf *cf = nullptr;
-    int rows, bins, lags, kdet = 0;
+    int rows, bins, lags, kdet = 0, nbasis = 0;
 
 public:
     batch(int nrows, int blocksize, int max_batch, int seg, int nlags, int ref_row = 0, int window = CRSDR_WINDOW_RECT, int guard = 0, int frames = 1, int device = 0);
@@ -46,6 +46,11 @@ public:
     // waits, and fills count and det, and snap if asked for; CRSDR_ESTATE with the detector off
     int fetch_cfar(bool want_snap = true);
     int max_det() const { return kdet; }
+    // the canceller in front of every later submit's Doppler stage (crsdr_caf_set_cancel; NULL: off).  Between submits, as set_cfar.
+    int set_cancel(const crsdr_caf_cancel_desc *desc);
+    // waits, and fills cinfo, and coef if asked for; CRSDR_ESTATE with the canceller off
+    int fetch_cancel(bool want_coef = true);
+    int basis() const { return nbasis; }             // taps (2 dopp + 1), 0 with the canceller off
     int lines() const { return nlines; }
     int nrows() const { return rows; }
     int nd() const { return bins; }
@@ -58,6 +63,10 @@ public:
     std::vector<det_t> det;                          // [lines][nrows + 1][max_det]: the strongest first, zeros behind the last
     std::vector<int32_t> count;                      // [lines][nrows + 1]: detected cells, which may be more than max_det
     std::vector<float> snap;                         // [lines][max_det][nrows][2]: chi of every row at the array map's detections
+    std::vector<float> coef;                         // [lines][nrows][basis][2]: the canceller's filter of every row
+    std::vector<float> cinfo;                        // [lines][nrows][2]: the share of the row's power that stays, and the status
+    float residual(int e, int c) const { return cinfo[2 * ((size_t)e * rows + c)]; }
+    bool singular(int e, int c) const { return cinfo[2 * ((size_t)e * rows + c) + 1] != 0.f; }
     // of line e and entry c: the number of detections held (at most max_det), and detection k of them
     int held(int e, int c) const { const int n = count[(size_t)e * (rows + 1) + c]; return n < kdet ? n : kdet; }
     const det_t &detection(int e, int c, int k) const { return det[((size_t)e * (rows + 1) + c) * kdet + k]; }

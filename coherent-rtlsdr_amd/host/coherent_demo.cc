@@ -70,6 +70,8 @@ int main(int argc, char **argv)
     bool cfar_on = false;
     double cfar_db = 0.0;
     crsdr_cfar_desc cfar = {1, 1, 3, 4, 0.f, 1, 16};
+    bool cancel_on = false;
+    crsdr_caf_cancel_desc cancel = {0, 0};
     bool engine_batches = false;
     int ranks = 1, rank = 0, device = 0;
     std::string idfile;
@@ -153,6 +155,14 @@ int main(int argc, char **argv)
             cfar.alpha = n == 1 || n == 5 ? (float)std::pow(10.0, cfar_db / 10.0) : -1.f;      // (refused below with the rest)
         }
         else if (a == "--max-det") val(cfar.max_det);
+        // with --caf: the least-squares canceller in front of the Doppler stage (crsdr_caf_set_cancel): the reference's first K delays, each
+        // at -P .. P Doppler bins (default 0), projected out of every other row.  One line per line of the batch: the mean share of the
+        // rows' power that stays, in dB.
+        else if (a == "--cancel" && i + 1 < argc) {
+            const int n = std::sscanf(argv[++i], "%d:%d", &cancel.taps, &cancel.dopp);
+            cancel_on = true;
+            if (n < 1) cancel.taps = -1;                                                     // (refused below with the rest)
+        }
         else if (a == "--guard") val(caf_guard);
         else if (a == "--band" && i + 1 < argc) { if (std::sscanf(argv[++i], "%d:%d", &sp_band_lo, &sp_band_hi) != 2) sp_nfft = -1; }
         else if (a == "--window" && i + 1 < argc) {
@@ -533,11 +543,21 @@ int main(int argc, char **argv)
             if (caf_seg > 0) caf.reset(new ccaf::batch(1 + nsig, B, batch, caf_seg, caf_lags, caf_ref, sb_window, caf_guard, caf_frames));
             if (!caf || !caf->ok()) { std::printf("caf: --caf SEG:LAGS[:REF] [--caf-frames F] [--guard G] [--window rect|hann] refused\nDEMO FAILED\n"); return 1; }
             if (cfar_on && caf->set_cfar(&cfar)) { std::printf("cfar: --cfar SNR_DB[:GD:GR:TD:TR] [--max-det K] refused\nDEMO FAILED\n"); return 1; }
+            if (cancel_on && caf->set_cancel(&cancel)) { std::printf("cancel: --cancel K[:P] refused\nDEMO FAILED\n"); return 1; }
         }
         auto ambiguity = [&](int b) {
             if (!caf || !ok) return;
-            ok = caf->submit(coherent.engine_plan()) == CRSDR_OK && caf->fetch() == CRSDR_OK && (!cfar_on || caf->fetch_cfar() == CRSDR_OK);
+            ok = caf->submit(coherent.engine_plan()) == CRSDR_OK && caf->fetch() == CRSDR_OK && (!cfar_on || caf->fetch_cfar() == CRSDR_OK) &&
+                 (!cancel_on || caf->fetch_cancel(false) == CRSDR_OK);
             if (!ok || !report) return;
+            for (int e = 0; cancel_on && e < caf->lines(); ++e) {
+                double sum = 0.0;
+                int n = 0, singular = 0;
+                for (int c = 0; c < caf->nrows(); ++c)
+                    if (c != caf_ref) { sum += (double)caf->residual(e, c); ++n; singular |= caf->singular(e, c); }
+                std::printf("cancel: batch %d line %d: taps %d dopp %d residual %.2f dB%s\n", b, e, cancel.taps, cancel.dopp, 10.0 * std::log10(sum / n),
+                            singular ? " (singular)" : "");
+            }
             for (int e = 0; cfar_on && e < caf->lines(); ++e)
                 for (int k = 0; k < caf->held(e, caf->nrows()); ++k) {
                     const ccaf::det_t &d = caf->detection(e, caf->nrows(), k);

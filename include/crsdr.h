@@ -1170,6 +1170,60 @@ int crsdr_cfar(float *det, int32_t *count, const float *src, int comps, int nd, 
  * set, train on fewer than ntrain cells and so run at a somewhat higher rate.  CRSDR_EINVAL for pfa outside (0, 1) or ntrain < 1. */
 int crsdr_cfar_alpha(double pfa, int ntrain, float *alpha);
 
+/* Cancellation.  A surveillance row holds the illuminator's own signal, strong and at short delays, and its ambiguity function has a
+ * noise-like floor about 1 / (nd Ls) below its peak in EVERY cell, which guard does not touch: an echo 40 dB down lies under it.  The
+ * canceller (the extensive cancellation algorithm, ECA) projects the reference and its first delays, optionally shifted by a few
+ * Doppler bins, out of every row between the range stage and the Doppler stage -- in the lag domain, on the exact integers; no float
+ * copy of the rows is made.  It is off until crsdr_caf_set_cancel; off, a submit is the same launches and the same bits.
+ *
+ * Parameters.  taps = K, dopp = P; the basis has n = K (2 P + 1) members.  Member (m, p), 0 <= m < K, -P <= p <= P, is in segment k
+ *     phi_p[k] X_r[j Ls + n - m],   phi_p[k] = exp(2 pi i p k / nd) in fp64
+ * (the phase constant within a segment, as the Doppler stage itself has it; X_r zero in front of the packet, as in y).
+ * Reference sums, exact in int32 with the bound of y:
+ *     G[k][m][tau] = sum_{n < Ls} X_r[j Ls + n - m] conj(X_r[j Ls + n - tau]),   m < K, tau < R;   G[k][0][tau] = y_r[k][tau]
+ * Per (line, row c != r), in fp64:
+ *     c_(m',p')       = sum_k conj(phi_p'[k]) y_c[k][m']
+ *     A_(m',p'),(m,p) = sum_k phi_(p-p')[k] G[k][m][m']        Hermitian; one A per line, shared by its rows
+ *     E               = sum |X_c|^2 over the line
+ *     A h_c = c  by Cholesky.  A pivot <= 2^-40 A_(0,0),(0,0) makes the line SINGULAR (an all-zero or rank-deficient reference): then
+ *     h = 0 for every row of the line, status bit 0 is set, and the line's chi has the bits the canceller-off path gives.
+ * Cancellation:
+ *     y'_c[k][tau] = y_c[k][tau] - sum_(m,p) h_c,(m,p) phi_p[k] G[k][m][tau]
+ * evaluated in fp64 from the integers and rounded ONCE to fp32; from there the Doppler stage runs as above (w[k], the transform, the
+ * scale).  Row r is left alone: its chi is bit for bit what the canceller-off path gives.  The array map, the peaks, the detector and
+ * snap run unchanged on the cancelled chi.
+ * Outputs per (line, row):
+ *     coef  [nest][nrows][n][2] float    h, index (p + P) K + m (m fastest within p), each part rounded once; row r zero
+ *     cinfo [nest][nrows][2] float       the share of the row's power that stays, clamp((E - Re sum conj(h) c) / E, 0, 1), 1 where E = 0;
+ *                                        and the status (0, or 1 = singular).  Row r: (1, 0)
+ * Bits.  Nothing depends on the order in which workgroups run: a line has the same bits wherever it sits in a batch, and
+ * crsdr_ambiguity_cancel launches the same kernels on the same arguments.
+ * Limits, all CRSDR_EINVAL and all checked before a device is touched, by one function for the engine and the per-op call:
+ * 0 <= P <= 2; 1 <= K <= min(R, 32); K (2 P + 1) <= 48; 2 P + 1 <= nd; (max_batch / frames) * nd * K * R <= 2^24. */
+typedef struct crsdr_caf_cancel_desc {
+    int32_t taps;             /* K: delays 0 .. K - 1 of the reference */
+    int32_t dopp;             /* P: Doppler shifts -P .. P bins of each */
+} crsdr_caf_cancel_desc;
+
+/* Sets the canceller (NULL: off).  Between submits only: it waits for the last one and allocates here, never in a submit; what a
+ * fetch_cancel would have returned is gone.  With it on a submit is seven launches (nine with the detector) whatever the number of
+ * blocks (crsdr_caf_last_submit). */
+int crsdr_caf_set_cancel(crsdr_caf *caf, const crsdr_caf_cancel_desc *desc);
+
+/* Waits for the last submit and copies out what is asked for (either pointer may be NULL), laid out as above.  CRSDR_ESTATE with the
+ * canceller off, or before the first submit since it was set. */
+int crsdr_caf_fetch_cancel(crsdr_caf *caf, float *coef, float *cinfo);
+
+/* Device addresses of coef and cinfo ([max_batch / frames] lines each).  They change with every crsdr_caf_set_cancel.  CRSDR_ESTATE
+ * with the canceller off. */
+int crsdr_caf_cancel_device_buffers(crsdr_caf *caf, void **coef, void **cinfo);
+
+/* crsdr_ambiguity with the canceller: its arguments, then taps, dopp and the two further outputs coef [nrows][n][2] and
+ * cinfo [nrows][2] (either may be NULL; with mem_kind CRSDR_MEM_DEVICE 4-byte aligned).  The same kernels on the same arguments as the
+ * engine, bit for bit. */
+int crsdr_ambiguity_cancel(float *chi, float *map, float *peak, const int8_t *matrix, int nrows, int blocksize, int seg, int nlags, int ref_row,
+                           int window, int guard, int mem_kind, int taps, int dopp, float *coef, float *cinfo);
+
 #ifdef __cplusplus
 }
 #endif

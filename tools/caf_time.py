@@ -17,6 +17,9 @@ with --cfar, on a second engine with the CFAR detector set (crsdr_caf_set_cfar: 
   get chi    the fetch of chi (pageable host memory, as Caf.fetch returns it) that the detection lists stand in for
   get cfar   the fetch of det + count + snap
 and the bytes of P the detector reads per submit (8 a cell of chi, 4 a cell of map), to set against its kernels' time from a profiler.
+with --cancel K[:P], on a further engine with the canceller set (crsdr_caf_set_cancel: K delays of the reference at -P .. P Doppler bins):
+  caf+cancel as caf with the canceller's five launches in the place of the rows' one, + a fetch of coef and cinfo as well; beside it the
+             fp64 multiply-adds of the subtraction (n complex ones a cell) per second
 
 Every figure is the mean of --reps back-to-back rounds closed by one wait; --runs rounds alternate all variants in one session, medians
 and ranges are reported.  --json FILE keeps the record."""
@@ -54,6 +57,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-model", action="store_true", help="skip the numpy model on one line")
     ap.add_argument("--cfar", action="store_true", help="add the CFAR detector's variants")
+    ap.add_argument("--cancel", metavar="K[:P]", help="add the canceller's variant")
     ap.add_argument("--json")
     a = ap.parse_args()
     sys.path.insert(0, ROOT)
@@ -102,6 +106,18 @@ def main():
             cfd = b.Caf(nrows, B, SEG, lags, 0, b.WINDOW_HANN, GUARD, max_batch=T, frames=FRAMES)
             cfd.set_cfar(b.cfar_desc(alpha=b.cfar_alpha(1e-6, 90), gd=1, gr=1, td=3, tr=4, max_det=16))
 
+        cfc, basis = None, 0
+        if a.cancel:
+            taps, dopp = (int(v) for v in (a.cancel + ":0").split(":")[:2])
+            cfc = b.Caf(nrows, B, SEG, lags, 0, b.WINDOW_HANN, GUARD, max_batch=T, frames=FRAMES)
+            cfc.set_cancel(taps, dopp)
+            basis = taps * (2 * dopp + 1)
+
+        def caf_cancel(i):
+            cfc.submit(pk, plan.packet_stride, plan.matrix_offset, T)
+            cfc.fetch(chi=False, map=False)
+            cfc.fetch_cancel()
+
         def caf_cfar(i):
             cfd.submit(pk, plan.packet_stride, plan.matrix_offset, T)
             cfd.fetch(chi=False, map=False)
@@ -119,6 +135,8 @@ def main():
             variants["caf+cfar"] = lambda: _mean(caf_cfar, lambda: None, a.reps)
             variants["get chi"] = lambda: _mean(lambda i: cf.fetch(map=False, peak=False), lambda: None, a.reps)
             variants["get cfar"] = lambda: _mean(lambda i: cfd.fetch_cfar(), lambda: None, a.reps)
+        if a.cancel:
+            variants["caf+cancel"] = lambda: _mean(caf_cancel, lambda: None, a.reps)
         plan.submit(d_in.data_ptr(), seq=0, flags=b.REFNOISE_ENABLED, nblocks=T, block_stride=nrows * B)      # lags and phasors for the locked submits
         plan.sync()
         for fn in variants.values():             # warm-up: code objects, allocations
@@ -142,6 +160,8 @@ def main():
                 note = f"  ({8 * cells / (med * 1e-3) / 1e9:.1f} GB/s of chi stored, {macs / (med * 1e-3) / 1e12:.2f} T complex int8 MAC/s)"
             if k == "caf+cfar":
                 note = f"  (+{med - shape['ms']['caf']['median']:.3f} ms behind caf; the detector reads {(T // FRAMES) * nd * lags * (8 * nrows + 4) / 1e6:.1f} MB of P)"
+            if k == "caf+cancel":
+                note = f"  (+{med - shape['ms']['caf']['median']:.3f} ms behind caf; {basis} complex fp64 multiply-adds a cell, {basis * cells / (med * 1e-3) / 1e9:.1f} G/s over the submit)"
             if k == "get chi":
                 note = f"  ({8 * cells / 1e6:.1f} MB)"
             if k == "get cfar":
@@ -164,6 +184,8 @@ def main():
         cf.close()
         if cfd:
             cfd.close()
+        if cfc:
+            cfc.close()
         sp.close()
         host.close()
         plan.close()
