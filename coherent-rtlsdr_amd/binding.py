@@ -53,7 +53,11 @@ ABI_SYMBOLS = [
     "crsdr_caf_device_buffers", "crsdr_caf_last_submit", "crsdr_ambiguity",
     "crsdr_caf_set_cfar", "crsdr_caf_fetch_cfar", "crsdr_caf_cfar_device_buffers", "crsdr_cfar", "crsdr_cfar_alpha",
     "crsdr_caf_set_cancel", "crsdr_caf_fetch_cancel", "crsdr_caf_cancel_device_buffers", "crsdr_ambiguity_cancel",
+    "crsdr_caf_set_bearing", "crsdr_caf_fetch_bearing", "crsdr_caf_bearing_device_buffers", "crsdr_bearing",
 ]
+BEARING_CONVENTIONAL, BEARING_ADAPTIVE = 1, 2
+BEARING_KEEP_SPECTRUM = 1
+BEARING_ZERO, BEARING_IDENTITY, BEARING_CELL = 1, 2, 4        # status bits 0, 1, 2: all-zero snapshot; W = I; a cell outside the map
 REFCANCEL_SINGULAR, REFCANCEL_IDLE = 1, 2                     # status bit 0: the solve failed (g = 0); 2: the pass did not run
 REFCANCEL_MAX_TAPS = 9
 ESPRIT_OFF, ESPRIT_BESIDE, ESPRIT_ONLY = 0, 1, 2
@@ -124,6 +128,13 @@ class CfarDesc(C.Structure):
 class CancelDesc(C.Structure):
     """crsdr_caf_cancel_desc: the reference's delays 0 .. taps - 1, each shifted by -dopp .. dopp Doppler bins."""
     _fields_ = [("taps", C.c_int32), ("dopp", C.c_int32)]
+
+
+class BearingDesc(C.Structure):
+    """crsdr_caf_bearing_desc: the mx x my array of the rows other than the reference, the scan grid, the spacing in wavelengths, the
+    mode with its loading, the zoom levels and the flags."""
+    _fields_ = [("mx", C.c_int32), ("my", C.c_int32), ("ncx", C.c_int32), ("ncy", C.c_int32), ("d", C.c_float), ("mode", C.c_int32),
+                ("loading", C.c_float), ("levels", C.c_int32), ("flags", C.c_uint32)]
 
 
 _lib = None
@@ -293,6 +304,11 @@ def lib():
         L.crsdr_caf_fetch_cancel.argtypes = [vp, f32p, f32p]
         L.crsdr_caf_cancel_device_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         L.crsdr_ambiguity_cancel.argtypes = [f32p, f32p, f32p, C.POINTER(C.c_int8)] + [C.c_int] * 10 + [f32p, f32p]
+    if hasattr(L, "crsdr_bearing"):                  # (likewise: an older build has no bearings)
+        L.crsdr_caf_set_bearing.argtypes = [vp, C.POINTER(BearingDesc)]
+        L.crsdr_caf_fetch_bearing.argtypes = [vp, f32p, f32p]
+        L.crsdr_caf_bearing_device_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+        L.crsdr_bearing.argtypes = [f32p, f32p, f32p] + [C.c_int] * 5 + [f32p, i32p, C.POINTER(CfarDesc), C.POINTER(BearingDesc), C.c_int]
     _lib = L
     return L
 
@@ -698,6 +714,33 @@ def cfar_device(det_ptr: int, count_ptr: int, src_ptr: int, comps, nd, R, guard,
     cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
     _check(lib().crsdr_cfar(cast(det_ptr, C.c_float), cast(count_ptr, C.c_int32), cast(src_ptr, C.c_float), int(comps), int(nd), int(R), int(guard), C.byref(desc),
                             MEM_DEVICE))
+
+
+def bearing_desc(mx, my, d, ncx=100, ncy=100, mode=BEARING_CONVENTIONAL, loading=1e-2, levels=0, flags=0):
+    return BearingDesc(int(mx), int(my), int(ncx), int(ncy), float(d), int(mode), float(loading), int(levels), int(flags))
+
+
+def bearing(chi, det, count, ref_row, guard, cfar, desc):
+    """crsdr_bearing on ONE line: chi [nrows][nd][R] complex64, the array map's det [K][8] float32 and count as cfar() or Caf.fetch_cfar
+    gave them -> (dir [K][8] float32 = cx, cy, T, dx, dy, alpha, beta, status; spec [K][ncx][ncy] float32 or None without
+    BEARING_KEEP_SPECTRUM).  The engine's bearings (Caf.set_bearing) on one line, bit for bit."""
+    a = np.ascontiguousarray(chi, dtype=np.complex64)
+    nrows, nd, R = a.shape
+    K = int(cfar.max_det)
+    t = np.ascontiguousarray(det, dtype=np.float32).reshape(K, 8)
+    n = np.array([count], dtype=np.int32).reshape(1)
+    out = np.zeros((K, 8), dtype=np.float32)
+    spec = np.zeros((K, desc.ncx, desc.ncy), dtype=np.float32) if desc.flags & BEARING_KEEP_SPECTRUM else None
+    _check(lib().crsdr_bearing(_p(out, C.c_float), _p(spec, C.c_float), _p(a.view(np.float32), C.c_float), nrows, nd, R, int(ref_row), int(guard), _p(t, C.c_float),
+                               _p(n, C.c_int32), C.byref(cfar), C.byref(desc), MEM_HOST))
+    return out, spec
+
+
+def bearing_device(dir_ptr: int, spec_ptr: int, chi_ptr: int, nrows, nd, R, ref_row, guard, det_ptr: int, count_ptr: int, cfar, desc):
+    """crsdr_bearing with CRSDR_MEM_DEVICE: every pointer on the device (dir or spec, not both, may be 0)."""
+    cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
+    _check(lib().crsdr_bearing(cast(dir_ptr, C.c_float), cast(spec_ptr, C.c_float), cast(chi_ptr, C.c_float), int(nrows), int(nd), int(R), int(ref_row), int(guard),
+                               cast(det_ptr, C.c_float), cast(count_ptr, C.c_int32), C.byref(cfar), C.byref(desc), MEM_DEVICE))
 
 
 def ambiguity_device(chi_ptr: int, map_ptr: int, peak_ptr: int, matrix_ptr: int, nrows, B, seg, nlags, ref_row, window, guard):
@@ -1420,6 +1463,27 @@ class Caf:
         ptrs = [C.c_void_p() for _ in range(3)]
         _check(lib().crsdr_caf_cfar_device_buffers(self._h, *[C.byref(p) for p in ptrs]))
         return dict(zip(("det", "count", "snap"), [p.value for p in ptrs]))
+
+    def set_bearing(self, desc: "BearingDesc | None"):
+        """crsdr_caf_set_bearing: a direction per detection of the array map behind every submit (None: off).  Between submits, with the
+        detector on."""
+        _check(lib().crsdr_caf_set_bearing(self._h, None if desc is None else C.byref(desc)))
+        self.grid = None if desc is None else (int(desc.ncx), int(desc.ncy), bool(desc.flags & BEARING_KEEP_SPECTRUM))
+
+    def fetch_bearing(self, dir=True, spec=None) -> dict:
+        """Waits for the last submit.  dir [nest][K][8] = cx, cy, T, dx, dy, alpha, beta, status; spec [nest][K][ncx][ncy] (by default
+        where it is kept)."""
+        n, K = self._last()[0], max(1, getattr(self, "max_det", 0))
+        ncx, ncy, kept = getattr(self, "grid", None) or (1, 1, False)
+        d = np.zeros((n, K, 8), dtype=np.float32) if dir else None
+        s = np.zeros((n, K, ncx, ncy), dtype=np.float32) if (kept if spec is None else spec) else None
+        _check(lib().crsdr_caf_fetch_bearing(self._h, _p(d, C.c_float), _p(s, C.c_float)))
+        return {k: v for k, v in (("dir", d), ("spec", s)) if v is not None}
+
+    def bearing_device_buffers(self) -> dict:
+        ptrs = [C.c_void_p() for _ in range(2)]
+        _check(lib().crsdr_caf_bearing_device_buffers(self._h, *[C.byref(p) for p in ptrs]))
+        return dict(zip(("dir", "spec"), [p.value for p in ptrs]))
 
     def set_cancel(self, taps: "int | None", dopp: int = 0):
         """crsdr_caf_set_cancel: the canceller in front of every submit's Doppler stage (taps None: off).  Between submits."""

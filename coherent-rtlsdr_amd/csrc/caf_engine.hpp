@@ -7,9 +7,12 @@
 //     the detection lists and the array map's snapshots.  Its buffers are made by set_cfar, between submits.
 //     With a canceller set (crsdr_caf_set_cancel; caf_cancel.hpp, caf_cancel_solve.hpp) five launches take the place of the rows' one:
 //     the reference's sums, the rows' first lags, the normal equations' sums, factor and solves, and the rows with the subtraction.
+//     With bearings set (crsdr_caf_set_bearing; caf_bearing.hpp, caf_bearing_solve.hpp) three more behind the detector's: the slots'
+//     records, the scan's tiles, and the merge with the zoom search.  Its buffers are made by set_bearing, between submits.
 #pragma once
 
 #include "caf.hpp"
+#include "caf_bearing.hpp"
 #include "caf_cancel.hpp"
 #include "caf_cfar_kernels.hpp"
 
@@ -28,7 +31,7 @@
     default: { constexpr int LG = 12; launch; } break;                              \
     }
 
-constexpr int kCafLaunches = 3, kCafCfarLaunches = 2, kCafCancelLaunches = 4;      // (the canceller's five take the place of one)
+constexpr int kCafLaunches = 3, kCafCfarLaunches = 2, kCafCancelLaunches = 4, kCafBearingLaunches = 3;      // (the canceller's five take the place of one)
 constexpr long long kCafMaxCells = 1ll << 24;           // (max_batch / frames) * nrows * nd * nlags
 
 // the canceller's device memory for `lines` lines: the engine's own buffers, or parts of one per-op slot
@@ -66,6 +69,14 @@ struct crsdr_caf {
         DevBuf<float> coef, cinfo;
         CancelBufs bufs() const { return CancelBufs{taps, dopp, G, Y, ph, S, C, W, h, E, status, coef, cinfo}; }
     } cn;
+    // crsdr_caf_set_bearing: on (false = off), the slots' records [lines][K][brg::REC], the tiles' maxima and the results
+    struct Bearing {
+        bool on = false, submitted = false;
+        brg::Params prm{};
+        DevBuf<double> rec;
+        DevBuf<bearing::Best> tbest;
+        DevBuf<float> dir, spec;
+    } bg;
     hipStream_t last_stream = nullptr;
     int last_nest = 0, last_launches = 0;
     bool submitted = false;
@@ -198,6 +209,48 @@ static int cfar_enqueue(hipStream_t S, const float2 *chi, const float *map, int 
     return CRSDR_OK;
 }
 
+// every limit of the bearings of section (w), for crsdr_caf_set_bearing and crsdr_bearing
+static int bearing_args_ok(const char *who, int nrows, long long lines, int K, const crsdr_caf_bearing_desc *d, brg::Params *prm)
+{
+    *prm = brg::Params{d->mx, d->my, d->ncx, d->ncy, d->d, d->mode, d->loading, d->levels, d->flags};
+    switch (brg::bad_limit(nrows, lines, K, *prm)) {
+    case 0: return CRSDR_OK;
+    case 1: return fail(CRSDR_EINVAL, "%s: mx, my = %d, %d (at least 1)", who, d->mx, d->my);
+    case 2: return fail(CRSDR_EINVAL, "%s: mx my = %lld (nrows - 1 = %d, in 2..%d)", who, (long long)d->mx * d->my, nrows - 1, brg::MAX_M);
+    case 3: return fail(CRSDR_EINVAL, "%s: ncx, ncy = %d, %d (%d..%d)", who, d->ncx, d->ncy, brg::MIN_NC, brg::MAX_NC);
+    case 4: return fail(CRSDR_EINVAL, "%s: d = %g (finite and greater than 0)", who, (double)d->d);
+    case 5: return fail(CRSDR_EINVAL, "%s: mode = %d", who, d->mode);
+    case 6: return fail(CRSDR_EINVAL, "%s: loading = %g (1e-6..1)", who, (double)d->loading);
+    case 7: return fail(CRSDR_EINVAL, "%s: levels = %d (0..%d)", who, d->levels, brg::MAX_LEVELS);
+    case 8: return fail(CRSDR_EINVAL, "%s: flags = 0x%x", who, d->flags);
+    default: return fail(CRSDR_EINVAL, "%s: (max_batch / frames) * max_det * ncx * ncy = %lld (at most 2^24 with the spectrum kept)", who, lines * K * d->ncx * d->ncy);
+    }
+}
+
+// k_bearing_slot's LDS at its largest: above the 64 KiB default.  One value for every caller, so that no call lowers another's.
+static int bearing_lds_limit()
+{
+    HIP_TRY(hipFuncSetAttribute((const void *)bearing::k_bearing_slot, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bearing::slot_lds_bytes(brg::MAX_M, cfar::MAX_HR)));
+    return CRSDR_OK;
+}
+
+// the bearings' three launches, for the object and for crsdr_bearing: the same kernels on the same arguments, so the same bits.
+// det, count: the array map's entry of the first line.
+static int bearing_enqueue(hipStream_t S, const float2 *chi, const float *det, size_t det_stride, const int32_t *count, size_t count_stride, int nest, int nrows, int nd,
+                           int R, int ref_row, int guard, const cfar::Params &cp, const brg::Params &bp, double *rec, bearing::Best *tbest, float *dir, float *spec)
+{
+    const int K = cp.max_det, tiles = bearing::tiles_of(bp.ncx, bp.ncy);
+    hipLaunchKernelGGL(bearing::k_bearing_slot, dim3((unsigned)K, (unsigned)nest), dim3(bearing::THREADS), bearing::slot_lds_bytes(bp.mx * bp.my, cp.gr + cp.tr), S, chi, det,
+                       det_stride, count, count_stride, nrows, nd, R, ref_row, guard, cp, bp, K, rec);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(bearing::k_bearing_scan, dim3((unsigned)tiles, (unsigned)K, (unsigned)nest), dim3(bearing::THREADS), 0, S, (const double *)rec, bp, K, spec, tbest);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(bearing::k_bearing_finish, dim3((unsigned)K, (unsigned)nest), dim3(bearing::FIN_THREADS), 0, S, (const double *)rec, (const bearing::Best *)tbest, tiles,
+                       bp, K, dir);
+    HIP_TRY(hipGetLastError());
+    return CRSDR_OK;
+}
+
 static void caf_free(crsdr_caf *q)
 {
     if (!q) return;
@@ -258,6 +311,12 @@ static int caf_launch(crsdr_caf *q, const int8_t *packets, size_t packet_stride,
                                  q->cf.det, q->cf.count, q->cf.snap);
     if (rc2) return rc2;
     q->cf.submitted = true; q->last_launches += kCafCfarLaunches;
+    if (!q->bg.on) return CRSDR_OK;
+    const size_t K = (size_t)q->cf.prm.max_det, entries = (size_t)(q->nrows + 1);
+    const int rc3 = bearing_enqueue(S, q->chi, q->cf.det.p + (size_t)q->nrows * K * 8, entries * K * 8, q->cf.count.p + q->nrows, entries, q->last_nest, q->nrows, q->nd,
+                                    q->nlags, q->ref_row, q->guard, q->cf.prm, q->bg.prm, q->bg.rec, q->bg.tbest, q->bg.dir, q->bg.spec);
+    if (rc3) return rc3;
+    q->bg.submitted = true; q->last_launches += kCafBearingLaunches;
     return CRSDR_OK;
 }
 
@@ -322,6 +381,7 @@ extern "C" int crsdr_caf_device_buffers(crsdr_caf *q, void **chi, void **map, vo
 extern "C" int crsdr_caf_set_cfar(crsdr_caf *q, const crsdr_cfar_desc *desc)
 {
     if (!q) return fail(CRSDR_EINVAL, "caf_set_cfar: NULL caf");
+    if (q->bg.on) return fail(CRSDR_ESTATE, "caf_set_cfar: bearings are on (crsdr_caf_set_bearing): their buffers and training set are this detector's; turn them off first");
     cfar::Params prm{};
     if (desc) { const int rc_ = cfar_args_ok("caf_set_cfar", q->nd, desc, &prm); if (rc_) return rc_; }
     HIP_TRY(hipSetDevice(q->device));
@@ -363,6 +423,95 @@ extern "C" int crsdr_caf_cfar_device_buffers(crsdr_caf *q, void **det, void **co
     if (count) *count = q->cf.count;
     if (snap) *snap = q->cf.snap;
     return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_set_bearing(crsdr_caf *q, const crsdr_caf_bearing_desc *desc)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_set_bearing: NULL caf");
+    const size_t lines = (size_t)(q->max_batch / q->frames);
+    brg::Params prm{};
+    if (desc) {
+        // (the detector off: the limits that need its K are checked with K = 1, and the call is refused for the state below)
+        const int rc_ = bearing_args_ok("caf_set_bearing", q->nrows, (long long)lines, q->cf.on ? q->cf.prm.max_det : 1, desc, &prm);
+        if (rc_) return rc_;
+        if (!q->cf.on) return fail(CRSDR_ESTATE, "caf_set_bearing: no detector set (crsdr_caf_set_cfar): there are no detections to take a bearing of");
+    }
+    HIP_TRY(hipSetDevice(q->device));
+    if (q->submitted) HIP_TRY(hipDeviceSynchronize());      // the last submit may still write the buffers let go here
+    q->bg = crsdr_caf::Bearing();
+    if (!desc) return CRSDR_OK;
+    const size_t K = (size_t)q->cf.prm.max_det, npts = (size_t)prm.ncx * (size_t)prm.ncy, tiles = (size_t)bearing::tiles_of(prm.ncx, prm.ncy);
+    crsdr_caf::Bearing &g = q->bg;
+    int r = CRSDR_OK;
+    if ((r = g.rec.alloc(lines * K * brg::REC)) || (r = g.tbest.alloc(lines * K * tiles)) || (r = g.dir.alloc(lines * K * 8)) ||
+        ((prm.flags & brg::KEEP_SPECTRUM) && (r = g.spec.alloc(lines * K * npts))) || (r = bearing_lds_limit())) {
+        q->bg = crsdr_caf::Bearing();
+        return r;
+    }
+    g.prm = prm; g.on = true;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_fetch_bearing(crsdr_caf *q, float *dir, float *spec)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_fetch_bearing: NULL caf");
+    if (!q->bg.on) return fail(CRSDR_ESTATE, "caf_fetch_bearing: no bearings set (crsdr_caf_set_bearing)");
+    if (!q->bg.submitted) return fail(CRSDR_ESTATE, "caf_fetch_bearing: nothing submitted since the bearings were set");
+    if (spec && !q->bg.spec.p) return fail(CRSDR_ESTATE, "caf_fetch_bearing: the spectrum is not kept (CRSDR_BEARING_KEEP_SPECTRUM)");
+    HIP_TRY(hipSetDevice(q->device));
+    const size_t slots = (size_t)q->last_nest * (size_t)q->cf.prm.max_det, npts = (size_t)q->bg.prm.ncx * (size_t)q->bg.prm.ncy;
+    if (dir) HIP_TRY(hipMemcpyAsync(dir, q->bg.dir.p, sizeof(float) * slots * 8, hipMemcpyDeviceToHost, q->last_stream));
+    if (spec) HIP_TRY(hipMemcpyAsync(spec, q->bg.spec.p, sizeof(float) * slots * npts, hipMemcpyDeviceToHost, q->last_stream));
+    HIP_TRY(hipStreamSynchronize(q->last_stream));
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_bearing_device_buffers(crsdr_caf *q, void **dir, void **spec)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_bearing_device_buffers: NULL caf");
+    if (!q->bg.on) return fail(CRSDR_ESTATE, "caf_bearing_device_buffers: no bearings set (crsdr_caf_set_bearing)");
+    if (dir) *dir = q->bg.dir;
+    if (spec) *spec = q->bg.spec;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_bearing(float *dir, float *spec, const float *chi, int nrows, int nd, int R, int ref_row, int guard, const float *det, const int32_t *count,
+                             const crsdr_cfar_desc *cdesc, const crsdr_caf_bearing_desc *bdesc, int mem_kind)
+{
+    if (!chi || !det || !count || !cdesc || !bdesc || (!dir && !spec)) return fail(CRSDR_EINVAL, "bearing: need chi, det, count, both descriptors and at least one of dir, spec");
+    const int lgd = nd >= 1 && nd <= (1 << caf::CAF_MAX_LOG2) ? ilog2_exact(nd) : -1;
+    if (lgd < caf::CAF_MIN_LOG2) return fail(CRSDR_EINVAL, "bearing: nd = %d (a power of two in [8, 4096])", nd);
+    if (R < 1 || R > caf::CAF_MAX_LAGS) return fail(CRSDR_EINVAL, "bearing: R = %d (1..%d)", R, caf::CAF_MAX_LAGS);
+    if (nrows < 2 || (long long)nrows * nd * R > kCafMaxCells) return fail(CRSDR_EINVAL, "bearing: nrows = %d (at least 2, nrows * nd * R at most 2^24)", nrows);
+    if (ref_row < 0 || ref_row >= nrows) return fail(CRSDR_EINVAL, "bearing: ref_row = %d (0..%d)", ref_row, nrows - 1);
+    if (guard < 0 || guard > nd / 2) return fail(CRSDR_EINVAL, "bearing: guard = %d (0..nd / 2 = %d)", guard, nd / 2);
+    cfar::Params cp{};
+    brg::Params bp{};
+    { const int rc_ = cfar_args_ok("bearing", nd, cdesc, &cp); if (rc_) return rc_; }
+    { const int rc_ = bearing_args_ok("bearing", nrows, 1, cp.max_det, bdesc, &bp); if (rc_) return rc_; }
+    if (spec && !(bp.flags & brg::KEEP_SPECTRUM)) return fail(CRSDR_EINVAL, "bearing: spec asked for without CRSDR_BEARING_KEEP_SPECTRUM");
+    OP_PROLOGUE_MEM("bearing", mem_kind);
+    const size_t cells = (size_t)nd * (size_t)R, K = (size_t)cp.max_det, npts = (size_t)bp.ncx * (size_t)bp.ncy, tiles = (size_t)bearing::tiles_of(bp.ncx, bp.ncy);
+    const size_t cb = sizeof(float2) * (size_t)nrows * cells, tb = sizeof(float) * K * 8, nb = sizeof(int32_t), db = sizeof(float) * K * 8, sb = sizeof(float) * K * npts;
+    const bool keep = (bp.flags & brg::KEEP_SPECTRUM) != 0;
+    OpStage st(mem_kind);
+    const float2 *d_c = (const float2 *)st.in(0, chi, cb, 8);
+    const float *d_t = (const float *)st.in(1, det, tb, 4);
+    const int32_t *d_n = (const int32_t *)st.in(2, count, nb, 4);
+    float *d_d = (float *)st.out(3, dir, db, 4);
+    float *d_s = keep ? (float *)st.out(4, spec, sb, 4) : nullptr;
+    if (st.rc) return st.rc;
+    if (st.misaligned) return fail(CRSDR_EINVAL, "bearing: device det, count, dir and spec 4-byte, chi 8-byte aligned");
+    // (device memory and an output not asked for: the kernels write it all the same)
+    if (!d_d) { OP_RESERVE(3, db); d_d = (float *)g_op.buf[3]; }
+    if (keep && !d_s) { OP_RESERVE(4, sb); d_s = (float *)g_op.buf[4]; }
+    OP_RESERVE(5, sizeof(double) * K * brg::REC);
+    OP_RESERVE(6, sizeof(bearing::Best) * K * tiles);
+    { const int rc_ = bearing_lds_limit(); if (rc_) return rc_; }
+    { const int rc_ = bearing_enqueue(0, d_c, d_t, 0, d_n, 0, 1, nrows, nd, R, ref_row, guard, cp, bp, (double *)g_op.buf[5], (bearing::Best *)g_op.buf[6], d_d, d_s); if (rc_) return rc_; }
+    st.back(dir, d_d, db);
+    if (keep) st.back(spec, d_s, sb);
+    return st.finish();
 }
 
 extern "C" int crsdr_caf_set_cancel(crsdr_caf *q, const crsdr_caf_cancel_desc *desc)

@@ -9,6 +9,8 @@ static_assert(sizeof(peak_t) == 6 * sizeof(float), "peak_t is crsdr_caf's six fl
 
 static_assert(sizeof(det_t) == 8 * sizeof(float), "det_t is the detector's eight floats");
 
+static_assert(sizeof(dir_t) == 8 * sizeof(float), "dir_t is the bearings' eight floats");
+
 double det_t::snr_db() const { return snr > 0.f ? 10.0 * std::log10((double)snr) : -INFINITY; }
 double peak_t::power_db() const { return power > 0.f ? 10.0 * std::log10((double)power) : -INFINITY; }
 double peak_t::ratio_db() const { return ratio > 0.f ? 10.0 * std::log10((double)ratio) : -INFINITY; }
@@ -60,6 +62,28 @@ int batch::fetch_cfar(bool want_snap)
     }
     if (!rc) nlines = nest;
     if (rc && cf && kdet) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::set_bearing(const crsdr_caf_bearing_desc *desc)
+{
+    int rc = cf ? crsdr_caf_set_bearing(cf, desc) : CRSDR_ESTATE;
+    if (!rc) { bearings = desc != nullptr; npts = desc && (desc->flags & CRSDR_BEARING_KEEP_SPECTRUM) ? desc->ncx * desc->ncy : 0; dir.clear(); spec.clear(); }
+    if (rc && cf) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::fetch_bearing(bool want_spec)
+{
+    int nest = 0;
+    int rc = !cf || !bearings ? CRSDR_ESTATE : crsdr_caf_last_submit(cf, &nest, nullptr);
+    if (!rc) {
+        want_spec = want_spec && npts > 0;
+        dir.assign((size_t)nest * kdet, dir_t{}); spec.assign(want_spec ? (size_t)nest * kdet * npts : 0, 0.f);
+        rc = crsdr_caf_fetch_bearing(cf, &dir[0].cx, want_spec ? spec.data() : nullptr);
+    }
+    if (!rc) nlines = nest;
+    if (rc && cf && bearings) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
     return rc;
 }
 

@@ -24,11 +24,19 @@ struct det_t {
     double snr_db() const;                           // the cell above its training cells' mean; -inf for 0
 };
 
+// (cx, cy, fit = T at the grid peak, dx, dy, alpha, beta, status) of one detection's bearing, as crsdr_caf's bearings lay them out
+struct dir_t {
+    float cx, cy, fit, dx, dy, alpha, beta, status;
+    double alpha_deg() const { return (double)alpha * (180.0 / 3.14159265358979323846); }
+    double beta_deg() const { return (double)beta * (180.0 / 3.14159265358979323846); }
+};
+
 // One line per `frames` consecutive packets of a submit: chi [nrows][nd][nlags] of every row against row ref_row over seg-sample
 // segments, the array map [nd][nlags], and nrows + 1 peaks (the rows', then the map's) searched outside |Doppler| < guard.
 class batch {
     crsdr_caf *cf = nullptr;
-    int rows, bins, lags, kdet = 0, nbasis = 0;
+    int rows, bins, lags, kdet = 0, nbasis = 0, npts = 0;
+    bool bearings = false;
 
 public:
     batch(int nrows, int blocksize, int max_batch, int seg, int nlags, int ref_row = 0, int window = CRSDR_WINDOW_RECT, int guard = 0, int frames = 1, int device = 0);
@@ -50,6 +58,11 @@ public:
     int set_cancel(const crsdr_caf_cancel_desc *desc);
     // waits, and fills cinfo, and coef if asked for; CRSDR_ESTATE with the canceller off
     int fetch_cancel(bool want_coef = true);
+    // a direction per detection of the array map behind every later submit (crsdr_caf_set_bearing; NULL: off).  Between submits, with
+    // the detector on; while it is on set_cfar is refused.
+    int set_bearing(const crsdr_caf_bearing_desc *desc);
+    // waits, and fills dir beside det, and spec if asked for and kept; CRSDR_ESTATE with the bearings off
+    int fetch_bearing(bool want_spec = false);
     int basis() const { return nbasis; }             // taps (2 dopp + 1), 0 with the canceller off
     int lines() const { return nlines; }
     int nrows() const { return rows; }
@@ -63,6 +76,9 @@ public:
     std::vector<det_t> det;                          // [lines][nrows + 1][max_det]: the strongest first, zeros behind the last
     std::vector<int32_t> count;                      // [lines][nrows + 1]: detected cells, which may be more than max_det
     std::vector<float> snap;                         // [lines][max_det][nrows][2]: chi of every row at the array map's detections
+    std::vector<dir_t> dir;                          // [lines][max_det]: the bearing of the array map's detection k, zeros behind the last
+    std::vector<float> spec;                         // [lines][max_det][ncx][ncy]: T on the grid, where kept and asked for
+    const dir_t &bearing(int e, int k) const { return dir[(size_t)e * kdet + k]; }
     std::vector<float> coef;                         // [lines][nrows][basis][2]: the canceller's filter of every row
     std::vector<float> cinfo;                        // [lines][nrows][2]: the share of the row's power that stays, and the status
     float residual(int e, int c) const { return cinfo[2 * ((size_t)e * rows + c)]; }

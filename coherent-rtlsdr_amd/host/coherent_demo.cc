@@ -70,7 +70,8 @@ int main(int argc, char **argv)
     bool cfar_on = false;
     double cfar_db = 0.0;
     crsdr_cfar_desc cfar = {1, 1, 3, 4, 0.f, 1, 16};
-    bool cancel_on = false;
+    bool cancel_on = false, bearing_on = false;
+    crsdr_caf_bearing_desc bearing = {0, 0, 100, 100, 0.5f, CRSDR_BEARING_CONVENTIONAL, 1e-2f, 0, 0u};
     crsdr_caf_cancel_desc cancel = {0, 0};
     bool engine_batches = false;
     int ranks = 1, rank = 0, device = 0;
@@ -163,6 +164,18 @@ int main(int argc, char **argv)
             cancel_on = true;
             if (n < 1) cancel.taps = -1;                                                     // (refused below with the rest)
         }
+        // with --caf and --cfar: a direction per detection of the array map (crsdr_caf_set_bearing), the signal rows as an MX x MY array on
+        // an NC x NC grid (100); --adaptive LOADING whitens with the training cells' covariance, --bearing-levels L refines off the grid.
+        // Prints one line per (batch, line, detection): cell, angles in degrees, fit
+        else if (a == "--bearing" && i + 1 < argc) {
+            int nc = 100;
+            const int n = std::sscanf(argv[++i], "%dx%d:%d", &bearing.mx, &bearing.my, &nc);
+            bearing_on = true;
+            bearing.ncx = bearing.ncy = nc;
+            if (n < 2) bearing.mx = -1;                                                      // (refused below with the rest)
+        }
+        else if (a == "--adaptive" && i + 1 < argc) { bearing.mode = CRSDR_BEARING_ADAPTIVE; bearing.loading = (float)std::atof(argv[++i]); }
+        else if (a == "--bearing-levels") val(bearing.levels);
         else if (a == "--guard") val(caf_guard);
         else if (a == "--band" && i + 1 < argc) { if (std::sscanf(argv[++i], "%d:%d", &sp_band_lo, &sp_band_hi) != 2) sp_nfft = -1; }
         else if (a == "--window" && i + 1 < argc) {
@@ -544,11 +557,16 @@ int main(int argc, char **argv)
             if (!caf || !caf->ok()) { std::printf("caf: --caf SEG:LAGS[:REF] [--caf-frames F] [--guard G] [--window rect|hann] refused\nDEMO FAILED\n"); return 1; }
             if (cfar_on && caf->set_cfar(&cfar)) { std::printf("cfar: --cfar SNR_DB[:GD:GR:TD:TR] [--max-det K] refused\nDEMO FAILED\n"); return 1; }
             if (cancel_on && caf->set_cancel(&cancel)) { std::printf("cancel: --cancel K[:P] refused\nDEMO FAILED\n"); return 1; }
+            if (bearing_on && !cfar_on) { std::printf("bearing: --bearing needs --cfar: there are no detections to take a bearing of\nDEMO FAILED\n"); return 1; }
+            if (bearing_on && caf->set_bearing(&bearing)) {
+                std::printf("bearing: --bearing MXxMY[:NC] [--adaptive LOADING] [--bearing-levels L] refused (MX MY must be --nsig = %d)\nDEMO FAILED\n", nsig);
+                return 1;
+            }
         }
         auto ambiguity = [&](int b) {
             if (!caf || !ok) return;
             ok = caf->submit(coherent.engine_plan()) == CRSDR_OK && caf->fetch() == CRSDR_OK && (!cfar_on || caf->fetch_cfar() == CRSDR_OK) &&
-                 (!cancel_on || caf->fetch_cancel(false) == CRSDR_OK);
+                 (!cancel_on || caf->fetch_cancel(false) == CRSDR_OK) && (!bearing_on || caf->fetch_bearing() == CRSDR_OK);
             if (!ok || !report) return;
             for (int e = 0; cancel_on && e < caf->lines(); ++e) {
                 double sum = 0.0;
@@ -563,6 +581,12 @@ int main(int argc, char **argv)
                     const ccaf::det_t &d = caf->detection(e, caf->nrows(), k);
                     std::printf("cfar: batch %d line %d det %d of %d: lag %d%+.3f doppler %d%+.3f snr %.2f dB\n", b, e, k, (int)caf->count[(size_t)e * (caf->nrows() + 1) + caf->nrows()],
                                 (int)d.lag, (double)d.dlag, (int)d.doppler, (double)d.ddop, d.snr_db());
+                }
+            for (int e = 0; bearing_on && e < caf->lines(); ++e)
+                for (int k = 0; k < caf->held(e, caf->nrows()); ++k) {
+                    const ccaf::dir_t &d = caf->bearing(e, k);
+                    std::printf("bearing: batch %d line %d det %d: cell (%d, %d) alpha %.3f deg beta %.3f deg fit %.4f\n", b, e, k, (int)d.cx, (int)d.cy, d.alpha_deg(),
+                                d.beta_deg(), (double)d.fit);
                 }
             for (int e = 0; e < caf->lines(); ++e)
                 for (int c = 0; c <= caf->nrows(); ++c) {

@@ -578,7 +578,8 @@ int crsdr_doa_direction_buffers(crsdr_doa *doa, void **found, void **peaks, void
  *   beams      y[t][b][n] = sum_c u[c-1] (I_c[n] + j Q_c[n]) / 127 over the signal rows c = 1 .. m, n < blocksize/2, fp32, NO
  *              conjugate: the covariance is X^H X, the conjugate of E[x x^H], so the steering vector at a MUSIC peak is conj(a_true) and
  *              w^H x with the textbook w = R^-1 a / (a^H R^-1 a) becomes u^T x; sum_c u_c conj(a_c) = 1 is the distortionless constraint.
- *              The mean is not removed from the samples.
+ *              The mean is not removed from the samples.  (crsdr_caf's bearings, section (w), meet the same convention from the
+ *              other side: chi_c carries a_true, so their snapshot is u = conj(chi) and the same emitter gives the same grid cell.)
  *   Slots b >= found[e]: weights 0, power -1, beam samples 0.
  * mode CRSDR_BEAM_OFF frees the buffers (the other arguments are then ignored).  loading in [1e-6, 1] (ignored for CONVENTIONAL).
  * Any time: waits for the device if a submit was made, then allocates weights, power and beams [max_batch][nbeams][blocksize/2][2].
@@ -1223,6 +1224,91 @@ int crsdr_caf_cancel_device_buffers(crsdr_caf *caf, void **coef, void **cinfo);
  * engine, bit for bit. */
 int crsdr_ambiguity_cancel(float *chi, float *map, float *peak, const int8_t *matrix, int nrows, int blocksize, int seg, int nlags, int ref_row,
                            int window, int guard, int mem_kind, int taps, int dopp, float *coef, float *cinfo);
+
+/* Bearings.  A detection of the array map says at which lag and Doppler a target is; snap holds its complex value across the rows.
+ * This stage, behind the detector and on the device, turns every such detection into a direction: a line's result is a list of
+ * (lag, Doppler, bearing) in a few hundred bytes.  It is off until crsdr_caf_set_bearing; off, a submit is the same launches and the
+ * same bits.
+ *
+ * Array.  The rows c != ref_row in ascending order are the elements e = 0 .. m - 1 of an mx x my uniform rectangular array,
+ * m = nrows - 1 = mx my, 2 <= m <= 64, in crsdr_pmusic2d's element order (e = iy mx + ix) and with crsdr_doa_set_refine's fp64
+ * steering expression at the cell coordinates (x, y):
+ *     alpha = x pi / ncx,  beta = y pi / ncy,  ph_e = 2 pi (double)d (ix cos(alpha) sin(beta) + iy cos(beta)),  a_e = (cos ph_e, sin ph_e)
+ * Snapshot.  For slot q < min(count, K) of the array map's detections (entry nrows; K = max_det), at the detection's cell (d*, tau*):
+ *     u_e = conj(chi_c[d*][tau*])      from the published fp32 chi, converted to fp64
+ * The conjugate is deliberate: chi_c carries a_true, and crsdr_doa's X^H X convention (see crsdr_doa_set_beams) peaks at conj(a_true);
+ * with u = conj(x) the same emitter gives the same grid cell from both engines.
+ * Weighting W (m x m Hermitian, fp64).
+ *     CRSDR_BEARING_CONVENTIONAL   W = I
+ *     CRSDR_BEARING_ADAPTIVE       the training set of the cell is exactly the detector's set of that cell (the same gd, gr, td, tr, the
+ *                                  same guard; Doppler wraps, lag does not), so N equals the ntrain the detection reports.  With u_t
+ *                                  the conjugated chi across the elements at a training cell,
+ *                                      Q = (1 / N) sum_train u_t u_t^H,   Q' = Q + loading (trace(Q) / m) I,   W = Q'^-1 by Cholesky.
+ *                                  Q' is positive definite whenever trace(Q) > 0, also for N < m, and cond(Q') <= 1 + m / loading.
+ *                                  N = 0 or trace(Q) = 0: W = I and status bit 1 is set (so, too, for a pivot that is not > 0, which only
+ *                                  a non-finite chi can give).  The order of the sum is not pinned.
+ * The training cells hold the direct path's ambiguity floor, whose spatial signature is the illuminator's direction in every cell and
+ * which pulls a weak target's conventional bearing toward the illuminator; whitening with their covariance removes that bias.
+ * Statistic.
+ *     T(x, y) = |a^H W u|^2 / ((a^H W a) (u^H W u))           in [0, 1] by Cauchy-Schwarz
+ * With W = I it is the share of the snapshot's power that a plane wave from (x, y) explains (the single-source maximum-likelihood
+ * statistic).  The order of the fp64 operations inside T is not pinned; on this array a^H W a is a 2-D trigonometric polynomial whose
+ * coefficients are the sums of W over the element pairs of equal co-array lag, and the device evaluates it so.
+ * u^H u = 0: T = 0 everywhere, every figure of the slot is 0 and status bit 0 is set.  Never a NaN.
+ * The adaptive T is far more selective than the conventional one, the more so the more elements there are and the stronger the
+ * target's own floor in its training cells: the grid must be fine enough to sample its main lobe, or the grid peak is not the
+ * target's (64 elements: a 64 x 64 grid where 32 x 32 serves the conventional mode).
+ * Grid peak.  (cx, cy) is the first maximum of T over cx < ncx, cy < ncy in row-major order (index cx ncy + cy).
+ * Refinement.  levels = 0 (off) or 1 .. 8: the zoom search of crsdr_doa_set_refine, word for word, on f = T -- x = cx, y = cy, s = 1/2;
+ * per level the 7 x 7 lattice of spacing s around (x, y), each point clamped to [0, ncx] x [0, ncy], in row-major order (i major); a
+ * point replaces the best so far if it is strictly above the centre and strictly above the best; then s = s / 4.
+ * Outputs per line:
+ *     dir  [nest][K][8] float           (cx, cy, T at the grid peak, x - cx, y - cy, alpha, beta, status), each figure rounded once from
+ *                                       fp64; the offsets are exact.  levels = 0: offsets 0, the angles are the grid point's.  Slots from
+ *                                       min(count, K) on are all zero.  status: bit 0 an all-zero snapshot, bit 1 W = I in the adaptive
+ *                                       mode, bit 2 (crsdr_bearing on hand-made det only) a lag or Doppler outside the map: figures 0.
+ *     spec [nest][K][ncx][ncy] float    with the flag CRSDR_BEARING_KEEP_SPECTRUM: T of every grid point; unused slots zero
+ * Bits.  Nothing depends on the order in which workgroups run: a line has the same bits wherever it sits in a batch, and crsdr_bearing
+ * launches the same kernels on the same arguments.
+ * Limits, all CRSDR_EINVAL and all checked before a device is touched, by one function for the engine and the per-op call:
+ * mx, my >= 1; m = mx my = nrows - 1 in 2 .. 64; 2 <= ncx, ncy <= 512; d finite and > 0; a valid mode; loading in [1e-6, 1] when
+ * adaptive; levels in 0 .. 8; no unknown flag; with the keep flag (max_batch / frames) * K * ncx * ncy <= 2^24. */
+enum { CRSDR_BEARING_CONVENTIONAL = 1, CRSDR_BEARING_ADAPTIVE = 2 };
+enum { CRSDR_BEARING_KEEP_SPECTRUM = 1u << 0 };
+
+typedef struct crsdr_caf_bearing_desc {
+    int32_t mx, my;           /* the array: mx my = nrows - 1 elements */
+    int32_t ncx, ncy;         /* the scan grid */
+    float d;                  /* element spacing in wavelengths */
+    int32_t mode;             /* CRSDR_BEARING_* */
+    float loading;            /* adaptive: diagonal loading, relative to trace(Q) / m */
+    int32_t levels;           /* zoom levels, 0 = the grid peak alone */
+    uint32_t flags;           /* CRSDR_BEARING_KEEP_SPECTRUM */
+} crsdr_caf_bearing_desc;
+
+/* Sets the bearings (NULL: off).  Between submits only: it waits for the last one and allocates here, never in a submit; what a
+ * fetch_bearing would have returned is gone.  CRSDR_ESTATE while the detector is off.  While bearings are on crsdr_caf_set_cfar returns
+ * CRSDR_ESTATE: the buffers are sized by its K and the training set is its own, so turn the bearings off first.  With bearings on a
+ * submit issues THREE launches more than without (eight, twelve with the canceller), whatever the number of blocks and whatever the
+ * counts, which the kernels read on the device (crsdr_caf_last_submit); empty slots write their zeros and leave. */
+int crsdr_caf_set_bearing(crsdr_caf *caf, const crsdr_caf_bearing_desc *desc);
+
+/* Waits for the last submit and copies out what is asked for (either pointer may be NULL), laid out as above.  CRSDR_ESTATE with the
+ * bearings off, before the first submit since they were set, or for spec without CRSDR_BEARING_KEEP_SPECTRUM. */
+int crsdr_caf_fetch_bearing(crsdr_caf *caf, float *dir, float *spec);
+
+/* Device addresses of dir and spec ([max_batch / frames] lines each; spec NULL unless kept).  They change with every
+ * crsdr_caf_set_bearing.  CRSDR_ESTATE with the bearings off. */
+int crsdr_caf_bearing_device_buffers(crsdr_caf *caf, void **dir, void **spec);
+
+/* The per-op form on ONE line: chi [nrows][nd][R][2], the array map's det [K][8] and count [1] as crsdr_cfar or the engine wrote them
+ * (or made by hand: only lag, Doppler and the position in the list are read), K = cfar->max_det; the detector's descriptor supplies
+ * the training set.  dir [K][8], spec [K][ncx][ncy] (asked for only with the keep flag); either may be NULL, not both.  nd, R, guard as
+ * crsdr_cfar has them, 0 <= ref_row < nrows, nrows nd R <= 2^24.  The same three kernels on the same arguments, bit for bit.
+ * mem_kind: CRSDR_MEM_HOST (copied) or CRSDR_MEM_DEVICE (every pointer on the device; det, count, dir and spec 4-byte, chi 8-byte
+ * aligned). */
+int crsdr_bearing(float *dir, float *spec, const float *chi, int nrows, int nd, int R, int ref_row, int guard, const float *det,
+                  const int32_t *count, const crsdr_cfar_desc *cfar, const crsdr_caf_bearing_desc *desc, int mem_kind);
 
 #ifdef __cplusplus
 }

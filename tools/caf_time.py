@@ -20,6 +20,13 @@ and the bytes of P the detector reads per submit (8 a cell of chi, 4 a cell of m
 with --cancel K[:P], on a further engine with the canceller set (crsdr_caf_set_cancel: K delays of the reference at -P .. P Doppler bins):
   caf+cancel as caf with the canceller's five launches in the place of the rows' one, + a fetch of coef and cinfo as well; beside it the
              fp64 multiply-adds of the subtraction (n complex ones a cell) per second
+with --bearing (implies --cfar; shapes whose signal rows are a 7 x 3 array, 22 rows), on three further engines whose detector has the
+threshold alpha = 3, so that noise fills every one of the 16 slots of every line, two of them with bearings set (crsdr_caf_set_bearing:
+spacing 0.506, a 100 x 100 grid, 5 zoom levels; conventional, and adaptive at loading 1e-2):
+  cfar low   as caf+cfar at that threshold: the same build's submit without bearings
+  +brg conv  as cfar low with the bearings' three launches behind the detector's, + a fetch of dir as well
+  +brg adpt  the same in the adaptive mode
+  get dir    the fetch of dir, against "get chi" + "get cfar" (snap among it) that a user's own bearing estimate would need
 
 Every figure is the mean of --reps back-to-back rounds closed by one wait; --runs rounds alternate all variants in one session, medians
 and ranges are reported.  --json FILE keeps the record."""
@@ -58,8 +65,10 @@ def main():
     ap.add_argument("--no-model", action="store_true", help="skip the numpy model on one line")
     ap.add_argument("--cfar", action="store_true", help="add the CFAR detector's variants")
     ap.add_argument("--cancel", metavar="K[:P]", help="add the canceller's variant")
+    ap.add_argument("--bearing", action="store_true", help="add the bearings' variants (with --cfar's)")
     ap.add_argument("--json")
     a = ap.parse_args()
+    a.cfar = a.cfar or a.bearing
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import torch
@@ -106,6 +115,24 @@ def main():
             cfd = b.Caf(nrows, B, SEG, lags, 0, b.WINDOW_HANN, GUARD, max_batch=T, frames=FRAMES)
             cfd.set_cfar(b.cfar_desc(alpha=b.cfar_alpha(1e-6, 90), gd=1, gr=1, td=3, tr=4, max_det=16))
 
+        brg = {}
+        if a.bearing and nrows == 22:
+            for name, mode in (("cfar low", None), ("+brg conv", b.BEARING_CONVENTIONAL), ("+brg adpt", b.BEARING_ADAPTIVE)):
+                e = b.Caf(nrows, B, SEG, lags, 0, b.WINDOW_HANN, GUARD, max_batch=T, frames=FRAMES)
+                e.set_cfar(b.cfar_desc(alpha=3.0, gd=1, gr=1, td=3, tr=4, max_det=16))
+                if mode is not None:
+                    e.set_bearing(b.bearing_desc(7, 3, (1.225 * 1.24) / 3.0, 100, 100, mode, 1e-2, 5))
+                brg[name] = e
+
+        def caf_bearing(e):
+            def run(i):
+                e.submit(pk, plan.packet_stride, plan.matrix_offset, T)
+                e.fetch(chi=False, map=False)
+                e.fetch_cfar()
+                if e is not brg["cfar low"]:
+                    e.fetch_bearing()
+            return run
+
         cfc, basis = None, 0
         if a.cancel:
             taps, dopp = (int(v) for v in (a.cancel + ":0").split(":")[:2])
@@ -135,6 +162,10 @@ def main():
             variants["caf+cfar"] = lambda: _mean(caf_cfar, lambda: None, a.reps)
             variants["get chi"] = lambda: _mean(lambda i: cf.fetch(map=False, peak=False), lambda: None, a.reps)
             variants["get cfar"] = lambda: _mean(lambda i: cfd.fetch_cfar(), lambda: None, a.reps)
+        for name, e in brg.items():
+            variants[name] = lambda e=e: _mean(caf_bearing(e), lambda: None, a.reps)
+        if brg:
+            variants["get dir"] = lambda: _mean(lambda i: brg["+brg adpt"].fetch_bearing(), lambda: None, a.reps)
         if a.cancel:
             variants["caf+cancel"] = lambda: _mean(caf_cancel, lambda: None, a.reps)
         plan.submit(d_in.data_ptr(), seq=0, flags=b.REFNOISE_ENABLED, nblocks=T, block_stride=nrows * B)      # lags and phasors for the locked submits
@@ -146,6 +177,10 @@ def main():
             for k, fn in variants.items():
                 rec[k].append(fn())
         shape = {"nrows": nrows, "batch": T, "lags": lags, "nd": nd, "ms": {}}
+        live = 0
+        if brg:                                  # the slots that hold a detection: the others write their zeros and leave
+            live = int(np.minimum(brg["+brg adpt"].fetch_cfar(det=False, snap=False)["count"][:, nrows], 16).sum())
+            shape["live_slots"] = live
         base = statistics.median(rec["plan"])
         cells = (T // FRAMES) * nrows * nd * lags
         macs = T * nrows * (B // 2) * lags
@@ -162,6 +197,10 @@ def main():
                 note = f"  (+{med - shape['ms']['caf']['median']:.3f} ms behind caf; the detector reads {(T // FRAMES) * nd * lags * (8 * nrows + 4) / 1e6:.1f} MB of P)"
             if k == "caf+cancel":
                 note = f"  (+{med - shape['ms']['caf']['median']:.3f} ms behind caf; {basis} complex fp64 multiply-adds a cell, {basis * cells / (med * 1e-3) / 1e9:.1f} G/s over the submit)"
+            if k in brg and k != "cfar low":
+                note = f"  (+{med - shape['ms']['cfar low']['median']:.3f} ms behind cfar low; {live} of {(T // FRAMES) * 16} slots hold a detection, 10^4 grid points each)"
+            if k == "get dir":
+                note = f"  ({(T // FRAMES) * 16 * 32 / 1e3:.1f} kB)"
             if k == "get chi":
                 note = f"  ({8 * cells / 1e6:.1f} MB)"
             if k == "get cfar":
@@ -186,6 +225,8 @@ def main():
             cfd.close()
         if cfc:
             cfc.close()
+        for e in brg.values():
+            e.close()
         sp.close()
         host.close()
         plan.close()
