@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "crsdr_caf_set_cfar", "crsdr_caf_fetch_cfar", "crsdr_caf_cfar_device_buffers", "crsdr_cfar", "crsdr_cfar_alpha",
     "crsdr_caf_set_cancel", "crsdr_caf_fetch_cancel", "crsdr_caf_cancel_device_buffers", "crsdr_ambiguity_cancel",
     "crsdr_caf_set_bearing", "crsdr_caf_fetch_bearing", "crsdr_caf_bearing_device_buffers", "crsdr_bearing",
+    "crsdr_caf_set_beams", "crsdr_caf_fetch_beams", "crsdr_caf_beams_device_buffers", "crsdr_beam_maps", "crsdr_beam_fuse", "crsdr_caf_beam_steer",
 ]
 BEARING_CONVENTIONAL, BEARING_ADAPTIVE = 1, 2
 BEARING_KEEP_SPECTRUM = 1
@@ -135,6 +136,11 @@ class BearingDesc(C.Structure):
     mode with its loading, the zoom levels and the flags."""
     _fields_ = [("mx", C.c_int32), ("my", C.c_int32), ("ncx", C.c_int32), ("ncy", C.c_int32), ("d", C.c_float), ("mode", C.c_int32),
                 ("loading", C.c_float), ("levels", C.c_int32), ("flags", C.c_uint32)]
+
+
+class BeamsDesc(C.Structure):
+    """crsdr_caf_beams_desc: nbeams weight rows [nbeams][m][2] float32 on the host (copied by the call), and the flags (none yet)."""
+    _fields_ = [("nbeams", C.c_int32), ("weights", C.POINTER(C.c_float)), ("flags", C.c_uint32)]
 
 
 _lib = None
@@ -309,6 +315,13 @@ def lib():
         L.crsdr_caf_fetch_bearing.argtypes = [vp, f32p, f32p]
         L.crsdr_caf_bearing_device_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         L.crsdr_bearing.argtypes = [f32p, f32p, f32p] + [C.c_int] * 5 + [f32p, i32p, C.POINTER(CfarDesc), C.POINTER(BearingDesc), C.c_int]
+    if hasattr(L, "crsdr_beam_maps"):                # (likewise: an older build has no beams)
+        L.crsdr_caf_set_beams.argtypes = [vp, C.POINTER(BeamsDesc)]
+        L.crsdr_caf_fetch_beams.argtypes = [vp, f32p, f32p, i32p, f32p, i32p]
+        L.crsdr_caf_beams_device_buffers.argtypes = [vp] + [C.POINTER(vp)] * 5
+        L.crsdr_beam_maps.argtypes = [f32p, f32p] + [C.c_int] * 4 + [f32p, C.c_int, C.c_int]
+        L.crsdr_beam_fuse.argtypes = [f32p, i32p, f32p, i32p] + [C.c_int] * 5
+        L.crsdr_caf_beam_steer.argtypes = [f32p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int]
     _lib = L
     return L
 
@@ -741,6 +754,61 @@ def bearing_device(dir_ptr: int, spec_ptr: int, chi_ptr: int, nrows, nd, R, ref_
     cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
     _check(lib().crsdr_bearing(cast(dir_ptr, C.c_float), cast(spec_ptr, C.c_float), cast(chi_ptr, C.c_float), int(nrows), int(nd), int(R), int(ref_row), int(guard),
                                cast(det_ptr, C.c_float), cast(count_ptr, C.c_int32), C.byref(cfar), C.byref(desc), MEM_DEVICE))
+
+
+def beams_desc(weights, flags=0):
+    """crsdr_caf_beams_desc of weights [nbeams][m] complex (or [nbeams][m][2] float).  The descriptor keeps the float32 array alive."""
+    w = np.asarray(weights)
+    w = np.ascontiguousarray(w, dtype=np.complex64).view(np.float32) if np.iscomplexobj(w) else np.ascontiguousarray(w, dtype=np.float32)
+    d = BeamsDesc(int(w.shape[0]), _p(w, C.c_float), int(flags))
+    d._keep = w
+    return d
+
+
+def beam_steer(mx, my, d, xy, ncx=100, ncy=100):
+    """crsdr_caf_beam_steer: weights [nbeams][mx my] complex64 = a(x, y) / sqrt(m) toward the cell coordinates xy [nbeams][2]."""
+    pts = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+    w = np.zeros((len(pts), max(int(mx) * int(my), 0)), dtype=np.complex64)
+    _check(lib().crsdr_caf_beam_steer(_p(w.view(np.float32), C.c_float), int(mx), int(my), float(d), int(ncx), int(ncy), pts.ctypes.data_as(C.POINTER(C.c_double)), len(pts)))
+    return w
+
+
+def beam_maps(chi, weights, ref_row=0):
+    """crsdr_beam_maps on ONE line: chi [nrows][nd][R] complex64, weights [nbeams][nrows - 1] complex64 -> bmap [nbeams][nd][R] float32.
+    The engine's beam maps (Caf.set_beams) on one line, bit for bit."""
+    a = np.ascontiguousarray(chi, dtype=np.complex64)
+    w = np.ascontiguousarray(weights, dtype=np.complex64)
+    nrows, nd, R = a.shape
+    out = np.zeros((w.shape[0], nd, R), dtype=np.float32)
+    _check(lib().crsdr_beam_maps(_p(out, C.c_float), _p(a.view(np.float32), C.c_float), nrows, nd, R, int(ref_row), _p(w.view(np.float32), C.c_float), int(w.shape[0]),
+                                 MEM_HOST))
+    return out
+
+
+def beam_maps_device(bmap_ptr: int, chi_ptr: int, nrows, nd, R, ref_row, weights):
+    """crsdr_beam_maps with CRSDR_MEM_DEVICE: bmap and chi on the device, the weights [nbeams][nrows - 1] complex64 on the host."""
+    cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
+    w = np.ascontiguousarray(weights, dtype=np.complex64)
+    _check(lib().crsdr_beam_maps(cast(bmap_ptr, C.c_float), cast(chi_ptr, C.c_float), int(nrows), int(nd), int(R), int(ref_row), _p(w.view(np.float32), C.c_float),
+                                 int(w.shape[0]), MEM_DEVICE))
+
+
+def beam_fuse(bdet, bcount, nd, R):
+    """crsdr_beam_fuse on ONE line: bdet [nbeams][K][8] float32, bcount [nbeams] int32 -> (fused [K][8] float32 = lag, doppler, power,
+    snr, noise, dlag, ddop, beam; nfused).  The engine's fusion on one line, bit for bit."""
+    t = np.ascontiguousarray(bdet, dtype=np.float32)
+    nb, K, _ = t.shape
+    n = np.ascontiguousarray(bcount, dtype=np.int32).reshape(nb)
+    out, nf = np.zeros((K, 8), dtype=np.float32), np.zeros(1, dtype=np.int32)
+    _check(lib().crsdr_beam_fuse(_p(out, C.c_float), _p(nf, C.c_int32), _p(t, C.c_float), _p(n, C.c_int32), nb, K, int(nd), int(R), MEM_HOST))
+    return out, int(nf[0])
+
+
+def beam_fuse_device(fused_ptr: int, nfused_ptr: int, bdet_ptr: int, bcount_ptr: int, nbeams, K, nd, R):
+    """crsdr_beam_fuse with CRSDR_MEM_DEVICE: every pointer on the device (fused or nfused, not both, may be 0)."""
+    cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
+    _check(lib().crsdr_beam_fuse(cast(fused_ptr, C.c_float), cast(nfused_ptr, C.c_int32), cast(bdet_ptr, C.c_float), cast(bcount_ptr, C.c_int32), int(nbeams), int(K),
+                                 int(nd), int(R), MEM_DEVICE))
 
 
 def ambiguity_device(chi_ptr: int, map_ptr: int, peak_ptr: int, matrix_ptr: int, nrows, B, seg, nlags, ref_row, window, guard):
@@ -1484,6 +1552,32 @@ class Caf:
         ptrs = [C.c_void_p() for _ in range(2)]
         _check(lib().crsdr_caf_bearing_device_buffers(self._h, *[C.byref(p) for p in ptrs]))
         return dict(zip(("dir", "spec"), [p.value for p in ptrs]))
+
+    def set_beams(self, weights, flags=0):
+        """crsdr_caf_set_beams: coherent beam maps across the rows behind every submit, weights [nbeams][nrows - 1] complex64 (None:
+        off).  Between submits.  With the detector on at this call every beam map is detected on and the lists are fused."""
+        desc = None if weights is None else (weights if isinstance(weights, BeamsDesc) else beams_desc(weights, flags))
+        _check(lib().crsdr_caf_set_beams(self._h, None if desc is None else C.byref(desc)))
+        self.nbeams, self.beams_detect = (0, False) if desc is None else (int(desc.nbeams), getattr(self, "max_det", 0) > 0)
+
+    def fetch_beams(self, bmap=True, lists=None, fused_only=False) -> dict:
+        """Waits for the last submit.  bmap [nest][nb][nd][nlags]; with the lists (by default where the detector was on at set_beams)
+        bdet [nest][nb][K][8], bcount [nest][nb] int32, fused [nest][K][8] = lag, doppler, power, snr, noise, dlag, ddop, beam, and
+        nfused [nest] int32; fused_only leaves bdet and bcount on the device."""
+        n, nb, K = self._last()[0], max(1, getattr(self, "nbeams", 0)), max(1, getattr(self, "max_det", 0))
+        lists = getattr(self, "beams_detect", False) if lists is None else lists
+        m = np.zeros((n, nb, self.nd, self.nlags), dtype=np.float32) if bmap else None
+        d = np.zeros((n, nb, K, 8), dtype=np.float32) if lists and not fused_only else None
+        c = np.zeros((n, nb), dtype=np.int32) if lists and not fused_only else None
+        f = np.zeros((n, K, 8), dtype=np.float32) if lists else None
+        nf = np.zeros(n, dtype=np.int32) if lists else None
+        _check(lib().crsdr_caf_fetch_beams(self._h, _p(m, C.c_float), _p(d, C.c_float), _p(c, C.c_int32), _p(f, C.c_float), _p(nf, C.c_int32)))
+        return {k: v for k, v in (("bmap", m), ("bdet", d), ("bcount", c), ("fused", f), ("nfused", nf)) if v is not None}
+
+    def beams_device_buffers(self) -> dict:
+        ptrs = [C.c_void_p() for _ in range(5)]
+        _check(lib().crsdr_caf_beams_device_buffers(self._h, *[C.byref(p) for p in ptrs]))
+        return dict(zip(("bmap", "bdet", "bcount", "fused", "nfused"), [p.value for p in ptrs]))
 
     def set_cancel(self, taps: "int | None", dopp: int = 0):
         """crsdr_caf_set_cancel: the canceller in front of every submit's Doppler stage (taps None: off).  Between submits."""

@@ -9,9 +9,13 @@
 //     the reference's sums, the rows' first lags, the normal equations' sums, factor and solves, and the rows with the subtraction.
 //     With bearings set (crsdr_caf_set_bearing; caf_bearing.hpp, caf_bearing_solve.hpp) three more behind the detector's: the slots'
 //     records, the scan's tiles, and the merge with the zoom search.  Its buffers are made by set_bearing, between submits.
+//     With beams set (crsdr_caf_set_beams; caf_beams.hpp, caf_beams_kernels.hpp) one more at the end: every beam's map across the rows on
+//     the fp32 matrix pipe; with the detector on three more behind it: the detector's two on the beam maps, (line, beam) taking the
+//     place of the line, and the fusion of the beams' lists into one per line.  Its buffers are made by set_beams, between submits.
 #pragma once
 
 #include "caf.hpp"
+#include "caf_beams_kernels.hpp"
 #include "caf_bearing.hpp"
 #include "caf_cancel.hpp"
 #include "caf_cfar_kernels.hpp"
@@ -32,6 +36,7 @@
     }
 
 constexpr int kCafLaunches = 3, kCafCfarLaunches = 2, kCafCancelLaunches = 4, kCafBearingLaunches = 3;      // (the canceller's five take the place of one)
+constexpr int kCafBeamLaunches = 1, kCafBeamDetLaunches = 3;                                                // (the maps; the detector's two on them and the fusion)
 constexpr long long kCafMaxCells = 1ll << 24;           // (max_batch / frames) * nrows * nd * nlags
 
 // the canceller's device memory for `lines` lines: the engine's own buffers, or parts of one per-op slot
@@ -77,6 +82,15 @@ struct crsdr_caf {
         DevBuf<bearing::Best> tbest;
         DevBuf<float> dir, spec;
     } bg;
+    // crsdr_caf_set_beams: on (false = off), det: the detector was on when they were set; the weights [nb][m][2], the maps and, with
+    // det, the detector's scratch for (line, beam) maps and the lists
+    struct Beams {
+        bool on = false, det = false, submitted = false;
+        int nb = 0;
+        DevBuf<float> w, bmap, bdet, fused;
+        DevBuf<int32_t> bcount, nfused, tcount;
+        DevBuf<cfar::Cand> slots;
+    } bb;
     hipStream_t last_stream = nullptr;
     int last_nest = 0, last_launches = 0;
     bool submitted = false;
@@ -251,6 +265,39 @@ static int bearing_enqueue(hipStream_t S, const float2 *chi, const float *det, s
     return CRSDR_OK;
 }
 
+// every limit of the beams of section (w), for crsdr_caf_set_beams and crsdr_beam_maps.  weights: on the host
+static int beams_args_ok(const char *who, int nrows, long long lines, int nd, int R, int nbeams, const float *weights, unsigned flags)
+{
+    switch (bm::bad_limit(nrows, lines, nd, R, nbeams, weights, flags)) {
+    case 0: return CRSDR_OK;
+    case 1: return fail(CRSDR_EINVAL, "%s: m = nrows - 1 = %d (1..%d)", who, nrows - 1, bm::MAX_M);
+    case 2: return fail(CRSDR_EINVAL, "%s: nbeams = %d (1..%d)", who, nbeams, bm::MAX_BEAMS);
+    case 3: return fail(CRSDR_EINVAL, "%s: NULL weights", who);
+    case 4: return fail(CRSDR_EINVAL, "%s: a weight is not finite", who);
+    case 5: return fail(CRSDR_EINVAL, "%s: flags = 0x%x (none yet)", who, flags);
+    default: return fail(CRSDR_EINVAL, "%s: (max_batch / frames) * nbeams * nd * R = %lld (at most 2^24)", who, lines * nbeams * nd * R);
+    }
+}
+
+// the beam maps' one launch, for the object and for crsdr_beam_maps: the same kernel on the same arguments, so the same bits
+static int beam_maps_enqueue(hipStream_t S, const float2 *chi, const float *w, int nest, int nrows, int cells, int ref_row, int nb, float *bmap)
+{
+    const dim3 grid((unsigned)((cells + caf_beams::WG_CELLS - 1) / caf_beams::WG_CELLS), (unsigned)nest);
+    const size_t lds = caf_beams::table_bytes(nrows - 1, nb);
+    if (caf_beams::groups_of(nb) == 1) hipLaunchKernelGGL((caf_beams::k_caf_beams<1>), grid, dim3(caf_beams::THREADS), lds, S, chi, w, nrows, cells, ref_row, nb, bmap);
+    else hipLaunchKernelGGL((caf_beams::k_caf_beams<2>), grid, dim3(caf_beams::THREADS), lds, S, chi, w, nrows, cells, ref_row, nb, bmap);
+    HIP_TRY(hipGetLastError());
+    return CRSDR_OK;
+}
+
+// the fusion's one launch, for the object and for crsdr_beam_fuse
+static int beam_fuse_enqueue(hipStream_t S, const float *bdet, const int32_t *bcount, int nest, int nb, int K, int nd, int R, float *fused, int32_t *nfused)
+{
+    hipLaunchKernelGGL(caf_beams::k_caf_beam_fuse, dim3((unsigned)nest), dim3(caf_beams::THREADS), 0, S, bdet, bcount, nb, K, nd, R, fused, nfused);
+    HIP_TRY(hipGetLastError());
+    return CRSDR_OK;
+}
+
 static void caf_free(crsdr_caf *q)
 {
     if (!q) return;
@@ -298,6 +345,23 @@ extern "C" int crsdr_caf_destroy(crsdr_caf *caf)
     return CRSDR_OK;
 }
 
+// the beams behind everything else of a submit (nothing with them off): the maps, and with the detector the lists and their fusion
+static int beams_launch(crsdr_caf *q, hipStream_t S)
+{
+    crsdr_caf::Beams &g = q->bb;
+    if (!g.on) return CRSDR_OK;
+    const int nest = q->last_nest, cells = q->nd * q->nlags;
+    { const int rc = beam_maps_enqueue(S, q->chi, g.w, nest, q->nrows, cells, q->ref_row, g.nb, g.bmap); if (rc) return rc; }
+    g.submitted = true; q->last_launches += kCafBeamLaunches;
+    if (!g.det) return CRSDR_OK;
+    // (line, beam) is the line of a one-map call, as crsdr_cfar has it with comps = 1
+    { const int rc = cfar_enqueue(S, nullptr, g.bmap, nest * g.nb, 0, 1, q->nd, q->nlags, q->guard, q->cf.prm, q->cf.keep, g.slots, g.tcount, g.bdet, g.bcount, nullptr);
+      if (rc) return rc; }
+    { const int rc = beam_fuse_enqueue(S, g.bdet, g.bcount, nest, g.nb, q->cf.prm.max_det, q->nd, q->nlags, g.fused, g.nfused); if (rc) return rc; }
+    q->last_launches += kCafBeamDetLaunches;
+    return CRSDR_OK;
+}
+
 static int caf_launch(crsdr_caf *q, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nblocks, hipStream_t S)
 {
     const CancelBufs cb = q->cn.bufs();
@@ -306,18 +370,18 @@ static int caf_launch(crsdr_caf *q, const int8_t *packets, size_t packet_stride,
     if (rc) return rc;
     q->last_stream = S; q->last_nest = nblocks / q->frames; q->submitted = true; q->last_launches = kCafLaunches;
     if (q->cn.on) { q->cn.submitted = true; q->last_launches += kCafCancelLaunches; }
-    if (!q->cf.on) return CRSDR_OK;
+    if (!q->cf.on) return beams_launch(q, S);
     const int rc2 = cfar_enqueue(S, q->chi, q->map, q->last_nest, q->nrows, q->nrows + 1, q->nd, q->nlags, q->guard, q->cf.prm, q->cf.keep, q->cf.slots, q->cf.tcount,
                                  q->cf.det, q->cf.count, q->cf.snap);
     if (rc2) return rc2;
     q->cf.submitted = true; q->last_launches += kCafCfarLaunches;
-    if (!q->bg.on) return CRSDR_OK;
+    if (!q->bg.on) return beams_launch(q, S);
     const size_t K = (size_t)q->cf.prm.max_det, entries = (size_t)(q->nrows + 1);
     const int rc3 = bearing_enqueue(S, q->chi, q->cf.det.p + (size_t)q->nrows * K * 8, entries * K * 8, q->cf.count.p + q->nrows, entries, q->last_nest, q->nrows, q->nd,
                                     q->nlags, q->ref_row, q->guard, q->cf.prm, q->bg.prm, q->bg.rec, q->bg.tbest, q->bg.dir, q->bg.spec);
     if (rc3) return rc3;
     q->bg.submitted = true; q->last_launches += kCafBearingLaunches;
-    return CRSDR_OK;
+    return beams_launch(q, S);
 }
 
 extern "C" int crsdr_caf_submit(crsdr_caf *q, const void *device_packets, size_t packet_stride, size_t matrix_offset, int nblocks, void *hip_stream)
@@ -381,6 +445,7 @@ extern "C" int crsdr_caf_device_buffers(crsdr_caf *q, void **chi, void **map, vo
 extern "C" int crsdr_caf_set_cfar(crsdr_caf *q, const crsdr_cfar_desc *desc)
 {
     if (!q) return fail(CRSDR_EINVAL, "caf_set_cfar: NULL caf");
+    if (q->bb.on) return fail(CRSDR_ESTATE, "caf_set_cfar: beams are on (crsdr_caf_set_beams): whether they are detected on, and the lists' sizes, are this detector's; turn them off first");
     if (q->bg.on) return fail(CRSDR_ESTATE, "caf_set_cfar: bearings are on (crsdr_caf_set_bearing): their buffers and training set are this detector's; turn them off first");
     cfar::Params prm{};
     if (desc) { const int rc_ = cfar_args_ok("caf_set_cfar", q->nd, desc, &prm); if (rc_) return rc_; }
@@ -512,6 +577,127 @@ extern "C" int crsdr_bearing(float *dir, float *spec, const float *chi, int nrow
     st.back(dir, d_d, db);
     if (keep) st.back(spec, d_s, sb);
     return st.finish();
+}
+
+extern "C" int crsdr_caf_set_beams(crsdr_caf *q, const crsdr_caf_beams_desc *desc)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_set_beams: NULL caf");
+    const size_t lines = (size_t)(q->max_batch / q->frames), cells = (size_t)q->nd * (size_t)q->nlags, m = (size_t)(q->nrows - 1);
+    if (desc) { const int rc_ = beams_args_ok("caf_set_beams", q->nrows, (long long)lines, q->nd, q->nlags, desc->nbeams, desc->weights, desc->flags); if (rc_) return rc_; }
+    HIP_TRY(hipSetDevice(q->device));
+    if (q->submitted) HIP_TRY(hipDeviceSynchronize());      // the last submit may still write the buffers let go here
+    q->bb = crsdr_caf::Beams();
+    if (!desc) return CRSDR_OK;
+    crsdr_caf::Beams &g = q->bb;
+    const size_t nb = (size_t)desc->nbeams, maps = lines * nb;
+    int r = CRSDR_OK;
+    if ((r = g.w.alloc(nb * m * 2)) || (r = g.bmap.alloc(maps * cells)) || (r = HIP_RC(hipMemcpy(g.w.p, desc->weights, sizeof(float) * nb * m * 2, hipMemcpyHostToDevice)))) {
+        q->bb = crsdr_caf::Beams();
+        return r;
+    }
+    if (q->cf.on) {
+        const size_t K = (size_t)q->cf.prm.max_det, tiles = (size_t)cfar::tiles_of(q->nd, q->nlags);
+        if ((r = g.slots.alloc(maps * tiles * (size_t)q->cf.keep)) || (r = g.tcount.alloc(maps * tiles)) || (r = g.bcount.alloc(maps)) || (r = g.bdet.alloc(maps * K * 8)) ||
+            (r = g.fused.alloc(lines * K * 8)) || (r = g.nfused.alloc(lines))) {
+            q->bb = crsdr_caf::Beams();
+            return r;
+        }
+    }
+    g.nb = desc->nbeams; g.det = q->cf.on; g.on = true;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_fetch_beams(crsdr_caf *q, float *bmap, float *bdet, int32_t *bcount, float *fused, int32_t *nfused)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_fetch_beams: NULL caf");
+    if (!q->bb.on) return fail(CRSDR_ESTATE, "caf_fetch_beams: no beams set (crsdr_caf_set_beams)");
+    if (!q->bb.submitted) return fail(CRSDR_ESTATE, "caf_fetch_beams: nothing submitted since the beams were set");
+    if ((bdet || bcount || fused || nfused) && !q->bb.det) return fail(CRSDR_ESTATE, "caf_fetch_beams: the detector was off when the beams were set: there are no lists");
+    HIP_TRY(hipSetDevice(q->device));
+    const size_t lines = (size_t)q->last_nest, maps = lines * (size_t)q->bb.nb, cells = (size_t)q->nd * (size_t)q->nlags, K = (size_t)q->cf.prm.max_det;
+    if (bmap) HIP_TRY(hipMemcpyAsync(bmap, q->bb.bmap.p, sizeof(float) * maps * cells, hipMemcpyDeviceToHost, q->last_stream));
+    if (bdet) HIP_TRY(hipMemcpyAsync(bdet, q->bb.bdet.p, sizeof(float) * maps * K * 8, hipMemcpyDeviceToHost, q->last_stream));
+    if (bcount) HIP_TRY(hipMemcpyAsync(bcount, q->bb.bcount.p, sizeof(int32_t) * maps, hipMemcpyDeviceToHost, q->last_stream));
+    if (fused) HIP_TRY(hipMemcpyAsync(fused, q->bb.fused.p, sizeof(float) * lines * K * 8, hipMemcpyDeviceToHost, q->last_stream));
+    if (nfused) HIP_TRY(hipMemcpyAsync(nfused, q->bb.nfused.p, sizeof(int32_t) * lines, hipMemcpyDeviceToHost, q->last_stream));
+    HIP_TRY(hipStreamSynchronize(q->last_stream));
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_beams_device_buffers(crsdr_caf *q, void **bmap, void **bdet, void **bcount, void **fused, void **nfused)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_beams_device_buffers: NULL caf");
+    if (!q->bb.on) return fail(CRSDR_ESTATE, "caf_beams_device_buffers: no beams set (crsdr_caf_set_beams)");
+    if (bmap) *bmap = q->bb.bmap;
+    if (bdet) *bdet = q->bb.bdet;
+    if (bcount) *bcount = q->bb.bcount;
+    if (fused) *fused = q->bb.fused;
+    if (nfused) *nfused = q->bb.nfused;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_beam_maps(float *bmap, const float *chi, int nrows, int nd, int R, int ref_row, const float *weights, int nbeams, int mem_kind)
+{
+    if (!bmap || !chi) return fail(CRSDR_EINVAL, "beam_maps: need bmap and chi");
+    // (the maps do not depend on the shape of a line, only on its nd R cells: nd need not be a power of two here)
+    if (nd < 1 || nd > (1 << caf::CAF_MAX_LOG2)) return fail(CRSDR_EINVAL, "beam_maps: nd = %d (1..4096)", nd);
+    if (R < 1 || R > caf::CAF_MAX_LAGS) return fail(CRSDR_EINVAL, "beam_maps: R = %d (1..%d)", R, caf::CAF_MAX_LAGS);
+    if (nrows < 2 || (long long)nrows * nd * R > kCafMaxCells) return fail(CRSDR_EINVAL, "beam_maps: nrows = %d (at least 2, nrows * nd * R at most 2^24)", nrows);
+    if (ref_row < 0 || ref_row >= nrows) return fail(CRSDR_EINVAL, "beam_maps: ref_row = %d (0..%d)", ref_row, nrows - 1);
+    { const int rc_ = beams_args_ok("beam_maps", nrows, 1, nd, R, nbeams, weights, 0u); if (rc_) return rc_; }
+    OP_PROLOGUE_MEM("beam_maps", mem_kind);
+    const size_t cells = (size_t)nd * (size_t)R, cb = sizeof(float2) * (size_t)nrows * cells, mb = sizeof(float) * (size_t)nbeams * cells;
+    const size_t wb = sizeof(float) * 2 * (size_t)nbeams * (size_t)(nrows - 1);
+    OpStage st(mem_kind);
+    const float2 *d_c = (const float2 *)st.in(0, chi, cb, 8);
+    float *d_m = (float *)st.out(1, bmap, mb, 4);
+    if (st.rc) return st.rc;
+    if (st.misaligned) return fail(CRSDR_EINVAL, "beam_maps: device bmap 4-byte, chi 8-byte aligned");
+    OP_RESERVE(2, wb);                                      // (the weights are the host's in either kind)
+    HIP_TRY(hipMemcpy(g_op.buf[2], weights, wb, hipMemcpyHostToDevice));
+    { const int rc_ = beam_maps_enqueue(0, d_c, (const float *)g_op.buf[2], 1, nrows, (int)cells, ref_row, nbeams, d_m); if (rc_) return rc_; }
+    st.back(bmap, d_m, mb);
+    return st.finish();
+}
+
+extern "C" int crsdr_beam_fuse(float *fused, int32_t *nfused, const float *bdet, const int32_t *bcount, int nbeams, int K, int nd, int R, int mem_kind)
+{
+    if (!bdet || !bcount || (!fused && !nfused)) return fail(CRSDR_EINVAL, "beam_fuse: need bdet, bcount and at least one of fused, nfused");
+    const int lgd = nd >= 1 && nd <= (1 << caf::CAF_MAX_LOG2) ? ilog2_exact(nd) : -1;
+    if (lgd < caf::CAF_MIN_LOG2) return fail(CRSDR_EINVAL, "beam_fuse: nd = %d (a power of two in [8, 4096])", nd);
+    if (R < 1 || R > caf::CAF_MAX_LAGS) return fail(CRSDR_EINVAL, "beam_fuse: R = %d (1..%d)", R, caf::CAF_MAX_LAGS);
+    if (nbeams < 1 || nbeams > bm::MAX_BEAMS) return fail(CRSDR_EINVAL, "beam_fuse: nbeams = %d (1..%d)", nbeams, bm::MAX_BEAMS);
+    if (K < 1 || K > cfar::MAX_DET) return fail(CRSDR_EINVAL, "beam_fuse: K = %d (1..%d)", K, cfar::MAX_DET);
+    OP_PROLOGUE_MEM("beam_fuse", mem_kind);
+    const size_t tb = sizeof(float) * (size_t)nbeams * (size_t)K * 8, nb = sizeof(int32_t) * (size_t)nbeams, fb = sizeof(float) * (size_t)K * 8;
+    OpStage st(mem_kind);
+    const float *d_t = (const float *)st.in(0, bdet, tb, 4);
+    const int32_t *d_n = (const int32_t *)st.in(1, bcount, nb, 4);
+    float *d_f = (float *)st.out(2, fused, fb, 4);
+    int32_t *d_k = (int32_t *)st.out(3, nfused, sizeof(int32_t), 4);
+    if (st.rc) return st.rc;
+    if (st.misaligned) return fail(CRSDR_EINVAL, "beam_fuse: device bdet, bcount, fused and nfused 4-byte aligned");
+    // (device memory and an output not asked for: the kernel writes it all the same)
+    if (!d_f) { OP_RESERVE(2, fb); d_f = (float *)g_op.buf[2]; }
+    if (!d_k) { OP_RESERVE(3, sizeof(int32_t)); d_k = (int32_t *)g_op.buf[3]; }
+    { const int rc_ = beam_fuse_enqueue(0, d_t, d_n, 1, nbeams, K, nd, R, d_f, d_k); if (rc_) return rc_; }
+    st.back(fused, d_f, fb);
+    st.back(nfused, d_k, sizeof(int32_t));
+    return st.finish();
+}
+
+extern "C" int crsdr_caf_beam_steer(float *weights, int mx, int my, float d, int ncx, int ncy, const double *xy, int nbeams)
+{
+    if (!weights || !xy) return fail(CRSDR_EINVAL, "caf_beam_steer: NULL argument");
+    if (mx < 1 || my < 1 || (long long)mx * my > bm::MAX_M) return fail(CRSDR_EINVAL, "caf_beam_steer: mx, my = %d, %d (at least 1, mx my at most %d)", mx, my, bm::MAX_M);
+    if (nbeams < 1 || nbeams > bm::MAX_BEAMS) return fail(CRSDR_EINVAL, "caf_beam_steer: nbeams = %d (1..%d)", nbeams, bm::MAX_BEAMS);
+    if (ncx < brg::MIN_NC || ncx > brg::MAX_NC || ncy < brg::MIN_NC || ncy > brg::MAX_NC)
+        return fail(CRSDR_EINVAL, "caf_beam_steer: ncx, ncy = %d, %d (%d..%d)", ncx, ncy, brg::MIN_NC, brg::MAX_NC);
+    if (!(d > 0.f) || !(d <= 3.402823466e+38f)) return fail(CRSDR_EINVAL, "caf_beam_steer: d = %g (finite and greater than 0)", (double)d);
+    for (int k = 0; k < 2 * nbeams; ++k)
+        if (!(xy[k] >= -1.7976931348623157e308 && xy[k] <= 1.7976931348623157e308)) return fail(CRSDR_EINVAL, "caf_beam_steer: a direction is not finite");
+    for (int b = 0; b < nbeams; ++b) bm::steer(weights + 2 * (size_t)b * mx * my, mx, my, d, ncx, ncy, xy[2 * b], xy[2 * b + 1]);
+    return CRSDR_OK;
 }
 
 extern "C" int crsdr_caf_set_cancel(crsdr_caf *q, const crsdr_caf_cancel_desc *desc)

@@ -11,6 +11,9 @@ static_assert(sizeof(det_t) == 8 * sizeof(float), "det_t is the detector's eight
 
 static_assert(sizeof(dir_t) == 8 * sizeof(float), "dir_t is the bearings' eight floats");
 
+static_assert(sizeof(fused_t) == 8 * sizeof(float), "fused_t is the fusion's eight floats");
+
+double fused_t::snr_db() const { return snr > 0.f ? 10.0 * std::log10((double)snr) : -INFINITY; }
 double det_t::snr_db() const { return snr > 0.f ? 10.0 * std::log10((double)snr) : -INFINITY; }
 double peak_t::power_db() const { return power > 0.f ? 10.0 * std::log10((double)power) : -INFINITY; }
 double peak_t::ratio_db() const { return ratio > 0.f ? 10.0 * std::log10((double)ratio) : -INFINITY; }
@@ -84,6 +87,32 @@ int batch::fetch_bearing(bool want_spec)
     }
     if (!rc) nlines = nest;
     if (rc && cf && bearings) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::set_beams(const crsdr_caf_beams_desc *desc)
+{
+    int rc = cf ? crsdr_caf_set_beams(cf, desc) : CRSDR_ESTATE;
+    if (!rc) { nb = desc ? desc->nbeams : 0; beam_lists = desc && kdet > 0; bmap.clear(); bdet.clear(); bcount.clear(); fused.clear(); nfused.clear(); }
+    if (rc && cf) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::fetch_beams(bool want_bmap, bool want_lists)
+{
+    int nest = 0;
+    int rc = !cf || !nb ? CRSDR_ESTATE : crsdr_caf_last_submit(cf, &nest, nullptr);
+    if (!rc) {
+        want_lists = want_lists && beam_lists;
+        const size_t maps = (size_t)nest * nb;
+        bmap.assign(want_bmap ? maps * bins * lags : 0, 0.f);
+        bdet.assign(want_lists ? maps * kdet : 0, det_t{}); bcount.assign(want_lists ? maps : 0, 0);
+        fused.assign(beam_lists ? (size_t)nest * kdet : 0, fused_t{}); nfused.assign(beam_lists ? (size_t)nest : 0, 0);
+        rc = crsdr_caf_fetch_beams(cf, want_bmap ? bmap.data() : nullptr, want_lists ? &bdet[0].lag : nullptr, want_lists ? bcount.data() : nullptr,
+                                   beam_lists ? &fused[0].lag : nullptr, beam_lists ? nfused.data() : nullptr);
+    }
+    if (!rc) nlines = nest;
+    if (rc && cf && nb) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
     return rc;
 }
 

@@ -31,12 +31,19 @@ struct dir_t {
     double beta_deg() const { return (double)beta * (180.0 / 3.14159265358979323846); }
 };
 
+// (lag, doppler, power, snr, noise, dlag, ddop, beam) of one fused detection of the beam maps, as crsdr_caf's beams lay them out
+struct fused_t {
+    float lag, doppler, power, snr, noise, dlag, ddop, beam;
+    double snr_db() const;                           // the cell above its training cells' mean in its beam's map; -inf for 0
+};
+
 // One line per `frames` consecutive packets of a submit: chi [nrows][nd][nlags] of every row against row ref_row over seg-sample
 // segments, the array map [nd][nlags], and nrows + 1 peaks (the rows', then the map's) searched outside |Doppler| < guard.
 class batch {
     crsdr_caf *cf = nullptr;
     int rows, bins, lags, kdet = 0, nbasis = 0, npts = 0;
-    bool bearings = false;
+    bool bearings = false, beam_lists = false;
+    int nb = 0;
 
 public:
     batch(int nrows, int blocksize, int max_batch, int seg, int nlags, int ref_row = 0, int window = CRSDR_WINDOW_RECT, int guard = 0, int frames = 1, int device = 0);
@@ -63,6 +70,13 @@ public:
     int set_bearing(const crsdr_caf_bearing_desc *desc);
     // waits, and fills dir beside det, and spec if asked for and kept; CRSDR_ESTATE with the bearings off
     int fetch_bearing(bool want_spec = false);
+    // coherent beam maps across the rows behind every later submit (crsdr_caf_set_beams; NULL: off), weights [nbeams][nrows - 1][2].
+    // Between submits; with the detector on at this call every beam map is detected on and the lists are fused into one per line;
+    // while beams are on set_cfar is refused.
+    int set_beams(const crsdr_caf_beams_desc *desc);
+    // waits, and fills fused and nfused (with the detector), and bmap, bdet and bcount if asked for; CRSDR_ESTATE with the beams off
+    int fetch_beams(bool want_bmap = false, bool want_lists = false);
+    int nbeams() const { return nb; }
     int basis() const { return nbasis; }             // taps (2 dopp + 1), 0 with the canceller off
     int lines() const { return nlines; }
     int nrows() const { return rows; }
@@ -79,6 +93,13 @@ public:
     std::vector<dir_t> dir;                          // [lines][max_det]: the bearing of the array map's detection k, zeros behind the last
     std::vector<float> spec;                         // [lines][max_det][ncx][ncy]: T on the grid, where kept and asked for
     const dir_t &bearing(int e, int k) const { return dir[(size_t)e * kdet + k]; }
+    std::vector<float> bmap;                         // [lines][nbeams][nd][nlags]: every beam's map
+    std::vector<det_t> bdet;                         // [lines][nbeams][max_det]: every beam map's detections
+    std::vector<int32_t> bcount;                     // [lines][nbeams]
+    std::vector<fused_t> fused;                      // [lines][max_det]: the beams' detections fused, the strongest first, zeros behind the last
+    std::vector<int32_t> nfused;                     // [lines]: the survivors of the fusion, which may be more than max_det
+    int fused_held(int e) const { return beam_lists ? (nfused[(size_t)e] < kdet ? nfused[(size_t)e] : kdet) : 0; }
+    const fused_t &fused_at(int e, int k) const { return fused[(size_t)e * kdet + k]; }
     std::vector<float> coef;                         // [lines][nrows][basis][2]: the canceller's filter of every row
     std::vector<float> cinfo;                        // [lines][nrows][2]: the share of the row's power that stays, and the status
     float residual(int e, int c) const { return cinfo[2 * ((size_t)e * rows + c)]; }

@@ -70,7 +70,8 @@ int main(int argc, char **argv)
     bool cfar_on = false;
     double cfar_db = 0.0;
     crsdr_cfar_desc cfar = {1, 1, 3, 4, 0.f, 1, 16};
-    bool cancel_on = false, bearing_on = false;
+    bool cancel_on = false, bearing_on = false, beams_on = false;
+    int beams_mx = 0, beams_my = 0, beams_nx = 0, beams_ny = 0;
     crsdr_caf_bearing_desc bearing = {0, 0, 100, 100, 0.5f, CRSDR_BEARING_CONVENTIONAL, 1e-2f, 0, 0u};
     crsdr_caf_cancel_desc cancel = {0, 0};
     bool engine_batches = false;
@@ -173,6 +174,14 @@ int main(int argc, char **argv)
             bearing_on = true;
             bearing.ncx = bearing.ncy = nc;
             if (n < 2) bearing.mx = -1;                                                      // (refused below with the rest)
+        }
+        // with --caf: a lattice of NX x NY conventional beams across the signal rows as an MX x MY array, on a 100 x 100 grid
+        // (crsdr_caf_set_beams): direction ((100 i + 48) / NX, (100 j + 96) / NY) is beam NY i + j (8 x 8: 6 + 12.5 i, 12 + 12.5 j).  With --cfar every beam map is detected on
+        // and the fused detections are printed with their beam's angles.
+        else if (a == "--caf-beams" && i + 1 < argc) {
+            const int n = std::sscanf(argv[++i], "%dx%d:%dx%d", &beams_mx, &beams_my, &beams_nx, &beams_ny);
+            beams_on = true;
+            if (n != 4) beams_mx = -1;                                                       // (refused below with the rest)
         }
         else if (a == "--adaptive" && i + 1 < argc) { bearing.mode = CRSDR_BEARING_ADAPTIVE; bearing.loading = (float)std::atof(argv[++i]); }
         else if (a == "--bearing-levels") val(bearing.levels);
@@ -552,6 +561,7 @@ int main(int argc, char **argv)
         // --bench --caf: ccaf::batch over crsdr_caf, behind every batch on the plan's stream like the spectra.  The synthetic channels are
         // copies of the reference noise with the integer lag taken out: with --guard 0 every row peaks at lag 0, Doppler 0.
         std::unique_ptr<ccaf::batch> caf;
+        std::vector<double> beam_xy;                                                         // [nbeams][2]: the lattice's cell coordinates
         if (caf_seg && !coherent.sharded()) {
             if (caf_seg > 0) caf.reset(new ccaf::batch(1 + nsig, B, batch, caf_seg, caf_lags, caf_ref, sb_window, caf_guard, caf_frames));
             if (!caf || !caf->ok()) { std::printf("caf: --caf SEG:LAGS[:REF] [--caf-frames F] [--guard G] [--window rect|hann] refused\nDEMO FAILED\n"); return 1; }
@@ -562,11 +572,28 @@ int main(int argc, char **argv)
                 std::printf("bearing: --bearing MXxMY[:NC] [--adaptive LOADING] [--bearing-levels L] refused (MX MY must be --nsig = %d)\nDEMO FAILED\n", nsig);
                 return 1;
             }
+            if (beams_on) {
+                const long long nbm = (long long)beams_nx * beams_ny;
+                bool good = beams_mx >= 1 && beams_my >= 1 && (long long)beams_mx * beams_my == nsig && beams_nx >= 1 && beams_ny >= 1 && nbm <= 64;
+                if (good) {
+                    beam_xy.resize(2 * (size_t)nbm);
+                    for (int i = 0; i < beams_nx; ++i)
+                        for (int j = 0; j < beams_ny; ++j) {
+                            beam_xy[2 * ((size_t)i * beams_ny + j)] = (100.0 * i + 48.0) / beams_nx;      // (inside the grid for any NX, NY)
+                            beam_xy[2 * ((size_t)i * beams_ny + j) + 1] = (100.0 * j + 96.0) / beams_ny;
+                        }
+                    std::vector<float> w(2 * (size_t)nbm * nsig);
+                    const crsdr_caf_beams_desc bd = {(int32_t)nbm, w.data(), 0u};
+                    good = crsdr_caf_beam_steer(w.data(), beams_mx, beams_my, bearing.d, 100, 100, beam_xy.data(), (int)nbm) == CRSDR_OK && caf->set_beams(&bd) == CRSDR_OK;
+                }
+                if (!good) { std::printf("beams: --caf-beams MXxMY:NXxNY refused (MX MY must be --nsig = %d, NX NY at most 64)\nDEMO FAILED\n", nsig); return 1; }
+            }
         }
         auto ambiguity = [&](int b) {
             if (!caf || !ok) return;
             ok = caf->submit(coherent.engine_plan()) == CRSDR_OK && caf->fetch() == CRSDR_OK && (!cfar_on || caf->fetch_cfar() == CRSDR_OK) &&
-                 (!cancel_on || caf->fetch_cancel(false) == CRSDR_OK) && (!bearing_on || caf->fetch_bearing() == CRSDR_OK);
+                 (!cancel_on || caf->fetch_cancel(false) == CRSDR_OK) && (!bearing_on || caf->fetch_bearing() == CRSDR_OK) &&
+                 (!beams_on || caf->fetch_beams() == CRSDR_OK);
             if (!ok || !report) return;
             for (int e = 0; cancel_on && e < caf->lines(); ++e) {
                 double sum = 0.0;
@@ -587,6 +614,15 @@ int main(int argc, char **argv)
                     const ccaf::dir_t &d = caf->bearing(e, k);
                     std::printf("bearing: batch %d line %d det %d: cell (%d, %d) alpha %.3f deg beta %.3f deg fit %.4f\n", b, e, k, (int)d.cx, (int)d.cy, d.alpha_deg(),
                                 d.beta_deg(), (double)d.fit);
+                }
+            if (beams_on && !cfar_on) std::printf("beams: %d maps per line (no detector: --cfar fuses their detections)\n", caf->nbeams());
+            for (int e = 0; beams_on && cfar_on && e < caf->lines(); ++e)
+                for (int k = 0; k < caf->fused_held(e); ++k) {
+                    const ccaf::fused_t &d = caf->fused_at(e, k);
+                    const int bm = (int)d.beam;
+                    std::printf("beams: batch %d line %d fused %d of %d: lag %d%+.3f doppler %d%+.3f power %.6g snr %.2f dB beam %d alpha %.3f deg beta %.3f deg\n", b, e, k,
+                                (int)caf->nfused[(size_t)e], (int)d.lag, (double)d.dlag, (int)d.doppler, (double)d.ddop, (double)d.power, d.snr_db(), bm,
+                                beam_xy[2 * (size_t)bm] * 1.8, beam_xy[2 * (size_t)bm + 1] * 1.8);
                 }
             for (int e = 0; e < caf->lines(); ++e)
                 for (int c = 0; c <= caf->nrows(); ++c) {

@@ -1310,6 +1310,75 @@ int crsdr_caf_bearing_device_buffers(crsdr_caf *caf, void **dir, void **spec);
 int crsdr_bearing(float *dir, float *spec, const float *chi, int nrows, int nd, int R, int ref_row, int guard, const float *det,
                   const int32_t *count, const crsdr_cfar_desc *cfar, const crsdr_caf_bearing_desc *desc, int mem_kind);
 
+/* Beams.  The array map sums the rows' powers: it gives away the array's coherent gain (a factor of m in power) and has no spatial
+ * selectivity, so the direct path's ambiguity floor, which carries the illuminator's spatial signature in every cell, enters it at full
+ * strength -- and a target it cannot detect never gets a bearing.  This stage forms a bank of coherent beams across the rows, on chi,
+ * which is linear in the rows: beams formed behind the Doppler stage equal beamforming the rows first, at a fraction of the cost.  The
+ * detector then runs on every beam's map and the beams' lists are fused into one per line.  It is off until crsdr_caf_set_beams; off,
+ * a submit is the same launches and the same bits, in every combination of canceller, detector and bearings.
+ *
+ * Elements.  The rows c != ref_row in ascending order are the elements e = 0 .. m - 1, m = nrows - 1, 1 <= m <= 64: the bearings'
+ * rule.  No geometry is implied: the weights w [nbeams][m][2] (re, im) are the caller's, 1 <= nbeams <= 64, every one finite.
+ * Beam sums, in fp32 from the published fp32 chi:
+ *     z_b[d][tau] = sum_e w_b,e chi_c(e)[d][tau]        re z = sum_e (wr cr - wi ci),   im z = sum_e (wr ci + wi cr)
+ *     bmap [nest][nbeams][nd][R] float = (float)((double)re z re z + (double)im z im z)
+ * The order of the sum and its fused multiply-adds are the kernel's (e ascending, per element re = fma(-wi, ci, fma(wr, cr, re)) and
+ * im = fma(wr, ci, fma(wi, cr, im)): what the fp32 matrix instruction leaves) and are not pinned against the model, whose bars hold for
+ * any order.  In the bearings' convention u = conj(chi) and |w^H u|^2 = |sum_e w_e chi_e|^2: with w = a(x, y) / sqrt(m)
+ * (crsdr_caf_beam_steer) the bmap value is the conventional T(x, y) of crsdr_caf_set_bearing times the array map's value at that cell.
+ * Non-finite inputs are the caller's; finite inputs never give a NaN.
+ * Beam detections (only with the detector on).  The detector of crsdr_caf_set_cfar runs unchanged on every beam map, with the same
+ * descriptor and guard: its two kernels take (line, beam) for the line of a one-map call, as crsdr_cfar has it with comps = 1.
+ *     bcount [nest][nbeams] int32,   bdet [nest][nbeams][K][8]        laid out and rounded exactly as count and det; no snapshots
+ * Fusion into one list per line.  The candidates are the slots q < min(bcount[b], K) of every beam, at most 64 x 64 of them (a
+ * hand-made slot whose lag or Doppler lies outside the map is none).  Candidate A comes before A' iff P > P', or P == P' and b < b', or
+ * both equal and i < i' with i = d R + tau (a hand-made list that names one cell twice in one beam: the earlier slot first, so that the
+ * order is total on any list).  A candidate is suppressed iff some other candidate of the line comes before it and lies
+ * within one cell of it -- lag difference at most 1, no wrap, and Doppler difference at most 1 modulo nd -- whether or not that other
+ * candidate is itself suppressed.
+ *     nfused [nest] int32         the number of survivors; may exceed K
+ *     fused  [nest][K][8]         the first K survivors in that order: the bdet record bit for bit, the eighth figure (ntrain)
+ *                                 replaced by the beam index as a float; unused slots zero
+ * Bits.  Nothing depends on the order in which workgroups or atomics arrive: a line has the same bits wherever it sits in a batch, and
+ * crsdr_beam_maps, crsdr_cfar and crsdr_beam_fuse launch the same kernels on the same arguments.
+ * Limits, all CRSDR_EINVAL and all checked before a device is touched, by one function for the engine and the per-op call:
+ * 1 <= m <= 64; 1 <= nbeams <= 64; weights not NULL and every one finite; no flag; (max_batch / frames) * nbeams * nd * R <= 2^24. */
+typedef struct crsdr_caf_beams_desc {
+    int32_t nbeams;
+    const float *weights;     /* host, [nbeams][m][2]; copied by the call */
+    uint32_t flags;           /* none yet: must be 0 */
+} crsdr_caf_beams_desc;
+
+/* Sets the beams (NULL: off).  Between submits only: it waits for the last one and allocates here, never in a submit; what a
+ * fetch_beams would have returned is gone.  Whether the beams are detected on is the detector's state at this call, and while beams
+ * are on crsdr_caf_set_cfar returns CRSDR_ESTATE: turn the beams off first.  With beams on a submit issues ONE launch more than without
+ * when the detector was off, FOUR when it was on (the maps, the detector's two, the fusion), whatever the number of blocks and
+ * whatever the counts (crsdr_caf_last_submit). */
+int crsdr_caf_set_beams(crsdr_caf *caf, const crsdr_caf_beams_desc *desc);
+
+/* Waits for the last submit and copies out what is asked for (any pointer may be NULL), laid out as above.  CRSDR_ESTATE with the beams
+ * off, before the first submit since they were set, or for bdet, bcount, fused or nfused when the detector was off at set_beams. */
+int crsdr_caf_fetch_beams(crsdr_caf *caf, float *bmap, float *bdet, int32_t *bcount, float *fused, int32_t *nfused);
+
+/* Device addresses ([max_batch / frames] lines each; the lists NULL when the detector was off).  They change with every
+ * crsdr_caf_set_beams.  CRSDR_ESTATE with the beams off. */
+int crsdr_caf_beams_device_buffers(crsdr_caf *caf, void **bmap, void **bdet, void **bcount, void **fused, void **nfused);
+
+/* The beam maps of ONE line: chi [nrows][nd][R][2] -> bmap [nbeams][nd][R].  1 <= nd <= 4096 (the maps do not depend on the shape of a
+ * line, only on its nd R cells: nd need not be a power of two here), 1 <= R <= 1024, 0 <= ref_row < nrows, nrows nd R <= 2^24.  The engine's kernel on the same arguments, bit for bit.  mem_kind: CRSDR_MEM_HOST (copied) or CRSDR_MEM_DEVICE
+ * (bmap 4-byte and chi 8-byte aligned, on the device); weights is host memory in either kind, as in the descriptor. */
+int crsdr_beam_maps(float *bmap, const float *chi, int nrows, int nd, int R, int ref_row, const float *weights, int nbeams, int mem_kind);
+
+/* The fusion of ONE line: bdet [nbeams][K][8] and bcount [nbeams] as crsdr_cfar or the engine wrote them (or made by hand: lag, Doppler,
+ * power and the position are read) -> fused [K][8], nfused [1]; either may be NULL, not both.  1 <= K <= 64.  The engine's kernel on
+ * the same arguments, bit for bit.  mem_kind as above, every pointer 4-byte aligned. */
+int crsdr_beam_fuse(float *fused, int32_t *nfused, const float *bdet, const int32_t *bcount, int nbeams, int K, int nd, int R, int mem_kind);
+
+/* Host only: weights [nbeams][mx my][2] = a(x, y) / sqrt(m) toward the nbeams cell coordinates xy [nbeams][2] of an ncx x ncy grid, with
+ * the bearings' fp64 steering expression and element order (e = iy mx + ix), each part rounded once to fp32.  mx, my >= 1,
+ * mx my <= 64, 2 <= ncx, ncy <= 512, d finite and > 0, every coordinate finite: else CRSDR_EINVAL. */
+int crsdr_caf_beam_steer(float *weights, int mx, int my, float d, int ncx, int ncy, const double *xy, int nbeams);
+
 #ifdef __cplusplus
 }
 #endif

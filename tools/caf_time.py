@@ -27,6 +27,14 @@ spacing 0.506, a 100 x 100 grid, 5 zoom levels; conventional, and adaptive at lo
   +brg conv  as cfar low with the bearings' three launches behind the detector's, + a fetch of dir as well
   +brg adpt  the same in the adaptive mode
   get dir    the fetch of dir, against "get chi" + "get cfar" (snap among it) that a user's own bearing estimate would need
+with --beams NB (shapes of 22 rows; NB a square number up to 64), on four further engines, two of them with a lattice of NB conventional
+beams of the 7 x 3 array set (crsdr_caf_set_beams), without the detector and with it (alpha for 1e-6 at 90 cells, 16 detections a map):
+  caf b      as caf: the same build's submit without beams
+  +beams     as caf b with the beam maps' one launch behind the three; bmap stays on the device
+  cfar b     as caf+cfar: the same build's submit with the detector and without beams
+  +beams det as cfar b with the beams' four launches behind the detector's, + a fetch of fused and nfused as well
+  get fused  the fetch of fused + nfused, against "get chi" that a user's own beamformer would need
+and the beam kernel's two bounds for the shape: the bytes it must move, and its MFMAs' cycles.
 
 Every figure is the mean of --reps back-to-back rounds closed by one wait; --runs rounds alternate all variants in one session, medians
 and ranges are reported.  --json FILE keeps the record."""
@@ -66,6 +74,7 @@ def main():
     ap.add_argument("--cfar", action="store_true", help="add the CFAR detector's variants")
     ap.add_argument("--cancel", metavar="K[:P]", help="add the canceller's variant")
     ap.add_argument("--bearing", action="store_true", help="add the bearings' variants (with --cfar's)")
+    ap.add_argument("--beams", type=int, default=0, metavar="NB", help="add the beam maps' variants: a lattice of NB beams (22 rows)")
     ap.add_argument("--json")
     a = ap.parse_args()
     a.cfar = a.cfar or a.bearing
@@ -133,6 +142,31 @@ def main():
                     e.fetch_bearing()
             return run
 
+        bms = {}
+        if a.beams and nrows == 22:
+            side = int(round(a.beams ** 0.5))
+            xy = np.array([((100.0 * i + 48.0) / side, (100.0 * j + 96.0) / side) for i in range(side) for j in range(side)])
+            wts = b.beam_steer(7, 3, (1.225 * 1.24) / 3.0, xy, 100, 100)
+            for name, det, on in (("caf b", False, False), ("+beams", False, True), ("cfar b", True, False), ("+beams det", True, True)):
+                e = b.Caf(nrows, B, SEG, lags, 0, b.WINDOW_HANN, GUARD, max_batch=T, frames=FRAMES)
+                if det:
+                    e.set_cfar(b.cfar_desc(alpha=b.cfar_alpha(1e-6, 90), gd=1, gr=1, td=3, tr=4, max_det=16))
+                if on:
+                    e.set_beams(wts)
+                bms[name] = (e, det, on)
+
+        def caf_beams(name):
+            e, det, on = bms[name]
+
+            def run(i):
+                e.submit(pk, plan.packet_stride, plan.matrix_offset, T)
+                e.fetch(chi=False, map=False)
+                if det:
+                    e.fetch_cfar()
+                if det and on:
+                    e.fetch_beams(bmap=False, fused_only=True)
+            return run
+
         cfc, basis = None, 0
         if a.cancel:
             taps, dopp = (int(v) for v in (a.cancel + ":0").split(":")[:2])
@@ -166,6 +200,12 @@ def main():
             variants[name] = lambda e=e: _mean(caf_bearing(e), lambda: None, a.reps)
         if brg:
             variants["get dir"] = lambda: _mean(lambda i: brg["+brg adpt"].fetch_bearing(), lambda: None, a.reps)
+        for name in bms:
+            variants[name] = lambda name=name: _mean(caf_beams(name), lambda: None, a.reps)
+        if bms:
+            variants["get fused"] = lambda: _mean(lambda i: bms["+beams det"][0].fetch_beams(bmap=False, fused_only=True), lambda: None, a.reps)
+            if "get chi" not in variants:
+                variants["get chi"] = lambda: _mean(lambda i: cf.fetch(map=False, peak=False), lambda: None, a.reps)
         if a.cancel:
             variants["caf+cancel"] = lambda: _mean(caf_cancel, lambda: None, a.reps)
         plan.submit(d_in.data_ptr(), seq=0, flags=b.REFNOISE_ENABLED, nblocks=T, block_stride=nrows * B)      # lags and phasors for the locked submits
@@ -201,6 +241,12 @@ def main():
                 note = f"  (+{med - shape['ms']['cfar low']['median']:.3f} ms behind cfar low; {live} of {(T // FRAMES) * 16} slots hold a detection, 10^4 grid points each)"
             if k == "get dir":
                 note = f"  ({(T // FRAMES) * 16 * 32 / 1e3:.1f} kB)"
+            if k == "+beams":
+                note = f"  (+{med - shape['ms']['caf b']['median']:.3f} ms behind caf b)"
+            if k == "+beams det":
+                note = f"  (+{med - shape['ms']['cfar b']['median']:.3f} ms behind cfar b)"
+            if k == "get fused":
+                note = f"  ({(T // FRAMES) * (16 * 32 + 4) / 1e3:.1f} kB)"
             if k == "get chi":
                 note = f"  ({8 * cells / 1e6:.1f} MB)"
             if k == "get cfar":
@@ -208,6 +254,12 @@ def main():
             if k == "host":
                 note = f"  ({T * plan.packet_stride / (med * 1e-3) / 1e9:.1f} GB/s)"
             print(f"rows {nrows:5d} batch {T:2d} {k:>10}: {med:9.3f} ms ({min(ms):.3f} .. {max(ms):.3f}){note}")
+        if bms:
+            nb, m, lcells = len(wts), nrows - 1, (T // FRAMES) * nd * lags
+            mfma = (lcells // 32) * 2 * m * ((nb + 31) // 32)
+            shape["beams"] = {"nbeams": nb, "bytes": lcells * (8 * m + 4 * nb), "mfma": mfma}
+            print(f"rows {nrows:5d} batch {T:2d} beam maps: {nb} beams, {lcells} cells: {lcells * (8 * m + 4 * nb) / 1e6:.1f} MB to move; {mfma} MFMAs of 64 cycles, "
+                  f"{mfma * 64 / 1024 / 2.4e9 * 1e3:.4f} ms over 1024 SIMDs at 2.4 GHz")
         if not a.no_model:
             import caf_model as M
             t0 = time.perf_counter()
@@ -226,6 +278,8 @@ def main():
         if cfc:
             cfc.close()
         for e in brg.values():
+            e.close()
+        for e, _, _ in bms.values():
             e.close()
         sp.close()
         host.close()
