@@ -98,7 +98,8 @@ def _input(kind, nrows, B, N, seed):
     return M.tone_matrix(nrows, B, N, 3 if kind == "tone" else N - 2)
 
 
-# (nrows, nfft, B, overlap, window, input).  Every transform size with B = 2N (J = 1 in both overlaps), 4N (J = 2 / 3) and 6N; exactly
+# (nrows, nfft, B, overlap, window, input).  Every second transform size (N = 16, 64, 256, 1024, 4096: a last pass of radix 16 or 4;
+# N = 32, 128, 512, 2048 are tests/test_gpu_spectra_sizes.py's) with B = 2N (J = 1 in both overlaps), 4N (J = 2 / 3) and 6N; exactly
 # one full fp32 chain per lane and one segment more (N = 16: 16 lanes of 32 segments, N = 64: 4 lanes, N = 256: one); nrows 2, 3 (the
 # matrix only 4-byte aligned), 22, 66 and 5 (a workgroup takes one row, so every count is a multiple: 5 stands for "odd and small");
 # both windows, both overlaps; Gaussian, full-scale, all-zero and on-bin tone inputs.
