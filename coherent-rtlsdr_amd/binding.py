@@ -55,7 +55,10 @@ ABI_SYMBOLS = [
     "crsdr_caf_set_cancel", "crsdr_caf_fetch_cancel", "crsdr_caf_cancel_device_buffers", "crsdr_ambiguity_cancel",
     "crsdr_caf_set_bearing", "crsdr_caf_fetch_bearing", "crsdr_caf_bearing_device_buffers", "crsdr_bearing",
     "crsdr_caf_set_beams", "crsdr_caf_fetch_beams", "crsdr_caf_beams_device_buffers", "crsdr_beam_maps", "crsdr_beam_fuse", "crsdr_caf_beam_steer",
+    "crsdr_caf_set_track", "crsdr_caf_track_reset", "crsdr_caf_fetch_track", "crsdr_caf_track_device_buffers", "crsdr_track_state_bytes", "crsdr_track",
 ]
+TRACK_SRC_ARRAY, TRACK_SRC_FUSED = 0, 1
+TRACK_FREE, TRACK_TENTATIVE, TRACK_CONFIRMED, TRACK_ENDED = 0, 1, 2, 3      # trk[..., 1]
 BEARING_CONVENTIONAL, BEARING_ADAPTIVE = 1, 2
 BEARING_KEEP_SPECTRUM = 1
 BEARING_ZERO, BEARING_IDENTITY, BEARING_CELL = 1, 2, 4        # status bits 0, 1, 2: all-zero snapshot; W = I; a cell outside the map
@@ -141,6 +144,14 @@ class BearingDesc(C.Structure):
 class BeamsDesc(C.Structure):
     """crsdr_caf_beams_desc: nbeams weight rows [nbeams][m][2] float32 on the host (copied by the call), and the flags (none yet)."""
     _fields_ = [("nbeams", C.c_int32), ("weights", C.POINTER(C.c_float)), ("flags", C.c_uint32)]
+
+
+class TrackDesc(C.Structure):
+    """crsdr_caf_track_desc: the slots, the source list, the measurement deviations, the gate on d2, the new track's rate variance, the
+    process noise per line, the lag-Doppler coupling, m-of-n confirmation and the misses that end a tentative and a confirmed track."""
+    _fields_ = [("max_tracks", C.c_int32), ("source", C.c_int32), ("sigma_r", C.c_double), ("sigma_f", C.c_double), ("gate", C.c_double),
+                ("p0_g", C.c_double), ("q_r", C.c_double), ("q_f", C.c_double), ("q_g", C.c_double), ("coupling", C.c_double),
+                ("m", C.c_int32), ("n", C.c_int32), ("tent_miss", C.c_int32), ("conf_miss", C.c_int32)]
 
 
 _lib = None
@@ -322,6 +333,13 @@ def lib():
         L.crsdr_beam_maps.argtypes = [f32p, f32p] + [C.c_int] * 4 + [f32p, C.c_int, C.c_int]
         L.crsdr_beam_fuse.argtypes = [f32p, i32p, f32p, i32p] + [C.c_int] * 5
         L.crsdr_caf_beam_steer.argtypes = [f32p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int]
+    if hasattr(L, "crsdr_track"):                    # (likewise: an older build has no tracker)
+        L.crsdr_caf_set_track.argtypes = [vp, C.POINTER(TrackDesc)]
+        L.crsdr_caf_track_reset.argtypes = [vp]
+        L.crsdr_caf_fetch_track.argtypes = [vp, f32p, i32p]
+        L.crsdr_caf_track_device_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+        L.crsdr_track_state_bytes.argtypes = [C.POINTER(TrackDesc), C.POINTER(C.c_size_t)]
+        L.crsdr_track.argtypes = [f32p, i32p, vp, f32p, i32p, f32p] + [C.c_int] * 4 + [C.POINTER(TrackDesc), C.c_int]
     _lib = L
     return L
 
@@ -809,6 +827,43 @@ def beam_fuse_device(fused_ptr: int, nfused_ptr: int, bdet_ptr: int, bcount_ptr:
     cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
     _check(lib().crsdr_beam_fuse(cast(fused_ptr, C.c_float), cast(nfused_ptr, C.c_int32), cast(bdet_ptr, C.c_float), cast(bcount_ptr, C.c_int32), int(nbeams), int(K),
                                  int(nd), int(R), MEM_DEVICE))
+
+
+def track_desc(max_tracks, m=3, n=5, gate=9.0, sigma_r=0.5, sigma_f=0.5, p0_g=1.0, q_r=1e-3, q_f=1e-3, q_g=1e-4, coupling=0.0, tent_miss=2, conf_miss=4,
+               source=TRACK_SRC_ARRAY):
+    return TrackDesc(int(max_tracks), int(source), float(sigma_r), float(sigma_f), float(gate), float(p0_g), float(q_r), float(q_f), float(q_g), float(coupling),
+                     int(m), int(n), int(tent_miss), int(conf_miss))
+
+
+def track_state_bytes(desc) -> int:
+    """crsdr_track_state_bytes: the size of track()'s state buffer, a 16-byte header and 128 bytes per slot."""
+    n = C.c_size_t(0)
+    _check(lib().crsdr_track_state_bytes(C.byref(desc), C.byref(n)))
+    return int(n.value)
+
+
+def track(det, count, nd, R, desc, aux=None, state=None):
+    """crsdr_track on nlines lines: det [nlines][K][8] float32, count [nlines] int32, aux [nlines][K][2] float32 or None -> (trk
+    [nlines][T][16] float32 = id, status, r, f, g, sqrt(P00), sqrt(P11), age, hits, misses, slot, d2, power, snr, aux0, aux1; ntrk
+    [nlines][4] int32 = live, confirmed, initiated, dropped; state).  state: the uint8 array an earlier call returned, or None for the
+    empty table; it is not changed, the state behind the last line is returned.  The engine's tracker (Caf.set_track), bit for bit."""
+    t = np.ascontiguousarray(det, dtype=np.float32)
+    L, K, _ = t.shape
+    n = np.ascontiguousarray(count, dtype=np.int32).reshape(L)
+    a = None if aux is None else np.ascontiguousarray(aux, dtype=np.float32).reshape(L, K, 2)
+    nbytes = track_state_bytes(desc)
+    s = np.zeros(nbytes // 8, dtype=np.float64).view(np.uint8) if state is None else np.array(state, dtype=np.uint8).reshape(nbytes).copy()
+    out, nout = np.zeros((L, int(desc.max_tracks), 16), dtype=np.float32), np.zeros((L, 4), dtype=np.int32)
+    _check(lib().crsdr_track(_p(out, C.c_float), _p(nout, C.c_int32), s.ctypes.data_as(C.c_void_p), _p(t, C.c_float), _p(n, C.c_int32), _p(a, C.c_float), L, K, int(nd),
+                             int(R), C.byref(desc), MEM_HOST))
+    return out, nout, s
+
+
+def track_device(trk_ptr: int, ntrk_ptr: int, state_ptr: int, det_ptr: int, count_ptr: int, aux_ptr: int, nlines, K, nd, R, desc):
+    """crsdr_track with CRSDR_MEM_DEVICE: every pointer on the device (trk or ntrk, not both, and aux may be 0)."""
+    cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
+    _check(lib().crsdr_track(cast(trk_ptr, C.c_float), cast(ntrk_ptr, C.c_int32), C.c_void_p(int(state_ptr) or None), cast(det_ptr, C.c_float), cast(count_ptr, C.c_int32),
+                             cast(aux_ptr, C.c_float), int(nlines), int(K), int(nd), int(R), C.byref(desc), MEM_DEVICE))
 
 
 def ambiguity_device(chi_ptr: int, map_ptr: int, peak_ptr: int, matrix_ptr: int, nrows, B, seg, nlags, ref_row, window, guard):
@@ -1578,6 +1633,30 @@ class Caf:
         ptrs = [C.c_void_p() for _ in range(5)]
         _check(lib().crsdr_caf_beams_device_buffers(self._h, *[C.byref(p) for p in ptrs]))
         return dict(zip(("bmap", "bdet", "bcount", "fused", "nfused"), [p.value for p in ptrs]))
+
+    def set_track(self, desc: "TrackDesc | None"):
+        """crsdr_caf_set_track: the tracker behind every submit's lists (None: off); empties its state.  Between submits, with the
+        detector on; the fused source with beams detected on."""
+        _check(lib().crsdr_caf_set_track(self._h, None if desc is None else C.byref(desc)))
+        self.max_tracks = 0 if desc is None else int(desc.max_tracks)
+
+    def track_reset(self):
+        """crsdr_caf_track_reset: the empty table, ids from 1."""
+        _check(lib().crsdr_caf_track_reset(self._h))
+
+    def fetch_track(self, trk=True, ntrk=True) -> dict:
+        """Waits for the last submit.  trk [nest][T][16] as track() lays it out, ntrk [nest][4] int32 = live, confirmed, initiated,
+        dropped."""
+        n, T = self._last()[0], max(1, getattr(self, "max_tracks", 0))
+        t = np.zeros((n, T, 16), dtype=np.float32) if trk else None
+        c = np.zeros((n, 4), dtype=np.int32) if ntrk else None
+        _check(lib().crsdr_caf_fetch_track(self._h, _p(t, C.c_float), _p(c, C.c_int32)))
+        return {k: v for k, v in (("trk", t), ("ntrk", c)) if v is not None}
+
+    def track_device_buffers(self) -> dict:
+        ptrs = [C.c_void_p() for _ in range(2)]
+        _check(lib().crsdr_caf_track_device_buffers(self._h, *[C.byref(p) for p in ptrs]))
+        return dict(zip(("trk", "ntrk"), [p.value for p in ptrs]))
 
     def set_cancel(self, taps: "int | None", dopp: int = 0):
         """crsdr_caf_set_cancel: the canceller in front of every submit's Doppler stage (taps None: off).  Between submits."""

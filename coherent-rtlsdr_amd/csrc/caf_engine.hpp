@@ -12,6 +12,8 @@
 //     With beams set (crsdr_caf_set_beams; caf_beams.hpp, caf_beams_kernels.hpp) one more at the end: every beam's map across the rows on
 //     the fp32 matrix pipe; with the detector on three more behind it: the detector's two on the beam maps, (line, beam) taking the
 //     place of the line, and the fusion of the beams' lists into one per line.  Its buffers are made by set_beams, between submits.
+//     With the tracker set (crsdr_caf_set_track; caf_track.hpp, caf_track_kernels.hpp) one more behind everything else: one workgroup
+//     that walks the lines of the submit and carries the tracks from submit to submit.  Its buffers are made by set_track.
 #pragma once
 
 #include "caf.hpp"
@@ -19,6 +21,7 @@
 #include "caf_bearing.hpp"
 #include "caf_cancel.hpp"
 #include "caf_cfar_kernels.hpp"
+#include "caf_track_kernels.hpp"
 
 // `launch` with LG = log2 nd, 3 .. 12
 #define CAF_DISPATCH(lg, launch)                                                    \
@@ -37,6 +40,7 @@
 
 constexpr int kCafLaunches = 3, kCafCfarLaunches = 2, kCafCancelLaunches = 4, kCafBearingLaunches = 3;      // (the canceller's five take the place of one)
 constexpr int kCafBeamLaunches = 1, kCafBeamDetLaunches = 3;                                                // (the maps; the detector's two on them and the fusion)
+constexpr int kCafTrackLaunches = 1, kTrackMaxLines = 4096;
 constexpr long long kCafMaxCells = 1ll << 24;           // (max_batch / frames) * nrows * nd * nlags
 
 // the canceller's device memory for `lines` lines: the engine's own buffers, or parts of one per-op slot
@@ -91,6 +95,14 @@ struct crsdr_caf {
         DevBuf<int32_t> bcount, nfused, tcount;
         DevBuf<cfar::Cand> slots;
     } bb;
+    // crsdr_caf_set_track: on (false = off), the state that a submit hands to the next, and the results
+    struct Track {
+        bool on = false, submitted = false;
+        trk::Params prm{};
+        DevBuf<unsigned char> state;
+        DevBuf<float> trk;
+        DevBuf<int32_t> ntrk;
+    } tk;
     hipStream_t last_stream = nullptr;
     int last_nest = 0, last_launches = 0;
     bool submitted = false;
@@ -298,6 +310,50 @@ static int beam_fuse_enqueue(hipStream_t S, const float *bdet, const int32_t *bc
     return CRSDR_OK;
 }
 
+// every limit of the tracker of section (w), for crsdr_caf_set_track, crsdr_track and crsdr_track_state_bytes
+static int track_args_ok(const char *who, const crsdr_caf_track_desc *d, trk::Params *prm)
+{
+    *prm = trk::Params{d->max_tracks, d->source, d->sigma_r, d->sigma_f, d->gate, d->p0_g, d->q_r, d->q_f, d->q_g, d->coupling, d->m, d->n, d->tent_miss, d->conf_miss};
+    switch (trk::bad_limit(*prm)) {
+    case 0: return CRSDR_OK;
+    case 1: return fail(CRSDR_EINVAL, "%s: max_tracks = %d (1..%d)", who, d->max_tracks, trk::MAX_TRACKS);
+    case 2: return fail(CRSDR_EINVAL, "%s: source = %d", who, d->source);
+    case 3: return fail(CRSDR_EINVAL, "%s: sigma_r, sigma_f = %g, %g (finite and greater than 0)", who, d->sigma_r, d->sigma_f);
+    case 4: return fail(CRSDR_EINVAL, "%s: gate = %g (finite and greater than 0)", who, d->gate);
+    case 5: return fail(CRSDR_EINVAL, "%s: p0_g = %g (finite and greater than 0)", who, d->p0_g);
+    case 6: return fail(CRSDR_EINVAL, "%s: q_r, q_f, q_g = %g, %g, %g (finite, none negative)", who, d->q_r, d->q_f, d->q_g);
+    case 7: return fail(CRSDR_EINVAL, "%s: coupling = %g (finite)", who, d->coupling);
+    case 8: return fail(CRSDR_EINVAL, "%s: m, n = %d, %d (1 <= m <= n <= %d)", who, d->m, d->n, trk::MAX_HIST);
+    default: return fail(CRSDR_EINVAL, "%s: tent_miss, conf_miss = %d, %d (at least 1)", who, d->tent_miss, d->conf_miss);
+    }
+}
+
+// k_caf_track's LDS at its largest: above the 64 KiB default.  One value for every caller, so that no call lowers another's; set once
+// per device (the attribute is the device's copy of the kernel's: a call on another device sets that one's)
+static int track_lds_limit()
+{
+    static std::mutex mu;
+    static std::vector<int> done;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mu);
+    for (int d : done)
+        if (d == dev) return CRSDR_OK;
+    HIP_TRY(hipFuncSetAttribute((const void *)caf_track::k_caf_track, hipFuncAttributeMaxDynamicSharedMemorySize, (int)caf_track::lds_bytes(trk::MAX_TRACKS, trk::MAX_MEAS)));
+    done.push_back(dev);
+    return CRSDR_OK;
+}
+
+// the tracker's one launch, for the object and for crsdr_track: the same kernel on the same arguments, so the same bits
+static int track_enqueue(hipStream_t S, const float *det, size_t det_stride, const int32_t *count, size_t count_stride, const float *aux, int aux_mode, int nlines, int K,
+                         int nd, int R, const trk::Params &prm, unsigned char *state, float *out, int32_t *nout)
+{
+    hipLaunchKernelGGL(caf_track::k_caf_track, dim3(1), dim3(caf_track::THREADS), caf_track::lds_bytes(prm.max_tracks, K), S, det, det_stride, count, count_stride, aux,
+                       aux_mode, nlines, K, nd, R, prm, state, out, nout);
+    HIP_TRY(hipGetLastError());
+    return CRSDR_OK;
+}
+
 static void caf_free(crsdr_caf *q)
 {
     if (!q) return;
@@ -362,7 +418,7 @@ static int beams_launch(crsdr_caf *q, hipStream_t S)
     return CRSDR_OK;
 }
 
-static int caf_launch(crsdr_caf *q, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nblocks, hipStream_t S)
+static int caf_launch_lists(crsdr_caf *q, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nblocks, hipStream_t S)
 {
     const CancelBufs cb = q->cn.bufs();
     const int rc = caf_enqueue(S, packets, packet_stride, matrix_offset, nblocks, q->nrows, q->B, q->frames, q->seg, q->nlags, q->ref_row, q->window, q->guard, q->tw, q->win,
@@ -382,6 +438,22 @@ static int caf_launch(crsdr_caf *q, const int8_t *packets, size_t packet_stride,
     if (rc3) return rc3;
     q->bg.submitted = true; q->last_launches += kCafBearingLaunches;
     return beams_launch(q, S);
+}
+
+// a submit: everything up to the lists, and the tracker behind bearings and fusion (nothing with it off)
+static int caf_launch(crsdr_caf *q, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nblocks, hipStream_t S)
+{
+    { const int rc = caf_launch_lists(q, packets, packet_stride, matrix_offset, nblocks, S); if (rc) return rc; }
+    crsdr_caf::Track &t = q->tk;
+    if (!t.on) return CRSDR_OK;
+    const size_t K = (size_t)q->cf.prm.max_det, entries = (size_t)(q->nrows + 1);
+    const bool fused = t.prm.source == trk::SRC_FUSED;
+    const int rc = fused ? track_enqueue(S, q->bb.fused, K * 8, q->bb.nfused, 1, nullptr, caf_track::AUX_BEAM, q->last_nest, (int)K, q->nd, q->nlags, t.prm, t.state, t.trk, t.ntrk)
+                         : track_enqueue(S, q->cf.det.p + (size_t)q->nrows * K * 8, entries * K * 8, q->cf.count.p + q->nrows, entries, q->bg.on ? q->bg.dir.p : nullptr,
+                                         q->bg.on ? caf_track::AUX_DIR : caf_track::AUX_NONE, q->last_nest, (int)K, q->nd, q->nlags, t.prm, t.state, t.trk, t.ntrk);
+    if (rc) return rc;
+    t.submitted = true; q->last_launches += kCafTrackLaunches;
+    return CRSDR_OK;
 }
 
 extern "C" int crsdr_caf_submit(crsdr_caf *q, const void *device_packets, size_t packet_stride, size_t matrix_offset, int nblocks, void *hip_stream)
@@ -445,6 +517,7 @@ extern "C" int crsdr_caf_device_buffers(crsdr_caf *q, void **chi, void **map, vo
 extern "C" int crsdr_caf_set_cfar(crsdr_caf *q, const crsdr_cfar_desc *desc)
 {
     if (!q) return fail(CRSDR_EINVAL, "caf_set_cfar: NULL caf");
+    if (q->tk.on) return fail(CRSDR_ESTATE, "caf_set_cfar: the tracker is on (crsdr_caf_set_track): its measurements are this detector's lists; turn it off first");
     if (q->bb.on) return fail(CRSDR_ESTATE, "caf_set_cfar: beams are on (crsdr_caf_set_beams): whether they are detected on, and the lists' sizes, are this detector's; turn them off first");
     if (q->bg.on) return fail(CRSDR_ESTATE, "caf_set_cfar: bearings are on (crsdr_caf_set_bearing): their buffers and training set are this detector's; turn them off first");
     cfar::Params prm{};
@@ -493,6 +566,7 @@ extern "C" int crsdr_caf_cfar_device_buffers(crsdr_caf *q, void **det, void **co
 extern "C" int crsdr_caf_set_bearing(crsdr_caf *q, const crsdr_caf_bearing_desc *desc)
 {
     if (!q) return fail(CRSDR_EINVAL, "caf_set_bearing: NULL caf");
+    if (q->tk.on) return fail(CRSDR_ESTATE, "caf_set_bearing: the tracker is on (crsdr_caf_set_track): its auxiliary pairs are these bearings; turn it off first");
     const size_t lines = (size_t)(q->max_batch / q->frames);
     brg::Params prm{};
     if (desc) {
@@ -582,6 +656,7 @@ extern "C" int crsdr_bearing(float *dir, float *spec, const float *chi, int nrow
 extern "C" int crsdr_caf_set_beams(crsdr_caf *q, const crsdr_caf_beams_desc *desc)
 {
     if (!q) return fail(CRSDR_EINVAL, "caf_set_beams: NULL caf");
+    if (q->tk.on) return fail(CRSDR_ESTATE, "caf_set_beams: the tracker is on (crsdr_caf_set_track): the fused list may be its source; turn it off first");
     const size_t lines = (size_t)(q->max_batch / q->frames), cells = (size_t)q->nd * (size_t)q->nlags, m = (size_t)(q->nrows - 1);
     if (desc) { const int rc_ = beams_args_ok("caf_set_beams", q->nrows, (long long)lines, q->nd, q->nlags, desc->nbeams, desc->weights, desc->flags); if (rc_) return rc_; }
     HIP_TRY(hipSetDevice(q->device));
@@ -698,6 +773,107 @@ extern "C" int crsdr_caf_beam_steer(float *weights, int mx, int my, float d, int
         if (!(xy[k] >= -1.7976931348623157e308 && xy[k] <= 1.7976931348623157e308)) return fail(CRSDR_EINVAL, "caf_beam_steer: a direction is not finite");
     for (int b = 0; b < nbeams; ++b) bm::steer(weights + 2 * (size_t)b * mx * my, mx, my, d, ncx, ncy, xy[2 * b], xy[2 * b + 1]);
     return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_set_track(crsdr_caf *q, const crsdr_caf_track_desc *desc)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_set_track: NULL caf");
+    trk::Params prm{};
+    if (desc) {
+        { const int rc_ = track_args_ok("caf_set_track", desc, &prm); if (rc_) return rc_; }
+        if (!q->cf.on) return fail(CRSDR_ESTATE, "caf_set_track: no detector set (crsdr_caf_set_cfar): there are no detections to track");
+        if (prm.source == trk::SRC_FUSED && !(q->bb.on && q->bb.det))
+            return fail(CRSDR_ESTATE, "caf_set_track: the fused source needs beams with detection (crsdr_caf_set_beams behind crsdr_caf_set_cfar)");
+    }
+    HIP_TRY(hipSetDevice(q->device));
+    if (q->submitted) HIP_TRY(hipDeviceSynchronize());      // the last submit may still write the buffers let go here
+    q->tk = crsdr_caf::Track();
+    if (!desc) return CRSDR_OK;
+    const size_t lines = (size_t)(q->max_batch / q->frames), T = (size_t)prm.max_tracks, sb = trk::state_bytes(prm.max_tracks);
+    crsdr_caf::Track &t = q->tk;
+    int r = CRSDR_OK;
+    if ((r = t.state.alloc(sb)) || (r = t.trk.alloc(lines * T * trk::REC)) || (r = t.ntrk.alloc(lines * 4)) || (r = HIP_RC(hipMemset(t.state.p, 0, sb))) ||
+        (r = track_lds_limit())) {
+        q->tk = crsdr_caf::Track();
+        return r;
+    }
+    t.prm = prm; t.on = true;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_track_reset(crsdr_caf *q)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_track_reset: NULL caf");
+    if (!q->tk.on) return fail(CRSDR_ESTATE, "caf_track_reset: no tracker set (crsdr_caf_set_track)");
+    HIP_TRY(hipSetDevice(q->device));
+    if (q->submitted) HIP_TRY(hipDeviceSynchronize());      // the last submit may still write the state
+    HIP_TRY(hipMemset(q->tk.state.p, 0, trk::state_bytes(q->tk.prm.max_tracks)));
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_fetch_track(crsdr_caf *q, float *out, int32_t *nout)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_fetch_track: NULL caf");
+    if (!q->tk.on) return fail(CRSDR_ESTATE, "caf_fetch_track: no tracker set (crsdr_caf_set_track)");
+    if (!q->tk.submitted) return fail(CRSDR_ESTATE, "caf_fetch_track: nothing submitted since the tracker was set");
+    HIP_TRY(hipSetDevice(q->device));
+    const size_t lines = (size_t)q->last_nest, T = (size_t)q->tk.prm.max_tracks;
+    if (out) HIP_TRY(hipMemcpyAsync(out, q->tk.trk.p, sizeof(float) * lines * T * trk::REC, hipMemcpyDeviceToHost, q->last_stream));
+    if (nout) HIP_TRY(hipMemcpyAsync(nout, q->tk.ntrk.p, sizeof(int32_t) * lines * 4, hipMemcpyDeviceToHost, q->last_stream));
+    HIP_TRY(hipStreamSynchronize(q->last_stream));
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_track_device_buffers(crsdr_caf *q, void **out, void **nout)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_track_device_buffers: NULL caf");
+    if (!q->tk.on) return fail(CRSDR_ESTATE, "caf_track_device_buffers: no tracker set (crsdr_caf_set_track)");
+    if (out) *out = q->tk.trk;
+    if (nout) *nout = q->tk.ntrk;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_track_state_bytes(const crsdr_caf_track_desc *desc, size_t *bytes)
+{
+    if (!desc || !bytes) return fail(CRSDR_EINVAL, "track_state_bytes: NULL argument");
+    trk::Params prm{};
+    { const int rc_ = track_args_ok("track_state_bytes", desc, &prm); if (rc_) return rc_; }
+    *bytes = trk::state_bytes(prm.max_tracks);
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_track(float *out, int32_t *nout, void *state, const float *det, const int32_t *count, const float *aux, int nlines, int K, int nd, int R,
+                           const crsdr_caf_track_desc *desc, int mem_kind)
+{
+    if (!state || !det || !count || !desc || (!out && !nout)) return fail(CRSDR_EINVAL, "track: need state, det, count, a descriptor and at least one of trk, ntrk");
+    if (nlines < 1 || nlines > kTrackMaxLines) return fail(CRSDR_EINVAL, "track: nlines = %d (1..%d)", nlines, kTrackMaxLines);
+    if (K < 1 || K > trk::MAX_MEAS) return fail(CRSDR_EINVAL, "track: K = %d (1..%d)", K, trk::MAX_MEAS);
+    const int lgd = nd >= 1 && nd <= (1 << caf::CAF_MAX_LOG2) ? ilog2_exact(nd) : -1;
+    if (lgd < caf::CAF_MIN_LOG2) return fail(CRSDR_EINVAL, "track: nd = %d (a power of two in [8, 4096])", nd);
+    if (R < 1 || R > caf::CAF_MAX_LAGS) return fail(CRSDR_EINVAL, "track: R = %d (1..%d)", R, caf::CAF_MAX_LAGS);
+    trk::Params prm{};
+    { const int rc_ = track_args_ok("track", desc, &prm); if (rc_) return rc_; }
+    OP_PROLOGUE_MEM("track", mem_kind);
+    const size_t L = (size_t)nlines, T = (size_t)prm.max_tracks, db = sizeof(float) * L * (size_t)K * 8, cb = sizeof(int32_t) * L, ab = sizeof(float) * L * (size_t)K * 2;
+    const size_t sb = trk::state_bytes(prm.max_tracks), tb = sizeof(float) * L * T * trk::REC, nb = sizeof(int32_t) * L * 4;
+    OpStage st(mem_kind);
+    const float *d_d = (const float *)st.in(0, det, db, 4);
+    const int32_t *d_c = (const int32_t *)st.in(1, count, cb, 4);
+    const float *d_a = aux ? (const float *)st.in(2, aux, ab, 4) : nullptr;
+    unsigned char *d_s = (unsigned char *)st.in(3, state, sb, 8);
+    float *d_t = (float *)st.out(4, out, tb, 4);
+    int32_t *d_n = (int32_t *)st.out(5, nout, nb, 4);
+    if (st.rc) return st.rc;
+    if (st.misaligned) return fail(CRSDR_EINVAL, "track: device det, count, aux, trk and ntrk 4-byte, state 8-byte aligned");
+    // (device memory and an output not asked for: the kernel writes it all the same)
+    if (!d_t) { OP_RESERVE(4, tb); d_t = (float *)g_op.buf[4]; }
+    if (!d_n) { OP_RESERVE(5, nb); d_n = (int32_t *)g_op.buf[5]; }
+    { const int rc_ = track_lds_limit(); if (rc_) return rc_; }
+    { const int rc_ = track_enqueue(0, d_d, (size_t)K * 8, d_c, 1, d_a, d_a ? caf_track::AUX_PAIRS : caf_track::AUX_NONE, nlines, K, nd, R, prm, d_s, d_t, d_n); if (rc_) return rc_; }
+    st.back(out, d_t, tb);
+    st.back(nout, d_n, nb);
+    st.back(state, d_s, sb);
+    return st.finish();
 }
 
 extern "C" int crsdr_caf_set_cancel(crsdr_caf *q, const crsdr_caf_cancel_desc *desc)

@@ -13,6 +13,8 @@ static_assert(sizeof(dir_t) == 8 * sizeof(float), "dir_t is the bearings' eight 
 
 static_assert(sizeof(fused_t) == 8 * sizeof(float), "fused_t is the fusion's eight floats");
 
+static_assert(sizeof(track_t) == 16 * sizeof(float), "track_t is the tracker's sixteen floats");
+
 double fused_t::snr_db() const { return snr > 0.f ? 10.0 * std::log10((double)snr) : -INFINITY; }
 double det_t::snr_db() const { return snr > 0.f ? 10.0 * std::log10((double)snr) : -INFINITY; }
 double peak_t::power_db() const { return power > 0.f ? 10.0 * std::log10((double)power) : -INFINITY; }
@@ -113,6 +115,34 @@ int batch::fetch_beams(bool want_bmap, bool want_lists)
     }
     if (!rc) nlines = nest;
     if (rc && cf && nb) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::set_track(const crsdr_caf_track_desc *desc)
+{
+    int rc = cf ? crsdr_caf_set_track(cf, desc) : CRSDR_ESTATE;
+    if (!rc) { ntracks = desc ? desc->max_tracks : 0; trk.clear(); ntrk.clear(); }
+    if (rc && cf) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::reset_track()
+{
+    int rc = cf ? crsdr_caf_track_reset(cf) : CRSDR_ESTATE;
+    if (rc && cf) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::fetch_track()
+{
+    int nest = 0;
+    int rc = !cf || !ntracks ? CRSDR_ESTATE : crsdr_caf_last_submit(cf, &nest, nullptr);
+    if (!rc) {
+        trk.assign((size_t)nest * ntracks, track_t{}); ntrk.assign((size_t)nest * 4, 0);
+        rc = crsdr_caf_fetch_track(cf, &trk[0].id, ntrk.data());
+    }
+    if (!rc) nlines = nest;
+    if (rc && cf && ntracks) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
     return rc;
 }
 

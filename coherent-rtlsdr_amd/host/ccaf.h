@@ -37,13 +37,20 @@ struct fused_t {
     double snr_db() const;                           // the cell above its training cells' mean in its beam's map; -inf for 0
 };
 
+// (id, status, r, f, g, sigma_r, sigma_f, age, hits, misses, slot, d2, power, snr, aux0, aux1) of one track slot of one line, as crsdr_caf's
+// tracker lays them out: status 0 free, 1 tentative, 2 confirmed, 3 ended in this line; r in lag cells, f in Doppler bins, g in bins per line
+struct track_t {
+    float id, status, r, f, g, sigma_r, sigma_f, age, hits, misses, slot, d2, power, snr, aux0, aux1;
+    bool confirmed() const { return status == 2.f; }
+};
+
 // One line per `frames` consecutive packets of a submit: chi [nrows][nd][nlags] of every row against row ref_row over seg-sample
 // segments, the array map [nd][nlags], and nrows + 1 peaks (the rows', then the map's) searched outside |Doppler| < guard.
 class batch {
     crsdr_caf *cf = nullptr;
     int rows, bins, lags, kdet = 0, nbasis = 0, npts = 0;
     bool bearings = false, beam_lists = false;
-    int nb = 0;
+    int nb = 0, ntracks = 0;
 
 public:
     batch(int nrows, int blocksize, int max_batch, int seg, int nlags, int ref_row = 0, int window = CRSDR_WINDOW_RECT, int guard = 0, int frames = 1, int device = 0);
@@ -77,6 +84,14 @@ public:
     // waits, and fills fused and nfused (with the detector), and bmap, bdet and bcount if asked for; CRSDR_ESTATE with the beams off
     int fetch_beams(bool want_bmap = false, bool want_lists = false);
     int nbeams() const { return nb; }
+    // the tracker behind every later submit's lists (crsdr_caf_set_track; NULL: off), its table empty.  Between submits, with the
+    // detector on (the fused source: with beams detected on); while it is on set_cfar, set_bearing and set_beams are refused.
+    int set_track(const crsdr_caf_track_desc *desc);
+    // the empty table again, ids from 1
+    int reset_track();
+    // waits, and fills trk and ntrk: the tracks of every line of the last submit; CRSDR_ESTATE with the tracker off
+    int fetch_track();
+    int max_tracks() const { return ntracks; }
     int basis() const { return nbasis; }             // taps (2 dopp + 1), 0 with the canceller off
     int lines() const { return nlines; }
     int nrows() const { return rows; }
@@ -100,6 +115,9 @@ public:
     std::vector<int32_t> nfused;                     // [lines]: the survivors of the fusion, which may be more than max_det
     int fused_held(int e) const { return beam_lists ? (nfused[(size_t)e] < kdet ? nfused[(size_t)e] : kdet) : 0; }
     const fused_t &fused_at(int e, int k) const { return fused[(size_t)e * kdet + k]; }
+    std::vector<track_t> trk;                        // [lines][max_tracks]: every slot of every line; free slots zero
+    std::vector<int32_t> ntrk;                       // [lines][4]: live tracks after the line, confirmed, initiated, dropped
+    const track_t &track_at(int e, int i) const { return trk[(size_t)e * ntracks + i]; }
     std::vector<float> coef;                         // [lines][nrows][basis][2]: the canceller's filter of every row
     std::vector<float> cinfo;                        // [lines][nrows][2]: the share of the row's power that stays, and the status
     float residual(int e, int c) const { return cinfo[2 * ((size_t)e * rows + c)]; }

@@ -74,6 +74,8 @@ int main(int argc, char **argv)
     int beams_mx = 0, beams_my = 0, beams_nx = 0, beams_ny = 0;
     crsdr_caf_bearing_desc bearing = {0, 0, 100, 100, 0.5f, CRSDR_BEARING_CONVENTIONAL, 1e-2f, 0, 0u};
     crsdr_caf_cancel_desc cancel = {0, 0};
+    bool track_on = false;
+    crsdr_caf_track_desc track = {16, CRSDR_TRACK_SRC_ARRAY, 0.5, 0.5, 9.0, 1.0, 1e-3, 1e-3, 1e-4, 0.0, 3, 5, 2, 4};
     bool engine_batches = false;
     int ranks = 1, rank = 0, device = 0;
     std::string idfile;
@@ -183,6 +185,19 @@ int main(int argc, char **argv)
             beams_on = true;
             if (n != 4) beams_mx = -1;                                                       // (refused below with the rest)
         }
+        // with --caf and --cfar: tracks across the lines from the detections (crsdr_caf_set_track): M-of-N confirmation, GATE on d2 (9),
+        // --track-max T slots (16), --track-sigma SR:SF measurement deviations in cells and bins (0.5:0.5), --track-q QR:QF:QG process
+        // noise per line (1e-3:1e-3:1e-4), --coupling C lag cells per line per Doppler bin (0).  The source is the fused list with
+        // --caf-beams, the array map's otherwise.  Prints per line the confirmed tracks: id, lag, Doppler, rate, age, and the beam or angles
+        else if (a == "--track" && i + 1 < argc) {
+            const int n = std::sscanf(argv[++i], "%d:%d:%lf", &track.m, &track.n, &track.gate);
+            track_on = true;
+            if (n < 2) track.m = -1;                                                         // (refused below with the rest)
+        }
+        else if (a == "--track-max") val(track.max_tracks);
+        else if (a == "--track-sigma" && i + 1 < argc) { if (std::sscanf(argv[++i], "%lf:%lf", &track.sigma_r, &track.sigma_f) != 2) track.sigma_r = -1.0; }
+        else if (a == "--track-q" && i + 1 < argc) { if (std::sscanf(argv[++i], "%lf:%lf:%lf", &track.q_r, &track.q_f, &track.q_g) != 3) track.q_r = -1.0; }
+        else if (a == "--coupling" && i + 1 < argc) track.coupling = std::atof(argv[++i]);
         else if (a == "--adaptive" && i + 1 < argc) { bearing.mode = CRSDR_BEARING_ADAPTIVE; bearing.loading = (float)std::atof(argv[++i]); }
         else if (a == "--bearing-levels") val(bearing.levels);
         else if (a == "--guard") val(caf_guard);
@@ -230,6 +245,18 @@ int main(int argc, char **argv)
             servo_table = true;
             for (char *tok = std::strtok(argv[++i], ","); tok; tok = std::strtok(nullptr, ",")) table_lags.push_back(std::atof(tok));
         }
+    }
+    if (track_on) {
+        // numbers only (no device): the tracker's limits are the library's own (crsdr_track_state_bytes checks them on the host)
+        size_t state_bytes = 0;
+        track.source = beams_on ? CRSDR_TRACK_SRC_FUSED : CRSDR_TRACK_SRC_ARRAY;
+        if (!caf_seg || !cfar_on) { std::printf("track: --track needs --caf and --cfar: there are no detections to track\nDEMO FAILED\n"); return 1; }
+        if (crsdr_track_state_bytes(&track, &state_bytes)) {
+            std::printf("track: --track M:N[:GATE] [--track-max T] [--track-sigma SR:SF] [--track-q QR:QF:QG] [--coupling C] refused: %s\nDEMO FAILED\n", crsdr_last_error());
+            return 1;
+        }
+        std::printf("track: %d of %d gate %g slots %d sigma %g:%g q %g:%g:%g coupling %g source %s\n", track.m, track.n, track.gate, track.max_tracks, track.sigma_r,
+                    track.sigma_f, track.q_r, track.q_f, track.q_g, track.coupling, beams_on ? "fused" : "array");
     }
     int fails = 0;
     if (servo_table) {
@@ -588,12 +615,13 @@ int main(int argc, char **argv)
                 }
                 if (!good) { std::printf("beams: --caf-beams MXxMY:NXxNY refused (MX MY must be --nsig = %d, NX NY at most 64)\nDEMO FAILED\n", nsig); return 1; }
             }
+            if (track_on && caf->set_track(&track)) { std::printf("track: --track refused: %s\nDEMO FAILED\n", crsdr_last_error()); return 1; }
         }
         auto ambiguity = [&](int b) {
             if (!caf || !ok) return;
             ok = caf->submit(coherent.engine_plan()) == CRSDR_OK && caf->fetch() == CRSDR_OK && (!cfar_on || caf->fetch_cfar() == CRSDR_OK) &&
                  (!cancel_on || caf->fetch_cancel(false) == CRSDR_OK) && (!bearing_on || caf->fetch_bearing() == CRSDR_OK) &&
-                 (!beams_on || caf->fetch_beams() == CRSDR_OK);
+                 (!beams_on || caf->fetch_beams() == CRSDR_OK) && (!track_on || caf->fetch_track() == CRSDR_OK);
             if (!ok || !report) return;
             for (int e = 0; cancel_on && e < caf->lines(); ++e) {
                 double sum = 0.0;
@@ -623,6 +651,16 @@ int main(int argc, char **argv)
                     std::printf("beams: batch %d line %d fused %d of %d: lag %d%+.3f doppler %d%+.3f power %.6g snr %.2f dB beam %d alpha %.3f deg beta %.3f deg\n", b, e, k,
                                 (int)caf->nfused[(size_t)e], (int)d.lag, (double)d.dlag, (int)d.doppler, (double)d.ddop, (double)d.power, d.snr_db(), bm,
                                 beam_xy[2 * (size_t)bm] * 1.8, beam_xy[2 * (size_t)bm + 1] * 1.8);
+                }
+            for (int e = 0; track_on && e < caf->lines(); ++e)
+                for (int i = 0; i < caf->max_tracks(); ++i) {
+                    const ccaf::track_t &t = caf->track_at(e, i);
+                    if (!t.confirmed()) continue;
+                    char where[96] = "";
+                    if (beams_on) std::snprintf(where, sizeof where, " beam %d", (int)t.aux0);
+                    else if (bearing_on) std::snprintf(where, sizeof where, " alpha %.3f deg beta %.3f deg", (double)t.aux0 * 180.0 / bearing.ncx, (double)t.aux1 * 180.0 / bearing.ncy);
+                    std::printf("track: batch %d line %d id %d: lag %.3f doppler %.3f rate %.4f age %d hits %d live %d%s\n", b, e, (int)t.id, (double)t.r, (double)t.f,
+                                (double)t.g, (int)t.age, (int)t.hits, (int)caf->ntrk[4 * (size_t)e], where);
                 }
             for (int e = 0; e < caf->lines(); ++e)
                 for (int c = 0; c <= caf->nrows(); ++c) {

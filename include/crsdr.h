@@ -1379,6 +1379,105 @@ int crsdr_beam_fuse(float *fused, int32_t *nfused, const float *bdet, const int3
  * mx my <= 64, 2 <= ncx, ncy <= 512, d finite and > 0, every coordinate finite: else CRSDR_EINVAL. */
 int crsdr_caf_beam_steer(float *weights, int mx, int my, float d, int ncx, int ncy, const double *xy, int nbeams);
 
+/* Tracks.  Everything above is per line: a list of (lag, Doppler, bearing) every line, false alarms at the detector's design rate among
+ * them, and which entry is last line's target is left to the host.  This stage, behind the detector and on the device, is a
+ * multi-target tracker in the lag-Doppler plane -- a Kalman filter per track, gating, a deterministic global-nearest-neighbour
+ * assignment, M-of-N confirmation, coasting through missed detections, Doppler wrap -- in fp64, in ONE workgroup per submit that loops
+ * over the lines, with its state carried from submit to submit.  The host fetches a short table of tracks in place of the lists.  It is
+ * off until crsdr_caf_set_track; off, a submit is the same launches and the same bits, in every combination of canceller, detector,
+ * bearings and beams.
+ *
+ * Source.  The measurements of a line are the slots q < min(count, K) of ONE detection list, K the detector's max_det:
+ *     CRSDR_TRACK_SRC_ARRAY   the array map's list (det entry nrows).  With bearings on the auxiliary pair of a detection is
+ *                             (cx + (x - cx), cy + (y - cy)) from its dir record, the two sums in fp64; with bearings off (-1, -1).
+ *     CRSDR_TRACK_SRC_FUSED   the fused list of the beams.  The auxiliary pair is (beam index, -1).
+ * A measurement is z = (lag + dlag, doppler + ddop), each the sum of the two published fp32 figures in fp64; its power and snr are
+ * copied from the record.  A slot whose lag or Doppler lies outside the map, or whose dlag or ddop is not finite (hand-made lists only),
+ * is no measurement.
+ * State.  T = max_tracks slots.  A live track has x = (r, f, g) -- lag in cells, Doppler in bins, Doppler rate in bins per line -- a
+ * symmetric 3 x 3 covariance P, an id, a status (1 tentative, 2 confirmed), age, hits, consecutive misses and a 32-bit hit history;
+ * everything fp64 or an integer.  With H = nd / 2, wrap(v) is the value of v in [-H, H) modulo nd; it is applied to f after every
+ * prediction and update, and to every Doppler innovation.
+ * Per line, in this order:
+ *  1. Predict every live track.  r' = r + coupling (f + g / 2), f' = wrap(f + g), g' = g; P' = F P F^T + diag(q_r, q_f, q_g) with F
+ *     that map's Jacobian.  coupling is the caller's figure in lag cells per line per Doppler bin; it may be 0 and its sign is the
+ *     caller's.
+ *  2. Range exit.  A track whose predicted r is < -1 or > R ends this line with status 3 and takes no further part: it is reported
+ *     with its predicted state, its counts as they were, slot -1.
+ *  3. Gate.  For track slot i and measurement slot j: nu = (z_r - r', wrap(z_f - f')), S = P'[0:2, 0:2] + diag(sigma_r^2, sigma_f^2),
+ *     d2 = nu^T S^-1 nu by the closed 2 x 2 inverse.  The pair is a candidate iff d2 <= gate.
+ *  4. Assign: greedy global nearest neighbour under a strict total order.  The candidates are sorted by (d2, i, j) ascending and walked
+ *     in that order; a candidate is taken iff its track and its measurement are both still free.  That sentence is the definition; the
+ *     device takes, in rounds, every candidate that is the first of its row and of its column among the free ones, which gives the
+ *     same set.
+ *  5. Update every assigned track: K = P' H^T S^-1, x = x' + K nu, f wrapped, P = P' - K S K^T, symmetrised by copying the upper
+ *     triangle; hits + 1, misses = 0, history << 1 | 1; it remembers its measurement's slot, d2, power, snr and auxiliary pair.
+ *     Coast every other live track: x = x', P = P', misses + 1, history << 1; the remembered power, snr and pair stay.
+ *     age + 1 for both.
+ *  6. Status.  A tentative track becomes confirmed when the popcount of the low N history bits is >= M; otherwise it ends (status 3)
+ *     when misses >= tent_miss or age >= N.  A confirmed track ends when misses >= conf_miss.  A slot that ended in this line is
+ *     reported once with status 3 and its last state; it is free from the next line on, never within this one.
+ *  7. Initiate.  Every unassigned measurement, in slot order, starts a tentative track in the lowest slot that was free at the start
+ *     of the line: x = (z_r, wrap(z_f), 0), P = diag(sigma_r^2, sigma_f^2, p0_g), age = 0, hits = 1, history 1, id = the engine's
+ *     counter, which then advances; it runs 1 .. 2^24 - 1 and continues at 1.  With no slot left the measurement is dropped and counted.
+ * Outputs per line:
+ *     trk  [nest][T][16] float    (id, status (0 free, 1, 2, 3), r, f, g, sqrt(P00), sqrt(P11), age, hits, misses, the measurement slot of
+ *                                 this line or -1, its d2 or 0, power, snr, aux0, aux1), each rounded once from fp64, the integers
+ *                                 exact; free slots all zero
+ *     ntrk [nest][4] int32        live tracks after the line, confirmed, initiated, dropped
+ * Carry-over and bits.  The state after the last line of a submit is the state before the first line of the next; crsdr_caf_track_reset
+ * empties it, and so does crsdr_caf_set_track.  A sequence of lines gives the same trk and ntrk bytes however it is cut into submits.
+ * The carry-over makes consecutive submits depend on each other: they must be ordered -- on one stream (the engine's own, or a plan's
+ * through crsdr_caf_submit_plan), or by the caller waiting for one before the next goes to another stream.  Two submits in flight on
+ * streams that nothing orders would both read and write the table; no other stage of crsdr_caf has that dependence.
+ * Nothing depends on the order in which waves or atomics arrive, and crsdr_track launches the same kernel on the same arguments.
+ * Limits, all CRSDR_EINVAL and all checked before a device is touched, by one function for the engine and the per-op call:
+ * 1 <= max_tracks <= 128; a valid source; sigma_r, sigma_f, gate, p0_g finite and > 0; q_r, q_f, q_g finite and >= 0; coupling finite;
+ * 1 <= m <= n <= 32; tent_miss, conf_miss >= 1. */
+enum { CRSDR_TRACK_SRC_ARRAY = 0, CRSDR_TRACK_SRC_FUSED = 1 };
+
+typedef struct crsdr_caf_track_desc {
+    int32_t max_tracks;       /* T: track slots, 1..128 */
+    int32_t source;           /* CRSDR_TRACK_SRC_* */
+    double sigma_r, sigma_f;  /* measurement deviations: lag cells, Doppler bins */
+    double gate;              /* on d2 */
+    double p0_g;              /* variance of the Doppler rate of a new track */
+    double q_r, q_f, q_g;     /* process noise per line */
+    double coupling;          /* lag cells per line per Doppler bin */
+    int32_t m, n;             /* confirmation: m hits in the last n lines */
+    int32_t tent_miss;        /* consecutive misses that end a tentative track */
+    int32_t conf_miss;        /* ... a confirmed one */
+} crsdr_caf_track_desc;
+
+/* Sets the tracker (NULL: off) and empties its state.  Between submits only: it waits for the last one and allocates here, never in a
+ * submit.  CRSDR_ESTATE while the detector is off, and for the fused source unless beams with detection are on.  While the tracker is
+ * on crsdr_caf_set_cfar, crsdr_caf_set_bearing and crsdr_caf_set_beams return CRSDR_ESTATE: turn it off first.  With the tracker on a
+ * submit issues ONE launch more than without, whatever the number of blocks and whatever the counts (crsdr_caf_last_submit). */
+int crsdr_caf_set_track(crsdr_caf *caf, const crsdr_caf_track_desc *desc);
+
+/* Empties the table and starts the ids again at 1 (it waits for the last submit).  CRSDR_ESTATE with the tracker off. */
+int crsdr_caf_track_reset(crsdr_caf *caf);
+
+/* Waits for the last submit and copies out what is asked for (either pointer may be NULL), laid out as above.  CRSDR_ESTATE with the
+ * tracker off, or before the first submit since it was set. */
+int crsdr_caf_fetch_track(crsdr_caf *caf, float *trk, int32_t *ntrk);
+
+/* Device addresses of trk and ntrk ([max_batch / frames] lines each).  They change with every crsdr_caf_set_track.  CRSDR_ESTATE with
+ * the tracker off. */
+int crsdr_caf_track_device_buffers(crsdr_caf *caf, void **trk, void **ntrk);
+
+/* *bytes = the size of the per-op call's state buffer: a 16-byte header and 128 bytes per slot.  Host only; the limits above. */
+int crsdr_track_state_bytes(const crsdr_caf_track_desc *desc, size_t *bytes);
+
+/* The per-op form on nlines lines of hand-made or fetched lists: det [nlines][K][8] and count [nlines] as crsdr_cfar, the engine or
+ * crsdr_beam_fuse wrote them (only lag, Doppler, dlag, ddop, power and snr are read from a record), aux [nlines][K][2] or NULL for
+ * (-1, -1).  state is an in/out buffer of crsdr_track_state_bytes bytes; zero-filled means empty.  trk [nlines][T][16], ntrk
+ * [nlines][4]; either may be NULL, not both.  1 <= nlines <= 4096, 1 <= K <= 64, nd a power of two in 8 .. 4096, 1 <= R <= 1024; desc's
+ * source must be valid and is not used otherwise.  The engine's kernel on the same arguments, bit for bit.  mem_kind: CRSDR_MEM_HOST (copied) or CRSDR_MEM_DEVICE
+ * (every pointer on the device; det, count, aux, trk and ntrk 4-byte, state 8-byte aligned). */
+int crsdr_track(float *trk, int32_t *ntrk, void *state, const float *det, const int32_t *count, const float *aux, int nlines, int K,
+                int nd, int R, const crsdr_caf_track_desc *desc, int mem_kind);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,12 @@ beams of the 7 x 3 array set (crsdr_caf_set_beams), without the detector and wit
   +beams det as cfar b with the beams' four launches behind the detector's, + a fetch of fused and nfused as well
   get fused  the fetch of fused + nfused, against "get chi" that a user's own beamformer would need
 and the beam kernel's two bounds for the shape: the bytes it must move, and its MFMAs' cycles.
+with --track (22 rows), on two further engines whose detector has the threshold alpha = 3 and 64 detections a map, so that noise fills
+the lists -- the tracker's worst case: a 128 x 64 table of d2 every line -- one of them with the tracker set (crsdr_caf_set_track: 128
+slots, 3 of 5, gate 9, the array map's list):
+  cfar trk   as caf+cfar at that threshold: the same build's submit without the tracker
+  +track     as cfar trk with the tracker's one launch behind the detector's, + a fetch of trk and ntrk in the place of det and count
+  get trk    the fetch of trk + ntrk, against "get lists", the fetch of det + count that a host tracker would need every submit
 
 Every figure is the mean of --reps back-to-back rounds closed by one wait; --runs rounds alternate all variants in one session, medians
 and ranges are reported.  --json FILE keeps the record."""
@@ -75,6 +81,7 @@ def main():
     ap.add_argument("--cancel", metavar="K[:P]", help="add the canceller's variant")
     ap.add_argument("--bearing", action="store_true", help="add the bearings' variants (with --cfar's)")
     ap.add_argument("--beams", type=int, default=0, metavar="NB", help="add the beam maps' variants: a lattice of NB beams (22 rows)")
+    ap.add_argument("--track", action="store_true", help="add the tracker's variants (22 rows)")
     ap.add_argument("--json")
     a = ap.parse_args()
     a.cfar = a.cfar or a.bearing
@@ -167,6 +174,27 @@ def main():
                     e.fetch_beams(bmap=False, fused_only=True)
             return run
 
+        trs = {}
+        if a.track and nrows == 22:
+            for name, on in (("cfar trk", False), ("+track", True)):
+                e = b.Caf(nrows, B, SEG, lags, 0, b.WINDOW_HANN, GUARD, max_batch=T, frames=FRAMES)
+                e.set_cfar(b.cfar_desc(alpha=3.0, gd=1, gr=1, td=3, tr=4, max_det=64))
+                if on:
+                    e.set_track(b.track_desc(128, m=3, n=5, gate=9.0))
+                trs[name] = e
+
+        def caf_track(name):
+            e = trs[name]
+
+            def run(i):
+                e.submit(pk, plan.packet_stride, plan.matrix_offset, T)
+                e.fetch(chi=False, map=False)
+                if name == "+track":
+                    e.fetch_track()
+                else:
+                    e.fetch_cfar(snap=False)
+            return run
+
         cfc, basis = None, 0
         if a.cancel:
             taps, dopp = (int(v) for v in (a.cancel + ":0").split(":")[:2])
@@ -206,6 +234,11 @@ def main():
             variants["get fused"] = lambda: _mean(lambda i: bms["+beams det"][0].fetch_beams(bmap=False, fused_only=True), lambda: None, a.reps)
             if "get chi" not in variants:
                 variants["get chi"] = lambda: _mean(lambda i: cf.fetch(map=False, peak=False), lambda: None, a.reps)
+        for name in trs:
+            variants[name] = lambda name=name: _mean(caf_track(name), lambda: None, a.reps)
+        if trs:
+            variants["get trk"] = lambda: _mean(lambda i: trs["+track"].fetch_track(), lambda: None, a.reps)
+            variants["get lists"] = lambda: _mean(lambda i: trs["cfar trk"].fetch_cfar(snap=False), lambda: None, a.reps)
         if a.cancel:
             variants["caf+cancel"] = lambda: _mean(caf_cancel, lambda: None, a.reps)
         plan.submit(d_in.data_ptr(), seq=0, flags=b.REFNOISE_ENABLED, nblocks=T, block_stride=nrows * B)      # lags and phasors for the locked submits
@@ -247,6 +280,12 @@ def main():
                 note = f"  (+{med - shape['ms']['cfar b']['median']:.3f} ms behind cfar b)"
             if k == "get fused":
                 note = f"  ({(T // FRAMES) * (16 * 32 + 4) / 1e3:.1f} kB)"
+            if k == "+track":
+                note = f"  (+{med - shape['ms']['cfar trk']['median']:.3f} ms behind cfar trk: {T // FRAMES} lines in one workgroup, {(med - shape['ms']['cfar trk']['median']) / (T // FRAMES) * 1e3:.1f} us a line)"
+            if k == "get trk":
+                note = f"  ({(T // FRAMES) * (128 * 64 + 16) / 1e3:.1f} kB)"
+            if k == "get lists":
+                note = f"  ({(T // FRAMES) * (nrows + 1) * (64 * 32 + 4) / 1e3:.1f} kB)"
             if k == "get chi":
                 note = f"  ({8 * cells / 1e6:.1f} MB)"
             if k == "get cfar":
@@ -280,6 +319,8 @@ def main():
         for e in brg.values():
             e.close()
         for e, _, _ in bms.values():
+            e.close()
+        for e in trs.values():
             e.close()
         sp.close()
         host.close()
