@@ -4,16 +4,23 @@
 //     map and the peak figures (caf.hpp, caf_peak.hpp).  Every buffer, the twiddle and window tables included, is made at create; a
 //     submit is three launches on one stream whatever the batch size (rows, map, peaks), no lock, no allocation, no synchronisation.
 //     With a detector set (crsdr_caf_set_cfar; caf_cfar.hpp, caf_cfar_kernels.hpp) two more: the tiles' candidates, and their merge into
-//     the detection lists and the array map's snapshots.  Its buffers are made by set_cfar, between submits.
+//     the detection lists and the array map's snapshots.
 //     With a canceller set (crsdr_caf_set_cancel; caf_cancel.hpp, caf_cancel_solve.hpp) five launches take the place of the rows' one:
 //     the reference's sums, the rows' first lags, the normal equations' sums, factor and solves, and the rows with the subtraction.
 //     With bearings set (crsdr_caf_set_bearing; caf_bearing.hpp, caf_bearing_solve.hpp) three more behind the detector's: the slots'
-//     records, the scan's tiles, and the merge with the zoom search.  Its buffers are made by set_bearing, between submits.
-//     With beams set (crsdr_caf_set_beams; caf_beams.hpp, caf_beams_kernels.hpp) one more at the end: every beam's map across the rows on
-//     the fp32 matrix pipe; with the detector on three more behind it: the detector's two on the beam maps, (line, beam) taking the
-//     place of the line, and the fusion of the beams' lists into one per line.  Its buffers are made by set_beams, between submits.
+//     records, the scan's tiles, and the merge with the zoom search.
+//     With beams set (crsdr_caf_set_beams; caf_beams.hpp, caf_beams_kernels.hpp) one more: every beam's map across the rows on the fp32
+//     matrix pipe; with the detector on three more behind it: the detector's two on the beam maps, (line, beam) taking the place of
+//     the line, and the fusion of the beams' lists into one per line.
 //     With the tracker set (crsdr_caf_set_track; caf_track.hpp, caf_track_kernels.hpp) one more behind everything else: one workgroup
-//     that walks the lines of the submit and carries the tracks from submit to submit.  Its buffers are made by set_track.
+//     that walks the lines of the submit and carries the tracks from submit to submit.
+//
+// Shape of the host code (doa_engine.hpp's).  A feature is a sub-struct of crsdr_caf: its parameters and its DevBufs.  Every launch
+// goes through caf_run, which checks and counts it.  A submit is caf_launch's flat list of stages (maps, detector, bearings, beams,
+// the beams' lists, tracker), each of which returns at once with its feature off; what it left (CafLast) is written once at its end.
+// A setter asks caf_rules, empties its feature behind caf_quiesce (caf_clear), builds the new one in a local, between submits, and
+// moves it in when every allocation has succeeded.  A fetch reads its state from CafLast and copies through DevFetch.  The per-op
+// calls share the *_enqueue functions with the stages (the same kernels on the same arguments, so the same bits) and caf_shape_ok.
 #pragma once
 
 #include "caf.hpp"
@@ -38,9 +45,7 @@
     default: { constexpr int LG = 12; launch; } break;                              \
     }
 
-constexpr int kCafLaunches = 3, kCafCfarLaunches = 2, kCafCancelLaunches = 4, kCafBearingLaunches = 3;      // (the canceller's five take the place of one)
-constexpr int kCafBeamLaunches = 1, kCafBeamDetLaunches = 3;                                                // (the maps; the detector's two on them and the fusion)
-constexpr int kCafTrackLaunches = 1, kTrackMaxLines = 4096;
+constexpr int kTrackMaxLines = 4096;
 constexpr long long kCafMaxCells = 1ll << 24;           // (max_batch / frames) * nrows * nd * nlags
 
 // the canceller's device memory for `lines` lines: the engine's own buffers, or parts of one per-op slot
@@ -53,6 +58,15 @@ struct CancelBufs {
     float *coef = nullptr, *cinfo = nullptr;
 };
 
+// what the last submit left: where, how much, and which features ran (kCafRan*).  A setter clears its feature's bit: "nothing submitted
+// since"; without kCafRanBase nothing is left at all
+constexpr unsigned kCafRanBase = 1u, kCafRanCancel = 2u, kCafRanCfar = 4u, kCafRanBearing = 8u, kCafRanBeams = 16u, kCafRanTrack = 32u;
+struct CafLast {
+    hipStream_t stream = nullptr;
+    int nest = 0, launches = 0;
+    unsigned ran = 0;
+};
+
 struct crsdr_caf {
     DoaStream own;
     int nrows = 0, B = 0, device = 0, max_batch = 1, frames = 1, seg = 0, nlags = 0, ref_row = 0, window = 0, guard = 0, nd = 0;
@@ -60,7 +74,7 @@ struct crsdr_caf {
     DevBuf<float> win, map, peak;
     // crsdr_caf_set_cfar: on (false = off), the tiles' candidates [lines][nrows + 1][tiles][keep] and counts, and the results
     struct Cfar {
-        bool on = false, submitted = false;
+        bool on = false;
         cfar::Params prm{};
         int keep = 0;
         DevBuf<cfar::Cand> slots;
@@ -69,7 +83,7 @@ struct crsdr_caf {
     } cf;
     // crsdr_caf_set_cancel: on (false = off) and what CancelBufs names
     struct Cancel {
-        bool on = false, submitted = false;
+        bool on = false;
         int taps = 0, dopp = 0;
         DevBuf<int2> G, Y;
         DevBuf<double2> ph, S, C, W, h;
@@ -80,7 +94,7 @@ struct crsdr_caf {
     } cn;
     // crsdr_caf_set_bearing: on (false = off), the slots' records [lines][K][brg::REC], the tiles' maxima and the results
     struct Bearing {
-        bool on = false, submitted = false;
+        bool on = false;
         brg::Params prm{};
         DevBuf<double> rec;
         DevBuf<bearing::Best> tbest;
@@ -89,7 +103,7 @@ struct crsdr_caf {
     // crsdr_caf_set_beams: on (false = off), det: the detector was on when they were set; the weights [nb][m][2], the maps and, with
     // det, the detector's scratch for (line, beam) maps and the lists
     struct Beams {
-        bool on = false, det = false, submitted = false;
+        bool on = false, det = false;
         int nb = 0;
         DevBuf<float> w, bmap, bdet, fused;
         DevBuf<int32_t> bcount, nfused, tcount;
@@ -97,16 +111,31 @@ struct crsdr_caf {
     } bb;
     // crsdr_caf_set_track: on (false = off), the state that a submit hands to the next, and the results
     struct Track {
-        bool on = false, submitted = false;
+        bool on = false;
         trk::Params prm{};
         DevBuf<unsigned char> state;
         DevBuf<float> trk;
         DevBuf<int32_t> ntrk;
     } tk;
-    hipStream_t last_stream = nullptr;
-    int last_nest = 0, last_launches = 0;
-    bool submitted = false;
+    CafLast last;
+    size_t lines() const { return (size_t)(max_batch / frames); }      // the most a submit leaves: what every setter sizes its buffers by
 };
+
+// a submit's stream, lines and launches so far; a per-op call's stream, and a count that nobody reads
+struct CafRun {
+    hipStream_t S;
+    int nest = 0, launches = 0;
+};
+
+// every launch: the kernel, its error, the count
+template <typename Kernel, typename... Args>
+static int caf_run(CafRun &r, Kernel kern, dim3 grid, dim3 block, size_t lds, const Args &...args)
+{
+    hipLaunchKernelGGL(kern, grid, block, lds, r.S, args...);
+    HIP_TRY(hipGetLastError());
+    ++r.launches;
+    return CRSDR_OK;
+}
 
 // every limit of section (w), for crsdr_caf_create and crsdr_ambiguity (max_batch = frames = 1)
 static int caf_args_ok(const char *who, int nrows, int blocksize, int max_batch, int frames, int seg, int nlags, int ref_row, int window, int guard)
@@ -131,6 +160,20 @@ static int caf_args_ok(const char *who, int nrows, int blocksize, int max_batch,
     return CRSDR_OK;
 }
 
+// What the per-op calls ask of a line's shape, in the order they have always asked it: nd (a power of two; any size with pow2 off, for
+// crsdr_beam_maps), R, nrows, ref_row, guard.  A call without rows or without a guard passes nrows 2, ref_row 0, guard 0: they hold.
+static int caf_shape_ok(const char *who, int nd, int R, int guard, int ref_row, int nrows, bool pow2 = true)
+{
+    const bool in_range = nd >= 1 && nd <= (1 << caf::CAF_MAX_LOG2);
+    if (pow2 && (!in_range || ilog2_exact(nd) < caf::CAF_MIN_LOG2)) return fail(CRSDR_EINVAL, "%s: nd = %d (a power of two in [8, 4096])", who, nd);
+    if (!in_range) return fail(CRSDR_EINVAL, "%s: nd = %d (1..4096)", who, nd);
+    if (R < 1 || R > caf::CAF_MAX_LAGS) return fail(CRSDR_EINVAL, "%s: R = %d (1..%d)", who, R, caf::CAF_MAX_LAGS);
+    if (nrows < 2 || (long long)nrows * nd * R > kCafMaxCells) return fail(CRSDR_EINVAL, "%s: nrows = %d (at least 2, nrows * nd * R at most 2^24)", who, nrows);
+    if (ref_row < 0 || ref_row >= nrows) return fail(CRSDR_EINVAL, "%s: ref_row = %d (0..%d)", who, ref_row, nrows - 1);
+    if (guard < 0 || guard > nd / 2) return fail(CRSDR_EINVAL, "%s: guard = %d (0..nd / 2 = %d)", who, guard, nd / 2);
+    return CRSDR_OK;
+}
+
 // every limit of the canceller of section (w), for crsdr_caf_set_cancel and crsdr_ambiguity_cancel
 static int cancel_args_ok(const char *who, int nd, int nlags, long long lines, const crsdr_caf_cancel_desc *d)
 {
@@ -145,63 +188,55 @@ static int cancel_args_ok(const char *who, int nd, int nlags, long long lines, c
 }
 
 // the phase table of the canceller, exp(2 pi i j / nd): at set_cancel, and per call for crsdr_ambiguity_cancel
-static int cancel_table(hipStream_t S, int nd, double2 *ph)
+static int cancel_table(CafRun &r, int nd, double2 *ph)
 {
-    hipLaunchKernelGGL(cancel::k_cancel_phase, dim3((unsigned)((nd + cancel::THREADS - 1) / cancel::THREADS)), dim3(cancel::THREADS), 0, S, nd, ph);
-    HIP_TRY(hipGetLastError());
-    return CRSDR_OK;
+    return caf_run(r, cancel::k_cancel_phase, dim3((unsigned)((nd + cancel::THREADS - 1) / cancel::THREADS)), dim3(cancel::THREADS), 0, nd, ph);
 }
 
 // the rows with the canceller: five launches in the place of k_caf's one
-static int cancel_enqueue(hipStream_t S, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nest, int nrows, int B, int frames, int lg, int lgseg,
+static int cancel_enqueue(CafRun &r, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nest, int nrows, int B, int frames, int lg, int lgseg,
                           int nlags, int ref_row, const float2 *tw, const float *win, float scale, float2 *chi, const CancelBufs &c)
 {
     const int nd = 1 << lg, K = c.taps, P = c.dopp, n = cc::basis(K, P), entries = (4 * P + 1) * K * K + nrows * n;
-    hipLaunchKernelGGL(cancel::k_cancel_g, dim3((unsigned)((nd * (nlags + K - 1) + cancel::THREADS - 1) / cancel::THREADS), (unsigned)nest), dim3(cancel::THREADS), 0, S,
-                       packets, packet_stride, matrix_offset, B, frames, lgseg, nd, nlags, K, ref_row, c.G);
-    HIP_TRY(hipGetLastError());
+    int rc = caf_run(r, cancel::k_cancel_g, dim3((unsigned)((nd * (nlags + K - 1) + cancel::THREADS - 1) / cancel::THREADS), (unsigned)nest), dim3(cancel::THREADS), 0,
+                     packets, packet_stride, matrix_offset, B, frames, lgseg, nd, nlags, K, ref_row, c.G);
+    if (rc) return rc;
     caf::CancelArgs a1, a2;
     a1.Y = c.Y; a1.E = c.E;
     a2.taps = K; a2.dopp = P; a2.nlags = nlags; a2.G = c.G; a2.h = c.h; a2.ph = c.ph; a2.status = c.status;
-    CAF_DISPATCH(lg, hipLaunchKernelGGL((caf::k_caf<LG, 1>), dim3((unsigned)(nrows * caf::caf_tiles(lg, K)), (unsigned)nest), dim3(caf::CAF_THREADS), 0, S, packets,
-                                        packet_stride, matrix_offset, nrows, B, frames, lgseg, K, ref_row, tw, win, scale, chi, a1));
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(cancel::k_cancel_sums, dim3((unsigned)((entries + cancel::SUM_ENTRIES - 1) / cancel::SUM_ENTRIES), (unsigned)nest), dim3(cancel::THREADS), 0, S,
-                       (const int2 *)c.G, (const int2 *)c.Y, (const double2 *)c.ph, nrows, nd, nlags, K, P, ref_row, c.S, c.C);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(cancel::k_cancel_solve, dim3((unsigned)nest, (unsigned)((nrows + cancel::SOLVE_ROWS - 1) / cancel::SOLVE_ROWS)), dim3(cancel::THREADS), 0, S, (const double2 *)c.S, (const double2 *)c.C, (const long long *)c.E, nrows,
-                       K, P, ref_row, c.W, c.h, c.status, c.coef, c.cinfo);
-    HIP_TRY(hipGetLastError());
-    CAF_DISPATCH(lg, hipLaunchKernelGGL((caf::k_caf<LG, 2>), dim3((unsigned)(nrows * caf::caf_tiles(lg, nlags)), (unsigned)nest), dim3(caf::CAF_THREADS), 0, S,
-                                        packets, packet_stride, matrix_offset, nrows, B, frames, lgseg, nlags, ref_row, tw, win, scale, chi, a2));
-    HIP_TRY(hipGetLastError());
-    return CRSDR_OK;
+    CAF_DISPATCH(lg, rc = caf_run(r, (caf::k_caf<LG, 1, caf::CancelArgs>), dim3((unsigned)(nrows * caf::caf_tiles(lg, K)), (unsigned)nest), dim3(caf::CAF_THREADS), 0, packets,
+                                  packet_stride, matrix_offset, nrows, B, frames, lgseg, K, ref_row, tw, win, scale, chi, a1));
+    if (rc || (rc = caf_run(r, cancel::k_cancel_sums, dim3((unsigned)((entries + cancel::SUM_ENTRIES - 1) / cancel::SUM_ENTRIES), (unsigned)nest), dim3(cancel::THREADS), 0,
+                            (const int2 *)c.G, (const int2 *)c.Y, (const double2 *)c.ph, nrows, nd, nlags, K, P, ref_row, c.S, c.C)) ||
+        (rc = caf_run(r, cancel::k_cancel_solve, dim3((unsigned)nest, (unsigned)((nrows + cancel::SOLVE_ROWS - 1) / cancel::SOLVE_ROWS)), dim3(cancel::THREADS), 0,
+                      (const double2 *)c.S, (const double2 *)c.C, (const long long *)c.E, nrows, K, P, ref_row, c.W, c.h, c.status, c.coef, c.cinfo)))
+        return rc;
+    CAF_DISPATCH(lg, rc = caf_run(r, (caf::k_caf<LG, 2, caf::CancelArgs>), dim3((unsigned)(nrows * caf::caf_tiles(lg, nlags)), (unsigned)nest), dim3(caf::CAF_THREADS), 0,
+                                  packets, packet_stride, matrix_offset, nrows, B, frames, lgseg, nlags, ref_row, tw, win, scale, chi, a2));
+    return rc;
 }
 
 // the three launches, for the object and for crsdr_ambiguity: the same kernels on the same arguments, so the same bits.  cn: the
 // canceller's buffers, or NULL with it off.
-static int caf_enqueue(hipStream_t S, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nblocks, int nrows, int B, int frames, int seg, int nlags,
+static int caf_enqueue(CafRun &r, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nblocks, int nrows, int B, int frames, int seg, int nlags,
                        int ref_row, int window, int guard, const float2 *tw, const float *win, float2 *chi, float *map, float *peak, const CancelBufs *cn = nullptr)
 {
     const int nest = nblocks / frames, nd = frames * (B / (2 * seg)), lg = ilog2_exact(nd), lgseg = ilog2_exact(seg), cells = nd * nlags;
     // sum w: nd (rect), nd / 2 (periodic Hann)
     const float scale = (float)(1.0 / (127.0 * 127.0 * (double)seg * (window == CRSDR_WINDOW_HANN ? 0.5 * (double)nd : (double)nd)));
     const dim3 grow((unsigned)(nrows * caf::caf_tiles(lg, nlags)), (unsigned)nest);
+    int rc = CRSDR_OK;
     if (cn) {
-        const int rc = cancel_enqueue(S, packets, packet_stride, matrix_offset, nest, nrows, B, frames, lg, lgseg, nlags, ref_row, tw, win, scale, chi, *cn);
-        if (rc) return rc;
+        rc = cancel_enqueue(r, packets, packet_stride, matrix_offset, nest, nrows, B, frames, lg, lgseg, nlags, ref_row, tw, win, scale, chi, *cn);
     } else {
-        CAF_DISPATCH(lg, hipLaunchKernelGGL((caf::k_caf<LG>), grow, dim3(caf::CAF_THREADS), 0, S, packets, packet_stride, matrix_offset, nrows, B, frames, lgseg, nlags,
-                                            ref_row, tw, win, scale, chi));
-        HIP_TRY(hipGetLastError());
+        CAF_DISPATCH(lg, rc = caf_run(r, (caf::k_caf<LG, 0>), grow, dim3(caf::CAF_THREADS), 0, packets, packet_stride, matrix_offset, nrows, B, frames, lgseg, nlags, ref_row,
+                                      tw, win, scale, chi));
     }
-    hipLaunchKernelGGL(caf::k_caf_map, dim3((unsigned)((cells + caf::CAF_MAP_CELLS - 1) / caf::CAF_MAP_CELLS), (unsigned)nest), dim3(caf::CAF_THREADS), 0, S,
-                       (const float2 *)chi, nrows, cells, ref_row, map);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(caf::k_caf_peak, dim3((unsigned)(nrows + 1), (unsigned)nest), dim3(caf::CAF_THREADS), 0, S, (const float2 *)chi, (const float *)map, nrows, nd, nlags,
-                       guard, peak);
-    HIP_TRY(hipGetLastError());
-    return CRSDR_OK;
+    if (rc || (rc = caf_run(r, caf::k_caf_map, dim3((unsigned)((cells + caf::CAF_MAP_CELLS - 1) / caf::CAF_MAP_CELLS), (unsigned)nest), dim3(caf::CAF_THREADS), 0,
+                            (const float2 *)chi, nrows, cells, ref_row, map)))
+        return rc;
+    return caf_run(r, caf::k_caf_peak, dim3((unsigned)(nrows + 1), (unsigned)nest), dim3(caf::CAF_THREADS), 0, (const float2 *)chi, (const float *)map, nrows, nd, nlags, guard,
+                   peak);
 }
 
 // every limit of the detector of section (w), for crsdr_caf_set_cfar and crsdr_cfar
@@ -222,17 +257,15 @@ static int cfar_args_ok(const char *who, int nd, const crsdr_cfar_desc *d, cfar:
 }
 
 // the detector's two launches, for the object and for crsdr_cfar: the same kernels on the same arguments, so the same bits
-static int cfar_enqueue(hipStream_t S, const float2 *chi, const float *map, int nest, int nrows, int entries, int nd, int R, int guard, const cfar::Params &prm, int keep,
+static int cfar_enqueue(CafRun &r, const float2 *chi, const float *map, int nest, int nrows, int entries, int nd, int R, int guard, const cfar::Params &prm, int keep,
                         cfar::Cand *slots, int32_t *tcount, float *det, int32_t *count, float *snap)
 {
     const int tiles = cfar::tiles_of(nd, R);
-    hipLaunchKernelGGL(cfar::k_caf_cfar, dim3((unsigned)(entries * tiles), (unsigned)nest), dim3(cfar::THREADS), 0, S, chi, map, nrows, entries, nd, R, guard, prm, keep, slots,
-                       tcount);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(cfar::k_caf_cfar_merge, dim3((unsigned)entries, (unsigned)nest), dim3(cfar::THREADS), 0, S, chi, map, nrows, entries, nd, R, guard, prm, keep,
-                       (const cfar::Cand *)slots, (const int32_t *)tcount, det, count, snap);
-    HIP_TRY(hipGetLastError());
-    return CRSDR_OK;
+    const int rc = caf_run(r, cfar::k_caf_cfar, dim3((unsigned)(entries * tiles), (unsigned)nest), dim3(cfar::THREADS), 0, chi, map, nrows, entries, nd, R, guard, prm, keep,
+                           slots, tcount);
+    if (rc) return rc;
+    return caf_run(r, cfar::k_caf_cfar_merge, dim3((unsigned)entries, (unsigned)nest), dim3(cfar::THREADS), 0, chi, map, nrows, entries, nd, R, guard, prm, keep,
+                   (const cfar::Cand *)slots, (const int32_t *)tcount, det, count, snap);
 }
 
 // every limit of the bearings of section (w), for crsdr_caf_set_bearing and crsdr_bearing
@@ -253,28 +286,17 @@ static int bearing_args_ok(const char *who, int nrows, long long lines, int K, c
     }
 }
 
-// k_bearing_slot's LDS at its largest: above the 64 KiB default.  One value for every caller, so that no call lowers another's.
-static int bearing_lds_limit()
-{
-    HIP_TRY(hipFuncSetAttribute((const void *)bearing::k_bearing_slot, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bearing::slot_lds_bytes(brg::MAX_M, cfar::MAX_HR)));
-    return CRSDR_OK;
-}
-
 // the bearings' three launches, for the object and for crsdr_bearing: the same kernels on the same arguments, so the same bits.
 // det, count: the array map's entry of the first line.
-static int bearing_enqueue(hipStream_t S, const float2 *chi, const float *det, size_t det_stride, const int32_t *count, size_t count_stride, int nest, int nrows, int nd,
+static int bearing_enqueue(CafRun &r, const float2 *chi, const float *det, size_t det_stride, const int32_t *count, size_t count_stride, int nest, int nrows, int nd,
                            int R, int ref_row, int guard, const cfar::Params &cp, const brg::Params &bp, double *rec, bearing::Best *tbest, float *dir, float *spec)
 {
     const int K = cp.max_det, tiles = bearing::tiles_of(bp.ncx, bp.ncy);
-    hipLaunchKernelGGL(bearing::k_bearing_slot, dim3((unsigned)K, (unsigned)nest), dim3(bearing::THREADS), bearing::slot_lds_bytes(bp.mx * bp.my, cp.gr + cp.tr), S, chi, det,
-                       det_stride, count, count_stride, nrows, nd, R, ref_row, guard, cp, bp, K, rec);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(bearing::k_bearing_scan, dim3((unsigned)tiles, (unsigned)K, (unsigned)nest), dim3(bearing::THREADS), 0, S, (const double *)rec, bp, K, spec, tbest);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(bearing::k_bearing_finish, dim3((unsigned)K, (unsigned)nest), dim3(bearing::FIN_THREADS), 0, S, (const double *)rec, (const bearing::Best *)tbest, tiles,
-                       bp, K, dir);
-    HIP_TRY(hipGetLastError());
-    return CRSDR_OK;
+    int rc = caf_run(r, bearing::k_bearing_slot, dim3((unsigned)K, (unsigned)nest), dim3(bearing::THREADS), bearing::slot_lds_bytes(bp.mx * bp.my, cp.gr + cp.tr), chi, det,
+                     det_stride, count, count_stride, nrows, nd, R, ref_row, guard, cp, bp, K, rec);
+    if (rc || (rc = caf_run(r, bearing::k_bearing_scan, dim3((unsigned)tiles, (unsigned)K, (unsigned)nest), dim3(bearing::THREADS), 0, (const double *)rec, bp, K, spec, tbest))) return rc;
+    return caf_run(r, bearing::k_bearing_finish, dim3((unsigned)K, (unsigned)nest), dim3(bearing::FIN_THREADS), 0, (const double *)rec, (const bearing::Best *)tbest, tiles, bp,
+                   K, dir);
 }
 
 // every limit of the beams of section (w), for crsdr_caf_set_beams and crsdr_beam_maps.  weights: on the host
@@ -292,22 +314,17 @@ static int beams_args_ok(const char *who, int nrows, long long lines, int nd, in
 }
 
 // the beam maps' one launch, for the object and for crsdr_beam_maps: the same kernel on the same arguments, so the same bits
-static int beam_maps_enqueue(hipStream_t S, const float2 *chi, const float *w, int nest, int nrows, int cells, int ref_row, int nb, float *bmap)
+static int beam_maps_enqueue(CafRun &r, const float2 *chi, const float *w, int nest, int nrows, int cells, int ref_row, int nb, float *bmap)
 {
     const dim3 grid((unsigned)((cells + caf_beams::WG_CELLS - 1) / caf_beams::WG_CELLS), (unsigned)nest);
-    const size_t lds = caf_beams::table_bytes(nrows - 1, nb);
-    if (caf_beams::groups_of(nb) == 1) hipLaunchKernelGGL((caf_beams::k_caf_beams<1>), grid, dim3(caf_beams::THREADS), lds, S, chi, w, nrows, cells, ref_row, nb, bmap);
-    else hipLaunchKernelGGL((caf_beams::k_caf_beams<2>), grid, dim3(caf_beams::THREADS), lds, S, chi, w, nrows, cells, ref_row, nb, bmap);
-    HIP_TRY(hipGetLastError());
-    return CRSDR_OK;
+    return caf_run(r, caf_beams::groups_of(nb) == 1 ? caf_beams::k_caf_beams<1> : caf_beams::k_caf_beams<2>, grid, dim3(caf_beams::THREADS),
+                   caf_beams::table_bytes(nrows - 1, nb), chi, w, nrows, cells, ref_row, nb, bmap);
 }
 
 // the fusion's one launch, for the object and for crsdr_beam_fuse
-static int beam_fuse_enqueue(hipStream_t S, const float *bdet, const int32_t *bcount, int nest, int nb, int K, int nd, int R, float *fused, int32_t *nfused)
+static int beam_fuse_enqueue(CafRun &r, const float *bdet, const int32_t *bcount, int nest, int nb, int K, int nd, int R, float *fused, int32_t *nfused)
 {
-    hipLaunchKernelGGL(caf_beams::k_caf_beam_fuse, dim3((unsigned)nest), dim3(caf_beams::THREADS), 0, S, bdet, bcount, nb, K, nd, R, fused, nfused);
-    HIP_TRY(hipGetLastError());
-    return CRSDR_OK;
+    return caf_run(r, caf_beams::k_caf_beam_fuse, dim3((unsigned)nest), dim3(caf_beams::THREADS), 0, bdet, bcount, nb, K, nd, R, fused, nfused);
 }
 
 // every limit of the tracker of section (w), for crsdr_caf_set_track, crsdr_track and crsdr_track_state_bytes
@@ -328,38 +345,71 @@ static int track_args_ok(const char *who, const crsdr_caf_track_desc *d, trk::Pa
     }
 }
 
-// k_caf_track's LDS at its largest: above the 64 KiB default.  One value for every caller, so that no call lowers another's; set once
-// per device (the attribute is the device's copy of the kernel's: a call on another device sets that one's)
-static int track_lds_limit()
+// the tracker's one launch, for the object and for crsdr_track: the same kernel on the same arguments, so the same bits
+static int track_enqueue(CafRun &r, const float *det, size_t det_stride, const int32_t *count, size_t count_stride, const float *aux, int aux_mode, int nlines, int K,
+                         int nd, int R, const trk::Params &prm, unsigned char *state, float *out, int32_t *nout)
 {
-    static std::mutex mu;
-    static std::vector<int> done;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(mu);
-    for (int d : done)
-        if (d == dev) return CRSDR_OK;
+    return caf_run(r, caf_track::k_caf_track, dim3(1), dim3(caf_track::THREADS), caf_track::lds_bytes(prm.max_tracks, K), det, det_stride, count, count_stride, aux, aux_mode,
+                   nlines, K, nd, R, prm, state, out, nout);
+}
+
+// The two dynamic LDS limits above the 64 KiB default, k_bearing_slot's and k_caf_track's, are function attributes of the current
+// device, shared by every live object: each create sets both to the most any object can ask for, so that no call lowers a limit under
+// another and no setter has to think of them.  crsdr_bearing and crsdr_track do the same for their calls.
+static int caf_lds_limits()
+{
+    HIP_TRY(hipFuncSetAttribute((const void *)bearing::k_bearing_slot, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bearing::slot_lds_bytes(brg::MAX_M, cfar::MAX_HR)));
     HIP_TRY(hipFuncSetAttribute((const void *)caf_track::k_caf_track, hipFuncAttributeMaxDynamicSharedMemorySize, (int)caf_track::lds_bytes(trk::MAX_TRACKS, trk::MAX_MEAS)));
-    done.push_back(dev);
     return CRSDR_OK;
 }
 
-// the tracker's one launch, for the object and for crsdr_track: the same kernel on the same arguments, so the same bits
-static int track_enqueue(hipStream_t S, const float *det, size_t det_stride, const int32_t *count, size_t count_stride, const float *aux, int aux_mode, int nlines, int K,
-                         int nd, int R, const trk::Params &prm, unsigned char *state, float *out, int32_t *nout)
+// ---- the object: create, destroy, and what the setters share ----
+// the object's device, and no kernel of the last submit still on the buffers: what every setter, track_reset and destroy do first
+static int caf_quiesce(crsdr_caf *q)
 {
-    hipLaunchKernelGGL(caf_track::k_caf_track, dim3(1), dim3(caf_track::THREADS), caf_track::lds_bytes(prm.max_tracks, K), S, det, det_stride, count, count_stride, aux,
-                       aux_mode, nlines, K, nd, R, prm, state, out, nout);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipSetDevice(q->device));
+    if (q->last.ran & kCafRanBase) HIP_TRY(hipDeviceSynchronize());      // (the last submit's stream may be the caller's, and gone)
     return CRSDR_OK;
 }
 
 static void caf_free(crsdr_caf *q)
 {
     if (!q) return;
-    (void)hipSetDevice(q->device);
-    if (q->submitted) (void)hipDeviceSynchronize();      // (the last submit's stream may be the caller's, and gone)
+    (void)caf_quiesce(q);
     delete q;                                            // the buffers, then the stream
+}
+
+// a setter's first half, behind its checks: the last submit may still write the buffers let go here; then the feature is off, and
+// nothing has been submitted since it was set.  The second half builds the new feature in a local and moves it in whole.
+template <typename Feature>
+static int caf_clear(crsdr_caf *q, Feature &f, unsigned ran_bit)
+{
+    const int rc = caf_quiesce(q);
+    if (!rc) { f = Feature(); q->last.ran &= ~ran_bit; }
+    return rc;
+}
+
+// Who must be off before whom, who must be on before whom: every rule of the setters, each feature's in the order they are asked.
+// must_be_on false: `feature` is not changed, set or turned off, while `other` is on, which works on its buffers and parameters (asked
+// ahead of the descriptor's limits).  true: `feature` is not set while `other` is off (asked behind them, and not to turn it off).
+enum { kCafCfar, kCafBearing, kCafBeams, kCafBeamLists, kCafTrack, kCafTrackFused };
+static const struct CafRule { int feature; bool must_be_on; int other; const char *refusal; } kCafRules[] = {
+    {kCafCfar, false, kCafTrack, "caf_set_cfar: the tracker is on (crsdr_caf_set_track): its measurements are this detector's lists; turn it off first"},
+    {kCafCfar, false, kCafBeams, "caf_set_cfar: beams are on (crsdr_caf_set_beams): whether they are detected on, and the lists' sizes, are this detector's; turn them off first"},
+    {kCafCfar, false, kCafBearing, "caf_set_cfar: bearings are on (crsdr_caf_set_bearing): their buffers and training set are this detector's; turn them off first"},
+    {kCafBearing, false, kCafTrack, "caf_set_bearing: the tracker is on (crsdr_caf_set_track): its auxiliary pairs are these bearings; turn it off first"},
+    {kCafBearing, true, kCafCfar, "caf_set_bearing: no detector set (crsdr_caf_set_cfar): there are no detections to take a bearing of"},
+    {kCafBeams, false, kCafTrack, "caf_set_beams: the tracker is on (crsdr_caf_set_track): the fused list may be its source; turn it off first"},
+    {kCafTrack, true, kCafCfar, "caf_set_track: no detector set (crsdr_caf_set_cfar): there are no detections to track"},
+    {kCafTrackFused, true, kCafBeamLists, "caf_set_track: the fused source needs beams with detection (crsdr_caf_set_beams behind crsdr_caf_set_cfar)"},
+};
+
+static int caf_rules(const crsdr_caf *q, int feature, bool must_be_on)
+{
+    const bool on[] = {q->cf.on, q->bg.on, q->bb.on, q->bb.on && q->bb.det, q->tk.on};
+    for (const CafRule &u : kCafRules)
+        if (u.feature == feature && u.must_be_on == must_be_on && on[u.other] != must_be_on) return fail(CRSDR_ESTATE, "%s", u.refusal);
+    return CRSDR_OK;
 }
 
 extern "C" int crsdr_caf_create(crsdr_caf **caf, const crsdr_caf_desc *desc)
@@ -377,13 +427,13 @@ extern "C" int crsdr_caf_create(crsdr_caf **caf, const crsdr_caf_desc *desc)
     if (!q) return fail(CRSDR_ENOMEM, "caf_create: out of host memory");
     q->nrows = desc->nrows; q->B = desc->blocksize; q->device = desc->device; q->max_batch = mb; q->frames = F; q->seg = desc->seg; q->nlags = desc->nlags;
     q->ref_row = desc->ref_row; q->window = desc->window; q->guard = desc->guard; q->nd = F * (q->B / (2 * q->seg));
-    const size_t lines = (size_t)(mb / F), cells = (size_t)q->nd * (size_t)q->nlags;
+    const size_t lines = q->lines(), cells = (size_t)q->nd * (size_t)q->nlags;
     int rc = [&]() -> int {
         HIP_TRY(hipSetDevice(q->device));
         HIP_TRY(hipStreamCreateWithFlags(&q->own.s, hipStreamNonBlocking));
         int r = CRSDR_OK;
         if ((r = q->tw.alloc((size_t)q->nd)) || (r = q->win.alloc((size_t)q->nd)) || (r = q->chi.alloc(lines * (size_t)q->nrows * cells)) || (r = q->map.alloc(lines * cells)) ||
-            (r = q->peak.alloc(lines * (size_t)(q->nrows + 1) * 6)))
+            (r = q->peak.alloc(lines * (size_t)(q->nrows + 1) * 6)) || (r = caf_lds_limits()))
             return r;
         if ((r = spectra_tables(q->own.s, q->nd, q->window, q->tw, q->win))) return r;
         HIP_TRY(hipStreamSynchronize(q->own.s));         // a submit may come on any stream
@@ -401,59 +451,76 @@ extern "C" int crsdr_caf_destroy(crsdr_caf *caf)
     return CRSDR_OK;
 }
 
-// the beams behind everything else of a submit (nothing with them off): the maps, and with the detector the lists and their fusion
-static int beams_launch(crsdr_caf *q, hipStream_t S)
+// ---- a submit: the stages in stream order, each of which returns at once with its feature off ----
+// the rows (plain, or the canceller's five), the map, the peaks
+static int caf_stage_maps(crsdr_caf *q, CafRun &r, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nblocks)
+{
+    const CancelBufs cb = q->cn.bufs();
+    return caf_enqueue(r, packets, packet_stride, matrix_offset, nblocks, q->nrows, q->B, q->frames, q->seg, q->nlags, q->ref_row, q->window, q->guard, q->tw, q->win, q->chi,
+                       q->map, q->peak, q->cn.on ? &cb : nullptr);
+}
+
+static int caf_stage_cfar(crsdr_caf *q, CafRun &r)
+{
+    crsdr_caf::Cfar &c = q->cf;
+    if (!c.on) return CRSDR_OK;
+    return cfar_enqueue(r, q->chi, q->map, r.nest, q->nrows, q->nrows + 1, q->nd, q->nlags, q->guard, c.prm, c.keep, c.slots, c.tcount, c.det, c.count, c.snap);
+}
+
+// (the bearings and the tracker read the array map's lists: entry nrows of the nrows + 1 of a line)
+static int caf_stage_bearing(crsdr_caf *q, CafRun &r)
+{
+    crsdr_caf::Bearing &g = q->bg;
+    if (!g.on) return CRSDR_OK;
+    const size_t K = (size_t)q->cf.prm.max_det, entries = (size_t)(q->nrows + 1);
+    return bearing_enqueue(r, q->chi, q->cf.det.p + (size_t)q->nrows * K * 8, entries * K * 8, q->cf.count.p + q->nrows, entries, r.nest, q->nrows, q->nd, q->nlags, q->ref_row,
+                           q->guard, q->cf.prm, g.prm, g.rec, g.tbest, g.dir, g.spec);
+}
+
+static int caf_stage_beams(crsdr_caf *q, CafRun &r)
 {
     crsdr_caf::Beams &g = q->bb;
     if (!g.on) return CRSDR_OK;
-    const int nest = q->last_nest, cells = q->nd * q->nlags;
-    { const int rc = beam_maps_enqueue(S, q->chi, g.w, nest, q->nrows, cells, q->ref_row, g.nb, g.bmap); if (rc) return rc; }
-    g.submitted = true; q->last_launches += kCafBeamLaunches;
-    if (!g.det) return CRSDR_OK;
-    // (line, beam) is the line of a one-map call, as crsdr_cfar has it with comps = 1
-    { const int rc = cfar_enqueue(S, nullptr, g.bmap, nest * g.nb, 0, 1, q->nd, q->nlags, q->guard, q->cf.prm, q->cf.keep, g.slots, g.tcount, g.bdet, g.bcount, nullptr);
-      if (rc) return rc; }
-    { const int rc = beam_fuse_enqueue(S, g.bdet, g.bcount, nest, g.nb, q->cf.prm.max_det, q->nd, q->nlags, g.fused, g.nfused); if (rc) return rc; }
-    q->last_launches += kCafBeamDetLaunches;
-    return CRSDR_OK;
+    return beam_maps_enqueue(r, q->chi, g.w, r.nest, q->nrows, q->nd * q->nlags, q->ref_row, g.nb, g.bmap);
 }
 
-static int caf_launch_lists(crsdr_caf *q, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nblocks, hipStream_t S)
+// the detector on the beams' maps and the fusion of their lists: (line, beam) is the line of a one-map call, as crsdr_cfar has it with comps = 1
+static int caf_stage_beam_lists(crsdr_caf *q, CafRun &r)
 {
-    const CancelBufs cb = q->cn.bufs();
-    const int rc = caf_enqueue(S, packets, packet_stride, matrix_offset, nblocks, q->nrows, q->B, q->frames, q->seg, q->nlags, q->ref_row, q->window, q->guard, q->tw, q->win,
-                               q->chi, q->map, q->peak, q->cn.on ? &cb : nullptr);
+    crsdr_caf::Beams &g = q->bb;
+    if (!g.on || !g.det) return CRSDR_OK;
+    const int rc = cfar_enqueue(r, nullptr, g.bmap, r.nest * g.nb, 0, 1, q->nd, q->nlags, q->guard, q->cf.prm, q->cf.keep, g.slots, g.tcount, g.bdet, g.bcount, nullptr);
     if (rc) return rc;
-    q->last_stream = S; q->last_nest = nblocks / q->frames; q->submitted = true; q->last_launches = kCafLaunches;
-    if (q->cn.on) { q->cn.submitted = true; q->last_launches += kCafCancelLaunches; }
-    if (!q->cf.on) return beams_launch(q, S);
-    const int rc2 = cfar_enqueue(S, q->chi, q->map, q->last_nest, q->nrows, q->nrows + 1, q->nd, q->nlags, q->guard, q->cf.prm, q->cf.keep, q->cf.slots, q->cf.tcount,
-                                 q->cf.det, q->cf.count, q->cf.snap);
-    if (rc2) return rc2;
-    q->cf.submitted = true; q->last_launches += kCafCfarLaunches;
-    if (!q->bg.on) return beams_launch(q, S);
-    const size_t K = (size_t)q->cf.prm.max_det, entries = (size_t)(q->nrows + 1);
-    const int rc3 = bearing_enqueue(S, q->chi, q->cf.det.p + (size_t)q->nrows * K * 8, entries * K * 8, q->cf.count.p + q->nrows, entries, q->last_nest, q->nrows, q->nd,
-                                    q->nlags, q->ref_row, q->guard, q->cf.prm, q->bg.prm, q->bg.rec, q->bg.tbest, q->bg.dir, q->bg.spec);
-    if (rc3) return rc3;
-    q->bg.submitted = true; q->last_launches += kCafBearingLaunches;
-    return beams_launch(q, S);
+    return beam_fuse_enqueue(r, g.bdet, g.bcount, r.nest, g.nb, q->cf.prm.max_det, q->nd, q->nlags, g.fused, g.nfused);
 }
 
-// a submit: everything up to the lists, and the tracker behind bearings and fusion (nothing with it off)
-static int caf_launch(crsdr_caf *q, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nblocks, hipStream_t S)
+static int caf_stage_track(crsdr_caf *q, CafRun &r)
 {
-    { const int rc = caf_launch_lists(q, packets, packet_stride, matrix_offset, nblocks, S); if (rc) return rc; }
     crsdr_caf::Track &t = q->tk;
     if (!t.on) return CRSDR_OK;
     const size_t K = (size_t)q->cf.prm.max_det, entries = (size_t)(q->nrows + 1);
-    const bool fused = t.prm.source == trk::SRC_FUSED;
-    const int rc = fused ? track_enqueue(S, q->bb.fused, K * 8, q->bb.nfused, 1, nullptr, caf_track::AUX_BEAM, q->last_nest, (int)K, q->nd, q->nlags, t.prm, t.state, t.trk, t.ntrk)
-                         : track_enqueue(S, q->cf.det.p + (size_t)q->nrows * K * 8, entries * K * 8, q->cf.count.p + q->nrows, entries, q->bg.on ? q->bg.dir.p : nullptr,
-                                         q->bg.on ? caf_track::AUX_DIR : caf_track::AUX_NONE, q->last_nest, (int)K, q->nd, q->nlags, t.prm, t.state, t.trk, t.ntrk);
-    if (rc) return rc;
-    t.submitted = true; q->last_launches += kCafTrackLaunches;
-    return CRSDR_OK;
+    if (t.prm.source == trk::SRC_FUSED)
+        return track_enqueue(r, q->bb.fused, K * 8, q->bb.nfused, 1, nullptr, caf_track::AUX_BEAM, r.nest, (int)K, q->nd, q->nlags, t.prm, t.state, t.trk, t.ntrk);
+    return track_enqueue(r, q->cf.det.p + (size_t)q->nrows * K * 8, entries * K * 8, q->cf.count.p + q->nrows, entries, q->bg.on ? q->bg.dir.p : nullptr,
+                         q->bg.on ? caf_track::AUX_DIR : caf_track::AUX_NONE, r.nest, (int)K, q->nd, q->nlags, t.prm, t.state, t.trk, t.ntrk);
+}
+
+static int caf_launch(crsdr_caf *q, const int8_t *packets, size_t packet_stride, size_t matrix_offset, int nblocks, hipStream_t S)
+{
+    CafRun r{S, nblocks / q->frames};
+    int rc = caf_stage_maps(q, r, packets, packet_stride, matrix_offset, nblocks);
+    if (!rc) rc = caf_stage_cfar(q, r);
+    if (!rc) rc = caf_stage_bearing(q, r);
+    if (!rc) rc = caf_stage_beams(q, r);
+    if (!rc) rc = caf_stage_beam_lists(q, r);
+    if (!rc) rc = caf_stage_track(q, r);
+    // Deliberately also behind a stage that failed to launch: the kernels ahead of it are on S and write the buffers, so the object
+    // counts as submitted from the first launch on, and destroy and the setters wait for them (caf_quiesce).  The features' bits
+    // stand for whole stages only.
+    if (r.launches)
+        q->last = CafLast{S, r.nest, r.launches, rc ? kCafRanBase : kCafRanBase | (q->cn.on ? kCafRanCancel : 0u) | (q->cf.on ? kCafRanCfar : 0u) | (q->bg.on ? kCafRanBearing : 0u) |
+                                                                      (q->bb.on ? kCafRanBeams : 0u) | (q->tk.on ? kCafRanTrack : 0u)};
+    return rc;
 }
 
 extern "C" int crsdr_caf_submit(crsdr_caf *q, const void *device_packets, size_t packet_stride, size_t matrix_offset, int nblocks, void *hip_stream)
@@ -486,23 +553,20 @@ extern "C" int crsdr_caf_submit_plan(crsdr_caf *q, crsdr_plan *p)
 extern "C" int crsdr_caf_last_submit(crsdr_caf *q, int *nest, int *launches)
 {
     if (!q) return fail(CRSDR_EINVAL, "caf_last_submit: NULL caf");
-    if (!q->submitted) return fail(CRSDR_ESTATE, "caf_last_submit: nothing submitted");
-    if (nest) *nest = q->last_nest;
-    if (launches) *launches = q->last_launches;
+    if (!(q->last.ran & kCafRanBase)) return fail(CRSDR_ESTATE, "caf_last_submit: nothing submitted");
+    if (nest) *nest = q->last.nest;
+    if (launches) *launches = q->last.launches;
     return CRSDR_OK;
 }
 
+// ---- the maps ----
 extern "C" int crsdr_caf_fetch(crsdr_caf *q, float *chi, float *map, float *peak)
 {
     if (!q) return fail(CRSDR_EINVAL, "caf_fetch: NULL caf");
-    if (!q->submitted) return fail(CRSDR_ESTATE, "caf_fetch: nothing submitted");
-    HIP_TRY(hipSetDevice(q->device));
-    const size_t lines = (size_t)q->last_nest, cells = (size_t)q->nd * (size_t)q->nlags;
-    if (chi) HIP_TRY(hipMemcpyAsync(chi, q->chi.p, sizeof(float2) * lines * (size_t)q->nrows * cells, hipMemcpyDeviceToHost, q->last_stream));
-    if (map) HIP_TRY(hipMemcpyAsync(map, q->map.p, sizeof(float) * lines * cells, hipMemcpyDeviceToHost, q->last_stream));
-    if (peak) HIP_TRY(hipMemcpyAsync(peak, q->peak.p, sizeof(float) * lines * (size_t)(q->nrows + 1) * 6, hipMemcpyDeviceToHost, q->last_stream));
-    HIP_TRY(hipStreamSynchronize(q->last_stream));
-    return CRSDR_OK;
+    if (!(q->last.ran & kCafRanBase)) return fail(CRSDR_ESTATE, "caf_fetch: nothing submitted");
+    const size_t lines = (size_t)q->last.nest, cells = (size_t)q->nd * (size_t)q->nlags;
+    return DevFetch(q->device, q->last.stream).copy(chi, q->chi.p, lines * (size_t)q->nrows * cells).copy(map, q->map.p, lines * cells)
+        .copy(peak, q->peak.p, lines * (size_t)(q->nrows + 1) * 6).wait();
 }
 
 extern "C" int crsdr_caf_device_buffers(crsdr_caf *q, void **chi, void **map, void **peak)
@@ -514,28 +578,22 @@ extern "C" int crsdr_caf_device_buffers(crsdr_caf *q, void **chi, void **map, vo
     return CRSDR_OK;
 }
 
+// ---- the detector ----
 extern "C" int crsdr_caf_set_cfar(crsdr_caf *q, const crsdr_cfar_desc *desc)
 {
     if (!q) return fail(CRSDR_EINVAL, "caf_set_cfar: NULL caf");
-    if (q->tk.on) return fail(CRSDR_ESTATE, "caf_set_cfar: the tracker is on (crsdr_caf_set_track): its measurements are this detector's lists; turn it off first");
-    if (q->bb.on) return fail(CRSDR_ESTATE, "caf_set_cfar: beams are on (crsdr_caf_set_beams): whether they are detected on, and the lists' sizes, are this detector's; turn them off first");
-    if (q->bg.on) return fail(CRSDR_ESTATE, "caf_set_cfar: bearings are on (crsdr_caf_set_bearing): their buffers and training set are this detector's; turn them off first");
+    { const int rc = caf_rules(q, kCafCfar, false); if (rc) return rc; }
     cfar::Params prm{};
     if (desc) { const int rc_ = cfar_args_ok("caf_set_cfar", q->nd, desc, &prm); if (rc_) return rc_; }
-    HIP_TRY(hipSetDevice(q->device));
-    if (q->submitted) HIP_TRY(hipDeviceSynchronize());      // the last submit may still write the buffers let go here (its stream may be the caller's, and gone)
-    q->cf = crsdr_caf::Cfar();
-    if (!desc) return CRSDR_OK;
-    const size_t maps = (size_t)(q->max_batch / q->frames) * (size_t)(q->nrows + 1), lines = (size_t)(q->max_batch / q->frames), K = (size_t)prm.max_det;
-    const size_t tiles = (size_t)cfar::tiles_of(q->nd, q->nlags);
-    const int keep = cfar::tile_keep(prm.max_det, q->nd, q->nlags);
+    { const int rc = caf_clear(q, q->cf, kCafRanCfar); if (rc || !desc) return rc; }
+    const size_t lines = q->lines(), maps = lines * (size_t)(q->nrows + 1), K = (size_t)prm.max_det, tiles = (size_t)cfar::tiles_of(q->nd, q->nlags);
+    crsdr_caf::Cfar f;
+    f.prm = prm; f.keep = cfar::tile_keep(prm.max_det, q->nd, q->nlags); f.on = true;
     int r = CRSDR_OK;
-    if ((r = q->cf.slots.alloc(maps * tiles * (size_t)keep)) || (r = q->cf.tcount.alloc(maps * tiles)) || (r = q->cf.count.alloc(maps)) || (r = q->cf.det.alloc(maps * K * 8)) ||
-        (r = q->cf.snap.alloc(lines * K * (size_t)q->nrows * 2))) {
-        q->cf = crsdr_caf::Cfar();
+    if ((r = f.slots.alloc(maps * tiles * (size_t)f.keep)) || (r = f.tcount.alloc(maps * tiles)) || (r = f.count.alloc(maps)) || (r = f.det.alloc(maps * K * 8)) ||
+        (r = f.snap.alloc(lines * K * (size_t)q->nrows * 2)))
         return r;
-    }
-    q->cf.prm = prm; q->cf.keep = keep; q->cf.on = true;
+    q->cf = std::move(f);
     return CRSDR_OK;
 }
 
@@ -543,14 +601,10 @@ extern "C" int crsdr_caf_fetch_cfar(crsdr_caf *q, float *det, int32_t *count, fl
 {
     if (!q) return fail(CRSDR_EINVAL, "caf_fetch_cfar: NULL caf");
     if (!q->cf.on) return fail(CRSDR_ESTATE, "caf_fetch_cfar: no detector set (crsdr_caf_set_cfar)");
-    if (!q->cf.submitted) return fail(CRSDR_ESTATE, "caf_fetch_cfar: nothing submitted since the detector was set");
-    HIP_TRY(hipSetDevice(q->device));
-    const size_t lines = (size_t)q->last_nest, maps = lines * (size_t)(q->nrows + 1), K = (size_t)q->cf.prm.max_det;
-    if (det) HIP_TRY(hipMemcpyAsync(det, q->cf.det.p, sizeof(float) * maps * K * 8, hipMemcpyDeviceToHost, q->last_stream));
-    if (count) HIP_TRY(hipMemcpyAsync(count, q->cf.count.p, sizeof(int32_t) * maps, hipMemcpyDeviceToHost, q->last_stream));
-    if (snap) HIP_TRY(hipMemcpyAsync(snap, q->cf.snap.p, sizeof(float) * lines * K * (size_t)q->nrows * 2, hipMemcpyDeviceToHost, q->last_stream));
-    HIP_TRY(hipStreamSynchronize(q->last_stream));
-    return CRSDR_OK;
+    if (!(q->last.ran & kCafRanCfar)) return fail(CRSDR_ESTATE, "caf_fetch_cfar: nothing submitted since the detector was set");
+    const size_t lines = (size_t)q->last.nest, maps = lines * (size_t)(q->nrows + 1), K = (size_t)q->cf.prm.max_det;
+    return DevFetch(q->device, q->last.stream).copy(det, q->cf.det.p, maps * K * 8).copy(count, q->cf.count.p, maps).copy(snap, q->cf.snap.p, lines * K * (size_t)q->nrows * 2)
+        .wait();
 }
 
 extern "C" int crsdr_caf_cfar_device_buffers(crsdr_caf *q, void **det, void **count, void **snap)
@@ -563,31 +617,65 @@ extern "C" int crsdr_caf_cfar_device_buffers(crsdr_caf *q, void **det, void **co
     return CRSDR_OK;
 }
 
+extern "C" int crsdr_cfar_alpha(double pfa, int ntrain, float *alpha)
+{
+    if (!alpha) return fail(CRSDR_EINVAL, "cfar_alpha: NULL alpha");
+    if (!(pfa > 0.0 && pfa < 1.0)) return fail(CRSDR_EINVAL, "cfar_alpha: pfa = %g (inside (0, 1))", pfa);
+    if (ntrain < 1) return fail(CRSDR_EINVAL, "cfar_alpha: ntrain = %d (at least 1)", ntrain);
+    *alpha = (float)((double)ntrain * (pow(pfa, -1.0 / (double)ntrain) - 1.0));
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_cfar(float *det, int32_t *count, const float *src, int comps, int nd, int R, int guard, const crsdr_cfar_desc *desc, int mem_kind)
+{
+    if (!src || !desc || (!det && !count)) return fail(CRSDR_EINVAL, "cfar: need src, a descriptor and at least one of det, count");
+    if (comps != 1 && comps != 2) return fail(CRSDR_EINVAL, "cfar: comps = %d (1: a map, 2: a chi)", comps);
+    { const int rc_ = caf_shape_ok("cfar", nd, R, guard, 0, 2); if (rc_) return rc_; }
+    cfar::Params prm{};
+    { const int rc_ = cfar_args_ok("cfar", nd, desc, &prm); if (rc_) return rc_; }
+    OP_PROLOGUE_MEM("cfar", mem_kind);
+    const size_t cells = (size_t)nd * (size_t)R, K = (size_t)prm.max_det, tiles = (size_t)cfar::tiles_of(nd, R);
+    const size_t sb = sizeof(float) * cells * (size_t)comps, db = sizeof(float) * K * 8, nb = sizeof(int32_t);
+    const int keep = cfar::tile_keep(prm.max_det, nd, R);
+    OpStage st(mem_kind);
+    const float *d_s = (const float *)st.in(0, src, sb, comps == 2 ? 8 : 4);
+    float *d_d = (float *)st.out(1, det, db, 4);
+    int32_t *d_n = (int32_t *)st.out(2, count, nb, 4);
+    if (st.rc) return st.rc;
+    if (st.misaligned) return fail(CRSDR_EINVAL, "cfar: device det, count and a map 4-byte, a chi 8-byte aligned");
+    if (st.spare(1, d_d, db) || st.spare(2, d_n, nb)) return st.rc;
+    OP_RESERVE(3, sizeof(cfar::Cand) * tiles * (size_t)keep);
+    OP_RESERVE(4, sizeof(int32_t) * tiles);
+    CafRun r{nullptr};
+    { const int rc_ = cfar_enqueue(r, comps == 2 ? (const float2 *)d_s : nullptr, comps == 1 ? d_s : nullptr, 1, comps == 2 ? 1 : 0, 1, nd, R, guard, prm, keep,
+                                   (cfar::Cand *)g_op.buf[3], (int32_t *)g_op.buf[4], d_d, d_n, nullptr); if (rc_) return rc_; }
+    st.back(det, d_d, db);
+    st.back(count, d_n, nb);
+    return st.finish();
+}
+
+// ---- the bearings ----
 extern "C" int crsdr_caf_set_bearing(crsdr_caf *q, const crsdr_caf_bearing_desc *desc)
 {
     if (!q) return fail(CRSDR_EINVAL, "caf_set_bearing: NULL caf");
-    if (q->tk.on) return fail(CRSDR_ESTATE, "caf_set_bearing: the tracker is on (crsdr_caf_set_track): its auxiliary pairs are these bearings; turn it off first");
-    const size_t lines = (size_t)(q->max_batch / q->frames);
+    { const int rc = caf_rules(q, kCafBearing, false); if (rc) return rc; }
+    const size_t lines = q->lines();
     brg::Params prm{};
     if (desc) {
         // (the detector off: the limits that need its K are checked with K = 1, and the call is refused for the state below)
         const int rc_ = bearing_args_ok("caf_set_bearing", q->nrows, (long long)lines, q->cf.on ? q->cf.prm.max_det : 1, desc, &prm);
         if (rc_) return rc_;
-        if (!q->cf.on) return fail(CRSDR_ESTATE, "caf_set_bearing: no detector set (crsdr_caf_set_cfar): there are no detections to take a bearing of");
+        { const int rc = caf_rules(q, kCafBearing, true); if (rc) return rc; }
     }
-    HIP_TRY(hipSetDevice(q->device));
-    if (q->submitted) HIP_TRY(hipDeviceSynchronize());      // the last submit may still write the buffers let go here
-    q->bg = crsdr_caf::Bearing();
-    if (!desc) return CRSDR_OK;
+    { const int rc = caf_clear(q, q->bg, kCafRanBearing); if (rc || !desc) return rc; }
     const size_t K = (size_t)q->cf.prm.max_det, npts = (size_t)prm.ncx * (size_t)prm.ncy, tiles = (size_t)bearing::tiles_of(prm.ncx, prm.ncy);
-    crsdr_caf::Bearing &g = q->bg;
+    crsdr_caf::Bearing f;
+    f.prm = prm; f.on = true;
     int r = CRSDR_OK;
-    if ((r = g.rec.alloc(lines * K * brg::REC)) || (r = g.tbest.alloc(lines * K * tiles)) || (r = g.dir.alloc(lines * K * 8)) ||
-        ((prm.flags & brg::KEEP_SPECTRUM) && (r = g.spec.alloc(lines * K * npts))) || (r = bearing_lds_limit())) {
-        q->bg = crsdr_caf::Bearing();
+    if ((r = f.rec.alloc(lines * K * brg::REC)) || (r = f.tbest.alloc(lines * K * tiles)) || (r = f.dir.alloc(lines * K * 8)) ||
+        ((prm.flags & brg::KEEP_SPECTRUM) && (r = f.spec.alloc(lines * K * npts))))
         return r;
-    }
-    g.prm = prm; g.on = true;
+    q->bg = std::move(f);
     return CRSDR_OK;
 }
 
@@ -595,14 +683,10 @@ extern "C" int crsdr_caf_fetch_bearing(crsdr_caf *q, float *dir, float *spec)
 {
     if (!q) return fail(CRSDR_EINVAL, "caf_fetch_bearing: NULL caf");
     if (!q->bg.on) return fail(CRSDR_ESTATE, "caf_fetch_bearing: no bearings set (crsdr_caf_set_bearing)");
-    if (!q->bg.submitted) return fail(CRSDR_ESTATE, "caf_fetch_bearing: nothing submitted since the bearings were set");
+    if (!(q->last.ran & kCafRanBearing)) return fail(CRSDR_ESTATE, "caf_fetch_bearing: nothing submitted since the bearings were set");
     if (spec && !q->bg.spec.p) return fail(CRSDR_ESTATE, "caf_fetch_bearing: the spectrum is not kept (CRSDR_BEARING_KEEP_SPECTRUM)");
-    HIP_TRY(hipSetDevice(q->device));
-    const size_t slots = (size_t)q->last_nest * (size_t)q->cf.prm.max_det, npts = (size_t)q->bg.prm.ncx * (size_t)q->bg.prm.ncy;
-    if (dir) HIP_TRY(hipMemcpyAsync(dir, q->bg.dir.p, sizeof(float) * slots * 8, hipMemcpyDeviceToHost, q->last_stream));
-    if (spec) HIP_TRY(hipMemcpyAsync(spec, q->bg.spec.p, sizeof(float) * slots * npts, hipMemcpyDeviceToHost, q->last_stream));
-    HIP_TRY(hipStreamSynchronize(q->last_stream));
-    return CRSDR_OK;
+    const size_t slots = (size_t)q->last.nest * (size_t)q->cf.prm.max_det, npts = (size_t)q->bg.prm.ncx * (size_t)q->bg.prm.ncy;
+    return DevFetch(q->device, q->last.stream).copy(dir, q->bg.dir.p, slots * 8).copy(spec, q->bg.spec.p, slots * npts).wait();
 }
 
 extern "C" int crsdr_caf_bearing_device_buffers(crsdr_caf *q, void **dir, void **spec)
@@ -618,12 +702,7 @@ extern "C" int crsdr_bearing(float *dir, float *spec, const float *chi, int nrow
                              const crsdr_cfar_desc *cdesc, const crsdr_caf_bearing_desc *bdesc, int mem_kind)
 {
     if (!chi || !det || !count || !cdesc || !bdesc || (!dir && !spec)) return fail(CRSDR_EINVAL, "bearing: need chi, det, count, both descriptors and at least one of dir, spec");
-    const int lgd = nd >= 1 && nd <= (1 << caf::CAF_MAX_LOG2) ? ilog2_exact(nd) : -1;
-    if (lgd < caf::CAF_MIN_LOG2) return fail(CRSDR_EINVAL, "bearing: nd = %d (a power of two in [8, 4096])", nd);
-    if (R < 1 || R > caf::CAF_MAX_LAGS) return fail(CRSDR_EINVAL, "bearing: R = %d (1..%d)", R, caf::CAF_MAX_LAGS);
-    if (nrows < 2 || (long long)nrows * nd * R > kCafMaxCells) return fail(CRSDR_EINVAL, "bearing: nrows = %d (at least 2, nrows * nd * R at most 2^24)", nrows);
-    if (ref_row < 0 || ref_row >= nrows) return fail(CRSDR_EINVAL, "bearing: ref_row = %d (0..%d)", ref_row, nrows - 1);
-    if (guard < 0 || guard > nd / 2) return fail(CRSDR_EINVAL, "bearing: guard = %d (0..nd / 2 = %d)", guard, nd / 2);
+    { const int rc_ = caf_shape_ok("bearing", nd, R, guard, ref_row, nrows); if (rc_) return rc_; }
     cfar::Params cp{};
     brg::Params bp{};
     { const int rc_ = cfar_args_ok("bearing", nd, cdesc, &cp); if (rc_) return rc_; }
@@ -641,44 +720,37 @@ extern "C" int crsdr_bearing(float *dir, float *spec, const float *chi, int nrow
     float *d_s = keep ? (float *)st.out(4, spec, sb, 4) : nullptr;
     if (st.rc) return st.rc;
     if (st.misaligned) return fail(CRSDR_EINVAL, "bearing: device det, count, dir and spec 4-byte, chi 8-byte aligned");
-    // (device memory and an output not asked for: the kernels write it all the same)
-    if (!d_d) { OP_RESERVE(3, db); d_d = (float *)g_op.buf[3]; }
-    if (keep && !d_s) { OP_RESERVE(4, sb); d_s = (float *)g_op.buf[4]; }
+    if (st.spare(3, d_d, db) || (keep && st.spare(4, d_s, sb))) return st.rc;
     OP_RESERVE(5, sizeof(double) * K * brg::REC);
     OP_RESERVE(6, sizeof(bearing::Best) * K * tiles);
-    { const int rc_ = bearing_lds_limit(); if (rc_) return rc_; }
-    { const int rc_ = bearing_enqueue(0, d_c, d_t, 0, d_n, 0, 1, nrows, nd, R, ref_row, guard, cp, bp, (double *)g_op.buf[5], (bearing::Best *)g_op.buf[6], d_d, d_s); if (rc_) return rc_; }
+    { const int rc_ = caf_lds_limits(); if (rc_) return rc_; }
+    CafRun r{nullptr};
+    { const int rc_ = bearing_enqueue(r, d_c, d_t, 0, d_n, 0, 1, nrows, nd, R, ref_row, guard, cp, bp, (double *)g_op.buf[5], (bearing::Best *)g_op.buf[6], d_d, d_s); if (rc_) return rc_; }
     st.back(dir, d_d, db);
     if (keep) st.back(spec, d_s, sb);
     return st.finish();
 }
 
+// ---- the beams ----
 extern "C" int crsdr_caf_set_beams(crsdr_caf *q, const crsdr_caf_beams_desc *desc)
 {
     if (!q) return fail(CRSDR_EINVAL, "caf_set_beams: NULL caf");
-    if (q->tk.on) return fail(CRSDR_ESTATE, "caf_set_beams: the tracker is on (crsdr_caf_set_track): the fused list may be its source; turn it off first");
-    const size_t lines = (size_t)(q->max_batch / q->frames), cells = (size_t)q->nd * (size_t)q->nlags, m = (size_t)(q->nrows - 1);
+    { const int rc = caf_rules(q, kCafBeams, false); if (rc) return rc; }
+    const size_t lines = q->lines(), cells = (size_t)q->nd * (size_t)q->nlags, m = (size_t)(q->nrows - 1);
     if (desc) { const int rc_ = beams_args_ok("caf_set_beams", q->nrows, (long long)lines, q->nd, q->nlags, desc->nbeams, desc->weights, desc->flags); if (rc_) return rc_; }
-    HIP_TRY(hipSetDevice(q->device));
-    if (q->submitted) HIP_TRY(hipDeviceSynchronize());      // the last submit may still write the buffers let go here
-    q->bb = crsdr_caf::Beams();
-    if (!desc) return CRSDR_OK;
-    crsdr_caf::Beams &g = q->bb;
+    { const int rc = caf_clear(q, q->bb, kCafRanBeams); if (rc || !desc) return rc; }
     const size_t nb = (size_t)desc->nbeams, maps = lines * nb;
+    crsdr_caf::Beams f;
+    f.nb = desc->nbeams; f.det = q->cf.on; f.on = true;
     int r = CRSDR_OK;
-    if ((r = g.w.alloc(nb * m * 2)) || (r = g.bmap.alloc(maps * cells)) || (r = HIP_RC(hipMemcpy(g.w.p, desc->weights, sizeof(float) * nb * m * 2, hipMemcpyHostToDevice)))) {
-        q->bb = crsdr_caf::Beams();
-        return r;
-    }
-    if (q->cf.on) {
+    if ((r = f.w.alloc(nb * m * 2)) || (r = f.bmap.alloc(maps * cells)) || (r = HIP_RC(hipMemcpy(f.w.p, desc->weights, sizeof(float) * nb * m * 2, hipMemcpyHostToDevice)))) return r;
+    if (f.det) {
         const size_t K = (size_t)q->cf.prm.max_det, tiles = (size_t)cfar::tiles_of(q->nd, q->nlags);
-        if ((r = g.slots.alloc(maps * tiles * (size_t)q->cf.keep)) || (r = g.tcount.alloc(maps * tiles)) || (r = g.bcount.alloc(maps)) || (r = g.bdet.alloc(maps * K * 8)) ||
-            (r = g.fused.alloc(lines * K * 8)) || (r = g.nfused.alloc(lines))) {
-            q->bb = crsdr_caf::Beams();
+        if ((r = f.slots.alloc(maps * tiles * (size_t)q->cf.keep)) || (r = f.tcount.alloc(maps * tiles)) || (r = f.bcount.alloc(maps)) || (r = f.bdet.alloc(maps * K * 8)) ||
+            (r = f.fused.alloc(lines * K * 8)) || (r = f.nfused.alloc(lines)))
             return r;
-        }
     }
-    g.nb = desc->nbeams; g.det = q->cf.on; g.on = true;
+    q->bb = std::move(f);
     return CRSDR_OK;
 }
 
@@ -686,17 +758,11 @@ extern "C" int crsdr_caf_fetch_beams(crsdr_caf *q, float *bmap, float *bdet, int
 {
     if (!q) return fail(CRSDR_EINVAL, "caf_fetch_beams: NULL caf");
     if (!q->bb.on) return fail(CRSDR_ESTATE, "caf_fetch_beams: no beams set (crsdr_caf_set_beams)");
-    if (!q->bb.submitted) return fail(CRSDR_ESTATE, "caf_fetch_beams: nothing submitted since the beams were set");
+    if (!(q->last.ran & kCafRanBeams)) return fail(CRSDR_ESTATE, "caf_fetch_beams: nothing submitted since the beams were set");
     if ((bdet || bcount || fused || nfused) && !q->bb.det) return fail(CRSDR_ESTATE, "caf_fetch_beams: the detector was off when the beams were set: there are no lists");
-    HIP_TRY(hipSetDevice(q->device));
-    const size_t lines = (size_t)q->last_nest, maps = lines * (size_t)q->bb.nb, cells = (size_t)q->nd * (size_t)q->nlags, K = (size_t)q->cf.prm.max_det;
-    if (bmap) HIP_TRY(hipMemcpyAsync(bmap, q->bb.bmap.p, sizeof(float) * maps * cells, hipMemcpyDeviceToHost, q->last_stream));
-    if (bdet) HIP_TRY(hipMemcpyAsync(bdet, q->bb.bdet.p, sizeof(float) * maps * K * 8, hipMemcpyDeviceToHost, q->last_stream));
-    if (bcount) HIP_TRY(hipMemcpyAsync(bcount, q->bb.bcount.p, sizeof(int32_t) * maps, hipMemcpyDeviceToHost, q->last_stream));
-    if (fused) HIP_TRY(hipMemcpyAsync(fused, q->bb.fused.p, sizeof(float) * lines * K * 8, hipMemcpyDeviceToHost, q->last_stream));
-    if (nfused) HIP_TRY(hipMemcpyAsync(nfused, q->bb.nfused.p, sizeof(int32_t) * lines, hipMemcpyDeviceToHost, q->last_stream));
-    HIP_TRY(hipStreamSynchronize(q->last_stream));
-    return CRSDR_OK;
+    const size_t lines = (size_t)q->last.nest, maps = lines * (size_t)q->bb.nb, cells = (size_t)q->nd * (size_t)q->nlags, K = (size_t)q->cf.prm.max_det;
+    return DevFetch(q->device, q->last.stream).copy(bmap, q->bb.bmap.p, maps * cells).copy(bdet, q->bb.bdet.p, maps * K * 8).copy(bcount, q->bb.bcount.p, maps)
+        .copy(fused, q->bb.fused.p, lines * K * 8).copy(nfused, q->bb.nfused.p, lines).wait();
 }
 
 extern "C" int crsdr_caf_beams_device_buffers(crsdr_caf *q, void **bmap, void **bdet, void **bcount, void **fused, void **nfused)
@@ -715,10 +781,7 @@ extern "C" int crsdr_beam_maps(float *bmap, const float *chi, int nrows, int nd,
 {
     if (!bmap || !chi) return fail(CRSDR_EINVAL, "beam_maps: need bmap and chi");
     // (the maps do not depend on the shape of a line, only on its nd R cells: nd need not be a power of two here)
-    if (nd < 1 || nd > (1 << caf::CAF_MAX_LOG2)) return fail(CRSDR_EINVAL, "beam_maps: nd = %d (1..4096)", nd);
-    if (R < 1 || R > caf::CAF_MAX_LAGS) return fail(CRSDR_EINVAL, "beam_maps: R = %d (1..%d)", R, caf::CAF_MAX_LAGS);
-    if (nrows < 2 || (long long)nrows * nd * R > kCafMaxCells) return fail(CRSDR_EINVAL, "beam_maps: nrows = %d (at least 2, nrows * nd * R at most 2^24)", nrows);
-    if (ref_row < 0 || ref_row >= nrows) return fail(CRSDR_EINVAL, "beam_maps: ref_row = %d (0..%d)", ref_row, nrows - 1);
+    { const int rc_ = caf_shape_ok("beam_maps", nd, R, 0, ref_row, nrows, false); if (rc_) return rc_; }
     { const int rc_ = beams_args_ok("beam_maps", nrows, 1, nd, R, nbeams, weights, 0u); if (rc_) return rc_; }
     OP_PROLOGUE_MEM("beam_maps", mem_kind);
     const size_t cells = (size_t)nd * (size_t)R, cb = sizeof(float2) * (size_t)nrows * cells, mb = sizeof(float) * (size_t)nbeams * cells;
@@ -730,7 +793,8 @@ extern "C" int crsdr_beam_maps(float *bmap, const float *chi, int nrows, int nd,
     if (st.misaligned) return fail(CRSDR_EINVAL, "beam_maps: device bmap 4-byte, chi 8-byte aligned");
     OP_RESERVE(2, wb);                                      // (the weights are the host's in either kind)
     HIP_TRY(hipMemcpy(g_op.buf[2], weights, wb, hipMemcpyHostToDevice));
-    { const int rc_ = beam_maps_enqueue(0, d_c, (const float *)g_op.buf[2], 1, nrows, (int)cells, ref_row, nbeams, d_m); if (rc_) return rc_; }
+    CafRun r{nullptr};
+    { const int rc_ = beam_maps_enqueue(r, d_c, (const float *)g_op.buf[2], 1, nrows, (int)cells, ref_row, nbeams, d_m); if (rc_) return rc_; }
     st.back(bmap, d_m, mb);
     return st.finish();
 }
@@ -738,9 +802,7 @@ extern "C" int crsdr_beam_maps(float *bmap, const float *chi, int nrows, int nd,
 extern "C" int crsdr_beam_fuse(float *fused, int32_t *nfused, const float *bdet, const int32_t *bcount, int nbeams, int K, int nd, int R, int mem_kind)
 {
     if (!bdet || !bcount || (!fused && !nfused)) return fail(CRSDR_EINVAL, "beam_fuse: need bdet, bcount and at least one of fused, nfused");
-    const int lgd = nd >= 1 && nd <= (1 << caf::CAF_MAX_LOG2) ? ilog2_exact(nd) : -1;
-    if (lgd < caf::CAF_MIN_LOG2) return fail(CRSDR_EINVAL, "beam_fuse: nd = %d (a power of two in [8, 4096])", nd);
-    if (R < 1 || R > caf::CAF_MAX_LAGS) return fail(CRSDR_EINVAL, "beam_fuse: R = %d (1..%d)", R, caf::CAF_MAX_LAGS);
+    { const int rc_ = caf_shape_ok("beam_fuse", nd, R, 0, 0, 2); if (rc_) return rc_; }
     if (nbeams < 1 || nbeams > bm::MAX_BEAMS) return fail(CRSDR_EINVAL, "beam_fuse: nbeams = %d (1..%d)", nbeams, bm::MAX_BEAMS);
     if (K < 1 || K > cfar::MAX_DET) return fail(CRSDR_EINVAL, "beam_fuse: K = %d (1..%d)", K, cfar::MAX_DET);
     OP_PROLOGUE_MEM("beam_fuse", mem_kind);
@@ -752,10 +814,9 @@ extern "C" int crsdr_beam_fuse(float *fused, int32_t *nfused, const float *bdet,
     int32_t *d_k = (int32_t *)st.out(3, nfused, sizeof(int32_t), 4);
     if (st.rc) return st.rc;
     if (st.misaligned) return fail(CRSDR_EINVAL, "beam_fuse: device bdet, bcount, fused and nfused 4-byte aligned");
-    // (device memory and an output not asked for: the kernel writes it all the same)
-    if (!d_f) { OP_RESERVE(2, fb); d_f = (float *)g_op.buf[2]; }
-    if (!d_k) { OP_RESERVE(3, sizeof(int32_t)); d_k = (int32_t *)g_op.buf[3]; }
-    { const int rc_ = beam_fuse_enqueue(0, d_t, d_n, 1, nbeams, K, nd, R, d_f, d_k); if (rc_) return rc_; }
+    if (st.spare(2, d_f, fb) || st.spare(3, d_k, sizeof(int32_t))) return st.rc;
+    CafRun r{nullptr};
+    { const int rc_ = beam_fuse_enqueue(r, d_t, d_n, 1, nbeams, K, nd, R, d_f, d_k); if (rc_) return rc_; }
     st.back(fused, d_f, fb);
     st.back(nfused, d_k, sizeof(int32_t));
     return st.finish();
@@ -775,29 +836,23 @@ extern "C" int crsdr_caf_beam_steer(float *weights, int mx, int my, float d, int
     return CRSDR_OK;
 }
 
+// ---- the tracker ----
 extern "C" int crsdr_caf_set_track(crsdr_caf *q, const crsdr_caf_track_desc *desc)
 {
     if (!q) return fail(CRSDR_EINVAL, "caf_set_track: NULL caf");
     trk::Params prm{};
     if (desc) {
         { const int rc_ = track_args_ok("caf_set_track", desc, &prm); if (rc_) return rc_; }
-        if (!q->cf.on) return fail(CRSDR_ESTATE, "caf_set_track: no detector set (crsdr_caf_set_cfar): there are no detections to track");
-        if (prm.source == trk::SRC_FUSED && !(q->bb.on && q->bb.det))
-            return fail(CRSDR_ESTATE, "caf_set_track: the fused source needs beams with detection (crsdr_caf_set_beams behind crsdr_caf_set_cfar)");
+        { const int rc = caf_rules(q, kCafTrack, true); if (rc) return rc; }
+        if (prm.source == trk::SRC_FUSED) { const int rc = caf_rules(q, kCafTrackFused, true); if (rc) return rc; }
     }
-    HIP_TRY(hipSetDevice(q->device));
-    if (q->submitted) HIP_TRY(hipDeviceSynchronize());      // the last submit may still write the buffers let go here
-    q->tk = crsdr_caf::Track();
-    if (!desc) return CRSDR_OK;
-    const size_t lines = (size_t)(q->max_batch / q->frames), T = (size_t)prm.max_tracks, sb = trk::state_bytes(prm.max_tracks);
-    crsdr_caf::Track &t = q->tk;
+    { const int rc = caf_clear(q, q->tk, kCafRanTrack); if (rc || !desc) return rc; }
+    const size_t T = (size_t)prm.max_tracks, sb = trk::state_bytes(prm.max_tracks);
+    crsdr_caf::Track f;
+    f.prm = prm; f.on = true;
     int r = CRSDR_OK;
-    if ((r = t.state.alloc(sb)) || (r = t.trk.alloc(lines * T * trk::REC)) || (r = t.ntrk.alloc(lines * 4)) || (r = HIP_RC(hipMemset(t.state.p, 0, sb))) ||
-        (r = track_lds_limit())) {
-        q->tk = crsdr_caf::Track();
-        return r;
-    }
-    t.prm = prm; t.on = true;
+    if ((r = f.state.alloc(sb)) || (r = f.trk.alloc(q->lines() * T * trk::REC)) || (r = f.ntrk.alloc(q->lines() * 4)) || (r = HIP_RC(hipMemset(f.state.p, 0, sb)))) return r;
+    q->tk = std::move(f);
     return CRSDR_OK;
 }
 
@@ -805,8 +860,7 @@ extern "C" int crsdr_caf_track_reset(crsdr_caf *q)
 {
     if (!q) return fail(CRSDR_EINVAL, "caf_track_reset: NULL caf");
     if (!q->tk.on) return fail(CRSDR_ESTATE, "caf_track_reset: no tracker set (crsdr_caf_set_track)");
-    HIP_TRY(hipSetDevice(q->device));
-    if (q->submitted) HIP_TRY(hipDeviceSynchronize());      // the last submit may still write the state
+    { const int rc = caf_quiesce(q); if (rc) return rc; }     // the last submit may still write the state
     HIP_TRY(hipMemset(q->tk.state.p, 0, trk::state_bytes(q->tk.prm.max_tracks)));
     return CRSDR_OK;
 }
@@ -815,13 +869,9 @@ extern "C" int crsdr_caf_fetch_track(crsdr_caf *q, float *out, int32_t *nout)
 {
     if (!q) return fail(CRSDR_EINVAL, "caf_fetch_track: NULL caf");
     if (!q->tk.on) return fail(CRSDR_ESTATE, "caf_fetch_track: no tracker set (crsdr_caf_set_track)");
-    if (!q->tk.submitted) return fail(CRSDR_ESTATE, "caf_fetch_track: nothing submitted since the tracker was set");
-    HIP_TRY(hipSetDevice(q->device));
-    const size_t lines = (size_t)q->last_nest, T = (size_t)q->tk.prm.max_tracks;
-    if (out) HIP_TRY(hipMemcpyAsync(out, q->tk.trk.p, sizeof(float) * lines * T * trk::REC, hipMemcpyDeviceToHost, q->last_stream));
-    if (nout) HIP_TRY(hipMemcpyAsync(nout, q->tk.ntrk.p, sizeof(int32_t) * lines * 4, hipMemcpyDeviceToHost, q->last_stream));
-    HIP_TRY(hipStreamSynchronize(q->last_stream));
-    return CRSDR_OK;
+    if (!(q->last.ran & kCafRanTrack)) return fail(CRSDR_ESTATE, "caf_fetch_track: nothing submitted since the tracker was set");
+    const size_t lines = (size_t)q->last.nest, T = (size_t)q->tk.prm.max_tracks;
+    return DevFetch(q->device, q->last.stream).copy(out, q->tk.trk.p, lines * T * trk::REC).copy(nout, q->tk.ntrk.p, lines * 4).wait();
 }
 
 extern "C" int crsdr_caf_track_device_buffers(crsdr_caf *q, void **out, void **nout)
@@ -848,9 +898,7 @@ extern "C" int crsdr_track(float *out, int32_t *nout, void *state, const float *
     if (!state || !det || !count || !desc || (!out && !nout)) return fail(CRSDR_EINVAL, "track: need state, det, count, a descriptor and at least one of trk, ntrk");
     if (nlines < 1 || nlines > kTrackMaxLines) return fail(CRSDR_EINVAL, "track: nlines = %d (1..%d)", nlines, kTrackMaxLines);
     if (K < 1 || K > trk::MAX_MEAS) return fail(CRSDR_EINVAL, "track: K = %d (1..%d)", K, trk::MAX_MEAS);
-    const int lgd = nd >= 1 && nd <= (1 << caf::CAF_MAX_LOG2) ? ilog2_exact(nd) : -1;
-    if (lgd < caf::CAF_MIN_LOG2) return fail(CRSDR_EINVAL, "track: nd = %d (a power of two in [8, 4096])", nd);
-    if (R < 1 || R > caf::CAF_MAX_LAGS) return fail(CRSDR_EINVAL, "track: R = %d (1..%d)", R, caf::CAF_MAX_LAGS);
+    { const int rc_ = caf_shape_ok("track", nd, R, 0, 0, 2); if (rc_) return rc_; }
     trk::Params prm{};
     { const int rc_ = track_args_ok("track", desc, &prm); if (rc_) return rc_; }
     OP_PROLOGUE_MEM("track", mem_kind);
@@ -865,36 +913,33 @@ extern "C" int crsdr_track(float *out, int32_t *nout, void *state, const float *
     int32_t *d_n = (int32_t *)st.out(5, nout, nb, 4);
     if (st.rc) return st.rc;
     if (st.misaligned) return fail(CRSDR_EINVAL, "track: device det, count, aux, trk and ntrk 4-byte, state 8-byte aligned");
-    // (device memory and an output not asked for: the kernel writes it all the same)
-    if (!d_t) { OP_RESERVE(4, tb); d_t = (float *)g_op.buf[4]; }
-    if (!d_n) { OP_RESERVE(5, nb); d_n = (int32_t *)g_op.buf[5]; }
-    { const int rc_ = track_lds_limit(); if (rc_) return rc_; }
-    { const int rc_ = track_enqueue(0, d_d, (size_t)K * 8, d_c, 1, d_a, d_a ? caf_track::AUX_PAIRS : caf_track::AUX_NONE, nlines, K, nd, R, prm, d_s, d_t, d_n); if (rc_) return rc_; }
+    if (st.spare(4, d_t, tb) || st.spare(5, d_n, nb)) return st.rc;
+    { const int rc_ = caf_lds_limits(); if (rc_) return rc_; }
+    CafRun r{nullptr};
+    { const int rc_ = track_enqueue(r, d_d, (size_t)K * 8, d_c, 1, d_a, d_a ? caf_track::AUX_PAIRS : caf_track::AUX_NONE, nlines, K, nd, R, prm, d_s, d_t, d_n); if (rc_) return rc_; }
     st.back(out, d_t, tb);
     st.back(nout, d_n, nb);
     st.back(state, d_s, sb);
     return st.finish();
 }
 
+// ---- the canceller ----
 extern "C" int crsdr_caf_set_cancel(crsdr_caf *q, const crsdr_caf_cancel_desc *desc)
 {
     if (!q) return fail(CRSDR_EINVAL, "caf_set_cancel: NULL caf");
-    const size_t lines = (size_t)(q->max_batch / q->frames);
+    const size_t lines = q->lines();
     if (desc) { const int rc_ = cancel_args_ok("caf_set_cancel", q->nd, q->nlags, (long long)lines, desc); if (rc_) return rc_; }
-    HIP_TRY(hipSetDevice(q->device));
-    if (q->submitted) HIP_TRY(hipDeviceSynchronize());      // the last submit may still use the buffers let go here
-    q->cn = crsdr_caf::Cancel();
-    if (!desc) return CRSDR_OK;
+    { const int rc = caf_clear(q, q->cn, kCafRanCancel); if (rc || !desc) return rc; }
     const size_t K = (size_t)desc->taps, P = (size_t)desc->dopp, n = K * (2 * P + 1), rows = lines * (size_t)q->nrows, nd = (size_t)q->nd;
-    crsdr_caf::Cancel &c = q->cn;
+    crsdr_caf::Cancel f;
+    f.taps = desc->taps; f.dopp = desc->dopp; f.on = true;
+    CafRun table{q->own.s};
     int r = CRSDR_OK;
-    if ((r = c.G.alloc(lines * nd * K * (size_t)q->nlags)) || (r = c.Y.alloc(rows * nd * K)) || (r = c.ph.alloc(nd)) || (r = c.S.alloc(lines * (4 * P + 1) * K * K)) ||
-        (r = c.C.alloc(rows * n)) || (r = c.W.alloc(rows * n)) || (r = c.h.alloc(rows * n)) || (r = c.E.alloc(rows)) || (r = c.status.alloc(lines)) ||
-        (r = c.coef.alloc(rows * n * 2)) || (r = c.cinfo.alloc(rows * 2)) || (r = cancel_table(q->own.s, q->nd, c.ph)) || (r = HIP_RC(hipStreamSynchronize(q->own.s)))) {
-        q->cn = crsdr_caf::Cancel();
+    if ((r = f.G.alloc(lines * nd * K * (size_t)q->nlags)) || (r = f.Y.alloc(rows * nd * K)) || (r = f.ph.alloc(nd)) || (r = f.S.alloc(lines * (4 * P + 1) * K * K)) ||
+        (r = f.C.alloc(rows * n)) || (r = f.W.alloc(rows * n)) || (r = f.h.alloc(rows * n)) || (r = f.E.alloc(rows)) || (r = f.status.alloc(lines)) ||
+        (r = f.coef.alloc(rows * n * 2)) || (r = f.cinfo.alloc(rows * 2)) || (r = cancel_table(table, q->nd, f.ph)) || (r = HIP_RC(hipStreamSynchronize(q->own.s))))
         return r;
-    }
-    c.taps = desc->taps; c.dopp = desc->dopp; c.on = true;
+    q->cn = std::move(f);
     return CRSDR_OK;
 }
 
@@ -902,13 +947,9 @@ extern "C" int crsdr_caf_fetch_cancel(crsdr_caf *q, float *coef, float *cinfo)
 {
     if (!q) return fail(CRSDR_EINVAL, "caf_fetch_cancel: NULL caf");
     if (!q->cn.on) return fail(CRSDR_ESTATE, "caf_fetch_cancel: no canceller set (crsdr_caf_set_cancel)");
-    if (!q->cn.submitted) return fail(CRSDR_ESTATE, "caf_fetch_cancel: nothing submitted since the canceller was set");
-    HIP_TRY(hipSetDevice(q->device));
-    const size_t rows = (size_t)q->last_nest * (size_t)q->nrows, n = (size_t)cc::basis(q->cn.taps, q->cn.dopp);
-    if (coef) HIP_TRY(hipMemcpyAsync(coef, q->cn.coef.p, sizeof(float) * rows * n * 2, hipMemcpyDeviceToHost, q->last_stream));
-    if (cinfo) HIP_TRY(hipMemcpyAsync(cinfo, q->cn.cinfo.p, sizeof(float) * rows * 2, hipMemcpyDeviceToHost, q->last_stream));
-    HIP_TRY(hipStreamSynchronize(q->last_stream));
-    return CRSDR_OK;
+    if (!(q->last.ran & kCafRanCancel)) return fail(CRSDR_ESTATE, "caf_fetch_cancel: nothing submitted since the canceller was set");
+    const size_t rows = (size_t)q->last.nest * (size_t)q->nrows, n = (size_t)cc::basis(q->cn.taps, q->cn.dopp);
+    return DevFetch(q->device, q->last.stream).copy(coef, q->cn.coef.p, rows * n * 2).copy(cinfo, q->cn.cinfo.p, rows * 2).wait();
 }
 
 extern "C" int crsdr_caf_cancel_device_buffers(crsdr_caf *q, void **coef, void **cinfo)
@@ -918,47 +959,6 @@ extern "C" int crsdr_caf_cancel_device_buffers(crsdr_caf *q, void **coef, void *
     if (coef) *coef = q->cn.coef;
     if (cinfo) *cinfo = q->cn.cinfo;
     return CRSDR_OK;
-}
-
-extern "C" int crsdr_cfar_alpha(double pfa, int ntrain, float *alpha)
-{
-    if (!alpha) return fail(CRSDR_EINVAL, "cfar_alpha: NULL alpha");
-    if (!(pfa > 0.0 && pfa < 1.0)) return fail(CRSDR_EINVAL, "cfar_alpha: pfa = %g (inside (0, 1))", pfa);
-    if (ntrain < 1) return fail(CRSDR_EINVAL, "cfar_alpha: ntrain = %d (at least 1)", ntrain);
-    *alpha = (float)((double)ntrain * (pow(pfa, -1.0 / (double)ntrain) - 1.0));
-    return CRSDR_OK;
-}
-
-extern "C" int crsdr_cfar(float *det, int32_t *count, const float *src, int comps, int nd, int R, int guard, const crsdr_cfar_desc *desc, int mem_kind)
-{
-    if (!src || !desc || (!det && !count)) return fail(CRSDR_EINVAL, "cfar: need src, a descriptor and at least one of det, count");
-    if (comps != 1 && comps != 2) return fail(CRSDR_EINVAL, "cfar: comps = %d (1: a map, 2: a chi)", comps);
-    const int lgd = nd >= 1 && nd <= (1 << caf::CAF_MAX_LOG2) ? ilog2_exact(nd) : -1;
-    if (lgd < caf::CAF_MIN_LOG2) return fail(CRSDR_EINVAL, "cfar: nd = %d (a power of two in [8, 4096])", nd);
-    if (R < 1 || R > caf::CAF_MAX_LAGS) return fail(CRSDR_EINVAL, "cfar: R = %d (1..%d)", R, caf::CAF_MAX_LAGS);
-    if (guard < 0 || guard > nd / 2) return fail(CRSDR_EINVAL, "cfar: guard = %d (0..nd / 2 = %d)", guard, nd / 2);
-    cfar::Params prm{};
-    { const int rc_ = cfar_args_ok("cfar", nd, desc, &prm); if (rc_) return rc_; }
-    OP_PROLOGUE_MEM("cfar", mem_kind);
-    const size_t cells = (size_t)nd * (size_t)R, K = (size_t)prm.max_det, tiles = (size_t)cfar::tiles_of(nd, R);
-    const size_t sb = sizeof(float) * cells * (size_t)comps, db = sizeof(float) * K * 8, nb = sizeof(int32_t);
-    const int keep = cfar::tile_keep(prm.max_det, nd, R);
-    OpStage st(mem_kind);
-    const float *d_s = (const float *)st.in(0, src, sb, comps == 2 ? 8 : 4);
-    float *d_d = (float *)st.out(1, det, db, 4);
-    int32_t *d_n = (int32_t *)st.out(2, count, nb, 4);
-    if (st.rc) return st.rc;
-    if (st.misaligned) return fail(CRSDR_EINVAL, "cfar: device det, count and a map 4-byte, a chi 8-byte aligned");
-    // (device memory and an output not asked for: the kernels write it all the same)
-    if (!d_d) { OP_RESERVE(1, db); d_d = (float *)g_op.buf[1]; }
-    if (!d_n) { OP_RESERVE(2, nb); d_n = (int32_t *)g_op.buf[2]; }
-    OP_RESERVE(3, sizeof(cfar::Cand) * tiles * (size_t)keep);
-    OP_RESERVE(4, sizeof(int32_t) * tiles);
-    { const int rc_ = cfar_enqueue(0, comps == 2 ? (const float2 *)d_s : nullptr, comps == 1 ? d_s : nullptr, 1, comps == 2 ? 1 : 0, 1, nd, R, guard, prm, keep,
-                                   (cfar::Cand *)g_op.buf[3], (int32_t *)g_op.buf[4], d_d, d_n, nullptr); if (rc_) return rc_; }
-    st.back(det, d_d, db);
-    st.back(count, d_n, nb);
-    return st.finish();
 }
 
 // crsdr_ambiguity (cd = NULL) and crsdr_ambiguity_cancel
@@ -980,18 +980,15 @@ static int ambiguity(float *chi, float *map, float *peak, const int8_t *matrix, 
     float *d_f = cd ? (float *)st.out(5, coef, fb, 4) : nullptr, *d_i = cd ? (float *)st.out(6, cinfo, ib, 4) : nullptr;
     if (st.rc) return st.rc;
     if (st.misaligned) return fail(CRSDR_EINVAL, "ambiguity: device matrix, map, peak, coef and cinfo 4-byte, chi 8-byte aligned");
-    // (device memory and an output not asked for: the kernels write it all the same)
-    if (!d_c) { OP_RESERVE(1, cb); d_c = (float2 *)g_op.buf[1]; }
-    if (!d_p) { OP_RESERVE(2, pb); d_p = (float *)g_op.buf[2]; }
-    if (!d_k) { OP_RESERVE(3, kb); d_k = (float *)g_op.buf[3]; }
+    if (st.spare(1, d_c, cb) || st.spare(2, d_p, pb) || st.spare(3, d_k, kb)) return st.rc;
     OP_RESERVE(4, sizeof(float2) * nd + sizeof(float) * nd);
     float2 *tw = (float2 *)g_op.buf[4];
     float *win = (float *)(tw + nd);
     { const int rc_ = spectra_tables(0, (int)nd, window, tw, win); if (rc_) return rc_; }
+    CafRun r{nullptr};
     CancelBufs c;
     if (cd) {
-        if (!d_f) { OP_RESERVE(5, fb); d_f = (float *)g_op.buf[5]; }
-        if (!d_i) { OP_RESERVE(6, ib); d_i = (float *)g_op.buf[6]; }
+        if (st.spare(5, d_f, fb) || st.spare(6, d_i, ib)) return st.rc;
         // one slot for the rest, the 16-byte types first
         const size_t nph = nd, nS = (4 * P + 1) * K * K, nC = (size_t)nrows * n, nG = nd * K * (size_t)nlags, nY = (size_t)nrows * nd * K;
         OP_RESERVE(7, sizeof(double2) * (nph + nS + 3 * nC) + sizeof(long long) * (size_t)nrows + sizeof(int2) * (nG + nY) + sizeof(int));
@@ -999,9 +996,9 @@ static int ambiguity(float *chi, float *map, float *peak, const int8_t *matrix, 
         c.ph = (double2 *)g_op.buf[7]; c.S = c.ph + nph; c.C = c.S + nS; c.W = c.C + nC; c.h = c.W + nC;
         c.E = (long long *)(c.h + nC); c.G = (int2 *)(c.E + nrows); c.Y = c.G + nG; c.status = (int *)(c.Y + nY);
         c.coef = d_f; c.cinfo = d_i;
-        { const int rc_ = cancel_table(0, (int)nd, c.ph); if (rc_) return rc_; }
+        { const int rc_ = cancel_table(r, (int)nd, c.ph); if (rc_) return rc_; }
     }
-    { const int rc_ = caf_enqueue(0, d_m, mb, 0, 1, nrows, blocksize, 1, seg, nlags, ref_row, window, guard, tw, win, d_c, d_p, d_k, cd ? &c : nullptr); if (rc_) return rc_; }
+    { const int rc_ = caf_enqueue(r, d_m, mb, 0, 1, nrows, blocksize, 1, seg, nlags, ref_row, window, guard, tw, win, d_c, d_p, d_k, cd ? &c : nullptr); if (rc_) return rc_; }
     st.back(coef, d_f, fb);
     st.back(cinfo, d_i, ib);
     st.back(chi, d_c, cb);

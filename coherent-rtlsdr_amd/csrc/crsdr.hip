@@ -586,6 +586,13 @@ struct OpStage {
         if (!rc) rc = op_reserve(slot, bytes);
         return g_op.buf[slot];
     }
+    // device memory and an output not asked for (d = NULL behind out()): the kernels write it all the same, into the slot.  Returns rc.
+    template <typename T>
+    int spare(int slot, T *&d, size_t bytes)
+    {
+        if (!d && !rc && !(rc = op_reserve(slot, bytes))) d = (T *)g_op.buf[slot];
+        return rc;
+    }
     void back(void *p, const void *d, size_t bytes) { if (host && p && !rc) rc = HIP_RC(hipMemcpy(p, d, bytes, hipMemcpyDeviceToHost)); }
     int finish() { return rc || host ? rc : HIP_RC(hipDeviceSynchronize()); }
 };
@@ -1975,7 +1982,7 @@ extern "C" int crsdr_subband_covariance(float *rbands, float *power, const int8_
     float *d_p = (float *)st.out(2, power, pb, 4);
     if (st.rc) return st.rc;
     if (st.misaligned) return fail(CRSDR_EINVAL, "subband_covariance: device matrix and power 4-byte, rbands 8-byte aligned");
-    if (!d_p) { OP_RESERVE(2, pb); d_p = (float *)g_op.buf[2]; }      // (device memory and no power asked for: the reducer writes it all the same)
+    if (st.spare(2, d_p, pb)) return st.rc;                           // (device memory and no power asked for: the reducer writes it all the same)
     OP_RESERVE(3, sizeof(float2) * (size_t)spb * subband::subband_partial(m, nfft));
     const dim3 grid((unsigned)spb, (unsigned)subband::subband_groups(m, nfft), 1);
     SUBBAND_DISPATCH(lg, hipLaunchKernelGGL(subband::k_doa_subband_cov<LG>, grid, dim3(subband::SB_THREADS), 0, 0, d_m, (size_t)0, (size_t)0, nrows, blocksize, 1, spb,

@@ -17,7 +17,7 @@
 //
 // Shape of the host code.  A feature is a sub-struct of crsdr_doa: its parameters and its device buffers, each buffer owned by a
 // DevBuf, so that "off" is an assignment of {} and nothing is freed by a list kept by hand.  What the last submit left (DoaLast) is
-// written once by doa_launch; every fetch reads its state from there and copies through DoaFetch.  A submit is doa_launch's stages.
+// written once by doa_launch; every fetch reads its state from there and copies through DevFetch.  A submit is doa_launch's stages.
 #pragma once
 
 // `launch` with NB = the apply kernel's slot count for nbeams (1, 2, 4, 8 or 16)
@@ -57,6 +57,20 @@ struct DevBuf {
 struct DoaStream {
     hipStream_t s = nullptr;
     ~DoaStream() { if (s) (void)hipStreamDestroy(s); }
+};
+// The frame of every engine's fetch, behind its own state checks: the object's device, copies on the last submit's stream for the host
+// pointers that are not NULL, one wait.  The first failure is the answer; the calls behind it do nothing.
+struct DevFetch {
+    hipStream_t S;
+    int rc;
+    DevFetch(int device, hipStream_t stream) : S(stream), rc(HIP_RC(hipSetDevice(device))) {}
+    template <typename T>
+    DevFetch &copy(void *host, const T *dev, size_t count)
+    {
+        if (host && !rc) rc = HIP_RC(hipMemcpyAsync(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost, S));
+        return *this;
+    }
+    int wait() { return rc ? rc : HIP_RC(hipStreamSynchronize(S)); }
 };
 
 // the buffers with one entry per matrix (estimate, or estimate and band)
@@ -520,20 +534,7 @@ extern "C" int crsdr_doa_last_submit(crsdr_doa *q, int *nest, int *launches)
 }
 
 // ---- fetches ----
-// The frame of every fetch, behind its own state checks: the object's device, copies on the last submit's stream for the host
-// pointers that are not NULL, one wait.  The first failure is the answer; the calls behind it do nothing.
-struct DoaFetch {
-    hipStream_t S;
-    int rc;
-    explicit DoaFetch(const crsdr_doa *q) : S(q->last.stream), rc(HIP_RC(hipSetDevice(q->device))) {}
-    template <typename T>
-    DoaFetch &copy(void *host, const T *dev, size_t count)
-    {
-        if (host && !rc) rc = HIP_RC(hipMemcpyAsync(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost, S));
-        return *this;
-    }
-    int wait() { return rc ? rc : HIP_RC(hipStreamSynchronize(S)); }
-};
+// Every fetch, behind its own state checks, copies through DevFetch on the last submit's stream.
 
 extern "C" int crsdr_doa_fetch(crsdr_doa *q, int32_t *peak, float *peak_value, float *sv, int32_t *status, float *pm, float *rxx)
 {
@@ -546,7 +547,7 @@ extern "C" int crsdr_doa_fetch(crsdr_doa *q, int32_t *peak, float *peak_value, f
     const size_t nest = (size_t)q->last.nest, m = (size_t)q->m, ms = (size_t)q->last.ms;
     static_assert(kMaxDoaMatrices >= kMaxBatch, "status of every matrix of a submit");
     int info[2 * kMaxDoaMatrices];
-    const int rc = DoaFetch(q).copy(peak, q->mat.peak.p, nest * 2).copy(peak_value, q->mat.peakv.p, nest).copy(sv, q->mat.sv.p, nest * ms)
+    const int rc = DevFetch(q->device, q->last.stream).copy(peak, q->mat.peak.p, nest * 2).copy(peak_value, q->mat.peakv.p, nest).copy(sv, q->mat.sv.p, nest * ms)
                        .copy(status ? info : nullptr, q->mat.info.p, nest * 2).copy(pm, q->mat.pm.p, nest * (size_t)q->ncx * q->ncy)
                        .copy(rxx, q->mat.rxx.p, nest * m * m).wait();
     if (rc) return rc;
@@ -570,7 +571,7 @@ extern "C" int crsdr_doa_fetch_subspace(crsdr_doa *q, float *vec)
 {
     if (!q || !vec) return fail(CRSDR_EINVAL, "doa_fetch_subspace: NULL doa or vec");
     if (!(q->last.ran & kRanBase)) return fail(CRSDR_ESTATE, "doa_fetch_subspace: nothing submitted");
-    return DoaFetch(q).copy(vec, q->mat.vec.p, (size_t)q->last.nest * (size_t)q->last.ms * q->last.ms).wait();
+    return DevFetch(q->device, q->last.stream).copy(vec, q->mat.vec.p, (size_t)q->last.nest * (size_t)q->last.ms * q->last.ms).wait();
 }
 
 // ---- the strongest local maxima of each spectrum (doa.hpp) ----
@@ -608,7 +609,7 @@ extern "C" int crsdr_doa_fetch_directions(crsdr_doa *q, int32_t *found, int32_t 
     if (!(q->last.ran & kRanPeaks)) return fail(CRSDR_ESTATE, "doa_fetch_directions: nothing submitted since crsdr_doa_set_peaks");
     if (!(q->last.ran & kRanScan)) return fail(CRSDR_ESTATE, "doa_fetch_directions: the last submit ran no scan (CRSDR_ESPRIT_ONLY)");
     const size_t nest = (size_t)q->last.nest, c = (size_t)q->peaks.count;
-    return DoaFetch(q).copy(found, q->peaks.found.p, nest).copy(peaks, q->peaks.dirs.p, nest * c * 2).copy(values, q->peaks.values.p, nest * c).wait();
+    return DevFetch(q->device, q->last.stream).copy(found, q->peaks.found.p, nest).copy(peaks, q->peaks.dirs.p, nest * c * 2).copy(values, q->peaks.values.p, nest * c).wait();
 }
 
 extern "C" int crsdr_doa_direction_buffers(crsdr_doa *q, void **found, void **peaks, void **values)
@@ -676,7 +677,7 @@ static int doa_fetch_beams(crsdr_doa *q, const char *who, bool band, float *weig
     if (!q->beams.mode || q->beams.band != band) return fail(CRSDR_ESTATE, "%s: no crsdr_doa_set_%sbeams", who, kind);
     if (!(q->last.ran & kRanBeams)) return fail(CRSDR_ESTATE, "%s: nothing submitted since crsdr_doa_set_%sbeams", who, kind);
     const size_t nmat = (size_t)q->last.nest, nb = (size_t)q->beams.nbeams;
-    return DoaFetch(q).copy(weights, q->beams.weights.p, nmat * nb * (size_t)q->m).copy(power, q->beams.power.p, nmat * nb)
+    return DevFetch(q->device, q->last.stream).copy(weights, q->beams.weights.p, nmat * nb * (size_t)q->m).copy(power, q->beams.power.p, nmat * nb)
                       .copy(beams, q->beams.beams.p, (size_t)q->last.nblocks * nb * doa_beam_points(q, band)).wait();
 }
 
@@ -742,7 +743,7 @@ extern "C" int crsdr_doa_fetch_refined(crsdr_doa *q, float *offsets, float *angl
     if (!(q->last.ran & kRanRefine)) return fail(CRSDR_ESTATE, "doa_fetch_refined: nothing submitted since crsdr_doa_set_refine");
     if (!(q->last.ran & kRanScan)) return fail(CRSDR_ESTATE, "doa_fetch_refined: the last submit ran no scan (CRSDR_ESPRIT_ONLY)");
     const size_t n = (size_t)q->last.nest * (size_t)q->last.slots;
-    return DoaFetch(q).copy(offsets, q->refine.offsets.p, 2 * n).copy(angles, q->refine.angles.p, 2 * n).copy(values, q->refine.values.p, n).wait();
+    return DevFetch(q->device, q->last.stream).copy(offsets, q->refine.offsets.p, 2 * n).copy(angles, q->refine.angles.p, 2 * n).copy(values, q->refine.values.p, n).wait();
 }
 
 extern "C" int crsdr_doa_refined_buffers(crsdr_doa *q, void **offsets, void **angles, void **values, int *slots)
@@ -782,7 +783,7 @@ extern "C" int crsdr_doa_fetch_esprit(crsdr_doa *q, int32_t *found, int32_t *sta
     if (!(q->last.ran & kRanBase) || !(q->last.ran & kRanEsprit)) return fail(CRSDR_ESTATE, "doa_fetch_esprit: nothing submitted since crsdr_doa_set_esprit");
     const DoaEsprit &es = q->esprit;
     const size_t nmat = (size_t)q->last.nest, n = nmat * (size_t)q->last.eslots;
-    return DoaFetch(q).copy(found, es.found.p, nmat).copy(status, es.status.p, nmat).copy(phases, es.phases.p, 2 * n).copy(angles, es.angles.p, 2 * n)
+    return DevFetch(q->device, q->last.stream).copy(found, es.found.p, nmat).copy(status, es.status.p, nmat).copy(phases, es.phases.p, 2 * n).copy(angles, es.angles.p, 2 * n)
                       .copy(modulus, es.modulus.p, 2 * n).copy(power, es.power.p, n).copy(flags, es.flags.p, n).wait();
 }
 
@@ -834,7 +835,7 @@ extern "C" int crsdr_doa_fetch_smoothed(crsdr_doa *q, float *rs)
     if (!q || !rs) return fail(CRSDR_EINVAL, "doa_fetch_smoothed: NULL doa or rs");
     if (!q->smooth.on) return fail(CRSDR_ESTATE, "doa_fetch_smoothed: no crsdr_doa_set_smoothing");
     if (!(q->last.ran & kRanSmooth)) return fail(CRSDR_ESTATE, "doa_fetch_smoothed: nothing submitted since crsdr_doa_set_smoothing");
-    return DoaFetch(q).copy(rs, q->smooth.rs.p, (size_t)q->last.nest * (size_t)q->ms() * q->ms()).wait();
+    return DevFetch(q->device, q->last.stream).copy(rs, q->smooth.rs.p, (size_t)q->last.nest * (size_t)q->ms() * q->ms()).wait();
 }
 
 // ---- co-array augmentation (augment.hpp) ----
@@ -870,7 +871,7 @@ extern "C" int crsdr_doa_fetch_augmented(crsdr_doa *q, float *ra)
     if (!q || !ra) return fail(CRSDR_EINVAL, "doa_fetch_augmented: NULL doa or ra");
     if (!q->augment.on) return fail(CRSDR_ESTATE, "doa_fetch_augmented: no crsdr_doa_set_augment");
     if (!(q->last.ran & kRanAugment)) return fail(CRSDR_ESTATE, "doa_fetch_augmented: nothing submitted since crsdr_doa_set_augment");
-    return DoaFetch(q).copy(ra, q->augment.ra.p, (size_t)q->last.nest * (size_t)q->ms() * q->ms()).wait();
+    return DevFetch(q->device, q->last.stream).copy(ra, q->augment.ra.p, (size_t)q->last.nest * (size_t)q->ms() * q->ms()).wait();
 }
 
 extern "C" int crsdr_doa_augment_buffers(crsdr_doa *q, void **ra, int *vx, int *vy)
@@ -906,7 +907,7 @@ extern "C" int crsdr_doa_fetch_order(crsdr_doa *q, int32_t *k, float *criterion_
     if (!q->order.crit) return fail(CRSDR_ESTATE, "doa_fetch_order: no crsdr_doa_set_order");
     if (!(q->last.ran & kRanOrder)) return fail(CRSDR_ESTATE, "doa_fetch_order: nothing submitted since crsdr_doa_set_order");
     const size_t nest = (size_t)q->last.nest, nc = (size_t)(q->order.kmax - q->order.kmin + 1);
-    return DoaFetch(q).copy(k, q->order.k.p, nest).copy(criterion_values, q->order.values.p, nest * nc).wait();
+    return DevFetch(q->device, q->last.stream).copy(k, q->order.k.p, nest).copy(criterion_values, q->order.values.p, nest * nc).wait();
 }
 
 extern "C" int crsdr_doa_order_buffers(crsdr_doa *q, void **k, void **criterion_values)
@@ -959,7 +960,7 @@ extern "C" int crsdr_doa_fetch_subbands(crsdr_doa *q, float *power)
     if (!q || !power) return fail(CRSDR_EINVAL, "doa_fetch_subbands: NULL doa or power");
     if (!q->sub.nfft) return fail(CRSDR_ESTATE, "doa_fetch_subbands: no crsdr_doa_set_subbands");
     if (!(q->last.ran & kRanBase)) return fail(CRSDR_ESTATE, "doa_fetch_subbands: nothing submitted since crsdr_doa_set_subbands");
-    return DoaFetch(q).copy(power, q->sub.power.p, (size_t)q->last.nest).wait();
+    return DevFetch(q->device, q->last.stream).copy(power, q->sub.power.p, (size_t)q->last.nest).wait();
 }
 
 extern "C" int crsdr_doa_subband_buffers(crsdr_doa *q, void **power)

@@ -177,13 +177,8 @@ extern "C" int crsdr_spectra_fetch(crsdr_spectra *q, float *psd, float *cross, f
 {
     if (!q) return fail(CRSDR_EINVAL, "spectra_fetch: NULL spectra");
     if (!q->submitted) return fail(CRSDR_ESTATE, "spectra_fetch: nothing submitted");
-    HIP_TRY(hipSetDevice(q->device));
     const size_t lines = (size_t)q->last_nest * (size_t)q->nrows, N = (size_t)q->nfft;
-    if (psd) HIP_TRY(hipMemcpyAsync(psd, q->psd.p, sizeof(float) * lines * N, hipMemcpyDeviceToHost, q->last_stream));
-    if (cross) HIP_TRY(hipMemcpyAsync(cross, q->cross.p, sizeof(float2) * lines * N, hipMemcpyDeviceToHost, q->last_stream));
-    if (align) HIP_TRY(hipMemcpyAsync(align, q->align.p, sizeof(float) * lines * 4, hipMemcpyDeviceToHost, q->last_stream));
-    HIP_TRY(hipStreamSynchronize(q->last_stream));
-    return CRSDR_OK;
+    return DevFetch(q->device, q->last_stream).copy(psd, q->psd.p, lines * N).copy(cross, q->cross.p, lines * N).copy(align, q->align.p, lines * 4).wait();
 }
 
 extern "C" int crsdr_spectra_device_buffers(crsdr_spectra *q, void **psd, void **cross, void **align)
@@ -212,10 +207,7 @@ extern "C" int crsdr_welch(float *psd, float *cross, float *align, const int8_t 
     float *d_a = (float *)st.out(3, align, ab, 4);
     if (st.rc) return st.rc;
     if (st.misaligned) return fail(CRSDR_EINVAL, "welch: device matrix, psd and align 4-byte, cross 8-byte aligned");
-    // (device memory and an output not asked for: the kernels write it all the same)
-    if (!d_p) { OP_RESERVE(1, pb); d_p = (float *)g_op.buf[1]; }
-    if (!d_c) { OP_RESERVE(2, cb); d_c = (float2 *)g_op.buf[2]; }
-    if (!d_a) { OP_RESERVE(3, ab); d_a = (float *)g_op.buf[3]; }
+    if (st.spare(1, d_p, pb) || st.spare(2, d_c, cb) || st.spare(3, d_a, ab)) return st.rc;
     OP_RESERVE(4, sizeof(float2) * N + sizeof(float) * N);
     OP_RESERVE(5, sizeof(float2) * J * N);
     float2 *tw = (float2 *)g_op.buf[4];
