@@ -343,8 +343,8 @@ def test_cfg5_long_blocks_full_size(b, oracle, model, synth):
 
 def test_full_scale_dc_rows_do_not_overflow(b, oracle):
     # worst case for the un-scaled integer transform chain: every sample -128-128j in every row.  The
-    # correlation is a triangle peaking at zero lag; |ifft|^2 reaches ~1e33 (< FLT_MAX) before the final
-    # 1/127^2 scale.  No inf / NaN, lag 0, mag equal to the oracle's.
+    # correlation is a triangle peaking at zero lag; |ifft|^2 reaches (B L 32768)^2 = 2^84 ~ 1.9e25 (< FLT_MAX) before the
+    # final 1/127^2 scale (B = 2^22: 2^116, test_gpu_long_chunks.py).  No inf / NaN, lag 0, mag equal to the oracle's.
     nsig, L = 3, 8192
     rows = np.full((nsig + 1, 2 * L), -128, dtype=np.int8)
     got = b.Plan(nsig + 1, 2 * L, b.MODE_DIGITAL).block(rows)
