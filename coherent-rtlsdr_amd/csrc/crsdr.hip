@@ -309,7 +309,9 @@ static SpinSwitch spin_switch(const char *e, int dflt)
 }
 struct Switches {
     // CRSDR_K1_VARIANT: 'a' (auto, default) = the two-row kernel (q, xcorr14q.hpp) for launches with enough rows per CU, the packed
-    // one-row kernel (p, xcorr14p.hpp) otherwise; "packed" / "q" force one of them.  Same arithmetic, identical bits.
+    // one-row kernel (p, xcorr14p.hpp) otherwise; "packed" / "q" / "r" force one of them.  Same arithmetic, identical bits.
+    // 'r' is the two-row kernel with the column twiddle chains carried from row to row (k_xcorr_lag14r): whatever holds for q
+    // (launch shape, work counter, snapshot, q_disabled, CRSDR_K1_QSPIN, wait flags) holds for r -- two_row() is the one test.
     // (Measured-slower experiments live in tools/: xcorr14h.hpp, half-row LDS images -- dead end (8) of DESIGN.md --, xcorr14w.hpp,
     // 1024 threads per row -- dead end (11) --, and xcorr14_scalar.hpp, the scalar-fp32 twin of r01.)
     char k1_variant;
@@ -324,7 +326,7 @@ static const Switches &sw()
     static const Switches s = [] {
         const char *v = getenv("CRSDR_K1_VARIANT"), *lq = getenv("CRSDR_LONG_Q");
         const char c = v ? v[0] : 'a';
-        return Switches{(c == 'p' || c == 'q') ? c : 'a', spin_switch(getenv("CRSDR_K1_QSPIN"), x14p::kQSpinLimit),
+        return Switches{(c == 'p' || c == 'q' || c == 'r') ? c : 'a', spin_switch(getenv("CRSDR_K1_QSPIN"), x14p::kQSpinLimit),
                         spin_switch(getenv("CRSDR_K1_REFSPIN"), kRefWaitBudget), spin_switch(getenv("CRSDR_K2_SPIN"), kFusedSpinLimit).value,
                         !lq || atoi(lq) != 0};
     }();
@@ -340,14 +342,15 @@ static int device_cus()
     }();
     return cus;
 }
-// which B = 16384 cross-correlation kernel a launch of rows_all rows takes: 'q' (two rows per CU) or 'p' (one)
+static bool two_row(char variant) { return variant == 'q' || variant == 'r'; }
+// which B = 16384 cross-correlation kernel a launch of rows_all rows takes: 'q' / 'r' (two rows per CU) or 'p' (one)
 static char k1_pick(int rows_all, bool allow_q)
 {
     char variant = sw().k1_variant;
     // measured (r01, T = 64): q is 3-7 % faster at 1024 / 256 / 128 / 96 / 48 rows per block (256 ... 12 rows per CU and launch),
     // 1.4 % at 64, level with p at 32 and 21 rows (8 and 5 per CU; r03: level at 10 as well)
-    if (variant == 'a') variant = rows_all >= 12 * device_cus() ? 'q' : 'p';
-    if (variant == 'q' && !allow_q) variant = 'p';   // a plan whose two-row kernel once ran out of a bounded wait stays on the packed kernel
+    if (variant == 'a') variant = rows_all >= 12 * device_cus() ? 'r' : 'p';
+    if (two_row(variant) && !allow_q) variant = 'p';   // a plan whose two-row kernel once ran out of a bounded wait stays on the packed kernel
     return variant;
 }
 
@@ -388,12 +391,12 @@ static hipError_t launch_xcorr_lag14(hipStream_t s, char variant, const XcorrArg
                                      int *waitflag, unsigned int *work, unsigned int *work_base)
 {
     const int items = row_count * a.nblocks + (a.fold ? a.nblocks : 0);
-    if (variant != 'q')
+    if (!two_row(variant))
         return launch_lds(x14p::k_xcorr_lag14p, dim3((unsigned)items), dim3(x14::THREADS), x14::LDS_BYTES, s, a, twA, twB, row_count);
     // two rows per CU in opposite phases (xcorr14q.hpp), one persistent workgroup per CU
     static long launches = 0;
     const int qspin = sw().qspin.at(launches++);
-    const hipError_t e = launch_lds(x14p::k_xcorr_lag14q, dim3((unsigned)std::max(1, std::min(device_cus(), (items + 1) / 2))), dim3(2 * x14p::QG),
+    const hipError_t e = launch_lds(variant == 'r' ? x14p::k_xcorr_lag14r : x14p::k_xcorr_lag14q, dim3((unsigned)std::max(1, std::min(device_cus(), (items + 1) / 2))), dim3(2 * x14p::QG),
                                     x14p::LDSQ14_BYTES, s, a, twA, twB, row_count, waitflag, work, *work_base, qspin);
     if (e == hipSuccess) *work_base += (unsigned)items;      // a launch that ran advances the device counter by exactly its item count (xcorr14q.hpp)
     return e;
@@ -1507,7 +1510,7 @@ static XcorrArgs xcorr_args(const crsdr_plan *p, const Batch &b, int slot)
 static bool two_line(const crsdr_plan *p, int cnt)
 {
     const char kv = sw().k1_variant;
-    return sw().long_q && (kv == 'a' || kv == 'q') && !p->q_disabled && ((long)1 << p->log2n1) * cnt >= 1024;
+    return sw().long_q && (kv == 'a' || two_row(kv)) && !p->q_disabled && ((long)1 << p->log2n1) * cnt >= 1024;
 }
 
 // K1 of long blocks (B = N1 x 16384): column FFTs -> row FFTs (x conj ref, inverse) -> inverse column FFTs + argmax -> finalize
@@ -1596,7 +1599,7 @@ static int k1_short(crsdr_plan *p, Batch &b)
     hipEvent_t *pe1 = prof_pair(p, CRSDR_KERNEL_XCORR_LAG);
     if (pe1) HIP_TRY(hipEventRecord(pe1[0], S));
     if (p->log2n == 14) {
-        const bool q = variant == 'q';
+        const bool q = two_row(variant);
         // every launch with bounded waits (the two-row kernel's, a folded launch's wait for its reference spectra) snapshots the
         // carried state first (one 28 B/row copy, ordered after the previous batch's kernels on this stream) while the ring has
         // room: what a wait that ran out is rolled back to

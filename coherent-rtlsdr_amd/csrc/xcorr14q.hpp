@@ -1,4 +1,5 @@
-// xcorr14q.hpp -- K1 with TWO rows per CU in opposite phases (experiment, CRSDR_K1_VARIANT=q).
+// xcorr14q.hpp -- K1 with TWO rows per CU in opposite phases (CRSDR_K1_VARIANT=q; =r: the same with the column twiddle chains
+// carried from row to row, what auto takes).
 //
 // tools/lds_valu_overlap.hip: on one SIMD the LDS stores of one wave overlap the packed VALU stream of the other,
 // but K1's two waves per SIMD run the same row and hit their store bursts together, so a row costs VALU time PLUS
@@ -130,7 +131,10 @@ __device__ __forceinline__ void q_tw_load(c2 *w, const c2 *__restrict__ tab, int
     tw_chain(w);
 }
 // P0 of one virtual thread without the stores (pass0_forward<false> of xcorr14p.hpp)
-__device__ __forceinline__ void q_p0_compute(c2 *v, const int8_t *__restrict__ row, const c2 *__restrict__ twA, uint32_t xor80, int vt)
+// CARRY: the column chain W_16384^(vt k) is the caller's wc (k_xcorr_lag14r: built by the previous row's q_p0i_compute, or
+// before the row loop); otherwise it is built here and wc is not looked at
+template <bool CARRY>
+__device__ __forceinline__ void q_p0_compute(c2 *v, const int8_t *__restrict__ row, const c2 *__restrict__ twA, uint32_t xor80, int vt, const c2 *wc)
 {
     const uint32_t x16 = xor80 & 0xFFFFu;
 #pragma unroll
@@ -140,9 +144,12 @@ __device__ __forceinline__ void q_p0_compute(c2 *v, const int8_t *__restrict__ r
         v[i] = mk((float)sext8(u, 0), (float)sext8(u, 1));
     }
     dft32s_pruned<false>(v);
-    c2 w[32];
-    q_tw_load(w, twA, TWA_STRIDE, vt);
-    tw_apply<-1, true, 1>(v, w);
+    if constexpr (CARRY) tw_apply<-1, true, 1>(v, wc);
+    else {
+        c2 w[32];
+        q_tw_load(w, twA, TWA_STRIDE, vt);
+        tw_apply<-1, true, 1>(v, w);
+    }
 }
 __device__ __forceinline__ void q_p0_store(c2 *A, const c2 *v, int vt)
 {
@@ -169,9 +176,12 @@ __device__ __forceinline__ void q_p0i_load(c2 *v, const c2 *A, int vt)
 #pragma unroll
     for (int k = 16; k < 32; ++k) v[k] = A[hi + (k - 16) * 528];
 }
-__device__ __forceinline__ void q_p0i_compute(float *m, c2 *v, const c2 *__restrict__ twA, int vt)
+// CARRY: the chain is built into the caller's wc, where the next row's q_p0_compute finds it
+template <bool CARRY>
+__device__ __forceinline__ void q_p0i_compute(float *m, c2 *v, const c2 *__restrict__ twA, int vt, c2 *wc)
 {
-    c2 w[32];
+    c2 wl[32];
+    c2 *w = CARRY ? wc : wl;
     q_tw_load(w, twA, TWA_STRIDE, vt);
     tw_dft32_inv<true>(v, w);
 #pragma unroll
@@ -376,9 +386,16 @@ __device__ __forceinline__ float q_pick(const float (&m0)[32], const float (&m1)
 }
 
 // grid: one workgroup per CU; items = owned rows x blocks, item (2k + g) * gridDim.x + blockIdx.x goes to group g
-__global__ __launch_bounds__(2 * QG, 1) void k_xcorr_lag14q(XcorrArgs a, const float2 *__restrict__ twA_, const float2 *__restrict__ twB_,
-                                                           int row_count, int *__restrict__ errflag, unsigned int *__restrict__ work,
-                                                           unsigned int work_base, int spin_limit)
+// The body of k_xcorr_lag14q (CARRY off) and k_xcorr_lag14r (on).  Every thread needs the column chains W_16384^(vt k), k = 1 .. 31,
+// of its two virtual threads in a row's first pass and again in its last one: the same two chains in every row.  Off, each pass
+// builds them (q_tw_load: 5 loads and 26 products each, four times per row).  On, the two chains are built once before the row
+// loop and carried over the back edge only: the last pass rebuilds each into the carried array (vt1 first), the next row's first
+// pass uses them (vt0 first) and builds nothing, so no chain is live through the ownership window.  Same function of the same
+// table values: identical bits.  A masked row touches neither array.
+template <bool CARRY>
+__device__ __forceinline__ void q_xcorr_lag14_body(XcorrArgs a,const float2 *__restrict__ twA_, const float2 *__restrict__ twB_,
+                                                   int row_count, int *__restrict__ errflag, unsigned int *__restrict__ work,
+                                                   unsigned int work_base, int spin_limit)
 {
     // 128-byte aligned (a symbol of its own: the alignment is this kernel's alone): q_junction_half addresses the image's
     // 16-byte slots by exclusive-or on the LDS byte address, which takes bits 4-6 of the image's base to be clear
@@ -413,6 +430,11 @@ __global__ __launch_bounds__(2 * QG, 1) void k_xcorr_lag14q(XcorrArgs a, const f
     // A workgroup that gets its CU late (a collective's kernel, K0 or another process is resident there) then simply takes
     // fewer rows; with a fixed share per workgroup it would run its whole share after everybody else had finished.
     int item = g * (int)gridDim.x + (int)blockIdx.x;
+    c2 wc0[32], wc1[32];      // CARRY: the column chains of tid and tid + QG, from one row's last pass to the next row's first
+    if constexpr (CARRY) {
+        q_tw_load(wc0, twA, TWA_STRIDE, tid);
+        q_tw_load(wc1, twA, TWA_STRIDE, tid + QG);
+    }
     for (int k = 0;; ++k) {
         // opaque per iteration: otherwise every LDS / table offset derived from the two virtual thread ids is hoisted out
         // of the row loop and ~40 registers' worth of them live (spilled) across it
@@ -433,8 +455,8 @@ __global__ __launch_bounds__(2 * QG, 1) void k_xcorr_lag14q(XcorrArgs a, const f
         c2 wB[32];
         {
             c2 v[32], v2[32];
-            q_p0_compute(v, src, twA, a.xor80, vt0);      // no LDS yet: both halves run beside the other group's middle section
-            q_p0_compute(v2, src, twA, a.xor80, vt1);
+            q_p0_compute<CARRY>(v, src, twA, a.xor80, vt0, wc0);      // no LDS yet: both halves run beside the other group's middle section
+            q_p0_compute<CARRY>(v2, src, twA, a.xor80, vt1, wc1);
             {
                 // P1 / P1' twiddles: from the workgroup's table (no chain per row), outside the ownership window
                 // one opaque LDS pointer per row (the table lies beyond the offset field when addressed from the image's base),
@@ -480,8 +502,13 @@ __global__ __launch_bounds__(2 * QG, 1) void k_xcorr_lag14q(XcorrArgs a, const f
             __builtin_amdgcn_s_setprio(0);
             int vb0 = tid, vb1 = tid + QG;               // opaque again: the column-twiddle addresses of the first pass would otherwise be kept (spilled) for this one
             asm volatile("" : "+v"(vb0), "+v"(vb1));
-            q_p0i_compute(m0, v, twA, vb0);
-            q_p0i_compute(m1, v2, twA, vb1);
+            if constexpr (CARRY) {                       // vt1 first: the next row's first pass takes vt0's chain first
+                q_p0i_compute<true>(m1, v2, twA, vb1, wc1);
+                q_p0i_compute<true>(m0, v, twA, vb0, wc0);
+            } else {
+                q_p0i_compute<false>(m0, v, twA, vb0, wc0);
+                q_p0i_compute<false>(m1, v2, twA, vb1, wc1);
+            }
         }
         // ---- argmax without a group barrier ------------------------------------------------------------------------------------
         // Each wave reduces its own 64 x 64 magnitudes to a candidate -- maximum VALUE first (v_max3, six DPP steps), then the first
@@ -560,6 +587,20 @@ __global__ __launch_bounds__(2 * QG, 1) void k_xcorr_lag14q(XcorrArgs a, const f
     if (threadIdx.x == QG && errflag) {
         if (__hip_atomic_load(&sy->err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) atomicAdd(errflag, 1);
     }
+}
+// plain kernels, not instantiations of a template kernel: the static tables (tools/k1_isa_count.py) find them by these names
+__global__ __launch_bounds__(2 * QG, 1) void k_xcorr_lag14q(XcorrArgs a, const float2 *__restrict__ twA_, const float2 *__restrict__ twB_,
+                                                           int row_count, int *__restrict__ errflag, unsigned int *__restrict__ work,
+                                                           unsigned int work_base, int spin_limit)
+{
+    q_xcorr_lag14_body<false>(a, twA_, twB_, row_count, errflag, work, work_base, spin_limit);
+}
+// the same with the column chains carried from row to row (CRSDR_K1_VARIANT=r)
+__global__ __launch_bounds__(2 * QG, 1) void k_xcorr_lag14r(XcorrArgs a, const float2 *__restrict__ twA_, const float2 *__restrict__ twB_,
+                                                           int row_count, int *__restrict__ errflag, unsigned int *__restrict__ work,
+                                                           unsigned int work_base, int spin_limit)
+{
+    q_xcorr_lag14_body<true>(a, twA_, twB_, row_count, errflag, work, work_base, spin_limit);
 }
 
 // ---- stage B of the long-block path (longblock.hpp) on the same two-lines-per-CU structure -----------------------------

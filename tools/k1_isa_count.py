@@ -4,7 +4,7 @@
     python3 tools/k1_isa_count.py [--asm FILE.s] [--pattern REGEX] [--loops] [--hazards]
 
 Compiles coherent-rtlsdr_amd/csrc/crsdr.hip to device assembly with the Makefile's flags (or reads FILE.s) and prints,
-per kernel whose name matches REGEX (default: K0 and the two B = 16384 K1 kernels), the number of vector ALU
+per kernel whose name matches REGEX (default: K0 and the three B = 16384 K1 kernels), the number of vector ALU
 instructions in its body, how many of them are packed fp32 (v_pk_add / v_pk_mul / v_pk_fma), and the VGPR / SGPR /
 scratch figures of the code object's metadata.  The counts are static (instructions in the code, not executed ones):
 k_xcorr_lag14q holds one row pair's worth of straight-line code, so its count is per row pair.
@@ -186,7 +186,7 @@ def table(txt, pattern, loops=False):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--asm", help="read this device assembly instead of compiling")
-    ap.add_argument("--pattern", default=r"k_xcorr_lag14[pq]|k_ref_spectrum14p")
+    ap.add_argument("--pattern", default=r"k_xcorr_lag14[pqr]|k_ref_spectrum14p")
     ap.add_argument("--hazards", action="store_true",
                     help="list unpadded packed-result and compare-mask reads in every kernel; exit status 1 if any")
     ap.add_argument("--loops", action="store_true",
