@@ -113,7 +113,69 @@ def full_positions(L):
     return np.arange(1, 2 * L)
 
 
+def sweep_batches(L, n):
+    """Every idx 1 .. B - 1 as submits of n signal rows per block: [(q, [ps of submit 0, ps of submit 1, ...])] for the two reference
+    positions, each a cut of its L positions into ceil(L / n) slices (a short last slice is padded by repeating its own entries)."""
+    out = []
+    for q, ps in zip(ref_positions(L), split_by_reference(L, full_positions(L))):
+        assert ps.size == L
+        out.append((q, [np.resize(ps[s:s + n], n) for s in range(0, L, n)]))
+    return out
+
+
+def gather_by_idx(L, order, res):
+    """The rows of a run put in order of their peak index.  order: [(q, ps)] of the fetched blocks in the order they were fetched,
+    res: lag, mag, frac [len(order)][1 + len(ps)] (pulse_run of test_gpu_peak.py).  Returns lag, mag, frac [B - 1] for idx 1 .. B - 1
+    (idx = L: the q = 0 row), lag_L, mag_L, frac_L [1] (idx = L under q = L - 1), and reached [2][B]: how many rows put their peak
+    on an idx under q = 0 / q = L - 1."""
+    B = 2 * L
+    got = {k: np.zeros(B, dtype=np.asarray(res[k]).dtype) for k in ("lag", "mag", "frac")}
+    at_L = {k: np.zeros(1, dtype=np.asarray(res[k]).dtype) for k in ("lag", "mag", "frac")}
+    reached = np.zeros((2, B), dtype=np.int64)
+    for t, (q, ps) in enumerate(order):
+        idx = L + np.asarray(ps, dtype=np.int64) - q
+        first = q == 0
+        np.add.at(reached[0 if first else 1], idx, 1)
+        for k in got:
+            vals = np.asarray(res[k][t])[1:]
+            keep = np.ones(idx.size, dtype=bool) if first else idx != L
+            got[k][idx[keep]] = vals[keep]
+            if not first and np.any(~keep):
+                at_L[k][0] = vals[~keep][0]
+    out = {k: v[1:] for k, v in got.items()}
+    out.update({k + "_L": v for k, v in at_L.items()})
+    out["reached"] = reached
+    return out
+
+
+def sweep_is_complete(L, reached):
+    """Failures (strings) unless the union of the indices reached is exactly {1 .. B - 1} and idx = L was reached under both references."""
+    B = 2 * L
+    union = np.flatnonzero(reached.sum(axis=0))
+    fails = []
+    if not np.array_equal(union, np.arange(1, B)):
+        missing = np.setdiff1d(np.arange(1, B), union)
+        fails.append(f"the sweep reached {union.size} of {B - 1} indices; missing {missing[:16].tolist()}, beyond 1 .. B-1: {np.setdiff1d(union, np.arange(1, B)).tolist()}")
+    if not (reached[0, L] >= 1 and reached[1, L] >= 1):
+        fails.append(f"idx = L reached {reached[0, L]} times under q = 0 and {reached[1, L]} times under q = L - 1")
+    if np.any(reached[0, :L]) or np.any(reached[1, L + 1:]):
+        fails.append("a reference position reached an index outside its half")
+    return fails
+
+
+def probe_positions(log2B, seeded=64, seed=41):
+    """The indices at which test_peak_cases_model.py proves the closed form for the full sweeps of B = 16384 and 2^15: the ends, the
+    centre and `seeded` more, drawn from all of 1 .. B - 1 (most of them no designed position of k1_positions / long_positions)."""
+    B = 1 << log2B
+    L = B // 2
+    return np.unique(np.concatenate([[1, 2, B - 2, B - 1, L - 1, L, L + 1], np.random.default_rng(seed + log2B).integers(1, B, size=seeded)]))
+
+
 K1_SEEDED, LONG_SEEDED, LONG_MAX_ROWS = 256, 64, 128
+K1_SWEEP_ROWS = 2048          # signal rows per block of a submit of the B = 16384 sweep (two blocks: 67 MB of input, as B = 8192's full sweep)
+# B = 2^15: 7 submits per reference position.  The plan cuts a block's rows into chunks of 1600 (400 MB of cf32 work area); a chunk
+# takes the two-line stage B from 512 rows on (1024 lines).  2048 rows would leave a last chunk of 448; 2341 = ceil(16384 / 7) leaves 741.
+LONG_SWEEP_ROWS = 2341
 
 
 def k1_positions(L=8192, seeded=K1_SEEDED, seed=14):

@@ -536,7 +536,8 @@ def test_device_input_and_bound_packet_alignments(b, synth, B):
 
 
 def test_k1_variants_agree(tmp_path):
-    # CRSDR_K1_VARIANT: packed (xcorr14p.hpp) and the two-row kernel q (xcorr14q.hpp; "auto", the default, picks by launch size)
+    # CRSDR_K1_VARIANT: packed (xcorr14p.hpp), the two-row kernel q and its carried-chain form r (xcorr14q.hpp; "auto", the default,
+    # takes r for launches of >= 12 rows per CU and packed below; q runs only when forced)
     # run the same passes with the same arithmetic: every output agrees bit for bit.  (The two-row kernel's argmax -- per-wave
     # candidates, an edge table, the last wave to arrive finishes -- against the packed kernel's barrier-and-atomicMin form: the
     # first maximum, its parabolic neighbours across wave edges and the lag-mask / skip path included.)  The variant is chosen
@@ -572,7 +573,7 @@ def test_k1_variants_agree(tmp_path):
     res = {}
     # "*_nofold" (CRSDR_K1_FOLD=0): the reference spectra from k_ref_spectrum14p on the aux stream instead of from the launch's own
     # first work items -- the same arithmetic in another place
-    for variant in ("packed", "q", "auto", "packed_nofold"):
+    for variant in ("packed", "q", "r", "auto", "packed_nofold"):
         out = tmp_path / f"{variant}.npz"
         env = dict(os.environ, CRSDR_K1_VARIANT=variant.split("_")[0], CRSDR_K1_FOLD="0" if variant.endswith("_nofold") else "1")
         r = subprocess.run([sys.executable, "-c", code, str(out)], env=env, capture_output=True, text=True, timeout=300)
@@ -584,8 +585,11 @@ def test_k1_variants_agree(tmp_path):
     for key in ("lag", "mag", "frac", "packet"):
         # q: the packed passes run by one persistent workgroup per CU, two rows in opposite phases (xcorr14q.hpp): identical bits
         assert np.array_equal(res["packed"][key].view(np.uint8), res["q"][key].view(np.uint8)), ("q", key)
-    for key in ("lag2", "mag2", "frac2"):      # 3200 items (>= 12 per CU): "auto" takes the two-row kernel here as well
+        # r: q with the column twiddle chains carried from row to row (k_xcorr_lag14r), a compilation of its own
+        assert np.array_equal(res["packed"][key].view(np.uint8), res["r"][key].view(np.uint8)), ("r", key)
+    for key in ("lag2", "mag2", "frac2"):      # 3200 items (>= 12 per CU): "auto" takes the two-row kernel r here by itself
         assert np.array_equal(res["packed"][key].view(np.uint8), res["q"][key].view(np.uint8)), ("q", key)
+        assert np.array_equal(res["packed"][key].view(np.uint8), res["r"][key].view(np.uint8)), ("r", key)
         assert np.array_equal(res["packed"][key].view(np.uint8), res["auto"][key].view(np.uint8)), ("auto", key)
     assert np.array_equal(res["q"]["lag2"][0, 1:], res["q"]["d2"])
 
