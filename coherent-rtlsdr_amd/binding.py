@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "crsdr_caf_create", "crsdr_caf_destroy", "crsdr_caf_submit", "crsdr_caf_submit_plan", "crsdr_caf_fetch",
     "crsdr_caf_device_buffers", "crsdr_caf_last_submit", "crsdr_ambiguity",
     "crsdr_caf_set_cfar", "crsdr_caf_fetch_cfar", "crsdr_caf_cfar_device_buffers", "crsdr_cfar", "crsdr_cfar_alpha",
+    "crsdr_caf_set_cfar_estimator", "crsdr_cfar_est", "crsdr_cfar_alpha_est",
     "crsdr_caf_set_cancel", "crsdr_caf_fetch_cancel", "crsdr_caf_cancel_device_buffers", "crsdr_ambiguity_cancel",
     "crsdr_caf_set_bearing", "crsdr_caf_fetch_bearing", "crsdr_caf_bearing_device_buffers", "crsdr_bearing",
     "crsdr_caf_set_beams", "crsdr_caf_fetch_beams", "crsdr_caf_beams_device_buffers", "crsdr_beam_maps", "crsdr_beam_fuse", "crsdr_caf_beam_steer",
@@ -127,6 +128,16 @@ class CfarDesc(C.Structure):
     training cells a detection needs, and K detections kept per map."""
     _fields_ = [("gd", C.c_int32), ("gr", C.c_int32), ("td", C.c_int32), ("tr", C.c_int32), ("alpha", C.c_float), ("min_train", C.c_int32),
                 ("max_det", C.c_int32)]
+
+
+CFAR_CA, CFAR_GO, CFAR_SO, CFAR_OS = 0, 1, 2, 3
+CFAR_AXIS_LAG, CFAR_AXIS_DOPPLER = 0, 1
+
+
+class CfarEstDesc(C.Structure):
+    """crsdr_cfar_est_desc: the noise estimate (CFAR_CA, _GO, _SO, _OS), the axis that GO and SO split the training set over, the rank
+    of OS among the Nfull cells of a whole window."""
+    _fields_ = [("estimator", C.c_int32), ("axis", C.c_int32), ("rank", C.c_int32)]
 
 
 class CancelDesc(C.Structure):
@@ -316,6 +327,10 @@ def lib():
         L.crsdr_caf_cfar_device_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.crsdr_cfar.argtypes = [f32p, i32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CfarDesc), C.c_int]
         L.crsdr_cfar_alpha.argtypes = [C.c_double, C.c_int, f32p]
+    if hasattr(L, "crsdr_cfar_est"):                 # (likewise: an older build knows cell averaging alone)
+        L.crsdr_caf_set_cfar_estimator.argtypes = [vp, C.POINTER(CfarEstDesc)]
+        L.crsdr_cfar_est.argtypes = [f32p, i32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CfarDesc), C.POINTER(CfarEstDesc), C.c_int]
+        L.crsdr_cfar_alpha_est.argtypes = [C.c_double, C.c_int, C.POINTER(CfarEstDesc), f32p]
     if hasattr(L, "crsdr_ambiguity_cancel"):         # (likewise: an older build has no canceller)
         L.crsdr_caf_set_cancel.argtypes = [vp, C.POINTER(CancelDesc)]
         L.crsdr_caf_fetch_cancel.argtypes = [vp, f32p, f32p]
@@ -745,6 +760,37 @@ def cfar_device(det_ptr: int, count_ptr: int, src_ptr: int, comps, nd, R, guard,
     cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
     _check(lib().crsdr_cfar(cast(det_ptr, C.c_float), cast(count_ptr, C.c_int32), cast(src_ptr, C.c_float), int(comps), int(nd), int(R), int(guard), C.byref(desc),
                             MEM_DEVICE))
+
+
+def cfar_est_desc(estimator=CFAR_CA, axis=CFAR_AXIS_LAG, rank=0):
+    return CfarEstDesc(int(estimator), int(axis), int(rank))
+
+
+def cfar_alpha_est(pfa, ntrain, est):
+    """crsdr_cfar_alpha_est: the alpha of a false-alarm probability pfa under exponential noise, from the estimator's exact equation.
+    ntrain: the cells of one half (GO, SO) or of the whole training set (OS, CA)."""
+    a = C.c_float(0.0)
+    _check(lib().crsdr_cfar_alpha_est(float(pfa), int(ntrain), None if est is None else C.byref(est), C.byref(a)))
+    return np.float32(a.value)
+
+
+def cfar_est(src, guard, desc, est):
+    """crsdr_cfar_est on ONE map: cfar() under the estimator est (None: cell averaging).  The engine's detector under
+    Caf.set_cfar_estimator on one map, bit for bit."""
+    comps = 2 if np.iscomplexobj(src) else 1
+    a = np.ascontiguousarray(src, dtype=np.complex64 if comps == 2 else np.float32)
+    nd, R = a.shape
+    det, count = np.zeros((desc.max_det, 8), dtype=np.float32), np.zeros(1, dtype=np.int32)
+    _check(lib().crsdr_cfar_est(_p(det, C.c_float), _p(count, C.c_int32), _p(a.view(np.float32), C.c_float), comps, nd, R, int(guard), C.byref(desc),
+                                None if est is None else C.byref(est), MEM_HOST))
+    return det, int(count[0])
+
+
+def cfar_est_device(det_ptr: int, count_ptr: int, src_ptr: int, comps, nd, R, guard, desc, est):
+    """crsdr_cfar_est with CRSDR_MEM_DEVICE: every pointer on the device."""
+    cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
+    _check(lib().crsdr_cfar_est(cast(det_ptr, C.c_float), cast(count_ptr, C.c_int32), cast(src_ptr, C.c_float), int(comps), int(nd), int(R), int(guard), C.byref(desc),
+                                None if est is None else C.byref(est), MEM_DEVICE))
 
 
 def bearing_desc(mx, my, d, ncx=100, ncy=100, mode=BEARING_CONVENTIONAL, loading=1e-2, levels=0, flags=0):
@@ -1572,6 +1618,11 @@ class Caf:
         """crsdr_caf_set_cfar: the CFAR detector behind every submit (None: off).  Between submits."""
         _check(lib().crsdr_caf_set_cfar(self._h, None if desc is None else C.byref(desc)))
         self.max_det = 0 if desc is None else int(desc.max_det)
+
+    def set_cfar_estimator(self, est: "CfarEstDesc | None"):
+        """crsdr_caf_set_cfar_estimator: the noise estimate of the detector that is on (None: cell averaging).  Between submits; every
+        set_cfar puts it back to cell averaging."""
+        _check(lib().crsdr_caf_set_cfar_estimator(self._h, None if est is None else C.byref(est)))
 
     def fetch_cfar(self, det=True, count=True, snap=True) -> dict:
         """Waits for the last submit.  det [nest][nrows + 1][K][8], count [nest][nrows + 1] int32, snap [nest][K][nrows] complex64."""

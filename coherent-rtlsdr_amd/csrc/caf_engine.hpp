@@ -239,6 +239,8 @@ static int caf_enqueue(CafRun &r, const int8_t *packets, size_t packet_stride, s
                    peak);
 }
 
+constexpr int kCfarAlphaMaxTrain = 65536;          // crsdr_cfar_alpha_est: the sums run over ntrain terms
+
 // every limit of the detector of section (w), for crsdr_caf_set_cfar and crsdr_cfar
 static int cfar_args_ok(const char *who, int nd, const crsdr_cfar_desc *d, cfar::Params *prm)
 {
@@ -256,12 +258,32 @@ static int cfar_args_ok(const char *who, int nd, const crsdr_cfar_desc *d, cfar:
     }
 }
 
-// the detector's two launches, for the object and for crsdr_cfar: the same kernels on the same arguments, so the same bits
+// the estimator's limits, for crsdr_caf_set_cfar_estimator and crsdr_cfar_est; prm: the detector's, whose window gives Nfull.  NULL or
+// cell averaging leaves prm as cfar_args_ok made it
+static int cfar_est_ok(const char *who, const crsdr_cfar_est_desc *e, cfar::Params *prm)
+{
+    if (!e) return CRSDR_OK;
+    cfar::Params t = *prm;
+    t.est = e->estimator;
+    t.axis = t.est == cfar::EST_GO || t.est == cfar::EST_SO ? e->axis : 0;
+    t.rank = t.est == cfar::EST_OS ? e->rank : 0;
+    switch (cfar::bad_estimator(t)) {
+    case 0: *prm = t; return CRSDR_OK;
+    case 1: return fail(CRSDR_EINVAL, "%s: estimator = %d (0 cell averaging, 1 greatest-of, 2 smallest-of, 3 ordered statistic)", who, e->estimator);
+    case 2: return fail(CRSDR_EINVAL, "%s: axis = %d (0 lag, 1 Doppler)", who, e->axis);
+    default: return fail(CRSDR_EINVAL, "%s: rank = %d (1..Nfull = %d)", who, e->rank, cfar::full_count(t));
+    }
+}
+
+// the detector's two launches, for the object and for crsdr_cfar: the same kernels on the same arguments, so the same bits.  The
+// estimator picks the tiles' kernel; the merge is the same behind each
 static int cfar_enqueue(CafRun &r, const float2 *chi, const float *map, int nest, int nrows, int entries, int nd, int R, int guard, const cfar::Params &prm, int keep,
                         cfar::Cand *slots, int32_t *tcount, float *det, int32_t *count, float *snap)
 {
     const int tiles = cfar::tiles_of(nd, R);
-    const int rc = caf_run(r, cfar::k_caf_cfar, dim3((unsigned)(entries * tiles), (unsigned)nest), dim3(cfar::THREADS), 0, chi, map, nrows, entries, nd, R, guard, prm, keep,
+    const auto kern = prm.est == cfar::EST_OS ? cfar::k_caf_cfar_os : prm.est == cfar::EST_GO ? cfar::k_caf_cfar<cfar::EST_GO> :
+                      prm.est == cfar::EST_SO ? cfar::k_caf_cfar<cfar::EST_SO> : cfar::k_caf_cfar<cfar::EST_CA>;
+    const int rc = caf_run(r, kern, dim3((unsigned)(entries * tiles), (unsigned)nest), dim3(cfar::THREADS), 0, chi, map, nrows, entries, nd, R, guard, prm, keep,
                            slots, tcount);
     if (rc) return rc;
     return caf_run(r, cfar::k_caf_cfar_merge, dim3((unsigned)entries, (unsigned)nest), dim3(cfar::THREADS), 0, chi, map, nrows, entries, nd, R, guard, prm, keep,
@@ -392,11 +414,15 @@ static int caf_clear(crsdr_caf *q, Feature &f, unsigned ran_bit)
 // Who must be off before whom, who must be on before whom: every rule of the setters, each feature's in the order they are asked.
 // must_be_on false: `feature` is not changed, set or turned off, while `other` is on, which works on its buffers and parameters (asked
 // ahead of the descriptor's limits).  true: `feature` is not set while `other` is off (asked behind them, and not to turn it off).
-enum { kCafCfar, kCafBearing, kCafBeams, kCafBeamLists, kCafTrack, kCafTrackFused };
+enum { kCafCfar, kCafBearing, kCafBeams, kCafBeamLists, kCafTrack, kCafTrackFused, kCafCfarEst };
 static const struct CafRule { int feature; bool must_be_on; int other; const char *refusal; } kCafRules[] = {
     {kCafCfar, false, kCafTrack, "caf_set_cfar: the tracker is on (crsdr_caf_set_track): its measurements are this detector's lists; turn it off first"},
     {kCafCfar, false, kCafBeams, "caf_set_cfar: beams are on (crsdr_caf_set_beams): whether they are detected on, and the lists' sizes, are this detector's; turn them off first"},
     {kCafCfar, false, kCafBearing, "caf_set_cfar: bearings are on (crsdr_caf_set_bearing): their buffers and training set are this detector's; turn them off first"},
+    {kCafCfarEst, false, kCafTrack, "caf_set_cfar_estimator: the tracker is on (crsdr_caf_set_track): its measurements are this detector's lists; turn it off first"},
+    {kCafCfarEst, false, kCafBeams, "caf_set_cfar_estimator: beams are on (crsdr_caf_set_beams): their lists are this detector's; turn them off first"},
+    {kCafCfarEst, false, kCafBearing, "caf_set_cfar_estimator: bearings are on (crsdr_caf_set_bearing): they follow this detector's lists; turn them off first"},
+    {kCafCfarEst, true, kCafCfar, "caf_set_cfar_estimator: no detector set (crsdr_caf_set_cfar): the estimator belongs to its descriptor"},
     {kCafBearing, false, kCafTrack, "caf_set_bearing: the tracker is on (crsdr_caf_set_track): its auxiliary pairs are these bearings; turn it off first"},
     {kCafBearing, true, kCafCfar, "caf_set_bearing: no detector set (crsdr_caf_set_cfar): there are no detections to take a bearing of"},
     {kCafBeams, false, kCafTrack, "caf_set_beams: the tracker is on (crsdr_caf_set_track): the fused list may be its source; turn it off first"},
@@ -597,6 +623,26 @@ extern "C" int crsdr_caf_set_cfar(crsdr_caf *q, const crsdr_cfar_desc *desc)
     return CRSDR_OK;
 }
 
+// The estimator of the descriptor last set.  Nothing is allocated: the lists' sizes are the descriptor's.
+extern "C" int crsdr_caf_set_cfar_estimator(crsdr_caf *q, const crsdr_cfar_est_desc *desc)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_set_cfar_estimator: NULL caf");
+    { const int rc = caf_rules(q, kCafCfarEst, false); if (rc) return rc; }
+    // (the estimator and the axis need no detector to be judged; the rank needs its window, so the state is asked between them)
+    if (desc && (desc->estimator < cfar::EST_CA || desc->estimator > cfar::EST_OS))
+        return fail(CRSDR_EINVAL, "caf_set_cfar_estimator: estimator = %d (0 cell averaging, 1 greatest-of, 2 smallest-of, 3 ordered statistic)", desc->estimator);
+    if (desc && (desc->estimator == cfar::EST_GO || desc->estimator == cfar::EST_SO) && (desc->axis < 0 || desc->axis > 1))
+        return fail(CRSDR_EINVAL, "caf_set_cfar_estimator: axis = %d (0 lag, 1 Doppler)", desc->axis);
+    { const int rc = caf_rules(q, kCafCfarEst, true); if (rc) return rc; }
+    cfar::Params prm = q->cf.prm;
+    prm.est = cfar::EST_CA; prm.axis = 0; prm.rank = 0;
+    { const int rc = cfar_est_ok("caf_set_cfar_estimator", desc, &prm); if (rc) return rc; }
+    { const int rc = caf_quiesce(q); if (rc) return rc; }
+    q->cf.prm = prm;
+    q->last.ran &= ~kCafRanCfar;
+    return CRSDR_OK;
+}
+
 extern "C" int crsdr_caf_fetch_cfar(crsdr_caf *q, float *det, int32_t *count, float *snap)
 {
     if (!q) return fail(CRSDR_EINVAL, "caf_fetch_cfar: NULL caf");
@@ -626,13 +672,58 @@ extern "C" int crsdr_cfar_alpha(double pfa, int ntrain, float *alpha)
     return CRSDR_OK;
 }
 
-extern "C" int crsdr_cfar(float *det, int32_t *count, const float *src, int comps, int nd, int R, int guard, const crsdr_cfar_desc *desc, int mem_kind)
+// The false-alarm probability of a cell under exponential noise of mean 1 in every cell, at threshold factor alpha (section (w)):
+//   SO   2 (2 + T)^-n sum_{i < n} C(n - 1 + i, i) (2 + T)^-i,  T = alpha / n, n the cells of a half; the terms through their logarithms
+//   GO   2 (1 + T)^-n - P_SO
+//   OS   prod_{i < rank} (N - i) / (N - i + alpha)
+static double cfar_pfa(int est, int n, int rank, double alpha)
 {
-    if (!src || !desc || (!det && !count)) return fail(CRSDR_EINVAL, "cfar: need src, a descriptor and at least one of det, count");
-    if (comps != 1 && comps != 2) return fail(CRSDR_EINVAL, "cfar: comps = %d (1: a map, 2: a chi)", comps);
-    { const int rc_ = caf_shape_ok("cfar", nd, R, guard, 0, 2); if (rc_) return rc_; }
+    if (est == cfar::EST_OS) {
+        double p = 1.0;
+        for (int i = 0; i < rank; ++i) p *= (double)(n - i) / ((double)(n - i) + alpha);
+        return p;
+    }
+    const double T = alpha / (double)n, lx = -log(2.0 + T);
+    double so = 0.0, lc = 0.0;
+    for (int i = 0; i < n; ++i) {
+        if (i) lc += log((double)(n - 1 + i) / (double)i);
+        so += exp(lc + (double)(n + i) * lx);
+    }
+    so *= 2.0;
+    return est == cfar::EST_SO ? so : 2.0 * exp(-(double)n * log(1.0 + T)) - so;
+}
+
+extern "C" int crsdr_cfar_alpha_est(double pfa, int ntrain, const crsdr_cfar_est_desc *est, float *alpha)
+{
+    if (!est || est->estimator == cfar::EST_CA) return crsdr_cfar_alpha(pfa, ntrain, alpha);
+    if (!alpha) return fail(CRSDR_EINVAL, "cfar_alpha_est: NULL alpha");
+    if (!(pfa > 0.0 && pfa < 1.0)) return fail(CRSDR_EINVAL, "cfar_alpha_est: pfa = %g (inside (0, 1))", pfa);
+    if (est->estimator < cfar::EST_CA || est->estimator > cfar::EST_OS) return fail(CRSDR_EINVAL, "cfar_alpha_est: estimator = %d (0..3)", est->estimator);
+    if (ntrain < 1 || ntrain > kCfarAlphaMaxTrain) return fail(CRSDR_EINVAL, "cfar_alpha_est: ntrain = %d (1..%d)", ntrain, kCfarAlphaMaxTrain);
+    if (est->estimator == cfar::EST_OS && (est->rank < 1 || est->rank > ntrain)) return fail(CRSDR_EINVAL, "cfar_alpha_est: rank = %d (1..ntrain = %d)", est->rank, ntrain);
+    // the probability falls as alpha grows, from 1 at alpha = 0: a bracket by doubling, then bisection down to neighbouring doubles
+    double lo = 0.0, hi = 1.0;
+    while (cfar_pfa(est->estimator, ntrain, est->rank, hi) > pfa && hi < 1e300) hi *= 2.0;
+    for (int it = 0; it < 2200; ++it) {
+        const double mid = 0.5 * (lo + hi);
+        if (!(mid > lo && mid < hi)) break;
+        if (cfar_pfa(est->estimator, ntrain, est->rank, mid) > pfa) lo = mid; else hi = mid;
+    }
+    *alpha = (float)hi;
+    return CRSDR_OK;
+}
+
+// crsdr_cfar and crsdr_cfar_est: est NULL is cell averaging
+static int cfar_op(const char *who, float *det, int32_t *count, const float *src, int comps, int nd, int R, int guard, const crsdr_cfar_desc *desc,
+                   const crsdr_cfar_est_desc *est, int mem_kind)
+{
+    if (!src || !desc || (!det && !count)) return fail(CRSDR_EINVAL, "%s: need src, a descriptor and at least one of det, count", who);
+    if (comps != 1 && comps != 2) return fail(CRSDR_EINVAL, "%s: comps = %d (1: a map, 2: a chi)", who, comps);
+    { const int rc_ = caf_shape_ok(who, nd, R, guard, 0, 2); if (rc_) return rc_; }
     cfar::Params prm{};
-    { const int rc_ = cfar_args_ok("cfar", nd, desc, &prm); if (rc_) return rc_; }
+    { const int rc_ = cfar_args_ok(who, nd, desc, &prm); if (rc_) return rc_; }
+    { const int rc_ = cfar_est_ok(who, est, &prm); if (rc_) return rc_; }
+    if (mem_kind != CRSDR_MEM_HOST && mem_kind != CRSDR_MEM_DEVICE) return fail(CRSDR_EINVAL, "%s: mem_kind = %d", who, mem_kind);
     OP_PROLOGUE_MEM("cfar", mem_kind);
     const size_t cells = (size_t)nd * (size_t)R, K = (size_t)prm.max_det, tiles = (size_t)cfar::tiles_of(nd, R);
     const size_t sb = sizeof(float) * cells * (size_t)comps, db = sizeof(float) * K * 8, nb = sizeof(int32_t);
@@ -642,7 +733,7 @@ extern "C" int crsdr_cfar(float *det, int32_t *count, const float *src, int comp
     float *d_d = (float *)st.out(1, det, db, 4);
     int32_t *d_n = (int32_t *)st.out(2, count, nb, 4);
     if (st.rc) return st.rc;
-    if (st.misaligned) return fail(CRSDR_EINVAL, "cfar: device det, count and a map 4-byte, a chi 8-byte aligned");
+    if (st.misaligned) return fail(CRSDR_EINVAL, "%s: device det, count and a map 4-byte, a chi 8-byte aligned", who);
     if (st.spare(1, d_d, db) || st.spare(2, d_n, nb)) return st.rc;
     OP_RESERVE(3, sizeof(cfar::Cand) * tiles * (size_t)keep);
     OP_RESERVE(4, sizeof(int32_t) * tiles);
@@ -652,6 +743,17 @@ extern "C" int crsdr_cfar(float *det, int32_t *count, const float *src, int comp
     st.back(det, d_d, db);
     st.back(count, d_n, nb);
     return st.finish();
+}
+
+extern "C" int crsdr_cfar(float *det, int32_t *count, const float *src, int comps, int nd, int R, int guard, const crsdr_cfar_desc *desc, int mem_kind)
+{
+    return cfar_op("cfar", det, count, src, comps, nd, R, guard, desc, nullptr, mem_kind);
+}
+
+extern "C" int crsdr_cfar_est(float *det, int32_t *count, const float *src, int comps, int nd, int R, int guard, const crsdr_cfar_desc *desc,
+                              const crsdr_cfar_est_desc *est, int mem_kind)
+{
+    return cfar_op("cfar_est", det, count, src, comps, nd, R, guard, desc, est, mem_kind);
 }
 
 // ---- the bearings ----

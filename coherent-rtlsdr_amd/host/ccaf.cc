@@ -56,6 +56,13 @@ int batch::set_cfar(const crsdr_cfar_desc *desc)
     return rc;
 }
 
+int batch::set_cfar_estimator(const crsdr_cfar_est_desc *est)
+{
+    int rc = cf ? crsdr_caf_set_cfar_estimator(cf, est) : CRSDR_ESTATE;
+    if (rc && cf) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
 int batch::fetch_cfar(bool want_snap)
 {
     int nest = 0;

@@ -65,6 +65,9 @@ public:
     int fetch(bool want_chi = false, bool want_map = false);
     // the CFAR detector behind every later submit (crsdr_caf_set_cfar; NULL: off).  Between submits: it waits for the last one.
     int set_cfar(const crsdr_cfar_desc *desc);
+    // the noise estimate of the detector that is on (crsdr_caf_set_cfar_estimator; NULL: cell averaging).  Between submits, with the
+    // bearings, beams and tracker off; every set_cfar puts it back to cell averaging.
+    int set_cfar_estimator(const crsdr_cfar_est_desc *est);
     // waits, and fills count and det, and snap if asked for; CRSDR_ESTATE with the detector off
     int fetch_cfar(bool want_snap = true);
     int max_det() const { return kdet; }

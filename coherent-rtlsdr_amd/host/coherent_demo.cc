@@ -70,6 +70,8 @@ int main(int argc, char **argv)
     bool cfar_on = false;
     double cfar_db = 0.0;
     crsdr_cfar_desc cfar = {1, 1, 3, 4, 0.f, 1, 16};
+    bool cfar_est_on = false, cfar_axis_on = false;
+    crsdr_cfar_est_desc cfar_est = {CRSDR_CFAR_CA, 0, 0};
     bool cancel_on = false, bearing_on = false, beams_on = false;
     int beams_mx = 0, beams_my = 0, beams_nx = 0, beams_ny = 0;
     crsdr_caf_bearing_desc bearing = {0, 0, 100, 100, 0.5f, CRSDR_BEARING_CONVENTIONAL, 1e-2f, 0, 0u};
@@ -159,6 +161,24 @@ int main(int argc, char **argv)
             cfar.alpha = n == 1 || n == 5 ? (float)std::pow(10.0, cfar_db / 10.0) : -1.f;      // (refused below with the rest)
         }
         else if (a == "--max-det") val(cfar.max_det);
+        // with --cfar: the noise estimate (crsdr_caf_set_cfar_estimator) in place of the mean of all training cells: go, so -- the greater
+        // or smaller of the means of the window's two halves over lag, or over Doppler with --cfar-axis doppler -- or os[:RANK], the
+        // RANK-th smallest training cell (default: three quarters of the window's cells)
+        else if (a == "--cfar-est" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            cfar_est_on = true;
+            cfar_est.rank = 0;
+            if (v == "go") cfar_est.estimator = CRSDR_CFAR_GO;
+            else if (v == "so") cfar_est.estimator = CRSDR_CFAR_SO;
+            else if (v == "os") cfar_est.estimator = CRSDR_CFAR_OS;
+            else if (v.compare(0, 3, "os:") == 0 && std::sscanf(v.c_str() + 3, "%d", &cfar_est.rank) == 1 && cfar_est.rank > 0) cfar_est.estimator = CRSDR_CFAR_OS;
+            else cfar_est.estimator = -1;                                                    // (refused below)
+        }
+        else if (a == "--cfar-axis" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            cfar_axis_on = true;
+            cfar_est.axis = v == "lag" ? 0 : v == "doppler" ? 1 : -1;                        // (refused below)
+        }
         // with --caf: the least-squares canceller in front of the Doppler stage (crsdr_caf_set_cancel): the reference's first K delays, each
         // at -P .. P Doppler bins (default 0), projected out of every other row.  One line per line of the batch: the mean share of the
         // rows' power that stays, in dB.
@@ -245,6 +265,19 @@ int main(int argc, char **argv)
             servo_table = true;
             for (char *tok = std::strtok(argv[++i], ","); tok; tok = std::strtok(nullptr, ",")) table_lags.push_back(std::atof(tok));
         }
+    }
+    if (cfar_est_on || cfar_axis_on) {
+        // numbers only (no device): the limits are the library's own, asked of crsdr_caf_set_cfar_estimator behind --caf
+        if (!cfar_on) { std::printf("cfar: --cfar-est and --cfar-axis need --cfar: there is no detector to estimate the noise for\nDEMO FAILED\n"); return 1; }
+        const bool halves = cfar_est.estimator == CRSDR_CFAR_GO || cfar_est.estimator == CRSDR_CFAR_SO;
+        if (!cfar_est_on || cfar_est.estimator < 0 || cfar_est.axis < 0 || (cfar_axis_on && !halves)) {
+            std::printf("cfar: --cfar-est go|so|os[:RANK] [--cfar-axis lag|doppler] refused (the axis is greatest-of's and smallest-of's)\nDEMO FAILED\n");
+            return 1;
+        }
+        if (cfar_est.estimator == CRSDR_CFAR_OS && !cfar_est.rank)
+            cfar_est.rank = std::max(1, 3 * ((2 * (cfar.gd + cfar.td) + 1) * (2 * (cfar.gr + cfar.tr) + 1) - (2 * cfar.gd + 1) * (2 * cfar.gr + 1)) / 4);
+        std::printf("cfar: estimator %s axis %s rank %d\n", cfar_est.estimator == CRSDR_CFAR_GO ? "go" : cfar_est.estimator == CRSDR_CFAR_SO ? "so" : "os",
+                    halves ? (cfar_est.axis ? "doppler" : "lag") : "-", cfar_est.rank);
     }
     if (track_on) {
         // numbers only (no device): the tracker's limits are the library's own (crsdr_track_state_bytes checks them on the host)
@@ -593,6 +626,7 @@ int main(int argc, char **argv)
             if (caf_seg > 0) caf.reset(new ccaf::batch(1 + nsig, B, batch, caf_seg, caf_lags, caf_ref, sb_window, caf_guard, caf_frames));
             if (!caf || !caf->ok()) { std::printf("caf: --caf SEG:LAGS[:REF] [--caf-frames F] [--guard G] [--window rect|hann] refused\nDEMO FAILED\n"); return 1; }
             if (cfar_on && caf->set_cfar(&cfar)) { std::printf("cfar: --cfar SNR_DB[:GD:GR:TD:TR] [--max-det K] refused\nDEMO FAILED\n"); return 1; }
+            if (cfar_est_on && caf->set_cfar_estimator(&cfar_est)) { std::printf("cfar: --cfar-est go|so|os[:RANK] [--cfar-axis lag|doppler] refused\nDEMO FAILED\n"); return 1; }
             if (cancel_on && caf->set_cancel(&cancel)) { std::printf("cancel: --cancel K[:P] refused\nDEMO FAILED\n"); return 1; }
             if (bearing_on && !cfar_on) { std::printf("bearing: --bearing needs --cfar: there are no detections to take a bearing of\nDEMO FAILED\n"); return 1; }
             if (bearing_on && caf->set_bearing(&bearing)) {

@@ -1171,6 +1171,50 @@ int crsdr_cfar(float *det, int32_t *count, const float *src, int comps, int nd, 
  * set, train on fewer than ntrain cells and so run at a somewhat higher rate.  CRSDR_EINVAL for pfa outside (0, 1) or ntrain < 1. */
 int crsdr_cfar_alpha(double pfa, int ntrain, float *alpha);
 
+/* Estimators.  The mean of all training cells has two known failures: a strong cell inside a weaker target's window lifts the mean
+ * over it (masking), and where the floor steps the mean of the low side under-estimates the high side (clutter edges).  Three more
+ * estimates of the noise can be chosen.  P, S, guard, i, the training set, N, the 3 x 3 test, the order of the detections, det[8],
+ * count and snap are as above, and a detected cell still needs noise > 0 and P > t, t = (double)alpha * noise: only noise and ntrain
+ * change.  Nfull = (2 Hd + 1)(2 Hr + 1) - (2 gd + 1)(2 gr + 1).
+ *   CRSDR_CFAR_CA   cell averaging, as above, bit for bit.
+ *   CRSDR_CFAR_GO,  greatest-of and smallest-of.  axis 0 (lag) splits the training set into the cells with b < 0 and those with b > 0,
+ *   CRSDR_CFAR_SO   axis 1 (Doppler) into a < 0 and a > 0; cells on the centre line (b = 0, or a = 0) train neither half.  A half counts
+ *                   if and only if its size N_h >= min_train; its mean is Z_h / (double)N_h, Z_h formed by additions only.  noise is
+ *                   the larger (GO) or smaller (SO) mean over the halves that count, the lower half (b < 0, a < 0) on equal means,
+ *                   and ntrain that half's N_h.  No counting half, or a chosen mean that is not above 0 (SO beside an all-zero half):
+ *                   no detection.  GO holds its rate across a clutter edge; SO sees past an interferer on one side.
+ *   CRSDR_CFAR_OS   ordered statistic.  1 <= rank <= Nfull.  At a cell with N >= min_train, k = max(1, ceil(rank N / Nfull)) in
+ *                   integers and noise is the k-th smallest P of the training set: a value of the map, without rounding; ntrain = N.
+ *                   Only cells of the set take part: a cell outside the lags or outside S is absent, not a zero, and a cell of S
+ *                   whose P is 0 is present.  It survives several interferers (fewer than N - k of them).
+ * The estimator belongs to the descriptor last set: every crsdr_caf_set_cfar, on or off, puts it back to cell averaging. */
+enum { CRSDR_CFAR_CA = 0, CRSDR_CFAR_GO = 1, CRSDR_CFAR_SO = 2, CRSDR_CFAR_OS = 3 };
+typedef struct crsdr_cfar_est_desc {
+    int32_t estimator;        /* CRSDR_CFAR_* */
+    int32_t axis;             /* GO, SO: 0 splits over lag, 1 over Doppler; not read otherwise */
+    int32_t rank;             /* OS: 1..Nfull; not read otherwise */
+} crsdr_cfar_est_desc;
+
+/* Sets the estimator of the detector that is on (NULL: cell averaging), wherever its descriptor goes: the rows' maps, the array map
+ * and the beam maps' detector; the bearings' adaptive training set is the window's geometry and does not change.  Between submits
+ * only: it waits for the last one; what a fetch_cfar would have returned is gone.  It allocates nothing and a submit's launches stay
+ * as many.  CRSDR_ESTATE while bearings, beams or the tracker are on (turn them off first), and with no detector set.
+ * CRSDR_EINVAL, before a device is touched, for an estimator outside 0..3, an axis outside 0..1 (GO, SO) or a rank outside
+ * 1..Nfull (OS). */
+int crsdr_caf_set_cfar_estimator(crsdr_caf *caf, const crsdr_cfar_est_desc *est);
+
+/* crsdr_cfar under an estimator: est NULL or CRSDR_CFAR_CA is crsdr_cfar, bit for bit; otherwise the same limits on est as above. */
+int crsdr_cfar_est(float *det, int32_t *count, const float *src, int comps, int nd, int R, int guard, const crsdr_cfar_desc *desc,
+                   const crsdr_cfar_est_desc *est, int mem_kind);
+
+/* Host only: the alpha that gives a false-alarm probability pfa per cell under exponentially distributed noise power, from the exact
+ * equation of the estimator by bisection in fp64, rounded once to fp32.  est NULL or CA: crsdr_cfar_alpha.
+ *   GO, SO   ntrain is the cells per half n, T = alpha / n:  P_SO = 2 (2 + T)^-n sum_{i < n} C(n - 1 + i, i) (2 + T)^-i,
+ *            P_GO = 2 (1 + T)^-n - P_SO
+ *   OS       rank <= ntrain = N:  P_OS = prod_{i < rank} (N - i) / (N - i + alpha)
+ * CRSDR_EINVAL for pfa outside (0, 1), an estimator outside 0..3, ntrain outside 1..65536 (CA: below 1), a rank outside 1..ntrain. */
+int crsdr_cfar_alpha_est(double pfa, int ntrain, const crsdr_cfar_est_desc *est, float *alpha);
+
 /* Cancellation.  A surveillance row holds the illuminator's own signal, strong and at short delays, and its ambiguity function has a
  * noise-like floor about 1 / (nd Ls) below its peak in EVERY cell, which guard does not touch: an echo 40 dB down lies under it.  The
  * canceller (the extensive cancellation algorithm, ECA) projects the reference and its first delays, optionally shifted by a few

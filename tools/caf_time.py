@@ -17,6 +17,12 @@ with --cfar, on a second engine with the CFAR detector set (crsdr_caf_set_cfar: 
   get chi    the fetch of chi (pageable host memory, as Caf.fetch returns it) that the detection lists stand in for
   get cfar   the fetch of det + count + snap
 and the bytes of P the detector reads per submit (8 a cell of chi, 4 a cell of map), to set against its kernels' time from a profiler.
+with --cfar --estimator, on three further engines with the same detector under another noise estimate (crsdr_caf_set_cfar_estimator), each with
+the alpha of 1e-6 under its own estimate (crsdr_cfar_alpha_est):
+  cfar go    as caf+cfar under greatest-of over lag (42 cells a half)
+  cfar so    as caf+cfar under smallest-of over lag
+  cfar os    as caf+cfar under the ordered statistic of rank 67 of 90
+each against the same build's caf+cfar: the tiles' kernel is the only launch that differs.
 with --cancel K[:P], on a further engine with the canceller set (crsdr_caf_set_cancel: K delays of the reference at -P .. P Doppler bins):
   caf+cancel as caf with the canceller's five launches in the place of the rows' one, + a fetch of coef and cinfo as well; beside it the
              fp64 multiply-adds of the subtraction (n complex ones a cell) per second
@@ -78,13 +84,14 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-model", action="store_true", help="skip the numpy model on one line")
     ap.add_argument("--cfar", action="store_true", help="add the CFAR detector's variants")
+    ap.add_argument("--estimator", action="store_true", help="add the detector under greatest-of, smallest-of and the ordered statistic (with --cfar's)")
     ap.add_argument("--cancel", metavar="K[:P]", help="add the canceller's variant")
     ap.add_argument("--bearing", action="store_true", help="add the bearings' variants (with --cfar's)")
     ap.add_argument("--beams", type=int, default=0, metavar="NB", help="add the beam maps' variants: a lattice of NB beams (22 rows)")
     ap.add_argument("--track", action="store_true", help="add the tracker's variants (22 rows)")
     ap.add_argument("--json")
     a = ap.parse_args()
-    a.cfar = a.cfar or a.bearing
+    a.cfar = a.cfar or a.bearing or a.estimator
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import torch
@@ -130,6 +137,22 @@ def main():
         if a.cfar:
             cfd = b.Caf(nrows, B, SEG, lags, 0, b.WINDOW_HANN, GUARD, max_batch=T, frames=FRAMES)
             cfd.set_cfar(b.cfar_desc(alpha=b.cfar_alpha(1e-6, 90), gd=1, gr=1, td=3, tr=4, max_det=16))
+
+        ests = {}
+        if a.estimator:
+            for name, ed, n in (("cfar go", b.cfar_est_desc(b.CFAR_GO, b.CFAR_AXIS_LAG), 42), ("cfar so", b.cfar_est_desc(b.CFAR_SO, b.CFAR_AXIS_LAG), 42),
+                                ("cfar os", b.cfar_est_desc(b.CFAR_OS, rank=67), 90)):
+                e = b.Caf(nrows, B, SEG, lags, 0, b.WINDOW_HANN, GUARD, max_batch=T, frames=FRAMES)
+                e.set_cfar(b.cfar_desc(alpha=b.cfar_alpha_est(1e-6, n, ed), gd=1, gr=1, td=3, tr=4, max_det=16))
+                e.set_cfar_estimator(ed)
+                ests[name] = e
+
+        def caf_est(e):
+            def run(i):
+                e.submit(pk, plan.packet_stride, plan.matrix_offset, T)
+                e.fetch(chi=False, map=False)
+                e.fetch_cfar()
+            return run
 
         brg = {}
         if a.bearing and nrows == 22:
@@ -224,6 +247,8 @@ def main():
             variants["caf+cfar"] = lambda: _mean(caf_cfar, lambda: None, a.reps)
             variants["get chi"] = lambda: _mean(lambda i: cf.fetch(map=False, peak=False), lambda: None, a.reps)
             variants["get cfar"] = lambda: _mean(lambda i: cfd.fetch_cfar(), lambda: None, a.reps)
+        for name, e in ests.items():
+            variants[name] = lambda e=e: _mean(caf_est(e), lambda: None, a.reps)
         for name, e in brg.items():
             variants[name] = lambda e=e: _mean(caf_bearing(e), lambda: None, a.reps)
         if brg:
@@ -268,6 +293,8 @@ def main():
                 note = f"  ({8 * cells / (med * 1e-3) / 1e9:.1f} GB/s of chi stored, {macs / (med * 1e-3) / 1e12:.2f} T complex int8 MAC/s)"
             if k == "caf+cfar":
                 note = f"  (+{med - shape['ms']['caf']['median']:.3f} ms behind caf; the detector reads {(T // FRAMES) * nd * lags * (8 * nrows + 4) / 1e6:.1f} MB of P)"
+            if k in ests:
+                note = f"  ({med - shape['ms']['caf+cfar']['median']:+.3f} ms against caf+cfar)"
             if k == "caf+cancel":
                 note = f"  (+{med - shape['ms']['caf']['median']:.3f} ms behind caf; {basis} complex fp64 multiply-adds a cell, {basis * cells / (med * 1e-3) / 1e9:.1f} G/s over the submit)"
             if k in brg and k != "cfar low":
@@ -316,7 +343,7 @@ def main():
             cfd.close()
         if cfc:
             cfc.close()
-        for e in brg.values():
+        for e in list(ests.values()) + list(brg.values()):
             e.close()
         for e, _, _ in bms.values():
             e.close()
