@@ -57,7 +57,10 @@ ABI_SYMBOLS = [
     "crsdr_caf_set_bearing", "crsdr_caf_fetch_bearing", "crsdr_caf_bearing_device_buffers", "crsdr_bearing",
     "crsdr_caf_set_beams", "crsdr_caf_fetch_beams", "crsdr_caf_beams_device_buffers", "crsdr_beam_maps", "crsdr_beam_fuse", "crsdr_caf_beam_steer",
     "crsdr_caf_set_track", "crsdr_caf_track_reset", "crsdr_caf_fetch_track", "crsdr_caf_track_device_buffers", "crsdr_track_state_bytes", "crsdr_track",
+    "crsdr_caf_set_integrate", "crsdr_caf_integrate_reset", "crsdr_caf_fetch_integrate", "crsdr_caf_integrate_device_buffers",
+    "crsdr_map_integrate_state_bytes", "crsdr_map_integrate",
 ]
+INTEGRATE_ARRAY, INTEGRATE_BEAMS = 1, 2
 TRACK_SRC_ARRAY, TRACK_SRC_FUSED = 0, 1
 TRACK_FREE, TRACK_TENTATIVE, TRACK_CONFIRMED, TRACK_ENDED = 0, 1, 2, 3      # trk[..., 1]
 BEARING_CONVENTIONAL, BEARING_ADAPTIVE = 1, 2
@@ -163,6 +166,12 @@ class TrackDesc(C.Structure):
     _fields_ = [("max_tracks", C.c_int32), ("source", C.c_int32), ("sigma_r", C.c_double), ("sigma_f", C.c_double), ("gate", C.c_double),
                 ("p0_g", C.c_double), ("q_r", C.c_double), ("q_f", C.c_double), ("q_g", C.c_double), ("coupling", C.c_double),
                 ("m", C.c_int32), ("n", C.c_int32), ("tent_miss", C.c_int32), ("conf_miss", C.c_int32)]
+
+
+class IntegrateDesc(C.Structure):
+    """crsdr_caf_integrate_desc: which maps (INTEGRATE_ARRAY, INTEGRATE_BEAMS), the forgetting factor in (0, 1] and the coupling in lag
+    cells per line per Doppler bin (the tracker's figure)."""
+    _fields_ = [("what", C.c_int32), ("reserved", C.c_int32), ("forget", C.c_double), ("coupling", C.c_double)]
 
 
 _lib = None
@@ -355,6 +364,13 @@ def lib():
         L.crsdr_caf_track_device_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         L.crsdr_track_state_bytes.argtypes = [C.POINTER(TrackDesc), C.POINTER(C.c_size_t)]
         L.crsdr_track.argtypes = [f32p, i32p, vp, f32p, i32p, f32p] + [C.c_int] * 4 + [C.POINTER(TrackDesc), C.c_int]
+    if hasattr(L, "crsdr_map_integrate"):            # (likewise: an older build has no integration across lines)
+        L.crsdr_caf_set_integrate.argtypes = [vp, C.POINTER(IntegrateDesc)]
+        L.crsdr_caf_integrate_reset.argtypes = [vp]
+        L.crsdr_caf_fetch_integrate.argtypes = [vp, f32p, f32p]
+        L.crsdr_caf_integrate_device_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        L.crsdr_map_integrate_state_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+        L.crsdr_map_integrate.argtypes = [f32p, vp, f32p] + [C.c_int] * 4 + [C.POINTER(IntegrateDesc), C.c_int]
     _lib = L
     return L
 
@@ -910,6 +926,38 @@ def track_device(trk_ptr: int, ntrk_ptr: int, state_ptr: int, det_ptr: int, coun
     cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
     _check(lib().crsdr_track(cast(trk_ptr, C.c_float), cast(ntrk_ptr, C.c_int32), C.c_void_p(int(state_ptr) or None), cast(det_ptr, C.c_float), cast(count_ptr, C.c_int32),
                              cast(aux_ptr, C.c_float), int(nlines), int(K), int(nd), int(R), C.byref(desc), MEM_DEVICE))
+
+
+def integrate_desc(forget, coupling=0.0, what=INTEGRATE_ARRAY):
+    return IntegrateDesc(int(what), 0, float(forget), float(coupling))
+
+
+def map_integrate_state_bytes(nmaps, nd, R) -> int:
+    """crsdr_map_integrate_state_bytes: the size of map_integrate()'s state buffer, a 16-byte header (int64 m, int64 0) and nmaps nd R
+    doubles."""
+    n = C.c_size_t(0)
+    _check(lib().crsdr_map_integrate_state_bytes(int(nmaps), int(nd), int(R), C.byref(n)))
+    return int(n.value)
+
+
+def map_integrate(maps, desc, state=None):
+    """crsdr_map_integrate on nlines lines: maps [nlines][nmaps][nd][R] float32 (or [nlines][nd][R]: one map a line) -> (imap of the same
+    shape, state).  state: the uint8 array an earlier call returned, or None for the empty state; it is not changed, the state behind
+    the last line is returned.  The engine's integration (Caf.set_integrate), bit for bit."""
+    m = np.ascontiguousarray(maps, dtype=np.float32)
+    L, nmaps, nd, R = m.shape if m.ndim == 4 else (m.shape[0], 1) + m.shape[1:]
+    nbytes = map_integrate_state_bytes(nmaps, nd, R)
+    s = np.zeros(nbytes // 8, dtype=np.float64).view(np.uint8) if state is None else np.array(state, dtype=np.uint8).reshape(nbytes).copy()
+    out = np.zeros(m.shape, dtype=np.float32)
+    _check(lib().crsdr_map_integrate(_p(out, C.c_float), s.ctypes.data_as(C.c_void_p), _p(m, C.c_float), L, nmaps, nd, R, C.byref(desc), MEM_HOST))
+    return out, s
+
+
+def map_integrate_device(imap_ptr: int, state_ptr: int, maps_ptr: int, nlines, nmaps, nd, R, desc):
+    """crsdr_map_integrate with CRSDR_MEM_DEVICE: every pointer on the device."""
+    cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
+    _check(lib().crsdr_map_integrate(cast(imap_ptr, C.c_float), C.c_void_p(int(state_ptr) or None), cast(maps_ptr, C.c_float), int(nlines), int(nmaps), int(nd), int(R),
+                                     C.byref(desc), MEM_DEVICE))
 
 
 def ambiguity_device(chi_ptr: int, map_ptr: int, peak_ptr: int, matrix_ptr: int, nrows, B, seg, nlags, ref_row, window, guard):
@@ -1708,6 +1756,29 @@ class Caf:
         ptrs = [C.c_void_p() for _ in range(2)]
         _check(lib().crsdr_caf_track_device_buffers(self._h, *[C.byref(p) for p in ptrs]))
         return dict(zip(("trk", "ntrk"), [p.value for p in ptrs]))
+
+    def set_integrate(self, desc: "IntegrateDesc | None"):
+        """crsdr_caf_set_integrate: the maps integrated across lines along the range walk, ahead of the detector (None: off); empties
+        its state.  Between submits, with bearings and the tracker off; INTEGRATE_BEAMS with beams on."""
+        _check(lib().crsdr_caf_set_integrate(self._h, None if desc is None else C.byref(desc)))
+        self.integrate = 0 if desc is None else int(desc.what)
+
+    def integrate_reset(self):
+        """crsdr_caf_integrate_reset: the empty state, m = 0."""
+        _check(lib().crsdr_caf_integrate_reset(self._h))
+
+    def fetch_integrate(self, imap=None, ibmap=None) -> dict:
+        """Waits for the last submit.  imap [nest][nd][nlags], ibmap [nest][nb][nd][nlags]; by default those whose flag is on."""
+        n, what, nb = self._last()[0], getattr(self, "integrate", 0), max(1, getattr(self, "nbeams", 0))
+        a = np.zeros((n, self.nd, self.nlags), dtype=np.float32) if (what & INTEGRATE_ARRAY if imap is None else imap) else None
+        m = np.zeros((n, nb, self.nd, self.nlags), dtype=np.float32) if (what & INTEGRATE_BEAMS if ibmap is None else ibmap) else None
+        _check(lib().crsdr_caf_fetch_integrate(self._h, _p(a, C.c_float), _p(m, C.c_float)))
+        return {k: v for k, v in (("imap", a), ("ibmap", m)) if v is not None}
+
+    def integrate_device_buffers(self) -> dict:
+        ptrs = [C.c_void_p() for _ in range(3)]
+        _check(lib().crsdr_caf_integrate_device_buffers(self._h, *[C.byref(p) for p in ptrs]))
+        return dict(zip(("imap", "ibmap", "state"), [p.value for p in ptrs]))
 
     def set_cancel(self, taps: "int | None", dopp: int = 0):
         """crsdr_caf_set_cancel: the canceller in front of every submit's Doppler stage (taps None: off).  Between submits."""

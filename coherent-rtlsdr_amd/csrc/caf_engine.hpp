@@ -14,10 +14,12 @@
 //     the line, and the fusion of the beams' lists into one per line.
 //     With the tracker set (crsdr_caf_set_track; caf_track.hpp, caf_track_kernels.hpp) one more behind everything else: one workgroup
 //     that walks the lines of the submit and carries the tracks from submit to submit.
+//     With integration set (crsdr_caf_set_integrate; caf_integrate.hpp, caf_integrate_solve.hpp) one more behind the array map, whose
+//     place the integrated map takes in front of the detector, and one more behind the beam maps, likewise.
 //
 // Shape of the host code (doa_engine.hpp's).  A feature is a sub-struct of crsdr_caf: its parameters and its DevBufs.  Every launch
-// goes through caf_run, which checks and counts it.  A submit is caf_launch's flat list of stages (maps, detector, bearings, beams,
-// the beams' lists, tracker), each of which returns at once with its feature off; what it left (CafLast) is written once at its end.
+// goes through caf_run, which checks and counts it.  A submit is caf_launch's flat list of stages (maps, integration, detector,
+// bearings, beams, their integration, the beams' lists, tracker), each of which returns at once with its feature off; what it left (CafLast) is written once at its end.
 // A setter asks caf_rules, empties its feature behind caf_quiesce (caf_clear), builds the new one in a local, between submits, and
 // moves it in when every allocation has succeeded.  A fetch reads its state from CafLast and copies through DevFetch.  The per-op
 // calls share the *_enqueue functions with the stages (the same kernels on the same arguments, so the same bits) and caf_shape_ok.
@@ -28,6 +30,7 @@
 #include "caf_bearing.hpp"
 #include "caf_cancel.hpp"
 #include "caf_cfar_kernels.hpp"
+#include "caf_integrate.hpp"
 #include "caf_track_kernels.hpp"
 
 // `launch` with LG = log2 nd, 3 .. 12
@@ -60,7 +63,7 @@ struct CancelBufs {
 
 // what the last submit left: where, how much, and which features ran (kCafRan*).  A setter clears its feature's bit: "nothing submitted
 // since"; without kCafRanBase nothing is left at all
-constexpr unsigned kCafRanBase = 1u, kCafRanCancel = 2u, kCafRanCfar = 4u, kCafRanBearing = 8u, kCafRanBeams = 16u, kCafRanTrack = 32u;
+constexpr unsigned kCafRanBase = 1u, kCafRanCancel = 2u, kCafRanCfar = 4u, kCafRanBearing = 8u, kCafRanBeams = 16u, kCafRanTrack = 32u, kCafRanIntegrate = 64u;
 struct CafLast {
     hipStream_t stream = nullptr;
     int nest = 0, launches = 0;
@@ -117,6 +120,17 @@ struct crsdr_caf {
         DevBuf<float> trk;
         DevBuf<int32_t> ntrk;
     } tk;
+    // crsdr_caf_set_integrate: on (false = off), which maps, the state that a submit hands to the next -- the array map's block, then
+    // the beam maps', each a header and its doubles; a block whose flag is off is not there -- and the integrated maps
+    struct Integrate {
+        bool on = false;
+        int what = 0;
+        integ::Params prm{};
+        DevBuf<unsigned char> state;
+        DevBuf<float> imap, ibmap;
+        bool array() const { return on && (what & integ::ARRAY); }
+        bool beams() const { return on && (what & integ::BEAMS); }
+    } ig;
     CafLast last;
     size_t lines() const { return (size_t)(max_batch / frames); }      // the most a submit leaves: what every setter sizes its buffers by
 };
@@ -375,6 +389,29 @@ static int track_enqueue(CafRun &r, const float *det, size_t det_stride, const i
                    nlines, K, nd, R, prm, state, out, nout);
 }
 
+// every limit of the integration of section (w), for crsdr_caf_set_integrate and crsdr_map_integrate (check_what false: `what` is not read)
+static int integrate_args_ok(const char *who, int nd, const crsdr_caf_integrate_desc *d, bool check_what, integ::Params *prm)
+{
+    *prm = integ::Params{d->forget, d->coupling};
+    switch (integ::bad_limit(nd, *prm)) {
+    case 0: break;
+    case 1: return fail(CRSDR_EINVAL, "%s: forget = %g (finite, in (0, 1])", who, d->forget);
+    case 2: return fail(CRSDR_EINVAL, "%s: coupling = %g (finite)", who, d->coupling);
+    default: return fail(CRSDR_EINVAL, "%s: |coupling| * (nd / 2) = %g (at most %g cells a line)", who, fabs(d->coupling) * (double)(nd / 2), integ::MAX_WALK);
+    }
+    if (check_what && (d->what < 1 || d->what > (integ::ARRAY | integ::BEAMS)))
+        return fail(CRSDR_EINVAL, "%s: what = %d (CRSDR_INTEGRATE_ARRAY, CRSDR_INTEGRATE_BEAMS or both)", who, d->what);
+    return CRSDR_OK;
+}
+
+// the integration's one launch, for the object and for crsdr_map_integrate: the same kernel on the same arguments, so the same bits
+static int integrate_enqueue(CafRun &r, const float *maps, int nlines, int nmaps, int nd, int R, const integ::Params &prm, unsigned char *state, float *imap)
+{
+    const int nb = caf_integrate::bins_of(nd, R);
+    return caf_run(r, caf_integrate::k_caf_integrate, dim3((unsigned)((nd + nb - 1) / nb), (unsigned)nmaps), dim3(caf_integrate::THREADS), caf_integrate::lds_bytes(nb, R), maps,
+                   nlines, nmaps, nd, R, nb, prm, state, imap);
+}
+
 // The two dynamic LDS limits above the 64 KiB default, k_bearing_slot's and k_caf_track's, are function attributes of the current
 // device, shared by every live object: each create sets both to the most any object can ask for, so that no call lowers a limit under
 // another and no setter has to think of them.  crsdr_bearing and crsdr_track do the same for their calls.
@@ -414,7 +451,7 @@ static int caf_clear(crsdr_caf *q, Feature &f, unsigned ran_bit)
 // Who must be off before whom, who must be on before whom: every rule of the setters, each feature's in the order they are asked.
 // must_be_on false: `feature` is not changed, set or turned off, while `other` is on, which works on its buffers and parameters (asked
 // ahead of the descriptor's limits).  true: `feature` is not set while `other` is off (asked behind them, and not to turn it off).
-enum { kCafCfar, kCafBearing, kCafBeams, kCafBeamLists, kCafTrack, kCafTrackFused, kCafCfarEst };
+enum { kCafCfar, kCafBearing, kCafBeams, kCafBeamLists, kCafTrack, kCafIntegrate, kCafTrackFused, kCafCfarEst, kCafIntegrateBeams };
 static const struct CafRule { int feature; bool must_be_on; int other; const char *refusal; } kCafRules[] = {
     {kCafCfar, false, kCafTrack, "caf_set_cfar: the tracker is on (crsdr_caf_set_track): its measurements are this detector's lists; turn it off first"},
     {kCafCfar, false, kCafBeams, "caf_set_cfar: beams are on (crsdr_caf_set_beams): whether they are detected on, and the lists' sizes, are this detector's; turn them off first"},
@@ -426,13 +463,17 @@ static const struct CafRule { int feature; bool must_be_on; int other; const cha
     {kCafBearing, false, kCafTrack, "caf_set_bearing: the tracker is on (crsdr_caf_set_track): its auxiliary pairs are these bearings; turn it off first"},
     {kCafBearing, true, kCafCfar, "caf_set_bearing: no detector set (crsdr_caf_set_cfar): there are no detections to take a bearing of"},
     {kCafBeams, false, kCafTrack, "caf_set_beams: the tracker is on (crsdr_caf_set_track): the fused list may be its source; turn it off first"},
+    {kCafBeams, false, kCafIntegrate, "caf_set_beams: integration is on (crsdr_caf_set_integrate): the beam maps' state has their number and size; turn it off first"},
     {kCafTrack, true, kCafCfar, "caf_set_track: no detector set (crsdr_caf_set_cfar): there are no detections to track"},
     {kCafTrackFused, true, kCafBeamLists, "caf_set_track: the fused source needs beams with detection (crsdr_caf_set_beams behind crsdr_caf_set_cfar)"},
+    {kCafIntegrate, false, kCafTrack, "caf_set_integrate: the tracker is on (crsdr_caf_set_track): its measurements are the lists of the maps this changes; turn it off first"},
+    {kCafIntegrate, false, kCafBearing, "caf_set_integrate: bearings are on (crsdr_caf_set_bearing): they follow the lists of the map this changes; turn them off first"},
+    {kCafIntegrateBeams, true, kCafBeams, "caf_set_integrate: CRSDR_INTEGRATE_BEAMS needs beams (crsdr_caf_set_beams): there are no beam maps to integrate"},
 };
 
 static int caf_rules(const crsdr_caf *q, int feature, bool must_be_on)
 {
-    const bool on[] = {q->cf.on, q->bg.on, q->bb.on, q->bb.on && q->bb.det, q->tk.on};
+    const bool on[] = {q->cf.on, q->bg.on, q->bb.on, q->bb.on && q->bb.det, q->tk.on, q->ig.on};
     for (const CafRule &u : kCafRules)
         if (u.feature == feature && u.must_be_on == must_be_on && on[u.other] != must_be_on) return fail(CRSDR_ESTATE, "%s", u.refusal);
     return CRSDR_OK;
@@ -486,11 +527,20 @@ static int caf_stage_maps(crsdr_caf *q, CafRun &r, const int8_t *packets, size_t
                        q->map, q->peak, q->cn.on ? &cb : nullptr);
 }
 
+// the array map across the lines: one launch whatever the batch (the state's first block)
+static int caf_stage_integrate(crsdr_caf *q, CafRun &r)
+{
+    crsdr_caf::Integrate &g = q->ig;
+    if (!g.array()) return CRSDR_OK;
+    return integrate_enqueue(r, q->map, r.nest, 1, q->nd, q->nlags, g.prm, g.state, g.imap);
+}
+
+// (the detector's array-map entry reads the integrated map where there is one; the rows' entries and the snapshots read chi as ever)
 static int caf_stage_cfar(crsdr_caf *q, CafRun &r)
 {
     crsdr_caf::Cfar &c = q->cf;
     if (!c.on) return CRSDR_OK;
-    return cfar_enqueue(r, q->chi, q->map, r.nest, q->nrows, q->nrows + 1, q->nd, q->nlags, q->guard, c.prm, c.keep, c.slots, c.tcount, c.det, c.count, c.snap);
+    return cfar_enqueue(r, q->chi, q->ig.array() ? q->ig.imap : q->map, r.nest, q->nrows, q->nrows + 1, q->nd, q->nlags, q->guard, c.prm, c.keep, c.slots, c.tcount, c.det, c.count, c.snap);
 }
 
 // (the bearings and the tracker read the array map's lists: entry nrows of the nrows + 1 of a line)
@@ -510,12 +560,21 @@ static int caf_stage_beams(crsdr_caf *q, CafRun &r)
     return beam_maps_enqueue(r, q->chi, g.w, r.nest, q->nrows, q->nd * q->nlags, q->ref_row, g.nb, g.bmap);
 }
 
+// the beam maps across the lines, (line, beam) in bmap's order: one launch (the state's block behind the array map's, if that is there)
+static int caf_stage_integrate_beams(crsdr_caf *q, CafRun &r)
+{
+    crsdr_caf::Integrate &g = q->ig;
+    if (!g.beams()) return CRSDR_OK;
+    unsigned char *state = g.state.p + (g.array() ? integ::state_bytes(1, q->nd, q->nlags) : 0);
+    return integrate_enqueue(r, q->bb.bmap, r.nest, q->bb.nb, q->nd, q->nlags, g.prm, state, g.ibmap);
+}
+
 // the detector on the beams' maps and the fusion of their lists: (line, beam) is the line of a one-map call, as crsdr_cfar has it with comps = 1
 static int caf_stage_beam_lists(crsdr_caf *q, CafRun &r)
 {
     crsdr_caf::Beams &g = q->bb;
     if (!g.on || !g.det) return CRSDR_OK;
-    const int rc = cfar_enqueue(r, nullptr, g.bmap, r.nest * g.nb, 0, 1, q->nd, q->nlags, q->guard, q->cf.prm, q->cf.keep, g.slots, g.tcount, g.bdet, g.bcount, nullptr);
+    const int rc = cfar_enqueue(r, nullptr, q->ig.beams() ? q->ig.ibmap : g.bmap, r.nest * g.nb, 0, 1, q->nd, q->nlags, q->guard, q->cf.prm, q->cf.keep, g.slots, g.tcount, g.bdet, g.bcount, nullptr);
     if (rc) return rc;
     return beam_fuse_enqueue(r, g.bdet, g.bcount, r.nest, g.nb, q->cf.prm.max_det, q->nd, q->nlags, g.fused, g.nfused);
 }
@@ -535,9 +594,11 @@ static int caf_launch(crsdr_caf *q, const int8_t *packets, size_t packet_stride,
 {
     CafRun r{S, nblocks / q->frames};
     int rc = caf_stage_maps(q, r, packets, packet_stride, matrix_offset, nblocks);
+    if (!rc) rc = caf_stage_integrate(q, r);
     if (!rc) rc = caf_stage_cfar(q, r);
     if (!rc) rc = caf_stage_bearing(q, r);
     if (!rc) rc = caf_stage_beams(q, r);
+    if (!rc) rc = caf_stage_integrate_beams(q, r);
     if (!rc) rc = caf_stage_beam_lists(q, r);
     if (!rc) rc = caf_stage_track(q, r);
     // Deliberately also behind a stage that failed to launch: the kernels ahead of it are on S and write the buffers, so the object
@@ -545,7 +606,7 @@ static int caf_launch(crsdr_caf *q, const int8_t *packets, size_t packet_stride,
     // stand for whole stages only.
     if (r.launches)
         q->last = CafLast{S, r.nest, r.launches, rc ? kCafRanBase : kCafRanBase | (q->cn.on ? kCafRanCancel : 0u) | (q->cf.on ? kCafRanCfar : 0u) | (q->bg.on ? kCafRanBearing : 0u) |
-                                                                      (q->bb.on ? kCafRanBeams : 0u) | (q->tk.on ? kCafRanTrack : 0u)};
+                                                                      (q->bb.on ? kCafRanBeams : 0u) | (q->tk.on ? kCafRanTrack : 0u) | (q->ig.on ? kCafRanIntegrate : 0u)};
     return rc;
 }
 
@@ -1021,6 +1082,103 @@ extern "C" int crsdr_track(float *out, int32_t *nout, void *state, const float *
     { const int rc_ = track_enqueue(r, d_d, (size_t)K * 8, d_c, 1, d_a, d_a ? caf_track::AUX_PAIRS : caf_track::AUX_NONE, nlines, K, nd, R, prm, d_s, d_t, d_n); if (rc_) return rc_; }
     st.back(out, d_t, tb);
     st.back(nout, d_n, nb);
+    st.back(state, d_s, sb);
+    return st.finish();
+}
+
+// ---- the integration across lines ----
+static size_t integrate_state_bytes(const crsdr_caf *q, int what, int nbeams)
+{
+    return (what & integ::ARRAY ? integ::state_bytes(1, q->nd, q->nlags) : 0) + (what & integ::BEAMS ? integ::state_bytes(nbeams, q->nd, q->nlags) : 0);
+}
+
+extern "C" int crsdr_caf_set_integrate(crsdr_caf *q, const crsdr_caf_integrate_desc *desc)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_set_integrate: NULL caf");
+    { const int rc = caf_rules(q, kCafIntegrate, false); if (rc) return rc; }
+    integ::Params prm{};
+    if (desc) {
+        { const int rc_ = integrate_args_ok("caf_set_integrate", q->nd, desc, true, &prm); if (rc_) return rc_; }
+        if (desc->what & integ::BEAMS) { const int rc = caf_rules(q, kCafIntegrateBeams, true); if (rc) return rc; }
+    }
+    { const int rc = caf_clear(q, q->ig, kCafRanIntegrate); if (rc || !desc) return rc; }
+    const size_t lines = q->lines(), cells = (size_t)q->nd * (size_t)q->nlags, sb = integrate_state_bytes(q, desc->what, q->bb.nb);
+    crsdr_caf::Integrate f;
+    f.what = desc->what; f.prm = prm; f.on = true;
+    int r = CRSDR_OK;
+    if ((r = f.state.alloc(sb)) || ((f.what & integ::ARRAY) && (r = f.imap.alloc(lines * cells))) ||
+        ((f.what & integ::BEAMS) && (r = f.ibmap.alloc(lines * (size_t)q->bb.nb * cells))) || (r = HIP_RC(hipMemset(f.state.p, 0, sb))))
+        return r;
+    q->ig = std::move(f);
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_integrate_reset(crsdr_caf *q)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_integrate_reset: NULL caf");
+    if (!q->ig.on) return fail(CRSDR_ESTATE, "caf_integrate_reset: no integration set (crsdr_caf_set_integrate)");
+    { const int rc = caf_quiesce(q); if (rc) return rc; }     // the last submit may still write the state
+    HIP_TRY(hipMemset(q->ig.state.p, 0, integrate_state_bytes(q, q->ig.what, q->bb.nb)));
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_fetch_integrate(crsdr_caf *q, float *imap, float *ibmap)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_fetch_integrate: NULL caf");
+    if (!q->ig.on) return fail(CRSDR_ESTATE, "caf_fetch_integrate: no integration set (crsdr_caf_set_integrate)");
+    if (!(q->last.ran & kCafRanIntegrate)) return fail(CRSDR_ESTATE, "caf_fetch_integrate: nothing submitted since the integration was set");
+    if (imap && !q->ig.array()) return fail(CRSDR_ESTATE, "caf_fetch_integrate: the array map is not integrated (CRSDR_INTEGRATE_ARRAY)");
+    if (ibmap && !q->ig.beams()) return fail(CRSDR_ESTATE, "caf_fetch_integrate: the beam maps are not integrated (CRSDR_INTEGRATE_BEAMS)");
+    const size_t lines = (size_t)q->last.nest, cells = (size_t)q->nd * (size_t)q->nlags;
+    return DevFetch(q->device, q->last.stream).copy(imap, q->ig.imap.p, lines * cells).copy(ibmap, q->ig.ibmap.p, lines * (size_t)q->bb.nb * cells).wait();
+}
+
+extern "C" int crsdr_caf_integrate_device_buffers(crsdr_caf *q, void **imap, void **ibmap, void **state)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_integrate_device_buffers: NULL caf");
+    if (!q->ig.on) return fail(CRSDR_ESTATE, "caf_integrate_device_buffers: no integration set (crsdr_caf_set_integrate)");
+    if (imap) *imap = q->ig.imap;
+    if (ibmap) *ibmap = q->ig.ibmap;
+    if (state) *state = q->ig.state;
+    return CRSDR_OK;
+}
+
+constexpr long long kIntegrateMaxCells = 1ll << 26;     // crsdr_map_integrate: nlines * nmaps * nd * R
+
+static int map_integrate_shape_ok(const char *who, int nmaps, int nd, int R)
+{
+    { const int rc_ = caf_shape_ok(who, nd, R, 0, 0, 2); if (rc_) return rc_; }
+    if (nmaps < 1 || (long long)nmaps * nd * R > kCafMaxCells) return fail(CRSDR_EINVAL, "%s: nmaps = %d (at least 1, nmaps * nd * R at most 2^24)", who, nmaps);
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_map_integrate_state_bytes(int nmaps, int nd, int R, size_t *bytes)
+{
+    if (!bytes) return fail(CRSDR_EINVAL, "map_integrate_state_bytes: NULL bytes");
+    { const int rc_ = map_integrate_shape_ok("map_integrate_state_bytes", nmaps, nd, R); if (rc_) return rc_; }
+    *bytes = integ::state_bytes(nmaps, nd, R);
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_map_integrate(float *imap, void *state, const float *maps, int nlines, int nmaps, int nd, int R, const crsdr_caf_integrate_desc *desc, int mem_kind)
+{
+    if (!imap || !state || !maps || !desc) return fail(CRSDR_EINVAL, "map_integrate: need imap, state, maps and a descriptor");
+    if (nlines < 1 || nlines > kTrackMaxLines) return fail(CRSDR_EINVAL, "map_integrate: nlines = %d (1..%d)", nlines, kTrackMaxLines);
+    { const int rc_ = map_integrate_shape_ok("map_integrate", nmaps, nd, R); if (rc_) return rc_; }
+    if ((long long)nlines * nmaps * nd * R > kIntegrateMaxCells) return fail(CRSDR_EINVAL, "map_integrate: nlines * nmaps * nd * R = %lld (at most 2^26)", (long long)nlines * nmaps * nd * R);
+    integ::Params prm{};
+    { const int rc_ = integrate_args_ok("map_integrate", nd, desc, false, &prm); if (rc_) return rc_; }
+    OP_PROLOGUE_MEM("map_integrate", mem_kind);
+    const size_t mb = sizeof(float) * (size_t)nlines * (size_t)nmaps * (size_t)nd * (size_t)R, sb = integ::state_bytes(nmaps, nd, R);
+    OpStage st(mem_kind);
+    const float *d_m = (const float *)st.in(0, maps, mb, 4);
+    unsigned char *d_s = (unsigned char *)st.in(1, state, sb, 8);
+    float *d_i = (float *)st.out(2, imap, mb, 4);
+    if (st.rc) return st.rc;
+    if (st.misaligned) return fail(CRSDR_EINVAL, "map_integrate: device maps and imap 4-byte, state 8-byte aligned");
+    CafRun r{nullptr};
+    { const int rc_ = integrate_enqueue(r, d_m, nlines, nmaps, nd, R, prm, d_s, d_i); if (rc_) return rc_; }
+    st.back(imap, d_i, mb);
     st.back(state, d_s, sb);
     return st.finish();
 }

@@ -153,6 +153,36 @@ int batch::fetch_track()
     return rc;
 }
 
+int batch::set_integrate(const crsdr_caf_integrate_desc *desc)
+{
+    int rc = cf ? crsdr_caf_set_integrate(cf, desc) : CRSDR_ESTATE;
+    if (!rc) { iwhat = desc ? desc->what : 0; imap.clear(); ibmap.clear(); }
+    if (rc && cf) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::reset_integrate()
+{
+    int rc = cf ? crsdr_caf_integrate_reset(cf) : CRSDR_ESTATE;
+    if (rc && cf) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::fetch_integrate()
+{
+    int nest = 0;
+    int rc = !cf || !iwhat ? CRSDR_ESTATE : crsdr_caf_last_submit(cf, &nest, nullptr);
+    if (!rc) {
+        const bool a = (iwhat & CRSDR_INTEGRATE_ARRAY) != 0, b = (iwhat & CRSDR_INTEGRATE_BEAMS) != 0;
+        const size_t cells = (size_t)nest * bins * lags;
+        imap.assign(a ? cells : 0, 0.f); ibmap.assign(b ? cells * nb : 0, 0.f);
+        rc = crsdr_caf_fetch_integrate(cf, a ? imap.data() : nullptr, b ? ibmap.data() : nullptr);
+    }
+    if (!rc) nlines = nest;
+    if (rc && cf && iwhat) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
 int batch::set_cancel(const crsdr_caf_cancel_desc *desc)
 {
     int rc = cf ? crsdr_caf_set_cancel(cf, desc) : CRSDR_ESTATE;

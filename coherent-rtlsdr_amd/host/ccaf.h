@@ -50,7 +50,7 @@ class batch {
     crsdr_caf *cf = nullptr;
     int rows, bins, lags, kdet = 0, nbasis = 0, npts = 0;
     bool bearings = false, beam_lists = false;
-    int nb = 0, ntracks = 0;
+    int nb = 0, ntracks = 0, iwhat = 0;
 
 public:
     batch(int nrows, int blocksize, int max_batch, int seg, int nlags, int ref_row = 0, int window = CRSDR_WINDOW_RECT, int guard = 0, int frames = 1, int device = 0);
@@ -95,6 +95,15 @@ public:
     // waits, and fills trk and ntrk: the tracks of every line of the last submit; CRSDR_ESTATE with the tracker off
     int fetch_track();
     int max_tracks() const { return ntracks; }
+    // the maps integrated across lines along the range walk, ahead of the detector (crsdr_caf_set_integrate; NULL: off), the state
+    // empty.  Between submits, with bearings and the tracker off (CRSDR_INTEGRATE_BEAMS: with beams on); while it is on set_beams is
+    // refused.  With it on det's entry nrows, and the beams' lists, are the integrated maps'.
+    int set_integrate(const crsdr_caf_integrate_desc *desc);
+    // the empty state again, m = 0
+    int reset_integrate();
+    // waits, and fills imap and ibmap, those whose flag is on; CRSDR_ESTATE with integration off
+    int fetch_integrate();
+    int integrated() const { return iwhat; }
     int basis() const { return nbasis; }             // taps (2 dopp + 1), 0 with the canceller off
     int lines() const { return nlines; }
     int nrows() const { return rows; }
@@ -121,6 +130,8 @@ public:
     std::vector<track_t> trk;                        // [lines][max_tracks]: every slot of every line; free slots zero
     std::vector<int32_t> ntrk;                       // [lines][4]: live tracks after the line, confirmed, initiated, dropped
     const track_t &track_at(int e, int i) const { return trk[(size_t)e * ntracks + i]; }
+    std::vector<float> imap;                         // [lines][nd][nlags]: the array map integrated across lines
+    std::vector<float> ibmap;                        // [lines][nbeams][nd][nlags]: every beam's map, likewise
     std::vector<float> coef;                         // [lines][nrows][basis][2]: the canceller's filter of every row
     std::vector<float> cinfo;                        // [lines][nrows][2]: the share of the row's power that stays, and the status
     float residual(int e, int c) const { return cinfo[2 * ((size_t)e * rows + c)]; }

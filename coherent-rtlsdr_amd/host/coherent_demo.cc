@@ -78,6 +78,9 @@ int main(int argc, char **argv)
     crsdr_caf_cancel_desc cancel = {0, 0};
     bool track_on = false;
     crsdr_caf_track_desc track = {16, CRSDR_TRACK_SRC_ARRAY, 0.5, 0.5, 9.0, 1.0, 1e-3, 1e-3, 1e-4, 0.0, 3, 5, 2, 4};
+    bool integrate_on = false;
+    double integrate_window = 0.0;
+    crsdr_caf_integrate_desc integrate = {CRSDR_INTEGRATE_ARRAY, 0, 1.0, 0.0};
     bool engine_batches = false;
     int ranks = 1, rank = 0, device = 0;
     std::string idfile;
@@ -218,6 +221,14 @@ int main(int argc, char **argv)
         else if (a == "--track-sigma" && i + 1 < argc) { if (std::sscanf(argv[++i], "%lf:%lf", &track.sigma_r, &track.sigma_f) != 2) track.sigma_r = -1.0; }
         else if (a == "--track-q" && i + 1 < argc) { if (std::sscanf(argv[++i], "%lf:%lf:%lf", &track.q_r, &track.q_f, &track.q_g) != 3) track.q_r = -1.0; }
         else if (a == "--coupling" && i + 1 < argc) track.coupling = std::atof(argv[++i]);
+        // with --caf: the array map integrated across the lines along the range walk, ahead of the detector (crsdr_caf_set_integrate):
+        // a window of W lines (forget = 1 / W), COUPLING lag cells per line per Doppler bin (0; give --track the same with --coupling).
+        // With --cfar the printed detections are the integrated map's; with --caf-beams the beam maps are integrated too
+        else if (a == "--integrate" && i + 1 < argc) {
+            const int n = std::sscanf(argv[++i], "%lf:%lf", &integrate_window, &integrate.coupling);
+            integrate_on = true;
+            if (n < 1) integrate_window = -1.0;                                              // (refused below with the rest)
+        }
         else if (a == "--adaptive" && i + 1 < argc) { bearing.mode = CRSDR_BEARING_ADAPTIVE; bearing.loading = (float)std::atof(argv[++i]); }
         else if (a == "--bearing-levels") val(bearing.levels);
         else if (a == "--guard") val(caf_guard);
@@ -290,6 +301,17 @@ int main(int argc, char **argv)
         }
         std::printf("track: %d of %d gate %g slots %d sigma %g:%g q %g:%g:%g coupling %g source %s\n", track.m, track.n, track.gate, track.max_tracks, track.sigma_r,
                     track.sigma_f, track.q_r, track.q_f, track.q_g, track.coupling, beams_on ? "fused" : "array");
+    }
+    if (integrate_on) {
+        // numbers only (no device): the window and the coupling; the coupling against nd is the library's to judge behind --caf
+        if (!caf_seg) { std::printf("integrate: --integrate needs --caf: there are no maps to integrate\nDEMO FAILED\n"); return 1; }
+        if (!(integrate_window >= 1.0) || !std::isfinite(integrate_window) || !std::isfinite(integrate.coupling)) {
+            std::printf("integrate: --integrate W[:COUPLING] refused (W at least 1 line, both finite)\nDEMO FAILED\n");
+            return 1;
+        }
+        integrate.forget = 1.0 / integrate_window;
+        integrate.what = CRSDR_INTEGRATE_ARRAY | (beams_on ? CRSDR_INTEGRATE_BEAMS : 0);
+        std::printf("integrate: window %g forget %g coupling %g maps %s\n", integrate_window, integrate.forget, integrate.coupling, beams_on ? "array+beams" : "array");
     }
     int fails = 0;
     if (servo_table) {
@@ -629,10 +651,13 @@ int main(int argc, char **argv)
             if (cfar_est_on && caf->set_cfar_estimator(&cfar_est)) { std::printf("cfar: --cfar-est go|so|os[:RANK] [--cfar-axis lag|doppler] refused\nDEMO FAILED\n"); return 1; }
             if (cancel_on && caf->set_cancel(&cancel)) { std::printf("cancel: --cancel K[:P] refused\nDEMO FAILED\n"); return 1; }
             if (bearing_on && !cfar_on) { std::printf("bearing: --bearing needs --cfar: there are no detections to take a bearing of\nDEMO FAILED\n"); return 1; }
-            if (bearing_on && caf->set_bearing(&bearing)) {
+            // (the order of the setters is detector / beams, integration, bearings, tracker: with --integrate the bearings wait for it)
+            auto set_bearing = [&]() {
+                if (!bearing_on || !caf->set_bearing(&bearing)) return true;
                 std::printf("bearing: --bearing MXxMY[:NC] [--adaptive LOADING] [--bearing-levels L] refused (MX MY must be --nsig = %d)\nDEMO FAILED\n", nsig);
-                return 1;
-            }
+                return false;
+            };
+            if (!integrate_on && !set_bearing()) return 1;
             if (beams_on) {
                 const long long nbm = (long long)beams_nx * beams_ny;
                 bool good = beams_mx >= 1 && beams_my >= 1 && (long long)beams_mx * beams_my == nsig && beams_nx >= 1 && beams_ny >= 1 && nbm <= 64;
@@ -649,14 +674,18 @@ int main(int argc, char **argv)
                 }
                 if (!good) { std::printf("beams: --caf-beams MXxMY:NXxNY refused (MX MY must be --nsig = %d, NX NY at most 64)\nDEMO FAILED\n", nsig); return 1; }
             }
+            if (integrate_on && caf->set_integrate(&integrate)) { std::printf("integrate: --integrate W[:COUPLING] refused: %s\nDEMO FAILED\n", crsdr_last_error()); return 1; }
+            if (integrate_on && !set_bearing()) return 1;
             if (track_on && caf->set_track(&track)) { std::printf("track: --track refused: %s\nDEMO FAILED\n", crsdr_last_error()); return 1; }
         }
         auto ambiguity = [&](int b) {
             if (!caf || !ok) return;
             ok = caf->submit(coherent.engine_plan()) == CRSDR_OK && caf->fetch() == CRSDR_OK && (!cfar_on || caf->fetch_cfar() == CRSDR_OK) &&
                  (!cancel_on || caf->fetch_cancel(false) == CRSDR_OK) && (!bearing_on || caf->fetch_bearing() == CRSDR_OK) &&
-                 (!beams_on || caf->fetch_beams() == CRSDR_OK) && (!track_on || caf->fetch_track() == CRSDR_OK);
+                 (!beams_on || caf->fetch_beams() == CRSDR_OK) && (!track_on || caf->fetch_track() == CRSDR_OK) &&
+                 (!integrate_on || caf->fetch_integrate() == CRSDR_OK);
             if (!ok || !report) return;
+            if (integrate_on) std::printf("integrate: batch %d: %d lines behind a window of %g%s\n", b, caf->lines(), integrate_window, cfar_on ? ": the detections are the integrated map's" : "");
             for (int e = 0; cancel_on && e < caf->lines(); ++e) {
                 double sum = 0.0;
                 int n = 0, singular = 0;

@@ -1522,6 +1522,78 @@ int crsdr_track_state_bytes(const crsdr_caf_track_desc *desc, size_t *bytes);
 int crsdr_track(float *trk, int32_t *ntrk, void *state, const float *det, const int32_t *count, const float *aux, int nlines, int K,
                 int nd, int R, const crsdr_caf_track_desc *desc, int mem_kind);
 
+/* Integration across lines.  Every stage ahead of the tracker treats a line on its own, so an echo that does not clear the threshold in
+ * one line's map never reaches the lists.  This stage, behind the maps and ahead of the detector, is the non-coherent integration of
+ * consecutive maps along the range walk: between two lines a target at Doppler bin f walks coupling * f lag cells (the tracker's
+ * prediction r' = r + coupling (f + g / 2) knows the same figure), so before every update the accumulated map is shifted along the lags
+ * by a whole number of cells per Doppler bin -- exact, no interpolation, no blur that grows with time -- and the detector, unchanged,
+ * runs on the integrated map.  The accumulator is fp64 and is carried from submit to submit like the tracker's table.  It is off until
+ * crsdr_caf_set_integrate; off, a submit is the same launches and the same bits, in every combination of the other features.
+ *
+ * Definition.  P_m [nd][R] is the published fp32 map of line m; m = 0, 1, ... counts the lines since the last reset, across submits.
+ * s(d) is the signed bin of the peaks.  The caller sets forget = a, 0 < a <= 1, and coupling = c in lag cells per line per Doppler bin:
+ * the tracker's figure with the tracker's sign, and a tracker behind this stage should be given the same one.  The state is I [nd][R]
+ * in fp64 and the counter m; empty is all zero and m = 0.
+ * Per line, in this order:
+ *  1. Offsets.  delta(d) = c * (double)s(d), one multiplication; o(m, d) = (int64) floor((double)m * delta(d) + 0.5), one multiplication
+ *     and one addition; D(d) = o(m, d) - o(m - 1, d) for m >= 1, and D = 0 at m = 0.
+ *  2. Shift, per Doppler bin, in whole cells, clamped at both ends of the lags: I'[d][tau] = I[d][min(max(tau - D(d), 0), R - 1)].  No
+ *     arithmetic touches the values; lag does not wrap.
+ *  3. Update.  lambda = max(a, 1.0 / (double)(m + 1)): the running mean until the window is full, exponential forgetting from then on.
+ *     diff = (double)P - I', t = lambda * diff, I = I' + t: three fp64 operations, each rounded on its own, never contracted into an FMA,
+ *     on the device or on the host.
+ *  4. Output.  imap_m = (float)I, rounded once; the counter becomes m + 1.
+ * Consequences.  At m = 0 imap = map bit for bit.  A sequence of lines gives the same imap bytes and the same final state however it is
+ * cut into submits.  The carry-over makes consecutive submits depend on each other: they must be ordered -- on one stream (the engine's
+ * own, or a plan's through crsdr_caf_submit_plan), or by the caller waiting for one before the next goes to another stream.  Nothing
+ * depends on the order in which workgroups or waves run, and crsdr_map_integrate launches the same kernel on the same arguments.
+ *
+ * In the engine.  CRSDR_INTEGRATE_ARRAY: one launch behind the array map; the detector is handed imap where it is handed map without,
+ * so entry nrows of det and count is the integrated map's; snap is still the current line's chi at those cells; the rows' entries, map,
+ * peak and chi keep their bits.  CRSDR_INTEGRATE_BEAMS: one launch behind the beam maps, every (line, beam) map integrated on its own;
+ * the beams' lists and the fused list are then ibmap's.  Each is ONE launch whatever the batch.  Bearings, fusion and the tracker follow
+ * the lists they are given.
+ * Limits, all CRSDR_EINVAL and all checked before a device is touched, by one function for the engine and the per-op call: forget finite
+ * and in (0, 1]; coupling finite and |coupling| * (nd / 2) <= 1024; what a non-empty subset of the two flags. */
+enum { CRSDR_INTEGRATE_ARRAY = 1, CRSDR_INTEGRATE_BEAMS = 2 };
+
+typedef struct crsdr_caf_integrate_desc {
+    int32_t what;             /* CRSDR_INTEGRATE_* */
+    int32_t reserved;         /* 0 */
+    double forget;            /* a: the weight of a new line once the window is full, (0, 1] */
+    double coupling;          /* c: lag cells per line per Doppler bin */
+} crsdr_caf_integrate_desc;
+
+/* Sets the integration (NULL: off) and empties its state.  Between submits only: it waits for the last one and allocates here, never in
+ * a submit.  CRSDR_ESTATE while bearings or the tracker are on -- the lists this changes are their input: the order is detector / beams,
+ * integration, bearings, tracker -- and for CRSDR_INTEGRATE_BEAMS with beams off.  While integration is on crsdr_caf_set_beams returns
+ * CRSDR_ESTATE (turn it off first); crsdr_caf_set_cfar and crsdr_caf_set_cfar_estimator stay allowed: the detector owns no integration
+ * buffer. */
+int crsdr_caf_set_integrate(crsdr_caf *caf, const crsdr_caf_integrate_desc *desc);
+
+/* Empties the state: all zero, m = 0 (it waits for the last submit).  CRSDR_ESTATE with integration off. */
+int crsdr_caf_integrate_reset(crsdr_caf *caf);
+
+/* Waits for the last submit and copies out what is asked for (either pointer may be NULL): imap [nest][nd][R], ibmap
+ * [nest][nbeams][nd][R].  CRSDR_ESTATE with integration off, before the first submit since it was set, or for a map whose flag is off. */
+int crsdr_caf_fetch_integrate(crsdr_caf *caf, float *imap, float *ibmap);
+
+/* Device addresses ([max_batch / frames] lines of maps; NULL for a map whose flag is off).  state: the array map's block, then the beam
+ * maps', each laid out as crsdr_map_integrate's state for its number of maps; a block whose flag is off is not there.  They change with
+ * every crsdr_caf_set_integrate.  CRSDR_ESTATE with integration off. */
+int crsdr_caf_integrate_device_buffers(crsdr_caf *caf, void **imap, void **ibmap, void **state);
+
+/* *bytes = the size of the per-op call's state buffer: a 16-byte header (int64 m, int64 0) and nmaps nd R doubles.  Host only; nd a
+ * power of two in 8 .. 4096, 1 <= R <= 1024, nmaps >= 1 and nmaps nd R <= 2^24. */
+int crsdr_map_integrate_state_bytes(int nmaps, int nd, int R, size_t *bytes);
+
+/* The per-op form on nlines lines of nmaps maps each: maps [nlines][nmaps][nd][R] -> imap of the same shape; every map of a line is
+ * integrated on its own.  state is an in/out buffer of crsdr_map_integrate_state_bytes bytes; zero-filled means empty.  1 <= nlines <=
+ * 4096, nlines nmaps nd R <= 2^26; desc's what is not read.  The engine's kernel on the same arguments, bit for bit.  mem_kind:
+ * CRSDR_MEM_HOST (copied) or CRSDR_MEM_DEVICE (every pointer on the device; maps and imap 4-byte, state 8-byte aligned). */
+int crsdr_map_integrate(float *imap, void *state, const float *maps, int nlines, int nmaps, int nd, int R,
+                        const crsdr_caf_integrate_desc *desc, int mem_kind);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,10 +47,21 @@ slots, 3 of 5, gate 9, the array map's list):
   cfar trk   as caf+cfar at that threshold: the same build's submit without the tracker
   +track     as cfar trk with the tracker's one launch behind the detector's, + a fetch of trk and ntrk in the place of det and count
   get trk    the fetch of trk + ntrk, against "get lists", the fetch of det + count that a host tracker would need every submit
+with --integrate [--beams NB], on a further engine with the integration across lines set (crsdr_caf_set_integrate: forget 1 / 8, coupling
+0.05; with --beams on the "+beams" engine's twin as well, array and beam maps):
+  integ off  as caf, on the object of the next line with the integration turned off: the same build's submit without.  On and off are
+             one object, set in front of every round outside the clock: two objects of one configuration differ by as much as the stage
+  +integ     that object with the integration's one launch behind the map; imap stays on the device.  Beside it the stage's bytes (8 a
+             cell and line, 16 a cell of state) over the difference, and those bytes against the array-map kernel's, which reads nrows - 1 chi
+  integ off bm, +integ bm   the same on an engine with beams: both integration launches
+  integ op   crsdr_map_integrate on device memory at the engine's shape: the launch, its wait, and nothing else
+  integ big  the same at 64 lines of 16 maps (2^24 cells, 138 MB): the kernel where the launch no longer counts, as bytes / s
+with --parent-lib LIB beside it: "caf" -- the integration-off submit -- of another build (e.g. the parent commit's) through CRSDR_LIB in a
+worker process, in the same alternation ("caf parent", and "caf self" from a worker of this build).
 
 Every figure is the mean of --reps back-to-back rounds closed by one wait; --runs rounds alternate all variants in one session, medians
 and ranges are reported.  --json FILE keeps the record."""
-import argparse, importlib, json, os, statistics, sys, time
+import argparse, importlib, json, os, statistics, subprocess, sys, time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -77,8 +88,34 @@ def _mean(fn, wait, reps):
     return (time.perf_counter() - t0) / reps
 
 
+def worker(nrows, reps):
+    """the plain submit ("caf") of whatever build CRSDR_LIB names: a line on stdin -> seconds per submit on stdout"""
+    sys.path.insert(0, ROOT)
+    import torch
+    b = importlib.import_module("coherent-rtlsdr_amd.binding")
+    T, lags = SHAPES.get(nrows, (FRAMES, 16))
+    d_in = torch.from_numpy(_blocks(T, nrows, np.random.default_rng(1)).view(np.uint8).reshape(T, -1)).to(torch.device("cuda", 0))
+    plan = b.Plan(nrows, B, b.MODE_DIGITAL, max_batch=T)
+    cf = b.Caf(nrows, B, SEG, lags, 0, b.WINDOW_HANN, GUARD, max_batch=T, frames=FRAMES)
+    plan.submit(d_in.data_ptr(), seq=0, flags=b.REFNOISE_ENABLED, nblocks=T, block_stride=nrows * B)
+    plan.sync()
+    pk = plan.device_buffers()["packet"]
+
+    def run(i):
+        cf.submit(pk, plan.packet_stride, plan.matrix_offset, T)
+        cf.fetch(chi=False, map=False)
+
+    _mean(run, lambda: None, 2)
+    print("ready", flush=True)
+    for _ in sys.stdin:
+        print(_mean(run, lambda: None, reps), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--integrate", action="store_true", help="add the variants of the integration across lines (with --beams: the beam maps' too)")
+    ap.add_argument("--parent-lib", help="with --integrate: the plain submit of another build, in a worker process")
+    ap.add_argument("--worker", type=int, metavar="ROWS", help=argparse.SUPPRESS)
     ap.add_argument("--rows", type=int, nargs="*", default=[22, 1025])
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--reps", type=int, default=5)
@@ -92,6 +129,8 @@ def main():
     ap.add_argument("--json")
     a = ap.parse_args()
     a.cfar = a.cfar or a.bearing or a.estimator
+    if a.worker:
+        return worker(a.worker, a.reps)
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import torch
@@ -218,6 +257,42 @@ def main():
                     e.fetch_cfar(snap=False)
             return run
 
+        igs, ops, workers = {}, {}, {}
+        if a.integrate:
+            idesc = lambda what: b.integrate_desc(1.0 / 8.0, 0.05, what=what)
+            e = b.Caf(nrows, B, SEG, lags, 0, b.WINDOW_HANN, GUARD, max_batch=T, frames=FRAMES)
+            e.set_integrate(idesc(b.INTEGRATE_ARRAY))
+            igs["+integ"] = e
+            if bms:
+                e = b.Caf(nrows, B, SEG, lags, 0, b.WINDOW_HANN, GUARD, max_batch=T, frames=FRAMES)
+                e.set_beams(wts)
+                e.set_integrate(idesc(b.INTEGRATE_ARRAY | b.INTEGRATE_BEAMS))
+                igs["+integ bm"] = e
+            dev = torch.device("cuda", 0)
+            for name, (L, n) in (("integ op", (T // FRAMES, 1)), ("integ big", (64, 16))):
+                ops[name] = (L, n, torch.rand(L * n * nd * lags, device=dev), torch.zeros(2 + n * nd * lags, device=dev, dtype=torch.float64),
+                             torch.empty(L * n * nd * lags, device=dev))
+            if a.parent_lib:
+                for name, env in (("caf self", dict(os.environ)), ("caf parent", dict(os.environ, CRSDR_LIB=os.path.abspath(a.parent_lib)))):
+                    workers[name] = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", str(nrows), "--reps", str(a.reps)], stdin=subprocess.PIPE,
+                                                     stdout=subprocess.PIPE, text=True, env=env)
+                    assert workers[name].stdout.readline().strip() == "ready"
+
+        def caf_integ(e):
+            def run(i):
+                e.submit(pk, plan.packet_stride, plan.matrix_offset, T)
+                e.fetch(chi=False, map=False)
+            return run
+
+        def integ_op(name):
+            L, n, maps, state, imap = ops[name]
+            return lambda i: b.map_integrate_device(imap.data_ptr(), state.data_ptr(), maps.data_ptr(), L, n, nd, lags, b.integrate_desc(1.0 / 8.0, 0.05))
+
+        def asked(w):
+            w.stdin.write("go\n")
+            w.stdin.flush()
+            return float(w.stdout.readline())
+
         cfc, basis = None, 0
         if a.cancel:
             taps, dopp = (int(v) for v in (a.cancel + ":0").split(":")[:2])
@@ -266,6 +341,23 @@ def main():
             variants["get lists"] = lambda: _mean(lambda i: trs["cfar trk"].fetch_cfar(snap=False), lambda: None, a.reps)
         if a.cancel:
             variants["caf+cancel"] = lambda: _mean(caf_cancel, lambda: None, a.reps)
+        def toggled(e, desc):
+            # the setter (it waits, and allocates) and one submit outside the clock: on and off are the SAME object, because two
+            # objects of one configuration differ by as much as the stage costs
+            def fn():
+                e.set_integrate(desc)
+                caf_integ(e)(0)
+                return _mean(caf_integ(e), lambda: None, a.reps)
+            return fn
+
+        for name, e in igs.items():
+            what = b.INTEGRATE_ARRAY | (b.INTEGRATE_BEAMS if name == "+integ bm" else 0)
+            variants[name.replace("+integ", "integ off")] = toggled(e, None)
+            variants[name] = toggled(e, idesc(what))
+        for name in ops:
+            variants[name] = lambda name=name: _mean(integ_op(name), lambda: None, a.reps)
+        for name, w in workers.items():
+            variants[name] = lambda w=w: asked(w)
         plan.submit(d_in.data_ptr(), seq=0, flags=b.REFNOISE_ENABLED, nblocks=T, block_stride=nrows * B)      # lags and phasors for the locked submits
         plan.sync()
         for fn in variants.values():             # warm-up: code objects, allocations
@@ -313,6 +405,18 @@ def main():
                 note = f"  ({(T // FRAMES) * (128 * 64 + 16) / 1e3:.1f} kB)"
             if k == "get lists":
                 note = f"  ({(T // FRAMES) * (nrows + 1) * (64 * 32 + 4) / 1e3:.1f} kB)"
+            if k in igs:
+                lcells, maps = nd * lags, 1 + (len(wts) if k == "+integ bm" else 0)
+                off = k.replace("+integ", "integ off")
+                bts, over = maps * lcells * (8 * (T // FRAMES) + 16), med - shape["ms"][off]["median"]
+                note = (f"  ({over:+.4f} ms behind '{off}', the same object: {bts / 1e6:.2f} MB in {maps > 1 and 'two launches' or 'one launch'}, "
+                        f"{f'{bts / over / 1e6:.1f} GB/s over the difference' if over > 0.002 else 'a difference inside the spread'}; the array-map kernel reads {(T // FRAMES) * (nrows - 1) * lcells * 8 / 1e6:.1f} MB)")
+            if k in ops:
+                L, n = ops[k][:2]
+                bts = n * nd * lags * (8 * L + 16)
+                note = f"  ({L} lines of {n} maps, {bts / 1e6:.2f} MB: {bts / (med * 1e-3) / 1e9:.1f} GB/s with the launch and its wait)"
+            if k in workers:
+                note = f"  ({med - shape['ms']['caf']['median']:+.4f} ms against this process's caf)"
             if k == "get chi":
                 note = f"  ({8 * cells / 1e6:.1f} MB)"
             if k == "get cfar":
@@ -347,8 +451,12 @@ def main():
             e.close()
         for e, _, _ in bms.values():
             e.close()
-        for e in trs.values():
+        for e in list(trs.values()) + list(igs.values()):
             e.close()
+        for w in workers.values():
+            w.stdin.close()
+            w.wait(timeout=60)
+        ops.clear()
         sp.close()
         host.close()
         plan.close()
