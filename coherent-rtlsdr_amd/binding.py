@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "crsdr_caf_set_cancel", "crsdr_caf_fetch_cancel", "crsdr_caf_cancel_device_buffers", "crsdr_ambiguity_cancel",
     "crsdr_caf_set_bearing", "crsdr_caf_fetch_bearing", "crsdr_caf_bearing_device_buffers", "crsdr_bearing",
     "crsdr_caf_set_beams", "crsdr_caf_fetch_beams", "crsdr_caf_beams_device_buffers", "crsdr_beam_maps", "crsdr_beam_fuse", "crsdr_caf_beam_steer",
+    "crsdr_caf_set_beam_adapt", "crsdr_caf_fetch_beam_adapt", "crsdr_caf_beam_adapt_device_buffers", "crsdr_beam_adapt",
     "crsdr_caf_set_track", "crsdr_caf_track_reset", "crsdr_caf_fetch_track", "crsdr_caf_track_device_buffers", "crsdr_track_state_bytes", "crsdr_track",
     "crsdr_caf_set_integrate", "crsdr_caf_integrate_reset", "crsdr_caf_fetch_integrate", "crsdr_caf_integrate_device_buffers",
     "crsdr_map_integrate_state_bytes", "crsdr_map_integrate",
@@ -158,6 +159,12 @@ class BearingDesc(C.Structure):
 class BeamsDesc(C.Structure):
     """crsdr_caf_beams_desc: nbeams weight rows [nbeams][m][2] float32 on the host (copied by the call), and the flags (none yet)."""
     _fields_ = [("nbeams", C.c_int32), ("weights", C.POINTER(C.c_float)), ("flags", C.c_uint32)]
+
+
+class BeamAdaptDesc(C.Structure):
+    """crsdr_caf_beam_adapt_desc: the training rectangle of a line -- Doppler bins (d_lo + a) mod nd, a < d_n, lags r_lo + b, b < r_n --
+    the diagonal loading relative to trace(Q) / m, and the flags (none yet)."""
+    _fields_ = [("d_lo", C.c_int32), ("d_n", C.c_int32), ("r_lo", C.c_int32), ("r_n", C.c_int32), ("loading", C.c_float), ("flags", C.c_uint32)]
 
 
 class TrackDesc(C.Structure):
@@ -357,6 +364,11 @@ def lib():
         L.crsdr_beam_maps.argtypes = [f32p, f32p] + [C.c_int] * 4 + [f32p, C.c_int, C.c_int]
         L.crsdr_beam_fuse.argtypes = [f32p, i32p, f32p, i32p] + [C.c_int] * 5
         L.crsdr_caf_beam_steer.argtypes = [f32p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int]
+    if hasattr(L, "crsdr_beam_adapt"):               # (likewise: an older build has no adaptive beams)
+        L.crsdr_caf_set_beam_adapt.argtypes = [vp, C.POINTER(BeamAdaptDesc)]
+        L.crsdr_caf_fetch_beam_adapt.argtypes = [vp, f32p, f32p, i32p]
+        L.crsdr_caf_beam_adapt_device_buffers.argtypes = [vp] + [C.POINTER(vp)] * 3
+        L.crsdr_beam_adapt.argtypes = [f32p, f32p, i32p, f32p] + [C.c_int] * 4 + [f32p, C.c_int, C.POINTER(BeamAdaptDesc), C.c_int]
     if hasattr(L, "crsdr_track"):                    # (likewise: an older build has no tracker)
         L.crsdr_caf_set_track.argtypes = [vp, C.POINTER(TrackDesc)]
         L.crsdr_caf_track_reset.argtypes = [vp]
@@ -871,6 +883,31 @@ def beam_maps_device(bmap_ptr: int, chi_ptr: int, nrows, nd, R, ref_row, weights
     w = np.ascontiguousarray(weights, dtype=np.complex64)
     _check(lib().crsdr_beam_maps(cast(bmap_ptr, C.c_float), cast(chi_ptr, C.c_float), int(nrows), int(nd), int(R), int(ref_row), _p(w.view(np.float32), C.c_float),
                                  int(w.shape[0]), MEM_DEVICE))
+
+
+def beam_adapt_desc(loading, d_lo, d_n, r_lo, r_n, flags=0):
+    return BeamAdaptDesc(int(d_lo), int(d_n), int(r_lo), int(r_n), float(loading), int(flags))
+
+
+def beam_adapt(chi, weights, desc: "BeamAdaptDesc", ref_row=0):
+    """crsdr_beam_adapt on ONE line: chi [nrows][nd][R] complex64, weights [nbeams][nrows - 1] complex64 -> (aw [nbeams][nrows - 1]
+    complex64, ainfo [nbeams][2] float32, astat int).  The engine's adaptive weights (Caf.set_beam_adapt) on one line, bit for bit;
+    beam_maps(chi, aw) is then the line's bmap."""
+    a = np.ascontiguousarray(chi, dtype=np.complex64)
+    w = np.ascontiguousarray(weights, dtype=np.complex64)
+    nrows, nd, R = a.shape
+    aw, info, stat = np.zeros(w.shape, dtype=np.complex64), np.zeros((w.shape[0], 2), dtype=np.float32), np.zeros(1, dtype=np.int32)
+    _check(lib().crsdr_beam_adapt(_p(aw.view(np.float32), C.c_float), _p(info, C.c_float), _p(stat, C.c_int32), _p(a.view(np.float32), C.c_float), nrows, nd, R, int(ref_row),
+                                  _p(w.view(np.float32), C.c_float), int(w.shape[0]), C.byref(desc), MEM_HOST))
+    return aw, info, int(stat[0])
+
+
+def beam_adapt_device(aw_ptr: int, ainfo_ptr: int, astat_ptr: int, chi_ptr: int, nrows, nd, R, ref_row, weights, desc: "BeamAdaptDesc"):
+    """crsdr_beam_adapt with CRSDR_MEM_DEVICE: aw, ainfo, astat (any but not all may be 0) and chi on the device, the weights on the host."""
+    cast = lambda p, t: C.cast(C.c_void_p(int(p) or None), C.POINTER(t))
+    w = np.ascontiguousarray(weights, dtype=np.complex64)
+    _check(lib().crsdr_beam_adapt(cast(aw_ptr, C.c_float), cast(ainfo_ptr, C.c_float), cast(astat_ptr, C.c_int32), cast(chi_ptr, C.c_float), int(nrows), int(nd), int(R),
+                                  int(ref_row), _p(w.view(np.float32), C.c_float), int(w.shape[0]), C.byref(desc), MEM_DEVICE))
 
 
 def beam_fuse(bdet, bcount, nd, R):
@@ -1727,6 +1764,26 @@ class Caf:
         nf = np.zeros(n, dtype=np.int32) if lists else None
         _check(lib().crsdr_caf_fetch_beams(self._h, _p(m, C.c_float), _p(d, C.c_float), _p(c, C.c_int32), _p(f, C.c_float), _p(nf, C.c_int32)))
         return {k: v for k, v in (("bmap", m), ("bdet", d), ("bcount", c), ("fused", f), ("nfused", nf)) if v is not None}
+
+    def set_beam_adapt(self, desc: "BeamAdaptDesc | None"):
+        """crsdr_caf_set_beam_adapt: per line MVDR weights from the covariance of the line's own training cells in place of the beams'
+        weights (None: off).  Between submits, with beams on and the integration and the tracker off; every set_beams turns it off."""
+        _check(lib().crsdr_caf_set_beam_adapt(self._h, None if desc is None else C.byref(desc)))
+
+    def fetch_beam_adapt(self, aw=True, ainfo=True, astat=True) -> dict:
+        """Waits for the last submit.  aw [nest][nb][nrows - 1] complex64, ainfo [nest][nb][2] = the training cells' mean power through
+        the adaptive beam and through the caller's, astat [nest] int32 (0, or the fallback's bits)."""
+        n, nb = self._last()[0], max(1, getattr(self, "nbeams", 0))
+        w = np.zeros((n, nb, self.nrows - 1), dtype=np.complex64) if aw else None
+        i = np.zeros((n, nb, 2), dtype=np.float32) if ainfo else None
+        s = np.zeros(n, dtype=np.int32) if astat else None
+        _check(lib().crsdr_caf_fetch_beam_adapt(self._h, _p(None if w is None else w.view(np.float32), C.c_float), _p(i, C.c_float), _p(s, C.c_int32)))
+        return {k: v for k, v in (("aw", w), ("ainfo", i), ("astat", s)) if v is not None}
+
+    def beam_adapt_device_buffers(self) -> dict:
+        ptrs = [C.c_void_p() for _ in range(3)]
+        _check(lib().crsdr_caf_beam_adapt_device_buffers(self._h, *[C.byref(p) for p in ptrs]))
+        return dict(zip(("aw", "ainfo", "astat"), [p.value for p in ptrs]))
 
     def beams_device_buffers(self) -> dict:
         ptrs = [C.c_void_p() for _ in range(5)]

@@ -46,14 +46,16 @@ __device__ inline void beam_step(const float2 *tab, int e, int col, int k, float
     }
 }
 
-// chi [nest][nrows][cells] float2, w [nbeams][m][2], bmap [nest][nbeams][cells]
+// chi [nest][nrows][cells] float2, w [nbeams][m][2] of line 0 and wstride floats from line to line (0: one set for every line;
+// nbeams m 2: the adaptive weights of caf_adapt_kernels.hpp), bmap [nest][nbeams][cells]
 template <int NG>
-__global__ __launch_bounds__(THREADS) void k_caf_beams(const float2 *__restrict__ chi, const float *__restrict__ w, int nrows, int cells, int ref_row, int nbeams,
-                                                       float *__restrict__ bmap)
+__global__ __launch_bounds__(THREADS) void k_caf_beams(const float2 *__restrict__ chi, const float *__restrict__ w0, size_t wstride, int nrows, int cells, int ref_row,
+                                                       int nbeams, float *__restrict__ bmap)
 {
     extern __shared__ float2 tab[];                                              // [m][32 NG]: (wr, wi) of beam b at element e; zeros past nbeams
     constexpr int NB = NG * bm::GROUP;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, m = nrows - 1, e_line = blockIdx.y;
+    const float *w = w0 + (size_t)e_line * wstride;
     for (int x = tid; x < m * NB; x += THREADS) {
         const int e = x / NB, b = x - e * NB;
         tab[x] = b < nbeams ? make_float2(w[2 * ((size_t)b * m + e)], w[2 * ((size_t)b * m + e) + 1]) : make_float2(0.f, 0.f);

@@ -12,6 +12,8 @@
 //     With beams set (crsdr_caf_set_beams; caf_beams.hpp, caf_beams_kernels.hpp) one more: every beam's map across the rows on the fp32
 //     matrix pipe; with the detector on three more behind it: the detector's two on the beam maps, (line, beam) taking the place of
 //     the line, and the fusion of the beams' lists into one per line.
+//     With adaptation set (crsdr_caf_set_beam_adapt; caf_adapt.hpp, caf_adapt_kernels.hpp) two more ahead of the beam maps: the training
+//     cells' covariance per line on the fp64 matrix pipe, and the line's solve, whose weights the beam kernel then reads.
 //     With the tracker set (crsdr_caf_set_track; caf_track.hpp, caf_track_kernels.hpp) one more behind everything else: one workgroup
 //     that walks the lines of the submit and carries the tracks from submit to submit.
 //     With integration set (crsdr_caf_set_integrate; caf_integrate.hpp, caf_integrate_solve.hpp) one more behind the array map, whose
@@ -26,6 +28,7 @@
 #pragma once
 
 #include "caf.hpp"
+#include "caf_adapt_kernels.hpp"
 #include "caf_beams_kernels.hpp"
 #include "caf_bearing.hpp"
 #include "caf_cancel.hpp"
@@ -63,7 +66,7 @@ struct CancelBufs {
 
 // what the last submit left: where, how much, and which features ran (kCafRan*).  A setter clears its feature's bit: "nothing submitted
 // since"; without kCafRanBase nothing is left at all
-constexpr unsigned kCafRanBase = 1u, kCafRanCancel = 2u, kCafRanCfar = 4u, kCafRanBearing = 8u, kCafRanBeams = 16u, kCafRanTrack = 32u, kCafRanIntegrate = 64u;
+constexpr unsigned kCafRanBase = 1u, kCafRanCancel = 2u, kCafRanCfar = 4u, kCafRanBearing = 8u, kCafRanBeams = 16u, kCafRanTrack = 32u, kCafRanIntegrate = 64u, kCafRanAdapt = 128u;
 struct CafLast {
     hipStream_t stream = nullptr;
     int nest = 0, launches = 0;
@@ -112,6 +115,14 @@ struct crsdr_caf {
         DevBuf<int32_t> bcount, nfused, tcount;
         DevBuf<cfar::Cand> slots;
     } bb;
+    // crsdr_caf_set_beam_adapt: on (false = off), the tiles' sums [lines][tiles][m (m + 1) / 2], the lines' weights, figures and status
+    struct Adapt {
+        bool on = false;
+        ad::Params prm{};
+        DevBuf<double2> part;
+        DevBuf<float> aw, ainfo;
+        DevBuf<int32_t> astat;
+    } ba;
     // crsdr_caf_set_track: on (false = off), the state that a submit hands to the next, and the results
     struct Track {
         bool on = false;
@@ -349,12 +360,42 @@ static int beams_args_ok(const char *who, int nrows, long long lines, int nd, in
     }
 }
 
-// the beam maps' one launch, for the object and for crsdr_beam_maps: the same kernel on the same arguments, so the same bits
-static int beam_maps_enqueue(CafRun &r, const float2 *chi, const float *w, int nest, int nrows, int cells, int ref_row, int nb, float *bmap)
+// every limit of the adaptive beams of section (w), for crsdr_caf_set_beam_adapt and crsdr_beam_adapt
+static int adapt_args_ok(const char *who, int nrows, int nd, int R, const crsdr_caf_beam_adapt_desc *d, ad::Params *prm)
+{
+    *prm = ad::Params{d->d_lo, d->d_n, d->r_lo, d->r_n, d->loading, d->flags};
+    switch (ad::bad_limit(nrows, nd, R, *prm)) {
+    case 0: return CRSDR_OK;
+    case 1: return fail(CRSDR_EINVAL, "%s: m = nrows - 1 = %d (1..%d)", who, nrows - 1, ad::MAX_M);
+    case 2: return fail(CRSDR_EINVAL, "%s: d_lo = %d (0..nd - 1 = %d)", who, d->d_lo, nd - 1);
+    case 3: return fail(CRSDR_EINVAL, "%s: d_n = %d (1..nd = %d)", who, d->d_n, nd);
+    case 4: return fail(CRSDR_EINVAL, "%s: r_lo = %d (not negative)", who, d->r_lo);
+    case 5: return fail(CRSDR_EINVAL, "%s: r_n = %d (at least 1)", who, d->r_n);
+    case 6: return fail(CRSDR_EINVAL, "%s: r_lo + r_n = %d + %d (at most R = %d)", who, d->r_lo, d->r_n, R);
+    case 7: return fail(CRSDR_EINVAL, "%s: loading = %g (1e-6..1)", who, (double)d->loading);
+    default: return fail(CRSDR_EINVAL, "%s: flags = 0x%x (none yet)", who, d->flags);
+    }
+}
+
+// the adaptive weights' two launches, for the object and for crsdr_beam_adapt: the same kernels on the same arguments, so the same bits
+static int beam_adapt_enqueue(CafRun &r, const float2 *chi, const float *w, int nest, int nrows, int nd, int R, int ref_row, int nb, const ad::Params &prm, double2 *part,
+                              float *aw, float *ainfo, int32_t *astat)
+{
+    const int m = nrows - 1;
+    const int rc = caf_run(r, caf_adapt::k_caf_beam_cov, dim3((unsigned)ad::tiles_of(ad::cells_of(prm)), (unsigned)nest), dim3(caf_adapt::THREADS), 0, chi, nrows, nd, R, ref_row,
+                           prm, part);
+    if (rc) return rc;
+    return caf_run(r, caf_adapt::k_caf_beam_adapt, dim3((unsigned)nest), dim3(caf_adapt::THREADS), caf_adapt::adapt_lds_bytes(m), (const double2 *)part, w, m, nb, prm, aw, ainfo,
+                   astat);
+}
+
+// the beam maps' one launch, for the object and for crsdr_beam_maps: the same kernel on the same arguments, so the same bits.
+// wstride: 0 for one set of weights, nb m 2 for a set per line (the adaptive ones)
+static int beam_maps_enqueue(CafRun &r, const float2 *chi, const float *w, size_t wstride, int nest, int nrows, int cells, int ref_row, int nb, float *bmap)
 {
     const dim3 grid((unsigned)((cells + caf_beams::WG_CELLS - 1) / caf_beams::WG_CELLS), (unsigned)nest);
     return caf_run(r, caf_beams::groups_of(nb) == 1 ? caf_beams::k_caf_beams<1> : caf_beams::k_caf_beams<2>, grid, dim3(caf_beams::THREADS),
-                   caf_beams::table_bytes(nrows - 1, nb), chi, w, nrows, cells, ref_row, nb, bmap);
+                   caf_beams::table_bytes(nrows - 1, nb), chi, w, wstride, nrows, cells, ref_row, nb, bmap);
 }
 
 // the fusion's one launch, for the object and for crsdr_beam_fuse
@@ -412,13 +453,14 @@ static int integrate_enqueue(CafRun &r, const float *maps, int nlines, int nmaps
                    nlines, nmaps, nd, R, nb, prm, state, imap);
 }
 
-// The two dynamic LDS limits above the 64 KiB default, k_bearing_slot's and k_caf_track's, are function attributes of the current
-// device, shared by every live object: each create sets both to the most any object can ask for, so that no call lowers a limit under
-// another and no setter has to think of them.  crsdr_bearing and crsdr_track do the same for their calls.
+// The three dynamic LDS limits above the 64 KiB default, k_bearing_slot's, k_caf_track's and k_caf_beam_adapt's, are function attributes of the current
+// device, shared by every live object: each create sets all three to the most any object can ask for, so that no call lowers a limit under
+// another and no setter has to think of them.  crsdr_bearing, crsdr_track and crsdr_beam_adapt do the same for their calls.
 static int caf_lds_limits()
 {
     HIP_TRY(hipFuncSetAttribute((const void *)bearing::k_bearing_slot, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bearing::slot_lds_bytes(brg::MAX_M, cfar::MAX_HR)));
     HIP_TRY(hipFuncSetAttribute((const void *)caf_track::k_caf_track, hipFuncAttributeMaxDynamicSharedMemorySize, (int)caf_track::lds_bytes(trk::MAX_TRACKS, trk::MAX_MEAS)));
+    HIP_TRY(hipFuncSetAttribute((const void *)caf_adapt::k_caf_beam_adapt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)caf_adapt::adapt_lds_bytes(ad::MAX_M)));
     return CRSDR_OK;
 }
 
@@ -451,7 +493,7 @@ static int caf_clear(crsdr_caf *q, Feature &f, unsigned ran_bit)
 // Who must be off before whom, who must be on before whom: every rule of the setters, each feature's in the order they are asked.
 // must_be_on false: `feature` is not changed, set or turned off, while `other` is on, which works on its buffers and parameters (asked
 // ahead of the descriptor's limits).  true: `feature` is not set while `other` is off (asked behind them, and not to turn it off).
-enum { kCafCfar, kCafBearing, kCafBeams, kCafBeamLists, kCafTrack, kCafIntegrate, kCafTrackFused, kCafCfarEst, kCafIntegrateBeams };
+enum { kCafCfar, kCafBearing, kCafBeams, kCafBeamLists, kCafTrack, kCafIntegrate, kCafTrackFused, kCafCfarEst, kCafIntegrateBeams, kCafAdapt };
 static const struct CafRule { int feature; bool must_be_on; int other; const char *refusal; } kCafRules[] = {
     {kCafCfar, false, kCafTrack, "caf_set_cfar: the tracker is on (crsdr_caf_set_track): its measurements are this detector's lists; turn it off first"},
     {kCafCfar, false, kCafBeams, "caf_set_cfar: beams are on (crsdr_caf_set_beams): whether they are detected on, and the lists' sizes, are this detector's; turn them off first"},
@@ -464,6 +506,9 @@ static const struct CafRule { int feature; bool must_be_on; int other; const cha
     {kCafBearing, true, kCafCfar, "caf_set_bearing: no detector set (crsdr_caf_set_cfar): there are no detections to take a bearing of"},
     {kCafBeams, false, kCafTrack, "caf_set_beams: the tracker is on (crsdr_caf_set_track): the fused list may be its source; turn it off first"},
     {kCafBeams, false, kCafIntegrate, "caf_set_beams: integration is on (crsdr_caf_set_integrate): the beam maps' state has their number and size; turn it off first"},
+    {kCafAdapt, false, kCafTrack, "caf_set_beam_adapt: the tracker is on (crsdr_caf_set_track): its state belongs to the maps this changes; turn it off first"},
+    {kCafAdapt, false, kCafIntegrate, "caf_set_beam_adapt: integration is on (crsdr_caf_set_integrate): its state belongs to the maps this changes; turn it off first"},
+    {kCafAdapt, true, kCafBeams, "caf_set_beam_adapt: no beams set (crsdr_caf_set_beams): the adaptation belongs to their descriptor"},
     {kCafTrack, true, kCafCfar, "caf_set_track: no detector set (crsdr_caf_set_cfar): there are no detections to track"},
     {kCafTrackFused, true, kCafBeamLists, "caf_set_track: the fused source needs beams with detection (crsdr_caf_set_beams behind crsdr_caf_set_cfar)"},
     {kCafIntegrate, false, kCafTrack, "caf_set_integrate: the tracker is on (crsdr_caf_set_track): its measurements are the lists of the maps this changes; turn it off first"},
@@ -557,7 +602,12 @@ static int caf_stage_beams(crsdr_caf *q, CafRun &r)
 {
     crsdr_caf::Beams &g = q->bb;
     if (!g.on) return CRSDR_OK;
-    return beam_maps_enqueue(r, q->chi, g.w, r.nest, q->nrows, q->nd * q->nlags, q->ref_row, g.nb, g.bmap);
+    crsdr_caf::Adapt &a = q->ba;
+    if (!a.on) return beam_maps_enqueue(r, q->chi, g.w, 0, r.nest, q->nrows, q->nd * q->nlags, q->ref_row, g.nb, g.bmap);
+    // the lines' own weights first: two launches whatever the batch, and the maps read aw line by line
+    const int rc = beam_adapt_enqueue(r, q->chi, g.w, r.nest, q->nrows, q->nd, q->nlags, q->ref_row, g.nb, a.prm, a.part, a.aw, a.ainfo, a.astat);
+    if (rc) return rc;
+    return beam_maps_enqueue(r, q->chi, a.aw, (size_t)g.nb * (size_t)(q->nrows - 1) * 2, r.nest, q->nrows, q->nd * q->nlags, q->ref_row, g.nb, g.bmap);
 }
 
 // the beam maps across the lines, (line, beam) in bmap's order: one launch (the state's block behind the array map's, if that is there)
@@ -606,7 +656,7 @@ static int caf_launch(crsdr_caf *q, const int8_t *packets, size_t packet_stride,
     // stand for whole stages only.
     if (r.launches)
         q->last = CafLast{S, r.nest, r.launches, rc ? kCafRanBase : kCafRanBase | (q->cn.on ? kCafRanCancel : 0u) | (q->cf.on ? kCafRanCfar : 0u) | (q->bg.on ? kCafRanBearing : 0u) |
-                                                                      (q->bb.on ? kCafRanBeams : 0u) | (q->tk.on ? kCafRanTrack : 0u) | (q->ig.on ? kCafRanIntegrate : 0u)};
+                                                                      (q->bb.on ? kCafRanBeams : 0u) | (q->tk.on ? kCafRanTrack : 0u) | (q->ig.on ? kCafRanIntegrate : 0u) | (q->ba.on ? kCafRanAdapt : 0u)};
     return rc;
 }
 
@@ -901,6 +951,7 @@ extern "C" int crsdr_caf_set_beams(crsdr_caf *q, const crsdr_caf_beams_desc *des
     { const int rc = caf_rules(q, kCafBeams, false); if (rc) return rc; }
     const size_t lines = q->lines(), cells = (size_t)q->nd * (size_t)q->nlags, m = (size_t)(q->nrows - 1);
     if (desc) { const int rc_ = beams_args_ok("caf_set_beams", q->nrows, (long long)lines, q->nd, q->nlags, desc->nbeams, desc->weights, desc->flags); if (rc_) return rc_; }
+    { const int rc = caf_clear(q, q->ba, kCafRanAdapt); if (rc) return rc; }       // the adaptation belongs to the descriptor that goes
     { const int rc = caf_clear(q, q->bb, kCafRanBeams); if (rc || !desc) return rc; }
     const size_t nb = (size_t)desc->nbeams, maps = lines * nb;
     crsdr_caf::Beams f;
@@ -957,8 +1008,80 @@ extern "C" int crsdr_beam_maps(float *bmap, const float *chi, int nrows, int nd,
     OP_RESERVE(2, wb);                                      // (the weights are the host's in either kind)
     HIP_TRY(hipMemcpy(g_op.buf[2], weights, wb, hipMemcpyHostToDevice));
     CafRun r{nullptr};
-    { const int rc_ = beam_maps_enqueue(r, d_c, (const float *)g_op.buf[2], 1, nrows, (int)cells, ref_row, nbeams, d_m); if (rc_) return rc_; }
+    { const int rc_ = beam_maps_enqueue(r, d_c, (const float *)g_op.buf[2], 0, 1, nrows, (int)cells, ref_row, nbeams, d_m); if (rc_) return rc_; }
     st.back(bmap, d_m, mb);
+    return st.finish();
+}
+
+// ---- the adaptive beams ----
+extern "C" int crsdr_caf_set_beam_adapt(crsdr_caf *q, const crsdr_caf_beam_adapt_desc *desc)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_set_beam_adapt: NULL caf");
+    { const int rc = caf_rules(q, kCafAdapt, false); if (rc) return rc; }
+    ad::Params prm{};
+    if (desc) {
+        { const int rc_ = adapt_args_ok("caf_set_beam_adapt", q->nrows, q->nd, q->nlags, desc, &prm); if (rc_) return rc_; }
+        { const int rc = caf_rules(q, kCafAdapt, true); if (rc) return rc; }
+    }
+    { const int rc = caf_clear(q, q->ba, kCafRanAdapt); if (rc || !desc) return rc; }
+    const size_t lines = q->lines(), m = (size_t)(q->nrows - 1), nb = (size_t)q->bb.nb;
+    crsdr_caf::Adapt f;
+    f.prm = prm; f.on = true;
+    int r = CRSDR_OK;
+    if ((r = f.part.alloc(lines * (size_t)ad::tiles_of(ad::cells_of(prm)) * (size_t)ad::pairs_of((int)m))) || (r = f.aw.alloc(lines * nb * m * 2)) ||
+        (r = f.ainfo.alloc(lines * nb * 2)) || (r = f.astat.alloc(lines)))
+        return r;
+    q->ba = std::move(f);
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_fetch_beam_adapt(crsdr_caf *q, float *aw, float *ainfo, int32_t *astat)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_fetch_beam_adapt: NULL caf");
+    if (!q->ba.on) return fail(CRSDR_ESTATE, "caf_fetch_beam_adapt: no adaptation set (crsdr_caf_set_beam_adapt)");
+    if (!(q->last.ran & kCafRanAdapt)) return fail(CRSDR_ESTATE, "caf_fetch_beam_adapt: nothing submitted since the adaptation was set");
+    const size_t lines = (size_t)q->last.nest, nb = (size_t)q->bb.nb, m = (size_t)(q->nrows - 1);
+    return DevFetch(q->device, q->last.stream).copy(aw, q->ba.aw.p, lines * nb * m * 2).copy(ainfo, q->ba.ainfo.p, lines * nb * 2).copy(astat, q->ba.astat.p, lines).wait();
+}
+
+extern "C" int crsdr_caf_beam_adapt_device_buffers(crsdr_caf *q, void **aw, void **ainfo, void **astat)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_beam_adapt_device_buffers: NULL caf");
+    if (!q->ba.on) return fail(CRSDR_ESTATE, "caf_beam_adapt_device_buffers: no adaptation set (crsdr_caf_set_beam_adapt)");
+    if (aw) *aw = q->ba.aw;
+    if (ainfo) *ainfo = q->ba.ainfo;
+    if (astat) *astat = q->ba.astat;
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_beam_adapt(float *aw, float *ainfo, int32_t *astat, const float *chi, int nrows, int nd, int R, int ref_row, const float *weights, int nbeams,
+                                const crsdr_caf_beam_adapt_desc *desc, int mem_kind)
+{
+    if (!chi || !desc || (!aw && !ainfo && !astat)) return fail(CRSDR_EINVAL, "beam_adapt: need chi, a descriptor and at least one of aw, ainfo, astat");
+    { const int rc_ = caf_shape_ok("beam_adapt", nd, R, 0, ref_row, nrows, false); if (rc_) return rc_; }
+    { const int rc_ = beams_args_ok("beam_adapt", nrows, 1, nd, R, nbeams, weights, 0u); if (rc_) return rc_; }
+    ad::Params prm{};
+    { const int rc_ = adapt_args_ok("beam_adapt", nrows, nd, R, desc, &prm); if (rc_) return rc_; }
+    OP_PROLOGUE_MEM("beam_adapt", mem_kind);
+    const size_t cells = (size_t)nd * (size_t)R, m = (size_t)(nrows - 1), nb = (size_t)nbeams, cb = sizeof(float2) * (size_t)nrows * cells;
+    const size_t wb = sizeof(float) * 2 * nb * m, ib = sizeof(float) * 2 * nb, sb = sizeof(int32_t);
+    OpStage st(mem_kind);
+    const float2 *d_c = (const float2 *)st.in(0, chi, cb, 8);
+    float *d_w = (float *)st.out(1, aw, wb, 4);
+    float *d_i = (float *)st.out(2, ainfo, ib, 4);
+    int32_t *d_s = (int32_t *)st.out(3, astat, sb, 4);
+    if (st.rc) return st.rc;
+    if (st.misaligned) return fail(CRSDR_EINVAL, "beam_adapt: device aw, ainfo and astat 4-byte, chi 8-byte aligned");
+    if (st.spare(1, d_w, wb) || st.spare(2, d_i, ib) || st.spare(3, d_s, sb)) return st.rc;
+    OP_RESERVE(4, wb);                                      // (the weights are the host's in either kind)
+    HIP_TRY(hipMemcpy(g_op.buf[4], weights, wb, hipMemcpyHostToDevice));
+    OP_RESERVE(5, sizeof(double2) * (size_t)ad::tiles_of(ad::cells_of(prm)) * (size_t)ad::pairs_of((int)m));
+    { const int rc_ = caf_lds_limits(); if (rc_) return rc_; }
+    CafRun r{nullptr};
+    { const int rc_ = beam_adapt_enqueue(r, d_c, (const float *)g_op.buf[4], 1, nrows, nd, R, ref_row, nbeams, prm, (double2 *)g_op.buf[5], d_w, d_i, d_s); if (rc_) return rc_; }
+    st.back(aw, d_w, wb);
+    st.back(ainfo, d_i, ib);
+    st.back(astat, d_s, sb);
     return st.finish();
 }
 

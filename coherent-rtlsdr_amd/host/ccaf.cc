@@ -102,7 +102,7 @@ int batch::fetch_bearing(bool want_spec)
 int batch::set_beams(const crsdr_caf_beams_desc *desc)
 {
     int rc = cf ? crsdr_caf_set_beams(cf, desc) : CRSDR_ESTATE;
-    if (!rc) { nb = desc ? desc->nbeams : 0; beam_lists = desc && kdet > 0; bmap.clear(); bdet.clear(); bcount.clear(); fused.clear(); nfused.clear(); }
+    if (!rc) { nb = desc ? desc->nbeams : 0; beam_lists = desc && kdet > 0; adapt = false; aw.clear(); ainfo.clear(); astat.clear(); bmap.clear(); bdet.clear(); bcount.clear(); fused.clear(); nfused.clear(); }
     if (rc && cf) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
     return rc;
 }
@@ -122,6 +122,29 @@ int batch::fetch_beams(bool want_bmap, bool want_lists)
     }
     if (!rc) nlines = nest;
     if (rc && cf && nb) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::set_beam_adapt(const crsdr_caf_beam_adapt_desc *desc)
+{
+    int rc = cf ? crsdr_caf_set_beam_adapt(cf, desc) : CRSDR_ESTATE;
+    if (!rc) { adapt = desc != nullptr; aw.clear(); ainfo.clear(); astat.clear(); }
+    if (rc && cf) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::fetch_beam_adapt(bool want_aw)
+{
+    int nest = 0;
+    int rc = !cf || !adapt ? CRSDR_ESTATE : crsdr_caf_last_submit(cf, &nest, nullptr);
+    if (!rc) {
+        const size_t beams = (size_t)nest * nb;
+        aw.assign(want_aw ? beams * (rows - 1) * 2 : 0, 0.f);
+        ainfo.assign(beams * 2, 0.f); astat.assign((size_t)nest, 0);
+        rc = crsdr_caf_fetch_beam_adapt(cf, want_aw ? aw.data() : nullptr, ainfo.data(), astat.data());
+    }
+    if (!rc) nlines = nest;
+    if (rc && cf && adapt) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
     return rc;
 }
 

@@ -49,7 +49,7 @@ struct track_t {
 class batch {
     crsdr_caf *cf = nullptr;
     int rows, bins, lags, kdet = 0, nbasis = 0, npts = 0;
-    bool bearings = false, beam_lists = false;
+    bool bearings = false, beam_lists = false, adapt = false;
     int nb = 0, ntracks = 0, iwhat = 0;
 
 public:
@@ -87,6 +87,13 @@ public:
     // waits, and fills fused and nfused (with the detector), and bmap, bdet and bcount if asked for; CRSDR_ESTATE with the beams off
     int fetch_beams(bool want_bmap = false, bool want_lists = false);
     int nbeams() const { return nb; }
+    // per line MVDR weights from the covariance of the line's own training cells in place of the beams' weights
+    // (crsdr_caf_set_beam_adapt; NULL: off).  Between submits, with beams on and the integration and the tracker off; every
+    // set_beams turns it off again.
+    int set_beam_adapt(const crsdr_caf_beam_adapt_desc *desc);
+    // waits, and fills ainfo and astat, and aw if asked for; CRSDR_ESTATE with the adaptation off
+    int fetch_beam_adapt(bool want_aw = false);
+    bool adaptive() const { return adapt; }
     // the tracker behind every later submit's lists (crsdr_caf_set_track; NULL: off), its table empty.  Between submits, with the
     // detector on (the fused source: with beams detected on); while it is on set_cfar, set_bearing and set_beams are refused.
     int set_track(const crsdr_caf_track_desc *desc);
@@ -127,6 +134,9 @@ public:
     std::vector<int32_t> nfused;                     // [lines]: the survivors of the fusion, which may be more than max_det
     int fused_held(int e) const { return beam_lists ? (nfused[(size_t)e] < kdet ? nfused[(size_t)e] : kdet) : 0; }
     const fused_t &fused_at(int e, int k) const { return fused[(size_t)e * kdet + k]; }
+    std::vector<float> aw;                           // [lines][nbeams][nrows - 1][2]: the adaptive weights, where asked for
+    std::vector<float> ainfo;                        // [lines][nbeams][2]: the training cells' mean power through the adaptive beam and the caller's
+    std::vector<int32_t> astat;                      // [lines]: 0, or the fallback's bits
     std::vector<track_t> trk;                        // [lines][max_tracks]: every slot of every line; free slots zero
     std::vector<int32_t> ntrk;                       // [lines][4]: live tracks after the line, confirmed, initiated, dropped
     const track_t &track_at(int e, int i) const { return trk[(size_t)e * ntracks + i]; }

@@ -74,6 +74,8 @@ int main(int argc, char **argv)
     crsdr_cfar_est_desc cfar_est = {CRSDR_CFAR_CA, 0, 0};
     bool cancel_on = false, bearing_on = false, beams_on = false;
     int beams_mx = 0, beams_my = 0, beams_nx = 0, beams_ny = 0;
+    bool adapt_on = false, adapt_region = false;
+    crsdr_caf_beam_adapt_desc adapt = {0, 0, 0, 0, 1e-2f, 0u};
     crsdr_caf_bearing_desc bearing = {0, 0, 100, 100, 0.5f, CRSDR_BEARING_CONVENTIONAL, 1e-2f, 0, 0u};
     crsdr_caf_cancel_desc cancel = {0, 0};
     bool track_on = false;
@@ -207,6 +209,15 @@ int main(int argc, char **argv)
             const int n = std::sscanf(argv[++i], "%dx%d:%dx%d", &beams_mx, &beams_my, &beams_nx, &beams_ny);
             beams_on = true;
             if (n != 4) beams_mx = -1;                                                       // (refused below with the rest)
+        }
+        // with --caf-beams: per line MVDR weights from the covariance of the line's own cells in place of the lattice's
+        // (crsdr_caf_set_beam_adapt).  The default region is the whole map less the zero-Doppler guard.  Prints per line the mean over
+        // the beams of 10 log10(ainfo[b][0] / ainfo[b][1]): what the adaptation takes out of the training cells' power
+        else if (a == "--caf-adapt" && i + 1 < argc) {
+            const int n = std::sscanf(argv[++i], "%f:%d:%d:%d:%d", &adapt.loading, &adapt.d_lo, &adapt.d_n, &adapt.r_lo, &adapt.r_n);
+            adapt_on = true;
+            adapt_region = n == 5;
+            if (n != 1 && n != 5) adapt.loading = -1.f;                                      // (refused below)
         }
         // with --caf and --cfar: tracks across the lines from the detections (crsdr_caf_set_track): M-of-N confirmation, GATE on d2 (9),
         // --track-max T slots (16), --track-sigma SR:SF measurement deviations in cells and bins (0.5:0.5), --track-q QR:QF:QG process
@@ -674,6 +685,14 @@ int main(int argc, char **argv)
                 }
                 if (!good) { std::printf("beams: --caf-beams MXxMY:NXxNY refused (MX MY must be --nsig = %d, NX NY at most 64)\nDEMO FAILED\n", nsig); return 1; }
             }
+            if (adapt_on) {
+                if (!adapt_region) { adapt.d_lo = caf_guard + 1; adapt.d_n = caf->nd() - 2 * caf_guard - 1; adapt.r_lo = 0; adapt.r_n = caf->nlags(); }
+                if (!beams_on || caf->set_beam_adapt(&adapt)) {
+                    std::printf("adapt: --caf-adapt LOADING[:D_LO:D_N:R_LO:R_N] refused (it needs --caf-beams; LOADING in [1e-6, 1])\nDEMO FAILED\n");
+                    return 1;
+                }
+                std::printf("adapt: loading %g doppler %d+%d lags %d+%d\n", (double)adapt.loading, adapt.d_lo, adapt.d_n, adapt.r_lo, adapt.r_n);
+            }
             if (integrate_on && caf->set_integrate(&integrate)) { std::printf("integrate: --integrate W[:COUPLING] refused: %s\nDEMO FAILED\n", crsdr_last_error()); return 1; }
             if (integrate_on && !set_bearing()) return 1;
             if (track_on && caf->set_track(&track)) { std::printf("track: --track refused: %s\nDEMO FAILED\n", crsdr_last_error()); return 1; }
@@ -682,7 +701,7 @@ int main(int argc, char **argv)
             if (!caf || !ok) return;
             ok = caf->submit(coherent.engine_plan()) == CRSDR_OK && caf->fetch() == CRSDR_OK && (!cfar_on || caf->fetch_cfar() == CRSDR_OK) &&
                  (!cancel_on || caf->fetch_cancel(false) == CRSDR_OK) && (!bearing_on || caf->fetch_bearing() == CRSDR_OK) &&
-                 (!beams_on || caf->fetch_beams() == CRSDR_OK) && (!track_on || caf->fetch_track() == CRSDR_OK) &&
+                 (!beams_on || caf->fetch_beams() == CRSDR_OK) && (!adapt_on || caf->fetch_beam_adapt() == CRSDR_OK) && (!track_on || caf->fetch_track() == CRSDR_OK) &&
                  (!integrate_on || caf->fetch_integrate() == CRSDR_OK);
             if (!ok || !report) return;
             if (integrate_on) std::printf("integrate: batch %d: %d lines behind a window of %g%s\n", b, caf->lines(), integrate_window, cfar_on ? ": the detections are the integrated map's" : "");
@@ -706,6 +725,15 @@ int main(int argc, char **argv)
                     std::printf("bearing: batch %d line %d det %d: cell (%d, %d) alpha %.3f deg beta %.3f deg fit %.4f\n", b, e, k, (int)d.cx, (int)d.cy, d.alpha_deg(),
                                 d.beta_deg(), (double)d.fit);
                 }
+            for (int e = 0; adapt_on && e < caf->lines(); ++e) {
+                double sum = 0.0;
+                int n = 0;
+                for (int bm = 0; bm < caf->nbeams(); ++bm) {
+                    const float *f = &caf->ainfo[2 * ((size_t)e * caf->nbeams() + bm)];
+                    if (f[0] > 0.f && f[1] > 0.f) { sum += 10.0 * std::log10((double)f[0] / (double)f[1]); ++n; }
+                }
+                std::printf("adapt: batch %d line %d status %d mean gain %.2f dB over %d beams\n", b, e, (int)caf->astat[(size_t)e], n ? sum / n : 0.0, n);
+            }
             if (beams_on && !cfar_on) std::printf("beams: %d maps per line (no detector: --cfar fuses their detections)\n", caf->nbeams());
             for (int e = 0; beams_on && cfar_on && e < caf->lines(); ++e)
                 for (int k = 0; k < caf->fused_held(e); ++k) {

@@ -1423,6 +1423,58 @@ int crsdr_beam_fuse(float *fused, int32_t *nfused, const float *bdet, const int3
  * mx my <= 64, 2 <= ncx, ncy <= 512, d finite and > 0, every coordinate finite: else CRSDR_EINVAL. */
 int crsdr_caf_beam_steer(float *weights, int mx, int my, float d, int ncx, int ncy, const double *xy, int nbeams);
 
+/* Adaptive beams.  The direct path's ambiguity floor carries the illuminator's spatial signature in every cell of chi and reaches a
+ * fixed beam through its sidelobes; a weak echo is then detectable only above (floor x sidelobe).  This stage replaces the caller's
+ * weights, per line, by sample-matrix-inversion MVDR weights from the covariance of the line's own cells.  Off until
+ * crsdr_caf_set_beam_adapt; off, a submit is the same launches and the same bits.  Everything behind bmap runs as it stands.
+ * Elements e = 0 .. m - 1 are the rows c != ref_row, ascending, 1 <= m <= 64; the caller's weights v_b are those of crsdr_caf_set_beams,
+ * taken as fp64.
+ * Training cells of a line: Doppler bins (d_lo + a) mod nd, a = 0 .. d_n - 1 (Doppler wraps), lags r_lo + b, b = 0 .. r_n - 1 (lag does
+ * not), N = d_n r_n >= 1.  The rectangle is the caller's business: to leave out the zero-Doppler guard, d_lo = guard + 1,
+ * d_n = nd - 2 guard - 1.
+ * Covariance: snapshot u_e = conj(chi_c(e)[cell]) from the published fp32 chi (the bearings' convention), Q = (1 / N) sum u u^H in
+ * fp64, Q' = Q + loading (trace(Q) / m) I, loading in [1e-6, 1]: cond(Q') <= 1 + m / loading, and Q' is positive definite whenever
+ * trace(Q) > 0, also for N < m.  The order of the sum is not pinned (every product of two fp32 values is exact in fp64, so the error of
+ * Q is fp64 rounding of the sums alone), but it is fixed by the shape alone: a line has the same bits wherever it sits in a batch.
+ * Weights, per beam: g = Q'^-1 v_b by Cholesky, den = v_b^H g, w_b = (v_b^H v_b / den) g: MVDR under w^H v_b = v_b^H v_b, so that the
+ * beam answers its own look direction exactly as the caller's weight does.  Q proportional to I gives w = v.  A beam whose v_b is all
+ * zero keeps it.
+ *     aw    [nest][nbeams][m][2] float   each part rounded once from fp64
+ *     ainfo [nest][nbeams][2]    float = (w_b^H Q w_b, v_b^H Q v_b), Q the unloaded one, fp64 rounded once: the training cells' mean
+ *                                        power through the adaptive beam and through the caller's; both 0 on a fallback line
+ *     astat [nest]               int32   0, or the fallback: bit 0 trace(Q) = 0; bit 1 a pivot not > 0 or a sum not finite (only a
+ *                                        non-finite chi gives that).  On a fallback line aw is v bit for bit.  Never a NaN comes from
+ *                                        finite input.
+ * bmap is then the beam kernel's chain with line l's aw in place of w.
+ * Limits (CRSDR_EINVAL): 0 <= d_lo < nd; 1 <= d_n <= nd; 0 <= r_lo; 1 <= r_n; r_lo + r_n <= R; loading finite and in range; flags = 0. */
+typedef struct crsdr_caf_beam_adapt_desc {
+    int32_t d_lo, d_n, r_lo, r_n;
+    float loading;
+    uint32_t flags;           /* = 0 */
+} crsdr_caf_beam_adapt_desc;
+
+/* Sets the adaptation of the beams that are on (NULL: off): the beams' counterpart of crsdr_caf_set_cfar_estimator.  It belongs to the
+ * beams' descriptor: every crsdr_caf_set_beams, on or off, turns it off again.  Between submits only: it waits for the last one and
+ * allocates here, never in a submit.  With adaptation on a submit issues TWO launches more, whatever the batch.  CRSDR_ESTATE with no
+ * beams set, and while the tracker or the integration is on -- their state belongs to the maps this changes: the order is beams, adapt,
+ * integrate, track. */
+int crsdr_caf_set_beam_adapt(crsdr_caf *caf, const crsdr_caf_beam_adapt_desc *desc);
+
+/* Waits for the last submit and copies out what is asked for (any pointer may be NULL), laid out as above.  CRSDR_ESTATE while the
+ * adaptation is off, or before the first submit since it was set. */
+int crsdr_caf_fetch_beam_adapt(crsdr_caf *caf, float *aw, float *ainfo, int32_t *astat);
+
+/* Device addresses ([max_batch / frames] lines) for consumers on the same stream.  They change with every crsdr_caf_set_beam_adapt.
+ * CRSDR_ESTATE while the adaptation is off. */
+int crsdr_caf_beam_adapt_device_buffers(crsdr_caf *caf, void **aw, void **ainfo, void **astat);
+
+/* The adaptive weights of ONE line: chi [nrows][nd][R][2], weights [nbeams][nrows - 1][2] on the host -> aw [nbeams][m][2],
+ * ainfo [nbeams][2], astat [1] (at least one of them).  1 <= nd <= 4096, and nd need not be a power of two, as in crsdr_beam_maps.  It
+ * runs the engine's kernels on the same arguments, bit for bit; the per-op chain is crsdr_beam_adapt followed by crsdr_beam_maps(aw).
+ * mem_kind as above: device aw, ainfo and astat 4-byte, chi 8-byte aligned. */
+int crsdr_beam_adapt(float *aw, float *ainfo, int32_t *astat, const float *chi, int nrows, int nd, int R, int ref_row,
+                     const float *weights, int nbeams, const crsdr_caf_beam_adapt_desc *desc, int mem_kind);
+
 /* Tracks.  Everything above is per line: a list of (lag, Doppler, bearing) every line, false alarms at the detector's design rate among
  * them, and which entry is last line's target is left to the host.  This stage, behind the detector and on the device, is a
  * multi-target tracker in the lag-Doppler plane -- a Kalman filter per track, gating, a deterministic global-nearest-neighbour

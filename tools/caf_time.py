@@ -47,6 +47,11 @@ slots, 3 of 5, gate 9, the array map's list):
   cfar trk   as caf+cfar at that threshold: the same build's submit without the tracker
   +track     as cfar trk with the tracker's one launch behind the detector's, + a fetch of trk and ntrk in the place of det and count
   get trk    the fetch of trk + ntrk, against "get lists", the fetch of det + count that a host tracker would need every submit
+with --adapt --beams NB [--cfar], on a further engine with the beams set (with --cfar: and the detector), the same object in turn without
+and with the adaptive weights (crsdr_caf_set_beam_adapt: loading 1e-2, the whole map less the zero-Doppler guard):
+  adapt off  the submit with the beams alone, + the fetches of "+beams" / "+beams det"
+  +adapt     the same with the adaptation's two launches ahead of the beam maps; against m N 8 bytes of chi read once a line, and
+             beside "+beams" less "caf b", the beam kernel's own time on the same cells
 with --integrate [--beams NB], on a further engine with the integration across lines set (crsdr_caf_set_integrate: forget 1 / 8, coupling
 0.05; with --beams on the "+beams" engine's twin as well, array and beam maps):
   integ off  as caf, on the object of the next line with the integration turned off: the same build's submit without.  On and off are
@@ -125,6 +130,7 @@ def main():
     ap.add_argument("--cancel", metavar="K[:P]", help="add the canceller's variant")
     ap.add_argument("--bearing", action="store_true", help="add the bearings' variants (with --cfar's)")
     ap.add_argument("--beams", type=int, default=0, metavar="NB", help="add the beam maps' variants: a lattice of NB beams (22 rows)")
+    ap.add_argument("--adapt", action="store_true", help="add the adaptive beams' variants (with --beams, 22 rows)")
     ap.add_argument("--track", action="store_true", help="add the tracker's variants (22 rows)")
     ap.add_argument("--json")
     a = ap.parse_args()
@@ -233,6 +239,23 @@ def main():
                 if det:
                     e.fetch_cfar()
                 if det and on:
+                    e.fetch_beams(bmap=False, fused_only=True)
+            return run
+
+        ads, adapt_engine = {}, None
+        if a.adapt and bms:
+            e = adapt_engine = b.Caf(nrows, B, SEG, lags, 0, b.WINDOW_HANN, GUARD, max_batch=T, frames=FRAMES)
+            if a.cfar:
+                e.set_cfar(b.cfar_desc(alpha=b.cfar_alpha(1e-6, 90), gd=1, gr=1, td=3, tr=4, max_det=16))
+            e.set_beams(wts)
+            ads = {"adapt off": (e, None), "+adapt": (e, b.beam_adapt_desc(1e-2, GUARD + 1, nd - 2 * GUARD - 1, 0, lags))}
+
+        def caf_adapt(e):
+            def run(i):
+                e.submit(pk, plan.packet_stride, plan.matrix_offset, T)
+                e.fetch(chi=False, map=False)
+                if a.cfar:
+                    e.fetch_cfar()
                     e.fetch_beams(bmap=False, fused_only=True)
             return run
 
@@ -350,6 +373,16 @@ def main():
                 return _mean(caf_integ(e), lambda: None, a.reps)
             return fn
 
+        def adapted(e, desc):
+            # (the same object on and off, as for the integration)
+            def fn():
+                e.set_beam_adapt(desc)
+                caf_adapt(e)(0)
+                return _mean(caf_adapt(e), lambda: None, a.reps)
+            return fn
+
+        for name, (e, desc) in ads.items():
+            variants[name] = adapted(e, desc)
         for name, e in igs.items():
             what = b.INTEGRATE_ARRAY | (b.INTEGRATE_BEAMS if name == "+integ bm" else 0)
             variants[name.replace("+integ", "integ off")] = toggled(e, None)
@@ -405,6 +438,12 @@ def main():
                 note = f"  ({(T // FRAMES) * (128 * 64 + 16) / 1e3:.1f} kB)"
             if k == "get lists":
                 note = f"  ({(T // FRAMES) * (nrows + 1) * (64 * 32 + 4) / 1e3:.1f} kB)"
+            if k == "+adapt":
+                N, m, over = (nd - 2 * GUARD - 1) * lags, nrows - 1, med - shape["ms"]["adapt off"]["median"]
+                bts, beam = (T // FRAMES) * m * N * 8, shape["ms"]["+beams"]["median"] - shape["ms"]["caf b"]["median"]
+                shape["adapt"] = {"bytes": bts, "over_ms": over, "beam_kernel_ms": beam}
+                note = (f"  ({over:+.4f} ms behind 'adapt off', the same object: {bts / 1e6:.2f} MB of chi read once in two launches, "
+                        f"{f'{bts / over / 1e6:.1f} GB/s over the difference' if over > 0.002 else 'a difference inside the spread'}; '+beams' less 'caf b': {beam:+.4f} ms)")
             if k in igs:
                 lcells, maps = nd * lags, 1 + (len(wts) if k == "+integ bm" else 0)
                 off = k.replace("+integ", "integ off")
@@ -451,7 +490,7 @@ def main():
             e.close()
         for e, _, _ in bms.values():
             e.close()
-        for e in list(trs.values()) + list(igs.values()):
+        for e in list(trs.values()) + list(igs.values()) + ([adapt_engine] if adapt_engine else []):
             e.close()
         for w in workers.values():
             w.stdin.close()
