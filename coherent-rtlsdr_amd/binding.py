@@ -60,7 +60,10 @@ ABI_SYMBOLS = [
     "crsdr_caf_set_track", "crsdr_caf_track_reset", "crsdr_caf_fetch_track", "crsdr_caf_track_device_buffers", "crsdr_track_state_bytes", "crsdr_track",
     "crsdr_caf_set_integrate", "crsdr_caf_integrate_reset", "crsdr_caf_fetch_integrate", "crsdr_caf_integrate_device_buffers",
     "crsdr_map_integrate_state_bytes", "crsdr_map_integrate",
+    "crsdr_caf_set_clean", "crsdr_caf_fetch_clean", "crsdr_caf_clean_device_buffers", "crsdr_ambiguity_clean",
 ]
+CLEAN_SINGULAR, CLEAN_TARGET = 1, 2                             # tinfo[..., 1]: the first stage is singular; a target column's pivot failed
+CLEAN_LAUNCHES = 9                                              # what a submit issues more with the cleaning on
 INTEGRATE_ARRAY, INTEGRATE_BEAMS = 1, 2
 TRACK_SRC_ARRAY, TRACK_SRC_FUSED = 0, 1
 TRACK_FREE, TRACK_TENTATIVE, TRACK_CONFIRMED, TRACK_ENDED = 0, 1, 2, 3      # trk[..., 1]
@@ -147,6 +150,20 @@ class CfarEstDesc(C.Structure):
 class CancelDesc(C.Structure):
     """crsdr_caf_cancel_desc: the reference's delays 0 .. taps - 1, each shifted by -dopp .. dopp Doppler bins."""
     _fields_ = [("taps", C.c_int32), ("dopp", C.c_int32)]
+
+
+class CleanDesc(C.Structure):
+    """crsdr_caf_clean_desc: at most max_targets picks a line, none under min_snr, each a cluster of lags l - wl .. l + wl and Dopplers
+    f - wq / 2 .. f + wq / 2 in steps of half a bin."""
+    _fields_ = [("max_targets", C.c_int32), ("min_snr", C.c_float), ("wl", C.c_int32), ("wq", C.c_int32)]
+
+
+CLEAN_KEYS = ("chi", "map", "peak", "coef", "cinfo", "det", "count", "snap", "tgt", "ntgt", "tcoef", "tinfo", "rchi", "rmap", "rdet", "rcount", "rsnap")
+
+
+class CleanOut(C.Structure):
+    """crsdr_clean_out: where crsdr_ambiguity_clean writes (NULL: not asked for)."""
+    _fields_ = [(k, C.c_void_p) for k in CLEAN_KEYS]
 
 
 class BearingDesc(C.Structure):
@@ -376,6 +393,12 @@ def lib():
         L.crsdr_caf_track_device_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         L.crsdr_track_state_bytes.argtypes = [C.POINTER(TrackDesc), C.POINTER(C.c_size_t)]
         L.crsdr_track.argtypes = [f32p, i32p, vp, f32p, i32p, f32p] + [C.c_int] * 4 + [C.POINTER(TrackDesc), C.c_int]
+    if hasattr(L, "crsdr_ambiguity_clean"):          # (likewise: an older build has no second cancellation stage)
+        L.crsdr_caf_set_clean.argtypes = [vp, C.POINTER(CleanDesc)]
+        L.crsdr_caf_fetch_clean.argtypes = [vp, f32p, i32p, f32p, f32p, f32p, f32p, f32p, i32p, f32p]
+        L.crsdr_caf_clean_device_buffers.argtypes = [vp] + [C.POINTER(vp)] * 9
+        L.crsdr_ambiguity_clean.argtypes = [C.POINTER(CleanOut), C.POINTER(C.c_int8)] + [C.c_int] * 8 + [C.POINTER(CancelDesc), C.POINTER(CfarDesc), C.POINTER(CfarEstDesc),
+                                                                                                         C.POINTER(CleanDesc)]
     if hasattr(L, "crsdr_map_integrate"):            # (likewise: an older build has no integration across lines)
         L.crsdr_caf_set_integrate.argtypes = [vp, C.POINTER(IntegrateDesc)]
         L.crsdr_caf_integrate_reset.argtypes = [vp]
@@ -1016,6 +1039,39 @@ def ambiguity_cancel(matrix, seg, nlags, taps, dopp=0, ref_row=0, window=WINDOW_
     _check(lib().crsdr_ambiguity_cancel(_p(chi.view(np.float32), C.c_float), _p(mp, C.c_float), _p(pk, C.c_float), _p(m, C.c_int8), nrows, B, int(seg), int(nlags),
                                         int(ref_row), int(window), int(guard), MEM_HOST, int(taps), int(dopp), _p(coef.view(np.float32), C.c_float), _p(cinfo, C.c_float)))
     return chi, mp, pk, coef, cinfo
+
+
+def clean_shapes(nrows, nd, R, n1, K, clean: "CleanDesc"):
+    """{name: (shape, dtype)} of one line's outputs of crsdr_ambiguity_clean, in CLEAN_KEYS' order"""
+    T, per = int(clean.max_targets), (2 * int(clean.wl) + 1) * (2 * int(clean.wq) + 1)
+    c64, f32, i32 = np.complex64, np.float32, np.int32
+    return {"chi": ((nrows, nd, R), c64), "map": ((nd, R), f32), "peak": ((nrows + 1, 6), f32), "coef": ((nrows, n1), c64), "cinfo": ((nrows, 2), f32),
+            "det": ((nrows + 1, K, 8), f32), "count": ((nrows + 1,), i32), "snap": ((K, nrows), c64), "tgt": ((T, 8), f32), "ntgt": ((1,), i32),
+            "tcoef": ((nrows, T, per), c64), "tinfo": ((nrows, 2), f32), "rchi": ((nrows, nd, R), c64), "rmap": ((nd, R), f32), "rdet": ((nrows + 1, K, 8), f32),
+            "rcount": ((nrows + 1,), i32), "rsnap": ((K, nrows), c64)}
+
+
+def ambiguity_clean(matrix, seg, nlags, cancel: "CancelDesc", cfar: "CfarDesc", clean: "CleanDesc", est: "CfarEstDesc | None" = None, ref_row=0, window=WINDOW_RECT,
+                    guard=0) -> dict:
+    """crsdr_ambiguity_clean: canceller, detector and the second cancellation stage on one packet's matrix [nrows][B] int8 -> dict of
+    CLEAN_KEYS.  The engine (Caf.set_cancel, set_cfar, set_clean) on one line of one packet, bit for bit."""
+    m = np.ascontiguousarray(matrix, dtype=np.int8)
+    nrows, B = m.shape
+    nd = B // (2 * int(seg)) if seg > 0 else 1
+    shapes = clean_shapes(nrows, max(nd, 1), int(nlags), int(cancel.taps) * (2 * int(cancel.dopp) + 1), int(cfar.max_det), clean)
+    # (a descriptor beyond its limits is refused by the call: the arrays only have to exist)
+    out = {k: np.zeros(sh if all(0 < x < 2 ** 20 for x in sh) else (1,), dtype=dt) for k, (sh, dt) in shapes.items()}
+    io = CleanOut(*[out[k].ctypes.data for k in CLEAN_KEYS])
+    _check(lib().crsdr_ambiguity_clean(C.byref(io), _p(m, C.c_int8), nrows, B, int(seg), int(nlags), int(ref_row), int(window), int(guard), 0, C.byref(cancel), C.byref(cfar),
+                                       None if est is None else C.byref(est), C.byref(clean)))
+    return out
+
+
+def ambiguity_clean_device(ptrs: dict, matrix_ptr: int, nrows, B, seg, nlags, ref_row, window, guard, cancel, cfar, clean, est=None):
+    """The same on device pointers (ptrs: CLEAN_KEYS -> address, missing or 0: not asked for)."""
+    io = CleanOut(*[int(ptrs.get(k) or 0) or None for k in CLEAN_KEYS])
+    _check(lib().crsdr_ambiguity_clean(C.byref(io), C.cast(C.c_void_p(int(matrix_ptr)), C.POINTER(C.c_int8)), int(nrows), int(B), int(seg), int(nlags), int(ref_row),
+                                       int(window), int(guard), 1, C.byref(cancel), C.byref(cfar), None if est is None else C.byref(est), C.byref(clean)))
 
 
 def ambiguity_cancel_device(chi_ptr: int, map_ptr: int, peak_ptr: int, matrix_ptr: int, nrows, B, seg, nlags, ref_row, window, guard, taps, dopp, coef_ptr: int,
@@ -1855,6 +1911,31 @@ class Caf:
         ptrs = [C.c_void_p() for _ in range(2)]
         _check(lib().crsdr_caf_cancel_device_buffers(self._h, *[C.byref(p) for p in ptrs]))
         return dict(zip(("coef", "cinfo"), [p.value for p in ptrs]))
+
+    def set_clean(self, desc: "CleanDesc | None"):
+        """crsdr_caf_set_clean: the second cancellation stage behind every submit's detector (None: off).  Between submits, with the
+        canceller and the detector on."""
+        _check(lib().crsdr_caf_set_clean(self._h, None if desc is None else C.byref(desc)))
+        self.clean = None if desc is None else (int(desc.max_targets), (2 * int(desc.wl) + 1) * (2 * int(desc.wq) + 1))
+
+    def fetch_clean(self, **want) -> dict:
+        """Waits for the last submit.  tgt [nest][T][8], ntgt [nest], tcoef [nest][nrows][T][per] complex64, tinfo [nest][nrows][2], and
+        rchi, rmap, rdet, rcount, rsnap as fetch() and fetch_cfar() lay out chi, map, det, count, snap.  name=False leaves one out."""
+        n, K = (self._last()[0] if getattr(self, "clean", None) else 0), max(1, getattr(self, "max_det", 0))
+        T, per = getattr(self, "clean", None) or (1, 1)
+        c64, f32, i32 = np.complex64, np.float32, np.int32
+        spec = (("tgt", (n, T, 8), f32), ("ntgt", (n,), i32), ("tcoef", (n, self.nrows, T, per), c64), ("tinfo", (n, self.nrows, 2), f32),
+                ("rchi", (n, self.nrows, self.nd, self.nlags), c64), ("rmap", (n, self.nd, self.nlags), f32), ("rdet", (n, self.nrows + 1, K, 8), f32),
+                ("rcount", (n, self.nrows + 1), i32), ("rsnap", (n, K, self.nrows), c64))
+        out = {k: np.zeros(sh, dtype=dt) for k, sh, dt in spec if want.get(k, True)}
+        args = [None if k not in out else _p(out[k].view(f32) if dt is c64 else out[k], C.c_int32 if dt is i32 else C.c_float) for k, _, dt in spec]
+        _check(lib().crsdr_caf_fetch_clean(self._h, *args))
+        return out
+
+    def clean_device_buffers(self) -> dict:
+        ptrs = [C.c_void_p() for _ in range(9)]
+        _check(lib().crsdr_caf_clean_device_buffers(self._h, *[C.byref(p) for p in ptrs]))
+        return dict(zip(CLEAN_KEYS[8:], [p.value for p in ptrs]))
 
     def last_launches(self) -> int:
         return self._last()[1]

@@ -31,7 +31,9 @@
 //                 LDS: A 34 KiB (32 KiB at nd = 4096, unpadded as in spectra.hpp) + max(twiddles, staged words) <= 64 KiB static.
 //                 k_caf<LG, 1> and k_caf<LG, 2> are the canceller's two passes around the same range stage (CancelArgs below,
 //                 caf_cancel.hpp): the sums of the first lags and the row's energy, and the rows with the reference's part taken out
-//                 of ACC in fp64 before the Doppler stage.  k_caf<LG> itself compiles to the instructions it had without them.
+//                 of ACC in fp64 before the Doppler stage.  k_caf<LG, 3> is the second stage's pass (CleanArgs, caf_clean.hpp): MODE 2
+//                 with the line's target members behind the canceller's.  k_caf<LG> itself compiles to the instructions it had
+//                 without them.
 //   k_caf_map     grid (cells / 32, line): the fp64 sum of |chi|^2 over the rows but r, eight interleaved parts of the rows added in a
 //                 fixed order, rounded once.
 //   k_caf_peak    grid (entry, line), 256 threads: caf_peak.hpp's search, one part per thread, merged by a tree in LDS.
@@ -39,6 +41,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "caf_clean_solve.hpp"
 #include "caf_peak.hpp"
 #include "fft_lds.hpp"
 #include "spectra.hpp"
@@ -73,11 +76,20 @@ struct CancelArgs {
     int2 *Y = nullptr;                             // [nest][nrows][nd][taps]
     long long *E = nullptr;                        // [nest][nrows]
 };
+// MODE 3 is MODE 2 on the joint coefficients of the second stage (caf_clean.hpp): the canceller's members as MODE 2 takes them, then the
+// line's target members.  h [nest][nrows][hstride], the canceller's n1 first; status: the joint solve's (bit 0: nothing is taken out;
+// bit 1: the canceller's members alone, whose h is then stage 1's).
+struct CleanArgs : CancelArgs {
+    int hstride = 0, slots = 0, members = 0;       // h's stride; G2's lags and ph2's members per line as allocated
+    const cl::Table *tab = nullptr;                // [nest]: the lines' members
+    const int2 *G2 = nullptr;                      // [nest][nd][slots][nlags]
+    const double2 *ph2 = nullptr;                  // [nest][members][nd]
+};
 
 template <typename T>
 __device__ __forceinline__ const T &caf_only(const T &t) { return t; }
 
-// MODE 0 takes no further argument; MODE 1 and 2 one CancelArgs.
+// MODE 0 takes no further argument; MODE 1 and 2 one CancelArgs; MODE 3 one CleanArgs.
 template <int LG, int MODE = 0, typename... CN>
 __global__ __launch_bounds__(CAF_THREADS) void k_caf(const int8_t *__restrict__ packets, size_t packet_stride, size_t matrix_off, int nrows, int B, int frames,
                                                      int lgseg, int nlags, int ref_row, const float2 *__restrict__ tw_g, const float *__restrict__ win, float scale,
@@ -184,13 +196,25 @@ __global__ __launch_bounds__(CAF_THREADS) void k_caf(const int8_t *__restrict__ 
         if (tid == 0) cn.E[(size_t)e * nrows + row] = red[0];
         return;
     }
-    if constexpr (MODE == 2) {
+    if constexpr (MODE >= 2) {
         // y' = y - sum_(m,p) h_(m,p) phi_p[k] G[k][m][tau]: fp64 from the integers, one rounding; its bits take y's place in ACC.
         // Row r and a singular line keep y: (float)(double)y is (float)y.
-        const CancelArgs &cn = caf_only(cna...);
-        const bool on = row != ref_row && cn.status[e] == 0;
+        // MODE 3: the same with the joint h, then y'' = y' - sum_i h_i phi_(g_i)[k] G2[k][slot_i][tau] over the line's target members
+        // (none where the joint solve fell back: its h is then stage 1's, and these are MODE 2's bits).
+        const auto &cn = caf_only(cna...);
         const int K = cn.taps, P = cn.dopp, Rg = cn.nlags;
-        const double2 *h = cn.h + ((size_t)e * nrows + row) * (size_t)(K * (2 * P + 1));
+        bool on = row != ref_row;
+        size_t hstride = (size_t)(K * (2 * P + 1));
+        [[maybe_unused]] int nm = 0;
+        if constexpr (MODE == 3) {
+            const int st = cn.status[e];
+            on = on && (st & 1) == 0;
+            nm = st == 0 ? cn.tab[e].nmem : 0;
+            hstride = (size_t)cn.hstride;
+        } else {
+            on = on && cn.status[e] == 0;
+        }
+        const double2 *h = cn.h + ((size_t)e * nrows + row) * hstride;
         const int2 *G = cn.G + (size_t)e * ND * (size_t)K * Rg + lag0;
 #pragma unroll 1
         for (int it = tid; it < CELLS; it += CAF_THREADS) {
@@ -210,6 +234,21 @@ __global__ __launch_bounds__(CAF_THREADS) void k_caf(const int8_t *__restrict__ 
                     const double2 f = cn.ph[(p * k) & (ND - 1)];
                     re = fma(-f.x, ar, re); re = fma(f.y, ai, re);
                     im = fma(-f.x, ai, im); im = fma(-f.y, ar, im);
+                }
+                if constexpr (MODE == 3) {
+                    const int2 *g2 = cn.G2 + ((size_t)e * ND + k) * (size_t)cn.slots * Rg + lag0 + l;
+                    const int *slot = cn.tab[e].slot;
+                    const double2 *ht = h + K * (2 * P + 1), *ph2 = cn.ph2 + (size_t)e * cn.members * ND + k;
+                    for (int i = 0; i < nm; ++i) {
+                        const int2 gi = g2[(size_t)slot[i] * Rg];
+                        const double2 hi = ht[i], f = ph2[(size_t)i * ND];
+                        const double gr = (double)gi.x, gq = (double)gi.y;
+                        double ar = 0.0, ai = 0.0;
+                        ar = fma(hi.x, gr, ar); ar = fma(-hi.y, gq, ar);
+                        ai = fma(hi.x, gq, ai); ai = fma(hi.y, gr, ai);
+                        re = fma(-f.x, ar, re); re = fma(f.y, ai, re);
+                        im = fma(-f.x, ai, im); im = fma(-f.y, ar, im);
+                    }
                 }
             }
             ACC[2 * it] = __float_as_int((float)re);
@@ -233,7 +272,7 @@ __global__ __launch_bounds__(CAF_THREADS) void k_caf(const int8_t *__restrict__ 
         const int i = tid + j * CAF_THREADS, k = i >> LT, l = i & (T - 1);
         if (i < CELLS) {
             const float w = win[k];
-            if constexpr (MODE == 2) A[spectra::sp_pad<LG>(l * ND + k)] = make_float2(__int_as_float(yr[j]) * w, __int_as_float(yi[j]) * w);
+            if constexpr (MODE >= 2) A[spectra::sp_pad<LG>(l * ND + k)] = make_float2(__int_as_float(yr[j]) * w, __int_as_float(yi[j]) * w);
             else A[spectra::sp_pad<LG>(l * ND + k)] = make_float2((float)yr[j] * w, (float)yi[j] * w);
         }
     }

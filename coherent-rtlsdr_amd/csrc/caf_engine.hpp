@@ -18,6 +18,9 @@
 //     that walks the lines of the submit and carries the tracks from submit to submit.
 //     With integration set (crsdr_caf_set_integrate; caf_integrate.hpp, caf_integrate_solve.hpp) one more behind the array map, whose
 //     place the integrated map takes in front of the detector, and one more behind the beam maps, likewise.
+//     With cleaning set (crsdr_caf_set_clean; caf_clean.hpp, caf_clean_solve.hpp) nine more behind the detector's: the picks, the
+//     reference's and the rows' sums at the picks' lags, the joint sums, factor and solves, the rows with the joint subtraction, their
+//     map, and the detector's two on them.
 //
 // Shape of the host code (doa_engine.hpp's).  A feature is a sub-struct of crsdr_caf: its parameters and its DevBufs.  Every launch
 // goes through caf_run, which checks and counts it.  A submit is caf_launch's flat list of stages (maps, integration, detector,
@@ -33,6 +36,7 @@
 #include "caf_bearing.hpp"
 #include "caf_cancel.hpp"
 #include "caf_cfar_kernels.hpp"
+#include "caf_clean.hpp"
 #include "caf_integrate.hpp"
 #include "caf_track_kernels.hpp"
 
@@ -66,7 +70,7 @@ struct CancelBufs {
 
 // what the last submit left: where, how much, and which features ran (kCafRan*).  A setter clears its feature's bit: "nothing submitted
 // since"; without kCafRanBase nothing is left at all
-constexpr unsigned kCafRanBase = 1u, kCafRanCancel = 2u, kCafRanCfar = 4u, kCafRanBearing = 8u, kCafRanBeams = 16u, kCafRanTrack = 32u, kCafRanIntegrate = 64u, kCafRanAdapt = 128u;
+constexpr unsigned kCafRanBase = 1u, kCafRanCancel = 2u, kCafRanCfar = 4u, kCafRanBearing = 8u, kCafRanBeams = 16u, kCafRanTrack = 32u, kCafRanIntegrate = 64u, kCafRanAdapt = 128u, kCafRanClean = 256u;
 struct CafLast {
     hipStream_t stream = nullptr;
     int nest = 0, launches = 0;
@@ -142,6 +146,20 @@ struct crsdr_caf {
         bool array() const { return on && (what & integ::ARRAY); }
         bool beams() const { return on && (what & integ::BEAMS); }
     } ig;
+    // crsdr_caf_set_clean: on (false = off), the sizes its buffers have (n2max target members, nmax members, slots member lags a
+    // line), the lines' member tables, the sums, the joint solve's scratch and coefficients, and the results
+    struct Clean {
+        bool on = false;
+        cl::Params prm{};
+        int n2max = 0, nmax = 0, slots = 0;
+        DevBuf<cl::Table> tab;
+        DevBuf<int2> G2, Y2;
+        DevBuf<double2> ph2, A2, C2, Wj, hj;
+        DevBuf<int> jstat;
+        DevBuf<float> tgt, tcoef, tinfo, rmap, rdet, rsnap;
+        DevBuf<int32_t> ntgt, rcount;
+        DevBuf<float2> rchi;
+    } cl_;
     CafLast last;
     size_t lines() const { return (size_t)(max_batch / frames); }      // the most a submit leaves: what every setter sizes its buffers by
 };
@@ -493,14 +511,18 @@ static int caf_clear(crsdr_caf *q, Feature &f, unsigned ran_bit)
 // Who must be off before whom, who must be on before whom: every rule of the setters, each feature's in the order they are asked.
 // must_be_on false: `feature` is not changed, set or turned off, while `other` is on, which works on its buffers and parameters (asked
 // ahead of the descriptor's limits).  true: `feature` is not set while `other` is off (asked behind them, and not to turn it off).
-enum { kCafCfar, kCafBearing, kCafBeams, kCafBeamLists, kCafTrack, kCafIntegrate, kCafTrackFused, kCafCfarEst, kCafIntegrateBeams, kCafAdapt };
+// (the first nine name a state that `other` can ask for; the rest only a setter's question)
+enum { kCafCfar, kCafBearing, kCafBeams, kCafBeamLists, kCafTrack, kCafIntegrate, kCafClean, kCafCancel, kCafArrayIntegrated, kCafTrackFused, kCafCfarEst,
+       kCafIntegrateBeams, kCafAdapt, kCafIntegrateArray };
 static const struct CafRule { int feature; bool must_be_on; int other; const char *refusal; } kCafRules[] = {
     {kCafCfar, false, kCafTrack, "caf_set_cfar: the tracker is on (crsdr_caf_set_track): its measurements are this detector's lists; turn it off first"},
     {kCafCfar, false, kCafBeams, "caf_set_cfar: beams are on (crsdr_caf_set_beams): whether they are detected on, and the lists' sizes, are this detector's; turn them off first"},
     {kCafCfar, false, kCafBearing, "caf_set_cfar: bearings are on (crsdr_caf_set_bearing): their buffers and training set are this detector's; turn them off first"},
+    {kCafCfar, false, kCafClean, "caf_set_cfar: cleaning is on (crsdr_caf_set_clean): its picks are this detector's list and its lists this detector's; turn it off first"},
     {kCafCfarEst, false, kCafTrack, "caf_set_cfar_estimator: the tracker is on (crsdr_caf_set_track): its measurements are this detector's lists; turn it off first"},
     {kCafCfarEst, false, kCafBeams, "caf_set_cfar_estimator: beams are on (crsdr_caf_set_beams): their lists are this detector's; turn them off first"},
     {kCafCfarEst, false, kCafBearing, "caf_set_cfar_estimator: bearings are on (crsdr_caf_set_bearing): they follow this detector's lists; turn them off first"},
+    {kCafCfarEst, false, kCafClean, "caf_set_cfar_estimator: cleaning is on (crsdr_caf_set_clean): its picks follow this detector's list; turn it off first"},
     {kCafCfarEst, true, kCafCfar, "caf_set_cfar_estimator: no detector set (crsdr_caf_set_cfar): the estimator belongs to its descriptor"},
     {kCafBearing, false, kCafTrack, "caf_set_bearing: the tracker is on (crsdr_caf_set_track): its auxiliary pairs are these bearings; turn it off first"},
     {kCafBearing, true, kCafCfar, "caf_set_bearing: no detector set (crsdr_caf_set_cfar): there are no detections to take a bearing of"},
@@ -514,11 +536,16 @@ static const struct CafRule { int feature; bool must_be_on; int other; const cha
     {kCafIntegrate, false, kCafTrack, "caf_set_integrate: the tracker is on (crsdr_caf_set_track): its measurements are the lists of the maps this changes; turn it off first"},
     {kCafIntegrate, false, kCafBearing, "caf_set_integrate: bearings are on (crsdr_caf_set_bearing): they follow the lists of the map this changes; turn them off first"},
     {kCafIntegrateBeams, true, kCafBeams, "caf_set_integrate: CRSDR_INTEGRATE_BEAMS needs beams (crsdr_caf_set_beams): there are no beam maps to integrate"},
+    {kCafIntegrateArray, false, kCafClean, "caf_set_integrate: cleaning is on (crsdr_caf_set_clean): with CRSDR_INTEGRATE_ARRAY its picks would come from another line's energy; turn it off first"},
+    {kCafCancel, false, kCafClean, "caf_set_cancel: cleaning is on (crsdr_caf_set_clean): its basis begins with this canceller's and its sums are this canceller's; turn it off first"},
+    {kCafClean, false, kCafArrayIntegrated, "caf_set_clean: CRSDR_INTEGRATE_ARRAY is on (crsdr_caf_set_integrate): the picks would come from another line's energy; turn it off first"},
+    {kCafClean, true, kCafCancel, "caf_set_clean: no canceller set (crsdr_caf_set_cancel): the joint basis begins with the canceller's"},
+    {kCafClean, true, kCafCfar, "caf_set_clean: no detector set (crsdr_caf_set_cfar): there are no detections to pick from"},
 };
 
 static int caf_rules(const crsdr_caf *q, int feature, bool must_be_on)
 {
-    const bool on[] = {q->cf.on, q->bg.on, q->bb.on, q->bb.on && q->bb.det, q->tk.on, q->ig.on};
+    const bool on[] = {q->cf.on, q->bg.on, q->bb.on, q->bb.on && q->bb.det, q->tk.on, q->ig.on, q->cl_.on, q->cn.on, q->ig.array()};
     for (const CafRule &u : kCafRules)
         if (u.feature == feature && u.must_be_on == must_be_on && on[u.other] != must_be_on) return fail(CRSDR_ESTATE, "%s", u.refusal);
     return CRSDR_OK;
@@ -588,6 +615,42 @@ static int caf_stage_cfar(crsdr_caf *q, CafRun &r)
     return cfar_enqueue(r, q->chi, q->ig.array() ? q->ig.imap : q->map, r.nest, q->nrows, q->nrows + 1, q->nd, q->nlags, q->guard, c.prm, c.keep, c.slots, c.tcount, c.det, c.count, c.snap);
 }
 
+// the second stage, behind the detector whose array-map list it picks from: nine launches whatever the batch and the picks.  It reads
+// the canceller's and the detector's buffers and writes its own; the detector's tile scratch is free again by stream order
+static int caf_stage_clean(crsdr_caf *q, CafRun &r, const int8_t *packets, size_t packet_stride, size_t matrix_offset)
+{
+    crsdr_caf::Clean &c = q->cl_;
+    if (!c.on) return CRSDR_OK;
+    const crsdr_caf::Cancel &cn = q->cn;
+    const crsdr_caf::Cfar &cf = q->cf;
+    const int nest = r.nest, nrows = q->nrows, nd = q->nd, R = q->nlags, lg = ilog2_exact(nd), lgseg = ilog2_exact(q->seg), K = cn.taps, P = cn.dopp, cells = nd * R;
+    const size_t Kd = (size_t)cf.prm.max_det, entries = (size_t)(nrows + 1);
+    const int sums = c.n2max * c.nmax + nrows * c.n2max;
+    const float scale = (float)(1.0 / (127.0 * 127.0 * (double)q->seg * (q->window == CRSDR_WINDOW_HANN ? 0.5 * (double)nd : (double)nd)));
+    int rc = caf_run(r, clean::k_clean_pick, dim3((unsigned)nest), dim3(64), 0, (const float *)(cf.det.p + (size_t)nrows * Kd * 8), entries * Kd * 8,
+                     (const int32_t *)(cf.count.p + nrows), entries, (int)Kd, nd, R, K, P, c.prm, c.tab.p, c.tgt.p, c.ntgt.p);
+    if (rc || (rc = caf_run(r, clean::k_clean_g, dim3((unsigned)nd, (unsigned)nest), dim3(clean::THREADS), 0, packets, packet_stride, matrix_offset, q->B, q->frames, lgseg, nd,
+                            R, q->ref_row, (const cl::Table *)c.tab.p, c.slots, c.n2max, c.G2.p, c.ph2.p)) ||
+        (rc = caf_run(r, clean::k_clean_y, dim3((unsigned)((nd * c.slots + clean::THREADS - 1) / clean::THREADS), (unsigned)nrows, (unsigned)nest), dim3(clean::THREADS), 0,
+                      packets, packet_stride, matrix_offset, nrows, q->B, q->frames, lgseg, nd, q->ref_row, (const cl::Table *)c.tab.p, c.slots, c.Y2.p)) ||
+        (rc = caf_run(r, clean::k_clean_sums, dim3((unsigned)((sums + clean::SUM_ENTRIES - 1) / clean::SUM_ENTRIES), (unsigned)nest), dim3(clean::THREADS), 0,
+                      (const int2 *)cn.G.p, (const int2 *)c.G2.p, (const int2 *)c.Y2.p, (const double2 *)c.ph2.p, (const cl::Table *)c.tab.p, nrows, nd, R, K, P, q->ref_row,
+                      c.slots, c.n2max, c.n2max, c.nmax, c.A2.p, c.C2.p)) ||
+        (rc = caf_run(r, clean::k_clean_solve, dim3((unsigned)nest, (unsigned)((nrows + clean::SOLVE_ROWS - 1) / clean::SOLVE_ROWS)), dim3(clean::THREADS), 0,
+                      (const double2 *)cn.S.p, (const double2 *)cn.C.p, (const long long *)cn.E.p, (const double2 *)cn.h.p, (const double2 *)c.A2.p, (const double2 *)c.C2.p,
+                      (const cl::Table *)c.tab.p, nrows, K, P, q->ref_row, c.n2max, c.nmax, cl::per_pick(c.prm), c.Wj.p, c.hj.p, c.jstat.p, c.tcoef.p, c.tinfo.p)))
+        return rc;
+    caf::CleanArgs a;
+    a.taps = K; a.dopp = P; a.nlags = R; a.G = cn.G; a.h = c.hj; a.ph = cn.ph; a.status = c.jstat;
+    a.hstride = c.nmax; a.slots = c.slots; a.members = c.n2max; a.tab = c.tab; a.G2 = c.G2; a.ph2 = c.ph2;
+    CAF_DISPATCH(lg, rc = caf_run(r, (caf::k_caf<LG, 3, caf::CleanArgs>), dim3((unsigned)(nrows * caf::caf_tiles(lg, R)), (unsigned)nest), dim3(caf::CAF_THREADS), 0, packets,
+                                  packet_stride, matrix_offset, nrows, q->B, q->frames, lgseg, R, q->ref_row, (const float2 *)q->tw.p, (const float *)q->win.p, scale, c.rchi.p, a));
+    if (rc || (rc = caf_run(r, caf::k_caf_map, dim3((unsigned)((cells + caf::CAF_MAP_CELLS - 1) / caf::CAF_MAP_CELLS), (unsigned)nest), dim3(caf::CAF_THREADS), 0,
+                            (const float2 *)c.rchi.p, nrows, cells, q->ref_row, c.rmap.p)))
+        return rc;
+    return cfar_enqueue(r, c.rchi, c.rmap, nest, nrows, nrows + 1, nd, R, q->guard, cf.prm, cf.keep, cf.slots, cf.tcount, c.rdet, c.rcount, c.rsnap);
+}
+
 // (the bearings and the tracker read the array map's lists: entry nrows of the nrows + 1 of a line)
 static int caf_stage_bearing(crsdr_caf *q, CafRun &r)
 {
@@ -646,6 +709,7 @@ static int caf_launch(crsdr_caf *q, const int8_t *packets, size_t packet_stride,
     int rc = caf_stage_maps(q, r, packets, packet_stride, matrix_offset, nblocks);
     if (!rc) rc = caf_stage_integrate(q, r);
     if (!rc) rc = caf_stage_cfar(q, r);
+    if (!rc) rc = caf_stage_clean(q, r, packets, packet_stride, matrix_offset);
     if (!rc) rc = caf_stage_bearing(q, r);
     if (!rc) rc = caf_stage_beams(q, r);
     if (!rc) rc = caf_stage_integrate_beams(q, r);
@@ -656,7 +720,7 @@ static int caf_launch(crsdr_caf *q, const int8_t *packets, size_t packet_stride,
     // stand for whole stages only.
     if (r.launches)
         q->last = CafLast{S, r.nest, r.launches, rc ? kCafRanBase : kCafRanBase | (q->cn.on ? kCafRanCancel : 0u) | (q->cf.on ? kCafRanCfar : 0u) | (q->bg.on ? kCafRanBearing : 0u) |
-                                                                      (q->bb.on ? kCafRanBeams : 0u) | (q->tk.on ? kCafRanTrack : 0u) | (q->ig.on ? kCafRanIntegrate : 0u) | (q->ba.on ? kCafRanAdapt : 0u)};
+                                                                      (q->bb.on ? kCafRanBeams : 0u) | (q->tk.on ? kCafRanTrack : 0u) | (q->ig.on ? kCafRanIntegrate : 0u) | (q->ba.on ? kCafRanAdapt : 0u) | (q->cl_.on ? kCafRanClean : 0u)};
     return rc;
 }
 
@@ -1223,6 +1287,7 @@ extern "C" int crsdr_caf_set_integrate(crsdr_caf *q, const crsdr_caf_integrate_d
     if (desc) {
         { const int rc_ = integrate_args_ok("caf_set_integrate", q->nd, desc, true, &prm); if (rc_) return rc_; }
         if (desc->what & integ::BEAMS) { const int rc = caf_rules(q, kCafIntegrateBeams, true); if (rc) return rc; }
+        if (desc->what & integ::ARRAY) { const int rc = caf_rules(q, kCafIntegrateArray, false); if (rc) return rc; }
     }
     { const int rc = caf_clear(q, q->ig, kCafRanIntegrate); if (rc || !desc) return rc; }
     const size_t lines = q->lines(), cells = (size_t)q->nd * (size_t)q->nlags, sb = integrate_state_bytes(q, desc->what, q->bb.nb);
@@ -1310,6 +1375,7 @@ extern "C" int crsdr_map_integrate(float *imap, void *state, const float *maps, 
 extern "C" int crsdr_caf_set_cancel(crsdr_caf *q, const crsdr_caf_cancel_desc *desc)
 {
     if (!q) return fail(CRSDR_EINVAL, "caf_set_cancel: NULL caf");
+    { const int rc = caf_rules(q, kCafCancel, false); if (rc) return rc; }
     const size_t lines = q->lines();
     if (desc) { const int rc_ = cancel_args_ok("caf_set_cancel", q->nd, q->nlags, (long long)lines, desc); if (rc_) return rc_; }
     { const int rc = caf_clear(q, q->cn, kCafRanCancel); if (rc || !desc) return rc; }
@@ -1401,4 +1467,135 @@ extern "C" int crsdr_ambiguity_cancel(float *chi, float *map, float *peak, const
 {
     const crsdr_caf_cancel_desc cd{taps, dopp};
     return ambiguity(chi, map, peak, matrix, nrows, blocksize, seg, nlags, ref_row, window, guard, mem_kind, &cd, coef, cinfo);
+}
+
+// ---- the second stage ----
+// every limit of the cleaning of section (w), for crsdr_caf_set_clean and crsdr_ambiguity_clean.  taps, dopp: the canceller's
+static int clean_args_ok(const char *who, int nd, int nlags, long long lines, int nrows, int taps, int dopp, const crsdr_caf_clean_desc *d, cl::Params *prm)
+{
+    *prm = cl::Params{d->max_targets, d->min_snr, d->wl, d->wq};
+    switch (cl::bad_limit(nd, nlags, lines, nrows, taps, dopp, *prm)) {
+    case 0: return CRSDR_OK;
+    case 1: return fail(CRSDR_EINVAL, "%s: max_targets = %d (1..%d)", who, d->max_targets, cl::MAX_TARGETS);
+    case 2: return fail(CRSDR_EINVAL, "%s: wl = %d (0..%d)", who, d->wl, cl::MAX_WL);
+    case 3: return fail(CRSDR_EINVAL, "%s: wq = %d (0..%d)", who, d->wq, cl::MAX_WQ);
+    case 4: return fail(CRSDR_EINVAL, "%s: taps (2 dopp + 1) + max_targets (2 wl + 1)(2 wq + 1) = %d (at most %d)", who, cc::basis(taps, dopp) + cl::max_target_members(*prm),
+                        cl::MAX_MEMBERS);
+    case 5: return fail(CRSDR_EINVAL, "%s: min_snr = %g (finite and greater than 0)", who, (double)d->min_snr);
+    case 6: return fail(CRSDR_EINVAL, "%s: (max_batch / frames) * nd * (taps + max_targets (2 wl + 1)) * nlags = %lld (at most 2^24)", who,
+                        lines * nd * (taps + cl::max_slots(*prm)) * nlags);
+    default: return fail(CRSDR_EINVAL, "%s: 2 * (max_batch / frames) * nrows * nd * nlags = %lld (at most 2^24: chi and the residual's)", who, 2 * lines * nrows * nd * nlags);
+    }
+}
+
+extern "C" int crsdr_caf_set_clean(crsdr_caf *q, const crsdr_caf_clean_desc *desc)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_set_clean: NULL caf");
+    const size_t lines = q->lines();
+    cl::Params prm{};
+    if (desc) {
+        { const int rc = caf_rules(q, kCafClean, false); if (rc) return rc; }         // (turning it off is never refused)
+        // (the canceller off: the limits that need its basis are checked with one member, and the call is refused for the state below)
+        const int rc_ = clean_args_ok("caf_set_clean", q->nd, q->nlags, (long long)lines, q->nrows, q->cn.on ? q->cn.taps : 1, q->cn.on ? q->cn.dopp : 0, desc, &prm);
+        if (rc_) return rc_;
+        { const int rc = caf_rules(q, kCafClean, true); if (rc) return rc; }
+    }
+    { const int rc = caf_clear(q, q->cl_, kCafRanClean); if (rc || !desc) return rc; }
+    const size_t rows = lines * (size_t)q->nrows, nd = (size_t)q->nd, R = (size_t)q->nlags, cells = nd * R, Kd = (size_t)q->cf.prm.max_det, T = (size_t)prm.max_targets;
+    crsdr_caf::Clean f;
+    f.prm = prm; f.n2max = cl::max_target_members(prm); f.nmax = cc::basis(q->cn.taps, q->cn.dopp) + f.n2max; f.slots = cl::slots_of(prm, q->nlags); f.on = true;
+    const size_t n2 = (size_t)f.n2max, nm = (size_t)f.nmax, sl = (size_t)f.slots, maps = lines * (size_t)(q->nrows + 1);
+    int r = CRSDR_OK;
+    if ((r = f.tab.alloc(lines)) || (r = f.G2.alloc(lines * nd * sl * R)) || (r = f.Y2.alloc(rows * nd * sl)) || (r = f.ph2.alloc(lines * n2 * nd)) ||
+        (r = f.A2.alloc(lines * n2 * nm)) || (r = f.C2.alloc(rows * n2)) || (r = f.Wj.alloc(rows * 2 * nm)) || (r = f.hj.alloc(rows * nm)) || (r = f.jstat.alloc(lines)) ||
+        (r = f.tgt.alloc(lines * T * 8)) || (r = f.ntgt.alloc(lines)) || (r = f.tcoef.alloc(rows * n2 * 2)) || (r = f.tinfo.alloc(rows * 2)) ||
+        (r = f.rchi.alloc(rows * cells)) || (r = f.rmap.alloc(lines * cells)) || (r = f.rdet.alloc(maps * Kd * 8)) || (r = f.rcount.alloc(maps)) ||
+        (r = f.rsnap.alloc(lines * Kd * (size_t)q->nrows * 2)))
+        return r;
+    q->cl_ = std::move(f);
+    return CRSDR_OK;
+}
+
+extern "C" int crsdr_caf_fetch_clean(crsdr_caf *q, float *tgt, int32_t *ntgt, float *tcoef, float *tinfo, float *rchi, float *rmap, float *rdet, int32_t *rcount,
+                                     float *rsnap)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_fetch_clean: NULL caf");
+    const crsdr_caf::Clean &c = q->cl_;
+    if (!c.on) return fail(CRSDR_ESTATE, "caf_fetch_clean: no cleaning set (crsdr_caf_set_clean)");
+    if (!(q->last.ran & kCafRanClean)) return fail(CRSDR_ESTATE, "caf_fetch_clean: nothing submitted since the cleaning was set");
+    const size_t lines = (size_t)q->last.nest, rows = lines * (size_t)q->nrows, cells = (size_t)q->nd * (size_t)q->nlags, maps = lines * (size_t)(q->nrows + 1);
+    const size_t Kd = (size_t)q->cf.prm.max_det;
+    return DevFetch(q->device, q->last.stream).copy(tgt, c.tgt.p, lines * (size_t)c.prm.max_targets * 8).copy(ntgt, c.ntgt.p, lines)
+        .copy(tcoef, c.tcoef.p, rows * (size_t)c.n2max * 2).copy(tinfo, c.tinfo.p, rows * 2).copy(rchi, c.rchi.p, rows * cells).copy(rmap, c.rmap.p, lines * cells)
+        .copy(rdet, c.rdet.p, maps * Kd * 8).copy(rcount, c.rcount.p, maps).copy(rsnap, c.rsnap.p, lines * Kd * (size_t)q->nrows * 2).wait();
+}
+
+extern "C" int crsdr_caf_clean_device_buffers(crsdr_caf *q, void **tgt, void **ntgt, void **tcoef, void **tinfo, void **rchi, void **rmap, void **rdet, void **rcount,
+                                              void **rsnap)
+{
+    if (!q) return fail(CRSDR_EINVAL, "caf_clean_device_buffers: NULL caf");
+    const crsdr_caf::Clean &c = q->cl_;
+    if (!c.on) return fail(CRSDR_ESTATE, "caf_clean_device_buffers: no cleaning set (crsdr_caf_set_clean)");
+    if (tgt) *tgt = c.tgt;
+    if (ntgt) *ntgt = c.ntgt;
+    if (tcoef) *tcoef = c.tcoef;
+    if (tinfo) *tinfo = c.tinfo;
+    if (rchi) *rchi = c.rchi;
+    if (rmap) *rmap = c.rmap;
+    if (rdet) *rdet = c.rdet;
+    if (rcount) *rcount = c.rcount;
+    if (rsnap) *rsnap = c.rsnap;
+    return CRSDR_OK;
+}
+
+// The per-op form: a one-line engine made for the call, on the current device -- the engine's stages, so the same kernels on the same
+// arguments.  Every check of the four descriptors comes before a device is touched.
+extern "C" int crsdr_ambiguity_clean(const crsdr_clean_out *out, const int8_t *matrix, int nrows, int blocksize, int seg, int nlags, int ref_row, int window, int guard,
+                                     int mem_kind, const crsdr_caf_cancel_desc *cancel, const crsdr_cfar_desc *cfar, const crsdr_cfar_est_desc *est,
+                                     const crsdr_caf_clean_desc *clean)
+{
+    if (!out || !matrix || !cancel || !cfar || !clean) return fail(CRSDR_EINVAL, "ambiguity_clean: need out, matrix, and the canceller's, the detector's and the cleaning's descriptors");
+    { const int rc_ = caf_args_ok("ambiguity_clean", nrows, blocksize, 1, 1, seg, nlags, ref_row, window, guard); if (rc_) return rc_; }
+    const int nd = blocksize / (2 * seg);
+    cfar::Params cp{};
+    cl::Params lp{};
+    { const int rc_ = cancel_args_ok("ambiguity_clean", nd, nlags, 1, cancel); if (rc_) return rc_; }
+    { const int rc_ = cfar_args_ok("ambiguity_clean", nd, cfar, &cp); if (rc_) return rc_; }
+    { const int rc_ = cfar_est_ok("ambiguity_clean", est, &cp); if (rc_) return rc_; }
+    { const int rc_ = clean_args_ok("ambiguity_clean", nd, nlags, 1, nrows, cancel->taps, cancel->dopp, clean, &lp); if (rc_) return rc_; }
+    if (mem_kind != CRSDR_MEM_HOST && mem_kind != CRSDR_MEM_DEVICE) return fail(CRSDR_EINVAL, "ambiguity_clean: mem_kind = %d", mem_kind);
+    const bool host = mem_kind == CRSDR_MEM_HOST;
+    if (!host) {
+        const void *p4[] = {matrix, out->map, out->peak, out->coef, out->cinfo, out->det, out->count, out->snap, out->tgt, out->ntgt, out->tcoef, out->tinfo, out->rmap,
+                            out->rdet, out->rcount, out->rsnap};
+        bool mis = (uintptr_t)out->chi % 8 != 0 || (uintptr_t)out->rchi % 8 != 0;
+        for (const void *p : p4) mis |= (uintptr_t)p % 4 != 0;
+        if (mis) return fail(CRSDR_EINVAL, "ambiguity_clean: device pointers 4-byte, chi and rchi 8-byte aligned");
+    }
+    { const int rc_ = require_device(); if (rc_) return rc_; }
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    const crsdr_caf_desc cd{nrows, blocksize, dev, 1, 1, seg, nlags, ref_row, window, guard};
+    crsdr_caf *q = nullptr;
+    int rc = crsdr_caf_create(&q, &cd);
+    if (rc) return rc;
+    DevBuf<int8_t> staged;
+    const size_t mb = (size_t)nrows * (size_t)blocksize;
+    if (!(rc = crsdr_caf_set_cancel(q, cancel)) && !(rc = crsdr_caf_set_cfar(q, cfar)) && !(rc = est ? crsdr_caf_set_cfar_estimator(q, est) : CRSDR_OK) &&
+        !(rc = crsdr_caf_set_clean(q, clean)) && !(rc = host ? staged.alloc(mb) : CRSDR_OK) &&
+        !(rc = host ? HIP_RC(hipMemcpy(staged.p, matrix, mb, hipMemcpyHostToDevice)) : CRSDR_OK) &&
+        !(rc = crsdr_caf_submit(q, host ? staged.p : matrix, mb, 0, 1, nullptr)) && !(rc = HIP_RC(hipStreamSynchronize(q->own.s)))) {
+        const size_t cells = (size_t)nd * (size_t)nlags, n1 = (size_t)cc::basis(cancel->taps, cancel->dopp), Kd = (size_t)cp.max_det, r = (size_t)nrows;
+        const crsdr_caf::Clean &c = q->cl_;
+        const struct { void *dst; const void *src; size_t bytes; } copies[] = {
+            {out->chi, q->chi.p, 8 * r * cells}, {out->map, q->map.p, 4 * cells}, {out->peak, q->peak.p, 4 * (r + 1) * 6}, {out->coef, q->cn.coef.p, 8 * r * n1},
+            {out->cinfo, q->cn.cinfo.p, 8 * r}, {out->det, q->cf.det.p, 4 * (r + 1) * Kd * 8}, {out->count, q->cf.count.p, 4 * (r + 1)}, {out->snap, q->cf.snap.p, 8 * Kd * r},
+            {out->tgt, c.tgt.p, 4 * (size_t)lp.max_targets * 8}, {out->ntgt, c.ntgt.p, 4}, {out->tcoef, c.tcoef.p, 8 * r * (size_t)c.n2max}, {out->tinfo, c.tinfo.p, 8 * r},
+            {out->rchi, c.rchi.p, 8 * r * cells}, {out->rmap, c.rmap.p, 4 * cells}, {out->rdet, c.rdet.p, 4 * (r + 1) * Kd * 8}, {out->rcount, c.rcount.p, 4 * (r + 1)},
+            {out->rsnap, c.rsnap.p, 8 * Kd * r}};
+        for (const auto &cp_ : copies)
+            if (cp_.dst && !rc) rc = HIP_RC(hipMemcpy(cp_.dst, cp_.src, cp_.bytes, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+    }
+    caf_free(q);
+    return rc;
 }

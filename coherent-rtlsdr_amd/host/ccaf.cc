@@ -227,6 +227,32 @@ int batch::fetch_cancel(bool want_coef)
     return rc;
 }
 
+int batch::set_clean(const crsdr_caf_clean_desc *desc)
+{
+    int rc = cf ? crsdr_caf_set_clean(cf, desc) : CRSDR_ESTATE;
+    if (!rc) {
+        ntargets = desc ? desc->max_targets : 0; nper = desc ? (2 * desc->wl + 1) * (2 * desc->wq + 1) : 0;
+        tgt.clear(); ntgt.clear(); tcoef.clear(); tinfo.clear(); rdet.clear(); rcount.clear();
+    }
+    if (rc && cf) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
+int batch::fetch_clean(bool want_tcoef)
+{
+    int nest = 0;
+    int rc = !cf || !ntargets ? CRSDR_ESTATE : crsdr_caf_last_submit(cf, &nest, nullptr);
+    if (!rc) {
+        const size_t maps = (size_t)nest * (rows + 1);
+        tgt.assign((size_t)nest * ntargets, det_t{}); ntgt.assign((size_t)nest, 0); tinfo.assign((size_t)nest * rows * 2, 0.f);
+        tcoef.assign(want_tcoef ? (size_t)nest * rows * ntargets * nper * 2 : 0, 0.f); rdet.assign(maps * kdet, det_t{}); rcount.assign(maps, 0);
+        rc = crsdr_caf_fetch_clean(cf, &tgt[0].lag, ntgt.data(), want_tcoef ? tcoef.data() : nullptr, tinfo.data(), nullptr, nullptr, &rdet[0].lag, rcount.data(), nullptr);
+    }
+    if (!rc) nlines = nest;
+    if (rc && cf && ntargets) std::fprintf(stderr, "ccaf::batch: %s\n", crsdr_last_error());
+    return rc;
+}
+
 int batch::fetch(bool want_chi, bool want_map)
 {
     int nest = 0;

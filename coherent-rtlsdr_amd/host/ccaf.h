@@ -50,7 +50,7 @@ class batch {
     crsdr_caf *cf = nullptr;
     int rows, bins, lags, kdet = 0, nbasis = 0, npts = 0;
     bool bearings = false, beam_lists = false, adapt = false;
-    int nb = 0, ntracks = 0, iwhat = 0;
+    int nb = 0, ntracks = 0, iwhat = 0, ntargets = 0, nper = 0;
 
 public:
     batch(int nrows, int blocksize, int max_batch, int seg, int nlags, int ref_row = 0, int window = CRSDR_WINDOW_RECT, int guard = 0, int frames = 1, int device = 0);
@@ -111,6 +111,14 @@ public:
     // waits, and fills imap and ibmap, those whose flag is on; CRSDR_ESTATE with integration off
     int fetch_integrate();
     int integrated() const { return iwhat; }
+    // the second cancellation stage behind every later submit's detector (crsdr_caf_set_clean; NULL: off): the strong detections of
+    // the array map's list join the canceller's basis, and the maps and the list are formed again on the residual.  Between submits,
+    // with the canceller and the detector on and the array map not integrated; while it is on set_cancel, set_cfar and
+    // set_cfar_estimator are refused.
+    int set_clean(const crsdr_caf_clean_desc *desc);
+    // waits, and fills tgt, ntgt, tinfo, rdet and rcount, and tcoef if asked for; CRSDR_ESTATE with the stage off
+    int fetch_clean(bool want_tcoef = false);
+    int max_targets() const { return ntargets; }
     int basis() const { return nbasis; }             // taps (2 dopp + 1), 0 with the canceller off
     int lines() const { return nlines; }
     int nrows() const { return rows; }
@@ -144,6 +152,15 @@ public:
     std::vector<float> ibmap;                        // [lines][nbeams][nd][nlags]: every beam's map, likewise
     std::vector<float> coef;                         // [lines][nrows][basis][2]: the canceller's filter of every row
     std::vector<float> cinfo;                        // [lines][nrows][2]: the share of the row's power that stays, and the status
+    std::vector<det_t> tgt;                          // [lines][max_targets]: the records the second stage picked, zeros behind the last
+    std::vector<int32_t> ntgt;                       // [lines]
+    std::vector<float> tcoef;                        // [lines][nrows][max_targets][(2 wq + 1)(2 wl + 1)][2]: the target members' filter of every row
+    std::vector<float> tinfo;                        // [lines][nrows][2]: the share that stays under the joint solve, and the status (0, 1, 2)
+    std::vector<det_t> rdet;                         // [lines][nrows + 1][max_det]: the residual's detections, laid out as det
+    std::vector<int32_t> rcount;                     // [lines][nrows + 1]
+    const det_t &picked(int e, int t) const { return tgt[(size_t)e * ntargets + t]; }
+    int residual_held(int e, int c) const { const int n = rcount[(size_t)e * (rows + 1) + c]; return n < kdet ? n : kdet; }
+    const det_t &residual_detection(int e, int c, int k) const { return rdet[((size_t)e * (rows + 1) + c) * kdet + k]; }
     float residual(int e, int c) const { return cinfo[2 * ((size_t)e * rows + c)]; }
     bool singular(int e, int c) const { return cinfo[2 * ((size_t)e * rows + c) + 1] != 0.f; }
     // of line e and entry c: the number of detections held (at most max_det), and detection k of them

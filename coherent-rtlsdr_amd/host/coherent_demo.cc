@@ -72,7 +72,8 @@ int main(int argc, char **argv)
     crsdr_cfar_desc cfar = {1, 1, 3, 4, 0.f, 1, 16};
     bool cfar_est_on = false, cfar_axis_on = false;
     crsdr_cfar_est_desc cfar_est = {CRSDR_CFAR_CA, 0, 0};
-    bool cancel_on = false, bearing_on = false, beams_on = false;
+    bool cancel_on = false, bearing_on = false, beams_on = false, clean_on = false;
+    crsdr_caf_clean_desc clean = {1, 100.f, 1, 1};
     int beams_mx = 0, beams_my = 0, beams_nx = 0, beams_ny = 0;
     bool adapt_on = false, adapt_region = false;
     crsdr_caf_beam_adapt_desc adapt = {0, 0, 0, 0, 1e-2f, 0u};
@@ -191,6 +192,16 @@ int main(int argc, char **argv)
             const int n = std::sscanf(argv[++i], "%d:%d", &cancel.taps, &cancel.dopp);
             cancel_on = true;
             if (n < 1) cancel.taps = -1;                                                     // (refused below with the rest)
+        }
+        // with --caf, --cancel and --cfar: the second cancellation stage (crsdr_caf_set_clean): up to T strong detections of the array map's
+        // list, none under MIN_SNR_DB (20 by default), each a cluster of half-widths WL lags and WQ half bins (1:1), join the canceller's
+        // basis; per line the picks and the residual's list are printed
+        else if (a == "--clean" && i + 1 < argc) {
+            double db = 20.0;
+            const int n = std::sscanf(argv[++i], "%d:%lf:%d:%d", &clean.max_targets, &db, &clean.wl, &clean.wq);
+            clean_on = true;
+            clean.min_snr = (float)std::pow(10.0, db / 10.0);
+            if (n < 1 || n == 3) clean.max_targets = -1;                                     // (refused below with the rest)
         }
         // with --caf and --cfar: a direction per detection of the array map (crsdr_caf_set_bearing), the signal rows as an MX x MY array on
         // an NC x NC grid (100); --adaptive LOADING whitens with the training cells' covariance, --bearing-levels L refines off the grid.
@@ -661,6 +672,7 @@ int main(int argc, char **argv)
             if (cfar_on && caf->set_cfar(&cfar)) { std::printf("cfar: --cfar SNR_DB[:GD:GR:TD:TR] [--max-det K] refused\nDEMO FAILED\n"); return 1; }
             if (cfar_est_on && caf->set_cfar_estimator(&cfar_est)) { std::printf("cfar: --cfar-est go|so|os[:RANK] [--cfar-axis lag|doppler] refused\nDEMO FAILED\n"); return 1; }
             if (cancel_on && caf->set_cancel(&cancel)) { std::printf("cancel: --cancel K[:P] refused\nDEMO FAILED\n"); return 1; }
+            if (clean_on && caf->set_clean(&clean)) { std::printf("clean: --clean T[:MIN_SNR_DB[:WL:WQ]] refused (it needs --cancel and --cfar): %s\nDEMO FAILED\n", crsdr_last_error()); return 1; }
             if (bearing_on && !cfar_on) { std::printf("bearing: --bearing needs --cfar: there are no detections to take a bearing of\nDEMO FAILED\n"); return 1; }
             // (the order of the setters is detector / beams, integration, bearings, tracker: with --integrate the bearings wait for it)
             auto set_bearing = [&]() {
@@ -702,7 +714,7 @@ int main(int argc, char **argv)
             ok = caf->submit(coherent.engine_plan()) == CRSDR_OK && caf->fetch() == CRSDR_OK && (!cfar_on || caf->fetch_cfar() == CRSDR_OK) &&
                  (!cancel_on || caf->fetch_cancel(false) == CRSDR_OK) && (!bearing_on || caf->fetch_bearing() == CRSDR_OK) &&
                  (!beams_on || caf->fetch_beams() == CRSDR_OK) && (!adapt_on || caf->fetch_beam_adapt() == CRSDR_OK) && (!track_on || caf->fetch_track() == CRSDR_OK) &&
-                 (!integrate_on || caf->fetch_integrate() == CRSDR_OK);
+                 (!integrate_on || caf->fetch_integrate() == CRSDR_OK) && (!clean_on || caf->fetch_clean() == CRSDR_OK);
             if (!ok || !report) return;
             if (integrate_on) std::printf("integrate: batch %d: %d lines behind a window of %g%s\n", b, caf->lines(), integrate_window, cfar_on ? ": the detections are the integrated map's" : "");
             for (int e = 0; cancel_on && e < caf->lines(); ++e) {
@@ -719,6 +731,20 @@ int main(int argc, char **argv)
                     std::printf("cfar: batch %d line %d det %d of %d: lag %d%+.3f doppler %d%+.3f snr %.2f dB\n", b, e, k, (int)caf->count[(size_t)e * (caf->nrows() + 1) + caf->nrows()],
                                 (int)d.lag, (double)d.dlag, (int)d.doppler, (double)d.ddop, d.snr_db());
                 }
+            for (int e = 0; clean_on && e < caf->lines(); ++e) {
+                const int rows = caf->nrows(), st = (int)caf->tinfo[2 * ((size_t)e * rows + (caf_ref == 0 ? 1 : 0)) + 1];
+                for (int t = 0; t < caf->ntgt[(size_t)e]; ++t) {
+                    const ccaf::det_t &d = caf->picked(e, t);
+                    std::printf("clean: batch %d line %d pick %d of %d: lag %d doppler %.3f snr %.2f dB\n", b, e, t, (int)caf->ntgt[(size_t)e], (int)d.lag,
+                                (double)d.doppler + (double)d.ddop, d.snr_db());
+                }
+                std::printf("clean: batch %d line %d: %d picks status %d residual list %d\n", b, e, (int)caf->ntgt[(size_t)e], st, (int)caf->rcount[(size_t)e * (rows + 1) + rows]);
+                for (int k = 0; k < caf->residual_held(e, rows); ++k) {
+                    const ccaf::det_t &d = caf->residual_detection(e, rows, k);
+                    std::printf("clean: batch %d line %d residual det %d: lag %d%+.3f doppler %d%+.3f snr %.2f dB\n", b, e, k, (int)d.lag, (double)d.dlag, (int)d.doppler,
+                                (double)d.ddop, d.snr_db());
+                }
+            }
             for (int e = 0; bearing_on && e < caf->lines(); ++e)
                 for (int k = 0; k < caf->held(e, caf->nrows()); ++k) {
                     const ccaf::dir_t &d = caf->bearing(e, k);

@@ -1269,6 +1269,97 @@ int crsdr_caf_cancel_device_buffers(crsdr_caf *caf, void **coef, void **cinfo);
 int crsdr_ambiguity_cancel(float *chi, float *map, float *peak, const int8_t *matrix, int nrows, int blocksize, int seg, int nlags, int ref_row,
                            int window, int guard, int mem_kind, int taps, int dopp, float *coef, float *cinfo);
 
+/* Cleaning.  An echo has the same floor about 1 / (nd Ls) below its own peak in every cell, and the canceller removes that floor for
+ * delays 0 .. K - 1 at |p| <= P alone.  A strong mover -- an aircraft close to the receiver -- lays it over the whole map, at Doppler
+ * bins the canceller never touches, and every weaker target under it is lost to the detector whichever estimator it runs.  The second
+ * stage takes the strong detections of the first pass, adds the reference delayed and Doppler-shifted to each of them to the
+ * canceller's basis, solves jointly, and forms the maps and the lists again on the residual.  It is off until crsdr_caf_set_clean and
+ * needs the canceller and the detector on.  Off, a submit is the same launches and the same bits; on, every other output -- chi, map,
+ * peak, det, count, snap, coef, cinfo, and what bearings, beams, integration and tracker publish -- keeps the bits it has with it off:
+ * the residual goes to buffers of its own, and nothing else reads them.
+ *
+ * Parameters.  max_targets = T, min_snr (the ratio a detection's snr is), wl and wq: the half-widths of a target's cluster over lag,
+ * and over Doppler in HALF bins.
+ * Picks, per line, from the array map's published list (entry nrows of det and count), decided in fp64 on the published fp32 figures
+ * and so exact.  The first min(count, K_det) records in their order; a record has f = (double)doppler + (double)ddop and l = lag.  The
+ * circular distance of two Dopplers is g = |f - f'|, or nd - g when g > nd / 2.  A record is skipped if snr < min_snr; if it touches
+ * the clutter basis, l - wl <= K - 1 and the circular distance of f to 0 < P + 1 + wq / 2; or if it touches an accepted pick,
+ * |l - l'| <= 2 wl and the circular distance of f to f' < wq + 1.  Otherwise it is accepted; the walk stops at T accepted.
+ * Members.  The canceller's n1 = K (2 P + 1) members first, their indices unchanged.  Then per pick in pick order, q = -wq .. wq outer,
+ * j = -wl .. wl inner, member (m, g) = (l + j, f + q / 2), in segment k
+ *     phi_g[k] X_r[j Ls + n - m],   phi_g[k] = exp(2 pi i g k / nd), evaluated in fp64 as sincospi(2 * ((g * k) / nd))
+ * A lag outside 0 .. R - 1 is left out, not wrapped.  n <= 64 members.
+ * Sums.  G[k][m][tau] as above, for every distinct member lag m and all tau < R, and y_c[k][m] at those lags: exact in int32.
+ * Normal equations of the line, member i = (m_i, g_i):
+ *     A_ij = sum_k phi_(g_j - g_i)[k] G[k][m_j][m_i]        c_i = sum_k conj(phi_(g_i)[k]) y_c[k][m_i]
+ * The canceller's block of A has the bits of the first stage's; the cross block and the target block are new.
+ * Solve.  Cholesky by columns in member order with the pivot floor above, 2^-40 A_(0,0),(0,0).  The canceller's members come first,
+ * so the leading block's factor is the first stage's bit for bit, and a line WITHOUT PICKS has rchi == chi, rmap == map,
+ * rdet == det, rcount == count and rsnap == snap, byte for byte.
+ *     Status 1: a pivot of the canceller's block at or under the floor (the first stage is singular).  h = 0; rchi has chi's bits.
+ *     Status 2: a target column's pivot at or under the floor.  The target coefficients are 0, the canceller's are the first
+ *               stage's, and rchi has chi's bits.
+ * Residual.
+ *     y''_c[k][tau] = y_c[k][tau] - sum_i h_c,i phi_(g_i)[k] G[k][m_i][tau]
+ * in fp64 from the integers with ONE rounding to fp32, the canceller's members in the first stage's order and the target members
+ * behind them; then the Doppler stage, the array map and the detector (under the descriptor's estimator) as they are.  Row r is left
+ * alone.
+ * Outputs per line:
+ *     tgt    [nest][T][8]                               the picked records, copied bit for bit; unused slots zero
+ *     ntgt   [nest] int32
+ *     tcoef  [nest][nrows][T][(2 wq + 1)(2 wl + 1)][2]  the target members' h per row, index (q + wq)(2 wl + 1) + (j + wl), each part
+ *                                                       rounded once: a target's complex amplitude across the rows.  Left-out
+ *                                                       members, unused picks and row r are zero
+ *     tinfo  [nest][nrows][2]                           the share of the row's power that stays under the joint solve (as cinfo has
+ *                                                       it, over all members), and the status (0, 1 or 2).  Row r: (1, 0)
+ *     rchi, rmap, rdet, rcount, rsnap                   laid out exactly as chi, map, det, count and snap
+ * Bits.  Nothing depends on the order in which workgroups run, there are no float atomics, a line has the same bits wherever it sits
+ * in a batch, and crsdr_ambiguity_clean runs the same kernels on the same arguments.
+ * Limits, all CRSDR_EINVAL and all checked before a device is touched, by one function for the engine and the per-op call:
+ * 1 <= T <= 8; 0 <= wl <= 2; 0 <= wq <= 2; n1 + T (2 wl + 1)(2 wq + 1) <= 64; min_snr finite and > 0;
+ * (max_batch / frames) * nd * (K + T (2 wl + 1)) * R <= 2^24; 2 * (max_batch / frames) * nrows * nd * R <= 2^24 (chi and rchi).
+ * State.  CRSDR_ESTATE: crsdr_caf_set_clean without the canceller or the detector, or with CRSDR_INTEGRATE_ARRAY on (the picks would
+ * come from another line's energy); while it is on, crsdr_caf_set_cancel, crsdr_caf_set_cfar, crsdr_caf_set_cfar_estimator and
+ * crsdr_caf_set_integrate with CRSDR_INTEGRATE_ARRAY (turn it off first).
+ * Launches.  NINE more per submit (crsdr_caf_last_submit), whatever the number of blocks and however many picks a line has. */
+typedef struct crsdr_caf_clean_desc {
+    int32_t max_targets;      /* T: picks per line, 1..8 */
+    float min_snr;            /* a record below it is not picked */
+    int32_t wl;               /* lags l - wl .. l + wl of a pick */
+    int32_t wq;               /* Dopplers f - wq / 2 .. f + wq / 2 of a pick, in steps of half a bin */
+} crsdr_caf_clean_desc;
+
+/* Sets the cleaning (NULL: off).  Between submits only: it waits for the last one and allocates here, never in a submit; what a
+ * fetch_clean would have returned is gone. */
+int crsdr_caf_set_clean(crsdr_caf *caf, const crsdr_caf_clean_desc *desc);
+
+/* Waits for the last submit and copies out what is asked for (any pointer may be NULL), laid out as above.  CRSDR_ESTATE with the
+ * cleaning off, or before the first submit since it was set. */
+int crsdr_caf_fetch_clean(crsdr_caf *caf, float *tgt, int32_t *ntgt, float *tcoef, float *tinfo, float *rchi, float *rmap, float *rdet, int32_t *rcount,
+                          float *rsnap);
+
+/* Device addresses of the same ([max_batch / frames] lines each).  They change with every crsdr_caf_set_clean.  CRSDR_ESTATE with
+ * the cleaning off. */
+int crsdr_caf_clean_device_buffers(crsdr_caf *caf, void **tgt, void **ntgt, void **tcoef, void **tinfo, void **rchi, void **rmap, void **rdet, void **rcount,
+                                   void **rsnap);
+
+/* The per-op form on one packet's matrix (frames = 1): canceller, detector (est NULL: cell averaging) and cleaning on one line, every
+ * output of the three laid out as above for nest = 1; any pointer of `out` may be NULL.  It makes a one-line engine for the call on
+ * the current device and runs its submit: the same kernels on the same arguments, bit for bit.  mem_kind: CRSDR_MEM_HOST (copied) or
+ * CRSDR_MEM_DEVICE (every pointer on the device, 4-byte aligned, chi and rchi 8-byte). */
+typedef struct crsdr_clean_out {
+    float *chi, *map, *peak, *coef, *cinfo, *det;
+    int32_t *count;
+    float *snap, *tgt;
+    int32_t *ntgt;
+    float *tcoef, *tinfo, *rchi, *rmap, *rdet;
+    int32_t *rcount;
+    float *rsnap;
+} crsdr_clean_out;
+int crsdr_ambiguity_clean(const crsdr_clean_out *out, const int8_t *matrix, int nrows, int blocksize, int seg, int nlags, int ref_row, int window, int guard,
+                          int mem_kind, const crsdr_caf_cancel_desc *cancel, const crsdr_cfar_desc *cfar, const crsdr_cfar_est_desc *est,
+                          const crsdr_caf_clean_desc *clean);
+
 /* Bearings.  A detection of the array map says at which lag and Doppler a target is; snap holds its complex value across the rows.
  * This stage, behind the detector and on the device, turns every such detection into a direction: a line's result is a list of
  * (lag, Doppler, bearing) in a few hundred bytes.  It is off until crsdr_caf_set_bearing; off, a submit is the same launches and the

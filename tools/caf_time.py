@@ -65,7 +65,11 @@ with --parent-lib LIB beside it: "caf" -- the integration-off submit -- of anoth
 worker process, in the same alternation ("caf parent", and "caf self" from a worker of this build).
 
 Every figure is the mean of --reps back-to-back rounds closed by one wait; --runs rounds alternate all variants in one session, medians
-and ranges are reported.  --json FILE keeps the record."""
+and ranges are reported.  --json FILE keeps the record.
+with --clean T, and nothing else: a 22-row engine with the canceller (4:1) and the detector, the same object in turn with the second
+cancellation stage off, on without picks and on with T picks in every line (crsdr_caf_set_clean; T movers are put into the rows):
+  clean off / +clean, no picks / +clean, T picks, and the share of the second pass (rows, map, detector again) in what the stage adds
+"""
 import argparse, importlib, json, os, statistics, subprocess, sys, time
 import numpy as np
 
@@ -116,8 +120,74 @@ def worker(nrows, reps):
         print(_mean(run, lambda: None, reps), flush=True)
 
 
+def _mover_blocks(T, nrows, picks, rng):
+    """_blocks with `picks` movers in every row but the first: the reference delayed by 8 + 6 t samples and rotated by 20.3 + 17 t bins a
+    line of FRAMES packets, the phase constant within a segment, at a = 0.5 / (1 + t / 4); complex samples this time"""
+    L, J = B // 2, B // 2 // SEG
+    rows = np.empty((T, nrows, B), dtype=np.int8)
+    cn = lambda *sh: (rng.standard_normal(sh) + 1j * rng.standard_normal(sh)).astype(np.complex64)
+    for t0 in range(0, T, FRAMES):
+        ref = 25 * cn(FRAMES, L)
+        for f in range(FRAMES):
+            x = 0.7 * ref[f][None, :] + 6 * cn(nrows, L)
+            k = f * J + np.arange(L) // SEG
+            for t in range(picks):
+                lag, bins = 8 + 6 * t, 20.3 + 17 * t
+                d = np.concatenate([np.zeros(lag, dtype=np.complex64), ref[f][:L - lag]])
+                x[1:] += (0.5 / (1 + t / 4)) * (d * np.exp(2j * np.pi * bins * k / (FRAMES * J)))[None, :]
+            x[0] = ref[f]
+            rows[t0 + f, :, 0::2] = np.clip(np.rint(x.real), -128, 127)
+            rows[t0 + f, :, 1::2] = np.clip(np.rint(x.imag), -128, 127)
+    return rows
+
+
+def clean_timing(a):
+    """--clean T: the submit with canceller (4:1) and detector against the same object's submit with the second stage on, at 22 rows:
+    no picks (min_snr out of reach: the second pass alone -- the rows again, their map, the detector), and every line at T picks
+    (the sums, the joint solve and the target members' terms on top).  Medians of --runs alternated rounds of --reps submits."""
+    sys.path.insert(0, ROOT)
+    import torch
+    b = importlib.import_module("coherent-rtlsdr_amd.binding")
+    nrows, (T, lags) = 22, SHAPES[22]
+    rng = np.random.default_rng(1)
+    d_in = torch.from_numpy(_mover_blocks(T, nrows, a.clean, rng).reshape(T, -1)).to(torch.device("cuda", 0))
+    cf = b.Caf(nrows, B, SEG, lags, 0, b.WINDOW_HANN, GUARD, max_batch=T, frames=FRAMES)
+    cf.set_cancel(4, 1)
+    cf.set_cfar(b.cfar_desc(alpha=b.cfar_alpha(1e-6, 90), gd=1, gr=1, td=3, tr=4, min_train=20, max_det=16))
+    variants = {"clean off": None, "+clean, no picks": b.CleanDesc(a.clean, 1e30, 1, 1), f"+clean, {a.clean} picks": b.CleanDesc(a.clean, 30.0, 1, 1)}
+
+    def run(i):
+        cf.submit(d_in.data_ptr(), nrows * B, 0, T)
+        cf.fetch(chi=False, map=False)
+
+    ms, info = {k: [] for k in variants}, {}
+    for r in range(a.runs + 1):
+        for name, desc in variants.items():
+            cf.set_clean(desc)
+            run(0)
+            if desc is not None and r == 0:
+                c = cf.fetch_clean(rchi=False, rmap=False)
+                info[name] = {"launches": cf.last_launches(), "picks": c["ntgt"].tolist(), "status": sorted(set(c["tinfo"][:, 1:, 1].ravel().tolist())),
+                              "rcount": c["rcount"][:, nrows].tolist()}
+            if r:
+                ms[name].append(1e3 * _mean(run, lambda: None, a.reps))
+    cf.set_clean(None)
+    cf.close()
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    off = med["clean off"]
+    out = {"rows": nrows, "lines": T // FRAMES, "nd": FRAMES * B // (2 * SEG), "lags": lags, "ms": {k: {"median": med[k], "min": min(v), "max": max(v)} for k, v in ms.items()}, "info": info}
+    for k, v in ms.items():
+        print(f"  {k:22s} {med[k]:8.4f} ms ({min(v):.4f} ... {max(v):.4f})  {med[k] - off:+.4f} ms  {info.get(k, '')}")
+    names = list(variants)
+    second, full = med[names[1]] - off, med[names[2]] - off
+    print(f"  the second pass alone {second:.4f} ms = {100 * second / max(full, 1e-9):.0f} % of the {full:.4f} ms the stage adds at {a.clean} picks a line")
+    if a.json:
+        json.dump(out, open(a.json, "w"), indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--clean", type=int, default=0, metavar="T", help="the second cancellation stage alone: off, on without picks, on with T picks a line (22 rows)")
     ap.add_argument("--integrate", action="store_true", help="add the variants of the integration across lines (with --beams: the beam maps' too)")
     ap.add_argument("--parent-lib", help="with --integrate: the plain submit of another build, in a worker process")
     ap.add_argument("--worker", type=int, metavar="ROWS", help=argparse.SUPPRESS)
@@ -137,6 +207,8 @@ def main():
     a.cfar = a.cfar or a.bearing or a.estimator
     if a.worker:
         return worker(a.worker, a.reps)
+    if a.clean:
+        return clean_timing(a)
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import torch
